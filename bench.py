@@ -10,13 +10,17 @@ resident in HBM (interleaved int32, the layout FlacSampleWriter::write receives)
 de-interleave -> fixed/LPC analysis -> channel-assignment decision -> residuals -> frame
 assembly (headers, Rice bit-packing, CRC-8/16) -> finished FLAC frame bytes in HBM.
 Stream bookkeeping that the reference keeps per stream on the host (MD5 of the PCM,
-metadata rewrite) is outside the step; the `end_to_end` block of the output line measures the
+metadata rewrite) is outside the step; the `end_to_end` block of a --full run measures the
 whole host PCM -> .flac bytes path (PCIe, MD5, container included) separately.
 
-Usage:  python bench.py --gpus N --steps K --warmup W [--config {2,3,4,5}]
+Usage:  python bench.py --gpus N --steps K --warmup W [--config {2,3,4,5}] [--full] [--dump-outputs DIR]
   N > 1 without WORLD_SIZE in the environment: this process starts N ranks of itself (one per
   GPU, before it touches any GPU) and relays rank 0's line; under torchrun the ranks are taken
   from the environment and --gpus must equal WORLD_SIZE.
+  A plain run sets up, warms up, times K steps and prints the headline figure; --full adds
+  everything else the bench measures and checks (oracle parity, sustained loop, variants, kernel
+  times and roofline, CPU baseline, end-to-end legs, other configurations) and the detail file.
+  --dump-outputs DIR writes the frames of the last timed step as DIR/*.npy (dump_outputs).
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -651,6 +655,10 @@ class Workload:
                 self.step()
             torch.cuda.synchronize()
             steps += 8
+        while self.n % len(self.ans):   # whole rotations: every run's timed steps then start at context 0, and its last
+            self.step()                 # step reads the same input buffer whatever the clock (--dump-outputs)
+            steps += 1
+        torch.cuda.synchronize()
         return steps
 
     def timed(self, k, dist=None):
@@ -1160,10 +1168,71 @@ def write_detail(out, path):
     return None
 
 
+DUMP_LIMIT = 64 << 20     # bytes --dump-outputs may write in all
+DUMP_SEED = 8192
+
+
+def max_frame_bytes(cfg):
+    """An upper bound of one frame's length: every subframe VERBATIM at bps + 1 bits (a side channel), plus headers and CRC."""
+    return (cfg["ch"] * BLOCK * (cfg["bps"] + 1) + 7) // 8 + 32 * cfg["ch"] + 32
+
+
+def join_shards(parts):
+    """(bytes, offsets) of several shards' consecutive frame ranges -> one run of frames with offsets into the whole."""
+    chunks, off = [], [0]
+    for d, o in parts:
+        base = off[-1]
+        off += [base + v for v in o[1:]]
+        chunks.append(d[: o[-1]])
+    return b"".join(chunks), off
+
+
+def dump_outputs(path, data, off, frame_bound):
+    """--dump-outputs: what the timed path's last step produced -- its finished FLAC frames and their offsets, the arrays a
+    caller of flacgpu_encode_device receives -- for comparing two builds output for output.  frame_offsets.npy (float64,
+    every frame), frame_index.npy (float64: the frames whose bytes follow) and frame_bytes.npy (float32: those frames' bytes,
+    in order).  Every frame while the bytes fit in DUMP_LIMIT; otherwise a fixed seeded sample of frames, as many as
+    `frame_bound` (an upper bound of one frame's length) lets fit, so that which frames are written depends on the
+    arguments alone."""
+    os.makedirs(path, exist_ok=True)
+    n = len(off) - 1
+    offs = np.asarray(off, dtype=np.int64)
+    budget = (DUMP_LIMIT - 16 * (n + 1) - 4096) // 4        # float32 bytes left beside the offsets and the index
+    if 4 * offs[-1] <= budget:
+        pick, body = np.arange(n), np.frombuffer(data, dtype=np.uint8, count=int(offs[-1]))
+    else:
+        k = max(1, min(n, budget // frame_bound))
+        pick = np.sort(np.random.Generator(np.random.PCG64(DUMP_SEED)).choice(n, k, replace=False))
+        buf = np.frombuffer(data, dtype=np.uint8)
+        body = np.concatenate([buf[offs[f]:offs[f + 1]] for f in pick])
+    assert body.size <= budget, "a frame longer than its bound"
+    np.save(os.path.join(path, "frame_offsets.npy"), offs.astype(np.float64))
+    np.save(os.path.join(path, "frame_index.npy"), pick.astype(np.float64))
+    np.save(os.path.join(path, "frame_bytes.npy"), body.astype(np.float32))
+
+
 def metric_text(cfg, bit_exact):
     what = {2: "level 5 (fixed predictors only), 48kHz/16-bit stereo", 3: "level 8, 48kHz/24-bit stereo",
             4: "level 8, 192kHz/24-bit 8-channel", 5: "level 8 exhaustive (LPC order 32), 96kHz/24-bit stereo"}[cfg]
     return f"Msamples/s encode at {what}" + ("; bit-exact vs reference" if bit_exact else "; NOT bit-exact (experiment)")
+
+
+def emit_stream(args, cfg, an, F, whole, dist, rank):
+    """--scaling strong --emit-flac: the stream itself -- frames of `an`'s last batch gathered to rank 0, metadata from the
+    gathered sizes -- written to the path given."""
+    from flac_codec_amd.encode import Options
+    from flac_codec_amd.parallel import finish_sharded_stream
+
+    data, off = an.fetch_frames(F)
+    o = Options.best() if cfg["lpc"] >= 12 else Options.default()
+    o = o.max_lpc_order(cfg["lpc"] or None).max_partition_order(cfg["po"])
+    flac = finish_sharded_stream(bytes(data[: off[F]]), [off[i + 1] - off[i] for i in range(F)], whole, o, cfg["rate"],
+                                 cfg["bps"], cfg["ch"], dist)
+    if rank != 0:
+        return None
+    with open(args.emit_flac, "wb") as fh:
+        fh.write(flac)
+    return {"path": args.emit_flac, "bytes": len(flac)}
 
 
 def in_process(args):
@@ -1211,6 +1280,9 @@ def in_process(args):
             step()
         md.wait()
         pre += 8
+    while n[0] % ctxs:   # whole rotations, as Workload.prewarm
+        step()
+        pre += 1
     for _ in range(args.warmup):
         step()
     md.wait()
@@ -1221,6 +1293,27 @@ def in_process(args):
     md.wait()
     sync()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, *join_shards([md.fetch_last(k, F) for k in range(N)]), max_frame_bytes(cfg))
+    samples_per_step = N * F * BLOCK * C
+    ms = elapsed / args.steps * 1e3
+    out = {
+        "metric": metric_text(args.config, True), "value": round(samples_per_step * args.steps / elapsed / 1e6, 2),
+        "unit": "Msamples/s", "n_gpus": N, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 4),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "i32/i64 (+f64 LPC analysis)",
+        "data": "synthetic",
+        "config": {"workload": f"config {args.config}: {cfg['text']}; {F} frames per GPU per step, PCM resident in HBM, "
+                               f"ONE process driving {N} device shard(s) through flacgpu_multi_* ({ctxs} contexts each)",
+                   "baseline_config": args.config, "level": cfg["level"], "frames_per_gpu": F, "frames_per_step": N * F,
+                   "parallelism": f"frame ranges x{N}, in-process", "contexts": ctxs, "devices": devices,
+                   "prewarm": f"{pre} untimed steps"},
+        "roofline": None, "cpu_baseline": None, "build_id": running_build_id(),
+        "hbm_bound_fraction": round((8.0 * samples_per_step / N) / (ms * 1e-3) / 8e12, 4),
+    }
+    if not args.full:
+        md.close()
+        print(final_line(out, write_detail(out, args.detail) if args.detail else None), flush=True)
+        return
     per_shard, merged = md.counters()
     # parity: every shard's last batch -- distinct frames byte for byte against the oracle
     oopts = orc_options_for(BLOCK, cfg["po"], cfg["lpc"], True, True)
@@ -1280,27 +1373,15 @@ def in_process(args):
         traffic, traffic_src, valu, stale = profile_figures(args.config, dom, kernels[dom]["ms"], args.signal)
     roofline = roofline_of(kernels, dom, alg, traffic, traffic_src, valu, stale)
     w.close()
-    samples_per_step = N * F * BLOCK * C
-    ms = elapsed / args.steps * 1e3
-    out = {
-        "metric": metric_text(args.config, True), "value": round(samples_per_step * args.steps / elapsed / 1e6, 2),
-        "unit": "Msamples/s", "n_gpus": N, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 4),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "i32/i64 (+f64 LPC analysis)",
-        "data": "synthetic",
-        "config": {"workload": f"config {args.config}: {cfg['text']}; {F} frames per GPU per step, PCM resident in HBM, "
-                               f"ONE process driving {N} device shard(s) through flacgpu_multi_* ({ctxs} contexts each)",
-                   "baseline_config": args.config, "level": cfg["level"], "frames_per_gpu": F, "frames_per_step": N * F,
-                   "parallelism": f"frame ranges x{N}, in-process", "contexts": ctxs, "devices": devices,
-                   "prewarm": f"{pre} untimed steps"},
-        "roofline": roofline, "cpu_baseline": None, "kernels": kernels, "build_id": running_build_id(),
-        "hbm_bound_fraction": round((8.0 * samples_per_step / N) / (ms * 1e-3) / 8e12, 4),
+    out.update({
+        "roofline": roofline, "kernels": kernels,
         "parity": {"frames_byte_identical_to_oracle_per_rank": identical // N, "frames_checked_per_rank": identical // N,
                    "ranks_checked": N},
         "shard_counters": {"total_frames": merged[0], "total_bytes": merged[1], "min_frame": merged[2],
                            "max_frame": merged[3], "frames_per_rank": [c[0] for c in per_shard], "ranks_seen": N,
                            "backend": "in-process (flacgpu_merge_counters)"},
         "host_to_host": host_leg,
-    }
+    })
     print(final_line(out, write_detail(out, args.detail)), flush=True)
 
 
@@ -1350,7 +1431,19 @@ def main():
     ap.add_argument("--in-process", action="store_true",
                     help="ONE process drives all --gpus devices through the C ABI's flacgpu_multi_* (no torch.distributed); "
                          "default: one process per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="everything the bench measures and checks beside the headline figure: parity of every context's "
+                         "batch with the oracle and the device round trip, the sustained loop with the GPU clock, the A/B "
+                         "variants, kernel times and the roofline, the MFMA experiment, the CPU baseline, the end-to-end "
+                         "legs, the other configurations, the batch sweep, the high-order input (the --no-* options narrow "
+                         "it), and the full record in the detail file.  Without it a run sets up, warms up, times --steps "
+                         "steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one produced (its frames' offsets and bytes, a "
+                         "fixed seeded sample of frames where all would exceed 64 MB) as DIR/*.npy (dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.in_process:
         return in_process(args)
@@ -1389,7 +1482,7 @@ def main():
         print(json.dumps({f"config{c}": batch_sweep(torch, c, args, local_rank) for c in (3, 4)}))
         return
     cfg = CONFIGS[args.config]
-    C, BPS, RATE, MAX_LPC = cfg["ch"], cfg["bps"], cfg["rate"], cfg["lpc"]
+    C, BPS, MAX_LPC = cfg["ch"], cfg["bps"], cfg["lpc"]
     strong = args.scaling == "strong"
     whole = None
     if strong:
@@ -1418,6 +1511,55 @@ def main():
     samples_per_step = total_frames * BLOCK * C
     value = samples_per_step * args.steps / elapsed / 1e6
     ms_per_step = elapsed / args.steps * 1e3
+    last = w.ans[(w.n - 1) % len(w.ans)]     # the context that ran the last timed step: its batch is still in HBM
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *last.fetch_frames(F), max_frame_bytes(cfg))
+
+    def headline(bit_exact):
+        return {
+            "metric": metric_text(args.config, bit_exact),
+            "value": round(value, 2),
+            "unit": "Msamples/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(ms_per_step, 4),
+            "higher_is_better": True,
+            "scaling": args.scaling,
+            "vs_baseline": None,
+            "dtype": "i32/i64 (+f64 LPC analysis)",
+            "data": "synthetic",
+            "config": {"signal": SIGNAL_TEXT[args.signal] if args.signal != "hi" else
+                       SIGNAL_TEXT["hi"] % (2 * HI_SECTIONS.get(args.config, 6)),
+                       "workload": f"config {args.config}: {cfg['text']}; "
+                                   + (f"ONE stream of {total_frames} frames per step cut into contiguous frame ranges over "
+                                      f"{world} rank(s)" if strong else f"{F} frames per GPU per step")
+                                   + f", PCM resident in HBM, frame bytes produced in HBM; consecutive batches rotate "
+                                     f"through {len(w.ans)} encoder context(s) on separate HIP streams, each reading its "
+                                     f"own input buffer",
+                       "baseline_config": args.config, "level": cfg["level"],
+                       "frames_per_gpu": F, "frames_per_step": total_frames, "parallelism": f"frame ranges x{world}",
+                       "contexts": len(w.ans), "distinct_input_buffers": len(w.ans) if not strong else 1,
+                       "prewarm": f"{prewarm_steps} untimed steps ({args.prewarm_ms:.0f} ms) before the warm-up"},
+        }
+
+    if not args.full:
+        # a plain run: the headline figure alone (what else the bench measures and checks runs under --full)
+        emitted = emit_stream(args, cfg, last, F, whole, dist, rank) if strong and args.emit_flac else None
+        out = None
+        if rank == 0:
+            out = headline(not args.experiment)
+            out.update({"roofline": None, "cpu_baseline": None, "build_id": running_build_id(),
+                        "hbm_bound_fraction": round((8.0 * samples_per_step / world) / (ms_per_step * 1e-3) / 8e12, 4),
+                        "experiment": args.experiment, "emitted_stream": emitted})
+        w.close()
+        if dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        if out is not None:
+            print(final_line(out, write_detail(out, args.detail) if args.detail else None), flush=True)
+        return
+
     sustained = None
     if args.sustained_steps > 0:
         sensors = GpuSensors(torch, local_rank)
@@ -1462,21 +1604,7 @@ def main():
         okv = int(t.item())
     assert okv == 1, "parity check failed on at least one rank"
 
-    emitted = None
-    if strong and args.emit_flac:
-        # the stream itself: frames of the last batch gathered to rank 0, metadata from the gathered sizes
-        from flac_codec_amd.encode import Options
-        from flac_codec_amd.parallel import finish_sharded_stream
-
-        data, off = an.fetch_frames(F)
-        o = Options.best() if cfg["lpc"] >= 12 else Options.default()
-        o = o.max_lpc_order(cfg["lpc"] or None).max_partition_order(cfg["po"])
-        flac = finish_sharded_stream(bytes(data[: off[F]]), [off[i + 1] - off[i] for i in range(F)], whole, o, RATE, BPS, C,
-                                     dist)
-        if rank == 0:
-            with open(args.emit_flac, "wb") as fh:
-                fh.write(flac)
-            emitted = {"path": args.emit_flac, "bytes": len(flac)}
+    emitted = emit_stream(args, cfg, an, F, whole, dist, rank) if strong and args.emit_flac else None
 
     out = None
     if rank == 0:
@@ -1514,7 +1642,6 @@ def main():
         # (the headline workload's contexts and device buffers are released BEFORE the host-path legs: with them alive
         # the pipelined leg measured 5-10 % below its stand-alone figure)
         pcm0 = w.pcm[0]
-        n_ctx = len(w.ans)
         w.close()
         torch.cuda.empty_cache()
         e2e = None
@@ -1535,31 +1662,8 @@ def main():
                 # the headline configuration on an input on which the encoder chooses HIGH LPC orders (SURVEY's generator
                 # makes it choose order 2 everywhere: `value` times a 2-tap FIR)
                 variants["high_order_input"] = measure_other_config(torch, args.config, args, local_rank, orc, signal="hi")
-        out = {
-            "metric": metric_text(args.config, differ == 0),
-            "value": round(value, 2),
-            "unit": "Msamples/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4),
-            "higher_is_better": True,
-            "scaling": args.scaling,
-            "vs_baseline": None,
-            "dtype": "i32/i64 (+f64 LPC analysis)",
-            "data": "synthetic",
-            "config": {"signal": SIGNAL_TEXT[args.signal] if args.signal != "hi" else
-                       SIGNAL_TEXT["hi"] % (2 * HI_SECTIONS.get(args.config, 6)),
-                       "workload": f"config {args.config}: {cfg['text']}; "
-                                   + (f"ONE stream of {total_frames} frames per step cut into contiguous frame ranges over "
-                                      f"{world} rank(s)" if strong else f"{F} frames per GPU per step")
-                                   + f", PCM resident in HBM, frame bytes produced in HBM; consecutive batches rotate "
-                                     f"through {len(w.ans)} encoder context(s) on separate HIP streams, each reading its "
-                                     f"own input buffer",
-                       "baseline_config": args.config, "level": cfg["level"],
-                       "frames_per_gpu": F, "frames_per_step": total_frames, "parallelism": f"frame ranges x{world}",
-                       "contexts": n_ctx, "distinct_input_buffers": n_ctx if not strong else 1,
-                       "prewarm": f"{prewarm_steps} untimed steps ({args.prewarm_ms:.0f} ms) before the warm-up"},
+        out = headline(differ == 0)
+        out.update({
             "sustained": sustained,
             "variants": variants,
             "roofline": roofline,
@@ -1580,7 +1684,7 @@ def main():
             "analysis_stats": analysis_stats,
             "shard_counters": counters,
             "emitted_stream": emitted,
-        }
+        })
         del pcm0
     else:
         w.close()

@@ -1,6 +1,7 @@
 """bench.py's bookkeeping that needs no GPU: which committed counter collection a bench line quotes (the newest of the
 right variant), and the `counters_stale` flag that compares the collection's build id with the running library's
-(VERDICT r03 weak 9 / ADVICE r03); the cached synthetic PCM; the dominance rule over HBM- and f64-priced kernels."""
+(VERDICT r03 weak 9 / ADVICE r03); the cached synthetic PCM; the dominance rule over HBM- and f64-priced kernels; the
+arrays --dump-outputs writes."""
 import json
 import os
 import sys
@@ -156,3 +157,47 @@ def test_detail_file_holds_the_full_record(tmp_path):
     full = _canned_full_record()
     path = bench.write_detail(full, str(tmp_path / "detail.json"))
     assert json.load(open(path)) == full
+
+
+def _frames(n, seed=3):
+    rng = np.random.default_rng(seed)
+    off = [0] + np.cumsum(rng.integers(100, 400, n)).tolist()
+    return rng.integers(0, 256, off[-1], dtype=np.uint8).tobytes(), off
+
+
+def test_dump_outputs_every_frame_when_they_fit(tmp_path):
+    import bench
+
+    data, off = _frames(300)
+    bench.dump_outputs(str(tmp_path), data, off, 400)
+    o, i, b = (np.load(tmp_path / f"{n}.npy") for n in ("frame_offsets", "frame_index", "frame_bytes"))
+    assert o.dtype == np.float64 and i.dtype == np.float64 and b.dtype == np.float32
+    assert o.tolist() == off and i.tolist() == list(range(300))
+    assert b.astype(np.uint8).tobytes() == data
+
+
+def test_dump_outputs_a_fixed_sample_within_the_limit(tmp_path, monkeypatch):
+    import bench
+
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 200_000)
+    data, off = _frames(1000)
+    for name in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / name), data, off, 400)
+        assert sum(os.path.getsize(tmp_path / name / f) for f in os.listdir(tmp_path / name)) <= bench.DUMP_LIMIT
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("frame_offsets", "frame_index", "frame_bytes")}
+    for n, v in a.items():
+        assert np.array_equal(v, np.load(tmp_path / "b" / f"{n}.npy")), n
+    idx = a["frame_index"].astype(int)
+    assert 50 < idx.size < 1000 and np.all(np.diff(idx) > 0)
+    assert a["frame_bytes"].astype(np.uint8).tobytes() == b"".join(data[off[f]:off[f + 1]] for f in idx)
+    # the sample does not depend on what the frames hold: another output of the same shape, the same frames
+    data2, off2 = _frames(1000, seed=4)
+    bench.dump_outputs(str(tmp_path / "c"), data2, off2, 400)
+    assert np.array_equal(np.load(tmp_path / "c" / "frame_index.npy"), a["frame_index"])
+
+
+def test_join_shards_offsets_into_the_whole():
+    import bench
+
+    data, off = bench.join_shards([(b"abcXX", [0, 1, 3]), (b"defg", [0, 4])])
+    assert data == b"abcdefg" and off == [0, 1, 3, 7]

@@ -26,7 +26,7 @@ def test_strong_scaling_two_ranks_emit_the_single_writers_stream(tmp_path, confi
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--scaling", "strong", "--config",
                         str(config), "--frames", str(frames), "--steps", "2", "--warmup", "1", "--prewarm-ms", "0",
-                        "--sustained-steps", "0", "--contexts", "2", "--no-cpu-baseline", "--no-end-to-end",
+                        "--sustained-steps", "0", "--contexts", "2", "--full", "--no-cpu-baseline", "--no-end-to-end",
                         "--no-other-configs", "--emit-flac", str(out), "--detail", str(tmp_path / "detail.json")],
                        cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -60,7 +60,7 @@ def test_in_process_multi_device_bench_line():
     env = dict(os.environ, FLAC_BENCH_SHARE_DEVICE="1")
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--in-process", "--frames", "64",
-                        "--steps", "3", "--warmup", "1", "--prewarm-ms", "0", "--contexts", "2", "--detail", os.devnull],
+                        "--steps", "3", "--warmup", "1", "--prewarm-ms", "0", "--contexts", "2", "--full", "--detail", os.devnull],
                        cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])

@@ -15,7 +15,7 @@ for spec in "$@"; do
     cfg=${run%%:*}; sig=${run##*:}
     ( [ "$name" != default ] && export FLACENC_AMD_LIBRARY=$ROOT/gpurun_variants/$name.so
       for kv in ${envs//,/ }; do export "$kv"; done
-      timeout 300 python3 bench.py --config $cfg --signal $sig --steps 30 --warmup 5 --no-cpu-baseline --no-end-to-end \
+      timeout 300 python3 bench.py --config $cfg --signal $sig --steps 30 --warmup 5 --full --no-cpu-baseline --no-end-to-end \
         --no-other-configs --sustained-steps 0 --detail $OUT/${name}_${cfg}${sig}_$rep.json > /dev/null 2> $OUT/${name}_${cfg}${sig}_$rep.err || echo "FAILED $spec $run" )
     python3 - "$OUT/${name}_${cfg}${sig}_$rep.json" "$spec" "$cfg$sig" <<'PY'
 import json,sys

@@ -14,7 +14,7 @@ TAG=${1:-r01}; shift || true
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
-COMMON="--contexts 1 --no-cpu-baseline --no-end-to-end --sustained-steps 0 --prewarm-ms 200 --no-other-configs"
+COMMON="--contexts 1 --full --no-cpu-baseline --no-end-to-end --sustained-steps 0 --prewarm-ms 200 --no-other-configs"
 python3 -c "import sys; sys.path.insert(0, '$ROOT'); from flac_codec_amd import _lib; print(_lib.build_id())" > $OUT/build_id.txt
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $ROOT/bench.py --steps 20 --warmup 3 $COMMON "$@" > $OUT/stats.log 2>&1
@@ -23,5 +23,5 @@ rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/write -- python3 $ROOT/be
 rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_WAVES --output-format csv -d $OUT/valu -- python3 $ROOT/bench.py --steps 3 --warmup 1 $COMMON "$@" > $OUT/valu.log 2>&1 || true
 cd $ROOT
 # the full record goes to bench.json (what summarize_profiles.py copies), the compact driver line to bench_line.json
-if [ -n "$FULL" ]; then python3 bench.py --steps 20 --warmup 5 --detail $OUT/bench.json "$@" > $OUT/bench_line.json 2> $OUT/bench.err; fi
+if [ -n "$FULL" ]; then python3 bench.py --steps 20 --warmup 5 --full --detail $OUT/bench.json "$@" > $OUT/bench_line.json 2> $OUT/bench.err; fi
 ls $OUT

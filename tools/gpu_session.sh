@@ -17,7 +17,7 @@ for spec in "$@"; do
   envs=${spec%%:*}; flags=${spec#*:}
   i=$((i+1))
   ( for kv in ${envs//,/ }; do [ -n "$kv" ] && export "$kv"; done
-    timeout 600 python3 bench.py --detail $OUT/bench_$i.json $flags > $OUT/bench_line_$i.json 2> $OUT/bench_$i.err
+    timeout 600 python3 bench.py --full --detail $OUT/bench_$i.json $flags > $OUT/bench_line_$i.json 2> $OUT/bench_$i.err
     echo "[$i] $spec rc=$?" )
   python3 - "$OUT/bench_$i.json" <<'PY'
 import json,sys

@@ -6,6 +6,6 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $OUT/trace -- python3 $ROOT/bench.py --steps 60 --warmup 5 --no-cpu-baseline --no-end-to-end --sustained-steps 0 --prewarm-ms 100 "$@" > $OUT/trace.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $OUT/trace -- python3 $ROOT/bench.py --steps 60 --warmup 5 --full --no-cpu-baseline --no-end-to-end --sustained-steps 0 --prewarm-ms 100 "$@" > $OUT/trace.log 2>&1
 cd $ROOT
 python3 tools/trace_overlap.py $OUT/trace
