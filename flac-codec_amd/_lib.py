@@ -15,6 +15,8 @@ MAX_CHANNELS = 8
 MAX_LPC_ORDER = 32
 MAX_PARTITIONS = 64
 N_KERNELS = 12
+DECODE_OUT_DEVICE = 1   # flacgpu_decoder_decode flags (include/flacenc_gpu.h)
+DECODE_NO_MD5 = 2
 
 
 class GpuOptions(C.Structure):
@@ -85,6 +87,11 @@ class StreamInfo(C.Structure):
         ("md5", C.c_uint8 * 16), ("decoded_md5", C.c_uint8 * 16),
         ("md5_status", C.c_uint32), ("reserved", C.c_uint32),
     ]
+
+
+class DecodedStream(C.Structure):
+    """flacgpu_decoded_stream: one stream's record of the batch decoder."""
+    _fields_ = [("rc", C.c_int32), ("reserved", C.c_uint32), ("out_offset", C.c_uint64), ("info", StreamInfo)]
 
 
 class ShardCounters(C.Structure):
@@ -172,6 +179,12 @@ def _load():
                                       C.c_uint32, C.c_void_p, C.c_void_p, ip, C.c_uint32,
                                       C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
     L.flacgpu_decode_stream.argtypes = [C.c_char_p, C.c_size_t, C.c_int, ip, C.c_size_t, C.POINTER(StreamInfo)]
+    L.flacgpu_decoder_create.argtypes = [C.c_int, C.POINTER(vp)]
+    L.flacgpu_decoder_destroy.argtypes = [vp]
+    L.flacgpu_decoder_destroy.restype = None
+    L.flacgpu_decoder_scan.argtypes = [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_uint32,
+                                       C.POINTER(DecodedStream), C.POINTER(C.c_uint64)]
+    L.flacgpu_decoder_decode.argtypes = [vp, vp, C.c_size_t, C.c_uint32, C.POINTER(DecodedStream)]
     L.flacgpu_pack_plans.argtypes = [vp, ip, C.c_uint32, C.c_uint32, C.POINTER(FramePlan), C.POINTER(SubframePlan),
                                      C.c_uint64, C.c_uint32]
     L.flacgpu_host_alloc.argtypes = [C.c_size_t]

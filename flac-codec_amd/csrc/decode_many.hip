@@ -1,0 +1,442 @@
+// decode_many.hip -- batch decoder: many FLAC streams in one call, frames found and decoded on the device, samples
+// to host or device memory, MD5 on the device (include/flacenc_gpu.h "batch decoder").
+// One of the translation units of libflacenc_amd.so (gfx950 only).  Kernels: kernels/frame_scan.inc (frame discovery)
+// and kernels/decode_many.inc (decode, CRC-16, finish, MD5); the subframe decoder is decode.inc's, unchanged.
+#include "kernels/types.h"
+
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <new>
+#include <vector>
+
+namespace {
+#include "kernels/common.inc"
+#include "kernels/decode.inc"
+#include "kernels/crc16.inc"
+#include "kernels/frame_scan.inc"
+#include "kernels/decode_many.inc"
+
+constexpr uint32_t kSlotTail = 64;   // zero bytes behind every stream's region (at least)
+
+// a device buffer that only grows
+struct DevBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+    int ensure(size_t bytes) {
+        if (bytes <= cap) return FLACGPU_OK;
+        const size_t want = std::max(bytes, cap + cap / 2);
+        (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+        HIP_TRY(hipMalloc(&p, want));
+        cap = want;
+        return FLACGPU_OK;
+    }
+    template <class T> T *as() const { return static_cast<T *>(p); }
+    ~DevBuf() { (void)hipFree(p); }
+};
+struct HostBuf {   // pinned
+    void *p = nullptr;
+    size_t cap = 0;
+    int ensure(size_t bytes) {
+        if (bytes <= cap) return FLACGPU_OK;
+        const size_t want = std::max(bytes, cap + cap / 2);
+        (void)hipHostFree(p);
+        p = nullptr;
+        cap = 0;
+        HIP_TRY(hipHostMalloc(&p, want, hipHostMallocDefault));
+        cap = want;
+        return FLACGPU_OK;
+    }
+    template <class T> T *as() const { return static_cast<T *>(p); }
+    ~HostBuf() { (void)hipHostFree(p); }
+};
+
+// flacgpu_decode_stream's metadata parse (fLaC marker, metadata blocks, STREAMINFO), with its return codes and the
+// fields it leaves in `info` on every path; *frames_at = the first byte behind the metadata
+int parse_metadata(const uint8_t *data, size_t len, flacgpu_stream_info *info, uint32_t *min_frame, size_t *frames_at) {
+    memset(info, 0, sizeof *info);
+    if (!data || len < 42 || memcmp(data, "fLaC", 4) != 0) return FLACGPU_ERR_INVALID_ARG;
+    size_t pos = 4;
+    bool have_si = false;
+    *min_frame = 0;
+    for (;;) {   // metadata blocks (metadata/mod.rs:257-266): last flag + type, 24-bit length
+        if (pos + 4 > len) return FLACGPU_ERR_INVALID_ARG;
+        const bool last = data[pos] & 0x80;
+        const uint32_t type = data[pos] & 0x7F;
+        const size_t blen = (size_t)data[pos + 1] << 16 | (size_t)data[pos + 2] << 8 | data[pos + 3];
+        pos += 4;
+        if (pos + blen > len) return FLACGPU_ERR_INVALID_ARG;
+        if (type == 0 && blen == 34) {   // STREAMINFO, metadata/mod.rs:1599-1630
+            const uint8_t *b = data + pos;
+            info->min_block = b[0] << 8 | b[1];
+            info->max_block = b[2] << 8 | b[3];
+            *min_frame = b[4] << 16 | b[5] << 8 | b[6];
+            info->sample_rate = (uint32_t)b[10] << 12 | (uint32_t)b[11] << 4 | b[12] >> 4;
+            info->channels = ((b[12] >> 1) & 7) + 1;
+            info->bits_per_sample = (((uint32_t)b[12] & 1) << 4 | b[13] >> 4) + 1;
+            info->total_samples = ((uint64_t)(b[13] & 15) << 32) | (uint64_t)b[14] << 24 | (uint64_t)b[15] << 16 |
+                                  (uint64_t)b[16] << 8 | b[17];
+            memcpy(info->md5, b + 18, 16);
+            have_si = true;
+        }
+        pos += blen;
+        if (last) break;
+    }
+    if (!have_si || info->channels > 8 || info->bits_per_sample > 32 || info->max_block < 1)
+        return FLACGPU_ERR_INVALID_ARG;
+    *frames_at = pos;
+    return FLACGPU_OK;
+}
+}  // namespace
+
+struct flacgpu_decoder {
+    int device = 0;
+    hipStream_t st = nullptr;
+    HostBuf staging;   // the batch buffer on its way up
+    DevBuf bytes, slots, mask, plocal, wg_cnt, wg_tail, wg_off, wg_carry;
+    DevBuf cand_pos, cand_info, cand_crc, cand_slot, slot_cand0, slot_pend, link;
+    DevBuf frames, scratch, codes, counts, jobs, digest, out_stage;
+    // the scanned batch
+    bool scanned = false;
+    std::vector<flacgpu_decoded_stream> res;
+    std::vector<int32_t> slot_of;          // stream -> slot, -1: no frame region on the device
+    std::vector<ManyFrame> frame_tab;
+    uint32_t n_slots = 0;
+    uint64_t total = 0, scratch_total = 0;
+};
+
+namespace {
+int scan_impl(flacgpu_decoder *d, const uint8_t *const *data, const size_t *len, uint32_t n) {
+    d->res.assign(n, flacgpu_decoded_stream{});
+    d->slot_of.assign(n, -1);
+    d->frame_tab.clear();
+    // ---- host: metadata, slot layout
+    std::vector<ScanSlot> slots;
+    std::vector<size_t> region_at;   // first byte of the frame region in the caller's buffer
+    std::vector<uint32_t> slot_stream;
+    uint64_t at = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        flacgpu_decoded_stream &r = d->res[i];
+        uint32_t min_frame = 0;
+        size_t pos = 0;
+        r.rc = parse_metadata(data ? data[i] : nullptr, len ? len[i] : 0, &r.info, &min_frame, &pos);
+        if (r.rc != FLACGPU_OK || pos >= len[i]) continue;   // no frame region: 0 frames, nothing bad
+        ScanSlot s;
+        s.base = at;
+        s.len = len[i] - pos;
+        s.block0 = at / 64;
+        s.channels = r.info.channels;
+        s.min_frame = min_frame;
+        d->slot_of[i] = (int32_t)slots.size();
+        slots.push_back(s);
+        region_at.push_back(pos);
+        slot_stream.push_back(i);
+        at += (s.len + kSlotTail + 63) & ~(uint64_t)63;
+    }
+    const uint32_t S = (uint32_t)slots.size();
+    d->n_slots = S;
+    std::vector<uint64_t> cpos;
+    std::vector<uint32_t> cinfo, cand0(S);
+    std::vector<int32_t> clink;
+    if (S) {
+        // the bit reader indexes dwords with 32 bits
+        if (at + 64 > ((uint64_t)1 << 34)) {
+            g_last_error = "flacgpu_decoder_scan: the batch's frames exceed 16 GiB";
+            return FLACGPU_ERR_UNSUPPORTED;
+        }
+        const uint64_t n_blocks = at / 64;
+        const uint64_t n_wg64 = (n_blocks + WG - 1) / WG;
+        if (n_wg64 > 0xFFFFFFFFull) return FLACGPU_ERR_UNSUPPORTED;
+        const uint32_t n_wg = (uint32_t)n_wg64;
+        // ---- one upload: every region into the pinned staging, zero tails, 64 bytes of look-ahead
+        const size_t buf_bytes = at + 64;
+        if (int rc = d->staging.ensure(buf_bytes)) return rc;
+        uint8_t *stg = d->staging.as<uint8_t>();
+        for (uint32_t s = 0; s < S; s++) {
+            const uint64_t b = slots[s].base, l = slots[s].len;
+            const uint64_t e = s + 1 < S ? slots[s + 1].base : buf_bytes;
+            memcpy(stg + b, data[slot_stream[s]] + region_at[s], l);
+            memset(stg + b + l, 0, e - b - l);
+        }
+        if (int rc = d->bytes.ensure(buf_bytes)) return rc;
+        if (int rc = d->slots.ensure(sizeof(ScanSlot) * S)) return rc;
+        if (int rc = d->mask.ensure(8 * n_blocks)) return rc;
+        if (int rc = d->plocal.ensure(2 * n_blocks)) return rc;
+        if (int rc = d->wg_cnt.ensure(4 * n_wg)) return rc;
+        if (int rc = d->wg_tail.ensure(4 * n_wg)) return rc;
+        if (int rc = d->wg_off.ensure(4 * (n_wg + 1))) return rc;
+        if (int rc = d->wg_carry.ensure(2 * n_wg)) return rc;
+        if (int rc = d->slot_cand0.ensure(4 * S)) return rc;
+        if (int rc = d->slot_pend.ensure(4 * S)) return rc;
+        HIP_TRY(hipMemcpyAsync(d->bytes.p, stg, buf_bytes, hipMemcpyHostToDevice, d->st));
+        HIP_TRY(hipMemcpyAsync(d->slots.p, slots.data(), sizeof(ScanSlot) * S, hipMemcpyHostToDevice, d->st));
+        ScanParams p{};
+        p.bytes = d->bytes.as<uint8_t>();
+        p.slots = d->slots.as<ScanSlot>();
+        p.n_slots = S;
+        p.n_blocks = n_blocks;
+        p.mask = d->mask.as<uint64_t>();
+        p.plocal = d->plocal.as<uint16_t>();
+        p.wg_cnt = d->wg_cnt.as<uint32_t>();
+        p.wg_tail = d->wg_tail.as<uint32_t>();
+        p.wg_off = d->wg_off.as<uint32_t>();
+        p.wg_carry = d->wg_carry.as<uint16_t>();
+        p.slot_cand0 = d->slot_cand0.as<uint32_t>();
+        p.slot_pend = d->slot_pend.as<uint32_t>();
+        hipLaunchKernelGGL(k_scan_blocks, dim3(n_wg), dim3(WG), 0, d->st, p);
+        hipLaunchKernelGGL(k_scan_carry, dim3(1), dim3(WG), 0, d->st, p, n_wg);
+        HIP_TRY(hipGetLastError());
+        uint32_t n_cand = 0;
+        HIP_TRY(hipMemcpyAsync(&n_cand, d->wg_off.as<uint32_t>() + n_wg, 4, hipMemcpyDeviceToHost, d->st));
+        HIP_TRY(hipStreamSynchronize(d->st));
+        const size_t nc = std::max<uint32_t>(n_cand, 1);
+        if (int rc = d->cand_pos.ensure(8 * nc)) return rc;
+        if (int rc = d->cand_info.ensure(4 * nc)) return rc;
+        if (int rc = d->cand_crc.ensure(4 * nc)) return rc;
+        if (int rc = d->cand_slot.ensure(4 * nc)) return rc;
+        if (int rc = d->link.ensure(4 * nc)) return rc;
+        p.cand_pos = d->cand_pos.as<uint64_t>();
+        p.cand_info = d->cand_info.as<uint32_t>();
+        p.cand_crc = d->cand_crc.as<uint32_t>();
+        p.cand_slot = d->cand_slot.as<uint32_t>();
+        p.link = d->link.as<int32_t>();
+        p.n_cand = n_cand;
+        hipLaunchKernelGGL(k_scan_emit, dim3(n_wg), dim3(WG), 0, d->st, p);
+        if (n_cand) hipLaunchKernelGGL(k_link, dim3((n_cand + WG - 1) / WG), dim3(WG), 0, d->st, p);
+        HIP_TRY(hipGetLastError());
+        try {
+            cpos.resize(n_cand);
+            cinfo.resize(n_cand);
+            clink.resize(n_cand);
+        } catch (const std::bad_alloc &) {
+            g_last_error = "flacgpu_decoder_scan: out of host memory";
+            return FLACGPU_ERR_UNSUPPORTED;
+        }
+        if (n_cand) {
+            HIP_TRY(hipMemcpyAsync(cpos.data(), p.cand_pos, 8 * (size_t)n_cand, hipMemcpyDeviceToHost, d->st));
+            HIP_TRY(hipMemcpyAsync(cinfo.data(), p.cand_info, 4 * (size_t)n_cand, hipMemcpyDeviceToHost, d->st));
+            HIP_TRY(hipMemcpyAsync(clink.data(), p.link, 4 * (size_t)n_cand, hipMemcpyDeviceToHost, d->st));
+        }
+        HIP_TRY(hipMemcpyAsync(cand0.data(), p.slot_cand0, 4 * (size_t)S, hipMemcpyDeviceToHost, d->st));
+        HIP_TRY(hipStreamSynchronize(d->st));
+        // ---- host walk: follow the links from each region's first byte (the host scan's lost-sync rule: a frame
+        // without an end is not taken, and nothing behind it is decoded)
+        for (uint32_t s = 0; s < S; s++) {
+            const ScanSlot &sl = slots[s];
+            flacgpu_stream_info &info = d->res[slot_stream[s]].info;
+            const uint32_t c_end = s + 1 < S ? cand0[s + 1] : n_cand;
+            uint32_t i = cand0[s];
+            uint64_t samples = 0;
+            uint32_t F = 0;
+            const uint64_t slot_end = s + 1 < S ? slots[s + 1].base : at;
+            if (i >= c_end || cpos[i] != sl.base) {
+                info.bad_frames = 1;
+            } else {
+                for (;;) {
+                    const int32_t nx = clink[i];
+                    if (nx == LINK_NONE) {
+                        info.bad_frames = 1;
+                        break;
+                    }
+                    ManyFrame f{};
+                    f.start = cpos[i];
+                    f.end = nx == LINK_END ? sl.base + sl.len : cpos[nx];
+                    f.cap = slot_end - 4;
+                    f.n = (cinfo[i] & 0xFFFFu) + 1u;
+                    f.slot = s;
+                    f.channels = info.channels;
+                    f.bps = info.bits_per_sample;
+                    f.out = samples;   // stream-relative here, made absolute below
+                    d->frame_tab.push_back(f);
+                    samples += f.n;
+                    F++;
+                    if (nx == LINK_END) break;
+                    i = (uint32_t)nx;
+                }
+            }
+            info.frames = F;
+            info.decoded_samples = samples;
+        }
+    }
+    // ---- output layout: streams one after another, interleaved
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        flacgpu_decoded_stream &r = d->res[i];
+        r.out_offset = total;
+        if (r.rc == FLACGPU_OK) total += r.info.decoded_samples * r.info.channels;
+    }
+    uint64_t scratch_total = 0;
+    for (ManyFrame &f : d->frame_tab) {
+        const flacgpu_decoded_stream &r = d->res[slot_stream[f.slot]];
+        f.out = r.out_offset + f.out * f.channels;
+        f.scratch = scratch_total;
+        scratch_total += (uint64_t)f.channels * ((f.n + 3u) & ~3u);
+    }
+    if (!d->frame_tab.empty()) {
+        if (int rc = d->frames.ensure(sizeof(ManyFrame) * d->frame_tab.size())) return rc;
+        HIP_TRY(hipMemcpyAsync(d->frames.p, d->frame_tab.data(), sizeof(ManyFrame) * d->frame_tab.size(),
+                               hipMemcpyHostToDevice, d->st));
+        HIP_TRY(hipStreamSynchronize(d->st));   // frame_tab may change before the copy is done otherwise
+    }
+    d->total = total;
+    d->scratch_total = scratch_total;
+    return FLACGPU_OK;
+}
+
+int decode_impl(flacgpu_decoder *d, int32_t *out, size_t cap, uint32_t flags) {
+    const uint32_t n = (uint32_t)d->res.size();
+    const uint32_t F = (uint32_t)d->frame_tab.size(), S = d->n_slots;
+    const bool to_device = flags & FLACGPU_DECODE_OUT_DEVICE, md5 = !(flags & FLACGPU_DECODE_NO_MD5);
+    int32_t *dst = out;
+    if (!to_device && d->total) {
+        if (int rc = d->out_stage.ensure(4 * d->total)) return rc;
+        dst = d->out_stage.as<int32_t>();
+    }
+    if (int rc = d->counts.ensure(8 * (size_t)std::max<uint32_t>(S, 1))) return rc;
+    HIP_TRY(hipMemsetAsync(d->counts.p, 0, 8 * (size_t)std::max<uint32_t>(S, 1), d->st));
+    if (F) {
+        if (int rc = d->scratch.ensure(4 * d->scratch_total)) return rc;
+        if (int rc = d->codes.ensure(4 * (size_t)F)) return rc;
+        const uint32_t lanes = 32;   // launch_decode_frames' wave size
+        hipLaunchKernelGGL(k_decode_many<32>, dim3((F + lanes - 1) / lanes), dim3(lanes), 0, d->st,
+                           d->bytes.as<const uint32_t>(), d->frames.as<const ManyFrame>(), F, d->scratch.as<int32_t>(),
+                           d->codes.as<uint32_t>());
+        hipLaunchKernelGGL(k_frame_crc, dim3(F), dim3(64), 0, d->st, d->bytes.as<const uint8_t>(),
+                           d->frames.as<const ManyFrame>(), d->counts.as<uint32_t>());
+        hipLaunchKernelGGL(k_finish_many, dim3(F), dim3(WG), 0, d->st, d->frames.as<const ManyFrame>(),
+                           d->scratch.as<const int32_t>(), d->codes.as<const uint32_t>(), dst,
+                           d->counts.as<uint32_t>());
+        HIP_TRY(hipGetLastError());
+    }
+    std::vector<Md5Job> jobs;
+    std::vector<uint32_t> job_stream, digest;
+    if (md5) {
+        for (uint32_t i = 0; i < n; i++) {
+            const flacgpu_decoded_stream &r = d->res[i];
+            if (r.rc != FLACGPU_OK) continue;
+            Md5Job j{};
+            j.off = r.out_offset;
+            j.count = r.info.decoded_samples * r.info.channels;
+            j.width = (r.info.bits_per_sample + 7) / 8;
+            memcpy(j.expect, r.info.md5, 16);
+            jobs.push_back(j);
+            job_stream.push_back(i);
+        }
+    }
+    const uint32_t J = (uint32_t)jobs.size();
+    if (J) {
+        if (int rc = d->jobs.ensure(sizeof(Md5Job) * J)) return rc;
+        if (int rc = d->digest.ensure(20 * (size_t)J)) return rc;
+        HIP_TRY(hipMemcpyAsync(d->jobs.p, jobs.data(), sizeof(Md5Job) * J, hipMemcpyHostToDevice, d->st));
+        hipLaunchKernelGGL(k_md5_many, dim3((J + 63) / 64), dim3(64), 0, d->st, dst, d->jobs.as<const Md5Job>(), J,
+                           d->digest.as<uint32_t>());
+        HIP_TRY(hipGetLastError());
+        digest.resize(5 * (size_t)J);
+        HIP_TRY(hipMemcpyAsync(digest.data(), d->digest.p, 20 * (size_t)J, hipMemcpyDeviceToHost, d->st));
+    }
+    std::vector<uint32_t> counts(2 * (size_t)S);
+    if (S) HIP_TRY(hipMemcpyAsync(counts.data(), d->counts.p, 8 * (size_t)S, hipMemcpyDeviceToHost, d->st));
+    if (!to_device && d->total)
+        HIP_TRY(hipMemcpyAsync(out, dst, 4 * d->total, hipMemcpyDeviceToHost, d->st));
+    HIP_TRY(hipStreamSynchronize(d->st));
+    (void)cap;
+    for (uint32_t i = 0; i < n; i++) {
+        flacgpu_decoded_stream &r = d->res[i];
+        const int32_t s = d->slot_of[i];
+        if (s >= 0 && r.info.frames) {
+            r.info.bad_frames += counts[2 * (size_t)s];
+            r.info.bad_crc16 = counts[2 * (size_t)s + 1];
+        }
+        if (r.rc == FLACGPU_OK && !md5) r.info.md5_status = 3;
+    }
+    for (uint32_t j = 0; j < J; j++) {
+        flacgpu_stream_info &info = d->res[job_stream[j]].info;
+        memcpy(info.decoded_md5, &digest[5 * (size_t)j], 16);
+        info.md5_status = digest[5 * (size_t)j + 4];
+    }
+    return FLACGPU_OK;
+}
+}  // namespace
+
+int flacgpu_decoder_create(int device, flacgpu_decoder **out) {
+    if (!out) return FLACGPU_ERR_INVALID_ARG;
+    *out = nullptr;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+        g_last_error = "no HIP device";
+        return FLACGPU_ERR_NO_DEVICE;
+    }
+    if (device >= ndev) {
+        g_last_error = "no such HIP device";
+        return FLACGPU_ERR_NO_DEVICE;
+    }
+    if (device < 0) HIP_TRY(hipGetDevice(&device));
+    flacgpu_decoder *d = new (std::nothrow) flacgpu_decoder();
+    if (!d) return FLACGPU_ERR_UNSUPPORTED;
+    d->device = device;
+    int prev = -1;
+    (void)hipGetDevice(&prev);
+    hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&d->st, hipStreamNonBlocking);
+    if (prev >= 0) (void)hipSetDevice(prev);
+    if (e != hipSuccess) {
+        g_last_error = std::string("flacgpu_decoder_create: ") + hipGetErrorString(e);
+        delete d;
+        return FLACGPU_ERR_HIP;
+    }
+    *out = d;
+    return FLACGPU_OK;
+}
+
+void flacgpu_decoder_destroy(flacgpu_decoder *d) {
+    if (!d) return;
+    int prev = -1;
+    (void)hipGetDevice(&prev);
+    (void)hipSetDevice(d->device);
+    if (d->st) (void)hipStreamSynchronize(d->st);
+    if (d->st) (void)hipStreamDestroy(d->st);
+    d->st = nullptr;
+    delete d;   // the buffers free themselves, on the decoder's device
+    if (prev >= 0) (void)hipSetDevice(prev);
+}
+
+int flacgpu_decoder_scan(flacgpu_decoder *d, const uint8_t *const *data, const size_t *len, uint32_t n_streams,
+                         flacgpu_decoded_stream *streams, uint64_t *total_samples) {
+    if (!d || (n_streams && (!data || !len || !streams)) || !total_samples) return FLACGPU_ERR_INVALID_ARG;
+    d->scanned = false;
+    int prev = -1;
+    const bool moved = hipGetDevice(&prev) == hipSuccess && prev != d->device && hipSetDevice(d->device) == hipSuccess;
+    const int rc = scan_impl(d, data, len, n_streams);
+    if (moved) (void)hipSetDevice(prev);
+    if (rc != FLACGPU_OK) return rc;
+    d->scanned = true;
+    if (n_streams) memcpy(streams, d->res.data(), sizeof(flacgpu_decoded_stream) * n_streams);
+    *total_samples = d->total;
+    return FLACGPU_OK;
+}
+
+int flacgpu_decoder_decode(flacgpu_decoder *d, int32_t *out, size_t out_cap_samples, uint32_t flags,
+                           flacgpu_decoded_stream *streams) {
+    if (!d || (flags & ~(FLACGPU_DECODE_OUT_DEVICE | FLACGPU_DECODE_NO_MD5))) return FLACGPU_ERR_INVALID_ARG;
+    if (!d->scanned) {
+        g_last_error = "flacgpu_decoder_decode: no scanned batch";
+        return FLACGPU_ERR_INVALID_ARG;
+    }
+    if (!d->res.empty() && !streams) return FLACGPU_ERR_INVALID_ARG;
+    if (d->total && (!out || out_cap_samples < d->total)) {
+        g_last_error = "output buffer too small";
+        return FLACGPU_ERR_BUFFER_TOO_SMALL;
+    }
+    int prev = -1;
+    const bool moved = hipGetDevice(&prev) == hipSuccess && prev != d->device && hipSetDevice(d->device) == hipSuccess;
+    std::vector<flacgpu_decoded_stream> keep = d->res;   // a second decode of the same scan starts from the scan's records
+    const int rc = decode_impl(d, out, out_cap_samples, flags);
+    if (moved) (void)hipSetDevice(prev);
+    if (rc == FLACGPU_OK && !d->res.empty())
+        memcpy(streams, d->res.data(), sizeof(flacgpu_decoded_stream) * d->res.size());
+    d->res.swap(keep);
+    return rc;
+}

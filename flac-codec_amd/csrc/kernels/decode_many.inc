@@ -1,0 +1,200 @@
+// decode_many.inc -- the batch decoder's frame kernels and MD5 (decode_many.hip).
+// Included inside decode_many.hip's anonymous namespace, after decode.inc, crc16.inc and frame_scan.inc.
+//   K_d1 k_decode_many   lane per frame: k_decode_frames with a per-frame descriptor (streams of any shape in one
+//                        launch), planar scratch of exactly channels x roundup4(n) samples per frame
+//   K_d2 k_frame_crc     wave per frame: CRC-16 of the frame, stored CRC included, must be 0
+//   K_d3 k_finish_many   workgroup per frame: undoes the stereo decorrelation (k_decode_finish's arithmetic) and
+//                        writes interleaved int32 at the stream's output offset
+//   K_d4 k_md5_many      lane per stream: MD5 of the stream's interleaved samples as ceil(bps / 8)-byte
+//                        little-endian values (decode.rs:1282-1310 `verify`)
+
+struct ManyFrame {
+    uint64_t start, end;   // byte offsets in the batch buffer: header .. CRC-16 inclusive
+    uint64_t cap;          // the slot's end - 4: the bit reader never leaves the slot's zero tail
+    uint64_t scratch;      // first planar sample of the frame (channel rows of roundup4(n) samples)
+    uint64_t out;          // first interleaved sample of the frame in the output
+    uint32_t n, slot, channels, bps;   // n: the scan's block size; channels / bps: STREAMINFO
+};
+
+template <int MAXO>
+__global__ void __launch_bounds__(64) k_decode_many(const uint32_t *__restrict__ words,
+                                                    const ManyFrame *__restrict__ frames, uint32_t n_frames,
+                                                    int32_t *__restrict__ scratch, uint32_t *__restrict__ codes) {
+    const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= n_frames) return;
+    const ManyFrame fr = frames[f];
+    const uint8_t *bytes = reinterpret_cast<const uint8_t *>(words);
+    const uint32_t end_bit = (uint32_t)(fr.end - fr.start) * 8;
+    const uint32_t ldb = (fr.n + 3u) & ~3u;
+    BitReader r;
+    r.init(words, fr.start, fr.cap, 0);
+    FrameHead fh;
+    bool bad = !parse_frame_header(r, bytes, fr.start, fh);
+    const uint32_t n = fh.n, acode = fh.acode;
+    const uint32_t bps = bps_of_code(fh.bps_code, fr.bps);
+    const uint32_t nch = acode < 8 ? acode + 1 : 2;
+    if (n != fr.n || bps != fr.bps || nch != fr.channels) bad = true;
+    for (uint32_t c = 0; c < nch && !bad; c++) {
+        int32_t *__restrict__ x = scratch + fr.scratch + (size_t)c * ldb;
+        if (!decode_subframe<MAXO>(r, subframe_bps(bps, acode, c), n, x, end_bit)) bad = true;
+    }
+    if (!bad && ((r.pos() + 7) & ~7u) + 16 != end_bit) bad = true;
+    if (!bad && (r.pos() & 7) && r.get(8 - (r.pos() & 7)) != 0) bad = true;
+    codes[f] = (bad ? 0x100u : 0u) | acode;
+}
+
+// the CRC-16 of the whole frame, its stored CRC included, is 0 exactly when the stored CRC is right
+__global__ void __launch_bounds__(64) k_frame_crc(const uint8_t *__restrict__ bytes,
+                                                  const ManyFrame *__restrict__ frames,
+                                                  uint32_t *__restrict__ slot_counts) {
+    __shared__ uint16_t T[256];
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t i = tid; i < 256; i += 64) {
+        uint32_t c = i << 8;
+        for (int b = 0; b < 8; b++) c = (c & 0x8000) ? ((c << 1) ^ 0x8005) & 0xFFFF : (c << 1) & 0xFFFF;
+        T[i] = (uint16_t)c;
+    }
+    __syncthreads();
+    const ManyFrame fr = frames[blockIdx.x];
+    const uint64_t len = fr.end - fr.start;
+    const uint64_t per = (len + 63) / 64;
+    const uint64_t a = min(len, tid * per), e = min(len, a + per);
+    uint32_t crc = 0;
+    for (uint64_t i = a; i < e; i++) crc = ((crc << 8) & 0xFFFFu) ^ T[((crc >> 8) ^ bytes[fr.start + i]) & 0xFFu];
+    uint32_t c = gf_mulmod(crc, gf_xpow_bytes(len - e));   // weighted by the bytes behind the slice
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) c ^= __shfl_xor(c, off, 64);
+    if (tid == 0 && c) atomicAdd(&slot_counts[2 * fr.slot + 1], 1u);
+}
+
+// k_decode_finish's decorrelation (decode.inc), planar scratch -> interleaved output.  A frame that did not parse is
+// counted and written as decoded (what flacgpu_decode_stream leaves for it: not defined by the stream).
+__global__ void __launch_bounds__(WG) k_finish_many(const ManyFrame *__restrict__ frames,
+                                                    const int32_t *__restrict__ scratch,
+                                                    const uint32_t *__restrict__ codes, int32_t *__restrict__ out,
+                                                    uint32_t *__restrict__ slot_counts) {
+    const uint32_t f = blockIdx.x;
+    const ManyFrame fr = frames[f];
+    const uint32_t code = codes[f], acode = code & 0xFFu;
+    const bool bad = code & 0x100u;
+    if (bad && threadIdx.x == 0) atomicAdd(&slot_counts[2 * fr.slot], 1u);
+    const uint32_t n = fr.n, C = fr.channels, ldb = (n + 3u) & ~3u;
+    const int32_t *rows = scratch + fr.scratch;
+    int32_t *o = out + fr.out;
+    if (!bad && acode >= 8) {
+        for (uint32_t i = threadIdx.x; i < n; i += WG) {
+            const long long a = rows[i], b = rows[ldb + i];
+            long long l, rr;
+            if (acode == 8) { l = a; rr = a - b; }
+            else if (acode == 9) { l = a + b; rr = b; }
+            else {
+                const long long sum = a * 2 + ((b < 0 ? -b : b) & 1);
+                l = (sum + b) >> 1;
+                rr = (sum - b) >> 1;
+            }
+            o[2 * (size_t)i] = (int32_t)l;
+            o[2 * (size_t)i + 1] = (int32_t)rr;
+        }
+    } else {
+        for (uint32_t i = threadIdx.x; i < n; i += WG)
+            for (uint32_t c = 0; c < C; c++) o[(size_t)i * C + c] = rows[(size_t)c * ldb + i];
+    }
+}
+
+// ---- MD5 (RFC 1321) ----
+struct Md5Job {
+    uint64_t off;        // first interleaved sample of the stream in the output
+    uint64_t count;      // interleaved samples
+    uint32_t width;      // bytes per sample: ceil(bps / 8)
+    uint32_t reserved;
+    uint32_t expect[4];  // STREAMINFO's MD5
+};
+struct Md5Consts {
+    uint32_t k[64];
+    constexpr Md5Consts() : k() {
+        const uint32_t t[64] = {
+            0xd76aa478u, 0xe8c7b756u, 0x242070dbu, 0xc1bdceeeu, 0xf57c0fafu, 0x4787c62au, 0xa8304613u, 0xfd469501u,
+            0x698098d8u, 0x8b44f7afu, 0xffff5bb1u, 0x895cd7beu, 0x6b901122u, 0xfd987193u, 0xa679438eu, 0x49b40821u,
+            0xf61e2562u, 0xc040b340u, 0x265e5a51u, 0xe9b6c7aau, 0xd62f105du, 0x02441453u, 0xd8a1e681u, 0xe7d3fbc8u,
+            0x21e1cde6u, 0xc33707d6u, 0xf4d50d87u, 0x455a14edu, 0xa9e3e905u, 0xfcefa3f8u, 0x676f02d9u, 0x8d2a4c8au,
+            0xfffa3942u, 0x8771f681u, 0x6d9d6122u, 0xfde5380cu, 0xa4beea44u, 0x4bdecfa9u, 0xf6bb4b60u, 0xbebfbc70u,
+            0x289b7ec6u, 0xeaa127fau, 0xd4ef3085u, 0x04881d05u, 0xd9d4d039u, 0xe6db99e5u, 0x1fa27cf8u, 0xc4ac5665u,
+            0xf4292244u, 0x432aff97u, 0xab9423a7u, 0xfc93a039u, 0x655b59c3u, 0x8f0ccc92u, 0xffeff47du, 0x85845dd1u,
+            0x6fa87e4fu, 0xfe2ce6e0u, 0xa3014314u, 0x4e0811a1u, 0xf7537e82u, 0xbd3af235u, 0x2ad7d2bbu, 0xeb86d391u};
+        for (int i = 0; i < 64; i++) k[i] = t[i];
+    }
+};
+constexpr Md5Consts kMd5 = Md5Consts();
+__device__ __forceinline__ void md5_block(uint32_t (&s)[4], const uint32_t (&m)[16]) {
+    constexpr int R[4][4] = {{7, 12, 17, 22}, {5, 9, 14, 20}, {4, 11, 16, 23}, {6, 10, 15, 21}};
+    uint32_t a = s[0], b = s[1], c = s[2], d = s[3];
+#pragma unroll
+    for (int i = 0; i < 64; i++) {
+        uint32_t f;
+        int g;
+        if (i < 16) { f = (b & c) | (~b & d); g = i; }
+        else if (i < 32) { f = (d & b) | (~d & c); g = (5 * i + 1) & 15; }
+        else if (i < 48) { f = b ^ c ^ d; g = (3 * i + 5) & 15; }
+        else { f = c ^ (b | ~d); g = (7 * i) & 15; }
+        const uint32_t t = a + f + kMd5.k[i] + m[g];
+        a = d;
+        d = c;
+        c = b;
+        b = b + __builtin_rotateleft32(t, R[i >> 4][i & 3]);
+    }
+    s[0] += a; s[1] += b; s[2] += c; s[3] += d;
+}
+// Lane per stream.  The message words are built in registers from the int32 samples: a 64-bit accumulator takes
+// `width` bytes per sample and gives one word per 4 bytes; the 0x80 byte, zeros and the bit length follow the data.
+// digest[5 * s]: the 16 digest bytes as 4 little-endian words, then md5_status (1 equal, 0 different, 2 no MD5).
+__global__ void __launch_bounds__(64) k_md5_many(const int32_t *__restrict__ out, const Md5Job *__restrict__ jobs,
+                                                 uint32_t n_jobs, uint32_t *__restrict__ digest) {
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n_jobs) return;
+    const Md5Job jb = jobs[s];
+    const int32_t *src = out + jb.off;
+    uint64_t left = jb.count;
+    const uint32_t width = jb.width;
+    const uint64_t wmask = (1ull << (8 * width)) - 1;
+    const uint64_t bits = jb.count * width * 8;
+    const uint64_t nblocks = (jb.count * width + 8) / 64 + 1;
+    uint64_t acc = 0;
+    uint32_t nb = 0;
+    bool padded = false;
+    uint32_t st[4] = {0x67452301u, 0xefcdab89u, 0x98badcfeu, 0x10325476u};
+    for (uint64_t blk = 0; blk < nblocks; blk++) {
+        const bool last = blk + 1 == nblocks;
+        uint32_t m[16];
+#pragma unroll
+        for (int k = 0; k < 16; k++) {
+            if (k >= 14 && last) {
+                m[k] = k == 14 ? (uint32_t)bits : (uint32_t)(bits >> 32);
+                continue;
+            }
+            while (nb < 4) {
+                if (left) {
+                    acc |= ((uint64_t)(uint32_t)*src++ & wmask) << (8 * nb);
+                    nb += width;
+                    left--;
+                } else if (!padded) {
+                    acc |= 0x80ull << (8 * nb);
+                    nb += 1;
+                    padded = true;
+                } else {
+                    nb = 4;
+                }
+            }
+            m[k] = (uint32_t)acc;
+            acc >>= 32;
+            nb -= 4;
+        }
+        md5_block(st, m);
+    }
+    const bool none = (jb.expect[0] | jb.expect[1] | jb.expect[2] | jb.expect[3]) == 0;
+    const bool same = st[0] == jb.expect[0] && st[1] == jb.expect[1] && st[2] == jb.expect[2] && st[3] == jb.expect[3];
+    digest[5 * (size_t)s + 0] = st[0];
+    digest[5 * (size_t)s + 1] = st[1];
+    digest[5 * (size_t)s + 2] = st[2];
+    digest[5 * (size_t)s + 3] = st[3];
+    digest[5 * (size_t)s + 4] = none ? 2u : (same ? 1u : 0u);
+}

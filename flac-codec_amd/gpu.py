@@ -390,6 +390,109 @@ def decode_stream(data, device=-1, want_pcm=True):
     return out, info
 
 
+class DecodedStream:
+    """One stream of a decode_many batch: rc (what flacgpu_decode_stream returns for it), info (StreamInfo), offset
+    (first int32 in the flat output) and pcm (a [samples, channels] view of the flat output; None when rc != 0)."""
+    __slots__ = ("rc", "info", "offset", "pcm")
+
+    def __init__(self, rc, info, offset, pcm):
+        self.rc, self.info, self.offset, self.pcm = rc, info, offset, pcm
+
+
+class Decoder:
+    """flacgpu_decoder: a batch decoder handle that keeps its device buffers and pinned staging between calls.
+    Not thread-safe."""
+
+    def __init__(self, device=-1):
+        self._h = None
+        L = _lib.lib()
+        h = C.c_void_p()
+        rc = L.flacgpu_decoder_create(device, C.byref(h))
+        if rc:
+            raise GpuError(rc, "flacgpu_decoder_create")
+        self._h = h
+        self.device = device
+
+    def close(self):
+        if self._h:
+            _lib.lib().flacgpu_decoder_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def scan(self, blobs):
+        """flacgpu_decoder_scan: returns (records, total int32 samples)."""
+        L = _lib.lib()
+        blobs = [b if isinstance(b, bytes) else bytes(b) for b in blobs]
+        n = len(blobs)
+        ptrs = (C.c_void_p * max(n, 1))()
+        lens = (C.c_size_t * max(n, 1))()
+        keep = []   # the bytes objects' own buffers, no copy; alive until the scan has uploaded them
+        for i, b in enumerate(blobs):
+            cp = C.c_char_p(b)
+            keep.append(cp)
+            ptrs[i] = C.cast(cp, C.c_void_p).value
+            lens[i] = len(b)
+        recs = (_lib.DecodedStream * max(n, 1))()
+        total = C.c_uint64(0)
+        rc = L.flacgpu_decoder_scan(self._h, ptrs, lens, n, recs, C.byref(total))
+        if rc:
+            raise GpuError(rc, "flacgpu_decoder_scan")
+        return recs, total.value
+
+    def decode(self, out_ptr, out_cap, flags, recs):
+        """flacgpu_decoder_decode into the int32 buffer at out_ptr (device or host address)."""
+        rc = _lib.lib().flacgpu_decoder_decode(self._h, out_ptr, out_cap, flags, recs)
+        if rc:
+            raise GpuError(rc, "flacgpu_decoder_decode")
+        return recs
+
+
+def decode_many(blobs, device=-1, out="device", verify_md5=True, decoder=None):
+    """Decode many FLAC streams in one GPU call (flacgpu_decoder_scan + flacgpu_decoder_decode).
+
+    Returns (flat, streams): `flat` holds every stream's interleaved int32 samples one after another -- a torch tensor
+    on the GPU for out="device", a numpy array for out="host" -- and `streams` is a list of DecodedStream.  Every record
+    equals what flacgpu_decode_stream gives for that stream alone (a stream without frames is hashed as the empty
+    input: md5_status 1 / 2 instead of 0).  verify_md5=False skips the MD5 (md5_status 3)."""
+    if out not in ("device", "host"):
+        raise ValueError("out must be 'device' or 'host'")
+    if out == "device":
+        import torch
+
+        torch.cuda.init()   # torch's HIP runtime first: initialised after the library's first HIP call it sees no GPU
+    own = decoder is None
+    dec = Decoder(device) if own else decoder
+    try:
+        recs, total = dec.scan(blobs)
+        flags = 0 if verify_md5 else _lib.DECODE_NO_MD5
+        if out == "device":
+            import torch
+
+            dev = dec.device if dec.device >= 0 else torch.cuda.current_device()
+            flat = torch.empty(total, dtype=torch.int32, device=f"cuda:{dev}")
+            torch.cuda.synchronize(dev)
+            dec.decode(flat.data_ptr() if total else None, total, flags | _lib.DECODE_OUT_DEVICE, recs)
+        else:
+            flat = np.empty(total, dtype=np.int32)
+            dec.decode(flat.ctypes.data if total else None, total, flags, recs)
+    finally:
+        if own:
+            dec.close()
+    streams = []
+    for i in range(len(blobs)):
+        r = recs[i]
+        info = _lib.StreamInfo()
+        C.memmove(C.byref(info), C.byref(r.info), C.sizeof(info))
+        pcm = None
+        if r.rc == 0:
+            ch = max(info.channels, 1)
+            pcm = flat[r.out_offset:r.out_offset + info.decoded_samples * ch].reshape(-1, ch)
+        streams.append(DecodedStream(r.rc, info, r.out_offset, pcm))
+    return flat, streams
+
+
 def host_pack_frames(sample_rate, bits_per_sample, channels, first_frame_number, n_frames,
                      row_stride, plans, subs, rows, threads=1):
     """Host bit-packing of an analysed batch (flacenc_pack_frames); returns (bytes, offsets)."""

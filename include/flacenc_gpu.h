@@ -508,6 +508,34 @@ typedef struct {
 int flacgpu_decode_stream(const uint8_t *data, size_t len, int device, int32_t *out, size_t out_cap_samples,
                           flacgpu_stream_info *info);
 
+/* ---- batch decoder: many FLAC streams in one call, into host or device memory -------------------------------------
+ * The same result as flacgpu_decode_stream for every stream (rc, every field of `info`, the samples), for any bytes,
+ * with frame discovery, decoding, the CRC-16 check and the MD5 on the device.  One exception: a stream without frames
+ * is hashed as the empty input (md5_status 1 when STREAMINFO holds the MD5 of nothing, 2 when it holds zeros), where
+ * flacgpu_decode_stream returns before hashing (md5_status 0).  The samples of a frame that does not decode are
+ * undefined in both.  A handle keeps its device buffers and pinned staging between calls; it is not thread-safe.
+ *   scan    parses the metadata on the host, uploads every stream's frames in one copy and finds the frames on the
+ *           device; fills rc, info (all but bad_crc16 and the MD5 fields, and bad_frames only for the scan), out_offset,
+ *           and *total_samples = the int32 count `out` must hold.  The inputs may be freed after return.
+ *   decode  decodes the scanned batch into `out`: device memory of the decoder's device with FLACGPU_DECODE_OUT_DEVICE,
+ *           else host memory.  Every stream's record is written in full.  Synchronous.  A whole-call failure (HIP
+ *           error, out of memory, FLACGPU_ERR_BUFFER_TOO_SMALL) writes nothing past out_cap_samples. */
+#define FLACGPU_DECODE_OUT_DEVICE 1u
+#define FLACGPU_DECODE_NO_MD5 2u   /* md5_status 3: not checked */
+typedef struct flacgpu_decoder flacgpu_decoder;
+typedef struct {
+    int32_t rc;                 /* what flacgpu_decode_stream returns for this stream alone */
+    uint32_t reserved;
+    uint64_t out_offset;        /* first int32 of this stream in `out` (interleaved samples) */
+    flacgpu_stream_info info;
+} flacgpu_decoded_stream;
+int flacgpu_decoder_create(int device, flacgpu_decoder **out);
+void flacgpu_decoder_destroy(flacgpu_decoder *d);
+int flacgpu_decoder_scan(flacgpu_decoder *d, const uint8_t *const *data, const size_t *len, uint32_t n_streams,
+                         flacgpu_decoded_stream *streams, uint64_t *total_samples);
+int flacgpu_decoder_decode(flacgpu_decoder *d, int32_t *out, size_t out_cap_samples, uint32_t flags,
+                           flacgpu_decoded_stream *streams);
+
 /* EXPERIMENT, not on the product path: recomputes the autocorrelation of the last analysed
  * batch on the f64 matrix cores (v_mfma_f64_16x16x4_f64, block-Gram form), times that kernel,
  * reruns Levinson/quantisation on it and reports how many candidates' quantised LPC parameters

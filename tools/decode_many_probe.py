@@ -1,0 +1,203 @@
+#!/usr/bin/env python3
+"""Wall times of the batch decoder (flacgpu_decoder_scan + flacgpu_decoder_decode) on three workloads, against a loop
+over flacgpu_decode_stream and the oracle's CPU decoder on one core; writes profiles/r07_decode_many.json.
+
+    python tools/decode_many_probe.py [--workloads clips,tracks,hour] [--out FILE] [--reps 3]
+    python tools/decode_many_probe.py --merge-stats kernel_stats.csv --out FILE   (adds one rocprofv3 --stats run)
+
+Workloads (default options of FlacSampleWriter; a few distinct streams repeated to the batch size -- the decoder
+does not see that they repeat):
+    clips   1024 clips of 10 s, 16 kHz mono 16-bit
+    tracks  256 tracks of 3 min, 44.1 kHz stereo 16-bit
+    hour    one stream of 1 h, 48 kHz stereo 24-bit
+"new" wall time: host bytes (a list of Python bytes) to interleaved int32 in HBM (a torch tensor), the handle warm
+(buffers already grown), median of --reps.  "loop": flacgpu_decode_stream per stream into host memory (its only
+output).  "oracle": orc_decode_stream on one core over the first streams until --oracle-seconds have passed, scaled
+to the workload by decoded samples."""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+WORKLOADS = {   # name: (streams, distinct, seconds, rate, channels, bps)
+    "clips": (1024, 16, 10, 16000, 1, 16),
+    "tracks": (256, 4, 180, 44100, 2, 16),
+    "hour": (1, 1, 3600, 48000, 2, 24),
+}
+COPY_TBPS = 6.3   # measured device copy rate
+
+
+def make_blobs(name):
+    from _pcm import synth_fast
+    from flac_codec_amd.encode import FlacSampleWriter, Options
+
+    n, distinct, secs, rate, ch, bps = WORKLOADS[name]
+    uniq = []
+    for k in range(distinct):
+        pcm = synth_fast(900 + k, ch, bps, secs * rate)
+        w = FlacSampleWriter(None, Options.default(), rate, bps, ch, pcm.size)
+        w.write(pcm)
+        w.finalize()
+        uniq.append(w.getvalue())
+        w.close()
+        del pcm
+    return [uniq[i % distinct] for i in range(n)]
+
+
+def time_new(blobs, reps, md5):
+    import torch
+
+    from flac_codec_amd import _lib
+    from flac_codec_amd.gpu import Decoder
+
+    dec = Decoder(0)
+    flags = _lib.DECODE_OUT_DEVICE | (0 if md5 else _lib.DECODE_NO_MD5)
+    recs, total = dec.scan(blobs)
+    out = torch.empty(total, dtype=torch.int32, device="cuda:0")
+    torch.cuda.synchronize()
+    dec.decode(out.data_ptr(), total, flags, recs)   # warm: buffers grown, code loaded
+    times, scan_t = [], []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        recs, total = dec.scan(blobs)
+        t1 = time.perf_counter()
+        dec.decode(out.data_ptr(), total, flags, recs)
+        t2 = time.perf_counter()
+        times.append(t2 - t0)
+        scan_t.append(t1 - t0)
+    bad = sum(1 for r in recs if r.rc or r.info.bad_frames or r.info.bad_crc16 or (md5 and r.info.md5_status != 1))
+    dec.close()
+    del out
+    return float(np.median(times)), float(np.median(scan_t)), int(total), bad
+
+
+def time_loop(blobs):
+    from flac_codec_amd import _lib
+
+    L = _lib.lib()
+    info = _lib.StreamInfo()
+    buf = None
+    t0 = time.perf_counter()
+    for b in blobs:
+        rc = L.flacgpu_decode_stream(b, len(b), 0, None, 0, C.byref(info))
+        need = info.decoded_samples * info.channels
+        if buf is None or buf.size < need:
+            buf = np.empty(need, np.int32)
+        rc |= L.flacgpu_decode_stream(b, len(b), 0, buf.ctypes.data_as(C.POINTER(C.c_int32)), buf.size, C.byref(info))
+        assert rc == 0 and info.md5_status == 1
+    return time.perf_counter() - t0
+
+
+def time_loop_single_call(blobs):
+    """one flacgpu_decode_stream call per stream (the size known beforehand), the loop's lower bound"""
+    from flac_codec_amd import _lib
+
+    L = _lib.lib()
+    info = _lib.StreamInfo()
+    sizes = []
+    for b in blobs[:1]:
+        L.flacgpu_decode_stream(b, len(b), 0, None, 0, C.byref(info))
+        sizes.append(info.decoded_samples * info.channels)
+    buf = np.empty(max(sizes) * 2, np.int32)
+    t0 = time.perf_counter()
+    for b in blobs:
+        rc = L.flacgpu_decode_stream(b, len(b), 0, buf.ctypes.data_as(C.POINTER(C.c_int32)), buf.size, C.byref(info))
+        assert rc == 0
+    return time.perf_counter() - t0
+
+
+def time_oracle(blobs, budget):
+    import _oracle as orc
+
+    t0 = time.perf_counter()
+    done, samples = 0, 0
+    for b in blobs:
+        rc, out, _ = orc.decode_stream(b)
+        assert rc == 0
+        done += 1
+        samples += out.size
+        if time.perf_counter() - t0 > budget:
+            break
+    return time.perf_counter() - t0, done, samples
+
+
+def run(args):
+    res = {"tool": "tools/decode_many_probe.py", "copy_rate_TBps": COPY_TBPS, "workloads": {}}
+    if os.path.exists(args.out):
+        with open(args.out) as f:
+            res = json.load(f)
+    for name in args.workloads.split(","):
+        t0 = time.perf_counter()
+        blobs = make_blobs(name)
+        n, _, secs, rate, ch, bps = WORKLOADS[name]
+        rec = {"streams": n, "seconds_each": secs, "rate": rate, "channels": ch, "bps": bps,
+               "flac_bytes": int(sum(len(b) for b in blobs)), "encode_s": time.perf_counter() - t0}
+        w_md5, scan_md5, total, bad = time_new(blobs, args.reps, True)
+        w_nomd5, scan_nomd5, _, bad2 = time_new(blobs, args.reps, False)
+        rec.update({"samples_interleaved": total, "new_md5_s": w_md5, "new_no_md5_s": w_nomd5,
+                    "new_scan_s": scan_md5, "streams_not_clean": bad + bad2})
+        rec["loop_decode_stream_s"] = time_loop(blobs)
+        rec["loop_single_call_s"] = time_loop_single_call(blobs)
+        ot, odone, osamp = time_oracle(blobs, args.oracle_seconds)
+        rec["oracle_one_core"] = {"streams_decoded": odone, "seconds": ot, "samples": osamp,
+                                  "scaled_to_workload_s": ot * total / max(osamp, 1)}
+        rec["speedup_vs_loop_md5"] = rec["loop_decode_stream_s"] / w_md5
+        res["workloads"][name] = rec
+        print(json.dumps({name: rec}), flush=True)
+        del blobs
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+
+
+def merge_stats(args):
+    """kernel_stats.csv of one rocprofv3 --kernel-trace --stats run (of --workloads, --reps 1) into the record"""
+    import csv
+
+    with open(args.out) as f:
+        res = json.load(f)
+    rows = {}
+    with open(args.merge_stats) as f:
+        for r in csv.DictReader(f):
+            rows[r["Name"]] = {"calls": int(r["Calls"]), "total_ms": float(r["TotalDurationNs"]) / 1e6,
+                               "avg_ms": float(r["AverageNs"]) / 1e6}
+    mine = {k: v for k, v in rows.items() if any(s in k for s in ("k_scan_", "k_link", "k_decode_many", "k_frame_crc",
+                                                                   "k_finish_many", "k_md5_many"))}
+    res.setdefault("kernel_stats", {})[args.stats_label] = mine
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(mine, indent=1))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--workloads", default="clips,tracks,hour")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r07_decode_many.json"))
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--oracle-seconds", type=float, default=20.0)
+    ap.add_argument("--merge-stats")
+    ap.add_argument("--stats-label", default="run")
+    ap.add_argument("--kernels-only", action="store_true", help="one warm decode per workload (for rocprofv3)")
+    args = ap.parse_args()
+    if args.merge_stats:
+        return merge_stats(args)
+    import torch
+
+    torch.cuda.init()   # before the library's first HIP call (else torch sees no GPU)
+    if args.kernels_only:
+        for name in args.workloads.split(","):   # (the hour's MD5 alone runs > 1 min: left to the timed run)
+            blobs = make_blobs(name)
+            time_new(blobs, 1, name != "hour")
+        return
+    run(args)
+
+
+if __name__ == "__main__":
+    main()
