@@ -42,7 +42,7 @@ bool launch_cand64_direct(const Params &p, const Knobs &kn, uint32_t B, uint32_t
                                                          : resident_workgroups(k_cand64p<64, 16, true, true>, res_lpc);
         const uint32_t cap = kn.cand_grid ? kn.cand_grid : resident;
         const uint32_t grid = blocks < cap ? blocks : cap;   // every resident slot of the chip, and no more (a persistent kernel)
-        if (!lpc)   // no k_autocorr4 / k_lpc before this kernel: it derives the candidate info itself
+        if (!lpc)   // no k_autocorr4 / k_lpc_u before this kernel: it derives the candidate info itself
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cand64p<64, 16, true, true, true>), dim3(grid), dim3(WG), 0, st, p);
         else if (p.max_lpc_order > 16)
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cand64p<64, 32, true, true>), dim3(grid), dim3(WG), 0, st, p);

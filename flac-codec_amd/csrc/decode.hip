@@ -15,8 +15,9 @@ namespace flacgpu_k {
 // CU's address path (lines per instruction x waves per CU), not the SIMD: measured on 4096 / 8192
 // / 32768 stereo frames, 32-lane waves win over 64 (fewer lines per instruction) and over 16 or 8
 // (fewer waves per CU): 1.17 / 1.44 / 2.93 ms.
-void launch_decode(uint32_t mo, uint32_t units, uint32_t lanes, const Params &pd, const PackParams &q,
-                   int32_t *decoded, uint32_t *verify_counts, hipStream_t st) {
+void launch_decode(uint32_t mo, uint32_t units, const Params &pd, const PackParams &q, int32_t *decoded,
+                   uint32_t *verify_counts, hipStream_t st) {
+    const uint32_t lanes = 32;
     const dim3 grid((units + lanes - 1) / lanes), block(lanes);
     // FIXED needs 4; the ring is also the store batch
     if (mo <= 8) hipLaunchKernelGGL(k_decode<8>, grid, block, 0, st, pd, q, decoded, verify_counts);

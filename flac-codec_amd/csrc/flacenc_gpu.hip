@@ -14,9 +14,9 @@
 //   K0    k_deinterleave2 / k_deinterleave_n / k_deinterleave + k_orbits, k_candinfo (k0_split.inc)
 //           audio.rs:190-199 Frame::fill_from_samples; encode.rs:2870-2898 wasted bits / all-zero
 //   K1    k_stereo_stats (generic_analysis.inc)  encode.rs:2463-2674 correlate_channels (fast mode)
-//   K3    k_autocorr3 / k_autocorr3_deep / k_autocorr2 (autocorr.inc)
+//   K3    k_autocorr4 / k_autocorr4_deep / k_autocorr2 (autocorr.inc)
 //           encode.rs:1785-1801 Window::apply + 3478-3501 autocorrelate (exact summation order)
-//   K4    k_lpc_u / k_lpc (lpc.inc)  encode.rs:3536-3580 lp_coefficients, 3656-3702
+//   K4    k_lpc_u, or the tail of k_autocorr4 (lpc.inc)  encode.rs:3536-3580 lp_coefficients, 3656-3702
 //           compute_best_order, 3334-3401 quantize
 //   K2+K5 k_cand64 (wave_cand.inc): FIXED + LPC + Rice search + choice of one candidate per wave
 //           encode.rs:2849-2898, 3020-3088, 3174-3203, 3747-3962, 2929-2979;
@@ -74,26 +74,13 @@ Knobs read_knobs() {
     k.no_direct = on("FLACGPU_NO_DIRECT");
     k.no_cand_pair = on("FLACGPU_NO_CAND_PAIR");
     k.force_fir_check = on("FLACGPU_FIR_CHECK");
-    k.no_sub64 = on("FLACGPU_NO_SUB64");
-    k.no_lpc_fuse = on("FLACGPU_NO_LPC_FUSE");
     k.no_xpose = on("FLACGPU_NO_XPOSE");
-    k.no_chunk = on("FLACGPU_NO_CHUNK");
     k.no_ac_fma = on("FLACGPU_NO_AC_FMA");
-    k.lpc_fuse_deep = on("FLACGPU_LPC_FUSE_DEEP");
-    k.upload_by_kernel = on("FLACGPU_UPLOAD_KERNEL");
     k.no_hand = on("FLACGPU_NO_HAND");   // A/B: k_frame64 fetches the samples and runs the FIR again (Params::hand_meta off)
     k.no_direct_short = on("FLACGPU_NO_DIRECT_SHORT");   // A/B: the shorter wave block lengths through K0 + k_cand64
-    k.no_fast = on("FLACGPU_NO_FAST");
     k.no_w64 = on("FLACGPU_NO_W64");
-    k.no_persist = on("FLACGPU_NO_PERSIST");
-    k.no_ac3 = on("FLACGPU_NO_AC3");
-    k.ac_private = on("FLACGPU_AC_PRIVATE");
     k.no_fused_pack = on("FLACGPU_NO_FUSED_PACK");
     k.no_frame64 = on("FLACGPU_NO_FRAME64");
-    k.no_fork = on("FLACGPU_NO_FORK");
-    k.lpc_dyn = on("FLACGPU_LPC_DYN");
-    k.ac_eight_waves = on("FLACGPU_AC_WAVES8");
-    k.cand_persist_n = on("FLACGPU_CAND_PERSIST_N");
     k.early_download = on("FLACGPU_EARLY_DOWNLOAD");
     if (const char *e = getenv("FLACGPU_CAND_GRID")) k.cand_grid = (uint32_t)atoi(e);
     // A/B: Params::defer_fixed (0 never, 1 by the estimate, 2 whenever LPC parameters exist) and its margin in 1/16 bit per
@@ -105,7 +92,6 @@ Knobs read_knobs() {
         k.experiment_mfma_ac = on("FLACGPU_EXPERIMENT_MFMA_AC");
         if (const char *e = getenv("FLACGPU_TIE_BAND")) { k.has_tie_band = true; k.tie_band = atof(e); }
         if (const char *e = getenv("FLACGPU_TIE_PERTURB")) { k.has_tie_perturb = true; k.tie_perturb = atof(e); }
-        if (const char *e = getenv("FLACGPU_DECODE_LANES")) k.decode_lanes = (uint32_t)atoi(e);
         if (const char *e = getenv("FLACGPU_FIR_SUSPECT_BITS")) k.fir_suspect_bits = (uint32_t)atoi(e);
     }
     return k;
@@ -141,10 +127,9 @@ struct flacgpu_ctx {
     uint32_t *d_stats_base = nullptr;   // Params::turn_counter words in front of d_stats (zeroed by the same memset)
     uint32_t *d_stats = nullptr;
     uint32_t *d_orbits = nullptr;   // OR of all samples per (frame, candidate); = d_stats + 4
-    uint32_t *d_ties = nullptr;     // candidates whose LPC order estimates tie (k_lpc), [F * NC]
+    uint32_t *d_ties = nullptr;     // candidates whose LPC order estimates tie (K4: note_order_tie), [F * NC]
     double tie_band = 1e-9, tie_perturb = 0.0;
     Knobs knobs;                  // the FLACGPU_* environment, read once at flacgpu_create
-    const uint8_t *packed_src = nullptr;   // upload by kernel (Knobs::upload_by_kernel): K0 reads the caller's pinned PCM itself
     // a batch made of SEGMENTS (flacgpu_encode_segments*): per-frame frame numbers and PCM addresses on the device, their
     // pinned staging copy, and the segments themselves (ensure_planar walks them)
     uint64_t *d_seg_fn = nullptr, *h_seg = nullptr;
@@ -374,8 +359,7 @@ bool packed_k0_supported(uint32_t block_size, uint32_t channels, uint32_t bytes)
 template <int C>
 void launch_k0_packed_c(flacgpu_ctx *c, uint32_t bytes, const dim3 &grid, uint32_t n_frames, uint32_t last_len,
                         uint32_t f0, hipStream_t st) {
-    const uint32_t *in = c->packed_src ? reinterpret_cast<const uint32_t *>(c->packed_src)
-                                       : reinterpret_cast<const uint32_t *>(c->d_in);
+    const uint32_t *in = reinterpret_cast<const uint32_t *>(c->d_in);
     const uint32_t B = c->opts.block_size;
     unsigned long long *abs = (C == 2 && c->d_abs && c->ncand == 4) ? c->d_abs : nullptr;   // (zeroed by the caller)
     switch (bytes) {
@@ -537,7 +521,7 @@ static int create_impl(flacgpu_ctx *c, const flacgpu_options *o) {
     ALLOC(c->d_frame_off, F + 1);
     ALLOC(c->d_tile_sync, F / 1024 + 2);
     HIP_TRY(hipMemset(c->d_tile_sync, 0, sizeof(unsigned long long) * (F / 1024 + 2)));
-    if (channels >= 5 && !read_knobs().no_sub64) ALLOC(c->d_edges, F * channels);   // (c->knobs is filled further down)
+    if (channels >= 5) ALLOC(c->d_edges, F * channels);
     if (B > LDS_BLOCK_LIMIT) ALLOC(c->d_big, F * NC * (size_t)big_scratch_ints((uint32_t)B));
     ALLOC(c->d_ties, F * NC);
     if (c->stereo4 && !o->exhaustive_channel_correlation) ALLOC(c->d_abs, F * 4);
@@ -698,8 +682,7 @@ static int resolve_stream(flacgpu_ctx *c, void *stream, hipStream_t *out) {
 // Params::planar).
 static bool direct_input_ok(const flacgpu_ctx *c, const Params &p, uint32_t last_len) {
     const Knobs &kn = c->knobs;
-    const bool off = kn.no_direct || kn.no_fast || kn.no_w64 || kn.no_persist || kn.no_ac3 || kn.ac_private ||
-                     kn.experiment_mfma_ac || kn.no_fused_pack || kn.no_frame64;
+    const bool off = kn.no_direct || kn.no_w64 || kn.experiment_mfma_ac || kn.no_fused_pack || kn.no_frame64;
     const uint32_t B = p.block_size;
     const bool block_ok = B == FN || (wave_block_size(B) && p.max_lpc_order <= 16 && !kn.no_direct_short);
     return !off && c->stereo4 && c->channels == 2 && c->bps <= 24 && block_ok && last_len == B &&
@@ -713,8 +696,7 @@ static bool split_input_ok(const flacgpu_ctx *c, const Params &p, uint32_t last_
     const uint32_t B = p.block_size;
     return !c->stereo4 && c->channels >= 1 && c->ncand == c->channels && p.max_lpc_order >= 1 && p.max_lpc_order <= 16 && B == FN &&
            last_len == B && p.ac_split != 2 && (c->bps <= 25u) && p.max_po <= 6 &&
-           !(c->knobs.no_direct || c->knobs.no_fast || c->knobs.no_w64 || c->knobs.no_ac3 || c->knobs.ac_private ||
-             c->knobs.experiment_mfma_ac);
+           !(c->knobs.no_direct || c->knobs.no_w64 || c->knobs.experiment_mfma_ac);
 }
 
 // k_layout's tiles find each other through PackParams::tile_sync, whose words carry the launch's 24-bit epoch: a new
@@ -915,7 +897,7 @@ static int analyze_impl(flacgpu_ctx *c, const int32_t *d_pcm, int layout, uint32
                            c->abs_valid ? c->d_abs : nullptr);
     // blocks of exactly 4096 samples take the register-resident kernels; anything else (other
     // block sizes, a short last frame, candidates wider than 25 bits) the generic LDS ones
-    const bool narrow = (c->bps + (c->stereo4 ? 1u : 0u) <= 25u) && !c->knobs.no_fast;
+    const bool narrow = c->bps + (c->stereo4 ? 1u : 0u) <= 25u;
     // wave-per-candidate kernel (FIXED + LPC analysis of a candidate in one wave, after the LPC
     // parameters are known): block lengths 64 x {16, 18, 32, 36, 64}, LPC order <= 16
     const bool w64 = narrow && wave_block_size(B) && (p.max_lpc_order <= 16 || B == FN) && p.max_po <= 6 &&
@@ -938,7 +920,7 @@ static int analyze_impl(flacgpu_ctx *c, const int32_t *d_pcm, int layout, uint32
     // Otherwise the FIXED analysis and the autocorrelation -> Levinson chain, which only share
     // their input, run concurrently on two HIP streams (fork after k_candinfo, join before
     // k_fir).  With per-kernel timing enabled everything is serialised on one stream.
-    const bool fork = lpc && !c->timing && !c->knobs.no_fork && !(w64 && pg.fcount == 0);
+    const bool fork = lpc && !c->timing && !(w64 && pg.fcount == 0);
     hipStream_t sf = fork ? c->aux_stream : st;
     if (fork) {
         HIP_TRY(hipEventRecord(c->ev_fork, st));
@@ -964,7 +946,7 @@ static int analyze_impl(flacgpu_ctx *c, const int32_t *d_pcm, int layout, uint32
                 return FLACGPU_ERR_UNSUPPORTED;
             }
             begin(4);
-            launch_lpc(p, c->knobs, (ncb + 63) / 64, st);
+            launch_lpc(p, (ncb + 63) / 64, st);
         }
         if (fork) HIP_TRY(hipStreamWaitEvent(st, c->ev_join, 0));
         if (pg.fcount) {
@@ -1018,7 +1000,7 @@ static int analyze_impl(flacgpu_ctx *c, const int32_t *d_pcm, int layout, uint32
 static int pack_impl(flacgpu_ctx *c, uint64_t first_frame_number, uint32_t sample_rate, hipStream_t st,
                      hipEvent_t after_layout);
 
-// The candidates k_lpc listed (two best order estimates closer than the device's log() can be trusted
+// The candidates K4 listed (two best order estimates closer than the device's log() can be trusted
 // to separate) are re-decided here with the HOST's libm -- Levinson, order choice and quantisation
 // from the device's exact autocorrelation (host/lpc_host.cpp) --, their parameters replaced, and the
 // candidate stage, the assignment decision and (when done before) the frame assembly run again, so
@@ -1200,7 +1182,7 @@ static int pack_impl(flacgpu_ctx *c, uint64_t first_frame_number, uint32_t sampl
     // through k_emit (residual rows) -> k_pack (one workgroup per subframe, zero-filled output,
     // atomic OR at shared words) -> k_crc
     const uint32_t B = p.block_size;
-    const bool narrow = (c->bps + (c->stereo4 ? 1u : 0u) <= 25u) && !c->knobs.no_fast;
+    const bool narrow = c->bps + (c->stereo4 ? 1u : 0u) <= 25u;
     uint32_t fbw = frame_fb_words(p.channels, c->bps, B);
     if (c->stereo4 && p.exhaustive) fbw = std::min(fbw, frame_fb_words_exhaustive_stereo(c->bps, B));
     // wave per subframe: block lengths 64 x {16, 18, 32, 36, 64}; orders 17..32 and 5..8 channels
@@ -1301,10 +1283,9 @@ int flacgpu_set_tuning(flacgpu_ctx *c, int key, int value) {
 static uint32_t chunk_frames(const flacgpu_ctx *c, const int32_t *d_pcm, int layout, uint32_t n_frames, uint32_t last_len) {
     const uint32_t B = c->opts.block_size;
     const Knobs &kn = c->knobs;
-    if (!c->chunk_samples || kn.no_chunk || c->timing || c->lag_split == 2 || B != FN || last_len != B || layout != FLACGPU_LAYOUT_INTERLEAVED) return 0;
+    if (!c->chunk_samples || c->timing || c->lag_split == 2 || B != FN || last_len != B || layout != FLACGPU_LAYOUT_INTERLEAVED) return 0;
     if (c->chunk_auto && !c->stereo4) return 0;   // independent channels: only on request (config 4: no gain measured)
-    if (((uintptr_t)d_pcm & 15u) || kn.no_direct || kn.no_fast || kn.no_w64 || kn.no_ac3 || kn.ac_private || kn.experiment_mfma_ac ||
-        kn.no_lpc_fuse || kn.no_fused_pack || kn.no_frame64 || kn.no_persist)
+    if (((uintptr_t)d_pcm & 15u) || kn.no_direct || kn.no_w64 || kn.experiment_mfma_ac || kn.no_fused_pack || kn.no_frame64)
         return 0;
     const uint32_t lo = c->opts.max_lpc_order;
     if (lo < 1 || lo > 16 || c->opts.max_partition_order > 6 || c->bps + (c->stereo4 ? 1u : 0u) > 25u) return 0;
@@ -1338,7 +1319,7 @@ int flacgpu_encode_device(flacgpu_ctx *c, const int32_t *d_pcm, int layout, uint
         (c->bps + (c->stereo4 ? 1u : 0u) <= 25u) &&
         (c->opts.max_lpc_order <= 16 || (B == FN && c->channels <= 4)) &&
         c->opts.max_partition_order <= 6 && (c->channels <= 4 || B == FN) && (layout == 0 || layout == 1) &&
-        (size_t)fbw * sizeof(int32_t) <= 150 * 1024 && !c->timing && !c->knobs.no_fast &&
+        (size_t)fbw * sizeof(int32_t) <= 150 * 1024 && !c->timing &&
         !c->knobs.no_w64 && !c->knobs.no_fused_pack && !c->knobs.no_frame64 &&
         c->two_ranges;
     hipStream_t st0;
@@ -1402,7 +1383,7 @@ int flacgpu_encode_device(flacgpu_ctx *c, const int32_t *d_pcm, int layout, uint
         hipLaunchKernelGGL(k_candinfo, dim3((ncb + WG - 1) / WG), dim3(WG), 0, st, r, c->d_orbits, (const unsigned long long *)nullptr);
         if (lpc) {
             if (!dispatch_autocorr(H, r, c->knobs, r.f0, r.fcount, B, c->d_window_full, st))
-                launch_lpc(r, c->knobs, (ncb + 63) / 64, st);
+                launch_lpc(r, (ncb + 63) / 64, st);
         }
         if (!launch_cand64(r, c->knobs, B, (ncb + 3) / 4, st)) hipLaunchKernelGGL(k_decide, dim3(r.fcount), dim3(64), 0, st, r);
         // frame assembly of this range; the second range's offsets continue from the first's
@@ -2066,22 +2047,12 @@ static int packed_async_impl(flacgpu_ctx *c, const uint8_t *pcm_le, uint32_t byt
     auto since = [&] { return std::chrono::duration<double, std::milli>(clk::now() - tr0).count(); };
     const size_t B = c->opts.block_size, C = c->channels;
     const size_t bytes = ((size_t)(n_frames - 1) * B + last_len) * C * bytes_per_sample;
-    // The upward leg.  Default: a copy engine (hipMemcpyAsync).  FLACGPU_UPLOAD_KERNEL=1 (A/B, pinned memory only): the
-    // bytes cross the link as kernel loads -- K0 reads the stream-width samples straight out of the caller's pinned
-    // buffer; int32 samples take a copy kernel into d_in
-    c->packed_src = nullptr;
-    if (c->knobs.upload_by_kernel && bytes_per_sample != 4) {
-        c->packed_src = pcm_le;
-    } else if (c->knobs.upload_by_kernel && bytes % 16 == 0) {   // (whole 16-byte pieces only: no read past the caller's buffer)
-        hipLaunchKernelGGL(k_copy16, dim3(1024), dim3(WG), 0, st, reinterpret_cast<const uint4 *>(pcm_le),
-                           reinterpret_cast<uint4 *>(c->d_in), bytes / 16);
-    } else {
-        HIP_TRY(hipMemcpyAsync(c->d_in, pcm_le, bytes, hipMemcpyHostToDevice, st));
-    }
+    // The upward leg: a copy engine.  (The bytes crossing the link as kernel loads instead -- K0 or a copy kernel reading the
+    // caller's pinned buffer -- was measured, profiles/r04_pipeline_ab.json, and removed; flacgpu_link_probe still times both ways.)
+    HIP_TRY(hipMemcpyAsync(c->d_in, pcm_le, bytes, hipMemcpyHostToDevice, st));
     if (trace) tr_up = since();
     const int arc = analyze_impl(c, c->d_in, FLACGPU_LAYOUT_INTERLEAVED, n_frames, last_len, st,
                                  bytes_per_sample == 4 ? 0 : bytes_per_sample);
-    c->packed_src = nullptr;
     if (arc) return arc;
     if (trace) tr_an = since();
     // the frame sizes leave the device as soon as k_layout has run (second stream), so that the host
@@ -2217,7 +2188,7 @@ int flacgpu_experiment_mfma_autocorr(flacgpu_ctx *c, float *kernel_ms, uint32_t 
         launch_autocorr_mfma(p, (uint32_t)((nc + 3) / 4), p.block_size, c->d_window_full, c->d_ac, st);
         if (it == 1) (void)hipEventRecord(c->ev[1], st);
     }
-    launch_lpc(p, c->knobs, (uint32_t)((nc + 63) / 64), st);   // the product's own K4 (no scratch, unlike the generic k_lpc)
+    launch_lpc(p, (uint32_t)((nc + 63) / 64), st);   // the product's own K4
     HIP_TRY(hipStreamSynchronize(st));
     float ms = 0.f;
     (void)hipEventElapsedTime(&ms, c->ev[0], c->ev[1]);
@@ -2291,11 +2262,7 @@ int flacgpu_verify_device(flacgpu_ctx *c, uint32_t sample_rate, uint64_t first_f
     HIP_TRY(hipEventRecord(c->ev_join, c->aux_stream));
     {
         const uint32_t units = p.n_frames * p.channels;
-        uint32_t lanes = 32;
-        if (const uint32_t v = c->knobs.decode_lanes) {  // experiment knob
-            if (v == 4 || v == 8 || v == 16 || v == 32 || v == 64) lanes = v;
-        }
-        launch_decode(c->opts.max_lpc_order, units, lanes, pd, q, c->d_decoded, c->d_verify, st);
+        launch_decode(c->opts.max_lpc_order, units, pd, q, c->d_decoded, c->d_verify, st);
         launch_decode_finish(pd, c->d_decoded, expect, c->d_verify, st);
     }
     HIP_TRY(hipStreamWaitEvent(st, c->ev_join, 0));

@@ -1,4 +1,4 @@
-// autocorr.inc -- K3: exact autocorrelation (wave-private tiles, deep history, generic, MFMA experiment).
+// autocorr.inc -- K3: exact autocorrelation (shared f64 tiles, deep history, generic, MFMA experiment).
 // Part of flacenc_gpu.hip (one translation unit; included inside its anonymous namespace).
 
 // ---------------------------------------------------------------------------------
@@ -11,21 +11,9 @@
 // (independent => full f64 pipeline with one wave per SIMD).  blockIdx.y selects the lag
 // group so the ring indexing stays static.  The window value is wave-uniform (scalar load).
 // H lags are computed (H = max order + 1 rounded up to a multiple of 4); extra lags are
-// simply not read by k_lpc.
+// simply not read by K4.
 // ---------------------------------------------------------------------------------
 
-// ---------------------------------------------------------------------------------
-// K3 for stereo frames (L, R, mid, side candidates) whose length is a multiple of 32, lags <= 16,
-// samples <= 24 bits: every wave is self-contained -- no workgroup barrier at all.
-//   lane = candidate (16 frames x 4 candidates per wave), wave pairs/quads split the lags.
-//   The wave stages the raw L/R rows of its 16 frames through a private, double-buffered LDS
-//   tile (32 rows x 32 samples), each lane reads its two source rows 16 samples at a time
-//   (ds_read_b128), forms (a + cb * b) >> sh (one v_mad_i32_i24 + one shift covers L, R,
-//   mid and side), converts to f64, multiplies by the window (wave-uniform, scalar loads) and
-//   accumulates its lags strictly in sample order (the reference's left fold per lag,
-//   encode.rs:3403-3413).  History is the previous 16-sample block, kept in registers and
-//   statically indexed (the loop is unrolled over two blocks).
-// ---------------------------------------------------------------------------------
 // A workgroup that is BEHIND gets the SIMD: a wave's issue priority falls with the quarter of the block it has reached.  (The
 // SIMD issues oldest wave first: left alone, the first-launched of a CU's two workgroups runs ahead and the other one ends
 // alone, one wave per SIMD.)
@@ -38,8 +26,6 @@ __device__ __forceinline__ void ac4_progress_prio(uint32_t t, uint32_t ntiles) {
         else __builtin_amdgcn_s_setprio(0);
     }
 }
-constexpr int AC3_TS = 32;            // samples per tile
-constexpr int AC3_LD = AC3_TS + 4;    // int row stride: 16-byte aligned, rows spread over banks
 
 // FMA: one v_fma_f64 per term instead of a multiply and an add -- ONLY where both factors are integers below 2^26 (samples
 // under a window value of exactly 1.0: the flat middle of a Tukey window): their product is then exact, so
@@ -82,182 +68,6 @@ __device__ __forceinline__ void ac3_block(const double (&w)[16], const double (&
             acc[k] = acc[k] + prod[k];
         }
         __builtin_amdgcn_sched_barrier(0);
-    }
-}
-
-// raw operands of one 16-sample block: the lane's two source rows + the window slice
-struct Ac3Raw {
-    int4 a[4], b[4];
-    double2 w[8];
-};
-__device__ __forceinline__ void ac3_load(const int32_t *ra, const int32_t *rb, const double *wt,
-                                         uint32_t col, Ac3Raw &r) {
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        r.a[q] = *reinterpret_cast<const int4 *>(ra + col + 4 * q);
-        r.b[q] = *reinterpret_cast<const int4 *>(rb + col + 4 * q);
-    }
-#pragma unroll
-    for (int q = 0; q < 8; q++) r.w[q] = *reinterpret_cast<const double2 *>(wt + col + 2 * q);  // broadcast
-}
-__device__ __forceinline__ void ac3_convert(const Ac3Raw &r, int32_t cb, uint32_t sh, double (&w)[16]) {
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const int32_t a[4] = {r.a[q].x, r.a[q].y, r.a[q].z, r.a[q].w};
-        const int32_t b[4] = {r.b[q].x, r.b[q].y, r.b[q].z, r.b[q].w};
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-            const int s = 4 * q + e;
-            const int32_t v = (__mul24(b[e], cb) + a[e]) >> sh;
-            const double win = (s & 1) ? r.w[s >> 1].y : r.w[s >> 1].x;
-            w[s] = (double)v * win;
-        }
-    }
-}
-
-
-// per-lane constants + staging registers of one wave; ROWS = staged rows per tile (32: the L/R rows
-// of 16 stereo frames, 64: one row per candidate for independent channels)
-template <int ROWS>
-struct Ac3Lane {
-    static constexpr int NIT = ROWS / 8;
-    static constexpr int RAW = ROWS * AC3_LD;       // ints of raw rows per buffer
-    static constexpr int BUF = RAW + 2 * AC3_TS;    // + the window slice (f64)
-    const int32_t *gsrc[NIT];  // global source of this lane's staged int4s (tile 0)
-    const double *wsrc;        // window slice source (2 f64 per lane of each 16-lane group)
-    uint32_t sdst[NIT];        // LDS destinations (ints, within a buffer)
-    uint32_t wdst;
-    uint32_t off_a, off_b;    // LDS offsets of the candidate's two source rows
-    int32_t cb;
-    uint32_t sh;
-    uint32_t ntiles;
-    int4 stage[NIT];
-    double2 wstage;
-};
-template <int ROWS>
-__device__ __forceinline__ void ac3_fetch(Ac3Lane<ROWS> &L, uint32_t t) {
-    t = t < L.ntiles ? t : L.ntiles - 1;
-#pragma unroll
-    for (int it = 0; it < ROWS / 8; it++) L.stage[it] = *reinterpret_cast<const int4 *>(L.gsrc[it] + t * AC3_TS);
-    L.wstage = *reinterpret_cast<const double2 *>(L.wsrc + t * AC3_TS);
-}
-template <int ROWS>
-__device__ __forceinline__ void ac3_commit(const Ac3Lane<ROWS> &L, int32_t *dst) {
-#pragma unroll
-    for (int it = 0; it < ROWS / 8; it++) *reinterpret_cast<int4 *>(dst + L.sdst[it]) = L.stage[it];
-    *reinterpret_cast<double2 *>(dst + L.wdst) = L.wstage;
-}
-__device__ __forceinline__ void ac3_sync() {  // LDS operations of one wave execute in order
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-// Software pipeline per tile of 32 samples (two blocks of 16):
-//   block 0: prefetch block 1's operands from LDS, convert + accumulate block 0
-//   block 1: commit tile t+1 (fetched one whole tile ago) into the other buffer, start the
-//            global fetch of tile t+2, prefetch the next tile's block 0, accumulate block 1
-template <int A, int LG, bool FIRST, int ROWS>
-__device__ __forceinline__ void ac3_tile(Ac3Lane<ROWS> &L, int32_t *tile, uint32_t t, Ac3Raw &r0, Ac3Raw &r1,
-                                         double (&w0)[16], double (&w1)[16], double (&acc)[LG]) {
-    const uint32_t buf = t & 1;
-    constexpr int AC3_RAW = Ac3Lane<ROWS>::RAW, AC3_BUF = Ac3Lane<ROWS>::BUF;
-    int32_t *cur = tile + buf * AC3_BUF, *nxt = tile + (buf ^ 1) * AC3_BUF;
-    ac3_load(cur + L.off_a, cur + L.off_b, reinterpret_cast<const double *>(cur + AC3_RAW), 16, r1);
-    __builtin_amdgcn_sched_barrier(0);
-    ac3_convert(r0, L.cb, L.sh, w0);
-    ac3_block<A, LG, FIRST>(w0, w1, acc);
-    __builtin_amdgcn_sched_barrier(0);
-    ac3_commit(L, nxt);
-    ac3_sync();
-    ac3_fetch(L, t + 2);
-    ac3_load(nxt + L.off_a, nxt + L.off_b, reinterpret_cast<const double *>(nxt + AC3_RAW), 0, r0);
-    __builtin_amdgcn_sched_barrier(0);
-    ac3_convert(r1, L.cb, L.sh, w1);
-    ac3_block<A, LG, false>(w1, w0, acc);
-    __builtin_amdgcn_sched_barrier(0);
-}
-
-// per-lane constants of a wave: which candidate, which staged rows, where to stage from
-template <bool STEREO>
-__device__ __forceinline__ bool ac3_setup(const Params &p, uint32_t frame0, uint32_t nframes, uint32_t n,
-                                          const double *__restrict__ win, uint32_t group,
-                                          Ac3Lane<STEREO ? 32 : 64> &L, uint32_t &frame_out,
-                                          uint32_t &cand_out) {
-    constexpr int ROWS = STEREO ? 32 : 64;
-    constexpr int AC3_RAW = Ac3Lane<ROWS>::RAW;
-    const uint32_t lane = threadIdx.x & 63;
-    const uint32_t total = nframes * p.ncand;            // candidates of this launch
-    const uint32_t cand0 = group * 64;
-    const bool live = cand0 + lane < total;
-    const uint32_t cc = live ? cand0 + lane : total - 1;  // clamped: results of dead lanes are dropped
-    const uint32_t frame = frame0 + cc / p.ncand, cand = cc % p.ncand;
-    frame_out = frame;
-    cand_out = cand;
-    const CandInfo ci = p.cinfo[(size_t)frame * p.ncand + cand];
-    const uint32_t wasted = (ci.active && !ci.is_const) ? ci.wasted : 0;
-    const uint32_t srow = lane >> 3, scol = (lane & 7) * 4;
-    if constexpr (STEREO) {
-        // candidate = (a + cb * b) >> sh over the frame's rows L (2 fl) and R (2 fl + 1)
-        const uint32_t f_lo = cand0 / 4, fl = lane >> 2, f_last = nframes - 1;
-        L.off_a = (2 * fl + (cand == 1 ? 1u : 0u)) * AC3_LD;
-        L.off_b = (2 * fl + 1) * AC3_LD;
-        L.cb = cand == 2 ? 1 : cand == 3 ? -1 : 0;
-        L.sh = wasted + (cand == 2 ? 1u : 0u);
-        // staging: lane -> (row = it * 8 + lane / 8, 4 samples at column 4 * (lane % 8))
-#pragma unroll
-        for (int it = 0; it < ROWS / 8; it++) {
-            const uint32_t r = it * 8 + srow;              // 0..31: frame r / 2, channel r & 1
-            const uint32_t fr = f_lo + r / 2 < nframes ? f_lo + r / 2 : f_last;
-            L.gsrc[it] = p.planar + ((size_t)(frame0 + fr) * 2 + (r & 1)) * p.ldb + scol;
-            L.sdst[it] = r * AC3_LD + scol;
-        }
-    } else {
-        // independent channels: candidate g of the launch is planar row frame0 * C + g
-        L.off_a = lane * AC3_LD;
-        L.off_b = L.off_a;
-        L.cb = 0;
-        L.sh = wasted;
-#pragma unroll
-        for (int it = 0; it < ROWS / 8; it++) {
-            const uint32_t r = it * 8 + srow;              // 0..63: candidate cand0 + r
-            const uint32_t g = cand0 + r < total ? cand0 + r : total - 1;
-            L.gsrc[it] = p.planar + ((size_t)frame0 * p.channels + g) * p.ldb + scol;
-            L.sdst[it] = r * AC3_LD + scol;
-        }
-    }
-    L.ntiles = n / AC3_TS;
-    // the window slice (32 f64) is staged by every group of 16 lanes (identical data, same addresses)
-    L.wsrc = win + 2 * (lane & 15);
-    L.wdst = AC3_RAW + 4 * (lane & 15);
-    return live;
-}
-
-template <int A, int LG, bool STEREO>
-__device__ __forceinline__ void ac3_wave(const Params &p, int32_t *tile /* [2][BUF] */,
-                                         uint32_t frame0, uint32_t nframes, uint32_t n,
-                                         const double *__restrict__ win, uint32_t group) {
-    constexpr int ROWS = STEREO ? 32 : 64;
-    constexpr int AC3_RAW = Ac3Lane<ROWS>::RAW;
-    Ac3Lane<ROWS> L;
-    uint32_t frame, cand;
-    const bool live = ac3_setup<STEREO>(p, frame0, nframes, n, win, group, L, frame, cand);
-    double acc[LG];
-#pragma unroll
-    for (int k = 0; k < LG; k++) acc[k] = -0.0;  // f64 `sum()` identity
-    double w0[16], w1[16];
-    Ac3Raw r0, r1;
-    ac3_fetch(L, 0);
-    ac3_commit(L, tile);
-    ac3_sync();
-    ac3_fetch(L, 1);
-    ac3_load(tile + L.off_a, tile + L.off_b, reinterpret_cast<const double *>(tile + AC3_RAW), 0, r0);
-    ac3_tile<A, LG, true>(L, tile, 0, r0, r1, w0, w1, acc);
-#pragma unroll 1
-    for (uint32_t t = 1; t < L.ntiles; t++) ac3_tile<A, LG, false>(L, tile, t, r0, r1, w0, w1, acc);
-    if (live) {
-        double *out = p.ac + ((size_t)frame * p.ncand + cand) * AC_LD + A;
-#pragma unroll
-        for (int k = 0; k < LG; k++) out[k] = acc[k];
     }
 }
 
@@ -306,109 +116,24 @@ __device__ __forceinline__ void ac3_block_deep(const double (&w)[16], const doub
     }
 }
 
-// one tile (two blocks): X0, X1 receive the tile's blocks; Y0, Y1 hold the previous tile's
-template <int A, int LG, bool FIRSTT, int ROWS>
-__device__ __forceinline__ void ac3_tile_deep(Ac3Lane<ROWS> &L, int32_t *tile, uint32_t t, Ac3Raw &raw,
-                                              double (&X0)[16], double (&X1)[16], double (&Y0)[16],
-                                              double (&Y1)[16], double (&acc)[LG]) {
-    const uint32_t buf = t & 1;
-    constexpr int AC3_RAW = Ac3Lane<ROWS>::RAW, AC3_BUF = Ac3Lane<ROWS>::BUF;
-    int32_t *cur = tile + buf * AC3_BUF, *nxt = tile + (buf ^ 1) * AC3_BUF;
-    ac3_load(cur + L.off_a, cur + L.off_b, reinterpret_cast<const double *>(cur + AC3_RAW), 0, raw);
-    ac3_convert(raw, L.cb, L.sh, X0);
-    ac3_block_deep<A, LG, FIRSTT ? 1 : 0>(X0, Y1, Y0, acc);
-    __builtin_amdgcn_sched_barrier(0);
-    ac3_load(cur + L.off_a, cur + L.off_b, reinterpret_cast<const double *>(cur + AC3_RAW), 16, raw);
-    ac3_commit(L, nxt);   // tile t+1, fetched one whole tile ago
-    ac3_sync();
-    ac3_fetch(L, t + 2);
-    __builtin_amdgcn_sched_barrier(0);
-    ac3_convert(raw, L.cb, L.sh, X1);
-    ac3_block_deep<A, LG, FIRSTT ? 2 : 0>(X1, X0, Y1, acc);
-    __builtin_amdgcn_sched_barrier(0);
-}
-
-template <int A, int LG, bool STEREO>
-__device__ __forceinline__ void ac3_wave_deep(const Params &p, int32_t *tile, uint32_t frame0,
-                                              uint32_t nframes, uint32_t n,
-                                              const double *__restrict__ win, uint32_t group) {
-    constexpr int ROWS = STEREO ? 32 : 64;
-    Ac3Lane<ROWS> L;
-    uint32_t frame, cand;
-    const bool live = ac3_setup<STEREO>(p, frame0, nframes, n, win, group, L, frame, cand);
-    double acc[LG];
-#pragma unroll
-    for (int k = 0; k < LG; k++) acc[k] = -0.0;  // f64 `sum()` identity
-    double wa[16], wb[16], wc[16], wd[16];
-    Ac3Raw raw;
-    ac3_fetch(L, 0);
-    ac3_commit(L, tile);
-    ac3_sync();
-    ac3_fetch(L, 1);
-    ac3_tile_deep<A, LG, true>(L, tile, 0, raw, wa, wb, wc, wd, acc);
-    uint32_t t = 1;
-#pragma unroll 1
-    for (; t + 1 < L.ntiles; t += 2) {  // n is a multiple of 64: an even number of tiles
-        ac3_tile_deep<A, LG, false>(L, tile, t, raw, wc, wd, wa, wb, acc);
-        ac3_tile_deep<A, LG, false>(L, tile, t + 1, raw, wa, wb, wc, wd, acc);
-    }
-    if (t < L.ntiles) ac3_tile_deep<A, LG, false>(L, tile, t, raw, wc, wd, wa, wb, acc);
-    if (live) {
-        double *out = p.ac + ((size_t)frame * p.ncand + cand) * AC_LD + A;
-#pragma unroll
-        for (int k = 0; k < LG; k++) out[k] = acc[k];
-    }
-}
-
-template <bool STEREO>
-__global__ void __launch_bounds__(256, 2)
-k_autocorr3_deep(Params p, uint32_t frame0, uint32_t nframes, uint32_t n, const double *__restrict__ win) {
-    __shared__ __attribute__((aligned(16))) int32_t tiles[4][2 * Ac3Lane<STEREO ? 32 : 64>::BUF];
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    int32_t *tile = tiles[wave];
-    switch (wave) {  // 33 lags: 8 + 8 + 8 + 9
-    case 0: ac3_wave_deep<0, 8, STEREO>(p, tile, frame0, nframes, n, win, blockIdx.x); break;
-    case 1: ac3_wave_deep<8, 8, STEREO>(p, tile, frame0, nframes, n, win, blockIdx.x); break;
-    case 2: ac3_wave_deep<16, 8, STEREO>(p, tile, frame0, nframes, n, win, blockIdx.x); break;
-    default: ac3_wave_deep<24, 9, STEREO>(p, tile, frame0, nframes, n, win, blockIdx.x); break;
-    }
-}
-
-// NL lags split over NS waves; lag ranges are [NL * w / NS, NL * (w + 1) / NS)
-template <int NL, int NS, bool STEREO>
-__global__ void __launch_bounds__(64 * NS)
-k_autocorr3(Params p, uint32_t frame0, uint32_t nframes, uint32_t n, const double *__restrict__ win) {
-    __shared__ __attribute__((aligned(16))) int32_t tiles[NS][2 * Ac3Lane<STEREO ? 32 : 64>::BUF];
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    int32_t *tile = tiles[wave];
-    constexpr int B0 = 0, B1 = NL * 1 / NS, B2 = NL * 2 / NS, B3 = NL * 3 / NS, B4 = NL * 4 / NS;
-    if constexpr (NS == 2) {
-        if (wave == 0) ac3_wave<B0, B1 - B0, STEREO>(p, tile, frame0, nframes, n, win, blockIdx.x);
-        else ac3_wave<B1, B2 - B1, STEREO>(p, tile, frame0, nframes, n, win, blockIdx.x);
-    } else {
-        switch (wave) {
-        case 0: ac3_wave<B0, B1 - B0, STEREO>(p, tile, frame0, nframes, n, win, blockIdx.x); break;
-        case 1: ac3_wave<B1, B2 - B1, STEREO>(p, tile, frame0, nframes, n, win, blockIdx.x); break;
-        case 2: ac3_wave<B2, B3 - B2, STEREO>(p, tile, frame0, nframes, n, win, blockIdx.x); break;
-        default: ac3_wave<B3, B4 - B3, STEREO>(p, tile, frame0, nframes, n, win, blockIdx.x); break;
-        }
-    }
-}
-
 // ---------------------------------------------------------------------------------
-// K3, shared-conversion variant (k_autocorr4): the same lane = candidate walk and the same
-// per-lag left folds as k_autocorr3, but the int -> windowed-f64 conversion (mid/side, wasted-bits
-// shift, cvt, window multiply: encode.rs:1799) is done ONCE per candidate sample by the workgroup and
-// handed to the NS lag-group waves through a double-buffered f64 tile in LDS, instead of being
-// repeated by every lag-group wave from a private copy of the raw rows.
+// K3 for frames whose length is a multiple of 32, lags <= 16 (k_autocorr4): stereo L / R / mid / side candidates of
+// <= 24-bit samples, or independent channels.  Lane = candidate (64 per workgroup), NS waves split the lags; every
+// lane accumulates its lags strictly in sample order (the reference's left fold per lag, encode.rs:3403-3413), 16
+// samples at a time, with the previous 16-sample block as history, both in registers and statically indexed
+// (ac3_block).  The int -> windowed-f64 conversion (mid/side, wasted-bits shift, cvt, window multiply:
+// encode.rs:1799) is done ONCE per candidate sample by the workgroup and handed to the NS lag-group waves through a
+// double-buffered f64 tile in LDS.  (A kernel whose every lag-group wave converted a private copy of the raw rows
+// itself, without workgroup barriers, was slower -- 0.231 against 0.177 ms, 683 against 274 MB of HBM traffic per
+// launch, profiles/r02_a_traffic.json -- and has been removed.)
 //   producers: the waves convert the next tile straight from their global loads, in units dealt out so
 //     that lags + conversion balance (Ac4Share below; a lane holds 2 consecutive samples of one L or R
 //     row; the partner row's samples come from lane ^ 8 with one DPP row_ror:8 move each; L-lanes emit L
 //     and mid, R-lanes R and side);
 //   consumers: lane = candidate row, 8 ds_read_b128 per 16-sample block (row stride 34 doubles:
-//     conflict-free for the 16-lane groups of ds_read_b128), then ac3_block as before;
+//     conflict-free for the 16-lane groups of ds_read_b128), then ac3_block;
 //   one workgroup barrier per 32-sample tile.
-// Per 64 candidates x 32 samples: 832 mul/add + ~150 conversion instructions instead of 832 + 4 x 128.
+// Per 64 candidates x 32 samples: 832 mul/add + ~150 conversion instructions (832 + 4 x 128 with private copies).
 // ---------------------------------------------------------------------------------
 constexpr int AC4_TS = 32;             // samples per tile
 constexpr int AC4_LDW = AC4_TS + 2;    // f64 row stride: 68 dwords = 4 mod 64
@@ -952,9 +677,11 @@ k_autocorr4(Params p, uint32_t frame0, uint32_t nframes, uint32_t n, const doubl
     }
 }
 
-// ---- shared-conversion variant for lags up to 32 (LPC orders 17..32): as k_autocorr4, with the two
-// blocks of history of k_autocorr3_deep (four f64 block buffers rotating with a period of two tiles)
-template <int A, int LG, int U, int U0, bool STEREO, bool DIRECT = false, bool FUSE_LPC = false>
+// ---- lags up to 32 (LPC orders 17..32): as k_autocorr4, with the two blocks of history of ac3_block_deep (four f64
+// block buffers rotating with a period of two tiles).  K4 is a launch of its own behind this kernel (k_lpc_u<32>): in the
+// kernel's tail, as in k_autocorr4, it was measured slower -- 228 instead of 153 VGPRs leave no room for another
+// kernel's wave beside two of these (profiles/r04_autocorr_lpc_fuse.json)
+template <int A, int LG, int U, int U0, bool STEREO, bool DIRECT = false>
 __device__ __forceinline__ void ac4_wave_deep(const Params &p, double (*wt)[64 * AC4_LDW], uint32_t frame0,
                                               uint32_t nframes, uint32_t n, const double *__restrict__ win,
                                               uint32_t group, uint32_t *ors = nullptr) {
@@ -1029,15 +756,9 @@ __device__ __forceinline__ void ac4_wave_deep(const Params &p, double (*wt)[64 *
 #pragma unroll
         for (int k = 0; k < LG; k++) out[k] = acc[k];
     }
-    if constexpr (FUSE_LPC) {   // as in ac4_wave: the lags into the idle tile for the kernel's Levinson tail
-        static_assert(DIRECT && AC4_LDW >= 33, "33 lags per candidate row");
-        double *row = wt[0] + lane * AC4_LDW + A;
-#pragma unroll
-        for (int k = 0; k < LG; k++) row[k] = acc[k];
-    }
 }
 
-template <bool STEREO, bool DIRECT = false, bool FUSE_LPC = false>
+template <bool STEREO, bool DIRECT = false>
 __global__ void __launch_bounds__(256, 2)
 k_autocorr4_deep(Params p, uint32_t frame0, uint32_t nframes, uint32_t n, const double *__restrict__ win) {
     static_assert(!DIRECT || STEREO, "direct input: interleaved stereo");
@@ -1046,23 +767,10 @@ k_autocorr4_deep(Params p, uint32_t frame0, uint32_t nframes, uint32_t n, const 
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     constexpr Ac4Share S = ac4_share<STEREO>(4, 8, 8, 8, 9);   // 33 lags: 8 + 8 + 8 + 9
     switch (wave) {
-    case 0: ac4_wave_deep<0, 8, S.units[0], S.first[0], STEREO, DIRECT, FUSE_LPC>(p, wt, frame0, nframes, n, win, blockIdx.x, ors); break;
-    case 1: ac4_wave_deep<8, 8, S.units[1], S.first[1], STEREO, DIRECT, FUSE_LPC>(p, wt, frame0, nframes, n, win, blockIdx.x, ors); break;
-    case 2: ac4_wave_deep<16, 8, S.units[2], S.first[2], STEREO, DIRECT, FUSE_LPC>(p, wt, frame0, nframes, n, win, blockIdx.x, ors); break;
-    default: ac4_wave_deep<24, 9, S.units[3], S.first[3], STEREO, DIRECT, FUSE_LPC>(p, wt, frame0, nframes, n, win, blockIdx.x, ors); break;
-    }
-    if constexpr (FUSE_LPC) {   // K4 in the tail, as in k_autocorr4 (orders up to 32: k_lpc_u<32> was 0.03-0.04 ms per batch)
-        __syncthreads();
-        if (wave != 0) return;
-        const uint32_t lane = threadIdx.x;
-        const uint32_t cc = blockIdx.x * 64 + lane;
-        if (cc >= nframes * p.ncand) return;
-        const uint32_t idx = frame0 * p.ncand + cc;
-        const bool act = p.exhaustive ? true : active_in_assignment(p.finfo[idx / p.ncand].assignment, idx % p.ncand);
-        const CandInfo ci = cand_info_from_or(p, idx % p.ncand, ors[lane], act);
-        p.cinfo[idx] = ci;
-        const double *row = wt[0] + lane * AC4_LDW;
-        lpc_candidate<32>(p, idx, n, ci, [row](int i) { return row[i]; });
+    case 0: ac4_wave_deep<0, 8, S.units[0], S.first[0], STEREO, DIRECT>(p, wt, frame0, nframes, n, win, blockIdx.x, ors); break;
+    case 1: ac4_wave_deep<8, 8, S.units[1], S.first[1], STEREO, DIRECT>(p, wt, frame0, nframes, n, win, blockIdx.x, ors); break;
+    case 2: ac4_wave_deep<16, 8, S.units[2], S.first[2], STEREO, DIRECT>(p, wt, frame0, nframes, n, win, blockIdx.x, ors); break;
+    default: ac4_wave_deep<24, 9, S.units[3], S.first[3], STEREO, DIRECT>(p, wt, frame0, nframes, n, win, blockIdx.x, ors); break;
     }
 }
 

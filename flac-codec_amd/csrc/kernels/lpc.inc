@@ -27,166 +27,6 @@ __device__ __forceinline__ uint8_t lpc_est8(double best_bits, uint32_t n) {
     return (uint8_t)(e >= 255.0 ? 255 : e >= 1.0 ? (int)e + 1 : 1);   // rounded UP: the hint must not flatter LPC
 }
 
-__global__ void __launch_bounds__(64) k_lpc(Params p) {
-    const uint32_t idx = p.f0 * p.ncand + blockIdx.x * 64 + threadIdx.x;
-    if (idx >= (p.f0 + p.fcount) * p.ncand) return;
-    const uint32_t frame = idx / p.ncand;
-    const uint32_t n = frame_len(p, frame);
-    // DIRECT input: the ORs came out of the autocorrelation kernel just before; this kernel is k_candinfo too
-    CandInfo ci;
-    if (p.inter || p.split_src) {
-        const bool act = p.exhaustive ? true : active_in_assignment(p.finfo[idx / p.ncand].assignment, idx % p.ncand);
-        ci = cand_info_from_or(p, idx % p.ncand, p.stats[4 + idx], act);
-        p.cinfo[idx] = ci;
-    } else {
-        ci = p.cinfo[idx];
-    }
-    LpcParams *out = p.lpc + idx;
-    if (!ci.active || ci.is_const) {
-        out->status = 1;
-        return;
-    }
-    const uint32_t L = p.max_lpc_order;
-    if (n <= L) {  // InsufficientLpcSamples, encode.rs:3300
-        out->status = 1;
-        atomicAdd(&p.stats[0], 1u);
-        return;
-    }
-    // precision table, encode.rs:3305-3315
-    const uint32_t precision = n <= 192 ? 7 : n <= 384 ? 8 : n <= 576 ? 9 : n <= 1152 ? 10
-                               : n <= 2304 ? 11 : n <= 4608 ? 12 : 13;
-    const double *ac = p.ac + (size_t)idx * AC_LD;
-    double c[FLACGPU_MAX_LPC_ORDER], cn[FLACGPU_MAX_LPC_ORDER], errs[FLACGPU_MAX_LPC_ORDER];
-    // pass 1: errors of every order (lp_coefficients, encode.rs:3536-3580)
-    {
-        double k = ac[1] / ac[0];
-        c[0] = k;
-        double err = ac[0] * (1.0 - k * k);
-        errs[0] = err;
-        for (uint32_t i = 1; i < L; i++) {
-            double s = -0.0;
-            for (uint32_t j = 0; j < i; j++) {
-                double prod = ac[i - j] * c[j];
-                s = s + prod;
-            }
-            double q = ac[i + 1] - s;
-            double kk = q / err;
-            for (uint32_t j = 0; j < i; j++) {
-                double t = kk * c[i - 1 - j];
-                cn[j] = c[j] - t;
-            }
-            cn[i] = kk;
-            for (uint32_t j = 0; j <= i; j++) c[j] = cn[j];
-            err = err * (1.0 - kk * kk);
-            errs[i] = err;
-        }
-    }
-    // compute_best_order, encode.rs:3656-3702 (bits-per-residual NOT clamped, :3675)
-    const double LN_2 = 0.693147180559945309417232121458176568;
-    const double error_scale = 0.5 / (double)n;
-    const double denom = 2.0 * LN_2;
-    int best = -1;
-    double best_bits = 0.0, second = 0.0;
-    bool have_second = false;
-    for (uint32_t i = 0; i < L; i++) {
-        if (!(errs[i] > 0.0)) break;  // take_while(error > 0.0)
-        uint32_t order = i + 1;
-        double header_bits = (double)(order * ((uint32_t)ci.bps + precision));
-        double bpr = log(errs[i] * error_scale) / denom;
-        double bits = __builtin_fma(bpr, (double)(n - order), header_bits);
-        bits = bits * (1.0 + ((i & 1) ? p.tie_perturb : -p.tie_perturb));   // test knob, exact when 0
-        if (best < 0) {
-            best = (int)i;
-            best_bits = bits;
-        } else if (total_key(bits) < total_key(best_bits)) {
-            second = best_bits;
-            have_second = true;
-            best = (int)i;
-            best_bits = bits;
-        } else if (!have_second || total_key(bits) < total_key(second)) {
-            second = bits;
-            have_second = true;
-        }
-    }
-    if (best < 0) {  // NoBestLpcOrder
-        out->status = 2;
-        atomicAdd(&p.stats[0], 1u);
-        return;
-    }
-    note_order_tie(p, idx, have_second, second, best_bits);
-    const uint32_t order = (uint32_t)best + 1;
-    // pass 2: coefficients of the chosen order (same recursion, same roundings)
-    {
-        double k = ac[1] / ac[0];
-        c[0] = k;
-        double err = ac[0] * (1.0 - k * k);
-        for (uint32_t i = 1; i < order; i++) {
-            double s = -0.0;
-            for (uint32_t j = 0; j < i; j++) {
-                double prod = ac[i - j] * c[j];
-                s = s + prod;
-            }
-            double q = ac[i + 1] - s;
-            double kk = q / err;
-            for (uint32_t j = 0; j < i; j++) {
-                double t = kk * c[i - 1 - j];
-                cn[j] = c[j] - t;
-            }
-            cn[i] = kk;
-            for (uint32_t j = 0; j <= i; j++) c[j] = cn[j];
-            err = err * (1.0 - kk * kk);
-        }
-    }
-    // quantize, encode.rs:3334-3401
-    const int32_t max_coeff = (1 << (precision - 1)) - 1, min_coeff = -(1 << (precision - 1));
-    double l = fabs(c[0]);
-    for (uint32_t i = 1; i < order; i++) {
-        double a = fabs(c[i]);
-        if (total_key(a) >= total_key(l)) l = a;
-    }
-    if (!(l > 0.0)) {  // ZeroLpCoefficients (also NaN)
-        out->status = 3;
-        atomicAdd(&p.stats[0], 1u);
-        return;
-    }
-    // floor(log2(l)) as the host libm computes it: exponent, bumped when l sits in the
-    // (few-ulp) band below 2^(e+1) where log2() rounds up to e+1 (table built on the host)
-    int32_t fl;
-    if (isinf(l)) {
-        fl = INT32_MAX;
-    } else {
-        int e = ilogb(l);
-        fl = e;
-        if (e >= -64 && e < 64 && l >= p.log2_thr[e + 64]) {
-            fl = e + 1;
-            atomicAdd(&p.stats[2], 1u);
-        }
-    }
-    int32_t sh = (int32_t)((uint32_t)(int32_t)(precision - 1) - (uint32_t)fl - 1u);
-    if (sh > 15) sh = 15;
-    if (sh < -16) {  // LpNegativeShiftError
-        out->status = 4;
-        atomicAdd(&p.stats[0], 1u);
-        return;
-    }
-    double error = 0.0;
-    const double scale = (double)(1 << (sh >= 0 ? sh : -sh));
-    for (uint32_t i = 0; i < order; i++) {
-        double sum = sh >= 0 ? __builtin_fma(c[i], scale, error) : (c[i] / scale) + error;
-        double rr = round(sum);
-        int32_t q = (rr != rr) ? 0 : rr >= 2147483647.0 ? INT32_MAX : rr <= -2147483648.0 ? INT32_MIN
-                                                                                         : (int32_t)rr;
-        q = q < min_coeff ? min_coeff : q > max_coeff ? max_coeff : q;
-        error = sum - (double)q;
-        out->qlp[i] = q;
-    }
-    out->status = 0;
-    out->order = (uint8_t)order;
-    out->precision = (uint8_t)precision;
-    out->shift = (uint8_t)(sh >= 0 ? sh : 0);
-    out->est8 = lpc_est8(best_bits, n);
-}
-
 // Levinson-Durbin recursion up to `upto` orders (lp_coefficients, encode.rs:3536-3580), every loop
 // unrolled and guarded so that the arrays stay in registers
 template <int LMAX>
@@ -222,8 +62,8 @@ __device__ __forceinline__ void levinson_u(const double (&acr)[LMAX + 1], uint32
     }
 }
 
-// K4 with max_lpc_order <= LMAX known at compile time: with run-time loop bounds the
-// coefficient arrays sit in scratch memory and every access is a memory round trip
+// K4 with max_lpc_order <= LMAX known at compile time (with run-time loop bounds the coefficient arrays would sit in
+// scratch memory and every access would be a memory round trip: 8 / 12 / 16 / 32 are instantiated).
 // lpc_candidate: one lane = one candidate; `ac(i)` returns autocorrelation lag i (from HBM in k_lpc_u, from the LDS hand-off of
 // the lag-group waves in the fused tail of k_autocorr4).
 template <int LMAX, class AcAt>

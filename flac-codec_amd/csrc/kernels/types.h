@@ -42,7 +42,7 @@ struct CandInfo {        // per (frame, candidate)
     uint8_t is_const;    // all samples zero -> CONSTANT, nothing else to analyse
 };
 
-struct LpcParams {       // per (frame, candidate), output of k_lpc
+struct LpcParams {       // per (frame, candidate), output of K4 (lpc_candidate)
     int32_t status;      // 0 ok; else the reference's error (1 Insufficient, 2 NoBestOrder,
                          // 3 ZeroCoeffs, 4 NegativeShift)
     uint8_t order, precision, shift;
@@ -65,7 +65,7 @@ struct Params {
     uint32_t max_lpc_order, max_po, use_rice2;
     uint32_t n_frames, last_len;
     uint32_t f0, fcount;                           // frames [f0, f0 + fcount) handled by this launch
-    uint32_t ac_split;                             // waves the lags of k_autocorr3 are split over (2 or 4)
+    uint32_t ac_split;                             // lag-group waves per 64 candidates of the planar k_autocorr4 (2 or 4)
     // k_autocorr4 / _deep: 32-sample tiles [fma_t0, fma_t1) of a FULL block whose every product has both factors under window
     // values of exactly 1.0 (and integer samples below 2^26): there a term is one v_fma_f64, bit-identical to the reference's
     // multiply + add because the product is exact.  fma_t0 >= fma_t1: nowhere (short last frame, other windows, wide samples)
@@ -114,7 +114,7 @@ struct Params {
     uint32_t fir_suspect_bits;   // 30; a TEST knob lowers it so that ordinary input exercises the re-run
     // The FIXED half's partition tree and exact bit count (encode.rs:3862-3947 for the FIXED residual) put off until the LPC
     // candidate's size is known (k_cand64p, direct stereo input) -- r05.  From the 64 leaf sums the order statistics hold a
-    // LOWER BOUND of the FIXED residual block's size follows at any partition order (wave_cand_fixed.inc).  When k_lpc's size
+    // LOWER BOUND of the FIXED residual block's size follows at any partition order (wave_cand_fixed.inc).  When K4's size
     // estimate of the LPC candidate (LpcParams::est8, 1/8 bit per sample) undercuts that bound by defer_margin16 / 16 bit per
     // sample, the wave runs the LPC half first; an exact lpc_bits < bound then DECIDES encode.rs:2929-2934 for LPC without
     // tree or count, otherwise the wave builds the tree, re-fetches its samples and counts after all.  0: never (A/B), 1: by
@@ -208,30 +208,22 @@ __host__ __device__ constexpr uint32_t frame_fb_words_exhaustive_stereo(uint32_t
 
 // Every FLACGPU_* environment knob, resolved ONCE per context (flacgpu_create; flacenc_gpu.hip read_knobs) -- the
 // dispatch path never calls getenv.  The A/B selectors keep an older or generic kernel reachable for measurements
-// and parity tests; the TEST knobs (tie_band, tie_perturb, experiment_mfma_ac, decode_lanes) are honoured only
-// when FLACGPU_TEST_KNOBS=1 is set as well.
+// and parity tests; the TEST knobs (tie_band, tie_perturb, experiment_mfma_ac, fir_suspect_bits) are honoured only
+// when FLACGPU_TEST_KNOBS=1 is set as well.  Every one of them is exercised by a test, a tool or a bench leg
+// ("Environment selectors"; tests/test_knob_inventory.py keeps that list honest).
 struct Knobs {
-    bool no_direct = false, no_fast = false, no_w64 = false, no_persist = false, no_ac3 = false, ac_private = false,
-         no_fused_pack = false, no_frame64 = false, no_fork = false, lpc_dyn = false,
-         ac_eight_waves = false,   // A/B: k_autocorr4<13, 8> (FLACGPU_AC_WAVES8)
-         cand_persist_n = false,   // A/B: persistent candidate kernel for independent channels (FLACGPU_CAND_PERSIST_N)
+    bool no_direct = false, no_w64 = false, no_fused_pack = false, no_frame64 = false,
          early_download = false,   // the frames' D2H copy queued before the sizes are known (FLACGPU_EARLY_DOWNLOAD)
          no_hand = false,          // A/B: Params::hand_meta off (FLACGPU_NO_HAND)
          no_direct_short = false,  // A/B: 1024 / 1152 / 2048 / 2304-sample blocks through K0 + k_cand64 (FLACGPU_NO_DIRECT_SHORT)
-         lpc_fuse_deep = false,    // A/B: K4 in the tail of k_autocorr4_deep as well (FLACGPU_LPC_FUSE_DEEP; measured slower)
          no_ac_fma = false,        // A/B: every autocorrelation term a multiply and an add (FLACGPU_NO_AC_FMA)
-         no_chunk = false,         // A/B: big in-place batches run as ONE range (FLACGPU_NO_CHUNK)
          no_xpose = false,         // A/B: 4 / 8 interleaved channels split into planar rows by k_autocorr4 instead of read in place (FLACGPU_NO_XPOSE)
-         no_lpc_fuse = false,      // A/B: K4 as a launch of its own behind the direct autocorrelation (FLACGPU_NO_LPC_FUSE)
-         no_sub64 = false,         // A/B: frames of 3..8 channels assembled by one workgroup per FRAME (k_frame64) (FLACGPU_NO_SUB64)
          no_cand_pair = false;     // A/B: four waves per frame also for the fast channel choice without LPC (FLACGPU_NO_CAND_PAIR)
-    bool upload_by_kernel = false;      // A/B: the asynchronous host path reads the caller's pinned PCM with kernel loads (FLACGPU_UPLOAD_KERNEL)
     bool force_fir_check = false;       // A/B + TEST: every candidate takes the exact ResidualOverflow test first (FLACGPU_FIR_CHECK)
     uint32_t cand_grid = 0;             // resident workgroups of the persistent candidate kernels, 0: default
     bool experiment_mfma_ac = false;    // TEST: the re-associating MFMA autocorrelation (not bit-exact)
     bool has_tie_band = false, has_tie_perturb = false;
     double tie_band = 0.0, tie_perturb = 0.0;   // TEST
-    uint32_t decode_lanes = 0;          // TEST: lanes per wave of the stand-alone decoder, 0: default
     uint32_t fir_suspect_bits = 0;      // TEST: Params::fir_suspect_bits, 0: default (30)
     int defer_fixed = -1;               // FLACGPU_DEFER_FIXED: 0 / 1 / 2 (Params::defer_fixed); -1: default (1)
     int defer_margin16 = -1;            // FLACGPU_DEFER_MARGIN16: Params::defer_margin16; -1: default
@@ -241,7 +233,7 @@ Knobs read_knobs();   // flacenc_gpu.hip
 // ---- launchers (one per kernel family; defined in the .hip file that holds the kernels) ----
 namespace flacgpu_k {
 // lpc.hip
-void launch_lpc(const Params &p, const Knobs &kn, uint32_t blocks, hipStream_t st);
+void launch_lpc(const Params &p, uint32_t blocks, hipStream_t st);
 // cand.hip
 // returns true when the kernel also chose the channel assignment and wrote out_plan / frame_plan (the
 // persistent stereo kernels: K6 in the workgroup) -- no k_decide launch for those frames then
@@ -250,7 +242,7 @@ bool launch_cand64(const Params &p, const Knobs &kn, uint32_t B, uint32_t blocks
 bool launch_cand64_direct(const Params &p, const Knobs &kn, uint32_t B, uint32_t blocks, hipStream_t st);   // true: channel choice made
 bool launch_cand64_direct_short(const Params &p, const Knobs &kn, uint32_t B, uint32_t blocks, hipStream_t st);
 // autocorr.hip
-// returns true when the kernel also ran K4 in its tail (the DIRECT k_autocorr4 instantiations): no launch_lpc then
+// returns true when the kernel also ran K4 in its tail (the DIRECT and SPLIT k_autocorr4 instantiations): no launch_lpc then
 bool dispatch_autocorr(uint32_t H, const Params &p, const Knobs &kn, uint32_t frame0, uint32_t nframes, uint32_t n,
                        const double *win, hipStream_t st);
 void launch_autocorr_mfma(const Params &p, uint32_t blocks, uint32_t n, const double *win, double *ac,
@@ -273,7 +265,7 @@ void launch_sub64(const Params &p, const PackParams &q, uint32_t frames, hipStre
 void launch_frame64_short(const Params &p, const PackParams &q, uint32_t B, uint32_t frames, size_t lds,
                           hipStream_t st);
 // decode.hip
-void launch_decode(uint32_t max_lpc_order, uint32_t units, uint32_t lanes, const Params &p, const PackParams &q,
+void launch_decode(uint32_t max_lpc_order, uint32_t units, const Params &p, const PackParams &q,
                    int32_t *decoded, uint32_t *verify_counts, hipStream_t st);
 void launch_decode_finish(const Params &p, int32_t *decoded, const int32_t *expect, uint32_t *verify_counts,
                           hipStream_t st, const uint32_t *frame_n = nullptr);

@@ -942,7 +942,7 @@ __global__ void __launch_bounds__(PAIR ? 128 : WG, CANDP_WAVES(MAXO)) k_cand64p(
     static_assert(!PAIR || (SELF && DIRECT), "two waves per frame: direct input without LPC");
     constexpr int NWAVES = PAIR ? 2 : 4;
     static_assert(!DIRECT || (STEREO && SPL % 2 == 0), "direct input: interleaved stereo, wave block lengths");
-    static_assert(!SELF || DIRECT, "the candidate info comes from k_candinfo / k_lpc otherwise");
+    static_assert(!SELF || DIRECT, "the candidate info comes from k_candinfo / K4 otherwise");
     constexpr uint32_t N = 64u * SPL;
     constexpr int NROWS = STEREO ? 2 : 4;
     // DIRECT: the frame as NSEG segments of <= 1 KB, 1280 bytes apart (the slack takes the per-segment shift below).

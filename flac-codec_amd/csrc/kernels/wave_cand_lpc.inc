@@ -1,5 +1,5 @@
 // wave_cand_lpc.inc -- LPC half of a candidate wave's analysis: in-place FIR with the quantised coefficients of
-// k_lpc, Rice search of the stored residual (encode.rs:3174-3203 + the same residual coding).  Textually included
+// K4, Rice search of the stored residual (encode.rs:3174-3203 + the same residual coding).  Textually included
 // (wave_cand_body.inc / wave_cand_split.inc).  In scope: p, lane, x[SPL] (shifted; destroyed), lpw, qv, wasted,
 // bps_eff, N, SPL, MAXO, HAND (Params::hand_meta: the fold keeps the signs) and a WaveRice `lw` to fill.  Leaves lpc_ok, lpc_bits, lorder, lprec, lshift, lw.
     // ---- LPC (encode.rs:3174-3203 + the same residual coding)
