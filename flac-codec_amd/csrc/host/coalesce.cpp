@@ -653,7 +653,10 @@ int flacenc_encode_many_coalesced(const flacenc_options *opts_in, flacenc_job *j
                 uint32_t common = ~0u;
                 for (size_t i = 0; i < nl; i++) common = std::min(common, live[i]->sg->n - live[i]->done);
                 const size_t bytes = (size_t)common * frame_bytes;
-                if (nl >= 2 && bytes % 64 == 0) {
+                // (get_state / set_state / add_blocks pass a chain's buffered partial block by: lockstep only from a block's start)
+                bool aligned = true;
+                for (size_t i = 0; i < nl; i++) aligned &= st[live[i]->sg->stream]->md5.buffered() == 0;
+                if (nl >= 2 && bytes % 64 == 0 && aligned) {
                     const int groups = (int)((nl + 15) / 16);
                     const uint8_t *ptr[3][16];
                     uint32_t mask[3] = {0, 0, 0};
@@ -673,7 +676,7 @@ int flacenc_encode_many_coalesced(const flacenc_options *opts_in, flacenc_job *j
                         m.set_state(w4);
                         m.add_blocks(bytes / 64);
                     }
-                } else {   // a lone chain, or runs that are not whole MD5 blocks: the scalar code
+                } else {   // a lone chain, runs that are not whole MD5 blocks or that start inside one: the scalar code
                     for (size_t i = 0; i < nl; i++) st[live[i]->sg->stream]->md5.update(live[i]->p + (size_t)live[i]->done * frame_bytes, bytes);
                 }
                 size_t w = 0;

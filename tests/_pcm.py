@@ -18,6 +18,13 @@ def read_raw(name, bps):
     return ((v << np.uint32(shift)).astype(np.int32) >> shift).astype(np.int32)
 
 
+def le_bytes(pcm, bps):
+    """Interleaved int32 samples -> the little-endian byte string of (bps + 7) // 8 bytes per sample that the STREAMINFO MD5
+    is taken of."""
+    w = (bps + 7) // 8
+    return np.ascontiguousarray(pcm, dtype="<i4").view(np.uint8).reshape(-1, 4)[:, :w].tobytes()
+
+
 def generate_sine_1(full_scale, sample_rate, samples, f1, a1, f2, a2):
     """tests/format.rs:687-711 (same arithmetic; used only as realistic input)."""
     d1 = 2.0 * np.pi / (sample_rate / f1)

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import _oracle as orc
+from _pcm import le_bytes as _le_bytes
 from _pcm import synth_fast
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -83,11 +84,6 @@ def _val(info, f):
 def _same_info(got, ref, skip=()):
     diff = {f: (_val(got, f), _val(ref, f)) for f in INFO_FIELDS if f not in skip and _val(got, f) != _val(ref, f)}
     assert not diff, diff
-
-
-def _le_bytes(pcm, bps):
-    w = (bps + 7) // 8
-    return np.ascontiguousarray(pcm, dtype="<i4").view(np.uint8).reshape(-1, 4)[:, :w].tobytes()
 
 
 def _empty_md5_status(info):
