@@ -84,6 +84,12 @@ struct BitReader {
         skip(n);
         return n ? v : 0;
     }
+    // a signed value of 1..33 bits: the 33rd is what a side channel of 32-bit stereo adds
+    __device__ __forceinline__ int64_t get_wide(uint32_t n) {
+        if (n <= 32) return get_signed(n);
+        const int64_t top = get_signed(n - 32);
+        return top * 4294967296ll + get(32);
+    }
     // zeros before the next 1 bit; `limit`: bit position that ends the frame
     __device__ __forceinline__ uint32_t unary1(uint32_t limit) {
         uint32_t q = 0;
@@ -316,11 +322,112 @@ __device__ __forceinline__ uint32_t bps_of_code(uint32_t code, uint32_t streamin
     return code ? bps_tab[code] : streaminfo_bps;
 }
 
+// The body of a 33-bit subframe: the side channel of 32-bit stereo, which the reference reads as i64
+// (read_subframe::<33, R, i64>, decode.rs:1520-1628).  Rare, so plain rather than fast: no ring in
+// registers.  The last 32 samples -- all a predictor can ask for -- wait in x[] as coded (before the
+// wasted-bits shift), their low words there and their 33rd bits in `hi` (bit j: sample i-1-j); a
+// sample that leaves the window is FINISHED in place:
+//   mid == nullptr  left/side, side/right: x[i] = the low word of the side.  The finish kernels
+//                   form left - side / side + right modulo 2^32, and the true result fits 32 bits.
+//   mid != nullptr  mid/side needs all 33 bits of the side (side >> 1), so the lane that has both
+//                   rows undoes the decorrelation itself (decode.rs:1598-1602): mid[i] becomes left,
+//                   x[i] right, and the caller records the frame as two independent channels.
+__device__ __forceinline__ int64_t wide_sample(int32_t lo, uint32_t bit32) {
+    return (int64_t)(((uint64_t)(0u - (bit32 & 1u)) << 32) | (uint32_t)lo);
+}
+__device__ __forceinline__ void wide_finish(int32_t *x, int32_t *mid, uint32_t i, int64_t coded, uint32_t wasted) {
+    const int64_t s = (int64_t)((uint64_t)coded << wasted);
+    if (mid) {
+        const int64_t sum = (int64_t)mid[i] * 2 + (s & 1);
+        mid[i] = (int32_t)((sum + s) >> 1);
+        x[i] = (int32_t)((sum - s) >> 1);
+    } else {
+        x[i] = (int32_t)s;
+    }
+}
+__device__ __forceinline__ bool decode_subframe_wide(BitReader &r, uint32_t type, uint32_t wasted, uint32_t n,
+                                                     int32_t *x, uint32_t end_bit, int32_t *mid) {
+    const uint32_t eb = 33 - wasted;
+    if (type == 0) {  // CONSTANT
+        const int64_t v = r.get_wide(eb);
+        for (uint32_t i = 0; i < n; i++) wide_finish(x, mid, i, v, wasted);
+        return true;
+    }
+    if (type == 1) {  // VERBATIM
+        for (uint32_t i = 0; i < n; i++) {
+            wide_finish(x, mid, i, r.get_wide(eb), wasted);
+            if (r.pos() > end_bit) return false;
+        }
+        return true;
+    }
+    if (!((type >= 8 && type <= 12) || type >= 32)) return false;
+    const bool lpc = type >= 32;
+    const uint32_t order = lpc ? type - 31 : type - 8;
+    if (order > n) return false;
+    uint32_t hi = 0;
+    for (uint32_t i = 0; i < order; i++) {  // warm-up
+        const int64_t v = r.get_wide(eb);
+        x[i] = (int32_t)v;
+        hi = (hi << 1) | ((uint32_t)(v >> 32) & 1u);
+        if (r.pos() > end_bit) return false;
+    }
+    int32_t coef[32];
+    uint32_t shift = 0;
+    if (lpc) {
+        const uint32_t prec = r.get(4) + 1;
+        const int32_t sh = r.get_signed(5);
+        if (prec == 16 || sh < 0) return false;
+        shift = (uint32_t)sh;
+#pragma unroll
+        for (int j = 0; j < 32; j++) {
+            coef[j] = 0;
+            if ((uint32_t)j < order) coef[j] = r.get_signed(prec);
+        }
+    } else {
+        const int32_t fc[5][4] = {{0, 0, 0, 0}, {1, 0, 0, 0}, {2, -1, 0, 0}, {3, -3, 1, 0}, {4, -6, 4, -1}};
+#pragma unroll
+        for (int j = 0; j < 32; j++) coef[j] = j < 4 ? fc[order][j] : 0;
+    }
+    const uint32_t method = r.get(2);
+    if (method > 1) return false;
+    const uint32_t hb = method ? 5u : 4u, esc = method ? 31u : 15u;
+    const uint32_t po = r.get(4);
+    const uint32_t plen = n >> po;
+    if (plen < order || (plen << po) != n) return false;
+    uint32_t i = order;
+    for (uint32_t part = 0; part < (1u << po); part++) {
+        const uint32_t k = r.get(hb);
+        const bool escaped = k == esc;
+        const uint32_t ebits = escaped ? r.get(5) : 0u;
+        for (uint32_t cnt = plen - (part ? 0u : order); cnt; cnt--, i++) {
+            if (r.pos() > end_bit) return false;
+            int32_t res;
+            if (escaped) {
+                res = r.get_signed(ebits);
+            } else {
+                const uint32_t u = r.rice(k, 1u << k, end_bit);
+                res = (int32_t)(u >> 1) ^ -(int32_t)(u & 1);
+            }
+            int64_t s = 0;
+#pragma unroll
+            for (int j = 0; j < 32; j++)
+                if ((uint32_t)j < order) s += (int64_t)coef[j] * wide_sample(x[i - 1 - j], hi >> j);
+            const int64_t v = res + (s >> shift);
+            if (i >= 32) wide_finish(x, mid, i - 32, wide_sample(x[i - 32], hi >> 31), wasted);
+            x[i] = (int32_t)v;
+            hi = (hi << 1) | ((uint32_t)(v >> 32) & 1u);
+        }
+    }
+    for (uint32_t j = n > 32 ? n - 32 : 0; j < n; j++) wide_finish(x, mid, j, wide_sample(x[j], hi >> (n - 1 - j)), wasted);
+    return r.pos() <= end_bit;
+}
+
 // One subframe (read_subframe, decode.rs:1635-1752) at the reader's position: header, wasted bits,
 // CONSTANT / VERBATIM / FIXED / LPC body; n samples to x[].  Returns false when it does not parse.
+// sbps == 33 goes to decode_subframe_wide; `mid` (then only): the mid channel's row of a mid/side frame.
 template <int MAXO>
 __device__ __forceinline__ bool decode_subframe(BitReader &r, uint32_t sbps, uint32_t n, int32_t *__restrict__ x,
-                                                uint32_t end_bit) {
+                                                uint32_t end_bit, int32_t *mid = nullptr) {
     bool bad = false;
     // SubframeHeader, stream.rs:1375-1388
     if (r.get(1)) bad = true;
@@ -330,6 +437,8 @@ __device__ __forceinline__ bool decode_subframe(BitReader &r, uint32_t sbps, uin
     const uint32_t eb = sbps - wasted;
     if (wasted >= sbps) {
         bad = true;
+    } else if (sbps > 32) {
+        if (bad || !decode_subframe_wide(r, type, wasted, n, x, end_bit, mid)) bad = true;
     } else if (type == 0) {  // CONSTANT
         const int32_t v = (int32_t)((uint32_t)r.get_signed(eb) << wasted);
         for (uint32_t i = 0; i < n; i++) x[i] = v;
@@ -382,6 +491,9 @@ __device__ __forceinline__ uint32_t subframe_bps(uint32_t bps, uint32_t acode, u
     // the side channel carries one more bit (decode.rs:1520-1628)
     return bps + (((acode == 8 && c == 1) || (acode == 9 && c == 0) || (acode == 10 && c == 1)) ? 1u : 0u);
 }
+// mid/side at 32 bits: the lane that decodes the 33-bit side also undoes the decorrelation (decode_subframe_wide),
+// and the frame goes to the finish kernel as two independent channels
+__device__ __forceinline__ bool wide_mid_side(uint32_t bps, uint32_t acode) { return bps == 32 && acode == 10; }
 
 // Verifier of this encoder's own output: one lane per SUBFRAME, starting where the plan says.
 template <int MAXO>
@@ -401,6 +513,8 @@ __global__ void __launch_bounds__(64) k_decode(Params p, PackParams q, int32_t *
     const uint32_t bps = bps_of_code(fh.bps_code, p.bps);
     const uint32_t nch = acode < 8 ? acode + 1 : 2;
     if (n != frame_len(p, frame) || bps != p.bps || nch != p.channels || fh.blocking) bad = true;
+    // not this encoder's output (it keeps 32-bit stereo independent), and no lane here holds both rows
+    if (wide_mid_side(bps, acode)) bad = true;
     // Where this subframe is said to start and end.  The chain is closed below: subframe 0 starts
     // where the header ends, every subframe must end exactly where the next one is said to start,
     // and the last one where the padding + CRC-16 begin -- which is what a decoder walking the
@@ -454,12 +568,13 @@ __global__ void __launch_bounds__(64) k_decode_frames(DecodeParams p, int32_t *_
     if (n != p.frame_n[frame] || n > p.ldb || bps != p.bps || nch != p.channels) bad = true;
     for (uint32_t c = 0; c < nch && !bad; c++) {
         int32_t *__restrict__ x = out + ((size_t)frame * p.channels + c) * p.ldb;
-        if (!decode_subframe<MAXO>(r, subframe_bps(bps, acode, c), n, x, end_bit)) bad = true;
+        int32_t *mid = (c == 1 && wide_mid_side(bps, acode)) ? x - p.ldb : nullptr;
+        if (!decode_subframe<MAXO>(r, subframe_bps(bps, acode, c), n, x, end_bit, mid)) bad = true;
     }
     // zero padding to a byte, then the CRC-16 ends the frame exactly
     if (!bad && ((r.pos() + 7) & ~7u) + 16 != end_bit) bad = true;
     if (!bad && (r.pos() & 7) && r.get(8 - (r.pos() & 7)) != 0) bad = true;
-    verify_counts[4 + frame] = (bad ? 0x100u : 0u) | acode;
+    verify_counts[4 + frame] = (bad ? 0x100u : 0u) | (wide_mid_side(bps, acode) ? 1u : acode);
 }
 
 // Undo the stereo decorrelation (decode.rs:1520-1628) and compare with the expected PCM: one

@@ -36,11 +36,12 @@ __global__ void __launch_bounds__(64) k_decode_many(const uint32_t *__restrict__
     if (n != fr.n || bps != fr.bps || nch != fr.channels) bad = true;
     for (uint32_t c = 0; c < nch && !bad; c++) {
         int32_t *__restrict__ x = scratch + fr.scratch + (size_t)c * ldb;
-        if (!decode_subframe<MAXO>(r, subframe_bps(bps, acode, c), n, x, end_bit)) bad = true;
+        int32_t *mid = (c == 1 && wide_mid_side(bps, acode)) ? x - ldb : nullptr;
+        if (!decode_subframe<MAXO>(r, subframe_bps(bps, acode, c), n, x, end_bit, mid)) bad = true;
     }
     if (!bad && ((r.pos() + 7) & ~7u) + 16 != end_bit) bad = true;
     if (!bad && (r.pos() & 7) && r.get(8 - (r.pos() & 7)) != 0) bad = true;
-    codes[f] = (bad ? 0x100u : 0u) | acode;
+    codes[f] = (bad ? 0x100u : 0u) | (wide_mid_side(bps, acode) ? 1u : acode);   // 1: nothing left to undo
 }
 
 // the CRC-16 of the whole frame, its stored CRC included, is 0 exactly when the stored CRC is right
