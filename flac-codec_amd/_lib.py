@@ -17,6 +17,8 @@ MAX_PARTITIONS = 64
 N_KERNELS = 12
 DECODE_OUT_DEVICE = 1   # flacgpu_decoder_decode flags (include/flacenc_gpu.h)
 DECODE_NO_MD5 = 2
+SAMPLE_I32, SAMPLE_I16, SAMPLE_F32 = 0, 1, 2   # flacgpu_out_format.dtype
+LAYOUT_FLAT, LAYOUT_PADDED = 0, 1              # flacgpu_out_format.layout
 
 
 class GpuOptions(C.Structure):
@@ -92,6 +94,12 @@ class StreamInfo(C.Structure):
 class DecodedStream(C.Structure):
     """flacgpu_decoded_stream: one stream's record of the batch decoder."""
     _fields_ = [("rc", C.c_int32), ("reserved", C.c_uint32), ("out_offset", C.c_uint64), ("info", StreamInfo)]
+
+
+class OutFormat(C.Structure):
+    """flacgpu_out_format: element type and layout of flacgpu_decoder_decode_as's output."""
+    _fields_ = [("dtype", C.c_uint32), ("layout", C.c_uint32), ("channels_padded", C.c_uint32),
+                ("reserved", C.c_uint32), ("samples_padded", C.c_uint64)]
 
 
 class ShardCounters(C.Structure):
@@ -185,6 +193,10 @@ def _load():
     L.flacgpu_decoder_scan.argtypes = [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_uint32,
                                        C.POINTER(DecodedStream), C.POINTER(C.c_uint64)]
     L.flacgpu_decoder_decode.argtypes = [vp, vp, C.c_size_t, C.c_uint32, C.POINTER(DecodedStream)]
+    L.flacgpu_decoder_plan_output.argtypes = [C.POINTER(OutFormat), C.POINTER(DecodedStream), C.c_uint32,
+                                              C.POINTER(C.c_uint64)]
+    L.flacgpu_decoder_decode_as.argtypes = [vp, vp, C.c_size_t, C.POINTER(OutFormat), C.c_uint32,
+                                            C.POINTER(DecodedStream)]
     L.flacgpu_pack_plans.argtypes = [vp, ip, C.c_uint32, C.c_uint32, C.POINTER(FramePlan), C.POINTER(SubframePlan),
                                      C.c_uint64, C.c_uint32]
     L.flacgpu_host_alloc.argtypes = [C.c_size_t]

@@ -9,6 +9,7 @@
 
 #include <algorithm>
 #include <new>
+#include <string>
 #include <vector>
 
 namespace {
@@ -99,10 +100,12 @@ struct flacgpu_decoder {
     DevBuf bytes, slots, mask, plocal, wg_cnt, wg_tail, wg_off, wg_carry;
     DevBuf cand_pos, cand_info, cand_crc, cand_slot, slot_cand0, slot_pend, link;
     DevBuf frames, scratch, codes, counts, jobs, digest, out_stage;
+    DevBuf md5_stage, pad_out, pad_streams;   // decode_as: interleaved int32 for the MD5, padded layout tables
     // the scanned batch
     bool scanned = false;
     std::vector<flacgpu_decoded_stream> res;
     std::vector<int32_t> slot_of;          // stream -> slot, -1: no frame region on the device
+    std::vector<uint32_t> slot_stream;     // slot -> stream
     std::vector<ManyFrame> frame_tab;
     uint32_t n_slots = 0;
     uint64_t total = 0, scratch_total = 0;
@@ -283,17 +286,83 @@ int scan_impl(flacgpu_decoder *d, const uint8_t *const *data, const size_t *len,
     }
     d->total = total;
     d->scratch_total = scratch_total;
+    d->slot_stream.swap(slot_stream);
     return FLACGPU_OK;
 }
 
-int decode_impl(flacgpu_decoder *d, int32_t *out, size_t cap, uint32_t flags) {
+constexpr size_t elem_size(uint32_t dtype) { return dtype == FLACGPU_SAMPLE_I16 ? 2 : 4; }
+
+// the finish kernel of a format other than I32 / FLAT
+template <uint32_t DT, bool PADDED>
+void launch_finish_as(flacgpu_decoder *d, uint32_t F, void *dst, uint64_t samples_padded, int32_t *side) {
+    const auto k = side ? k_finish_as<DT, PADDED, true> : k_finish_as<DT, PADDED, false>;
+    hipLaunchKernelGGL(k, dim3(F), dim3(WG), 0, d->st, d->frames.as<const ManyFrame>(),
+                       d->scratch.as<const int32_t>(), d->codes.as<const uint32_t>(), static_cast<uint8_t *>(dst),
+                       d->pad_out.as<const uint64_t>(), samples_padded, side, d->counts.as<uint32_t>());
+}
+
+// decode_as, before the frame kernels: for PADDED the first element of every frame and the kernel that zeroes what no
+// frame writes (rows' tails, absent channels, streams without samples)
+int finish_as_tables(flacgpu_decoder *d, const flacgpu_out_format &fmt, void *dst) {
+    if (fmt.layout != FLACGPU_LAYOUT_PADDED) return FLACGPU_OK;
+    const uint32_t n = (uint32_t)d->res.size(), Cp = fmt.channels_padded;
+    const uint64_t T = fmt.samples_padded;
+    const size_t F = d->frame_tab.size();
+    if (!n || !Cp || !T) return FLACGPU_OK;
+    if ((uint64_t)n * Cp > 0x7FFFFFFFull) {
+        g_last_error = "flacgpu_decoder_decode_as: more than 2^31 - 1 padded rows";
+        return FLACGPU_ERR_UNSUPPORTED;
+    }
+    std::vector<uint64_t> first(F);
+    for (size_t f = 0; f < F; f++) {
+        const ManyFrame &fr = d->frame_tab[f];
+        const uint32_t i = d->slot_stream[fr.slot];
+        first[f] = (uint64_t)i * Cp * T + (fr.out - d->res[i].out_offset) / fr.channels;
+    }
+    std::vector<PadStream> ps(n);
+    for (uint32_t i = 0; i < n; i++) {
+        const flacgpu_decoded_stream &r = d->res[i];
+        ps[i] = r.rc == FLACGPU_OK ? PadStream{r.info.decoded_samples, r.info.channels, 0} : PadStream{0, 0, 0};
+    }
+    if (F) {
+        if (int rc = d->pad_out.ensure(8 * F)) return rc;
+        HIP_TRY(hipMemcpyAsync(d->pad_out.p, first.data(), 8 * F, hipMemcpyHostToDevice, d->st));
+    }
+    if (int rc = d->pad_streams.ensure(sizeof(PadStream) * n)) return rc;
+    HIP_TRY(hipMemcpyAsync(d->pad_streams.p, ps.data(), sizeof(PadStream) * n, hipMemcpyHostToDevice, d->st));
+    HIP_TRY(hipStreamSynchronize(d->st));   // the tables leave scope
+    if (fmt.dtype == FLACGPU_SAMPLE_I16)
+        hipLaunchKernelGGL(k_pad_rows<2>, dim3(n * Cp), dim3(WG), 0, d->st, d->pad_streams.as<const PadStream>(), Cp, T,
+                           static_cast<uint8_t *>(dst));
+    else
+        hipLaunchKernelGGL(k_pad_rows<4>, dim3(n * Cp), dim3(WG), 0, d->st, d->pad_streams.as<const PadStream>(), Cp, T,
+                           static_cast<uint8_t *>(dst));
+    HIP_TRY(hipGetLastError());
+    return FLACGPU_OK;
+}
+
+// fmt == nullptr: interleaved int32, streams back to back (flacgpu_decoder_decode); else a validated format other than
+// that one, of out_bytes bytes
+int decode_impl(flacgpu_decoder *d, void *out, size_t cap, uint32_t flags, const flacgpu_out_format *fmt = nullptr,
+                uint64_t out_bytes = 0) {
     const uint32_t n = (uint32_t)d->res.size();
     const uint32_t F = (uint32_t)d->frame_tab.size(), S = d->n_slots;
     const bool to_device = flags & FLACGPU_DECODE_OUT_DEVICE, md5 = !(flags & FLACGPU_DECODE_NO_MD5);
-    int32_t *dst = out;
-    if (!to_device && d->total) {
-        if (int rc = d->out_stage.ensure(4 * d->total)) return rc;
-        dst = d->out_stage.as<int32_t>();
+    if (!fmt) out_bytes = 4 * d->total;
+    void *dst = out;
+    if (!to_device && out_bytes) {
+        if (int rc = d->out_stage.ensure(out_bytes)) return rc;
+        dst = d->out_stage.p;
+    }
+    const int32_t *hashed = static_cast<const int32_t *>(dst);   // what k_md5_many reads
+    if (fmt) {
+        int32_t *side = nullptr;
+        if (md5 && d->total) {
+            if (int rc = d->md5_stage.ensure(4 * d->total)) return rc;
+            side = d->md5_stage.as<int32_t>();
+        }
+        hashed = side;
+        if (int rc = finish_as_tables(d, *fmt, dst)) return rc;
     }
     if (int rc = d->counts.ensure(8 * (size_t)std::max<uint32_t>(S, 1))) return rc;
     HIP_TRY(hipMemsetAsync(d->counts.p, 0, 8 * (size_t)std::max<uint32_t>(S, 1), d->st));
@@ -306,9 +375,23 @@ int decode_impl(flacgpu_decoder *d, int32_t *out, size_t cap, uint32_t flags) {
                            d->codes.as<uint32_t>());
         hipLaunchKernelGGL(k_frame_crc, dim3(F), dim3(64), 0, d->st, d->bytes.as<const uint8_t>(),
                            d->frames.as<const ManyFrame>(), d->counts.as<uint32_t>());
-        hipLaunchKernelGGL(k_finish_many, dim3(F), dim3(WG), 0, d->st, d->frames.as<const ManyFrame>(),
-                           d->scratch.as<const int32_t>(), d->codes.as<const uint32_t>(), dst,
-                           d->counts.as<uint32_t>());
+        if (!fmt) {
+            hipLaunchKernelGGL(k_finish_many, dim3(F), dim3(WG), 0, d->st, d->frames.as<const ManyFrame>(),
+                               d->scratch.as<const int32_t>(), d->codes.as<const uint32_t>(),
+                               static_cast<int32_t *>(dst), d->counts.as<uint32_t>());
+        } else {
+            const bool padded = fmt->layout == FLACGPU_LAYOUT_PADDED;
+            int32_t *side = const_cast<int32_t *>(hashed);
+            const uint64_t T = fmt->samples_padded;
+            if (fmt->dtype == FLACGPU_SAMPLE_I16)
+                padded ? launch_finish_as<DT_I16, true>(d, F, dst, T, side)
+                       : launch_finish_as<DT_I16, false>(d, F, dst, T, side);
+            else if (fmt->dtype == FLACGPU_SAMPLE_F32)
+                padded ? launch_finish_as<DT_F32, true>(d, F, dst, T, side)
+                       : launch_finish_as<DT_F32, false>(d, F, dst, T, side);
+            else   // I32 / FLAT takes the branch above
+                launch_finish_as<DT_I32, true>(d, F, dst, T, side);
+        }
         HIP_TRY(hipGetLastError());
     }
     std::vector<Md5Job> jobs;
@@ -331,7 +414,7 @@ int decode_impl(flacgpu_decoder *d, int32_t *out, size_t cap, uint32_t flags) {
         if (int rc = d->jobs.ensure(sizeof(Md5Job) * J)) return rc;
         if (int rc = d->digest.ensure(20 * (size_t)J)) return rc;
         HIP_TRY(hipMemcpyAsync(d->jobs.p, jobs.data(), sizeof(Md5Job) * J, hipMemcpyHostToDevice, d->st));
-        hipLaunchKernelGGL(k_md5_many, dim3((J + 63) / 64), dim3(64), 0, d->st, dst, d->jobs.as<const Md5Job>(), J,
+        hipLaunchKernelGGL(k_md5_many, dim3((J + 63) / 64), dim3(64), 0, d->st, hashed, d->jobs.as<const Md5Job>(), J,
                            d->digest.as<uint32_t>());
         HIP_TRY(hipGetLastError());
         digest.resize(5 * (size_t)J);
@@ -339,8 +422,8 @@ int decode_impl(flacgpu_decoder *d, int32_t *out, size_t cap, uint32_t flags) {
     }
     std::vector<uint32_t> counts(2 * (size_t)S);
     if (S) HIP_TRY(hipMemcpyAsync(counts.data(), d->counts.p, 8 * (size_t)S, hipMemcpyDeviceToHost, d->st));
-    if (!to_device && d->total)
-        HIP_TRY(hipMemcpyAsync(out, dst, 4 * d->total, hipMemcpyDeviceToHost, d->st));
+    if (!to_device && out_bytes)
+        HIP_TRY(hipMemcpyAsync(out, dst, out_bytes, hipMemcpyDeviceToHost, d->st));
     HIP_TRY(hipStreamSynchronize(d->st));
     (void)cap;
     for (uint32_t i = 0; i < n; i++) {
@@ -434,6 +517,85 @@ int flacgpu_decoder_decode(flacgpu_decoder *d, int32_t *out, size_t out_cap_samp
     const bool moved = hipGetDevice(&prev) == hipSuccess && prev != d->device && hipSetDevice(d->device) == hipSuccess;
     std::vector<flacgpu_decoded_stream> keep = d->res;   // a second decode of the same scan starts from the scan's records
     const int rc = decode_impl(d, out, out_cap_samples, flags);
+    if (moved) (void)hipSetDevice(prev);
+    if (rc == FLACGPU_OK && !d->res.empty())
+        memcpy(streams, d->res.data(), sizeof(flacgpu_decoded_stream) * d->res.size());
+    d->res.swap(keep);
+    return rc;
+}
+
+int flacgpu_decoder_plan_output(const flacgpu_out_format *fmt, const flacgpu_decoded_stream *streams,
+                                uint32_t n_streams, uint64_t *out_bytes) {
+    if (!fmt || !out_bytes || (n_streams && !streams)) return FLACGPU_ERR_INVALID_ARG;
+    *out_bytes = 0;
+    const bool padded = fmt->layout == FLACGPU_LAYOUT_PADDED;
+    if (fmt->dtype > FLACGPU_SAMPLE_F32 || fmt->layout > FLACGPU_LAYOUT_PADDED || fmt->reserved ||
+        (!padded && (fmt->channels_padded || fmt->samples_padded))) {
+        g_last_error = "flacgpu_decoder_plan_output: unknown dtype or layout, reserved not 0, or padded fields under FLAT";
+        return FLACGPU_ERR_INVALID_ARG;
+    }
+    uint64_t total = 0;
+    bool any = false;
+    for (uint32_t i = 0; i < n_streams; i++) {
+        const flacgpu_decoded_stream &r = streams[i];
+        if (r.rc != FLACGPU_OK) continue;
+        if (fmt->dtype == FLACGPU_SAMPLE_I16 && r.info.bits_per_sample > 16) {
+            g_last_error = "flacgpu_decoder_plan_output: int16 output, but stream " + std::to_string(i) + " has " +
+                           std::to_string(r.info.bits_per_sample) + " bits per sample";
+            return FLACGPU_ERR_UNSUPPORTED;
+        }
+        total += r.info.decoded_samples * r.info.channels;
+        any = any || (r.info.decoded_samples && r.info.channels);
+    }
+    const uint64_t es = elem_size(fmt->dtype);
+    if (!padded) {
+        *out_bytes = total * es;
+        return FLACGPU_OK;
+    }
+    for (uint32_t i = 0; i < n_streams && any; i++) {
+        const flacgpu_decoded_stream &r = streams[i];
+        if (r.rc != FLACGPU_OK) continue;
+        if (r.info.channels > fmt->channels_padded || r.info.decoded_samples > fmt->samples_padded) {
+            g_last_error = "flacgpu_decoder_plan_output: stream " + std::to_string(i) + " (" +
+                           std::to_string(r.info.channels) + " channels, " + std::to_string(r.info.decoded_samples) +
+                           " samples) does not fit channels_padded x samples_padded";
+            return FLACGPU_ERR_INVALID_ARG;
+        }
+    }
+    uint64_t bytes = 0;
+    if (__builtin_mul_overflow((uint64_t)n_streams * fmt->channels_padded, fmt->samples_padded, &bytes) ||
+        __builtin_mul_overflow(bytes, es, &bytes)) {
+        g_last_error = "flacgpu_decoder_plan_output: the padded batch exceeds 2^64 bytes";
+        return FLACGPU_ERR_UNSUPPORTED;
+    }
+    *out_bytes = bytes;
+    return FLACGPU_OK;
+}
+
+int flacgpu_decoder_decode_as(flacgpu_decoder *d, void *out, size_t out_cap_bytes, const flacgpu_out_format *fmt,
+                              uint32_t flags, flacgpu_decoded_stream *streams) {
+    if (!d || !fmt || (flags & ~(FLACGPU_DECODE_OUT_DEVICE | FLACGPU_DECODE_NO_MD5))) return FLACGPU_ERR_INVALID_ARG;
+    if (!d->scanned) {
+        g_last_error = "flacgpu_decoder_decode_as: no scanned batch";
+        return FLACGPU_ERR_INVALID_ARG;
+    }
+    if (!d->res.empty() && !streams) return FLACGPU_ERR_INVALID_ARG;
+    uint64_t out_bytes = 0;
+    if (int rc = flacgpu_decoder_plan_output(fmt, d->res.data(), (uint32_t)d->res.size(), &out_bytes)) return rc;
+    if (fmt->dtype == FLACGPU_SAMPLE_I32 && fmt->layout == FLACGPU_LAYOUT_FLAT)
+        return flacgpu_decoder_decode(d, static_cast<int32_t *>(out), out_cap_bytes / 4, flags, streams);
+    if (out_bytes && (!out || out_cap_bytes < out_bytes)) {
+        g_last_error = "output buffer too small";
+        return FLACGPU_ERR_BUFFER_TOO_SMALL;
+    }
+    if (reinterpret_cast<uintptr_t>(out) % elem_size(fmt->dtype)) {
+        g_last_error = "flacgpu_decoder_decode_as: out is not aligned to its element size";
+        return FLACGPU_ERR_INVALID_ARG;
+    }
+    int prev = -1;
+    const bool moved = hipGetDevice(&prev) == hipSuccess && prev != d->device && hipSetDevice(d->device) == hipSuccess;
+    std::vector<flacgpu_decoded_stream> keep = d->res;   // as flacgpu_decoder_decode: the scan's records stay
+    const int rc = decode_impl(d, out, out_cap_bytes, flags, fmt, out_bytes);
     if (moved) (void)hipSetDevice(prev);
     if (rc == FLACGPU_OK && !d->res.empty())
         memcpy(streams, d->res.data(), sizeof(flacgpu_decoded_stream) * d->res.size());

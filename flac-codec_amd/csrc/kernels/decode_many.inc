@@ -7,6 +7,10 @@
 //                        writes interleaved int32 at the stream's output offset
 //   K_d4 k_md5_many      lane per stream: MD5 of the stream's interleaved samples as ceil(bps / 8)-byte
 //                        little-endian values (decode.rs:1282-1310 `verify`)
+//   K_d5 k_finish_as     workgroup per frame: k_finish_many's arithmetic, the samples converted in registers to
+//                        int16 / float32 (or left int32) and written flat or into padded planar rows; with MD5 also
+//                        the interleaved int32 that k_md5_many reads
+//   K_d6 k_pad_rows      workgroup per (stream, channel row) of a padded batch: zeroes what no frame writes
 
 struct ManyFrame {
     uint64_t start, end;   // byte offsets in the batch buffer: header .. CRC-16 inclusive
@@ -99,6 +103,143 @@ __global__ void __launch_bounds__(WG) k_finish_many(const ManyFrame *__restrict_
     } else {
         for (uint32_t i = threadIdx.x; i < n; i += WG)
             for (uint32_t c = 0; c < C; c++) o[(size_t)i * C + c] = rows[(size_t)c * ldb + i];
+    }
+}
+
+// ---- other sample formats and layouts (flacgpu_decoder_decode_as) ----
+constexpr uint32_t DT_I32 = 0, DT_I16 = 1, DT_F32 = 2;   // FLACGPU_SAMPLE_*
+
+// One sample of a frame, the stereo decorrelation undone: k_finish_many's arithmetic (64-bit mid/side; a code of 1
+// means that nothing is left to undo), kept apart from it so that its code stays as it is.
+__device__ __forceinline__ int32_t frame_sample(const int32_t *__restrict__ rows, uint32_t ldb, uint32_t acode,
+                                                uint32_t i, uint32_t c) {
+    if (acode < 8) return rows[(size_t)c * ldb + i];
+    const long long a = rows[i], b = rows[ldb + i];
+    long long l, rr;
+    if (acode == 8) { l = a; rr = a - b; }
+    else if (acode == 9) { l = a + b; rr = b; }
+    else {
+        const long long sum = a * 2 + ((b < 0 ? -b : b) & 1);
+        l = (sum + b) >> 1;
+        rr = (sum - b) >> 1;
+    }
+    return (int32_t)(c ? rr : l);
+}
+
+// The bits of one output element: I16 sample << (16 - bps) in the low half, F32 (float)sample * 2^-(bps - 1)
+// (the int -> float conversion rounds to nearest even, the scale is a power of two and so exact).
+template <uint32_t DT> __device__ __forceinline__ uint32_t sample_bits(int32_t v, uint32_t bps) {
+    if (DT == DT_I16) return ((uint32_t)v << ((16u - bps) & 15u)) & 0xFFFFu;
+    if (DT == DT_F32) return __float_as_uint(__int2float_rn(v) * __uint_as_float((128u - bps) << 23));
+    return (uint32_t)v;
+}
+
+// n elements of ES bytes to dst (ES-aligned), element e = get(e) in the low bits of a dword: single elements up to
+// the first 16-byte boundary, then 16 bytes per lane (consecutive lanes, consecutive 16 bytes), then single elements.
+template <uint32_t ES, class Get>
+__device__ __forceinline__ void store_run(uint8_t *dst, uint32_t n, uint32_t tid, uint32_t nthreads, Get get) {
+    constexpr uint32_t V = 16 / ES;
+    const uint32_t mis = (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 15u) / ES;
+    const uint32_t head = min(n, (V - mis) % V);
+    const uint32_t nv = (n - head) / V, tail_at = head + nv * V;
+    if (tid < head) {
+        if (ES == 2) reinterpret_cast<uint16_t *>(dst)[tid] = (uint16_t)get(tid);
+        else reinterpret_cast<uint32_t *>(dst)[tid] = get(tid);
+    }
+    uint4 *body = reinterpret_cast<uint4 *>(dst + (size_t)head * ES);
+    for (uint32_t v = tid; v < nv; v += nthreads) {
+        const uint32_t e = head + v * V;
+        uint4 w;
+        if (ES == 2) {
+            w.x = get(e) | get(e + 1) << 16;
+            w.y = get(e + 2) | get(e + 3) << 16;
+            w.z = get(e + 4) | get(e + 5) << 16;
+            w.w = get(e + 6) | get(e + 7) << 16;
+        } else {
+            w.x = get(e);
+            w.y = get(e + 1);
+            w.z = get(e + 2);
+            w.w = get(e + 3);
+        }
+        body[v] = w;
+    }
+    if (tid < n - tail_at) {
+        const uint32_t e = tail_at + tid;
+        if (ES == 2) reinterpret_cast<uint16_t *>(dst)[e] = (uint16_t)get(e);
+        else reinterpret_cast<uint32_t *>(dst)[e] = get(e);
+    }
+}
+
+// pad_out (PADDED only): the frame's first element of channel 0, row + the frame's first sample; channel c is
+// samples_padded elements further per channel.  side (MD5 only): interleaved int32 at the frame's flat offset,
+// written as k_finish_many writes it.
+template <uint32_t DT, bool PADDED, bool SIDE>
+__global__ void __launch_bounds__(WG) k_finish_as(const ManyFrame *__restrict__ frames,
+                                                  const int32_t *__restrict__ scratch,
+                                                  const uint32_t *__restrict__ codes, uint8_t *__restrict__ out,
+                                                  const uint64_t *__restrict__ pad_out, uint64_t samples_padded,
+                                                  int32_t *__restrict__ side, uint32_t *__restrict__ slot_counts) {
+    constexpr uint32_t ES = DT == DT_I16 ? 2 : 4;
+    const uint32_t f = blockIdx.x;
+    const ManyFrame fr = frames[f];
+    const uint32_t code = codes[f];
+    const bool bad = code & 0x100u;
+    const uint32_t acode = bad ? 0u : (code & 0xFFu);   // a frame that did not parse is written as decoded
+    if (bad && threadIdx.x == 0) atomicAdd(&slot_counts[2 * fr.slot], 1u);
+    const uint32_t n = fr.n, C = fr.channels, bps = fr.bps, ldb = (n + 3u) & ~3u;
+    const int32_t *rows = scratch + fr.scratch;
+    if (PADDED) {
+        for (uint32_t c = 0; c < C; c++)
+            store_run<ES>(out + (pad_out[f] + (uint64_t)c * samples_padded) * ES, n, threadIdx.x, WG, [&](uint32_t i) {
+                return sample_bits<DT>(frame_sample(rows, ldb, acode, i, c), bps);
+            });
+    } else {
+        uint8_t *o = out + fr.out * ES;
+        if (C == 1)
+            store_run<ES>(o, n, threadIdx.x, WG,
+                          [&](uint32_t e) { return sample_bits<DT>(rows[e], bps); });
+        else if (C == 2)
+            store_run<ES>(o, 2 * n, threadIdx.x, WG, [&](uint32_t e) {
+                return sample_bits<DT>(frame_sample(rows, ldb, acode, e >> 1, e & 1u), bps);
+            });
+        else
+            store_run<ES>(o, C * n, threadIdx.x, WG, [&](uint32_t e) {
+                return sample_bits<DT>(rows[(size_t)(e % C) * ldb + e / C], bps);
+            });
+    }
+    if (SIDE) {
+        int32_t *o = side + fr.out;
+        for (uint32_t i = threadIdx.x; i < n; i += WG)
+            for (uint32_t c = 0; c < C; c++) o[(size_t)i * C + c] = frame_sample(rows, ldb, acode, i, c);
+    }
+}
+
+struct PadStream {
+    uint64_t samples;    // decoded samples per channel; 0 for a stream with rc != 0
+    uint32_t channels;   // 0 for a stream with rc != 0
+    uint32_t reserved;
+};
+// Workgroup per (stream, channel row): zeroes [decoded_samples, samples_padded) of a channel the stream has and the
+// whole row of one it has not.  Elements up to the first 16-byte boundary, 16 bytes per lane, elements.
+template <uint32_t ES>
+__global__ void __launch_bounds__(WG) k_pad_rows(const PadStream *__restrict__ streams, uint32_t channels_padded,
+                                                 uint64_t samples_padded, uint8_t *__restrict__ out) {
+    const uint32_t s = blockIdx.x / channels_padded, c = blockIdx.x % channels_padded;
+    const PadStream ps = streams[s];
+    const uint64_t from = c < ps.channels ? ps.samples : 0;
+    uint8_t *p = out + ((uint64_t)blockIdx.x * samples_padded + from) * ES;
+    const uint64_t bytes = (samples_padded - from) * ES;
+    const uint64_t head = min(bytes, (uint64_t)((16u - (uint32_t)(reinterpret_cast<uintptr_t>(p) & 15u)) & 15u));
+    const uint64_t nv = (bytes - head) / 16, tail_at = head + nv * 16;
+    if (threadIdx.x * ES < head) {
+        if (ES == 2) reinterpret_cast<uint16_t *>(p)[threadIdx.x] = 0;
+        else reinterpret_cast<uint32_t *>(p)[threadIdx.x] = 0;
+    }
+    uint4 *body = reinterpret_cast<uint4 *>(p + head);
+    for (uint64_t v = threadIdx.x; v < nv; v += WG) body[v] = make_uint4(0, 0, 0, 0);
+    if (threadIdx.x * ES < bytes - tail_at) {
+        if (ES == 2) reinterpret_cast<uint16_t *>(p + tail_at)[threadIdx.x] = 0;
+        else reinterpret_cast<uint32_t *>(p + tail_at)[threadIdx.x] = 0;
     }
 }
 

@@ -392,7 +392,8 @@ def decode_stream(data, device=-1, want_pcm=True):
 
 class DecodedStream:
     """One stream of a decode_many batch: rc (what flacgpu_decode_stream returns for it), info (StreamInfo), offset
-    (first int32 in the flat output) and pcm (a [samples, channels] view of the flat output; None when rc != 0)."""
+    (first element in the flat output) and pcm (a [samples, channels] view of the flat output, or the
+    [channels, samples] view batch[i, :channels, :decoded_samples] of a padded batch; None when rc != 0)."""
     __slots__ = ("rc", "info", "offset", "pcm")
 
     def __init__(self, rc, info, offset, pcm):
@@ -448,16 +449,84 @@ class Decoder:
             raise GpuError(rc, "flacgpu_decoder_decode")
         return recs
 
+    @staticmethod
+    def plan_output(fmt, recs, n):
+        """flacgpu_decoder_plan_output: the bytes the output of `fmt` takes for the first n scanned records."""
+        need = C.c_uint64(0)
+        rc = _lib.lib().flacgpu_decoder_plan_output(C.byref(fmt), recs, n, C.byref(need))
+        if rc:
+            raise GpuError(rc, "flacgpu_decoder_plan_output")
+        return need.value
 
-def decode_many(blobs, device=-1, out="device", verify_md5=True, decoder=None):
+    def decode_as(self, out_ptr, out_cap_bytes, fmt, flags, recs):
+        """flacgpu_decoder_decode_as into the buffer at out_ptr (device or host address) in the format `fmt`
+        (_lib.OutFormat)."""
+        rc = _lib.lib().flacgpu_decoder_decode_as(self._h, out_ptr, out_cap_bytes, C.byref(fmt), flags, recs)
+        if rc:
+            raise GpuError(rc, "flacgpu_decoder_decode_as")
+        return recs
+
+
+_DTYPES = {"int32": _lib.SAMPLE_I32, "int16": _lib.SAMPLE_I16, "float32": _lib.SAMPLE_F32}
+
+
+def _decode_many_as(dec, recs, n, out, flags, dtype, layout, pad_to, pad_channels):
+    """decode_many's other formats: (flat or [B, C, T] batch, streams)."""
+    fmt = _lib.OutFormat(_DTYPES[dtype], _lib.LAYOUT_FLAT, 0, 0, 0)
+    ok = [recs[i] for i in range(n) if recs[i].rc == 0]
+    if layout == "padded":
+        fmt.layout = _lib.LAYOUT_PADDED
+        fmt.samples_padded = pad_to or max([r.info.decoded_samples for r in ok], default=0)
+        fmt.channels_padded = pad_channels or max([r.info.channels for r in ok], default=0)
+        shape = (n, fmt.channels_padded, fmt.samples_padded)
+    else:
+        shape = (sum(r.info.decoded_samples * r.info.channels for r in ok),)
+    need = Decoder.plan_output(fmt, recs, n)   # refuses before anything is allocated
+    if out == "device":
+        import torch
+
+        dev = dec.device if dec.device >= 0 else torch.cuda.current_device()
+        buf = torch.empty(shape, dtype=getattr(torch, dtype), device=f"cuda:{dev}")
+        torch.cuda.synchronize(dev)
+        dec.decode_as(buf.data_ptr() if need else None, need, fmt, flags | _lib.DECODE_OUT_DEVICE, recs)
+    else:
+        buf = np.empty(shape, dtype=dtype)
+        dec.decode_as(buf.ctypes.data if need else None, need, fmt, flags, recs)
+    streams = []
+    for i in range(n):
+        r = recs[i]
+        info = _lib.StreamInfo()
+        C.memmove(C.byref(info), C.byref(r.info), C.sizeof(info))
+        pcm = None
+        if r.rc == 0 and layout == "padded":
+            pcm = buf[i, :info.channels, :info.decoded_samples]
+        elif r.rc == 0:
+            ch = max(info.channels, 1)
+            pcm = buf[r.out_offset:r.out_offset + info.decoded_samples * ch].reshape(-1, ch)
+        streams.append(DecodedStream(r.rc, info, r.out_offset, pcm))
+    return buf, streams
+
+
+def decode_many(blobs, device=-1, out="device", verify_md5=True, decoder=None, dtype="int32", layout="flat",
+                pad_to=None, pad_channels=None):
     """Decode many FLAC streams in one GPU call (flacgpu_decoder_scan + flacgpu_decoder_decode).
 
     Returns (flat, streams): `flat` holds every stream's interleaved int32 samples one after another -- a torch tensor
     on the GPU for out="device", a numpy array for out="host" -- and `streams` is a list of DecodedStream.  Every record
     equals what flacgpu_decode_stream gives for that stream alone (a stream without frames is hashed as the empty
-    input: md5_status 1 / 2 instead of 0).  verify_md5=False skips the MD5 (md5_status 3)."""
+    input: md5_status 1 / 2 instead of 0).  verify_md5=False skips the MD5 (md5_status 3).
+
+    dtype "int16" (sample << (16 - bps); every stream must have bps <= 16) or "float32" (sample * 2^-(bps - 1))
+    converts in the same kernel pass (flacgpu_decoder_decode_as).  layout="padded" returns (batch, streams): `batch` is
+    [B, C, T], planar and zero-padded, with T = pad_to or the longest stream and C = pad_channels or the most channels;
+    streams[i].pcm is the view batch[i, :channels, :decoded_samples], and the lengths vector a padded batch goes with
+    is [s.info.decoded_samples for s in streams].  A stream with rc != 0 is a row of zeros."""
     if out not in ("device", "host"):
         raise ValueError("out must be 'device' or 'host'")
+    if dtype not in _DTYPES or layout not in ("flat", "padded"):
+        raise ValueError("dtype must be 'int32', 'int16' or 'float32' and layout 'flat' or 'padded'")
+    if layout == "flat" and (pad_to is not None or pad_channels is not None):
+        raise ValueError("pad_to and pad_channels go with layout='padded'")
     if out == "device":
         import torch
 
@@ -467,6 +536,8 @@ def decode_many(blobs, device=-1, out="device", verify_md5=True, decoder=None):
     try:
         recs, total = dec.scan(blobs)
         flags = 0 if verify_md5 else _lib.DECODE_NO_MD5
+        if (dtype, layout) != ("int32", "flat"):
+            return _decode_many_as(dec, recs, len(blobs), out, flags, dtype, layout, pad_to, pad_channels)
         if out == "device":
             import torch
 

@@ -536,6 +536,45 @@ int flacgpu_decoder_scan(flacgpu_decoder *d, const uint8_t *const *data, const s
 int flacgpu_decoder_decode(flacgpu_decoder *d, int32_t *out, size_t out_cap_samples, uint32_t flags,
                            flacgpu_decoded_stream *streams);
 
+/* ---- batch decoder: other sample formats and layouts -----------------------------------------------------------------
+ * decode_as decodes the scanned batch as flacgpu_decoder_decode does (flags, host or device `out`, the records), in
+ * the element type and layout of `fmt`, converted on the sample's one way from the decoder's scratch to `out`:
+ *   I32  the sample.
+ *   I16  sample << (16 - bps).  Needs bps <= 16 in every stream with rc == 0; else the whole call returns
+ *        FLACGPU_ERR_UNSUPPORTED, flacgpu_last_error names the first such stream, and nothing is written.
+ *   F32  (float)sample (round to nearest even) * 2^-(bps - 1): exact for bps <= 25, correctly rounded above.
+ *   FLAT    streams back to back, each [samples][channels]; stream i starts at element out_offset (of the scan).
+ *   PADDED  [n_streams][channels_padded][samples_padded], planar: stream i starts at element
+ *           i * channels_padded * samples_padded, channel c at c * samples_padded behind that.  Elements with
+ *           c >= channels or t >= decoded_samples, and every element of a stream with rc != 0 or without frames, are
+ *           zero.  channels_padded and samples_padded must cover every stream with rc == 0 (FLACGPU_ERR_INVALID_ARG
+ *           otherwise); 0 is valid only when no stream has samples.
+ * After FLACGPU_OK all out_bytes (plan_output) are defined, whatever `out` held before; the samples of a frame that
+ * does not decode are undefined, inside that frame's own samples of its own stream's rows.  A refused call
+ * (INVALID_ARG, UNSUPPORTED, BUFFER_TOO_SMALL when out_cap_bytes < out_bytes) writes nothing.  For host output the
+ * decoder stages and downloads out_bytes, not 4 bytes per sample.  A scan may be decoded any number of times, in any
+ * formats, in either order with flacgpu_decoder_decode.
+ * The MD5 is taken over interleaved int32: with a format other than I32 / FLAT, verification costs 4 * total_samples
+ * bytes of device memory (a decoder-owned copy the same kernel pass writes); FLACGPU_DECODE_NO_MD5 neither writes nor
+ * allocates it.
+ * plan_output is a pure host function (no device, no handle): validates `fmt` against scanned records and returns
+ * the bytes `out` must hold. */
+#define FLACGPU_SAMPLE_I32 0u
+#define FLACGPU_SAMPLE_I16 1u
+#define FLACGPU_SAMPLE_F32 2u
+#define FLACGPU_LAYOUT_FLAT   0u  /* streams back to back, each [samples][channels]: flacgpu_decoder_decode's layout */
+#define FLACGPU_LAYOUT_PADDED 1u  /* [n_streams][channels_padded][samples_padded], planar, zero-filled */
+typedef struct {
+    uint32_t dtype, layout;
+    uint32_t channels_padded;   /* PADDED only, else 0 */
+    uint32_t reserved;          /* 0 */
+    uint64_t samples_padded;    /* PADDED only, else 0 */
+} flacgpu_out_format;
+int flacgpu_decoder_plan_output(const flacgpu_out_format *fmt, const flacgpu_decoded_stream *streams,
+                                uint32_t n_streams, uint64_t *out_bytes);
+int flacgpu_decoder_decode_as(flacgpu_decoder *d, void *out, size_t out_cap_bytes, const flacgpu_out_format *fmt,
+                              uint32_t flags, flacgpu_decoded_stream *streams);
+
 /* EXPERIMENT, not on the product path: recomputes the autocorrelation of the last analysed
  * batch on the f64 matrix cores (v_mfma_f64_16x16x4_f64, block-Gram form), times that kernel,
  * reruns Levinson/quantisation on it and reports how many candidates' quantised LPC parameters

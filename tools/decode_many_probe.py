@@ -4,6 +4,16 @@ over flacgpu_decode_stream and the oracle's CPU decoder on one core; writes prof
 
     python tools/decode_many_probe.py [--workloads clips,tracks,hour] [--out FILE] [--reps 3]
     python tools/decode_many_probe.py --merge-stats kernel_stats.csv --out FILE   (adds one rocprofv3 --stats run)
+    python tools/decode_many_probe.py --formats [--out profiles/r09_decode_formats.json] [--reps 9]
+    python tools/decode_many_probe.py --formats --label parent --package-root DIR   (DIR: a built checkout of the
+                                             parent commit; the default int32 path only, into the same file)
+    python tools/decode_many_probe.py --formats --kernels-only   (one warm call per leg, for rocprofv3)
+
+--formats (flacgpu_decoder_decode_as): on the clips, device output, no MD5, handle warm, the wall time of one
+scan + decode call into (a) what a caller of flacgpu_decoder_decode does -- interleaved int32, then torch ops to the
+same [B, 1, T] float32 (or int16) padded tensor -- and (b) decode_many(dtype=, layout="padded") in one call; and the
+default int32 path itself, whose figure the parent's build repeats on the same box (the regression guard: the margin is
+the spread over --reps that this probe sees).
 
 Workloads (default options of FlacSampleWriter; a few distinct streams repeated to the batch size -- the decoder
 does not see that they repeat):
@@ -129,6 +139,97 @@ def time_oracle(blobs, budget):
     return time.perf_counter() - t0, done, samples
 
 
+def _sclk_mhz():
+    """The shader clock now (MHz), read only; None when rocm-smi does not answer."""
+    import re
+    import subprocess
+
+    try:
+        out = subprocess.run(["rocm-smi", "--showclocks", "-d", "0"], capture_output=True, text=True, timeout=20).stdout
+    except (OSError, subprocess.SubprocessError):
+        return None
+    m = re.search(r"sclk clock level.*?\((\d+)Mhz\)", out)
+    return int(m.group(1)) if m else None
+
+
+def _spread(times):
+    t = sorted(times)
+    return {"median_s": float(np.median(t)), "min_s": t[0], "max_s": t[-1], "reps": len(t)}
+
+
+def formats(args):
+    """The --formats leg (see the module docstring)."""
+    import torch
+
+    from flac_codec_amd import _lib
+    from flac_codec_amd.gpu import Decoder, decode_many
+
+    blobs = make_blobs("clips")
+    new_abi = hasattr(_lib, "OutFormat")
+    dec = Decoder(0)
+    scale = {"float32": 2.0 ** -15, "int16": None}
+
+    def legacy(dtype):   # (a): the parent's only output, then a second pass over HBM in torch
+        flat, streams = decode_many(blobs, out="device", verify_md5=False, decoder=dec)
+        T = max(s.info.decoded_samples for s in streams)
+        batch = torch.zeros((len(streams), 1, T), dtype=getattr(torch, dtype), device=flat.device)
+        for i, s in enumerate(streams):   # mono: [samples, 1] -> [1, samples]
+            row = s.pcm.T
+            batch[i, :, :row.shape[1]] = row.to(torch.float32) * scale[dtype] if scale[dtype] else row.to(torch.int16)
+        return batch
+
+    def legacy_equal_lengths(dtype):   # (a) at its best: every clip as long as the others, one reshape
+        flat, streams = decode_many(blobs, out="device", verify_md5=False, decoder=dec)
+        v = flat.view(len(streams), 1, -1)
+        return v.to(torch.float32) * scale[dtype] if scale[dtype] else v.to(torch.int16)
+
+    def fused(dtype):    # (b)
+        return decode_many(blobs, out="device", verify_md5=False, decoder=dec, dtype=dtype, layout="padded")[0]
+
+    def default():
+        return decode_many(blobs, out="device", verify_md5=False, decoder=dec)[0]
+
+    legs = {"int32_flat_default": default}
+    if new_abi and args.label == "this":
+        for dt in ("float32", "int16"):
+            legs[f"a_int32_then_torch_{dt}"] = (lambda dt=dt: legacy(dt))
+            legs[f"a_equal_lengths_reshape_{dt}"] = (lambda dt=dt: legacy_equal_lengths(dt))
+            legs[f"b_decode_as_padded_{dt}"] = (lambda dt=dt: fused(dt))
+    if args.kernels_only:
+        for fn in legs.values():
+            fn()
+            fn()
+        torch.cuda.synchronize()
+        dec.close()
+        return
+    res = {"tool": "tools/decode_many_probe.py --formats", "workload": "clips: 1024 x 10 s, 16 kHz mono 16-bit",
+           "device_output": True, "md5": False, "runs": {}}
+    if os.path.exists(args.out):
+        with open(args.out) as f:
+            res = json.load(f)
+    rec = {"build_id": _lib.build_id(), "sclk_mhz_before": _sclk_mhz(), "legs": {}}
+    if new_abi and args.label == "this":   # (a) and (b) give the same tensor
+        for dt in ("float32", "int16"):
+            assert torch.equal(legacy(dt), fused(dt)) and torch.equal(legacy_equal_lengths(dt), fused(dt))
+    for name, fn in legs.items():
+        fn()
+        torch.cuda.synchronize()   # warm: buffers grown, code loaded
+        times = []
+        for _ in range(args.reps):
+            t0 = time.perf_counter()
+            out = fn()
+            torch.cuda.synchronize()
+            times.append(time.perf_counter() - t0)
+        rec["legs"][name] = dict(_spread(times), output_bytes=int(out.numel() * out.element_size()))
+        del out
+    rec["sclk_mhz_after"] = _sclk_mhz()
+    res["runs"][args.label] = rec
+    dec.close()
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps({args.label: rec}, indent=1), flush=True)
+
+
 def run(args):
     res = {"tool": "tools/decode_many_probe.py", "copy_rate_TBps": COPY_TBPS, "workloads": {}}
     if os.path.exists(args.out):
@@ -169,7 +270,8 @@ def merge_stats(args):
             rows[r["Name"]] = {"calls": int(r["Calls"]), "total_ms": float(r["TotalDurationNs"]) / 1e6,
                                "avg_ms": float(r["AverageNs"]) / 1e6}
     mine = {k: v for k, v in rows.items() if any(s in k for s in ("k_scan_", "k_link", "k_decode_many", "k_frame_crc",
-                                                                   "k_finish_many", "k_md5_many"))}
+                                                                   "k_finish_many", "k_md5_many", "k_finish_as",
+                                                                   "k_pad_rows"))}
     res.setdefault("kernel_stats", {})[args.stats_label] = mine
     with open(args.out, "w") as f:
         json.dump(res, f, indent=1)
@@ -179,18 +281,27 @@ def merge_stats(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workloads", default="clips,tracks,hour")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r07_decode_many.json"))
+    ap.add_argument("--out")
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--formats", action="store_true", help="the output-format leg: profiles/r09_decode_formats.json")
+    ap.add_argument("--label", default="this", help="--formats: the run's name in the file (this | parent)")
+    ap.add_argument("--package-root", help="--formats: measure the flac_codec_amd of this checkout, not of this one")
     ap.add_argument("--oracle-seconds", type=float, default=20.0)
     ap.add_argument("--merge-stats")
     ap.add_argument("--stats-label", default="run")
     ap.add_argument("--kernels-only", action="store_true", help="one warm decode per workload (for rocprofv3)")
     args = ap.parse_args()
+    if not args.out:
+        args.out = os.path.join(ROOT, "profiles", "r09_decode_formats.json" if args.formats else "r07_decode_many.json")
     if args.merge_stats:
         return merge_stats(args)
+    if args.package_root:
+        sys.path.insert(0, os.path.abspath(args.package_root))
     import torch
 
     torch.cuda.init()   # before the library's first HIP call (else torch sees no GPU)
+    if args.formats:
+        return formats(args)
     if args.kernels_only:
         for name in args.workloads.split(","):   # (the hour's MD5 alone runs > 1 min: left to the timed run)
             blobs = make_blobs(name)
