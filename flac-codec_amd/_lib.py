@@ -187,6 +187,8 @@ def _load():
                                       C.c_uint32, C.c_void_p, C.c_void_p, ip, C.c_uint32,
                                       C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
     L.flacgpu_decode_stream.argtypes = [C.c_char_p, C.c_size_t, C.c_int, ip, C.c_size_t, C.POINTER(StreamInfo)]
+    L.flacgpu_scan_stream_host.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(StreamInfo), C.POINTER(C.c_uint64),
+                                           C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_uint32)]
     L.flacgpu_decoder_create.argtypes = [C.c_int, C.POINTER(vp)]
     L.flacgpu_decoder_destroy.argtypes = [vp]
     L.flacgpu_decoder_destroy.restype = None

@@ -1,8 +1,9 @@
-// decode_many.hip -- batch decoder: many FLAC streams in one call, frames found and decoded on the device, samples
-// to host or device memory, MD5 on the device (include/flacenc_gpu.h "batch decoder").
+// decode_many.hip -- batch decoder: many FLAC streams in one call, metadata parsed by flacgpu_decode_stream's parser
+// (host/flac_stream.cpp), frames found and decoded, samples hashed (MD5) on the device (include/flacenc_gpu.h "batch decoder").
 // One of the translation units of libflacenc_amd.so (gfx950 only).  Kernels: kernels/frame_scan.inc (frame discovery)
 // and kernels/decode_many.inc (decode, CRC-16, finish, MD5); the subframe decoder is decode.inc's, unchanged.
 #include "kernels/types.h"
+#include "flac_stream.h"
 
 #include <stdlib.h>
 #include <string.h>
@@ -21,82 +22,30 @@ namespace {
 
 constexpr uint32_t kSlotTail = 64;   // zero bytes behind every stream's region (at least)
 
-// a device buffer that only grows
-struct DevBuf {
+// a buffer that only grows: device memory, or pinned host memory
+template <bool PINNED> struct GrowBuf {
     void *p = nullptr;
     size_t cap = 0;
+    void release() { (void)(PINNED ? hipHostFree(p) : hipFree(p)); p = nullptr; cap = 0; }
     int ensure(size_t bytes) {
         if (bytes <= cap) return FLACGPU_OK;
         const size_t want = std::max(bytes, cap + cap / 2);
-        (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        HIP_TRY(hipMalloc(&p, want));
+        release();
+        if (PINNED) HIP_TRY(hipHostMalloc(&p, want, hipHostMallocDefault));
+        else HIP_TRY(hipMalloc(&p, want));
         cap = want;
         return FLACGPU_OK;
     }
     template <class T> T *as() const { return static_cast<T *>(p); }
-    ~DevBuf() { (void)hipFree(p); }
+    ~GrowBuf() { release(); }
 };
-struct HostBuf {   // pinned
-    void *p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t bytes) {
-        if (bytes <= cap) return FLACGPU_OK;
-        const size_t want = std::max(bytes, cap + cap / 2);
-        (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-        HIP_TRY(hipHostMalloc(&p, want, hipHostMallocDefault));
-        cap = want;
-        return FLACGPU_OK;
-    }
-    template <class T> T *as() const { return static_cast<T *>(p); }
-    ~HostBuf() { (void)hipHostFree(p); }
-};
-
-// flacgpu_decode_stream's metadata parse (fLaC marker, metadata blocks, STREAMINFO), with its return codes and the
-// fields it leaves in `info` on every path; *frames_at = the first byte behind the metadata
-int parse_metadata(const uint8_t *data, size_t len, flacgpu_stream_info *info, uint32_t *min_frame, size_t *frames_at) {
-    memset(info, 0, sizeof *info);
-    if (!data || len < 42 || memcmp(data, "fLaC", 4) != 0) return FLACGPU_ERR_INVALID_ARG;
-    size_t pos = 4;
-    bool have_si = false;
-    *min_frame = 0;
-    for (;;) {   // metadata blocks (metadata/mod.rs:257-266): last flag + type, 24-bit length
-        if (pos + 4 > len) return FLACGPU_ERR_INVALID_ARG;
-        const bool last = data[pos] & 0x80;
-        const uint32_t type = data[pos] & 0x7F;
-        const size_t blen = (size_t)data[pos + 1] << 16 | (size_t)data[pos + 2] << 8 | data[pos + 3];
-        pos += 4;
-        if (pos + blen > len) return FLACGPU_ERR_INVALID_ARG;
-        if (type == 0 && blen == 34) {   // STREAMINFO, metadata/mod.rs:1599-1630
-            const uint8_t *b = data + pos;
-            info->min_block = b[0] << 8 | b[1];
-            info->max_block = b[2] << 8 | b[3];
-            *min_frame = b[4] << 16 | b[5] << 8 | b[6];
-            info->sample_rate = (uint32_t)b[10] << 12 | (uint32_t)b[11] << 4 | b[12] >> 4;
-            info->channels = ((b[12] >> 1) & 7) + 1;
-            info->bits_per_sample = (((uint32_t)b[12] & 1) << 4 | b[13] >> 4) + 1;
-            info->total_samples = ((uint64_t)(b[13] & 15) << 32) | (uint64_t)b[14] << 24 | (uint64_t)b[15] << 16 |
-                                  (uint64_t)b[16] << 8 | b[17];
-            memcpy(info->md5, b + 18, 16);
-            have_si = true;
-        }
-        pos += blen;
-        if (last) break;
-    }
-    if (!have_si || info->channels > 8 || info->bits_per_sample > 32 || info->max_block < 1)
-        return FLACGPU_ERR_INVALID_ARG;
-    *frames_at = pos;
-    return FLACGPU_OK;
-}
+using DevBuf = GrowBuf<false>;
 }  // namespace
 
 struct flacgpu_decoder {
     int device = 0;
     hipStream_t st = nullptr;
-    HostBuf staging;   // the batch buffer on its way up
+    GrowBuf<true> staging;   // pinned: the batch buffer on its way up
     DevBuf bytes, slots, mask, plocal, wg_cnt, wg_tail, wg_off, wg_carry;
     DevBuf cand_pos, cand_info, cand_crc, cand_slot, slot_cand0, slot_pend, link;
     DevBuf frames, scratch, codes, counts, jobs, digest, out_stage;
@@ -125,7 +74,8 @@ int scan_impl(flacgpu_decoder *d, const uint8_t *const *data, const size_t *len,
         flacgpu_decoded_stream &r = d->res[i];
         uint32_t min_frame = 0;
         size_t pos = 0;
-        r.rc = parse_metadata(data ? data[i] : nullptr, len ? len[i] : 0, &r.info, &min_frame, &pos);
+        const char *why = flacenc::parse_metadata(data ? data[i] : nullptr, len ? len[i] : 0, &r.info, &min_frame, &pos);
+        r.rc = why ? FLACGPU_ERR_INVALID_ARG : FLACGPU_OK;
         if (r.rc != FLACGPU_OK || pos >= len[i]) continue;   // no frame region: 0 frames, nothing bad
         ScanSlot s;
         s.base = at;
@@ -341,10 +291,12 @@ int finish_as_tables(flacgpu_decoder *d, const flacgpu_out_format &fmt, void *ds
     return FLACGPU_OK;
 }
 
-// fmt == nullptr: interleaved int32, streams back to back (flacgpu_decoder_decode); else a validated format other than
-// that one, of out_bytes bytes
-int decode_impl(flacgpu_decoder *d, void *out, size_t cap, uint32_t flags, const flacgpu_out_format *fmt = nullptr,
-                uint64_t out_bytes = 0) {
+// flacgpu_decoder_decode / _decode_as behind their argument checks.  fmt == nullptr: interleaved int32, streams back to
+// back; else a validated format other than that one, of out_bytes bytes.  d->res keeps the scan's records (a second
+// decode of the same scan starts from them); `streams` gets them completed, after everything that can fail.
+int decode_impl(flacgpu_decoder *d, void *out, uint32_t flags, flacgpu_decoded_stream *streams,
+                const flacgpu_out_format *fmt = nullptr, uint64_t out_bytes = 0) {
+    DeviceGuard guard(d->device);
     const uint32_t n = (uint32_t)d->res.size();
     const uint32_t F = (uint32_t)d->frame_tab.size(), S = d->n_slots;
     const bool to_device = flags & FLACGPU_DECODE_OUT_DEVICE, md5 = !(flags & FLACGPU_DECODE_NO_MD5);
@@ -425,9 +377,9 @@ int decode_impl(flacgpu_decoder *d, void *out, size_t cap, uint32_t flags, const
     if (!to_device && out_bytes)
         HIP_TRY(hipMemcpyAsync(out, dst, out_bytes, hipMemcpyDeviceToHost, d->st));
     HIP_TRY(hipStreamSynchronize(d->st));
-    (void)cap;
+    if (n) memcpy(streams, d->res.data(), sizeof(flacgpu_decoded_stream) * n);
     for (uint32_t i = 0; i < n; i++) {
-        flacgpu_decoded_stream &r = d->res[i];
+        flacgpu_decoded_stream &r = streams[i];
         const int32_t s = d->slot_of[i];
         if (s >= 0 && r.info.frames) {
             r.info.bad_frames += counts[2 * (size_t)s];
@@ -436,7 +388,7 @@ int decode_impl(flacgpu_decoder *d, void *out, size_t cap, uint32_t flags, const
         if (r.rc == FLACGPU_OK && !md5) r.info.md5_status = 3;
     }
     for (uint32_t j = 0; j < J; j++) {
-        flacgpu_stream_info &info = d->res[job_stream[j]].info;
+        flacgpu_stream_info &info = streams[job_stream[j]].info;
         memcpy(info.decoded_md5, &digest[5 * (size_t)j], 16);
         info.md5_status = digest[5 * (size_t)j + 4];
     }
@@ -490,11 +442,8 @@ int flacgpu_decoder_scan(flacgpu_decoder *d, const uint8_t *const *data, const s
                          flacgpu_decoded_stream *streams, uint64_t *total_samples) {
     if (!d || (n_streams && (!data || !len || !streams)) || !total_samples) return FLACGPU_ERR_INVALID_ARG;
     d->scanned = false;
-    int prev = -1;
-    const bool moved = hipGetDevice(&prev) == hipSuccess && prev != d->device && hipSetDevice(d->device) == hipSuccess;
-    const int rc = scan_impl(d, data, len, n_streams);
-    if (moved) (void)hipSetDevice(prev);
-    if (rc != FLACGPU_OK) return rc;
+    DeviceGuard guard(d->device);
+    if (int rc = scan_impl(d, data, len, n_streams)) return rc;
     d->scanned = true;
     if (n_streams) memcpy(streams, d->res.data(), sizeof(flacgpu_decoded_stream) * n_streams);
     *total_samples = d->total;
@@ -513,15 +462,7 @@ int flacgpu_decoder_decode(flacgpu_decoder *d, int32_t *out, size_t out_cap_samp
         g_last_error = "output buffer too small";
         return FLACGPU_ERR_BUFFER_TOO_SMALL;
     }
-    int prev = -1;
-    const bool moved = hipGetDevice(&prev) == hipSuccess && prev != d->device && hipSetDevice(d->device) == hipSuccess;
-    std::vector<flacgpu_decoded_stream> keep = d->res;   // a second decode of the same scan starts from the scan's records
-    const int rc = decode_impl(d, out, out_cap_samples, flags);
-    if (moved) (void)hipSetDevice(prev);
-    if (rc == FLACGPU_OK && !d->res.empty())
-        memcpy(streams, d->res.data(), sizeof(flacgpu_decoded_stream) * d->res.size());
-    d->res.swap(keep);
-    return rc;
+    return decode_impl(d, out, flags, streams);
 }
 
 int flacgpu_decoder_plan_output(const flacgpu_out_format *fmt, const flacgpu_decoded_stream *streams,
@@ -592,13 +533,5 @@ int flacgpu_decoder_decode_as(flacgpu_decoder *d, void *out, size_t out_cap_byte
         g_last_error = "flacgpu_decoder_decode_as: out is not aligned to its element size";
         return FLACGPU_ERR_INVALID_ARG;
     }
-    int prev = -1;
-    const bool moved = hipGetDevice(&prev) == hipSuccess && prev != d->device && hipSetDevice(d->device) == hipSuccess;
-    std::vector<flacgpu_decoded_stream> keep = d->res;   // as flacgpu_decoder_decode: the scan's records stay
-    const int rc = decode_impl(d, out, out_cap_bytes, flags, fmt, out_bytes);
-    if (moved) (void)hipSetDevice(prev);
-    if (rc == FLACGPU_OK && !d->res.empty())
-        memcpy(streams, d->res.data(), sizeof(flacgpu_decoded_stream) * d->res.size());
-    d->res.swap(keep);
-    return rc;
+    return decode_impl(d, out, flags, streams, fmt, out_bytes);
 }

@@ -50,9 +50,11 @@ uint16_t crc16(const uint8_t *p, size_t n) {
         uint8_t b1 = static_cast<uint8_t>(p[i + 1] ^ (c & 0xFF));
         c = static_cast<uint16_t>(kCrc16.t[3][b0] ^ kCrc16.t[2][b1] ^ kCrc16.t[1][p[i + 2]] ^ kCrc16.t[0][p[i + 3]]);
     }
-    for (; i < n; i++) c = static_cast<uint16_t>(kCrc16.t[0][(c >> 8) ^ p[i]] ^ (c << 8));
+    for (; i < n; i++) c = crc16_step(kCrc16.t[0], c, p[i]);
     return c;
 }
+
+const uint16_t *crc16_table() { return kCrc16.t[0]; }
 
 // ---- MD5, RFC 1321 ----
 namespace {

@@ -9,6 +9,10 @@ namespace flacenc {
 
 uint8_t crc8(const uint8_t *p, size_t n);
 uint16_t crc16(const uint8_t *p, size_t n);
+const uint16_t *crc16_table();   // T of crc16_step: the CRC-16 continued over one byte
+inline uint16_t crc16_step(const uint16_t *T, uint16_t crc, uint8_t byte) {
+    return static_cast<uint16_t>(T[(crc >> 8) ^ byte] ^ (crc << 8));
+}
 
 class Md5 {
 public:

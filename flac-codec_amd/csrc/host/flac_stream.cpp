@@ -1,0 +1,154 @@
+#include "flac_stream.h"
+
+#include <algorithm>
+#include <cstring>
+
+#include "checksums.h"
+
+namespace flacenc {
+const char *parse_metadata(const uint8_t *data, size_t len, flacgpu_stream_info *info, uint32_t *min_frame,
+                           size_t *frames_at) {
+    memset(info, 0, sizeof *info);
+    *min_frame = 0;
+    if (!data || len < 42 || memcmp(data, "fLaC", 4) != 0) return "not a FLAC stream (no fLaC marker)";
+    size_t pos = 4;
+    bool have_si = false;
+    for (;;) {   // metadata blocks (metadata/mod.rs:257-266): last flag + type, 24-bit length
+        if (pos + 4 > len) return "";
+        const bool last = data[pos] & 0x80;
+        const uint32_t type = data[pos] & 0x7F;
+        const size_t blen = (size_t)data[pos + 1] << 16 | (size_t)data[pos + 2] << 8 | data[pos + 3];
+        pos += 4;
+        if (pos + blen > len) return "";
+        if (type == 0 && blen == 34) {   // STREAMINFO, metadata/mod.rs:1599-1630
+            const uint8_t *b = data + pos;
+            info->min_block = b[0] << 8 | b[1];
+            info->max_block = b[2] << 8 | b[3];
+            *min_frame = b[4] << 16 | b[5] << 8 | b[6];
+            info->sample_rate = (uint32_t)b[10] << 12 | (uint32_t)b[11] << 4 | b[12] >> 4;
+            info->channels = ((b[12] >> 1) & 7) + 1;
+            info->bits_per_sample = (((uint32_t)b[12] & 1) << 4 | b[13] >> 4) + 1;
+            info->total_samples = ((uint64_t)(b[13] & 15) << 32) | (uint64_t)b[14] << 24 | (uint64_t)b[15] << 16 |
+                                  (uint64_t)b[16] << 8 | b[17];
+            memcpy(info->md5, b + 18, 16);
+            have_si = true;
+        }
+        pos += blen;
+        if (last) break;
+    }
+    if (!have_si || info->channels > 8 || info->bits_per_sample > 32 || info->max_block < 1)
+        return "no usable STREAMINFO block";
+    *frames_at = pos;
+    return nullptr;
+}
+
+bool host_parse_header(const uint8_t *d, size_t avail, HostFrameHead &h) {
+    if (avail < 6 || d[0] != 0xFF || (d[1] & 0xFE) != 0xF8) return false;
+    h.blocking = d[1] & 1;
+    const uint32_t bcode = d[2] >> 4, rcode = d[2] & 15;
+    h.acode = d[3] >> 4;
+    h.bps_code = (d[3] >> 1) & 7;
+    if ((d[3] & 1) || h.acode > 10 || bcode == 0 || rcode == 15 || h.bps_code == 3) return false;
+    size_t k = 4;
+    {   // UTF-8 like number
+        const uint8_t b0 = d[k];
+        uint32_t ones = 0;
+        while (ones < 8 && (b0 & (0x80 >> ones))) ones++;
+        if (ones == 1 || ones > 7) return false;
+        const uint32_t extra = ones ? ones - 1 : 0;
+        if (k + 1 + extra > avail) return false;
+        for (uint32_t i = 1; i <= extra; i++)
+            if ((d[k + i] & 0xC0) != 0x80) return false;
+        k += 1 + extra;
+    }
+    switch (bcode) {
+    case 1: h.n = 192; break;
+    case 2: h.n = 576; break;
+    case 3: h.n = 1152; break;
+    case 4: h.n = 2304; break;
+    case 5: h.n = 4608; break;
+    case 6:
+        if (k + 1 > avail) return false;
+        h.n = d[k] + 1u;
+        k += 1;
+        break;
+    case 7:
+        if (k + 2 > avail) return false;
+        h.n = ((uint32_t)d[k] << 8 | d[k + 1]) + 1u;
+        k += 2;
+        break;
+    default: h.n = 256u << (bcode - 8); break;
+    }
+    if (rcode == 12) k += 1;
+    else if (rcode == 13 || rcode == 14) k += 2;
+    if (k + 1 > avail) return false;
+    if (crc8(d, k) != d[k]) return false;
+    h.header_bytes = (uint32_t)k + 1;
+    return true;
+}
+
+void scan_frames(const uint8_t *data, size_t len, size_t pos, uint32_t min_frame, flacgpu_stream_info *info, FrameScan &scan) {
+    const uint16_t *const T = crc16_table();   // taken once: the inner loop is one table step per byte
+    size_t p = pos;
+    while (p < len) {
+        HostFrameHead h;
+        if (!host_parse_header(data + p, len - p, h)) {
+            info->bad_frames++;
+            break;   // lost synchronisation: what follows is not decoded
+        }
+        uint16_t crc = 0, d1 = 0, d2 = 0;   // the CRC-16 of [p, q), of [p, q - 1), of [p, q - 2)
+        size_t q = p, end = 0;
+        const size_t min_end = p + std::max<size_t>(h.header_bytes + 2 + info->channels, min_frame);
+        for (; q < len; q++) {
+            // candidate: a header starts at q and bytes [q-2, q) are the CRC-16 of [p, q-2)
+            if (q >= min_end && q >= p + 2 && data[q] == 0xFF && (data[q + (q + 1 < len ? 1 : 0)] & 0xFE) == 0xF8 &&
+                (uint16_t)(data[q - 2] << 8 | data[q - 1]) == d2) {
+                HostFrameHead hn;
+                if (host_parse_header(data + q, len - q, hn) && hn.blocking == h.blocking) {
+                    end = q;
+                    break;
+                }
+            }
+            d2 = d1;
+            d1 = crc;
+            crc = crc16_step(T, crc, data[q]);
+        }
+        if (!end) {   // the last frame ends with the stream
+            if (q == len && len >= p + 2 && (uint16_t)(data[len - 2] << 8 | data[len - 1]) == d2) end = len;
+            else {
+                info->bad_frames++;
+                break;
+            }
+        }
+        scan.off.push_back(p);
+        scan.n.push_back(h.n);
+        info->decoded_samples += h.n;
+        p = end;
+    }
+    scan.off.push_back(p);
+    info->frames = (uint32_t)scan.n.size();
+}
+
+void finish_stream(const int32_t *planar, size_t ldb, const std::vector<uint32_t> &frame_n, int32_t *out,
+                   flacgpu_stream_info *info) {
+    const size_t F = frame_n.size(), C = info->channels;
+    Md5 md5;
+    const unsigned width = (info->bits_per_sample + 7) / 8;
+    std::vector<uint8_t> le(*std::max_element(frame_n.begin(), frame_n.end()) * C * width);
+    size_t o = 0;
+    for (size_t f = 0; f < F; f++) {
+        const size_t n = frame_n[f];
+        size_t k = 0;
+        for (size_t i = 0; i < n; i++)
+            for (size_t ch = 0; ch < C; ch++) {
+                const int32_t v = planar[(f * C + ch) * ldb + i];
+                if (out) out[o++] = v;
+                for (unsigned w = 0; w < width; w++) le[k++] = (uint8_t)((uint32_t)v >> (8 * w));
+            }
+        md5.update(le.data(), k);
+    }
+    const uint8_t zero[16] = {0};
+    md5.digest(info->decoded_md5);
+    info->md5_status = memcmp(info->md5, zero, 16) == 0 ? 2 : (memcmp(info->md5, info->decoded_md5, 16) == 0 ? 1 : 0);
+}
+}  // namespace flacenc

@@ -1,0 +1,37 @@
+// flac_stream.h -- the host's view of a FLAC stream of any origin, for both decoders (decode.hip, decode_many.hip):
+// metadata, frame headers, the scan for frame boundaries, and the tail that interleaves and hashes the decoded PCM.
+// Plain C++: no HIP call, no global state; every byte read is bounded by the length given.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+#include "flacenc_gpu.h"
+
+namespace flacenc {
+// fLaC marker, metadata blocks, STREAMINFO.  `info` is zeroed first and the STREAMINFO fields are filled as soon as the
+// block is seen, also when a later block is truncated.  Returns nullptr and *min_frame = STREAMINFO's minimum frame size
+// (0: unknown), *frames_at = the first byte behind the metadata; or why the stream is refused (FLACGPU_ERR_INVALID_ARG
+// to the caller): the last-error text, "" for a truncated block list, which sets none.
+const char *parse_metadata(const uint8_t *data, size_t len, flacgpu_stream_info *info, uint32_t *min_frame,
+                           size_t *frames_at);
+
+struct HostFrameHead {
+    uint32_t n = 0, header_bytes = 0, blocking = 0, acode = 0, bps_code = 0;
+};
+// FrameHeader::parse (stream.rs:214-240) + CRC-8 on `avail` bytes
+bool host_parse_header(const uint8_t *d, size_t avail, HostFrameHead &h);
+
+struct FrameScan {
+    std::vector<uint64_t> off;   // [frames + 1] frame starts, then where the scan stopped
+    std::vector<uint32_t> n;     // [frames] block sizes
+};
+// The frames of data[pos, len), by the rule of DESIGN.md "The scan finds the host scan's frames, for any bytes"; fills
+// info->frames, decoded_samples and bad_frames (1: the scan lost synchronisation) for the channels `info` names.
+void scan_frames(const uint8_t *data, size_t len, size_t pos, uint32_t min_frame, flacgpu_stream_info *info, FrameScan &scan);
+
+// The decoded frames (at least one), planar [frame][channel][ldb], interleaved into `out` (may be null) and hashed as
+// ceil(bps / 8)-byte little-endian samples (decode.rs:1282 verify): fills info->decoded_md5 and info->md5_status.
+void finish_stream(const int32_t *planar, size_t ldb, const std::vector<uint32_t> &frame_n, int32_t *out,
+                   flacgpu_stream_info *info);
+}  // namespace flacenc

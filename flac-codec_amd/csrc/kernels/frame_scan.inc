@@ -84,7 +84,7 @@ __device__ __forceinline__ uint32_t crc16_bytes(uint32_t crc, const uint8_t *p, 
     return crc;
 }
 
-// host_parse_header (flacenc_gpu.hip) on the device: FrameHeader::parse (stream.rs:214-240) + CRC-8, every read
+// host_parse_header (host/flac_stream.cpp) on the device: FrameHeader::parse (stream.rs:214-240) + CRC-8, every read
 // bounded by `avail` = bytes left in the stream.
 struct ScanHead {
     uint32_t n, header_bytes, blocking;

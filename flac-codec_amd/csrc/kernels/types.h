@@ -30,6 +30,19 @@ extern thread_local std::string g_last_error;  // defined in flacenc_gpu.hip
         }                                                                               \
     } while (0)
 
+// Every entry point runs with its context's (or decoder's) device current and restores the caller's device on the way
+// out (a context may be created on one thread and used from another, whose current device is a different GPU).
+struct DeviceGuard {
+    int prev = -1;
+    bool changed = false;
+    explicit DeviceGuard(int dev) {
+        if (hipGetDevice(&prev) == hipSuccess && prev != dev) changed = hipSetDevice(dev) == hipSuccess;
+    }
+    ~DeviceGuard() { if (changed) (void)hipSetDevice(prev); }
+    DeviceGuard(const DeviceGuard &) = delete;
+    DeviceGuard &operator=(const DeviceGuard &) = delete;
+};
+
 // ---------------------------------------------------------------------------------
 // device-side records
 // ---------------------------------------------------------------------------------

@@ -390,6 +390,24 @@ def decode_stream(data, device=-1, want_pcm=True):
     return out, info
 
 
+def scan_stream_host(data):
+    """flacgpu_scan_stream_host: the metadata parse and frame scan flacgpu_decode_stream starts with, on the host alone
+    (no GPU needed).  Returns (StreamInfo, frame start offsets, block sizes)."""
+    L = _lib.lib()
+    info = _lib.StreamInfo()
+    data = bytes(data)
+    n = C.c_uint32(0)
+    rc = L.flacgpu_scan_stream_host(data, len(data), C.byref(info), None, None, 0, C.byref(n))   # the count
+    if rc:
+        raise GpuError(rc, "flacgpu_scan_stream_host")
+    offsets, sizes = np.empty(n.value, dtype=np.uint64), np.empty(n.value, dtype=np.uint32)
+    rc = L.flacgpu_scan_stream_host(data, len(data), C.byref(info), offsets.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                    sizes.ctypes.data_as(C.POINTER(C.c_uint32)), n.value, C.byref(n))
+    if rc:
+        raise GpuError(rc, "flacgpu_scan_stream_host")
+    return info, offsets, sizes
+
+
 class DecodedStream:
     """One stream of a decode_many batch: rc (what flacgpu_decode_stream returns for it), info (StreamInfo), offset
     (first element in the flat output) and pcm (a [samples, channels] view of the flat output, or the

@@ -507,6 +507,14 @@ typedef struct {
 } flacgpu_stream_info;
 int flacgpu_decode_stream(const uint8_t *data, size_t len, int device, int32_t *out, size_t out_cap_samples,
                           flacgpu_stream_info *info);
+/* The host half of flacgpu_decode_stream alone: the metadata parse and the frame scan, the very code that call starts
+ * with.  Makes no HIP call and needs no device.  Returns what flacgpu_decode_stream returns for the metadata; fills
+ * `info` as it stands after the scan (STREAMINFO fields, frames, decoded_samples, bad_frames = 1 when the scan lost
+ * synchronisation; the CRC-16 and MD5 fields stay 0) and *n_frames = info->frames.  frame_off / frame_n (either may be
+ * NULL: the count alone) receive every frame's first byte in `data` and its block size; with one given and
+ * cap < *n_frames the call writes neither and returns FLACGPU_ERR_BUFFER_TOO_SMALL. */
+int flacgpu_scan_stream_host(const uint8_t *data, size_t len, flacgpu_stream_info *info, uint64_t *frame_off,
+                             uint32_t *frame_n, size_t cap, uint32_t *n_frames);
 
 /* ---- batch decoder: many FLAC streams in one call, into host or device memory -------------------------------------
  * The same result as flacgpu_decode_stream for every stream (rc, every field of `info`, the samples), for any bytes,

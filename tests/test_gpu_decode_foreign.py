@@ -130,3 +130,40 @@ def test_invalid_subframes_are_refused_without_a_stray_write():
             n_bad = st.pcm.size - 2 * 192
             assert np.array_equal(mine[:192], st.pcm[:192]) and np.array_equal(mine[192 + n_bad:], st.pcm[192 + n_bad:])
             assert np.array_equal(sout[:192], st.pcm[:192]) and np.array_equal(sout[192 + n_bad:], st.pcm[192 + n_bad:])
+
+
+def test_three_scans_agree_on_the_matrix_and_on_damaged_streams():
+    """flacgpu_scan_stream_host (no device), flacgpu_decoder_scan's records before any decode (metadata on the host, frames
+    found on the device) and flacgpu_decode_stream give the same rc, frames, decoded_samples, scan-time bad_frames and
+    STREAMINFO fields, for the matrix and for the damaged streams of test_stream_scan.py.  flacgpu_decode_stream adds the
+    frames that do not decode to bad_frames: there are none where every frame the scan kept is a valid frame of the matrix
+    byte for byte, and elsewhere at most as many as the other frames kept."""
+    import _scan_model as model
+    from flac_codec_amd import _lib
+    from flac_codec_amd.gpu import Decoder
+
+    L = _lib.lib()
+    blobs = [(st.name, st.blob) for st in fm.valid_cases()] + [(r, st.blob) for r, st in fm.invalid_cases()] + \
+        list(model.damaged_cases())
+    pristine = {c for st in fm.valid_cases() for c in st.frame_bytes}
+    dec = Decoder(0)
+    try:
+        recs, _ = dec.scan([b for _, b in blobs])
+    finally:
+        dec.close()
+    scan_fields = ["frames", "decoded_samples", "bad_frames"] + model.STREAMINFO_FIELDS
+    for (label, blob), rec in zip(blobs, recs):
+        info, n = _lib.StreamInfo(), C.c_uint32(0)
+        rc = L.flacgpu_scan_stream_host(blob, len(blob), C.byref(info), None, None, 0, C.byref(n))
+        off = np.zeros(n.value, np.uint64)
+        assert rc == L.flacgpu_scan_stream_host(blob, len(blob), C.byref(info), off.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                None, n.value, C.byref(n)), label
+        host = {f: _val(info, f) for f in scan_fields}
+        assert (rec.rc, {f: _val(rec.info, f) for f in scan_fields}) == (rc, host), label
+        src, sinfo, _ = _single(blob)
+        single = {f: _val(sinfo, f) for f in scan_fields}
+        ends = off.tolist()[1:] + [len(blob) if not info.bad_frames else None]   # (lost sync: the last end is not reported)
+        other = sum(1 for a, b in zip(off.tolist(), ends)
+                    if (blob[a:b] not in pristine if b else not any(blob.startswith(c, a) for c in pristine)))
+        extra = single.pop("bad_frames") - host.pop("bad_frames")
+        assert (src, single) == (rc, host) and 0 <= extra <= other, label
