@@ -102,6 +102,17 @@ class OutFormat(C.Structure):
                 ("reserved", C.c_uint32), ("samples_padded", C.c_uint64)]
 
 
+class Window(C.Structure):
+    """flacgpu_window: samples [start, start + length) per channel of one scanned stream."""
+    _fields_ = [("stream", C.c_uint32), ("reserved", C.c_uint32), ("start", C.c_uint64), ("length", C.c_uint64)]
+
+
+class WindowResult(C.Structure):
+    """flacgpu_window_result: one window's record of flacgpu_decoder_decode_windows."""
+    _fields_ = [("rc", C.c_int32), ("frames", C.c_uint32), ("bad_frames", C.c_uint32), ("bad_crc16", C.c_uint32),
+                ("samples", C.c_uint64)]
+
+
 class ShardCounters(C.Structure):
     """flacgpu_shard_counters: the four integers that cross shards of a stream (include/flacenc_gpu.h)."""
     _fields_ = [("frames", C.c_uint64), ("bytes", C.c_uint64), ("min_frame", C.c_uint64), ("max_frame", C.c_uint64)]
@@ -199,6 +210,12 @@ def _load():
                                               C.POINTER(C.c_uint64)]
     L.flacgpu_decoder_decode_as.argtypes = [vp, vp, C.c_size_t, C.POINTER(OutFormat), C.c_uint32,
                                             C.POINTER(DecodedStream)]
+    L.flacgpu_decoder_plan_windows.argtypes = [C.POINTER(OutFormat), C.POINTER(DecodedStream), C.c_uint32,
+                                               C.POINTER(Window), C.c_uint32, C.POINTER(C.c_uint64)]
+    L.flacgpu_decoder_decode_windows.argtypes = [vp, vp, C.c_size_t, C.POINTER(OutFormat), C.c_uint32,
+                                                 C.POINTER(Window), C.c_uint32, C.POINTER(WindowResult)]
+    L.flacgpu_window_frames.argtypes = [C.POINTER(C.c_uint32), C.c_uint32, C.c_uint64, C.c_uint64,
+                                        C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
     L.flacgpu_pack_plans.argtypes = [vp, ip, C.c_uint32, C.c_uint32, C.POINTER(FramePlan), C.POINTER(SubframePlan),
                                      C.c_uint64, C.c_uint32]
     L.flacgpu_host_alloc.argtypes = [C.c_size_t]

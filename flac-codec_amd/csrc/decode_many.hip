@@ -50,6 +50,7 @@ struct flacgpu_decoder {
     DevBuf cand_pos, cand_info, cand_crc, cand_slot, slot_cand0, slot_pend, link;
     DevBuf frames, scratch, codes, counts, jobs, digest, out_stage;
     DevBuf md5_stage, pad_out, pad_streams;   // decode_as: interleaved int32 for the MD5, padded layout tables
+    DevBuf win_frames, win_desc;              // decode_windows: the selected frames (d->frames stays the scan's)
     // the scanned batch
     bool scanned = false;
     std::vector<flacgpu_decoded_stream> res;
@@ -58,6 +59,10 @@ struct flacgpu_decoder {
     std::vector<ManyFrame> frame_tab;
     uint32_t n_slots = 0;
     uint64_t total = 0, scratch_total = 0;
+    // decode_windows' index of frame_tab: slot s owns frames [slot_frame0[s], slot_frame0[s + 1]); frame_first is a
+    // frame's first sample per channel in its stream
+    std::vector<uint32_t> slot_frame0;
+    std::vector<uint64_t> frame_first;
 };
 
 namespace {
@@ -394,6 +399,155 @@ int decode_impl(flacgpu_decoder *d, void *out, uint32_t flags, flacgpu_decoded_s
     }
     return FLACGPU_OK;
 }
+
+// ---- sample windows ----
+// The frames of a stream that samples [start, start + length) touch.  first_of(i) is the first sample of frame i of
+// the stream's n_frames, rising; the stream has `total` samples.  A window that is empty or lies past the end touches
+// none.  skip: the samples of frame `first` in front of `start`.
+template <class FirstOf>
+void window_frames(FirstOf first_of, uint32_t n_frames, uint64_t total, uint64_t start, uint64_t length,
+                   uint32_t *first, uint32_t *count, uint64_t *skip) {
+    *first = *count = 0;
+    *skip = 0;
+    const uint64_t end = std::min(start + length, total);
+    if (start >= end) return;
+    const auto holding = [&](uint64_t sample) {   // the last frame that starts at or before `sample`
+        uint32_t lo = 0, hi = n_frames;
+        while (hi - lo > 1) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if (first_of(mid) <= sample) lo = mid;
+            else hi = mid;
+        }
+        return lo;
+    };
+    *first = holding(start);
+    *count = holding(end - 1) - *first + 1;
+    *skip = start - first_of(*first);
+}
+
+void index_frames(flacgpu_decoder *d) {
+    const size_t F = d->frame_tab.size();
+    d->slot_frame0.assign((size_t)d->n_slots + 1, (uint32_t)F);
+    d->frame_first.resize(F);
+    for (size_t f = F; f-- > 0;) {
+        const ManyFrame &fr = d->frame_tab[f];
+        d->slot_frame0[fr.slot] = (uint32_t)f;
+        d->frame_first[f] = (fr.out - d->res[d->slot_stream[fr.slot]].out_offset) / fr.channels;
+    }
+    for (uint32_t s = d->n_slots; s-- > 0;)   // a slot without frames owns an empty run
+        d->slot_frame0[s] = std::min(d->slot_frame0[s], d->slot_frame0[s + 1]);
+}
+
+// flacgpu_decoder_decode_windows behind its argument checks: out_bytes > 0, every window valid for `fmt`
+int decode_windows_impl(flacgpu_decoder *d, void *out, uint64_t out_bytes, const flacgpu_out_format &fmt, uint32_t flags,
+                        const flacgpu_window *w, uint32_t n_windows, flacgpu_window_result *results) {
+    DeviceGuard guard(d->device);
+    const uint32_t Cp = fmt.channels_padded;
+    const uint64_t T = fmt.samples_padded;
+    if ((uint64_t)n_windows * Cp > 0x7FFFFFFFull) {
+        g_last_error = "flacgpu_decoder_decode_windows: more than 2^31 - 1 padded rows";
+        return FLACGPU_ERR_UNSUPPORTED;
+    }
+    // ---- host: the frames every window touches, compact, with scratch of their own
+    std::vector<ManyFrame> sel;
+    std::vector<WinFrame> desc;
+    std::vector<PadStream> pad(n_windows);
+    uint64_t scratch_total = 0;
+    try {
+        for (uint32_t i = 0; i < n_windows; i++) {
+            const flacgpu_decoded_stream &r = d->res[w[i].stream];
+            flacgpu_window_result &res = results[i];
+            res = flacgpu_window_result{};
+            res.rc = r.rc;
+            pad[i] = PadStream{0, 0, 0};
+            const int32_t s = d->slot_of[w[i].stream];
+            if (r.rc != FLACGPU_OK || s < 0) continue;
+            const uint32_t f0 = d->slot_frame0[s], nf = d->slot_frame0[s + 1] - f0;
+            uint32_t first = 0, count = 0;
+            uint64_t skip = 0;
+            window_frames([&](uint32_t k) { return d->frame_first[f0 + k]; }, nf, r.info.decoded_samples, w[i].start,
+                          w[i].length, &first, &count, &skip);
+            if (!count) continue;
+            res.frames = count;
+            res.samples = std::min(w[i].length, r.info.decoded_samples - w[i].start);
+            pad[i] = PadStream{res.samples, r.info.channels, 0};
+            for (uint32_t k = 0; k < count; k++) {
+                ManyFrame fr = d->frame_tab[f0 + first + k];
+                const uint64_t at = d->frame_first[f0 + first + k];   // the frame's first sample in the stream
+                WinFrame wf{};
+                wf.row = (uint64_t)i * Cp * T;
+                wf.keep_first = k ? 0 : (uint32_t)skip;
+                wf.keep_last = (uint32_t)std::min<uint64_t>(fr.n, w[i].start + res.samples - at);
+                wf.at = at + wf.keep_first - w[i].start;
+                wf.channels = fr.channels;
+                wf.bps = fr.bps;
+                wf.window = i;
+                fr.slot = i;   // k_frame_crc counts per window
+                fr.scratch = scratch_total;
+                scratch_total += (uint64_t)fr.channels * ((fr.n + 3u) & ~3u);
+                sel.push_back(fr);
+                desc.push_back(wf);
+            }
+        }
+    } catch (const std::bad_alloc &) {
+        g_last_error = "flacgpu_decoder_decode_windows: out of host memory";
+        return FLACGPU_ERR_UNSUPPORTED;
+    }
+    if (sel.size() > 0x7FFFFFFFull) {
+        g_last_error = "flacgpu_decoder_decode_windows: more than 2^31 - 1 selected frames";
+        return FLACGPU_ERR_UNSUPPORTED;
+    }
+    const uint32_t F = (uint32_t)sel.size();
+    const bool to_device = flags & FLACGPU_DECODE_OUT_DEVICE;
+    void *dst = out;
+    if (!to_device) {
+        if (int rc = d->out_stage.ensure(out_bytes)) return rc;
+        dst = d->out_stage.p;
+    }
+    if (int rc = d->pad_streams.ensure(sizeof(PadStream) * n_windows)) return rc;
+    if (int rc = d->counts.ensure(8 * (size_t)n_windows)) return rc;
+    if (F) {   // scratch by the selected frames, not by the batch
+        if (int rc = d->win_frames.ensure(sizeof(ManyFrame) * F)) return rc;
+        if (int rc = d->win_desc.ensure(sizeof(WinFrame) * F)) return rc;
+        if (int rc = d->scratch.ensure(4 * scratch_total)) return rc;
+        if (int rc = d->codes.ensure(4 * (size_t)F)) return rc;
+    }
+    HIP_TRY(hipMemcpyAsync(d->pad_streams.p, pad.data(), sizeof(PadStream) * n_windows, hipMemcpyHostToDevice, d->st));
+    HIP_TRY(hipMemsetAsync(d->counts.p, 0, 8 * (size_t)n_windows, d->st));
+    // a window's samples and channels stand where k_pad_rows reads a stream's: it zeroes what no frame writes
+    if (fmt.dtype == FLACGPU_SAMPLE_I16)
+        hipLaunchKernelGGL(k_pad_rows<2>, dim3(n_windows * Cp), dim3(WG), 0, d->st, d->pad_streams.as<const PadStream>(),
+                           Cp, T, static_cast<uint8_t *>(dst));
+    else
+        hipLaunchKernelGGL(k_pad_rows<4>, dim3(n_windows * Cp), dim3(WG), 0, d->st, d->pad_streams.as<const PadStream>(),
+                           Cp, T, static_cast<uint8_t *>(dst));
+    if (F) {
+        HIP_TRY(hipMemcpyAsync(d->win_frames.p, sel.data(), sizeof(ManyFrame) * F, hipMemcpyHostToDevice, d->st));
+        HIP_TRY(hipMemcpyAsync(d->win_desc.p, desc.data(), sizeof(WinFrame) * F, hipMemcpyHostToDevice, d->st));
+        const ManyFrame *frames = d->win_frames.as<const ManyFrame>();
+        const uint32_t lanes = 32;   // as decode_impl launches it
+        hipLaunchKernelGGL(k_decode_many<32>, dim3((F + lanes - 1) / lanes), dim3(lanes), 0, d->st,
+                           d->bytes.as<const uint32_t>(), frames, F, d->scratch.as<int32_t>(), d->codes.as<uint32_t>());
+        hipLaunchKernelGGL(k_frame_crc, dim3(F), dim3(64), 0, d->st, d->bytes.as<const uint8_t>(), frames,
+                           d->counts.as<uint32_t>());
+        const auto k = fmt.dtype == FLACGPU_SAMPLE_I16   ? k_finish_window<DT_I16>
+                       : fmt.dtype == FLACGPU_SAMPLE_F32 ? k_finish_window<DT_F32>
+                                                         : k_finish_window<DT_I32>;
+        hipLaunchKernelGGL(k, dim3(F), dim3(WG), 0, d->st, frames, d->win_desc.as<const WinFrame>(),
+                           d->scratch.as<const int32_t>(), d->codes.as<const uint32_t>(), static_cast<uint8_t *>(dst), T,
+                           d->counts.as<uint32_t>());
+    }
+    HIP_TRY(hipGetLastError());
+    std::vector<uint32_t> counts(2 * (size_t)n_windows);
+    HIP_TRY(hipMemcpyAsync(counts.data(), d->counts.p, 8 * (size_t)n_windows, hipMemcpyDeviceToHost, d->st));
+    if (!to_device) HIP_TRY(hipMemcpyAsync(out, dst, out_bytes, hipMemcpyDeviceToHost, d->st));
+    HIP_TRY(hipStreamSynchronize(d->st));   // the tables leave scope behind this
+    for (uint32_t i = 0; i < n_windows; i++) {
+        results[i].bad_frames = counts[2 * (size_t)i];
+        results[i].bad_crc16 = counts[2 * (size_t)i + 1];
+    }
+    return FLACGPU_OK;
+}
 }  // namespace
 
 int flacgpu_decoder_create(int device, flacgpu_decoder **out) {
@@ -444,6 +598,7 @@ int flacgpu_decoder_scan(flacgpu_decoder *d, const uint8_t *const *data, const s
     d->scanned = false;
     DeviceGuard guard(d->device);
     if (int rc = scan_impl(d, data, len, n_streams)) return rc;
+    index_frames(d);
     d->scanned = true;
     if (n_streams) memcpy(streams, d->res.data(), sizeof(flacgpu_decoded_stream) * n_streams);
     *total_samples = d->total;
@@ -534,4 +689,90 @@ int flacgpu_decoder_decode_as(flacgpu_decoder *d, void *out, size_t out_cap_byte
         return FLACGPU_ERR_INVALID_ARG;
     }
     return decode_impl(d, out, flags, streams, fmt, out_bytes);
+}
+
+int flacgpu_window_frames(const uint32_t *frame_n, uint32_t n_frames, uint64_t start, uint64_t length, uint32_t *first,
+                          uint32_t *count, uint64_t *skip) {
+    uint64_t end = 0;
+    if ((n_frames && !frame_n) || !first || !count || !skip || __builtin_add_overflow(start, length, &end))
+        return FLACGPU_ERR_INVALID_ARG;
+    std::vector<uint64_t> first_of(n_frames);
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < n_frames; i++) {
+        first_of[i] = total;
+        total += frame_n[i];
+    }
+    window_frames([&](uint32_t i) { return first_of[i]; }, n_frames, total, start, length, first, count, skip);
+    return FLACGPU_OK;
+}
+
+int flacgpu_decoder_plan_windows(const flacgpu_out_format *fmt, const flacgpu_decoded_stream *streams,
+                                 uint32_t n_streams, const flacgpu_window *w, uint32_t n_windows, uint64_t *out_bytes) {
+    if (!fmt || !out_bytes || (n_streams && !streams) || (n_windows && !w)) return FLACGPU_ERR_INVALID_ARG;
+    *out_bytes = 0;
+    if (fmt->dtype > FLACGPU_SAMPLE_F32 || fmt->layout != FLACGPU_LAYOUT_PADDED || fmt->reserved) {
+        g_last_error = "flacgpu_decoder_plan_windows: unknown dtype, a layout other than PADDED, or reserved not 0";
+        return FLACGPU_ERR_INVALID_ARG;
+    }
+    for (uint32_t i = 0; i < n_windows; i++) {
+        uint64_t end = 0;
+        if (w[i].stream >= n_streams || w[i].reserved || __builtin_add_overflow(w[i].start, w[i].length, &end)) {
+            g_last_error = "flacgpu_decoder_plan_windows: window " + std::to_string(i) +
+                           " names no stream of the batch, has reserved not 0, or start + length overflows";
+            return FLACGPU_ERR_INVALID_ARG;
+        }
+        const flacgpu_decoded_stream &r = streams[w[i].stream];
+        if (w[i].length > fmt->samples_padded || (r.rc == FLACGPU_OK && r.info.channels > fmt->channels_padded)) {
+            g_last_error = "flacgpu_decoder_plan_windows: window " + std::to_string(i) + " (" +
+                           std::to_string(w[i].length) + " samples of stream " + std::to_string(w[i].stream) +
+                           ") does not fit channels_padded x samples_padded";
+            return FLACGPU_ERR_INVALID_ARG;
+        }
+    }
+    for (uint32_t i = 0; i < n_windows && fmt->dtype == FLACGPU_SAMPLE_I16; i++) {
+        const flacgpu_decoded_stream &r = streams[w[i].stream];
+        if (r.rc == FLACGPU_OK && r.info.bits_per_sample > 16) {
+            g_last_error = "flacgpu_decoder_plan_windows: int16 output, but stream " + std::to_string(w[i].stream) +
+                           " has " + std::to_string(r.info.bits_per_sample) + " bits per sample";
+            return FLACGPU_ERR_UNSUPPORTED;
+        }
+    }
+    uint64_t bytes = 0;
+    if (__builtin_mul_overflow((uint64_t)n_windows * fmt->channels_padded, fmt->samples_padded, &bytes) ||
+        __builtin_mul_overflow(bytes, (uint64_t)elem_size(fmt->dtype), &bytes)) {
+        g_last_error = "flacgpu_decoder_plan_windows: the windows exceed 2^64 bytes";
+        return FLACGPU_ERR_UNSUPPORTED;
+    }
+    *out_bytes = bytes;
+    return FLACGPU_OK;
+}
+
+int flacgpu_decoder_decode_windows(flacgpu_decoder *d, void *out, size_t out_cap_bytes, const flacgpu_out_format *fmt,
+                                   uint32_t flags, const flacgpu_window *w, uint32_t n_windows,
+                                   flacgpu_window_result *results) {
+    if (!d || !fmt || (flags & ~(FLACGPU_DECODE_OUT_DEVICE | FLACGPU_DECODE_NO_MD5))) return FLACGPU_ERR_INVALID_ARG;
+    if (!d->scanned) {
+        g_last_error = "flacgpu_decoder_decode_windows: no scanned batch";
+        return FLACGPU_ERR_INVALID_ARG;
+    }
+    if (n_windows && (!w || !results)) return FLACGPU_ERR_INVALID_ARG;
+    uint64_t out_bytes = 0;
+    if (int rc = flacgpu_decoder_plan_windows(fmt, d->res.data(), (uint32_t)d->res.size(), w, n_windows, &out_bytes))
+        return rc;
+    if (out_bytes && (!out || out_cap_bytes < out_bytes)) {
+        g_last_error = "output buffer too small";
+        return FLACGPU_ERR_BUFFER_TOO_SMALL;
+    }
+    if (reinterpret_cast<uintptr_t>(out) % elem_size(fmt->dtype)) {
+        g_last_error = "flacgpu_decoder_decode_windows: out is not aligned to its element size";
+        return FLACGPU_ERR_INVALID_ARG;
+    }
+    if (!out_bytes) {   // no element to write: every window is empty or on a stream with rc != 0
+        for (uint32_t i = 0; i < n_windows; i++) {
+            results[i] = flacgpu_window_result{};
+            results[i].rc = d->res[w[i].stream].rc;
+        }
+        return FLACGPU_OK;
+    }
+    return decode_windows_impl(d, out, out_bytes, *fmt, flags, w, n_windows, results);
 }

@@ -11,6 +11,8 @@
 //                        int16 / float32 (or left int32) and written flat or into padded planar rows; with MD5 also
 //                        the interleaved int32 that k_md5_many reads
 //   K_d6 k_pad_rows      workgroup per (stream, channel row) of a padded batch: zeroes what no frame writes
+//   K_d7 k_finish_window workgroup per selected frame of a sample window (flacgpu_decoder_decode_windows): k_finish_as's
+//                        arithmetic and conversions on the part of the frame the window keeps, into the window's rows
 
 struct ManyFrame {
     uint64_t start, end;   // byte offsets in the batch buffer: header .. CRC-16 inclusive
@@ -339,4 +341,40 @@ __global__ void __launch_bounds__(64) k_md5_many(const int32_t *__restrict__ out
     digest[5 * (size_t)s + 2] = st[2];
     digest[5 * (size_t)s + 3] = st[3];
     digest[5 * (size_t)s + 4] = none ? 2u : (same ? 1u : 0u);
+}
+
+// ---- sample windows (flacgpu_decoder_decode_windows) ----
+// One selected frame of one window.  The frame's ManyFrame stands at the same index of the compact frame array; its
+// `slot` is the window index there, so that k_frame_crc counts per window.
+struct WinFrame {
+    uint64_t row;          // first element of the window's channel 0 row in the output
+    uint64_t at;           // the row position of the first kept sample: frame start + keep_first - window start
+    uint32_t keep_first;   // samples [keep_first, keep_last) of the frame lie inside the window
+    uint32_t keep_last;
+    uint32_t channels, bps;
+    uint32_t window;
+    uint32_t reserved;
+};
+// Workgroup per selected frame: frame_sample's decorrelation and sample_bits' conversion of the kept samples, planar
+// into the window's rows.  A row position is arbitrary, hence store_run.  A frame that did not parse is counted for
+// its window (win_counts[2 * window]) and written as decoded, as k_finish_as does.
+template <uint32_t DT>
+__global__ void __launch_bounds__(WG) k_finish_window(const ManyFrame *__restrict__ frames,
+                                                      const WinFrame *__restrict__ win,
+                                                      const int32_t *__restrict__ scratch,
+                                                      const uint32_t *__restrict__ codes, uint8_t *__restrict__ out,
+                                                      uint64_t samples_padded, uint32_t *__restrict__ win_counts) {
+    constexpr uint32_t ES = DT == DT_I16 ? 2 : 4;
+    const uint32_t f = blockIdx.x;
+    const ManyFrame fr = frames[f];
+    const WinFrame w = win[f];
+    const uint32_t code = codes[f];
+    const bool bad = code & 0x100u;
+    const uint32_t acode = bad ? 0u : (code & 0xFFu);
+    if (bad && threadIdx.x == 0) atomicAdd(&win_counts[2 * w.window], 1u);
+    const uint32_t ldb = (fr.n + 3u) & ~3u, bps = w.bps;
+    const int32_t *rows = scratch + fr.scratch + w.keep_first;   // sample i of the run is sample keep_first + i
+    for (uint32_t c = 0; c < w.channels; c++)
+        store_run<ES>(out + (w.row + (uint64_t)c * samples_padded + w.at) * ES, w.keep_last - w.keep_first, threadIdx.x,
+                      WG, [&](uint32_t i) { return sample_bits<DT>(frame_sample(rows, ldb, acode, i, c), bps); });
 }

@@ -484,6 +484,47 @@ class Decoder:
             raise GpuError(rc, "flacgpu_decoder_decode_as")
         return recs
 
+    @staticmethod
+    def plan_windows(fmt, recs, n, windows):
+        """flacgpu_decoder_plan_windows: the bytes the windows (a _lib.Window array) take in `fmt` for the first n
+        scanned records."""
+        need = C.c_uint64(0)
+        rc = _lib.lib().flacgpu_decoder_plan_windows(C.byref(fmt), recs, n, windows, len(windows), C.byref(need))
+        if rc:
+            raise GpuError(rc, "flacgpu_decoder_plan_windows")
+        return need.value
+
+    def decode_windows(self, out_ptr, out_cap_bytes, fmt, flags, windows):
+        """flacgpu_decoder_decode_windows of the scanned batch into the buffer at out_ptr (device or host address):
+        `windows` is a _lib.Window array, `fmt` a PADDED _lib.OutFormat.  Returns the _lib.WindowResult array."""
+        n = len(windows)
+        results = (_lib.WindowResult * max(n, 1))()
+        rc = _lib.lib().flacgpu_decoder_decode_windows(self._h, out_ptr, out_cap_bytes, C.byref(fmt), flags, windows, n,
+                                                       results)
+        if rc:
+            raise GpuError(rc, "flacgpu_decoder_decode_windows")
+        return results
+
+
+def window_frames(frame_sizes, start, length):
+    """flacgpu_window_frames: (first, count, skip) of the frames of a stream with these block sizes that samples
+    [start, start + length) touch.  Needs no GPU."""
+    sizes = np.ascontiguousarray(frame_sizes, dtype=np.uint32)
+    first, count, skip = C.c_uint32(0), C.c_uint32(0), C.c_uint64(0)
+    rc = _lib.lib().flacgpu_window_frames(sizes.ctypes.data_as(C.POINTER(C.c_uint32)), sizes.size, start, length,
+                                          C.byref(first), C.byref(count), C.byref(skip))
+    if rc:
+        raise GpuError(rc, "flacgpu_window_frames")
+    return first.value, count.value, skip.value
+
+
+def window_array(windows):
+    """A _lib.Window array from (stream, start, length) tuples or an [N, 3] integer array."""
+    rows = [tuple(int(v) for v in w) for w in windows]
+    if any(len(r) != 3 for r in rows):
+        raise ValueError("a window is (stream, start, length)")
+    return (_lib.Window * len(rows))(*[_lib.Window(s, 0, a, n) for s, a, n in rows])
+
 
 _DTYPES = {"int32": _lib.SAMPLE_I32, "int16": _lib.SAMPLE_I16, "float32": _lib.SAMPLE_F32}
 
@@ -580,6 +621,40 @@ def decode_many(blobs, device=-1, out="device", verify_md5=True, decoder=None, d
             pcm = flat[r.out_offset:r.out_offset + info.decoded_samples * ch].reshape(-1, ch)
         streams.append(DecodedStream(r.rc, info, r.out_offset, pcm))
     return flat, streams
+
+
+def decode_windows(decoder, recs, windows, dtype="float32", out="device", pad_to=None, pad_channels=None):
+    """Sample windows (random crops) of the batch that `decoder` has scanned (`recs`: what Decoder.scan returned):
+    only the frames a window touches are decoded, and only the windows are written (flacgpu_decoder_decode_windows).
+
+    `windows` is a sequence of (stream, start, length) tuples or an [N, 3] integer array.  Returns (batch, results):
+    `batch` is [N, C, T], planar and zero-padded -- a torch tensor on the GPU for out="device", a numpy array for
+    out="host" -- with T = pad_to or the longest window and C = pad_channels or the most channels of a named stream;
+    results[i] is the _lib.WindowResult of window i (rc, frames, bad_frames, bad_crc16, samples: the valid samples of
+    batch[i], fewer than the window's length where it reaches past the stream's end).  dtype as for decode_many."""
+    if out not in ("device", "host"):
+        raise ValueError("out must be 'device' or 'host'")
+    if dtype not in _DTYPES:
+        raise ValueError("dtype must be 'int32', 'int16' or 'float32'")
+    wins = window_array(windows)
+    n = len(recs)
+    named = [recs[w.stream] for w in wins if w.stream < n and recs[w.stream].rc == 0]
+    fmt = _lib.OutFormat(_DTYPES[dtype], _lib.LAYOUT_PADDED, 0, 0, 0)
+    fmt.samples_padded = pad_to or max([w.length for w in wins], default=0)
+    fmt.channels_padded = pad_channels or max([r.info.channels for r in named], default=0)
+    shape = (len(wins), fmt.channels_padded, fmt.samples_padded)
+    need = Decoder.plan_windows(fmt, recs, n, wins)   # refuses before anything is allocated
+    if out == "device":
+        import torch
+
+        dev = decoder.device if decoder.device >= 0 else torch.cuda.current_device()
+        buf = torch.empty(shape, dtype=getattr(torch, dtype), device=f"cuda:{dev}")
+        torch.cuda.synchronize(dev)
+        results = decoder.decode_windows(buf.data_ptr() if need else None, need, fmt, _lib.DECODE_OUT_DEVICE, wins)
+    else:
+        buf = np.empty(shape, dtype=dtype)
+        results = decoder.decode_windows(buf.ctypes.data if need else None, need, fmt, 0, wins)
+    return buf, list(results)[:len(wins)]
 
 
 def host_pack_frames(sample_rate, bits_per_sample, channels, first_frame_number, n_frames,

@@ -583,6 +583,51 @@ int flacgpu_decoder_plan_output(const flacgpu_out_format *fmt, const flacgpu_dec
 int flacgpu_decoder_decode_as(flacgpu_decoder *d, void *out, size_t out_cap_bytes, const flacgpu_out_format *fmt,
                               uint32_t flags, flacgpu_decoded_stream *streams);
 
+/* ---- batch decoder: sample windows of a scanned batch (random crops) ---------------------------------------------
+ * decode_windows decodes only the frames that each window touches and writes only the windows:
+ * [n_windows][channels_padded][samples_padded], planar, in fmt->dtype with decode_as's conversions.  fmt->layout must be
+ * FLACGPU_LAYOUT_PADDED, samples_padded must cover the longest window and channels_padded every stream with rc == 0
+ * that a window names.  Element [w][c][t] is sample start + t of channel c for c < channels and t < samples (of the
+ * window's result); every other element is zero, and so is the whole block of a window on a stream with rc != 0.  After
+ * FLACGPU_OK all out_bytes (plan_windows) are defined, whatever `out` held before.  `out` is host or device memory as
+ * for decode_as; `flags` are its flags.
+ * The frames come from the scan's own frame table, which is exact for any stream (variable block sizes included); a
+ * SEEKTABLE is not read.  Windows may overlap, come in any order, and name a stream several times or not at all; a
+ * frame that two windows touch is decoded once per window.  The samples of a frame that does not decode are undefined,
+ * inside that frame's share of that window only.  No MD5 is computed (a window has none; FLACGPU_DECODE_NO_MD5 changes
+ * nothing); the CRC-16 of every decoded frame is checked and counted per window.  Device scratch is sized by the
+ * selected frames, not by the batch.
+ * A refused call writes nothing: no scanned batch, stream >= n_streams, reserved != 0, start + length overflowing, a
+ * layout other than PADDED or padding too small (FLACGPU_ERR_INVALID_ARG), out_cap_bytes < out_bytes
+ * (FLACGPU_ERR_BUFFER_TOO_SMALL), I16 with a named rc == 0 stream of more than 16 bits (FLACGPU_ERR_UNSUPPORTED,
+ * flacgpu_last_error names the stream of the first such window).  A stream that no window names takes no part in these
+ * checks.  n_windows == 0 is valid and writes nothing.  decode, decode_as and decode_windows may follow one another in
+ * any order on one scan.
+ * plan_windows is a pure host function (no device, no handle): the checks above on scanned records, and the bytes `out`
+ * must hold.  flacgpu_window_frames is the frame selection alone on a list of block sizes: frames [*first, *first +
+ * *count) hold samples [start, start + length) clipped to the stream, *skip samples of frame *first lie in front of
+ * `start`; an empty window or one past the end gives *count = 0 (*first = 0, *skip = 0). */
+typedef struct {
+    uint32_t stream;    /* index into the scanned batch */
+    uint32_t reserved;  /* 0 */
+    uint64_t start;     /* first sample per channel */
+    uint64_t length;    /* samples per channel; 0 is valid */
+} flacgpu_window;
+typedef struct {
+    int32_t  rc;         /* the stream's scan rc; a window on an rc != 0 stream is all zero */
+    uint32_t frames;     /* frames decoded for this window */
+    uint32_t bad_frames; /* of those, frames that did not parse */
+    uint32_t bad_crc16;  /* of those */
+    uint64_t samples;    /* valid samples per channel: clamp(decoded_samples - start, 0, length) */
+} flacgpu_window_result;
+int flacgpu_decoder_plan_windows(const flacgpu_out_format *fmt, const flacgpu_decoded_stream *streams,
+                                 uint32_t n_streams, const flacgpu_window *w, uint32_t n_windows, uint64_t *out_bytes);
+int flacgpu_decoder_decode_windows(flacgpu_decoder *d, void *out, size_t out_cap_bytes, const flacgpu_out_format *fmt,
+                                   uint32_t flags, const flacgpu_window *w, uint32_t n_windows,
+                                   flacgpu_window_result *results);
+int flacgpu_window_frames(const uint32_t *frame_n, uint32_t n_frames, uint64_t start, uint64_t length, uint32_t *first,
+                          uint32_t *count, uint64_t *skip);
+
 /* EXPERIMENT, not on the product path: recomputes the autocorrelation of the last analysed
  * batch on the f64 matrix cores (v_mfma_f64_16x16x4_f64, block-Gram form), times that kernel,
  * reruns Levinson/quantisation on it and reports how many candidates' quantised LPC parameters

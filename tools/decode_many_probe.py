@@ -8,12 +8,22 @@ over flacgpu_decode_stream and the oracle's CPU decoder on one core; writes prof
     python tools/decode_many_probe.py --formats --label parent --package-root DIR   (DIR: a built checkout of the
                                              parent commit; the default int32 path only, into the same file)
     python tools/decode_many_probe.py --formats --kernels-only   (one warm call per leg, for rocprofv3)
+    python tools/decode_many_probe.py --windows [--workloads tracks,clips] [--out profiles/r10_decode_windows.json]
+                                             [--reps 15] [--kernels-only]
 
 --formats (flacgpu_decoder_decode_as): on the clips, device output, no MD5, handle warm, the wall time of one
 scan + decode call into (a) what a caller of flacgpu_decoder_decode does -- interleaved int32, then torch ops to the
 same [B, 1, T] float32 (or int16) padded tensor -- and (b) decode_many(dtype=, layout="padded") in one call; and the
 default int32 path itself, whose figure the parent's build repeats on the same box (the regression guard: the margin is
 the spread over --reps that this probe sees).
+
+--windows (flacgpu_decoder_decode_windows): on a resident scan (scanned once, outside the timed part), device output,
+no MD5, handle warm, the wall time of one round of random crops -- one crop of 5 s (tracks) or 1 s (clips) per stream
+at seeded random positions -- as (a) what a caller without windows does: decode_as float32 PADDED of the whole batch,
+then torch slicing into [B, C, T]; and (b) decode_windows.  Each leg runs in its own decoder and reports the peak
+device memory it adds on top of the resident scan (hipMemGetInfo through torch, so the library's buffers count).  (a)
+needs the whole batch's padded output beside the scan; when that does not fit, both legs take the largest prefix of the
+batch that does, and the record says so.
 
 Workloads (default options of FlacSampleWriter; a few distinct streams repeated to the batch size -- the decoder
 does not see that they repeat):
@@ -230,6 +240,87 @@ def formats(args):
     print(json.dumps({args.label: rec}, indent=1), flush=True)
 
 
+def windows(args):
+    """The --windows leg (see the module docstring)."""
+    import torch
+
+    from flac_codec_amd import _lib
+    from flac_codec_amd.gpu import Decoder, decode_windows, window_array
+
+    res = {"tool": "tools/decode_many_probe.py --windows", "device_output": True, "md5": False, "workloads": {}}
+    if os.path.exists(args.out):
+        with open(args.out) as f:
+            res = json.load(f)
+    crop_s = {"tracks": 5, "clips": 1}
+
+    def used():   # device memory in use, whoever allocated it
+        torch.cuda.synchronize()
+        free, total = torch.cuda.mem_get_info(0)
+        return total - free
+
+    for name in args.workloads.split(","):
+        n, _, secs, rate, ch, bps = WORKLOADS[name]
+        blobs = make_blobs(name)
+        T = crop_s[name] * rate
+        free = torch.cuda.mem_get_info(0)[0]
+        # (a) holds the padded float32 batch beside the scan (and its scratch, as large again)
+        fit = min(n, int(free * 0.8 // (3 * 4 * ch * secs * rate + len(blobs[0]))))
+        blobs = blobs[:fit]
+        rng = np.random.default_rng(10)
+        rounds = [[(i, int(rng.integers(0, secs * rate - T + 1)), T) for i in range(fit)]
+                  for _ in range(args.reps + 1)]
+        rec = {"streams": fit, "of": n, "prefix_because_full_output_does_not_fit": fit < n, "crop_samples": T,
+               "channels": ch, "build_id": _lib.build_id(), "sclk_mhz_before": _sclk_mhz(), "legs": {}}
+
+        def leg_a(dec, recs, wins):
+            fmt = _lib.OutFormat(_lib.SAMPLE_F32, _lib.LAYOUT_PADDED, ch, 0, secs * rate)
+            full = torch.empty((fit, ch, secs * rate), dtype=torch.float32, device="cuda:0")
+            dec.decode_as(full.data_ptr(), full.numel() * 4, fmt, _lib.DECODE_OUT_DEVICE | _lib.DECODE_NO_MD5, recs)
+            idx = torch.tensor([w[1] for w in wins], device="cuda:0")[:, None] + torch.arange(T, device="cuda:0")
+            return torch.gather(full, 2, idx[:, None, :].expand(fit, ch, T))
+
+        def leg_b(dec, recs, wins):
+            return decode_windows(dec, recs, wins, dtype="float32", out="device")[0]
+
+        outs = {}
+        for leg, fn in (("a_decode_as_padded_then_slice", leg_a), ("b_decode_windows", leg_b)):
+            base = used()
+            dec = Decoder(0)
+            recs, _ = dec.scan(blobs)
+            resident = used()
+            out = fn(dec, recs, rounds[0])   # warm: buffers grown, code loaded
+            outs[leg] = out.clone()
+            del out
+            torch.cuda.empty_cache()
+            if args.kernels_only:
+                fn(dec, recs, rounds[1])
+                torch.cuda.synchronize()
+                dec.close()
+                continue
+            times, peak = [], 0
+            for wins in rounds[1:]:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                out = fn(dec, recs, wins)
+                torch.cuda.synchronize()
+                times.append(time.perf_counter() - t0)
+                peak = max(peak, used())
+                del out
+                torch.cuda.empty_cache()
+            rec["legs"][leg] = dict(_spread(times), resident_scan_bytes=int(resident - base),
+                                    peak_bytes_over_resident_scan=int(peak - resident))
+            dec.close()
+            del dec
+        assert torch.equal(outs["a_decode_as_padded_then_slice"], outs["b_decode_windows"])   # the same crops
+        rec["sclk_mhz_after"] = _sclk_mhz()
+        res["workloads"][name] = rec
+        print(json.dumps({name: rec}, indent=1), flush=True)
+        del blobs, outs
+    if not args.kernels_only:
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
 def run(args):
     res = {"tool": "tools/decode_many_probe.py", "copy_rate_TBps": COPY_TBPS, "workloads": {}}
     if os.path.exists(args.out):
@@ -271,7 +362,7 @@ def merge_stats(args):
                                "avg_ms": float(r["AverageNs"]) / 1e6}
     mine = {k: v for k, v in rows.items() if any(s in k for s in ("k_scan_", "k_link", "k_decode_many", "k_frame_crc",
                                                                    "k_finish_many", "k_md5_many", "k_finish_as",
-                                                                   "k_pad_rows"))}
+                                                                   "k_pad_rows", "k_finish_window"))}
     res.setdefault("kernel_stats", {})[args.stats_label] = mine
     with open(args.out, "w") as f:
         json.dump(res, f, indent=1)
@@ -284,6 +375,7 @@ def main():
     ap.add_argument("--out")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--formats", action="store_true", help="the output-format leg: profiles/r09_decode_formats.json")
+    ap.add_argument("--windows", action="store_true", help="the random-crop leg: profiles/r10_decode_windows.json")
     ap.add_argument("--label", default="this", help="--formats: the run's name in the file (this | parent)")
     ap.add_argument("--package-root", help="--formats: measure the flac_codec_amd of this checkout, not of this one")
     ap.add_argument("--oracle-seconds", type=float, default=20.0)
@@ -292,7 +384,10 @@ def main():
     ap.add_argument("--kernels-only", action="store_true", help="one warm decode per workload (for rocprofv3)")
     args = ap.parse_args()
     if not args.out:
-        args.out = os.path.join(ROOT, "profiles", "r09_decode_formats.json" if args.formats else "r07_decode_many.json")
+        args.out = os.path.join(ROOT, "profiles", "r10_decode_windows.json" if args.windows else
+                                "r09_decode_formats.json" if args.formats else "r07_decode_many.json")
+    if args.windows and args.workloads == "clips,tracks,hour":
+        args.workloads = "tracks,clips"
     if args.merge_stats:
         return merge_stats(args)
     if args.package_root:
@@ -302,6 +397,8 @@ def main():
     torch.cuda.init()   # before the library's first HIP call (else torch sees no GPU)
     if args.formats:
         return formats(args)
+    if args.windows:
+        return windows(args)
     if args.kernels_only:
         for name in args.workloads.split(","):   # (the hour's MD5 alone runs > 1 min: left to the timed run)
             blobs = make_blobs(name)
