@@ -102,6 +102,16 @@ class OutFormat(C.Structure):
                 ("reserved", C.c_uint32), ("samples_padded", C.c_uint64)]
 
 
+class DeviceJob(C.Structure):
+    """flacenc_device_job: one stream of flacenc_encode_many_device (include/flacenc_stream.h); the tensor's format is
+    an OutFormat (flacenc_tensor_format is flacgpu_out_format)."""
+    _fields_ = [("in_offset", C.c_uint64), ("samples", C.c_uint64), ("out", C.c_void_p), ("out_cap", C.c_size_t),
+                ("out_len", C.c_size_t), ("status", C.c_int32), ("altered", C.c_uint32), ("md5", C.c_uint8 * 16)]
+
+
+DEVICE_NO_MD5 = 1   # FLACENC_DEVICE_NO_MD5
+
+
 class Window(C.Structure):
     """flacgpu_window: samples [start, start + length) per channel of one scanned stream."""
     _fields_ = [("stream", C.c_uint32), ("reserved", C.c_uint32), ("start", C.c_uint64), ("length", C.c_uint64)]

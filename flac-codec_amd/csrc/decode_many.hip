@@ -550,6 +550,18 @@ int decode_windows_impl(flacgpu_decoder *d, void *out, uint64_t out_bytes, const
 }
 }  // namespace
 
+// k_md5_many for the encoder's ingest pass (ingest.hip): one job per ingested stream, no digest to compare with
+void flacgpu_k::launch_md5_many(const int32_t *samples, const Md5JobRec *jobs, uint32_t n_jobs, uint32_t *digest,
+                                hipStream_t st) {
+    static_assert(sizeof(Md5JobRec) == sizeof(Md5Job) && offsetof(Md5JobRec, count) == offsetof(Md5Job, count) &&
+                      offsetof(Md5JobRec, width) == offsetof(Md5Job, width) &&
+                      offsetof(Md5JobRec, expect) == offsetof(Md5Job, expect),
+                  "Md5JobRec is Md5Job");
+    if (!n_jobs) return;
+    hipLaunchKernelGGL(k_md5_many, dim3((n_jobs + 63) / 64), dim3(64), 0, st, samples,
+                       reinterpret_cast<const Md5Job *>(jobs), n_jobs, digest);
+}
+
 int flacgpu_decoder_create(int device, flacgpu_decoder **out) {
     if (!out) return FLACGPU_ERR_INVALID_ARG;
     *out = nullptr;

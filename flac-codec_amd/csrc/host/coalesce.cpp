@@ -225,11 +225,7 @@ static uint32_t coalesce_batch_cap(uint32_t batch_frames, size_t samples_per_blo
 // `whole[k]` = whole blocks of stream k; batch_cap = frames a slot's context takes.  Invariants (tests/test_coalesce_plan.py):
 // every block of every stream exactly once, a stream's segments in stream order and in non-decreasing batches, no batch above
 // batch_cap, and a stream of up to kSolo blocks in ONE segment (its MD5 chain is one run hashed by one task).
-struct PlanSeg {
-    uint32_t stream;   // index into `whole`
-    uint64_t first;    // first block of the segment in its stream
-    uint32_t n;        // blocks
-};
+// (PlanSeg -- stream, first block, blocks -- is host_internal.h's: device_batch.cpp plans its batches here too)
 static std::vector<std::vector<PlanSeg>> plan_batches(const std::vector<uint64_t> &whole, uint32_t batch_cap) {
     uint64_t total_whole = 0;
     size_t n_active = 0;
@@ -339,6 +335,7 @@ size_t flacenc_coalesce_plan(const uint64_t *whole, size_t n_streams, uint32_t b
 void flacenc_release_pools(void) {
     RingPool::get().release_all();
     release_lane_pool();
+    release_device_batch_pool();
 }
 
 int flacenc_encode_many_coalesced(const flacenc_options *opts_in, flacenc_job *jobs, size_t n_jobs, uint32_t threads) {
@@ -954,3 +951,29 @@ int flacenc_encode_many_coalesced(const flacenc_options *opts_in, flacenc_job *j
 }
 
 }  // extern "C"
+
+// ---- what device_batch.cpp shares with this file (host_internal.h): the batch plan and the pooled contexts ----------------
+namespace flacenc_host {
+std::vector<std::vector<PlanSeg>> plan_stream_batches(const std::vector<uint64_t> &whole, uint32_t batch_frames,
+                                                      size_t samples_per_block, uint32_t *batch_cap) {
+    uint64_t total = 0;
+    for (uint64_t w : whole) total += w;
+    *batch_cap = coalesce_batch_cap(batch_frames, samples_per_block, total);
+    return plan_batches(whole, *batch_cap);
+}
+int pooled_context_take(const flacgpu_options &g, uint32_t bps, uint32_t channels, uint32_t frames, int device, PooledContext *out) {
+    RingSlot s;
+    if (int rc = RingPool::get().take(RingKey{g, bps, channels, frames, device}, 0, &s)) return rc;
+    *out = PooledContext{s.ctx, s.in, s.out, s.in_cap, s.out_cap};
+    return 0;
+}
+void pooled_context_give(const flacgpu_options &g, uint32_t bps, uint32_t channels, uint32_t frames, int device, const PooledContext &c) {
+    RingSlot s;
+    s.ctx = c.ctx;
+    s.in = c.in;
+    s.out = c.out;
+    s.in_cap = c.in_cap;
+    s.out_cap = c.out_cap;
+    RingPool::get().give(RingKey{g, bps, channels, frames, device}, s);
+}
+}  // namespace flacenc_host

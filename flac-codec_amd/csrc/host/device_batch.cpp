@@ -1,0 +1,395 @@
+// device_batch.cpp -- flacenc_encode_many_device: a batch of streams of one shape held in DEVICE memory (int32, int16 or
+// float32; planar and padded, or interleaved and flat) -> finished .flac files in the callers' host buffers, the samples
+// never visiting the host.  The mirror image of flacgpu_decoder_decode_as.
+//
+//   * plan (pure host code): the checks, the elements the tensor must hold, the staging bytes;
+//   * ingest (ingest.hip, kernels/ingest.inc): one kernel pass converts the tensor by ingest_sample (kernels/ingest_rule.h)
+//     into interleaved int32 in the ingest handle's staging buffer, every stream from a 16-byte boundary -- what
+//     flacgpu_encode_segments_device reads in place.  This version always ingests (an aligned FLAT I32 batch could be read
+//     in place: a follow-up);
+//   * MD5 on the device, one k_md5_many lane per stream (about 15 MB/s per stream, DESIGN.md section 4b: fine for many
+//     clips, poor for one long stream -- FLACENC_DEVICE_NO_MD5 is the way round it today), queued behind the ingest on
+//     the handle's stream, so that it runs beside the analysis;
+//   * whole blocks: batches of segments planned as flacenc_encode_many_coalesced plans them (plan_stream_batches), on two
+//     pooled contexts in rotation -- batch i + 1 is submitted before batch i's frames are fetched into its pinned buffer,
+//     so one batch's kernels run while the other's frames cross the link -- and copied once to their places in `out`;
+//   * a stream's short last block: a one-frame flacgpu_encode_device call on the staging pointer (two one-frame contexts
+//     in rotation), as coalesce.cpp does from host PCM;
+//   * everything in front of the first frame: flacenc_stream_header, as in coalesce.cpp.
+#include <algorithm>
+#include <atomic>
+#include <cstring>
+#include <map>
+#include <mutex>
+#include <numeric>
+#include <string>
+#include <vector>
+
+#include "../kernels/ingest_rule.h"
+#include "host_internal.h"
+
+using namespace flacenc_host;
+
+namespace {
+
+// idle ingest handles (a stream, an event and the staging buffer: kept between calls like the analysis contexts)
+struct IngestPool {
+    std::mutex mu;
+    std::vector<flacgpu_ingest *> idle;
+    static IngestPool &get() {
+        static IngestPool *p = new IngestPool();   // leaked on purpose: no HIP calls during static destruction
+        return *p;
+    }
+    int take(int device, flacgpu_ingest **out) {
+        {
+            std::lock_guard<std::mutex> l(mu);
+            for (size_t i = 0; i < idle.size(); i++)
+                if (flacgpu_ingest_device(idle[i]) == device) {
+                    *out = idle[i];
+                    idle.erase(idle.begin() + (ptrdiff_t)i);
+                    return 0;
+                }
+        }
+        return flacgpu_ingest_create(device, out);
+    }
+    void give(flacgpu_ingest *g) {
+        flacgpu_ingest *drop = nullptr;
+        {
+            std::lock_guard<std::mutex> l(mu);
+            idle.push_back(g);
+            if (idle.size() > 2) {   // the oldest goes
+                drop = idle.front();
+                idle.erase(idle.begin());
+            }
+        }
+        flacgpu_ingest_destroy(drop);
+    }
+    void release_all() {
+        std::vector<flacgpu_ingest *> all;
+        {
+            std::lock_guard<std::mutex> l(mu);
+            all.swap(idle);
+        }
+        for (flacgpu_ingest *g : all) flacgpu_ingest_destroy(g);
+    }
+};
+
+int gpu_error(int rc) {
+    set_last_error(std::string("gpu: ") + flacgpu_last_error());
+    return rc == FLACGPU_ERR_UNSUPPORTED ? FLACENC_ERR_UNSUPPORTED : FLACENC_ERR_GPU;
+}
+int refuse(int rc, const std::string &why) {
+    set_last_error("flacenc_device_batch_plan: " + why);
+    return rc;
+}
+
+// The checks of plan / encode; staging_off (may be null) receives every stream's first int32 in the staging buffer.
+int plan_impl(const flacenc_options *o, const flacenc_tensor_format *fmt, uint32_t bps, uint32_t channels,
+              const flacenc_device_job *jobs, size_t n_jobs, uint64_t *in_elements, uint64_t *staging_elements,
+              std::vector<uint64_t> *staging_off) {
+    if (!o || !fmt || (!jobs && n_jobs)) return refuse(FLACENC_ERR_INVALID_ARG, "a null argument");
+    if (int e = options_error(*o)) return e;
+    const bool padded = fmt->layout == FLACGPU_LAYOUT_PADDED;
+    if (fmt->dtype > FLACGPU_SAMPLE_F32 || fmt->layout > FLACGPU_LAYOUT_PADDED || fmt->reserved ||
+        (!padded && (fmt->channels_padded || fmt->samples_padded)))
+        return refuse(FLACENC_ERR_INVALID_ARG, "unknown dtype or layout, reserved not 0, or padded fields under FLAT");
+    if (channels < 1 || channels > FLACGPU_MAX_CHANNELS || bps < 1 || bps > 32)
+        return refuse(FLACENC_ERR_INVALID_ARG, "channels outside 1..8 or bits per sample outside 1..32");
+    if (fmt->dtype == FLACGPU_SAMPLE_I16 && bps > 16)
+        return refuse(FLACENC_ERR_UNSUPPORTED, "int16 input, but " + std::to_string(bps) + " bits per sample");
+    if (n_jobs > 0xFFFFFFFFull) return refuse(FLACENC_ERR_UNSUPPORTED, "more than 2^32 - 1 streams");
+    if (padded && fmt->channels_padded < channels)
+        return refuse(FLACENC_ERR_INVALID_ARG, "channels_padded is less than channels");
+    uint64_t in_end = 0, staging = 0;
+    if (staging_off) staging_off->assign(n_jobs, 0);
+    std::vector<std::pair<uint64_t, uint64_t>> spans;   // FLAT: [first element, end) of every stream with samples
+    for (size_t i = 0; i < n_jobs; i++) {
+        uint64_t count = 0, rounded = 0;
+        if (__builtin_mul_overflow(jobs[i].samples, (uint64_t)channels, &count) ||
+            __builtin_add_overflow(count, (uint64_t)3, &rounded) ||
+            __builtin_add_overflow(staging, rounded & ~(uint64_t)3, &rounded))
+            return refuse(FLACENC_ERR_UNSUPPORTED, "the batch exceeds 2^64 samples");
+        if (staging_off) (*staging_off)[i] = staging;
+        staging = rounded;
+        if (padded) {
+            if (jobs[i].samples > fmt->samples_padded)
+                return refuse(FLACENC_ERR_INVALID_ARG, "stream " + std::to_string(i) + " is longer than samples_padded");
+        } else if (count) {
+            uint64_t end = 0;
+            if (__builtin_add_overflow(jobs[i].in_offset, count, &end))
+                return refuse(FLACENC_ERR_INVALID_ARG, "stream " + std::to_string(i) + ": in_offset + its elements overflows");
+            spans.emplace_back(jobs[i].in_offset, end);
+            in_end = std::max(in_end, end);
+        }
+    }
+    if (padded) {
+        if (__builtin_mul_overflow((uint64_t)n_jobs * fmt->channels_padded, fmt->samples_padded, &in_end))
+            return refuse(FLACENC_ERR_UNSUPPORTED, "the padded batch exceeds 2^64 elements");
+    } else {
+        std::sort(spans.begin(), spans.end());
+        for (size_t k = 1; k < spans.size(); k++)
+            if (spans[k].first < spans[k - 1].second) return refuse(FLACENC_ERR_INVALID_ARG, "FLAT streams overlap");
+    }
+    if (staging > (~(uint64_t)0) / 4) return refuse(FLACENC_ERR_UNSUPPORTED, "the staging buffer exceeds 2^64 bytes");
+    *in_elements = in_end;
+    *staging_elements = staging;
+    return 0;
+}
+
+struct Stream {
+    uint64_t whole = 0;             // whole blocks
+    uint32_t tail = 0;              // samples of the short last block (0: none)
+    size_t hlen = 0;                // bytes in front of the first frame
+    uint64_t pos = 0;               // bytes of the frames placed so far
+    std::vector<uint32_t> sizes;    // per frame
+    std::vector<uint8_t> tail_bytes;
+};
+struct CopyJob {
+    const uint8_t *src;
+    uint8_t *dst;
+    size_t n;
+};
+
+// the frames of a retired batch to their places, a few threads side by side (one copy per output byte)
+void run_copies(const std::vector<CopyJob> &cj) {
+    size_t bytes = 0;
+    for (const CopyJob &c : cj) bytes += c.n;
+    std::atomic<size_t> next{0};
+    const auto work = [&]() {
+        for (size_t i; (i = next.fetch_add(1)) < cj.size();) std::memcpy(cj[i].dst, cj[i].src, cj[i].n);
+    };
+    const unsigned helpers = (unsigned)std::min<size_t>({bytes >> 20, cj.size() ? cj.size() - 1 : 0, (size_t)std::min(usable_cpus(), 8u) - 1});
+    run_parallel(helpers, work);
+}
+
+}  // namespace
+
+namespace flacenc_host {
+void release_device_batch_pool() { IngestPool::get().release_all(); }
+}  // namespace flacenc_host
+
+extern "C" {
+
+int32_t flacenc_ingest_sample(uint32_t sample_type, uint32_t raw_bits, uint32_t bits_per_sample, int *altered) {
+    int a = 1;
+    int32_t v = 0;
+    if (sample_type <= INGEST_F32 && bits_per_sample >= 1 && bits_per_sample <= 32 &&
+        !(sample_type == INGEST_I16 && bits_per_sample > 16))
+        v = ingest_sample(sample_type, raw_bits, bits_per_sample, &a);
+    if (altered) *altered = a;
+    return v;
+}
+
+int flacenc_device_batch_plan(const flacenc_options *opts, const flacenc_tensor_format *fmt, uint32_t bits_per_sample,
+                              uint32_t channels, const flacenc_device_job *jobs, size_t n_jobs, size_t *in_elements,
+                              size_t *staging_bytes) {
+    uint64_t in = 0, st = 0;
+    if (int rc = plan_impl(opts, fmt, bits_per_sample, channels, jobs, n_jobs, &in, &st, nullptr)) return rc;
+    if (in_elements) *in_elements = (size_t)in;
+    if (staging_bytes) *staging_bytes = (size_t)(4 * st);
+    return 0;
+}
+
+int flacenc_encode_many_device(const flacenc_options *opts, const void *d_pcm, const flacenc_tensor_format *fmt,
+                               uint32_t sample_rate, uint32_t bits_per_sample, uint32_t channels, flacenc_device_job *jobs,
+                               size_t n_jobs, uint32_t flags, void *stream) {
+    uint64_t in_elements = 0, staging_elements = 0;
+    std::vector<uint64_t> staging_off;
+    if (int rc = plan_impl(opts, fmt, bits_per_sample, channels, jobs, n_jobs, &in_elements, &staging_elements, &staging_off))
+        return rc;
+    if ((flags & ~FLACENC_DEVICE_NO_MD5) || (in_elements && !d_pcm) ||
+        reinterpret_cast<uintptr_t>(d_pcm) % (fmt->dtype == FLACGPU_SAMPLE_I16 ? 2 : 4)) {
+        set_last_error("flacenc_encode_many_device: unknown flags, no tensor, or a tensor not aligned to its element size");
+        return FLACENC_ERR_INVALID_ARG;
+    }
+    const flacenc_options &o = *opts;
+    const uint32_t B = o.block_size, ch = channels, bps = bits_per_sample;
+    const size_t per = (size_t)B * ch;
+    const bool md5 = !(flags & FLACENC_DEVICE_NO_MD5);
+    const int device = o.device >= 0 ? o.device : flacgpu_current_device();
+    const flacgpu_options g = gpu_options(o, B);
+
+    // ---- the streams: what flacenc_encode_many checks per job, and the size of what stands in front of the first frame
+    std::vector<Stream> st(n_jobs);
+    std::map<uint64_t, std::pair<int, size_t>> header_memo;   // (streams of one length share their header's size)
+    for (size_t i = 0; i < n_jobs; i++) {
+        flacenc_device_job &j = jobs[i];
+        j.out_len = 0;
+        j.status = 0;
+        j.altered = 0;
+        std::memset(j.md5, 0, 16);
+        if (!j.samples || !j.out) {
+            j.status = FLACENC_ERR_INVALID_ARG;
+            continue;
+        }
+        auto it = header_memo.find(j.samples);
+        if (it == header_memo.end()) {
+            size_t l = 0;
+            const int rc = stream_header_len(o, sample_rate, bps, ch, j.samples, &l);
+            it = header_memo.emplace(j.samples, std::make_pair(rc, l)).first;
+        }
+        if (it->second.first) {
+            j.status = it->second.first;
+            continue;
+        }
+        Stream &s = st[i];
+        s.hlen = it->second.second;
+        if (s.hlen > j.out_cap) {
+            j.status = FLACENC_ERR_IO;
+            continue;
+        }
+        s.whole = j.samples / B;
+        s.tail = (uint32_t)(j.samples % B);
+        s.sizes.assign(s.whole + (s.tail ? 1 : 0), 0);
+    }
+    const auto fail = [&](size_t i, int rc) {
+        if (!jobs[i].status) jobs[i].status = rc;
+    };
+    const auto fail_all = [&](int rc) {
+        for (size_t i = 0; i < n_jobs; i++) fail(i, rc);
+        return rc;
+    };
+
+    // ---- ingest (and the MD5 chains behind it)
+    flacgpu_ingest *ing = nullptr;
+    if (int rc = IngestPool::get().take(device, &ing)) return fail_all(gpu_error(rc));
+    struct Giver {
+        flacgpu_ingest *g;
+        ~Giver() { IngestPool::get().give(g); }
+    } giver{ing};
+    std::vector<flacgpu_ingest_stream> is(n_jobs);
+    for (size_t i = 0; i < n_jobs; i++) is[i] = flacgpu_ingest_stream{jobs[i].in_offset, jobs[i].samples, staging_off[i]};
+    int32_t *d_staging = nullptr;
+    if (int rc = flacgpu_ingest_submit(ing, d_pcm, fmt, bps, ch, is.data(), (uint32_t)n_jobs, staging_elements,
+                                       md5 ? FLACGPU_INGEST_MD5 : 0u, stream, &d_staging))
+        return fail_all(gpu_error(rc));
+
+    // ---- whole blocks: batches of segments, two contexts in rotation
+    std::vector<uint64_t> whole(n_jobs);
+    for (size_t i = 0; i < n_jobs; i++) whole[i] = jobs[i].status ? 0 : st[i].whole;
+    uint32_t batch_cap = 0;
+    const std::vector<std::vector<PlanSeg>> batches = plan_stream_batches(whole, o.batch_frames, per, &batch_cap);
+    int whole_rc = 0;
+    if (!batches.empty()) {
+        PooledContext slot[2] = {};
+        const size_t n_slots = std::min<size_t>(2, batches.size());
+        size_t have = 0;
+        for (; have < n_slots; have++)
+            if (int rc = pooled_context_take(g, bps, ch, batch_cap, device, &slot[have])) {
+                whole_rc = gpu_error(rc);
+                break;
+            }
+        const auto submit = [&](size_t b) {
+            std::vector<flacgpu_segment> gs(batches[b].size());
+            for (size_t k = 0; k < gs.size(); k++) {
+                const PlanSeg &p = batches[b][k];
+                gs[k].pcm = d_staging + staging_off[p.stream] + p.first * per;
+                gs[k].n_frames = p.n;
+                gs[k].reserved = 0;
+                gs[k].first_frame_number = p.first;
+            }
+            return flacgpu_encode_segments_device(slot[b % 2].ctx, gs.data(), (uint32_t)gs.size(), sample_rate, nullptr);
+        };
+        std::vector<uint64_t> off;
+        std::vector<CopyJob> cj;
+        int rc = whole_rc ? FLACGPU_ERR_HIP : submit(0);
+        for (size_t b = 0; b < batches.size() && !rc; b++) {
+            if (b + 1 < batches.size()) rc = submit(b + 1);   // its kernels run while batch b's frames are fetched
+            if (rc) break;
+            const PooledContext &s = slot[b % 2];
+            uint32_t frames = 0;
+            for (const PlanSeg &p : batches[b]) frames += p.n;
+            off.assign((size_t)frames + 1, 0);
+            uint64_t total = 0;
+            rc = flacgpu_fetch_frames(s.ctx, s.out, s.out_cap, off.data(), &total);
+            if (rc) break;
+            cj.clear();
+            uint32_t f = 0;
+            for (const PlanSeg &p : batches[b]) {
+                Stream &sm = st[p.stream];
+                flacenc_device_job &j = jobs[p.stream];
+                const uint64_t bytes = off[f + p.n] - off[f];
+                for (uint32_t k = 0; k < p.n; k++) sm.sizes[p.first + k] = (uint32_t)(off[f + k + 1] - off[f + k]);
+                if (sm.hlen + sm.pos + bytes > j.out_cap) fail(p.stream, FLACENC_ERR_IO);
+                else if (!j.status) cj.push_back(CopyJob{s.out + off[f], j.out + sm.hlen + sm.pos, (size_t)bytes});
+                sm.pos += bytes;
+                f += p.n;
+            }
+            run_copies(cj);
+        }
+        if (rc && !whole_rc) whole_rc = gpu_error(rc);
+        for (size_t k = 0; k < have; k++) {
+            (void)flacgpu_wait(slot[k].ctx);   // (a batch submitted before a failure: nothing of this call may be in flight)
+            pooled_context_give(g, bps, ch, batch_cap, device, slot[k]);
+        }
+        if (whole_rc)
+            for (size_t i = 0; i < n_jobs; i++)
+                if (whole[i]) fail(i, whole_rc);
+    }
+
+    // ---- the short last blocks: one frame each, two one-frame contexts in rotation
+    std::vector<size_t> tails;
+    for (size_t i = 0; i < n_jobs; i++)
+        if (!jobs[i].status && st[i].tail) tails.push_back(i);
+    if (!tails.empty()) {
+        PooledContext slot[2] = {};
+        const size_t n_slots = std::min<size_t>(2, tails.size());
+        size_t have = 0;
+        int rc = 0;
+        for (; have < n_slots && !rc; have++) rc = pooled_context_take(g, bps, ch, 1u, device, &slot[have]);
+        if (rc) have--;
+        const auto submit = [&](size_t t) {
+            const size_t i = tails[t];
+            return flacgpu_encode_device(slot[t % 2].ctx, d_staging + staging_off[i] + st[i].whole * per,
+                                         FLACGPU_LAYOUT_INTERLEAVED, 1, st[i].tail, st[i].whole, sample_rate, nullptr);
+        };
+        if (!rc) rc = submit(0);
+        for (size_t t = 0; t < tails.size() && !rc; t++) {
+            if (t + 1 < tails.size()) rc = submit(t + 1);
+            if (rc) break;
+            const PooledContext &s = slot[t % 2];
+            Stream &sm = st[tails[t]];
+            uint64_t total = 0, off2[2] = {0, 0};
+            rc = flacgpu_fetch_frames(s.ctx, s.out, s.out_cap, off2, &total);
+            if (rc) break;
+            sm.sizes[sm.whole] = (uint32_t)total;
+            sm.tail_bytes.assign(s.out, s.out + total);
+        }
+        const int tail_rc = rc ? gpu_error(rc) : 0;
+        for (size_t k = 0; k < have; k++) {
+            (void)flacgpu_wait(slot[k].ctx);
+            pooled_context_give(g, bps, ch, 1u, device, slot[k]);
+        }
+        if (tail_rc)
+            for (size_t i : tails)
+                if (st[i].tail_bytes.empty()) fail(i, tail_rc);
+    }
+
+    // ---- the digests, then every stream's metadata and its last frame
+    std::vector<uint32_t> altered(n_jobs);
+    std::vector<uint8_t> digests(16 * n_jobs, 0);
+    if (int rc = flacgpu_ingest_finish(ing, altered.data(), md5 ? digests.data() : nullptr)) return fail_all(gpu_error(rc));
+    for (size_t i = 0; i < n_jobs; i++) {
+        flacenc_device_job &j = jobs[i];
+        j.altered = altered[i];
+        std::memcpy(j.md5, &digests[16 * i], 16);
+        if (j.status) continue;
+        Stream &s = st[i];
+        size_t hlen = 0;
+        const uint32_t last_len = s.tail ? s.tail : B;
+        int rc = flacenc_stream_header(&o, sample_rate, bps, ch, j.samples, j.md5, s.sizes.size(), s.sizes.data(), last_len,
+                                       j.out, j.out_cap, &hlen);
+        if (!rc && hlen != s.hlen) rc = FLACENC_ERR_IO;   // (cannot happen: the header's size is fixed at `new`)
+        if (rc || s.hlen + s.pos + s.tail_bytes.size() > j.out_cap) {
+            fail(i, rc && rc != FLACENC_ERR_INVALID_ARG ? rc : FLACENC_ERR_IO);
+            continue;
+        }
+        if (!s.tail_bytes.empty()) std::memcpy(j.out + s.hlen + s.pos, s.tail_bytes.data(), s.tail_bytes.size());
+        j.out_len = s.hlen + s.pos + s.tail_bytes.size();
+    }
+    for (size_t i = 0; i < n_jobs; i++)
+        if (jobs[i].status) return jobs[i].status;
+    return 0;
+}
+
+}  // extern "C"

@@ -3,6 +3,8 @@
 #include <cstddef>
 #include <cstdint>
 #include <functional>
+#include <string>
+#include <vector>
 
 #include "flacenc_gpu.h"
 #include "flacenc_stream.h"
@@ -20,9 +22,33 @@ int stream_header_len(const flacenc_options &o, uint32_t sample_rate, uint32_t b
                       uint64_t total_pcm_frames, size_t *len);
 // `helpers` parked threads of the process-wide pool run fn() side by side with the caller; returns when all are done
 void run_parallel(unsigned helpers, const std::function<void()> &fn);
+// what flacenc_last_error() answers on this thread
+void set_last_error(const std::string &text);
 // CPUs this process may really use: the cgroup's CPU quota when there is one (coalesce.cpp), else the hardware threads
 unsigned usable_cpus();
 // idle analysis lanes of the per-stream writers (flacenc_release_pools)
 void release_lane_pool();
+// idle ingest handles of flacenc_encode_many_device (device_batch.cpp; flacenc_release_pools)
+void release_device_batch_pool();
+
+// ---- coalesce.cpp's batch plan and context pool, for the other front end that batches segments of many streams
+// (device_batch.cpp) ----
+struct PlanSeg {
+    uint32_t stream;   // index into `whole`
+    uint64_t first;    // first block of the segment in its stream
+    uint32_t n;        // blocks
+};
+// the batches of streams of whole[k] whole blocks of one shape (samples_per_block = block size x channels): plan_batches
+// under the frames-per-batch rule of flacenc_encode_many_coalesced (*batch_cap: what a batch's context must hold)
+std::vector<std::vector<PlanSeg>> plan_stream_batches(const std::vector<uint64_t> &whole, uint32_t batch_frames,
+                                                      size_t samples_per_block, uint32_t *batch_cap);
+// an analysis context for `frames` frames with its pinned buffers, from the coalescing front end's pool of idle ones
+struct PooledContext {
+    flacgpu_ctx *ctx;
+    uint8_t *in, *out;   // pinned; out holds flacgpu_packed_cap(ctx) bytes
+    size_t in_cap, out_cap;
+};
+int pooled_context_take(const flacgpu_options &g, uint32_t bps, uint32_t channels, uint32_t frames, int device, PooledContext *out);
+void pooled_context_give(const flacgpu_options &g, uint32_t bps, uint32_t channels, uint32_t frames, int device, const PooledContext &c);
 
 }  // namespace flacenc_host

@@ -1622,6 +1622,7 @@ int stream_header_len(const flacenc_options &o, uint32_t sample_rate, uint32_t b
     return rc;
 }
 void run_parallel(unsigned helpers, const std::function<void()> &fn) { WorkerPool::get().run(helpers, fn); }
+void set_last_error(const std::string &text) { g_err = text; }
 void release_lane_pool() {
     std::vector<Lane *> all;
     {

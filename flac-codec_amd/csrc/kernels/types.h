@@ -285,5 +285,14 @@ void launch_decode_finish(const Params &p, int32_t *decoded, const int32_t *expe
 void launch_decode_frames(const uint32_t *words, const uint64_t *frame_off, const uint32_t *frame_n,
                           uint64_t cap_bytes, uint32_t n_frames, uint32_t channels, uint32_t bps, uint32_t ldb,
                           int32_t *decoded, uint32_t *verify_counts, hipStream_t st);
+// decode_many.hip: k_md5_many for callers outside that file (ingest.hip).  Md5JobRec is its Md5Job
+// (kernels/decode_many.inc); digest receives 5 words per job, as the kernel leaves them.
+struct Md5JobRec {
+    uint64_t off, count;   // first interleaved int32 sample of the stream in `samples`, and how many
+    uint32_t width;        // bytes per sample: ceil(bps / 8)
+    uint32_t reserved;
+    uint32_t expect[4];    // the digest to compare with (all zero: none)
+};
+void launch_md5_many(const int32_t *samples, const Md5JobRec *jobs, uint32_t n_jobs, uint32_t *digest, hipStream_t st);
 }  // namespace flacgpu_k
 #endif

@@ -187,6 +187,15 @@ def _stream_lib():
         L.flacenc_encode_many_devices.argtypes = [po, C.POINTER(_CJob), C.c_size_t, C.c_uint32, C.POINTER(C.c_int),
                                                   C.c_uint32]
         L.flacenc_encode_many_coalesced.argtypes = [po, C.POINTER(_CJob), C.c_size_t, C.c_uint32]
+        pf = C.POINTER(_lib.OutFormat)
+        L.flacenc_device_batch_plan.argtypes = [po, pf, C.c_uint32, C.c_uint32, C.POINTER(_lib.DeviceJob), C.c_size_t,
+                                                C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+        L.flacenc_encode_many_device.argtypes = [po, vp, pf, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                 C.POINTER(_lib.DeviceJob), C.c_size_t, C.c_uint32, vp]
+        L.flacenc_ingest_sample.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int)]
+        L.flacenc_ingest_sample.restype = C.c_int32
+        L.flacenc_worst_case_bytes.restype = C.c_size_t
+        L.flacenc_worst_case_bytes.argtypes = [po, C.c_uint32, C.c_uint32, C.c_uint64]
         _bound = True
     return L
 
@@ -623,3 +632,64 @@ class BatchEncoder:
         h = self.prepare(streams, sample_rate, bits_per_sample, channels)
         self.run(h)
         return self.results(h, copy)
+
+    def prepare_device(self, tensor, lengths, bits_per_sample):
+        """The job array of an encode_device call: a [B, C, T] tensor is a PADDED batch of B streams of C channels,
+        stream i of lengths[i] (default T) samples; output buffers sized for the worst case and reused by later calls."""
+        L = _stream_lib()
+        if tensor.dim() != 3 or not tensor.is_contiguous() or not tensor.is_cuda:
+            raise ValueError("tensor must be a contiguous [B, C, T] tensor on the GPU")
+        dtype = {"torch.int32": _lib.SAMPLE_I32, "torch.int16": _lib.SAMPLE_I16, "torch.float32": _lib.SAMPLE_F32}.get(
+            str(tensor.dtype))
+        if dtype is None:
+            raise ValueError("tensor must be int16, int32 or float32")
+        n, channels, padded = (int(v) for v in tensor.shape)
+        lengths = [padded] * n if lengths is None else [int(v) for v in lengths]
+        if len(lengths) != n:
+            raise ValueError("one length per stream")
+        fmt = _lib.OutFormat(dtype, _lib.LAYOUT_PADDED, channels, 0, padded)
+        jobs = (_lib.DeviceJob * max(n, 1))()
+        co = self._opts._c_options()
+        for i, samples in enumerate(lengths):
+            cap = int(L.flacenc_worst_case_bytes(C.byref(co), bits_per_sample, max(channels, 1), samples))
+            if i >= len(self._bufs):
+                self._bufs.append(np.empty(cap, dtype=np.uint8))
+            elif self._bufs[i].size < cap:
+                self._bufs[i] = np.empty(cap, dtype=np.uint8)
+            jobs[i].samples = samples
+            jobs[i].out = self._bufs[i].ctypes.data
+            jobs[i].out_cap = self._bufs[i].size
+        return (jobs, n, co, fmt, channels)
+
+    def run_device(self, handle, tensor, sample_rate, bits_per_sample, verify_md5=True, stream=None):
+        """One call of flacenc_encode_many_device on a prepared job array; returns its return code (0, or the first
+        failing job's status -- every job's own status, out_len, altered and md5 are in the array)."""
+        import torch
+
+        L = _stream_lib()
+        jobs, n, co, fmt, channels = handle
+        if stream is None:
+            stream = torch.cuda.current_stream(tensor.device).cuda_stream
+        if co.device < 0:
+            co.device = tensor.device.index
+        return L.flacenc_encode_many_device(C.byref(co), tensor.data_ptr() if tensor.numel() else None, C.byref(fmt),
+                                            sample_rate, bits_per_sample, channels, jobs, n,
+                                            0 if verify_md5 else _lib.DEVICE_NO_MD5, stream or None)
+
+    def encode_device(self, tensor, lengths=None, sample_rate=44100, bits_per_sample=16, verify_md5=True, copy=True):
+        """A batch of streams held on the GPU -> .flac bytes, the samples never visiting the host
+        (flacenc_encode_many_device).  tensor: contiguous [B, C, T] torch tensor on the GPU, int16 (x >> (16 - bps)),
+        int32 (clamped to bps bits) or float32 (x * 2^(bps - 1), rounded to nearest even, clamped; NaN -> 0); lengths:
+        samples of every stream (default T; what lies behind is never read).  Runs behind the work queued on the tensor's
+        current torch stream and returns when the files are complete.  verify_md5=False leaves STREAMINFO's MD5 zero
+        ("unknown") and skips the hash kernel.  self.last_altered: per stream, the elements that were clamped, NaN or
+        (int16) lost non-zero low bits; self.last_md5: the digests."""
+        h = self.prepare_device(tensor, lengths, bits_per_sample)
+        rc = self.run_device(h, tensor, sample_rate, bits_per_sample, verify_md5)
+        jobs, n = h[0], h[1]
+        self.last_altered = [int(jobs[i].altered) for i in range(n)]
+        self.last_status = [int(jobs[i].status) for i in range(n)]
+        self.last_md5 = [bytes(jobs[i].md5) for i in range(n)]
+        _check(rc)
+        views = [self._bufs[i][: jobs[i].out_len] for i in range(n)]
+        return [v.tobytes() for v in views] if copy else views

@@ -628,6 +628,38 @@ int flacgpu_decoder_decode_windows(flacgpu_decoder *d, void *out, size_t out_cap
 int flacgpu_window_frames(const uint32_t *frame_n, uint32_t n_frames, uint64_t start, uint64_t length, uint32_t *first,
                           uint32_t *count, uint64_t *skip);
 
+/* ---- the encoder's ingest pass: a device tensor -> interleaved int32 the encoder reads in place ----------------------
+ * The device half of flacenc_encode_many_device (include/flacenc_stream.h), the mirror image of
+ * flacgpu_decoder_decode_as: a batch of streams of one shape held in device memory as int32, int16 or float32, planar and
+ * padded or interleaved and flat (flacgpu_out_format describes the INPUT here), is converted and written as interleaved
+ * int32 into a staging buffer the handle owns -- stream i at int32 element staging_offset (a multiple of 4: a 16-byte
+ * boundary, from which flacgpu_encode_segments_device reads segments in place).  Conversion (csrc/kernels/ingest_rule.h,
+ * the inverse of decode_as's): I32 clamped to bps bits; I16 x >> (16 - bps), bps <= 16; F32 x * 2^(bps - 1) rounded to
+ * nearest even and clamped, NaN -> 0.  Padding (rows c >= channels, elements t >= samples, gaps between flat streams) is
+ * never read.  This version always ingests; reading an aligned FLAT I32 batch in place is a follow-up.
+ *   submit  runs the pass on a stream of the handle's, ordered after `stream` (a hipStream_t; NULL: the legacy default
+ *           stream), and returns when the staging buffer is complete: d_pcm may be reused, *d_staging (valid until the next
+ *           submit) may be read from any stream.  With FLACGPU_INGEST_MD5 the MD5 of every stream's samples as
+ *           ceil(bps / 8)-byte little-endian values (k_md5_many, one lane per stream: about 15 MB/s per stream, fine for
+ *           many clips and poor for one long stream) is queued behind it and runs beside whatever the caller does next.
+ *   finish  waits for it; altered[i] (may be NULL) = elements of stream i that were clamped, NaN or (I16) lost non-zero
+ *           low bits; md5 (may be NULL; [n_streams][16]) is written only when the MD5 was asked for.
+ * The arguments are the ones flacenc_device_batch_plan validates; submit repeats the checks its kernel's bounds rest on. */
+#define FLACGPU_INGEST_MD5 1u
+typedef struct flacgpu_ingest flacgpu_ingest;
+typedef struct {
+    uint64_t in_offset;        /* FLAT: first element of the stream in d_pcm; PADDED: ignored (stream i is block i) */
+    uint64_t samples;          /* per channel */
+    uint64_t staging_offset;   /* first int32 of the stream in the staging buffer, a multiple of 4 */
+} flacgpu_ingest_stream;
+int flacgpu_ingest_create(int device, flacgpu_ingest **out);
+void flacgpu_ingest_destroy(flacgpu_ingest *g);
+int flacgpu_ingest_device(const flacgpu_ingest *g);
+int flacgpu_ingest_submit(flacgpu_ingest *g, const void *d_pcm, const flacgpu_out_format *fmt, uint32_t bits_per_sample,
+                          uint32_t channels, const flacgpu_ingest_stream *streams, uint32_t n_streams,
+                          uint64_t staging_elements, uint32_t flags, void *stream, int32_t **d_staging);
+int flacgpu_ingest_finish(flacgpu_ingest *g, uint32_t *altered, uint8_t *md5);
+
 /* EXPERIMENT, not on the product path: recomputes the autocorrelation of the last analysed
  * batch on the f64 matrix cores (v_mfma_f64_16x16x4_f64, block-Gram form), times that kernel,
  * reruns Levinson/quantisation on it and reports how many candidates' quantised LPC parameters

@@ -25,6 +25,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "flacenc_gpu.h" /* flacgpu_out_format, FLACGPU_SAMPLE_*, FLACGPU_LAYOUT_* (flacenc_encode_many_device) */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -200,6 +202,59 @@ void flacenc_release_pools(void);
 #define FLACENC_ALL_DEVICES 0xFFFFFFFFu
 int flacenc_encode_many_devices(const flacenc_options *opts, flacenc_job *jobs, size_t n_jobs, uint32_t threads,
                                 const int *devices, uint32_t n_devices);
+
+/* ---- a batch of streams RESIDENT IN DEVICE MEMORY -> finished .flac files, without a host copy of the samples --------
+ * The mirror image of flacgpu_decoder_decode_as (include/flacenc_gpu.h): `d_pcm` is a device tensor of int32, int16 or
+ * float32 elements holding n_jobs streams of one shape (sample rate, bits per sample, channels), laid out as `fmt` says
+ * (FLACGPU_SAMPLE_* / FLACGPU_LAYOUT_* as in the decoder; the format describes the INPUT here):
+ *   PADDED  [n_jobs][channels_padded][samples_padded], planar; of stream i only the first `channels` rows and the first
+ *           jobs[i].samples elements of each are read -- padding may hold anything;
+ *   FLAT    stream i is [samples][channels] interleaved from element jobs[i].in_offset; the streams must not overlap,
+ *           what lies between them is never read.
+ * Conversion to bits_per_sample-bit samples (csrc/kernels/ingest_rule.h, the exact inverse of decode_as's; testable on
+ * the host through flacenc_ingest_sample): I32 the value clamped to [-2^(bps-1), 2^(bps-1) - 1]; I16 x >> (16 - bps),
+ * bps <= 16 only; F32 x * 2^(bps-1) rounded to nearest even, clamped, NaN -> 0.  jobs[i].altered counts the elements of
+ * stream i that were clamped, were NaN or (I16) had non-zero bits below the ones kept.
+ * What happens: one ingest pass writes interleaved int32 into a staging buffer of the library's (staging_bytes = 4 x the
+ * sum over the streams of samples x channels rounded up to 4; this version always ingests -- reading an aligned FLAT I32
+ * batch in place is a follow-up); the MD5 of every stream is taken on the device (k_md5_many: one lane per stream, about
+ * 15 MB/s per stream -- fine for many clips, poor for one long stream; a faster chain is out of scope, and
+ * FLACENC_DEVICE_NO_MD5 is the way round it today); runs of whole blocks of several streams go through
+ * flacgpu_encode_segments_device in batches planned as flacenc_encode_many_coalesced plans them, on two pooled contexts in
+ * rotation (one batch's kernels run while the other's frames travel to pinned memory); a stream's short last block is a
+ * one-frame flacgpu_encode_device call on the staging buffer; everything in front of the first frame is
+ * flacenc_stream_header's; every output byte is copied once, from pinned memory to jobs[i].out.
+ * Output byte-identical to flacenc_encode_many's on the converted samples, stream by stream; a stream without samples
+ * gets FLACENC_ERR_INVALID_ARG in its status, as there; an `out` too small FLACENC_ERR_IO in that job's status, the other
+ * streams unaffected.  Synchronous: `d_pcm` may be reused when the call returns.  The ingest is ordered after `stream` (a
+ * hipStream_t; NULL: the legacy default stream, the rule of flacgpu_analyze_device).  opts->device < 0: the current device;
+ * d_pcm must live on that device.
+ * plan is pure host code (no device): it validates the call -- FLACENC_ERR_INVALID_ARG for channels_padded < channels, a
+ * stream longer than samples_padded, FLAT streams that overlap, channels outside 1..8, bits_per_sample outside 1..32, an
+ * unknown type or layout, reserved != 0, padded fields under FLAT; FLACENC_ERR_UNSUPPORTED for I16 with more than 16
+ * bits -- and returns the elements d_pcm must hold and the staging bytes.  encode runs the same checks first: a refused
+ * call launches nothing and writes nothing (no job field, no output byte).  Returns 0 or the first failing job's status. */
+typedef flacgpu_out_format flacenc_tensor_format;   /* the decoder's format record under a direction-neutral name */
+typedef struct {
+    uint64_t in_offset;      /* FLAT: first element of the stream; PADDED: ignored */
+    uint64_t samples;        /* per channel */
+    uint8_t *out;            /* caller-owned host buffer for the finished .flac */
+    size_t out_cap, out_len;
+    int32_t status;          /* FLACENC_OK or this stream's error */
+    uint32_t altered;
+    uint8_t md5[16];         /* what went into STREAMINFO */
+} flacenc_device_job;
+#define FLACENC_DEVICE_NO_MD5 1u   /* STREAMINFO MD5 all zero ("unknown"); no hash kernel, no digest download */
+int flacenc_device_batch_plan(const flacenc_options *opts, const flacenc_tensor_format *fmt, uint32_t bits_per_sample,
+                              uint32_t channels, const flacenc_device_job *jobs, size_t n_jobs, size_t *in_elements,
+                              size_t *staging_bytes);
+int flacenc_encode_many_device(const flacenc_options *opts, const void *d_pcm, const flacenc_tensor_format *fmt,
+                               uint32_t sample_rate, uint32_t bits_per_sample, uint32_t channels, flacenc_device_job *jobs,
+                               size_t n_jobs, uint32_t flags, void *stream);
+/* The conversion rule on the host, one element: raw_bits holds the element's bits (I16: in the low half).  *altered
+ * (may be NULL) = 1 when the element was changed beyond rounding.  A combination plan refuses (unknown type, bps outside
+ * 1..32, I16 with bps > 16) gives 0 and *altered = 1. */
+int32_t flacenc_ingest_sample(uint32_t sample_type, uint32_t raw_bits, uint32_t bits_per_sample, int *altered);
 
 /* FlacStreamWriter (encode.rs:1050-1290): header-less subset frames, parameters per call. */
 typedef struct flacenc_stream_writer flacenc_stream_writer;

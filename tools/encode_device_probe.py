@@ -1,0 +1,121 @@
+#!/usr/bin/env python3
+"""What BatchEncoder.encode_device saves a caller who holds a float32 [B, C, T] batch on the GPU.
+
+Workloads (the r07 shapes): 1024 clips of 10 s, 16 kHz mono 16-bit; 256 tracks of 3 min, 44.1 kHz stereo 16-bit.
+  leg (a)  what such a caller did before: tensor.cpu(), numpy quantise + interleave, BatchEncoder(coalesce=True).encode
+  leg (b)  encode_device, with and without the MD5
+Handle warm, median and min-max of --repeats (15) runs, sclk read before and after; both legs must give identical
+files.  Writes profiles/r11_encode_device.json.  --kernels: one encode_device call per workload and nothing else, for a
+`rocprofv3 --kernel-trace --stats -- python tools/encode_device_probe.py --kernels` run of its own (the per-kernel split:
+k_ingest, k_md5_many and the one-frame tail calls)."""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+WORKLOADS = {
+    "clips_1024x10s_16k_mono": dict(n=1024, samples=160000, channels=1, rate=16000),
+    "tracks_256x3min_44k1_stereo": dict(n=256, samples=3 * 60 * 44100, channels=2, rate=44100),
+}
+
+
+def sclk():
+    try:
+        out = subprocess.run(["rocm-smi", "--showclocks", "--json"], capture_output=True, text=True, timeout=20).stdout
+        return {k: v.get("sclk clock speed:") for k, v in json.loads(out).items() if isinstance(v, dict)}
+    except Exception as e:   # the figure is context, not a result
+        return {"error": str(e)}
+
+
+def make_batch(w, shrink):
+    import torch
+    from _pcm import synth_fast
+
+    n, T, ch = max(1, w["n"] // shrink), w["samples"], w["channels"]
+    base = synth_fast(11, ch, 16, T + 4096).reshape(-1, ch).T.astype(np.float32) / 32768.0   # [ch, T + 4096]
+    host = np.stack([base[:, (37 * i) % 4096:(37 * i) % 4096 + T] for i in range(n)])
+    return torch.from_numpy(np.ascontiguousarray(host)).cuda()
+
+
+def leg_a(enc, t):
+    x = t.cpu().numpy()
+    q = np.clip(np.rint(x.astype(np.float64) * 32768.0), -32768, 32767).astype(np.int32)
+    streams = [np.ascontiguousarray(q[i].T).reshape(-1) for i in range(q.shape[0])]
+    return enc.encode(streams, enc_rate, 16, x.shape[1])
+
+
+def timed(fn, repeats):
+    import torch
+
+    fn()   # warm: contexts, pinned buffers, staging
+    ts = []
+    for _ in range(repeats):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return {"median_ms": statistics.median(ts), "min_ms": min(ts), "max_ms": max(ts), "runs": repeats}
+
+
+def main():
+    global enc_rate
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeats", type=int, default=15)
+    ap.add_argument("--shrink", type=int, default=1, help="divide the stream counts (a quick look)")
+    ap.add_argument("--only", default=None, help="one workload's name")
+    ap.add_argument("--kernels", action="store_true")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r11_encode_device.json"))
+    a = ap.parse_args()
+    import torch
+
+    torch.cuda.init()
+    from flac_codec_amd import _lib
+    from flac_codec_amd.encode import BatchEncoder, Options
+
+    result = {"build_id": _lib.lib().flacgpu_build_id().decode() if hasattr(_lib.lib(), "flacgpu_build_id") else None,
+              "sclk_before": sclk(), "workloads": {}}
+    result["shrink"] = a.shrink
+    for name, w in WORKLOADS.items():
+        if a.only and name != a.only:
+            continue
+        t = make_batch(w, a.shrink)
+        enc_rate = w["rate"]
+        dev = BatchEncoder(Options.default())
+        if a.kernels:
+            dev.encode_device(t, None, sample_rate=w["rate"], bits_per_sample=16)
+            continue
+        host = BatchEncoder(Options.default(), coalesce=True)
+        files_a = leg_a(host, t)
+        files_b = dev.encode_device(t, None, sample_rate=w["rate"], bits_per_sample=16)
+        assert files_a == files_b, f"{name}: the two legs differ"
+        samples = t.numel()
+        r = {"streams": t.shape[0], "samples": samples,
+             "a_cpu_numpy_coalesced": timed(lambda: leg_a(host, t), a.repeats),
+             "b_encode_device": timed(lambda: dev.encode_device(t, None, sample_rate=w["rate"], bits_per_sample=16, copy=False), a.repeats),
+             "b_encode_device_no_md5": timed(lambda: dev.encode_device(t, None, sample_rate=w["rate"], bits_per_sample=16, verify_md5=False, copy=False), a.repeats)}
+        for k in ("a_cpu_numpy_coalesced", "b_encode_device", "b_encode_device_no_md5"):
+            r[k]["gsamples_per_s"] = samples / r[k]["median_ms"] / 1e6
+        result["workloads"][name] = r
+        print(name, json.dumps(r))
+        del t
+        torch.cuda.empty_cache()
+    if a.kernels:
+        return
+    result["sclk_after"] = sclk()
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(result, f, indent=1)
+    print("wrote", a.out)
+
+
+if __name__ == "__main__":
+    main()
