@@ -18,6 +18,7 @@ N_KERNELS = 12
 DECODE_OUT_DEVICE = 1   # flacgpu_decoder_decode flags (include/flacenc_gpu.h)
 DECODE_NO_MD5 = 2
 SAMPLE_I32, SAMPLE_I16, SAMPLE_F32 = 0, 1, 2   # flacgpu_out_format.dtype
+SAMPLE_S24 = 24   # packed 3-byte little-endian elements
 LAYOUT_FLAT, LAYOUT_PADDED = 0, 1              # flacgpu_out_format.layout
 
 

@@ -3,6 +3,7 @@
 // One of the translation units of libflacenc_amd.so (gfx950 only).  Kernels: kernels/frame_scan.inc (frame discovery)
 // and kernels/decode_many.inc (decode, CRC-16, finish, MD5); the subframe decoder is decode.inc's, unchanged.
 #include "kernels/types.h"
+#include "kernels/sample_types.h"
 #include "flac_stream.h"
 
 #include <stdlib.h>
@@ -245,7 +246,12 @@ int scan_impl(flacgpu_decoder *d, const uint8_t *const *data, const size_t *len,
     return FLACGPU_OK;
 }
 
-constexpr size_t elem_size(uint32_t dtype) { return dtype == FLACGPU_SAMPLE_I16 ? 2 : 4; }
+// k_pad_rows for the element size of `dtype`
+void launch_pad_rows(uint32_t dtype, uint32_t rows, hipStream_t st, const PadStream *streams, uint32_t Cp, uint64_t T,
+                     void *dst) {
+    const auto k = dtype == FLACGPU_SAMPLE_I16 ? k_pad_rows<2> : dtype == FLACGPU_SAMPLE_S24 ? k_pad_rows<3> : k_pad_rows<4>;
+    hipLaunchKernelGGL(k, dim3(rows), dim3(WG), 0, st, streams, Cp, T, static_cast<uint8_t *>(dst));
+}
 
 // the finish kernel of a format other than I32 / FLAT
 template <uint32_t DT, bool PADDED>
@@ -286,12 +292,7 @@ int finish_as_tables(flacgpu_decoder *d, const flacgpu_out_format &fmt, void *ds
     if (int rc = d->pad_streams.ensure(sizeof(PadStream) * n)) return rc;
     HIP_TRY(hipMemcpyAsync(d->pad_streams.p, ps.data(), sizeof(PadStream) * n, hipMemcpyHostToDevice, d->st));
     HIP_TRY(hipStreamSynchronize(d->st));   // the tables leave scope
-    if (fmt.dtype == FLACGPU_SAMPLE_I16)
-        hipLaunchKernelGGL(k_pad_rows<2>, dim3(n * Cp), dim3(WG), 0, d->st, d->pad_streams.as<const PadStream>(), Cp, T,
-                           static_cast<uint8_t *>(dst));
-    else
-        hipLaunchKernelGGL(k_pad_rows<4>, dim3(n * Cp), dim3(WG), 0, d->st, d->pad_streams.as<const PadStream>(), Cp, T,
-                           static_cast<uint8_t *>(dst));
+    launch_pad_rows(fmt.dtype, n * Cp, d->st, d->pad_streams.as<const PadStream>(), Cp, T, dst);
     HIP_TRY(hipGetLastError());
     return FLACGPU_OK;
 }
@@ -346,6 +347,9 @@ int decode_impl(flacgpu_decoder *d, void *out, uint32_t flags, flacgpu_decoded_s
             else if (fmt->dtype == FLACGPU_SAMPLE_F32)
                 padded ? launch_finish_as<DT_F32, true>(d, F, dst, T, side)
                        : launch_finish_as<DT_F32, false>(d, F, dst, T, side);
+            else if (fmt->dtype == FLACGPU_SAMPLE_S24)
+                padded ? launch_finish_as<DT_S24, true>(d, F, dst, T, side)
+                       : launch_finish_as<DT_S24, false>(d, F, dst, T, side);
             else   // I32 / FLAT takes the branch above
                 launch_finish_as<DT_I32, true>(d, F, dst, T, side);
         }
@@ -515,12 +519,7 @@ int decode_windows_impl(flacgpu_decoder *d, void *out, uint64_t out_bytes, const
     HIP_TRY(hipMemcpyAsync(d->pad_streams.p, pad.data(), sizeof(PadStream) * n_windows, hipMemcpyHostToDevice, d->st));
     HIP_TRY(hipMemsetAsync(d->counts.p, 0, 8 * (size_t)n_windows, d->st));
     // a window's samples and channels stand where k_pad_rows reads a stream's: it zeroes what no frame writes
-    if (fmt.dtype == FLACGPU_SAMPLE_I16)
-        hipLaunchKernelGGL(k_pad_rows<2>, dim3(n_windows * Cp), dim3(WG), 0, d->st, d->pad_streams.as<const PadStream>(),
-                           Cp, T, static_cast<uint8_t *>(dst));
-    else
-        hipLaunchKernelGGL(k_pad_rows<4>, dim3(n_windows * Cp), dim3(WG), 0, d->st, d->pad_streams.as<const PadStream>(),
-                           Cp, T, static_cast<uint8_t *>(dst));
+    launch_pad_rows(fmt.dtype, n_windows * Cp, d->st, d->pad_streams.as<const PadStream>(), Cp, T, dst);
     if (F) {
         HIP_TRY(hipMemcpyAsync(d->win_frames.p, sel.data(), sizeof(ManyFrame) * F, hipMemcpyHostToDevice, d->st));
         HIP_TRY(hipMemcpyAsync(d->win_desc.p, desc.data(), sizeof(WinFrame) * F, hipMemcpyHostToDevice, d->st));
@@ -532,6 +531,7 @@ int decode_windows_impl(flacgpu_decoder *d, void *out, uint64_t out_bytes, const
                            d->counts.as<uint32_t>());
         const auto k = fmt.dtype == FLACGPU_SAMPLE_I16   ? k_finish_window<DT_I16>
                        : fmt.dtype == FLACGPU_SAMPLE_F32 ? k_finish_window<DT_F32>
+                       : fmt.dtype == FLACGPU_SAMPLE_S24 ? k_finish_window<DT_S24>
                                                          : k_finish_window<DT_I32>;
         hipLaunchKernelGGL(k, dim3(F), dim3(WG), 0, d->st, frames, d->win_desc.as<const WinFrame>(),
                            d->scratch.as<const int32_t>(), d->codes.as<const uint32_t>(), static_cast<uint8_t *>(dst), T,
@@ -637,7 +637,7 @@ int flacgpu_decoder_plan_output(const flacgpu_out_format *fmt, const flacgpu_dec
     if (!fmt || !out_bytes || (n_streams && !streams)) return FLACGPU_ERR_INVALID_ARG;
     *out_bytes = 0;
     const bool padded = fmt->layout == FLACGPU_LAYOUT_PADDED;
-    if (fmt->dtype > FLACGPU_SAMPLE_F32 || fmt->layout > FLACGPU_LAYOUT_PADDED || fmt->reserved ||
+    if (!sample_type_known(fmt->dtype) || fmt->layout > FLACGPU_LAYOUT_PADDED || fmt->reserved ||
         (!padded && (fmt->channels_padded || fmt->samples_padded))) {
         g_last_error = "flacgpu_decoder_plan_output: unknown dtype or layout, reserved not 0, or padded fields under FLAT";
         return FLACGPU_ERR_INVALID_ARG;
@@ -647,15 +647,15 @@ int flacgpu_decoder_plan_output(const flacgpu_out_format *fmt, const flacgpu_dec
     for (uint32_t i = 0; i < n_streams; i++) {
         const flacgpu_decoded_stream &r = streams[i];
         if (r.rc != FLACGPU_OK) continue;
-        if (fmt->dtype == FLACGPU_SAMPLE_I16 && r.info.bits_per_sample > 16) {
-            g_last_error = "flacgpu_decoder_plan_output: int16 output, but stream " + std::to_string(i) + " has " +
-                           std::to_string(r.info.bits_per_sample) + " bits per sample";
+        if (sample_type_max_bits(fmt->dtype) && r.info.bits_per_sample > sample_type_max_bits(fmt->dtype)) {
+            g_last_error = std::string("flacgpu_decoder_plan_output: ") + sample_type_name(fmt->dtype) + " output, but stream " +
+                           std::to_string(i) + " has " + std::to_string(r.info.bits_per_sample) + " bits per sample";
             return FLACGPU_ERR_UNSUPPORTED;
         }
         total += r.info.decoded_samples * r.info.channels;
         any = any || (r.info.decoded_samples && r.info.channels);
     }
-    const uint64_t es = elem_size(fmt->dtype);
+    const uint64_t es = sample_type_bytes(fmt->dtype);
     if (!padded) {
         *out_bytes = total * es;
         return FLACGPU_OK;
@@ -696,7 +696,7 @@ int flacgpu_decoder_decode_as(flacgpu_decoder *d, void *out, size_t out_cap_byte
         g_last_error = "output buffer too small";
         return FLACGPU_ERR_BUFFER_TOO_SMALL;
     }
-    if (reinterpret_cast<uintptr_t>(out) % elem_size(fmt->dtype)) {
+    if (reinterpret_cast<uintptr_t>(out) % sample_type_align(fmt->dtype)) {
         g_last_error = "flacgpu_decoder_decode_as: out is not aligned to its element size";
         return FLACGPU_ERR_INVALID_ARG;
     }
@@ -722,7 +722,7 @@ int flacgpu_decoder_plan_windows(const flacgpu_out_format *fmt, const flacgpu_de
                                  uint32_t n_streams, const flacgpu_window *w, uint32_t n_windows, uint64_t *out_bytes) {
     if (!fmt || !out_bytes || (n_streams && !streams) || (n_windows && !w)) return FLACGPU_ERR_INVALID_ARG;
     *out_bytes = 0;
-    if (fmt->dtype > FLACGPU_SAMPLE_F32 || fmt->layout != FLACGPU_LAYOUT_PADDED || fmt->reserved) {
+    if (!sample_type_known(fmt->dtype) || fmt->layout != FLACGPU_LAYOUT_PADDED || fmt->reserved) {
         g_last_error = "flacgpu_decoder_plan_windows: unknown dtype, a layout other than PADDED, or reserved not 0";
         return FLACGPU_ERR_INVALID_ARG;
     }
@@ -741,17 +741,18 @@ int flacgpu_decoder_plan_windows(const flacgpu_out_format *fmt, const flacgpu_de
             return FLACGPU_ERR_INVALID_ARG;
         }
     }
-    for (uint32_t i = 0; i < n_windows && fmt->dtype == FLACGPU_SAMPLE_I16; i++) {
+    for (uint32_t i = 0; i < n_windows && sample_type_max_bits(fmt->dtype); i++) {
         const flacgpu_decoded_stream &r = streams[w[i].stream];
-        if (r.rc == FLACGPU_OK && r.info.bits_per_sample > 16) {
-            g_last_error = "flacgpu_decoder_plan_windows: int16 output, but stream " + std::to_string(w[i].stream) +
-                           " has " + std::to_string(r.info.bits_per_sample) + " bits per sample";
+        if (r.rc == FLACGPU_OK && r.info.bits_per_sample > sample_type_max_bits(fmt->dtype)) {
+            g_last_error = std::string("flacgpu_decoder_plan_windows: ") + sample_type_name(fmt->dtype) + " output, but stream " +
+                           std::to_string(w[i].stream) + " has " + std::to_string(r.info.bits_per_sample) +
+                           " bits per sample";
             return FLACGPU_ERR_UNSUPPORTED;
         }
     }
     uint64_t bytes = 0;
     if (__builtin_mul_overflow((uint64_t)n_windows * fmt->channels_padded, fmt->samples_padded, &bytes) ||
-        __builtin_mul_overflow(bytes, (uint64_t)elem_size(fmt->dtype), &bytes)) {
+        __builtin_mul_overflow(bytes, (uint64_t)sample_type_bytes(fmt->dtype), &bytes)) {
         g_last_error = "flacgpu_decoder_plan_windows: the windows exceed 2^64 bytes";
         return FLACGPU_ERR_UNSUPPORTED;
     }
@@ -775,7 +776,7 @@ int flacgpu_decoder_decode_windows(flacgpu_decoder *d, void *out, size_t out_cap
         g_last_error = "output buffer too small";
         return FLACGPU_ERR_BUFFER_TOO_SMALL;
     }
-    if (reinterpret_cast<uintptr_t>(out) % elem_size(fmt->dtype)) {
+    if (reinterpret_cast<uintptr_t>(out) % sample_type_align(fmt->dtype)) {
         g_last_error = "flacgpu_decoder_decode_windows: out is not aligned to its element size";
         return FLACGPU_ERR_INVALID_ARG;
     }

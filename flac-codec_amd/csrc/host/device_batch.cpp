@@ -1,5 +1,5 @@
-// device_batch.cpp -- flacenc_encode_many_device: a batch of streams of one shape held in DEVICE memory (int32, int16 or
-// float32; planar and padded, or interleaved and flat) -> finished .flac files in the callers' host buffers, the samples
+// device_batch.cpp -- flacenc_encode_many_device: a batch of streams of one shape held in DEVICE memory (int32, int16, packed
+// 24-bit or float32; planar and padded, or interleaved and flat) -> finished .flac files in the callers' host buffers, the samples
 // never visiting the host.  The mirror image of flacgpu_decoder_decode_as.
 //
 //   * plan (pure host code): the checks, the elements the tensor must hold, the staging bytes;
@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "../kernels/ingest_rule.h"
+#include "../kernels/sample_types.h"
 #include "host_internal.h"
 
 using namespace flacenc_host;
@@ -90,13 +91,14 @@ int plan_impl(const flacenc_options *o, const flacenc_tensor_format *fmt, uint32
     if (!o || !fmt || (!jobs && n_jobs)) return refuse(FLACENC_ERR_INVALID_ARG, "a null argument");
     if (int e = options_error(*o)) return e;
     const bool padded = fmt->layout == FLACGPU_LAYOUT_PADDED;
-    if (fmt->dtype > FLACGPU_SAMPLE_F32 || fmt->layout > FLACGPU_LAYOUT_PADDED || fmt->reserved ||
+    if (!sample_type_known(fmt->dtype) || fmt->layout > FLACGPU_LAYOUT_PADDED || fmt->reserved ||
         (!padded && (fmt->channels_padded || fmt->samples_padded)))
         return refuse(FLACENC_ERR_INVALID_ARG, "unknown dtype or layout, reserved not 0, or padded fields under FLAT");
     if (channels < 1 || channels > FLACGPU_MAX_CHANNELS || bps < 1 || bps > 32)
         return refuse(FLACENC_ERR_INVALID_ARG, "channels outside 1..8 or bits per sample outside 1..32");
-    if (fmt->dtype == FLACGPU_SAMPLE_I16 && bps > 16)
-        return refuse(FLACENC_ERR_UNSUPPORTED, "int16 input, but " + std::to_string(bps) + " bits per sample");
+    if (sample_type_max_bits(fmt->dtype) && bps > sample_type_max_bits(fmt->dtype))
+        return refuse(FLACENC_ERR_UNSUPPORTED, std::string(sample_type_name(fmt->dtype)) + " input, but " + std::to_string(bps) +
+                                                   " bits per sample");
     if (n_jobs > 0xFFFFFFFFull) return refuse(FLACENC_ERR_UNSUPPORTED, "more than 2^32 - 1 streams");
     if (padded && fmt->channels_padded < channels)
         return refuse(FLACENC_ERR_INVALID_ARG, "channels_padded is less than channels");
@@ -173,8 +175,8 @@ extern "C" {
 int32_t flacenc_ingest_sample(uint32_t sample_type, uint32_t raw_bits, uint32_t bits_per_sample, int *altered) {
     int a = 1;
     int32_t v = 0;
-    if (sample_type <= INGEST_F32 && bits_per_sample >= 1 && bits_per_sample <= 32 &&
-        !(sample_type == INGEST_I16 && bits_per_sample > 16))
+    if (sample_type_known(sample_type) && bits_per_sample >= 1 && bits_per_sample <= 32 &&
+        !(sample_type_max_bits(sample_type) && bits_per_sample > sample_type_max_bits(sample_type)))
         v = ingest_sample(sample_type, raw_bits, bits_per_sample, &a);
     if (altered) *altered = a;
     return v;
@@ -198,7 +200,7 @@ int flacenc_encode_many_device(const flacenc_options *opts, const void *d_pcm, c
     if (int rc = plan_impl(opts, fmt, bits_per_sample, channels, jobs, n_jobs, &in_elements, &staging_elements, &staging_off))
         return rc;
     if ((flags & ~FLACENC_DEVICE_NO_MD5) || (in_elements && !d_pcm) ||
-        reinterpret_cast<uintptr_t>(d_pcm) % (fmt->dtype == FLACGPU_SAMPLE_I16 ? 2 : 4)) {
+        reinterpret_cast<uintptr_t>(d_pcm) % sample_type_align(fmt->dtype)) {
         set_last_error("flacenc_encode_many_device: unknown flags, no tensor, or a tensor not aligned to its element size");
         return FLACENC_ERR_INVALID_ARG;
     }

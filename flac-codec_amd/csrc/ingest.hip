@@ -4,6 +4,7 @@
 // One of the translation units of libflacenc_amd.so (gfx950 only).
 #include "kernels/types.h"
 #include "kernels/ingest_rule.h"
+#include "kernels/sample_types.h"
 
 #include <string.h>
 
@@ -99,11 +100,11 @@ int flacgpu_ingest_submit(flacgpu_ingest *g, const void *d_pcm, const flacgpu_ou
     if (!g || !fmt || !d_staging || (n_streams && !streams) || (flags & ~FLACGPU_INGEST_MD5)) return FLACGPU_ERR_INVALID_ARG;
     *d_staging = nullptr;
     const bool padded = fmt->layout == FLACGPU_LAYOUT_PADDED;
-    const size_t es = fmt->dtype == FLACGPU_SAMPLE_I16 ? 2 : 4;
-    if (fmt->dtype > FLACGPU_SAMPLE_F32 || fmt->layout > FLACGPU_LAYOUT_PADDED || channels < 1 ||
+    const uint32_t widest = sample_type_max_bits(fmt->dtype);
+    if (!sample_type_known(fmt->dtype) || fmt->layout > FLACGPU_LAYOUT_PADDED || channels < 1 ||
         channels > FLACGPU_MAX_CHANNELS || bits_per_sample < 1 || bits_per_sample > 32 ||
-        (fmt->dtype == FLACGPU_SAMPLE_I16 && bits_per_sample > 16) || (padded && fmt->channels_padded < channels) ||
-        reinterpret_cast<uintptr_t>(d_pcm) % es) {
+        (widest && bits_per_sample > widest) || (padded && fmt->channels_padded < channels) ||
+        reinterpret_cast<uintptr_t>(d_pcm) % sample_type_align(fmt->dtype)) {
         g_last_error = "flacgpu_ingest_submit: a format, shape or alignment that flacenc_device_batch_plan refuses";
         return FLACGPU_ERR_INVALID_ARG;
     }
@@ -166,6 +167,8 @@ int flacgpu_ingest_submit(flacgpu_ingest *g, const void *d_pcm, const flacgpu_ou
         const uint32_t T = (uint32_t)tiles;
         if (fmt->dtype == FLACGPU_SAMPLE_I16)
             launch_ingest<INGEST_I16>(padded, T, g->st, d_pcm, ds, n_streams, channels, bits_per_sample, fmt->samples_padded, out, alt);
+        else if (fmt->dtype == FLACGPU_SAMPLE_S24)
+            launch_ingest<INGEST_S24>(padded, T, g->st, d_pcm, ds, n_streams, channels, bits_per_sample, fmt->samples_padded, out, alt);
         else if (fmt->dtype == FLACGPU_SAMPLE_F32)
             launch_ingest<INGEST_F32>(padded, T, g->st, d_pcm, ds, n_streams, channels, bits_per_sample, fmt->samples_padded, out, alt);
         else

@@ -8,7 +8,8 @@
 //   K_d4 k_md5_many      lane per stream: MD5 of the stream's interleaved samples as ceil(bps / 8)-byte
 //                        little-endian values (decode.rs:1282-1310 `verify`)
 //   K_d5 k_finish_as     workgroup per frame: k_finish_many's arithmetic, the samples converted in registers to
-//                        int16 / float32 (or left int32) and written flat or into padded planar rows; with MD5 also
+//                        int16 / packed 24-bit / float32 (or left int32) and written flat or into padded planar rows;
+//                        with MD5 also
 //                        the interleaved int32 that k_md5_many reads
 //   K_d6 k_pad_rows      workgroup per (stream, channel row) of a padded batch: zeroes what no frame writes
 //   K_d7 k_finish_window workgroup per selected frame of a sample window (flacgpu_decoder_decode_windows): k_finish_as's
@@ -109,7 +110,9 @@ __global__ void __launch_bounds__(WG) k_finish_many(const ManyFrame *__restrict_
 }
 
 // ---- other sample formats and layouts (flacgpu_decoder_decode_as) ----
-constexpr uint32_t DT_I32 = 0, DT_I16 = 1, DT_F32 = 2;   // FLACGPU_SAMPLE_*
+constexpr uint32_t DT_I32 = 0, DT_I16 = 1, DT_F32 = 2, DT_S24 = 24;   // FLACGPU_SAMPLE_*
+// bytes per element; S24 elements are 3 bytes, little-endian, packed
+template <uint32_t DT> constexpr uint32_t elem_bytes() { return DT == DT_I16 ? 2 : DT == DT_S24 ? 3 : 4; }
 
 // One sample of a frame, the stereo decorrelation undone: k_finish_many's arithmetic (64-bit mid/side; a code of 1
 // means that nothing is left to undo), kept apart from it so that its code stays as it is.
@@ -128,9 +131,11 @@ __device__ __forceinline__ int32_t frame_sample(const int32_t *__restrict__ rows
     return (int32_t)(c ? rr : l);
 }
 
-// The bits of one output element: I16 sample << (16 - bps) in the low half, F32 (float)sample * 2^-(bps - 1)
+// The bits of one output element: I16 sample << (16 - bps) in the low half, S24 sample << (24 - bps) in the low 24
+// bits (bits 24-31 zero: store_run3 ORs neighbours together), F32 (float)sample * 2^-(bps - 1)
 // (the int -> float conversion rounds to nearest even, the scale is a power of two and so exact).
 template <uint32_t DT> __device__ __forceinline__ uint32_t sample_bits(int32_t v, uint32_t bps) {
+    if (DT == DT_S24) return ((uint32_t)v << ((24u - bps) & 31u)) & 0xFFFFFFu;
     if (DT == DT_I16) return ((uint32_t)v << ((16u - bps) & 15u)) & 0xFFFFu;
     if (DT == DT_F32) return __float_as_uint(__int2float_rn(v) * __uint_as_float((128u - bps) << 23));
     return (uint32_t)v;
@@ -172,6 +177,48 @@ __device__ __forceinline__ void store_run(uint8_t *dst, uint32_t n, uint32_t tid
     }
 }
 
+// n packed 3-byte elements to dst (any byte address), element e = get(e) in the low 24 bits of a dword, bits 24-31
+// zero.  The run is the 3n bytes [dst, dst + 3n): byte b belongs to element b / 3 and is its byte b % 3.  Single bytes
+// up to the first 16-byte boundary (at most 15; an element may straddle the boundary), then 16 bytes per lane
+// (consecutive lanes, consecutive 16 bytes), then single bytes (at most 15).  Every byte of the run is stored exactly
+// once and no other byte is touched: two runs that meet at any byte (adjacent frames of a FLAT stream) never write the
+// same byte.  Indices are 32-bit (3n < 2^32: n <= 65535 * 8), so that / 3 is a multiply-high.
+// A 16-byte group at run byte B (B + 16 <= 3n), with e0 = B / 3 and r = B % 3, holds bytes of elements e0 .. e0 + 5 and
+// of no other: its last byte B + 15 belongs to element (B + 15) / 3 = e0 + (r + 15) / 3 = e0 + 5 for r = 0, 1, 2.  That
+// byte lies inside the run, B + 15 <= 3n - 1, hence e0 + 5 <= (3n - 1) / 3 = n - 1: get(n) is never needed, nor any
+// element whose bytes the group does not hold.  The 18 bytes of the six elements are put together from e0's first byte
+// on (u0 .. u4) and shifted down by r bytes; dword k of the group is then get-bits of run bytes B + 4k .. B + 4k + 3,
+// which is get(e) >> 8r' | get(e + 1) << (24 - 8r') for e = (B + 4k) / 3, r' = (B + 4k) % 3.
+template <class Get>
+__device__ __forceinline__ void store_run3(uint8_t *dst, uint32_t n, uint32_t tid, uint32_t nthreads, Get get) {
+    const uint32_t bytes = 3u * n;
+    const uint32_t head = min(bytes, (16u - (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 15u)) & 15u);
+    const uint32_t nv = (bytes - head) / 16u, tail_at = head + nv * 16u;
+    if (tid < head) dst[tid] = (uint8_t)(get(tid / 3u) >> (8u * (tid % 3u)));
+    uint4 *body = reinterpret_cast<uint4 *>(dst + head);
+    for (uint32_t v = tid; v < nv; v += nthreads) {
+        const uint32_t at = head + v * 16u, e = at / 3u, sh = 8u * (at - 3u * e);
+        const uint32_t g0 = get(e), g1 = get(e + 1), g2 = get(e + 2), g3 = get(e + 3), g4 = get(e + 4), g5 = get(e + 5);
+        const uint64_t u10 = (uint64_t)(g0 | g1 << 24) | (uint64_t)(g1 >> 8 | g2 << 16) << 32;
+        const uint64_t u21 = (u10 >> 32) | (uint64_t)(g2 >> 16 | g3 << 8) << 32;
+        const uint64_t u32 = (u21 >> 32) | (uint64_t)(g4 | g5 << 24) << 32;
+        const uint64_t u43 = (u32 >> 32) | (uint64_t)(g5 >> 8) << 32;
+        body[v] = make_uint4((uint32_t)(u10 >> sh), (uint32_t)(u21 >> sh), (uint32_t)(u32 >> sh),
+                             (uint32_t)(u43 >> sh));
+    }
+    if (tid < bytes - tail_at) {
+        const uint32_t b = tail_at + tid;
+        dst[b] = (uint8_t)(get(b / 3u) >> (8u * (b % 3u)));
+    }
+}
+
+// a run of n elements of DT: store_run, or store_run3 for the packed 3-byte elements
+template <uint32_t ES, class Get>
+__device__ __forceinline__ void store_elems(uint8_t *dst, uint32_t n, uint32_t tid, uint32_t nthreads, Get get) {
+    if constexpr (ES == 3) store_run3(dst, n, tid, nthreads, get);
+    else store_run<ES>(dst, n, tid, nthreads, get);
+}
+
 // pad_out (PADDED only): the frame's first element of channel 0, row + the frame's first sample; channel c is
 // samples_padded elements further per channel.  side (MD5 only): interleaved int32 at the frame's flat offset,
 // written as k_finish_many writes it.
@@ -181,7 +228,7 @@ __global__ void __launch_bounds__(WG) k_finish_as(const ManyFrame *__restrict__ 
                                                   const uint32_t *__restrict__ codes, uint8_t *__restrict__ out,
                                                   const uint64_t *__restrict__ pad_out, uint64_t samples_padded,
                                                   int32_t *__restrict__ side, uint32_t *__restrict__ slot_counts) {
-    constexpr uint32_t ES = DT == DT_I16 ? 2 : 4;
+    constexpr uint32_t ES = elem_bytes<DT>();
     const uint32_t f = blockIdx.x;
     const ManyFrame fr = frames[f];
     const uint32_t code = codes[f];
@@ -192,20 +239,20 @@ __global__ void __launch_bounds__(WG) k_finish_as(const ManyFrame *__restrict__ 
     const int32_t *rows = scratch + fr.scratch;
     if (PADDED) {
         for (uint32_t c = 0; c < C; c++)
-            store_run<ES>(out + (pad_out[f] + (uint64_t)c * samples_padded) * ES, n, threadIdx.x, WG, [&](uint32_t i) {
+            store_elems<ES>(out + (pad_out[f] + (uint64_t)c * samples_padded) * ES, n, threadIdx.x, WG, [&](uint32_t i) {
                 return sample_bits<DT>(frame_sample(rows, ldb, acode, i, c), bps);
             });
     } else {
         uint8_t *o = out + fr.out * ES;
         if (C == 1)
-            store_run<ES>(o, n, threadIdx.x, WG,
+            store_elems<ES>(o, n, threadIdx.x, WG,
                           [&](uint32_t e) { return sample_bits<DT>(rows[e], bps); });
         else if (C == 2)
-            store_run<ES>(o, 2 * n, threadIdx.x, WG, [&](uint32_t e) {
+            store_elems<ES>(o, 2 * n, threadIdx.x, WG, [&](uint32_t e) {
                 return sample_bits<DT>(frame_sample(rows, ldb, acode, e >> 1, e & 1u), bps);
             });
         else
-            store_run<ES>(o, C * n, threadIdx.x, WG, [&](uint32_t e) {
+            store_elems<ES>(o, C * n, threadIdx.x, WG, [&](uint32_t e) {
                 return sample_bits<DT>(rows[(size_t)(e % C) * ldb + e / C], bps);
             });
     }
@@ -222,7 +269,8 @@ struct PadStream {
     uint32_t reserved;
 };
 // Workgroup per (stream, channel row): zeroes [decoded_samples, samples_padded) of a channel the stream has and the
-// whole row of one it has not.  Elements up to the first 16-byte boundary, 16 bytes per lane, elements.
+// whole row of one it has not.  Elements up to the first 16-byte boundary, 16 bytes per lane, elements (ES == 3, the
+// packed 24-bit elements: single bytes on both sides, a row begins and ends at any byte).
 template <uint32_t ES>
 __global__ void __launch_bounds__(WG) k_pad_rows(const PadStream *__restrict__ streams, uint32_t channels_padded,
                                                  uint64_t samples_padded, uint8_t *__restrict__ out) {
@@ -233,13 +281,17 @@ __global__ void __launch_bounds__(WG) k_pad_rows(const PadStream *__restrict__ s
     const uint64_t bytes = (samples_padded - from) * ES;
     const uint64_t head = min(bytes, (uint64_t)((16u - (uint32_t)(reinterpret_cast<uintptr_t>(p) & 15u)) & 15u));
     const uint64_t nv = (bytes - head) / 16, tail_at = head + nv * 16;
-    if (threadIdx.x * ES < head) {
+    if (ES == 3) {
+        if (threadIdx.x < head) p[threadIdx.x] = 0;
+    } else if (threadIdx.x * ES < head) {
         if (ES == 2) reinterpret_cast<uint16_t *>(p)[threadIdx.x] = 0;
         else reinterpret_cast<uint32_t *>(p)[threadIdx.x] = 0;
     }
     uint4 *body = reinterpret_cast<uint4 *>(p + head);
     for (uint64_t v = threadIdx.x; v < nv; v += WG) body[v] = make_uint4(0, 0, 0, 0);
-    if (threadIdx.x * ES < bytes - tail_at) {
+    if (ES == 3) {
+        if (threadIdx.x < bytes - tail_at) p[tail_at + threadIdx.x] = 0;
+    } else if (threadIdx.x * ES < bytes - tail_at) {
         if (ES == 2) reinterpret_cast<uint16_t *>(p + tail_at)[threadIdx.x] = 0;
         else reinterpret_cast<uint32_t *>(p + tail_at)[threadIdx.x] = 0;
     }
@@ -356,7 +408,7 @@ struct WinFrame {
     uint32_t reserved;
 };
 // Workgroup per selected frame: frame_sample's decorrelation and sample_bits' conversion of the kept samples, planar
-// into the window's rows.  A row position is arbitrary, hence store_run.  A frame that did not parse is counted for
+// into the window's rows.  A row position is arbitrary, hence store_run / store_run3.  A frame that did not parse is counted for
 // its window (win_counts[2 * window]) and written as decoded, as k_finish_as does.
 template <uint32_t DT>
 __global__ void __launch_bounds__(WG) k_finish_window(const ManyFrame *__restrict__ frames,
@@ -364,7 +416,7 @@ __global__ void __launch_bounds__(WG) k_finish_window(const ManyFrame *__restric
                                                       const int32_t *__restrict__ scratch,
                                                       const uint32_t *__restrict__ codes, uint8_t *__restrict__ out,
                                                       uint64_t samples_padded, uint32_t *__restrict__ win_counts) {
-    constexpr uint32_t ES = DT == DT_I16 ? 2 : 4;
+    constexpr uint32_t ES = elem_bytes<DT>();
     const uint32_t f = blockIdx.x;
     const ManyFrame fr = frames[f];
     const WinFrame w = win[f];
@@ -375,6 +427,6 @@ __global__ void __launch_bounds__(WG) k_finish_window(const ManyFrame *__restric
     const uint32_t ldb = (fr.n + 3u) & ~3u, bps = w.bps;
     const int32_t *rows = scratch + fr.scratch + w.keep_first;   // sample i of the run is sample keep_first + i
     for (uint32_t c = 0; c < w.channels; c++)
-        store_run<ES>(out + (w.row + (uint64_t)c * samples_padded + w.at) * ES, w.keep_last - w.keep_first, threadIdx.x,
+        store_elems<ES>(out + (w.row + (uint64_t)c * samples_padded + w.at) * ES, w.keep_last - w.keep_first, threadIdx.x,
                       WG, [&](uint32_t i) { return sample_bits<DT>(frame_sample(rows, ldb, acode, i, c), bps); });
 }

@@ -1,6 +1,7 @@
 // ingest.inc -- the encoder's ingest pass (ingest.hip): a caller's device tensor -> what the encoder reads in place.
 // Included inside ingest.hip's anonymous namespace, after ingest_rule.h.
-//   K_i1 k_ingest<DT, PADDED>  workgroup per tile of one stream: int32 / int16 / float32 elements, planar rows of a padded
+//   K_i1 k_ingest<DT, PADDED>  workgroup per tile of one stream: int32 / int16 / packed 24-bit / float32 elements, planar
+//                              rows of a padded
 //                              [n_streams][channels_padded][samples_padded] batch or interleaved streams at element
 //                              offsets of their own, converted by ingest_sample (ingest_rule.h) and written as
 //                              interleaved int32 into the staging buffer -- every stream from a 16-byte boundary, the
@@ -65,6 +66,64 @@ __device__ __forceinline__ void load_run(const uint8_t *src, uint32_t n, uint32_
     }
 }
 
+// n packed 3-byte elements from src (any byte address), put(e, bits) with the element's 24 bits in the low end of a
+// dword -- bits 24-31 hold whatever followed and ingest_sample ignores them.  store_run3's mirror (kernels/
+// decode_many.inc): the run is the 3n bytes [src, src + 3n), read as single bytes up to the first 16-byte boundary, 16
+// bytes per lane, single bytes.  An element belongs to the part its FIRST byte lies in:
+//   head  elements e with 3e < head (at most 5), a lane each, three byte loads (the last may reach into the body);
+//   body  the lane of the 16 bytes at run byte B takes the elements that start in [B, B + 16): the first at offset
+//         o = (3 - B % 3) % 3, then every 3 bytes -- five of them, and a sixth at offset 15 when o == 0.  The last one
+//         reaches up to 2 bytes past the group: into the next group's first dword (inside the run, as that whole group
+//         is), or, behind the last group, into tail bytes, each loaded only if it lies inside the run.  The five dwords
+//         are shifted down by o bytes once, so that every element is cut from constant positions (no indexed registers);
+//   tail  elements that start at or behind the last group's end (at most 5), a lane each, three byte loads.
+// An element that starts inside the run ends inside it, so no byte outside [src, src + 3n) is ever read.  Indices are
+// 32-bit (3n <= 3 * INGEST_TILE).
+template <class Put>
+__device__ __forceinline__ void load_run3(const uint8_t *src, uint32_t n, uint32_t tid, uint32_t nthreads, Put put) {
+    const uint32_t bytes = 3u * n;
+    const uint32_t head = min(bytes, (16u - (uint32_t)(reinterpret_cast<uintptr_t>(src) & 15u)) & 15u);
+    const uint32_t nv = (bytes - head) / 16u, tail_at = head + nv * 16u;
+    const uint32_t head_n = (head + 2u) / 3u, tail_e = (tail_at + 2u) / 3u;
+    const auto bytewise = [&](uint32_t e) {
+        const uint8_t *p = src + 3u * e;
+        put(e, (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16);
+    };
+    if (tid < head_n) bytewise(tid);
+    const uint32_t *body = reinterpret_cast<const uint32_t *>(src + head);
+#pragma nounroll
+    for (uint32_t v = tid; v < nv; v += nthreads) {
+        const uint4 w = reinterpret_cast<const uint4 *>(body)[v];
+        const uint32_t at = head + v * 16u;
+        uint32_t next = 0;
+        if (v + 1 < nv) {
+            next = body[4u * v + 4u];
+        } else {
+            if (at + 16u < bytes) next = src[at + 16u];
+            if (at + 17u < bytes) next |= (uint32_t)src[at + 17u] << 8;
+        }
+        const uint32_t e = (at + 2u) / 3u, sh = 8u * (3u * e - at);   // the first element that starts in the group
+        const uint32_t s0 = (uint32_t)(((uint64_t)w.y << 32 | w.x) >> sh);
+        const uint32_t s1 = (uint32_t)(((uint64_t)w.z << 32 | w.y) >> sh);
+        const uint32_t s2 = (uint32_t)(((uint64_t)w.w << 32 | w.z) >> sh);
+        const uint32_t s3 = (uint32_t)(((uint64_t)next << 32 | w.w) >> sh);
+        put(e, s0);
+        put(e + 1, s0 >> 24 | s1 << 8);
+        put(e + 2, s1 >> 16 | s2 << 16);
+        put(e + 3, s2 >> 8);
+        put(e + 4, s3);
+        if (sh == 0) put(e + 5, s3 >> 24 | next << 8);
+    }
+    if (tid < n - tail_e) bytewise(tail_e + tid);
+}
+
+// a run of n elements of ES bytes: load_run, or load_run3 for the packed 3-byte elements
+template <uint32_t ES, class Put>
+__device__ __forceinline__ void load_elems(const uint8_t *src, uint32_t n, uint32_t tid, uint32_t nthreads, Put put) {
+    if constexpr (ES == 3) load_run3(src, n, tid, nthreads, put);
+    else load_run<ES>(src, n, tid, nthreads, put);
+}
+
 // n dwords to dst (16-byte aligned: a tile's place in the staging buffer), dword e = get(e): 16 bytes per lane, then
 // single dwords.  Writes [dst, dst + n).
 template <class Get>
@@ -91,7 +150,7 @@ __global__ void __launch_bounds__(WG) k_ingest(const uint8_t *__restrict__ in, c
                                                uint32_t n_streams, uint32_t channels, uint32_t bps,
                                                uint64_t samples_padded, int32_t *__restrict__ staging,
                                                uint32_t *__restrict__ altered) {
-    constexpr uint32_t ES = DT == INGEST_I16 ? 2 : 4;
+    constexpr uint32_t ES = DT == INGEST_I16 ? 2 : DT == INGEST_S24 ? 3 : 4;
     __shared__ __attribute__((aligned(16))) uint32_t lds[INGEST_LDS];
     // the stream of this tile: the last one whose first tile is not behind it (streams without tiles stand in front
     // of the one that owns their tile0, or at the very end)
@@ -115,10 +174,10 @@ __global__ void __launch_bounds__(WG) k_ingest(const uint8_t *__restrict__ in, c
     };
     if (PADDED) {
         for (uint32_t c = 0; c < channels; c++)
-            load_run<ES>(in + (st.in_off + (uint64_t)c * samples_padded + s0) * ES, n, threadIdx.x, WG,
+            load_elems<ES>(in + (st.in_off + (uint64_t)c * samples_padded + s0) * ES, n, threadIdx.x, WG,
                          [&](uint32_t i, uint32_t raw) { lds[c * ld + i] = convert(raw); });
     } else {
-        load_run<ES>(in + (st.in_off + s0 * channels) * ES, n * channels, threadIdx.x, WG,
+        load_elems<ES>(in + (st.in_off + s0 * channels) * ES, n * channels, threadIdx.x, WG,
                      [&](uint32_t e, uint32_t raw) { lds[e] = convert(raw); });
     }
 #pragma unroll

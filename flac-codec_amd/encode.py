@@ -633,24 +633,48 @@ class BatchEncoder:
         self.run(h)
         return self.results(h, copy)
 
-    def prepare_device(self, tensor, lengths, bits_per_sample):
+    def prepare_device(self, tensor, lengths, bits_per_sample, dtype=None, offsets=None, channels=None):
         """The job array of an encode_device call: a [B, C, T] tensor is a PADDED batch of B streams of C channels,
-        stream i of lengths[i] (default T) samples; output buffers sized for the worst case and reused by later calls."""
+        stream i of lengths[i] (default T) samples; with `offsets` the tensor is FLAT, stream i interleaved from element
+        offsets[i].  dtype="int24": uint8 with a trailing axis of 3.  Output buffers sized for the worst case and reused
+        by later calls."""
         L = _stream_lib()
-        if tensor.dim() != 3 or not tensor.is_contiguous() or not tensor.is_cuda:
-            raise ValueError("tensor must be a contiguous [B, C, T] tensor on the GPU")
-        dtype = {"torch.int32": _lib.SAMPLE_I32, "torch.int16": _lib.SAMPLE_I16, "torch.float32": _lib.SAMPLE_F32}.get(
-            str(tensor.dtype))
-        if dtype is None:
-            raise ValueError("tensor must be int16, int32 or float32")
-        n, channels, padded = (int(v) for v in tensor.shape)
-        lengths = [padded] * n if lengths is None else [int(v) for v in lengths]
+        if dtype not in (None, "int24"):
+            raise ValueError("dtype must be None (the tensor's own: int16, int32 or float32) or 'int24'")
+        if not tensor.is_contiguous() or not tensor.is_cuda:
+            raise ValueError("tensor must be a contiguous tensor on the GPU")
+        if dtype == "int24":
+            if str(tensor.dtype) != "torch.uint8" or tensor.dim() < 2 or tensor.shape[-1] != 3:
+                raise ValueError("dtype='int24' takes a uint8 tensor with a trailing axis of 3")
+            code, shape = _lib.SAMPLE_S24, tuple(int(v) for v in tensor.shape[:-1])
+        else:
+            code = {"torch.int32": _lib.SAMPLE_I32, "torch.int16": _lib.SAMPLE_I16,
+                    "torch.float32": _lib.SAMPLE_F32}.get(str(tensor.dtype))
+            if code is None:
+                raise ValueError("tensor must be int16, int32 or float32, or uint8 [..., 3] with dtype='int24'")
+            shape = tuple(int(v) for v in tensor.shape)
+        if offsets is None:
+            if len(shape) != 3:
+                raise ValueError("a padded batch is [B, C, T] ([B, C, T, 3] for dtype='int24')")
+            n, channels, padded = shape
+            lengths = [padded] * n if lengths is None else [int(v) for v in lengths]
+            offsets = [0] * n
+            fmt = _lib.OutFormat(code, _lib.LAYOUT_PADDED, channels, 0, padded)
+        else:
+            if len(shape) != 1 or lengths is None or not channels:
+                raise ValueError("a flat batch is [elements] ([elements, 3] for dtype='int24') with offsets, lengths "
+                                 "and channels")
+            offsets, lengths, channels = [int(v) for v in offsets], [int(v) for v in lengths], int(channels)
+            n = len(offsets)
+            if any(o < 0 or o + s * channels > shape[0] for o, s in zip(offsets, lengths)):
+                raise ValueError("a stream reaches past the tensor")
+            fmt = _lib.OutFormat(code, _lib.LAYOUT_FLAT, 0, 0, 0)
         if len(lengths) != n:
             raise ValueError("one length per stream")
-        fmt = _lib.OutFormat(dtype, _lib.LAYOUT_PADDED, channels, 0, padded)
         jobs = (_lib.DeviceJob * max(n, 1))()
         co = self._opts._c_options()
         for i, samples in enumerate(lengths):
+            jobs[i].in_offset = offsets[i]
             cap = int(L.flacenc_worst_case_bytes(C.byref(co), bits_per_sample, max(channels, 1), samples))
             if i >= len(self._bufs):
                 self._bufs.append(np.empty(cap, dtype=np.uint8))
@@ -676,15 +700,19 @@ class BatchEncoder:
                                             sample_rate, bits_per_sample, channels, jobs, n,
                                             0 if verify_md5 else _lib.DEVICE_NO_MD5, stream or None)
 
-    def encode_device(self, tensor, lengths=None, sample_rate=44100, bits_per_sample=16, verify_md5=True, copy=True):
+    def encode_device(self, tensor, lengths=None, sample_rate=44100, bits_per_sample=16, verify_md5=True, copy=True,
+                      dtype=None, offsets=None, channels=None):
         """A batch of streams held on the GPU -> .flac bytes, the samples never visiting the host
         (flacenc_encode_many_device).  tensor: contiguous [B, C, T] torch tensor on the GPU, int16 (x >> (16 - bps)),
-        int32 (clamped to bps bits) or float32 (x * 2^(bps - 1), rounded to nearest even, clamped; NaN -> 0); lengths:
-        samples of every stream (default T; what lies behind is never read).  Runs behind the work queued on the tensor's
-        current torch stream and returns when the files are complete.  verify_md5=False leaves STREAMINFO's MD5 zero
+        int32 (clamped to bps bits) or float32 (x * 2^(bps - 1), rounded to nearest even, clamped; NaN -> 0); with
+        dtype="int24" a uint8 tensor [B, C, T, 3] of packed little-endian 24-bit elements (sign-extended, then
+        x >> (24 - bps); bps <= 24).  lengths: samples of every stream (default T; what lies behind is never read).
+        offsets (with lengths and channels): the tensor is flat instead -- [elements], or [elements, 3] for "int24" --
+        and stream i is [lengths[i]][channels] interleaved from element offsets[i]; what lies between is never read.
+        Runs behind the work queued on the tensor's current torch stream and returns when the files are complete.  verify_md5=False leaves STREAMINFO's MD5 zero
         ("unknown") and skips the hash kernel.  self.last_altered: per stream, the elements that were clamped, NaN or
-        (int16) lost non-zero low bits; self.last_md5: the digests."""
-        h = self.prepare_device(tensor, lengths, bits_per_sample)
+        (int16, int24) lost non-zero low bits; self.last_md5: the digests."""
+        h = self.prepare_device(tensor, lengths, bits_per_sample, dtype, offsets, channels)
         rc = self.run_device(h, tensor, sample_rate, bits_per_sample, verify_md5)
         jobs, n = h[0], h[1]
         self.last_altered = [int(jobs[i].altered) for i in range(n)]

@@ -526,7 +526,13 @@ def window_array(windows):
     return (_lib.Window * len(rows))(*[_lib.Window(s, 0, a, n) for s, a, n in rows])
 
 
-_DTYPES = {"int32": _lib.SAMPLE_I32, "int16": _lib.SAMPLE_I16, "float32": _lib.SAMPLE_F32}
+_DTYPES = {"int32": _lib.SAMPLE_I32, "int16": _lib.SAMPLE_I16, "float32": _lib.SAMPLE_F32, "int24": _lib.SAMPLE_S24}
+
+
+def _element_array(dtype, shape):
+    """(array dtype name, shape) of an output of `shape` elements: "int24" has no array dtype, its elements are a
+    trailing axis of 3 uint8 (little-endian)."""
+    return ("uint8", tuple(shape) + (3,)) if dtype == "int24" else (dtype, tuple(shape))
 
 
 def _decode_many_as(dec, recs, n, out, flags, dtype, layout, pad_to, pad_channels):
@@ -541,15 +547,16 @@ def _decode_many_as(dec, recs, n, out, flags, dtype, layout, pad_to, pad_channel
     else:
         shape = (sum(r.info.decoded_samples * r.info.channels for r in ok),)
     need = Decoder.plan_output(fmt, recs, n)   # refuses before anything is allocated
+    array_dtype, shape = _element_array(dtype, shape)
     if out == "device":
         import torch
 
         dev = dec.device if dec.device >= 0 else torch.cuda.current_device()
-        buf = torch.empty(shape, dtype=getattr(torch, dtype), device=f"cuda:{dev}")
+        buf = torch.empty(shape, dtype=getattr(torch, array_dtype), device=f"cuda:{dev}")
         torch.cuda.synchronize(dev)
         dec.decode_as(buf.data_ptr() if need else None, need, fmt, flags | _lib.DECODE_OUT_DEVICE, recs)
     else:
-        buf = np.empty(shape, dtype=dtype)
+        buf = np.empty(shape, dtype=array_dtype)
         dec.decode_as(buf.ctypes.data if need else None, need, fmt, flags, recs)
     streams = []
     for i in range(n):
@@ -561,7 +568,7 @@ def _decode_many_as(dec, recs, n, out, flags, dtype, layout, pad_to, pad_channel
             pcm = buf[i, :info.channels, :info.decoded_samples]
         elif r.rc == 0:
             ch = max(info.channels, 1)
-            pcm = buf[r.out_offset:r.out_offset + info.decoded_samples * ch].reshape(-1, ch)
+            pcm = buf[r.out_offset:r.out_offset + info.decoded_samples * ch].reshape((-1, ch) + tuple(shape[1:]))
         streams.append(DecodedStream(r.rc, info, r.out_offset, pcm))
     return buf, streams
 
@@ -575,15 +582,17 @@ def decode_many(blobs, device=-1, out="device", verify_md5=True, decoder=None, d
     equals what flacgpu_decode_stream gives for that stream alone (a stream without frames is hashed as the empty
     input: md5_status 1 / 2 instead of 0).  verify_md5=False skips the MD5 (md5_status 3).
 
-    dtype "int16" (sample << (16 - bps); every stream must have bps <= 16) or "float32" (sample * 2^-(bps - 1))
-    converts in the same kernel pass (flacgpu_decoder_decode_as).  layout="padded" returns (batch, streams): `batch` is
-    [B, C, T], planar and zero-padded, with T = pad_to or the longest stream and C = pad_channels or the most channels;
+    dtype "int16" (sample << (16 - bps); every stream must have bps <= 16), "int24" (sample << (24 - bps) as 3
+    little-endian bytes, bps <= 24: uint8 with a trailing axis of 3 -- flat [total_elements, 3] with pcm views
+    [samples, channels, 3], padded [B, C, T, 3] -- which is a WAV data chunk as it stands) or "float32"
+    (sample * 2^-(bps - 1)) converts in the same kernel pass (flacgpu_decoder_decode_as).  layout="padded" returns
+    (batch, streams): `batch` is [B, C, T], planar and zero-padded, with T = pad_to or the longest stream and C = pad_channels or the most channels;
     streams[i].pcm is the view batch[i, :channels, :decoded_samples], and the lengths vector a padded batch goes with
     is [s.info.decoded_samples for s in streams].  A stream with rc != 0 is a row of zeros."""
     if out not in ("device", "host"):
         raise ValueError("out must be 'device' or 'host'")
     if dtype not in _DTYPES or layout not in ("flat", "padded"):
-        raise ValueError("dtype must be 'int32', 'int16' or 'float32' and layout 'flat' or 'padded'")
+        raise ValueError("dtype must be 'int32', 'int16', 'int24' or 'float32' and layout 'flat' or 'padded'")
     if layout == "flat" and (pad_to is not None or pad_channels is not None):
         raise ValueError("pad_to and pad_channels go with layout='padded'")
     if out == "device":
@@ -631,11 +640,12 @@ def decode_windows(decoder, recs, windows, dtype="float32", out="device", pad_to
     `batch` is [N, C, T], planar and zero-padded -- a torch tensor on the GPU for out="device", a numpy array for
     out="host" -- with T = pad_to or the longest window and C = pad_channels or the most channels of a named stream;
     results[i] is the _lib.WindowResult of window i (rc, frames, bad_frames, bad_crc16, samples: the valid samples of
-    batch[i], fewer than the window's length where it reaches past the stream's end).  dtype as for decode_many."""
+    batch[i], fewer than the window's length where it reaches past the stream's end).  dtype as for decode_many
+    ("int24": uint8 [N, C, T, 3])."""
     if out not in ("device", "host"):
         raise ValueError("out must be 'device' or 'host'")
     if dtype not in _DTYPES:
-        raise ValueError("dtype must be 'int32', 'int16' or 'float32'")
+        raise ValueError("dtype must be 'int32', 'int16', 'int24' or 'float32'")
     wins = window_array(windows)
     n = len(recs)
     named = [recs[w.stream] for w in wins if w.stream < n and recs[w.stream].rc == 0]
@@ -644,15 +654,16 @@ def decode_windows(decoder, recs, windows, dtype="float32", out="device", pad_to
     fmt.channels_padded = pad_channels or max([r.info.channels for r in named], default=0)
     shape = (len(wins), fmt.channels_padded, fmt.samples_padded)
     need = Decoder.plan_windows(fmt, recs, n, wins)   # refuses before anything is allocated
+    array_dtype, shape = _element_array(dtype, shape)
     if out == "device":
         import torch
 
         dev = decoder.device if decoder.device >= 0 else torch.cuda.current_device()
-        buf = torch.empty(shape, dtype=getattr(torch, dtype), device=f"cuda:{dev}")
+        buf = torch.empty(shape, dtype=getattr(torch, array_dtype), device=f"cuda:{dev}")
         torch.cuda.synchronize(dev)
         results = decoder.decode_windows(buf.data_ptr() if need else None, need, fmt, _lib.DECODE_OUT_DEVICE, wins)
     else:
-        buf = np.empty(shape, dtype=dtype)
+        buf = np.empty(shape, dtype=array_dtype)
         results = decoder.decode_windows(buf.ctypes.data if need else None, need, fmt, 0, wins)
     return buf, list(results)[:len(wins)]
 

@@ -550,6 +550,9 @@ int flacgpu_decoder_decode(flacgpu_decoder *d, int32_t *out, size_t out_cap_samp
  *   I32  the sample.
  *   I16  sample << (16 - bps).  Needs bps <= 16 in every stream with rc == 0; else the whole call returns
  *        FLACGPU_ERR_UNSUPPORTED, flacgpu_last_error names the first such stream, and nothing is written.
+ *   S24  (sample << (24 - bps)) & 0xFFFFFF as 3 bytes, little-endian, two's complement, no padding between elements:
+ *        element e starts at byte 3 * e (WAV's left-justified 24-bit container).  Needs bps <= 24 in every stream with
+ *        rc == 0; refused like I16 otherwise.  `out` needs no alignment.
  *   F32  (float)sample (round to nearest even) * 2^-(bps - 1): exact for bps <= 25, correctly rounded above.
  *   FLAT    streams back to back, each [samples][channels]; stream i starts at element out_offset (of the scan).
  *   PADDED  [n_streams][channels_padded][samples_padded], planar: stream i starts at element
@@ -570,6 +573,7 @@ int flacgpu_decoder_decode(flacgpu_decoder *d, int32_t *out, size_t out_cap_samp
 #define FLACGPU_SAMPLE_I32 0u
 #define FLACGPU_SAMPLE_I16 1u
 #define FLACGPU_SAMPLE_F32 2u
+#define FLACGPU_SAMPLE_S24 24u    /* packed 3-byte little-endian elements (the value is 24, not 3) */
 #define FLACGPU_LAYOUT_FLAT   0u  /* streams back to back, each [samples][channels]: flacgpu_decoder_decode's layout */
 #define FLACGPU_LAYOUT_PADDED 1u  /* [n_streams][channels_padded][samples_padded], planar, zero-filled */
 typedef struct {
@@ -599,8 +603,8 @@ int flacgpu_decoder_decode_as(flacgpu_decoder *d, void *out, size_t out_cap_byte
  * selected frames, not by the batch.
  * A refused call writes nothing: no scanned batch, stream >= n_streams, reserved != 0, start + length overflowing, a
  * layout other than PADDED or padding too small (FLACGPU_ERR_INVALID_ARG), out_cap_bytes < out_bytes
- * (FLACGPU_ERR_BUFFER_TOO_SMALL), I16 with a named rc == 0 stream of more than 16 bits (FLACGPU_ERR_UNSUPPORTED,
- * flacgpu_last_error names the stream of the first such window).  A stream that no window names takes no part in these
+ * (FLACGPU_ERR_BUFFER_TOO_SMALL), I16 with a named rc == 0 stream of more than 16 bits or S24 with one of more than 24
+ * (FLACGPU_ERR_UNSUPPORTED, flacgpu_last_error names the stream of the first such window).  A stream that no window names takes no part in these
  * checks.  n_windows == 0 is valid and writes nothing.  decode, decode_as and decode_windows may follow one another in
  * any order on one scan.
  * plan_windows is a pure host function (no device, no handle): the checks above on scanned records, and the bytes `out`
@@ -630,11 +634,12 @@ int flacgpu_window_frames(const uint32_t *frame_n, uint32_t n_frames, uint64_t s
 
 /* ---- the encoder's ingest pass: a device tensor -> interleaved int32 the encoder reads in place ----------------------
  * The device half of flacenc_encode_many_device (include/flacenc_stream.h), the mirror image of
- * flacgpu_decoder_decode_as: a batch of streams of one shape held in device memory as int32, int16 or float32, planar and
+ * flacgpu_decoder_decode_as: a batch of streams of one shape held in device memory as int32, int16, packed 24-bit or float32, planar and
  * padded or interleaved and flat (flacgpu_out_format describes the INPUT here), is converted and written as interleaved
  * int32 into a staging buffer the handle owns -- stream i at int32 element staging_offset (a multiple of 4: a 16-byte
  * boundary, from which flacgpu_encode_segments_device reads segments in place).  Conversion (csrc/kernels/ingest_rule.h,
- * the inverse of decode_as's): I32 clamped to bps bits; I16 x >> (16 - bps), bps <= 16; F32 x * 2^(bps - 1) rounded to
+ * the inverse of decode_as's): I32 clamped to bps bits; I16 x >> (16 - bps), bps <= 16; S24 (3-byte little-endian elements,
+ * element e at byte 3 * e, d_pcm at any byte) sign_extend24(x) >> (24 - bps), bps <= 24; F32 x * 2^(bps - 1) rounded to
  * nearest even and clamped, NaN -> 0.  Padding (rows c >= channels, elements t >= samples, gaps between flat streams) is
  * never read.  This version always ingests; reading an aligned FLAT I32 batch in place is a follow-up.
  *   submit  runs the pass on a stream of the handle's, ordered after `stream` (a hipStream_t; NULL: the legacy default
@@ -642,7 +647,7 @@ int flacgpu_window_frames(const uint32_t *frame_n, uint32_t n_frames, uint64_t s
  *           submit) may be read from any stream.  With FLACGPU_INGEST_MD5 the MD5 of every stream's samples as
  *           ceil(bps / 8)-byte little-endian values (k_md5_many, one lane per stream: about 15 MB/s per stream, fine for
  *           many clips and poor for one long stream) is queued behind it and runs beside whatever the caller does next.
- *   finish  waits for it; altered[i] (may be NULL) = elements of stream i that were clamped, NaN or (I16) lost non-zero
+ *   finish  waits for it; altered[i] (may be NULL) = elements of stream i that were clamped, NaN or (I16, S24) lost non-zero
  *           low bits; md5 (may be NULL; [n_streams][16]) is written only when the MD5 was asked for.
  * The arguments are the ones flacenc_device_batch_plan validates; submit repeats the checks its kernel's bounds rest on. */
 #define FLACGPU_INGEST_MD5 1u

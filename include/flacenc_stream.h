@@ -204,8 +204,9 @@ int flacenc_encode_many_devices(const flacenc_options *opts, flacenc_job *jobs, 
                                 const int *devices, uint32_t n_devices);
 
 /* ---- a batch of streams RESIDENT IN DEVICE MEMORY -> finished .flac files, without a host copy of the samples --------
- * The mirror image of flacgpu_decoder_decode_as (include/flacenc_gpu.h): `d_pcm` is a device tensor of int32, int16 or
- * float32 elements holding n_jobs streams of one shape (sample rate, bits per sample, channels), laid out as `fmt` says
+ * The mirror image of flacgpu_decoder_decode_as (include/flacenc_gpu.h): `d_pcm` is a device tensor of int32, int16,
+ * packed 24-bit (FLACGPU_SAMPLE_S24: 3 bytes per element, little-endian, element e at byte 3 * e, no alignment) or float32
+ * elements holding n_jobs streams of one shape (sample rate, bits per sample, channels), laid out as `fmt` says
  * (FLACGPU_SAMPLE_* / FLACGPU_LAYOUT_* as in the decoder; the format describes the INPUT here):
  *   PADDED  [n_jobs][channels_padded][samples_padded], planar; of stream i only the first `channels` rows and the first
  *           jobs[i].samples elements of each are read -- padding may hold anything;
@@ -213,8 +214,8 @@ int flacenc_encode_many_devices(const flacenc_options *opts, flacenc_job *jobs, 
  *           what lies between them is never read.
  * Conversion to bits_per_sample-bit samples (csrc/kernels/ingest_rule.h, the exact inverse of decode_as's; testable on
  * the host through flacenc_ingest_sample): I32 the value clamped to [-2^(bps-1), 2^(bps-1) - 1]; I16 x >> (16 - bps),
- * bps <= 16 only; F32 x * 2^(bps-1) rounded to nearest even, clamped, NaN -> 0.  jobs[i].altered counts the elements of
- * stream i that were clamped, were NaN or (I16) had non-zero bits below the ones kept.
+ * bps <= 16 only; S24 sign_extend24(x) >> (24 - bps), bps <= 24 only; F32 x * 2^(bps-1) rounded to nearest even, clamped, NaN -> 0.  jobs[i].altered counts the elements of
+ * stream i that were clamped, were NaN or (I16, S24) had non-zero bits below the ones kept.
  * What happens: one ingest pass writes interleaved int32 into a staging buffer of the library's (staging_bytes = 4 x the
  * sum over the streams of samples x channels rounded up to 4; this version always ingests -- reading an aligned FLAT I32
  * batch in place is a follow-up); the MD5 of every stream is taken on the device (k_md5_many: one lane per stream, about
@@ -232,7 +233,7 @@ int flacenc_encode_many_devices(const flacenc_options *opts, flacenc_job *jobs, 
  * plan is pure host code (no device): it validates the call -- FLACENC_ERR_INVALID_ARG for channels_padded < channels, a
  * stream longer than samples_padded, FLAT streams that overlap, channels outside 1..8, bits_per_sample outside 1..32, an
  * unknown type or layout, reserved != 0, padded fields under FLAT; FLACENC_ERR_UNSUPPORTED for I16 with more than 16
- * bits -- and returns the elements d_pcm must hold and the staging bytes.  encode runs the same checks first: a refused
+ * bits or S24 with more than 24 -- and returns the elements d_pcm must hold (S24: 3-byte elements) and the staging bytes.  encode runs the same checks first: a refused
  * call launches nothing and writes nothing (no job field, no output byte).  Returns 0 or the first failing job's status. */
 typedef flacgpu_out_format flacenc_tensor_format;   /* the decoder's format record under a direction-neutral name */
 typedef struct {
@@ -251,9 +252,10 @@ int flacenc_device_batch_plan(const flacenc_options *opts, const flacenc_tensor_
 int flacenc_encode_many_device(const flacenc_options *opts, const void *d_pcm, const flacenc_tensor_format *fmt,
                                uint32_t sample_rate, uint32_t bits_per_sample, uint32_t channels, flacenc_device_job *jobs,
                                size_t n_jobs, uint32_t flags, void *stream);
-/* The conversion rule on the host, one element: raw_bits holds the element's bits (I16: in the low half).  *altered
+/* The conversion rule on the host, one element: raw_bits holds the element's bits (I16: in the low half; S24: in the low 24 bits, bits
+ * 24-31 are ignored).  *altered
  * (may be NULL) = 1 when the element was changed beyond rounding.  A combination plan refuses (unknown type, bps outside
- * 1..32, I16 with bps > 16) gives 0 and *altered = 1. */
+ * 1..32, I16 with bps > 16, S24 with bps > 24) gives 0 and *altered = 1. */
 int32_t flacenc_ingest_sample(uint32_t sample_type, uint32_t raw_bits, uint32_t bits_per_sample, int *altered);
 
 /* FlacStreamWriter (encode.rs:1050-1290): header-less subset frames, parameters per call. */

@@ -8,6 +8,7 @@ over flacgpu_decode_stream and the oracle's CPU decoder on one core; writes prof
     python tools/decode_many_probe.py --formats --label parent --package-root DIR   (DIR: a built checkout of the
                                              parent commit; the default int32 path only, into the same file)
     python tools/decode_many_probe.py --formats --kernels-only   (one warm call per leg, for rocprofv3)
+    python tools/decode_many_probe.py --formats --s24 [--out profiles/r12_s24.json] [--reps 15] [--shrink 4]
     python tools/decode_many_probe.py --windows [--workloads tracks,clips] [--out profiles/r10_decode_windows.json]
                                              [--reps 15] [--kernels-only]
 
@@ -16,6 +17,11 @@ scan + decode call into (a) what a caller of flacgpu_decoder_decode does -- inte
 same [B, 1, T] float32 (or int16) padded tensor -- and (b) decode_many(dtype=, layout="padded") in one call; and the
 default int32 path itself, whose figure the parent's build repeats on the same box (the regression guard: the margin is
 the spread over --reps that this probe sees).
+
+--formats --s24 (FLACGPU_SAMPLE_S24, dtype="int24"): on 1024 clips of 10 s, 48 kHz stereo 24-bit (divided by
+--shrink), no MD5, handle warm.  Host output: (a) decode_many(dtype="int32", out="host") and the numpy pack to 3 bytes
+that a WAV writer then needs, against (b) one decode_many(dtype="int24", out="host"); both must give the same bytes.
+Device output: the int32 call against the int24 call, with the bytes each holds.
 
 --windows (flacgpu_decoder_decode_windows): on a resident scan (scanned once, outside the timed part), device output,
 no MD5, handle warm, the wall time of one round of random crops -- one crop of 5 s (tracks) or 1 s (clips) per stream
@@ -49,6 +55,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 WORKLOADS = {   # name: (streams, distinct, seconds, rate, channels, bps)
     "clips": (1024, 16, 10, 16000, 1, 16),
+    "clips24": (1024, 16, 10, 48000, 2, 24),
     "tracks": (256, 4, 180, 44100, 2, 16),
     "hour": (1, 1, 3600, 48000, 2, 24),
 }
@@ -200,7 +207,7 @@ def formats(args):
         return decode_many(blobs, out="device", verify_md5=False, decoder=dec)[0]
 
     legs = {"int32_flat_default": default}
-    if new_abi and args.label == "this":
+    if new_abi and args.label != "parent":
         for dt in ("float32", "int16"):
             legs[f"a_int32_then_torch_{dt}"] = (lambda dt=dt: legacy(dt))
             legs[f"a_equal_lengths_reshape_{dt}"] = (lambda dt=dt: legacy_equal_lengths(dt))
@@ -218,7 +225,7 @@ def formats(args):
         with open(args.out) as f:
             res = json.load(f)
     rec = {"build_id": _lib.build_id(), "sclk_mhz_before": _sclk_mhz(), "legs": {}}
-    if new_abi and args.label == "this":   # (a) and (b) give the same tensor
+    if new_abi and args.label != "parent":   # (a) and (b) give the same tensor
         for dt in ("float32", "int16"):
             assert torch.equal(legacy(dt), fused(dt)) and torch.equal(legacy_equal_lengths(dt), fused(dt))
     for name, fn in legs.items():
@@ -238,6 +245,69 @@ def formats(args):
     with open(args.out, "w") as f:
         json.dump(res, f, indent=1)
     print(json.dumps({args.label: rec}, indent=1), flush=True)
+
+
+def s24(args):
+    """The --formats --s24 leg (see the module docstring)."""
+    import torch
+
+    from flac_codec_amd import _lib
+    from flac_codec_amd.gpu import Decoder, decode_many
+
+    blobs = make_blobs("clips24")
+    blobs = blobs[:max(1, len(blobs) // args.shrink)]
+    dec = Decoder(0)
+
+    def a_host():   # the int32 download, then the pack on the CPU
+        flat, _ = decode_many(blobs, out="host", verify_md5=False, decoder=dec)
+        return np.ascontiguousarray(flat.view(np.uint8).reshape(-1, 4)[:, :3])
+
+    def a_host_call_only():
+        return decode_many(blobs, out="host", verify_md5=False, decoder=dec)[0]
+
+    def b_host():
+        return decode_many(blobs, out="host", verify_md5=False, decoder=dec, dtype="int24")[0]
+
+    def dev(dtype):
+        return decode_many(blobs, out="device", verify_md5=False, decoder=dec, dtype=dtype)[0]
+
+    legs = {"host_a_int32_then_numpy_pack": a_host, "host_a_int32_call_alone": a_host_call_only,
+            "host_b_int24": b_host, "device_int32": lambda: dev("int32"), "device_int24": lambda: dev("int24")}
+    if args.kernels_only:
+        for fn in legs.values():
+            fn()
+            fn()
+        torch.cuda.synchronize()
+        dec.close()
+        return
+    assert np.array_equal(a_host(), b_host())
+    assert np.array_equal(dev("int24").cpu().numpy(), b_host())
+    n = len(blobs)
+    rec = {"tool": "tools/decode_many_probe.py --formats --s24", "build_id": _lib.build_id(),
+           "workload": f"{n} clips x 10 s, 48 kHz stereo 24-bit", "md5": False, "legs": {}}
+    for name, fn in legs.items():
+        fn()
+        torch.cuda.synchronize()   # warm: buffers grown, code loaded
+        sclk_before = _sclk_mhz()
+        times = []
+        for _ in range(args.reps):
+            t0 = time.perf_counter()
+            out = fn()
+            torch.cuda.synchronize()
+            times.append(time.perf_counter() - t0)
+        rec["legs"][name] = dict(_spread(times), sclk_mhz_before=sclk_before, sclk_mhz_after=_sclk_mhz(),
+                                 output_bytes=int(out.nbytes if isinstance(out, np.ndarray) else
+                                                  out.numel() * out.element_size()))
+        del out
+    dec.close()
+    res = {}
+    if os.path.exists(args.out):
+        with open(args.out) as f:
+            res = json.load(f)
+    res["decoder"] = rec
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(rec, indent=1), flush=True)
 
 
 def windows(args):
@@ -376,7 +446,10 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--formats", action="store_true", help="the output-format leg: profiles/r09_decode_formats.json")
     ap.add_argument("--windows", action="store_true", help="the random-crop leg: profiles/r10_decode_windows.json")
-    ap.add_argument("--label", default="this", help="--formats: the run's name in the file (this | parent)")
+    ap.add_argument("--s24", action="store_true", help="with --formats: the packed 24-bit leg, profiles/r12_s24.json")
+    ap.add_argument("--shrink", type=int, default=1, help="--s24: divide the clip count")
+    ap.add_argument("--label", default="this", help="--formats: the run's name in the file (parent: the default int32 "
+                    "leg only; any other name: every leg)")
     ap.add_argument("--package-root", help="--formats: measure the flac_codec_amd of this checkout, not of this one")
     ap.add_argument("--oracle-seconds", type=float, default=20.0)
     ap.add_argument("--merge-stats")
@@ -385,6 +458,7 @@ def main():
     args = ap.parse_args()
     if not args.out:
         args.out = os.path.join(ROOT, "profiles", "r10_decode_windows.json" if args.windows else
+                                "r12_s24.json" if args.s24 else
                                 "r09_decode_formats.json" if args.formats else "r07_decode_many.json")
     if args.windows and args.workloads == "clips,tracks,hour":
         args.workloads = "tracks,clips"
@@ -395,6 +469,8 @@ def main():
     import torch
 
     torch.cuda.init()   # before the library's first HIP call (else torch sees no GPU)
+    if args.formats and args.s24:
+        return s24(args)
     if args.formats:
         return formats(args)
     if args.windows:

@@ -7,7 +7,11 @@ Workloads (the r07 shapes): 1024 clips of 10 s, 16 kHz mono 16-bit; 256 tracks o
 Handle warm, median and min-max of --repeats (15) runs, sclk read before and after; both legs must give identical
 files.  Writes profiles/r11_encode_device.json.  --kernels: one encode_device call per workload and nothing else, for a
 `rocprofv3 --kernel-trace --stats -- python tools/encode_device_probe.py --kernels` run of its own (the per-kernel split:
-k_ingest, k_md5_many and the one-frame tail calls)."""
+k_ingest, k_md5_many and the one-frame tail calls).
+
+--int24: the packed 24-bit leg instead, on 1024 clips of 10 s, 48 kHz stereo 24-bit held as [B, C, T, 3] uint8 (divided
+by --shrink): (a) the caller widens the bytes to int32 in torch and calls encode_device on that, (b)
+encode_device(dtype="int24"); identical files asserted.  Merged into profiles/r12_s24.json under "encoder"."""
 import argparse
 import json
 import os
@@ -53,6 +57,50 @@ def leg_a(enc, t):
     return enc.encode(streams, enc_rate, 16, x.shape[1])
 
 
+def int24_leg(a):
+    import torch
+    from _pcm import synth_fast
+    from flac_codec_amd import _lib
+    from flac_codec_amd.encode import BatchEncoder, Options
+
+    n, T, ch, rate = max(1, 1024 // a.shrink), 480000, 2, 48000
+    base = synth_fast(12, ch, 24, T + 4096).reshape(-1, ch).T   # [ch, T + 4096] int32 of 24 bits
+    host = np.stack([base[:, (37 * i) % 4096:(37 * i) % 4096 + T] for i in range(n)])
+    packed = np.ascontiguousarray(np.ascontiguousarray(host, dtype="<i4").view(np.uint8).reshape(n, ch, T, 4)[..., :3])
+    t = torch.from_numpy(packed).cuda()
+    del host, packed
+    enc = BatchEncoder(Options.default())
+
+    def widen_then_encode(copy=False):
+        x = t.to(torch.int32)
+        x = (x[..., 0] | x[..., 1] << 8 | x[..., 2] << 16) << 8 >> 8   # sign-extended
+        return enc.encode_device(x.contiguous(), None, sample_rate=rate, bits_per_sample=24, copy=copy)
+
+    def direct(copy=False):
+        return enc.encode_device(t, None, sample_rate=rate, bits_per_sample=24, copy=copy, dtype="int24")
+
+    if a.kernels:
+        direct()
+        return
+    assert widen_then_encode(True) == direct(True), "the two legs differ"
+    r = {"tool": "tools/encode_device_probe.py --int24", "build_id": _lib.build_id(),
+         "workload": f"{n} clips x 10 s, 48 kHz stereo 24-bit", "samples": n * ch * T, "tensor_bytes_int24": t.numel(),
+         "tensor_bytes_int32": 4 * n * ch * T}
+    for k, fn in (("a_torch_widen_then_encode_device_int32", widen_then_encode), ("b_encode_device_int24", direct)):
+        before = sclk()   # around every leg: a clock change between the legs shows
+        r[k] = dict(timed(fn, a.repeats), sclk_before=before, sclk_after=sclk())
+    for k in ("a_torch_widen_then_encode_device_int32", "b_encode_device_int24"):
+        r[k]["gsamples_per_s"] = r["samples"] / r[k]["median_ms"] / 1e6
+    res = {}
+    if os.path.exists(a.out):
+        with open(a.out) as f:
+            res = json.load(f)
+    res["encoder"] = r
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(r, indent=1))
+
+
 def timed(fn, repeats):
     import torch
 
@@ -73,11 +121,15 @@ def main():
     ap.add_argument("--shrink", type=int, default=1, help="divide the stream counts (a quick look)")
     ap.add_argument("--only", default=None, help="one workload's name")
     ap.add_argument("--kernels", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r11_encode_device.json"))
+    ap.add_argument("--int24", action="store_true", help="the packed 24-bit leg: profiles/r12_s24.json")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "r12_s24.json" if a.int24 else "r11_encode_device.json")
     import torch
 
     torch.cuda.init()
+    if a.int24:
+        return int24_leg(a)
     from flac_codec_amd import _lib
     from flac_codec_amd.encode import BatchEncoder, Options
 
