@@ -124,6 +124,20 @@ class WindowResult(C.Structure):
                 ("samples", C.c_uint64)]
 
 
+class FrameRecord(C.Structure):
+    """flacgpu_frame_record: one kept frame of a raw frame stream (64 bytes)."""
+    _fields_ = [("byte_offset", C.c_uint64), ("number", C.c_uint64), ("out_offset", C.c_uint64),
+                ("stream", C.c_uint32), ("bytes", C.c_uint32), ("block_size", C.c_uint32), ("sample_rate", C.c_uint32),
+                ("channels", C.c_uint32), ("bits_per_sample", C.c_uint32), ("assignment", C.c_uint32),
+                ("blocking", C.c_uint32), ("status", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class RawStream(C.Structure):
+    """flacgpu_raw_stream: one input's summary of a raw frame scan (32 bytes)."""
+    _fields_ = [("first_frame", C.c_uint64), ("skipped_bytes", C.c_uint64), ("frames", C.c_uint32),
+                ("gaps", C.c_uint32), ("uniform", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class ShardCounters(C.Structure):
     """flacgpu_shard_counters: the four integers that cross shards of a stream (include/flacenc_gpu.h)."""
     _fields_ = [("frames", C.c_uint64), ("bytes", C.c_uint64), ("min_frame", C.c_uint64), ("max_frame", C.c_uint64)]
@@ -227,6 +241,13 @@ def _load():
                                                  C.POINTER(Window), C.c_uint32, C.POINTER(WindowResult)]
     L.flacgpu_window_frames.argtypes = [C.POINTER(C.c_uint32), C.c_uint32, C.c_uint64, C.c_uint64,
                                         C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+    L.flacgpu_scan_frames_host.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(FrameRecord), C.c_size_t,
+                                           C.POINTER(C.c_uint32), C.POINTER(RawStream)]
+    L.flacgpu_decoder_scan_frames.argtypes = [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_uint32,
+                                              C.POINTER(DecodedStream), C.POINTER(RawStream), C.POINTER(C.c_uint64),
+                                              C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.flacgpu_decoder_frame_records.argtypes = [vp, C.POINTER(FrameRecord), C.c_size_t]
+    L.flacgpu_decoder_decode_frames.argtypes = [vp, vp, C.c_size_t, C.c_uint32, C.POINTER(FrameRecord), C.c_size_t]
     L.flacgpu_pack_plans.argtypes = [vp, ip, C.c_uint32, C.c_uint32, C.POINTER(FramePlan), C.POINTER(SubframePlan),
                                      C.c_uint64, C.c_uint32]
     L.flacgpu_host_alloc.argtypes = [C.c_size_t]

@@ -78,6 +78,24 @@ int flacgpu_scan_stream_host(const uint8_t *data, size_t len, flacgpu_stream_inf
     return FLACGPU_OK;
 }
 
+// The raw-frame rule (host/flac_stream.cpp scan_raw_frames) for one input, without a device.
+int flacgpu_scan_frames_host(const uint8_t *data, size_t len, flacgpu_frame_record *frames, size_t cap,
+                             uint32_t *n_frames, flacgpu_raw_stream *summary) {
+    if ((!data && len) || !n_frames || !summary) return FLACGPU_ERR_INVALID_ARG;
+    *n_frames = 0;
+    std::vector<flacgpu_frame_record> found;
+    flacgpu_raw_stream sum{};
+    flacenc::scan_raw_frames(data, len, found, sum);
+    *n_frames = sum.frames;
+    if (frames && cap < found.size()) {
+        g_last_error = "output buffer too small";
+        return FLACGPU_ERR_BUFFER_TOO_SMALL;
+    }
+    if (frames) std::copy(found.begin(), found.end(), frames);
+    *summary = sum;
+    return FLACGPU_OK;
+}
+
 // Decodes a whole FLAC stream held in host memory: the host finds the frame boundaries (scan_stream), the GPU decodes the
 // frames in parallel, one lane per frame, re-checks every CRC-16 and undoes the stereo decorrelation; the host compares
 // the MD5 of the decoded PCM with STREAMINFO's (decode.rs:1282 `verify`, 1388-1436 read_frame, 1494-1856).

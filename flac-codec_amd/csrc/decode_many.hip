@@ -64,9 +64,114 @@ struct flacgpu_decoder {
     // frame's first sample per channel in its stream
     std::vector<uint32_t> slot_frame0;
     std::vector<uint64_t> frame_first;
+    // a raw scan (flacgpu_decoder_scan_frames): every kept frame's record, the streams' summaries, and decode_frames' own
+    // frame table -- every kept frame with `out` = the record's out_offset and `slot` = the frame's index, so that the
+    // frame kernels' per-slot counts come out per frame.  frame_tab holds the frames of the uniform streams alone.
+    bool raw = false;
+    std::vector<flacgpu_frame_record> records;
+    std::vector<flacgpu_raw_stream> raw_streams;
+    std::vector<ManyFrame> raw_tab;   // uploaded to raw_frames by the first decode_frames of the scan
+    bool raw_tab_uploaded = false;
+    DevBuf raw_frames;
+    uint64_t raw_elements = 0, raw_scratch = 0;
 };
 
 namespace {
+// The device half of a scan: uploads every slot's bytes in one copy (zero tails, 64 bytes of look-ahead) and runs the
+// scan kernels; leaves the candidates' positions, records and links and every slot's first candidate on the host.
+// `at` = the end of the last slot.  raw: the scan of raw frame streams (k_scan_subset, k_link_raw).
+int device_scan(flacgpu_decoder *d, const uint8_t *const *data, const std::vector<ScanSlot> &slots,
+                const std::vector<size_t> &region_at, const std::vector<uint32_t> &slot_stream, uint64_t at, bool raw,
+                std::vector<uint64_t> &cpos, std::vector<uint32_t> &cinfo, std::vector<int32_t> &clink,
+                std::vector<uint32_t> &cand0, uint32_t *n_cand_out) {
+    const uint32_t S = (uint32_t)slots.size();
+    const std::string who = raw ? "flacgpu_decoder_scan_frames" : "flacgpu_decoder_scan";
+    // the bit reader indexes dwords with 32 bits
+    if (at + 64 > ((uint64_t)1 << 34)) {
+        g_last_error = who + ": the batch's frames exceed 16 GiB";
+        return FLACGPU_ERR_UNSUPPORTED;
+    }
+    const uint64_t n_blocks = at / 64;
+    const uint64_t n_wg64 = (n_blocks + WG - 1) / WG;
+    if (n_wg64 > 0xFFFFFFFFull) return FLACGPU_ERR_UNSUPPORTED;
+    const uint32_t n_wg = (uint32_t)n_wg64;
+    // ---- one upload: every region into the pinned staging, zero tails, 64 bytes of look-ahead
+    const size_t buf_bytes = at + 64;
+    if (int rc = d->staging.ensure(buf_bytes)) return rc;
+    uint8_t *stg = d->staging.as<uint8_t>();
+    for (uint32_t s = 0; s < S; s++) {
+        const uint64_t b = slots[s].base, l = slots[s].len;
+        const uint64_t e = s + 1 < S ? slots[s + 1].base : buf_bytes;
+        memcpy(stg + b, data[slot_stream[s]] + region_at[s], l);
+        memset(stg + b + l, 0, e - b - l);
+    }
+    if (int rc = d->bytes.ensure(buf_bytes)) return rc;
+    if (int rc = d->slots.ensure(sizeof(ScanSlot) * S)) return rc;
+    if (int rc = d->mask.ensure(8 * n_blocks)) return rc;
+    if (int rc = d->plocal.ensure(2 * n_blocks)) return rc;
+    if (int rc = d->wg_cnt.ensure(4 * n_wg)) return rc;
+    if (int rc = d->wg_tail.ensure(4 * n_wg)) return rc;
+    if (int rc = d->wg_off.ensure(4 * (n_wg + 1))) return rc;
+    if (int rc = d->wg_carry.ensure(2 * n_wg)) return rc;
+    if (int rc = d->slot_cand0.ensure(4 * S)) return rc;
+    if (int rc = d->slot_pend.ensure(4 * S)) return rc;
+    HIP_TRY(hipMemcpyAsync(d->bytes.p, stg, buf_bytes, hipMemcpyHostToDevice, d->st));
+    HIP_TRY(hipMemcpyAsync(d->slots.p, slots.data(), sizeof(ScanSlot) * S, hipMemcpyHostToDevice, d->st));
+    ScanParams p{};
+    p.bytes = d->bytes.as<uint8_t>();
+    p.slots = d->slots.as<ScanSlot>();
+    p.n_slots = S;
+    p.n_blocks = n_blocks;
+    p.mask = d->mask.as<uint64_t>();
+    p.plocal = d->plocal.as<uint16_t>();
+    p.wg_cnt = d->wg_cnt.as<uint32_t>();
+    p.wg_tail = d->wg_tail.as<uint32_t>();
+    p.wg_off = d->wg_off.as<uint32_t>();
+    p.wg_carry = d->wg_carry.as<uint16_t>();
+    p.slot_cand0 = d->slot_cand0.as<uint32_t>();
+    p.slot_pend = d->slot_pend.as<uint32_t>();
+    hipLaunchKernelGGL(k_scan_blocks, dim3(n_wg), dim3(WG), 0, d->st, p);
+    if (raw) hipLaunchKernelGGL(k_scan_subset, dim3(n_wg), dim3(WG), 0, d->st, p);
+    hipLaunchKernelGGL(k_scan_carry, dim3(1), dim3(WG), 0, d->st, p, n_wg);
+    HIP_TRY(hipGetLastError());
+    uint32_t n_cand = 0;
+    HIP_TRY(hipMemcpyAsync(&n_cand, d->wg_off.as<uint32_t>() + n_wg, 4, hipMemcpyDeviceToHost, d->st));
+    HIP_TRY(hipStreamSynchronize(d->st));
+    const size_t nc = std::max<uint32_t>(n_cand, 1);
+    if (int rc = d->cand_pos.ensure(8 * nc)) return rc;
+    if (int rc = d->cand_info.ensure(4 * nc)) return rc;
+    if (int rc = d->cand_crc.ensure(4 * nc)) return rc;
+    if (int rc = d->cand_slot.ensure(4 * nc)) return rc;
+    if (int rc = d->link.ensure(4 * nc)) return rc;
+    p.cand_pos = d->cand_pos.as<uint64_t>();
+    p.cand_info = d->cand_info.as<uint32_t>();
+    p.cand_crc = d->cand_crc.as<uint32_t>();
+    p.cand_slot = d->cand_slot.as<uint32_t>();
+    p.link = d->link.as<int32_t>();
+    p.n_cand = n_cand;
+    hipLaunchKernelGGL(k_scan_emit, dim3(n_wg), dim3(WG), 0, d->st, p);
+    if (n_cand && raw) hipLaunchKernelGGL(k_link_raw, dim3((n_cand + WG - 1) / WG), dim3(WG), 0, d->st, p);
+    else if (n_cand) hipLaunchKernelGGL(k_link, dim3((n_cand + WG - 1) / WG), dim3(WG), 0, d->st, p);
+    HIP_TRY(hipGetLastError());
+    try {
+        cpos.resize(n_cand);
+        cinfo.resize(n_cand);
+        clink.resize(n_cand);
+    } catch (const std::bad_alloc &) {
+        g_last_error = who + ": out of host memory";
+        return FLACGPU_ERR_UNSUPPORTED;
+    }
+    if (n_cand) {
+        HIP_TRY(hipMemcpyAsync(cpos.data(), p.cand_pos, 8 * (size_t)n_cand, hipMemcpyDeviceToHost, d->st));
+        HIP_TRY(hipMemcpyAsync(cinfo.data(), p.cand_info, 4 * (size_t)n_cand, hipMemcpyDeviceToHost, d->st));
+        HIP_TRY(hipMemcpyAsync(clink.data(), p.link, 4 * (size_t)n_cand, hipMemcpyDeviceToHost, d->st));
+    }
+    HIP_TRY(hipMemcpyAsync(cand0.data(), p.slot_cand0, 4 * (size_t)S, hipMemcpyDeviceToHost, d->st));
+    HIP_TRY(hipStreamSynchronize(d->st));
+    *n_cand_out = n_cand;
+    return FLACGPU_OK;
+}
+
 int scan_impl(flacgpu_decoder *d, const uint8_t *const *data, const size_t *len, uint32_t n) {
     d->res.assign(n, flacgpu_decoded_stream{});
     d->slot_of.assign(n, -1);
@@ -100,87 +205,10 @@ int scan_impl(flacgpu_decoder *d, const uint8_t *const *data, const size_t *len,
     std::vector<uint64_t> cpos;
     std::vector<uint32_t> cinfo, cand0(S);
     std::vector<int32_t> clink;
+    uint32_t n_cand = 0;
     if (S) {
-        // the bit reader indexes dwords with 32 bits
-        if (at + 64 > ((uint64_t)1 << 34)) {
-            g_last_error = "flacgpu_decoder_scan: the batch's frames exceed 16 GiB";
-            return FLACGPU_ERR_UNSUPPORTED;
-        }
-        const uint64_t n_blocks = at / 64;
-        const uint64_t n_wg64 = (n_blocks + WG - 1) / WG;
-        if (n_wg64 > 0xFFFFFFFFull) return FLACGPU_ERR_UNSUPPORTED;
-        const uint32_t n_wg = (uint32_t)n_wg64;
-        // ---- one upload: every region into the pinned staging, zero tails, 64 bytes of look-ahead
-        const size_t buf_bytes = at + 64;
-        if (int rc = d->staging.ensure(buf_bytes)) return rc;
-        uint8_t *stg = d->staging.as<uint8_t>();
-        for (uint32_t s = 0; s < S; s++) {
-            const uint64_t b = slots[s].base, l = slots[s].len;
-            const uint64_t e = s + 1 < S ? slots[s + 1].base : buf_bytes;
-            memcpy(stg + b, data[slot_stream[s]] + region_at[s], l);
-            memset(stg + b + l, 0, e - b - l);
-        }
-        if (int rc = d->bytes.ensure(buf_bytes)) return rc;
-        if (int rc = d->slots.ensure(sizeof(ScanSlot) * S)) return rc;
-        if (int rc = d->mask.ensure(8 * n_blocks)) return rc;
-        if (int rc = d->plocal.ensure(2 * n_blocks)) return rc;
-        if (int rc = d->wg_cnt.ensure(4 * n_wg)) return rc;
-        if (int rc = d->wg_tail.ensure(4 * n_wg)) return rc;
-        if (int rc = d->wg_off.ensure(4 * (n_wg + 1))) return rc;
-        if (int rc = d->wg_carry.ensure(2 * n_wg)) return rc;
-        if (int rc = d->slot_cand0.ensure(4 * S)) return rc;
-        if (int rc = d->slot_pend.ensure(4 * S)) return rc;
-        HIP_TRY(hipMemcpyAsync(d->bytes.p, stg, buf_bytes, hipMemcpyHostToDevice, d->st));
-        HIP_TRY(hipMemcpyAsync(d->slots.p, slots.data(), sizeof(ScanSlot) * S, hipMemcpyHostToDevice, d->st));
-        ScanParams p{};
-        p.bytes = d->bytes.as<uint8_t>();
-        p.slots = d->slots.as<ScanSlot>();
-        p.n_slots = S;
-        p.n_blocks = n_blocks;
-        p.mask = d->mask.as<uint64_t>();
-        p.plocal = d->plocal.as<uint16_t>();
-        p.wg_cnt = d->wg_cnt.as<uint32_t>();
-        p.wg_tail = d->wg_tail.as<uint32_t>();
-        p.wg_off = d->wg_off.as<uint32_t>();
-        p.wg_carry = d->wg_carry.as<uint16_t>();
-        p.slot_cand0 = d->slot_cand0.as<uint32_t>();
-        p.slot_pend = d->slot_pend.as<uint32_t>();
-        hipLaunchKernelGGL(k_scan_blocks, dim3(n_wg), dim3(WG), 0, d->st, p);
-        hipLaunchKernelGGL(k_scan_carry, dim3(1), dim3(WG), 0, d->st, p, n_wg);
-        HIP_TRY(hipGetLastError());
-        uint32_t n_cand = 0;
-        HIP_TRY(hipMemcpyAsync(&n_cand, d->wg_off.as<uint32_t>() + n_wg, 4, hipMemcpyDeviceToHost, d->st));
-        HIP_TRY(hipStreamSynchronize(d->st));
-        const size_t nc = std::max<uint32_t>(n_cand, 1);
-        if (int rc = d->cand_pos.ensure(8 * nc)) return rc;
-        if (int rc = d->cand_info.ensure(4 * nc)) return rc;
-        if (int rc = d->cand_crc.ensure(4 * nc)) return rc;
-        if (int rc = d->cand_slot.ensure(4 * nc)) return rc;
-        if (int rc = d->link.ensure(4 * nc)) return rc;
-        p.cand_pos = d->cand_pos.as<uint64_t>();
-        p.cand_info = d->cand_info.as<uint32_t>();
-        p.cand_crc = d->cand_crc.as<uint32_t>();
-        p.cand_slot = d->cand_slot.as<uint32_t>();
-        p.link = d->link.as<int32_t>();
-        p.n_cand = n_cand;
-        hipLaunchKernelGGL(k_scan_emit, dim3(n_wg), dim3(WG), 0, d->st, p);
-        if (n_cand) hipLaunchKernelGGL(k_link, dim3((n_cand + WG - 1) / WG), dim3(WG), 0, d->st, p);
-        HIP_TRY(hipGetLastError());
-        try {
-            cpos.resize(n_cand);
-            cinfo.resize(n_cand);
-            clink.resize(n_cand);
-        } catch (const std::bad_alloc &) {
-            g_last_error = "flacgpu_decoder_scan: out of host memory";
-            return FLACGPU_ERR_UNSUPPORTED;
-        }
-        if (n_cand) {
-            HIP_TRY(hipMemcpyAsync(cpos.data(), p.cand_pos, 8 * (size_t)n_cand, hipMemcpyDeviceToHost, d->st));
-            HIP_TRY(hipMemcpyAsync(cinfo.data(), p.cand_info, 4 * (size_t)n_cand, hipMemcpyDeviceToHost, d->st));
-            HIP_TRY(hipMemcpyAsync(clink.data(), p.link, 4 * (size_t)n_cand, hipMemcpyDeviceToHost, d->st));
-        }
-        HIP_TRY(hipMemcpyAsync(cand0.data(), p.slot_cand0, 4 * (size_t)S, hipMemcpyDeviceToHost, d->st));
-        HIP_TRY(hipStreamSynchronize(d->st));
+        if (int rc = device_scan(d, data, slots, region_at, slot_stream, at, false, cpos, cinfo, clink, cand0, &n_cand))
+            return rc;
         // ---- host walk: follow the links from each region's first byte (the host scan's lost-sync rule: a frame
         // without an end is not taken, and nothing behind it is decoded)
         for (uint32_t s = 0; s < S; s++) {
@@ -243,6 +271,205 @@ int scan_impl(flacgpu_decoder *d, const uint8_t *const *data, const size_t *len,
     d->total = total;
     d->scratch_total = scratch_total;
     d->slot_stream.swap(slot_stream);
+    return FLACGPU_OK;
+}
+
+// flacgpu_decoder_scan_frames behind its argument checks: a slot is a whole input, the device finds the candidates and
+// their ends by the raw rule, and the host walks them with a cursor (DESIGN.md "Raw frame streams").
+int scan_raw_impl(flacgpu_decoder *d, const uint8_t *const *data, const size_t *len, uint32_t n) {
+    std::vector<ScanSlot> slots;
+    std::vector<size_t> region_at;
+    std::vector<uint32_t> slot_stream, cinfo, cand0;
+    std::vector<uint64_t> cpos;
+    std::vector<int32_t> clink;
+    uint64_t at = 0;
+    try {   // no exception crosses the C ABI
+        d->res.assign(n, flacgpu_decoded_stream{});
+        d->slot_of.assign(n, -1);
+        d->frame_tab.clear();
+        d->records.clear();
+        d->raw_streams.assign(n, flacgpu_raw_stream{});
+        for (uint32_t i = 0; i < n; i++) {
+            if (!data[i] || !len[i]) continue;   // nothing to scan: no kept frame
+            ScanSlot s{};
+            s.base = at;
+            s.len = len[i];
+            s.block0 = at / 64;
+            d->slot_of[i] = (int32_t)slots.size();
+            slots.push_back(s);
+            region_at.push_back(0);
+            slot_stream.push_back(i);
+            at += (s.len + kSlotTail + 63) & ~(uint64_t)63;
+        }
+        cand0.resize(slots.size());
+    } catch (const std::bad_alloc &) {
+        g_last_error = "flacgpu_decoder_scan_frames: out of host memory";
+        return FLACGPU_ERR_UNSUPPORTED;
+    }
+    const uint32_t S = (uint32_t)slots.size();
+    d->n_slots = S;
+    uint32_t n_cand = 0;
+    if (S)
+        if (int rc = device_scan(d, data, slots, region_at, slot_stream, at, true, cpos, cinfo, clink, cand0, &n_cand))
+            return rc;
+    // ---- host walk, stream by stream: the candidates in ascending order, those below the cursor ignored, one without
+    // an end passed over, one with an end kept and the cursor moved to that end.  A kept frame's record is read from
+    // its own header in the staging copy of the bytes.
+    std::vector<ManyFrame> &all = d->raw_tab;   // decode_frames' table
+    all.clear();
+    d->raw_tab_uploaded = false;
+    const uint8_t *stg = d->staging.as<const uint8_t>();
+    uint64_t elements = 0, total = 0, raw_scratch = 0, scratch_total = 0;
+    try {
+        d->records.reserve(n_cand);   // a kept frame is a candidate
+        all.reserve(n_cand);
+        d->frame_tab.reserve(n_cand);
+        for (uint32_t i = 0; i < n; i++) {
+            flacgpu_decoded_stream &r = d->res[i];
+            flacgpu_raw_stream &sum = d->raw_streams[i];
+            const size_t first = d->records.size();
+            const int32_t s = d->slot_of[i];
+            if (s >= 0) {
+                const ScanSlot &sl = slots[s];
+                const uint32_t c_end = (uint32_t)s + 1 < S ? cand0[s + 1] : n_cand;
+                const uint64_t slot_end = (uint32_t)s + 1 < S ? slots[s + 1].base : at;
+                uint64_t cursor = sl.base;
+                for (uint32_t c = cand0[s]; c < c_end; c++) {
+                    if (cpos[c] < cursor || clink[c] == LINK_NONE) continue;
+                    const uint64_t end = clink[c] == LINK_END ? sl.base + sl.len : cpos[clink[c]];
+                    flacenc::HostFrameInfo h;   // the header was accepted by K_s1: its record, and the rest from its bytes
+                    h.n = (cinfo[c] & 0xFFFFu) + 1u;
+                    h.header_bytes = (cinfo[c] >> 16) & 0xFFu;
+                    h.blocking = cinfo[c] >> 24;
+                    h.acode = stg[cpos[c] + 3] >> 4;
+                    h.bps_code = (stg[cpos[c] + 3] >> 1) & 7;
+                    flacenc::host_frame_fields(stg + cpos[c], h);
+                    flacgpu_frame_record f{};
+                    f.byte_offset = cpos[c] - sl.base;
+                    f.number = h.number;
+                    f.out_offset = elements;
+                    f.stream = i;
+                    f.bytes = (uint32_t)(end - cpos[c]);
+                    f.block_size = h.n;
+                    f.sample_rate = h.sample_rate;
+                    f.channels = h.channels;
+                    f.bits_per_sample = h.bits_per_sample;
+                    f.assignment = h.acode;
+                    f.blocking = h.blocking;
+                    ManyFrame m{};
+                    m.start = cpos[c];
+                    m.end = end;
+                    m.cap = slot_end - 4;
+                    m.scratch = raw_scratch;
+                    m.out = elements;
+                    m.n = h.n;
+                    m.slot = (uint32_t)d->records.size();   // the frame kernels count per slot: per frame here
+                    m.channels = h.channels;
+                    m.bps = h.bits_per_sample;
+                    d->records.push_back(f);
+                    all.push_back(m);
+                    elements += (uint64_t)h.n * h.channels;
+                    raw_scratch += (uint64_t)h.channels * ((h.n + 3u) & ~3u);
+                    cursor = end;
+                }
+            }
+            const size_t count = d->records.size() - first;
+            flacenc::summarise_raw_frames(d->records.data() + first, count, len[i], sum);
+            sum.first_frame = first;
+            // ---- the stream's place in the regular batch calls
+            r.out_offset = total;
+            if (!sum.uniform) {
+                r.rc = count ? FLACGPU_ERR_UNSUPPORTED : FLACGPU_ERR_INVALID_ARG;
+                continue;
+            }
+            const flacgpu_frame_record &f0 = d->records[first];
+            r.info.sample_rate = f0.sample_rate;
+            r.info.channels = f0.channels;
+            r.info.bits_per_sample = f0.bits_per_sample;
+            r.info.min_block = r.info.max_block = f0.block_size;
+            r.info.frames = (uint32_t)count;
+            for (size_t k = first; k < first + count; k++) {
+                const flacgpu_frame_record &f = d->records[k];
+                r.info.min_block = std::min(r.info.min_block, f.block_size);
+                r.info.max_block = std::max(r.info.max_block, f.block_size);
+                ManyFrame m = all[k];
+                m.slot = (uint32_t)s;
+                m.out = total + r.info.decoded_samples * f.channels;
+                m.scratch = scratch_total;
+                scratch_total += (uint64_t)m.channels * ((m.n + 3u) & ~3u);
+                d->frame_tab.push_back(m);
+                r.info.decoded_samples += f.block_size;
+            }
+            total += r.info.decoded_samples * r.info.channels;
+        }
+    } catch (const std::bad_alloc &) {
+        g_last_error = "flacgpu_decoder_scan_frames: out of host memory";
+        return FLACGPU_ERR_UNSUPPORTED;
+    }
+    if (all.size() > 0x7FFFFFFFull) {
+        g_last_error = "flacgpu_decoder_scan_frames: more than 2^31 - 1 frames";
+        return FLACGPU_ERR_UNSUPPORTED;
+    }
+    if (!d->frame_tab.empty()) {
+        if (int rc = d->frames.ensure(sizeof(ManyFrame) * d->frame_tab.size())) return rc;
+        HIP_TRY(hipMemcpyAsync(d->frames.p, d->frame_tab.data(), sizeof(ManyFrame) * d->frame_tab.size(),
+                               hipMemcpyHostToDevice, d->st));
+        HIP_TRY(hipStreamSynchronize(d->st));   // frame_tab may change before the copy is done otherwise
+    }
+    d->total = total;
+    d->scratch_total = scratch_total;
+    d->raw_elements = elements;
+    d->raw_scratch = raw_scratch;
+    d->slot_stream.swap(slot_stream);
+    return FLACGPU_OK;
+}
+
+// flacgpu_decoder_decode_frames behind its argument checks: decode's frame kernels over decode_frames' own table, whose
+// slots are the frames, so that counts[2 f] / counts[2 f + 1] say whether frame f parsed and whether its CRC-16 is right.
+int decode_frames_impl(flacgpu_decoder *d, int32_t *out, uint32_t flags, flacgpu_frame_record *records) {
+    DeviceGuard guard(d->device);
+    const uint32_t F = (uint32_t)d->records.size();
+    if (!F) return FLACGPU_OK;
+    const bool to_device = flags & FLACGPU_DECODE_OUT_DEVICE;
+    const size_t out_bytes = 4 * d->raw_elements;
+    int32_t *dst = out;
+    if (!to_device) {
+        if (int rc = d->out_stage.ensure(out_bytes)) return rc;
+        dst = d->out_stage.as<int32_t>();
+    }
+    if (int rc = d->counts.ensure(8 * (size_t)F)) return rc;
+    if (int rc = d->scratch.ensure(4 * d->raw_scratch)) return rc;
+    if (int rc = d->codes.ensure(4 * (size_t)F)) return rc;
+    if (!d->raw_tab_uploaded) {   // once per scan: a batch that only goes through decode / decode_as never pays for it
+        if (int rc = d->raw_frames.ensure(sizeof(ManyFrame) * (size_t)F)) return rc;
+        HIP_TRY(hipMemcpyAsync(d->raw_frames.p, d->raw_tab.data(), sizeof(ManyFrame) * (size_t)F, hipMemcpyHostToDevice, d->st));
+        HIP_TRY(hipStreamSynchronize(d->st));
+        d->raw_tab_uploaded = true;
+    }
+    HIP_TRY(hipMemsetAsync(d->counts.p, 0, 8 * (size_t)F, d->st));
+    const ManyFrame *frames = d->raw_frames.as<const ManyFrame>();
+    const uint32_t lanes = 32;   // as decode_impl launches it
+    hipLaunchKernelGGL(k_decode_many<32>, dim3((F + lanes - 1) / lanes), dim3(lanes), 0, d->st,
+                       d->bytes.as<const uint32_t>(), frames, F, d->scratch.as<int32_t>(), d->codes.as<uint32_t>());
+    hipLaunchKernelGGL(k_frame_crc, dim3(F), dim3(64), 0, d->st, d->bytes.as<const uint8_t>(), frames,
+                       d->counts.as<uint32_t>());
+    hipLaunchKernelGGL(k_finish_many, dim3(F), dim3(WG), 0, d->st, frames, d->scratch.as<const int32_t>(),
+                       d->codes.as<const uint32_t>(), dst, d->counts.as<uint32_t>());
+    HIP_TRY(hipGetLastError());
+    std::vector<uint32_t> counts;
+    try {   // no exception crosses the C ABI; the kernels are waited for before the return
+        counts.resize(2 * (size_t)F);
+    } catch (const std::bad_alloc &) {
+        (void)hipStreamSynchronize(d->st);
+        g_last_error = "flacgpu_decoder_decode_frames: out of host memory";
+        return FLACGPU_ERR_UNSUPPORTED;
+    }
+    HIP_TRY(hipMemcpyAsync(counts.data(), d->counts.p, 8 * (size_t)F, hipMemcpyDeviceToHost, d->st));
+    if (!to_device) HIP_TRY(hipMemcpyAsync(out, dst, out_bytes, hipMemcpyDeviceToHost, d->st));
+    HIP_TRY(hipStreamSynchronize(d->st));
+    memcpy(records, d->records.data(), sizeof(flacgpu_frame_record) * F);
+    for (uint32_t f = 0; f < F; f++)
+        records[f].status = (counts[2 * (size_t)f] ? 1u : 0u) | (counts[2 * (size_t)f + 1] ? 2u : 0u);
     return FLACGPU_OK;
 }
 
@@ -607,7 +834,7 @@ void flacgpu_decoder_destroy(flacgpu_decoder *d) {
 int flacgpu_decoder_scan(flacgpu_decoder *d, const uint8_t *const *data, const size_t *len, uint32_t n_streams,
                          flacgpu_decoded_stream *streams, uint64_t *total_samples) {
     if (!d || (n_streams && (!data || !len || !streams)) || !total_samples) return FLACGPU_ERR_INVALID_ARG;
-    d->scanned = false;
+    d->scanned = d->raw = false;
     DeviceGuard guard(d->device);
     if (int rc = scan_impl(d, data, len, n_streams)) return rc;
     index_frames(d);
@@ -615,6 +842,55 @@ int flacgpu_decoder_scan(flacgpu_decoder *d, const uint8_t *const *data, const s
     if (n_streams) memcpy(streams, d->res.data(), sizeof(flacgpu_decoded_stream) * n_streams);
     *total_samples = d->total;
     return FLACGPU_OK;
+}
+
+int flacgpu_decoder_scan_frames(flacgpu_decoder *d, const uint8_t *const *data, const size_t *len, uint32_t n_streams,
+                                flacgpu_decoded_stream *streams, flacgpu_raw_stream *raw, uint64_t *total_frames,
+                                uint64_t *total_elements, uint64_t *total_samples) {
+    if (!d || (n_streams && (!data || !len || !streams)) || !total_frames || !total_elements || !total_samples)
+        return FLACGPU_ERR_INVALID_ARG;
+    d->scanned = d->raw = false;
+    DeviceGuard guard(d->device);
+    if (int rc = scan_raw_impl(d, data, len, n_streams)) return rc;
+    index_frames(d);
+    d->scanned = d->raw = true;
+    if (n_streams) memcpy(streams, d->res.data(), sizeof(flacgpu_decoded_stream) * n_streams);
+    if (n_streams && raw) memcpy(raw, d->raw_streams.data(), sizeof(flacgpu_raw_stream) * n_streams);
+    *total_frames = d->records.size();
+    *total_elements = d->raw_elements;
+    *total_samples = d->total;
+    return FLACGPU_OK;
+}
+
+int flacgpu_decoder_frame_records(flacgpu_decoder *d, flacgpu_frame_record *records, size_t cap) {
+    if (!d) return FLACGPU_ERR_INVALID_ARG;
+    if (!d->scanned || !d->raw) {
+        g_last_error = "flacgpu_decoder_frame_records: no scanned batch of raw frame streams";
+        return FLACGPU_ERR_INVALID_ARG;
+    }
+    if (d->records.empty()) return FLACGPU_OK;
+    if (!records) return FLACGPU_ERR_INVALID_ARG;
+    if (cap < d->records.size()) {
+        g_last_error = "output buffer too small";
+        return FLACGPU_ERR_BUFFER_TOO_SMALL;
+    }
+    memcpy(records, d->records.data(), sizeof(flacgpu_frame_record) * d->records.size());
+    return FLACGPU_OK;
+}
+
+int flacgpu_decoder_decode_frames(flacgpu_decoder *d, int32_t *out, size_t out_cap_elements, uint32_t flags,
+                                  flacgpu_frame_record *records, size_t cap) {
+    if (!d || (flags & ~FLACGPU_DECODE_OUT_DEVICE)) return FLACGPU_ERR_INVALID_ARG;
+    if (!d->scanned || !d->raw) {
+        g_last_error = "flacgpu_decoder_decode_frames: no scanned batch of raw frame streams";
+        return FLACGPU_ERR_INVALID_ARG;
+    }
+    if (!d->records.empty() && !records) return FLACGPU_ERR_INVALID_ARG;
+    if (cap < d->records.size() || (d->raw_elements && (!out || out_cap_elements < d->raw_elements))) {
+        g_last_error = "output buffer too small";
+        return FLACGPU_ERR_BUFFER_TOO_SMALL;
+    }
+    return decode_frames_impl(d, out, flags, records);
 }
 
 int flacgpu_decoder_decode(flacgpu_decoder *d, int32_t *out, size_t out_cap_samples, uint32_t flags,

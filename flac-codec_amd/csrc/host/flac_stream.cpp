@@ -87,6 +87,105 @@ bool host_parse_header(const uint8_t *d, size_t avail, HostFrameHead &h) {
     return true;
 }
 
+bool host_parse_frame_info(const uint8_t *d, size_t avail, HostFrameInfo &h) {
+    if (!host_parse_header(d, avail, h)) return false;
+    host_frame_fields(d, h);
+    return true;
+}
+
+void host_frame_fields(const uint8_t *d, HostFrameInfo &h) {
+    static const uint32_t kRate[12] = {0, 88200, 176400, 192000, 8000, 16000, 22050, 24000, 32000, 44100, 48000, 96000};
+    static const uint32_t kBits[8] = {0, 8, 12, 0, 16, 20, 24, 32};
+    h.rcode = d[2] & 15;
+    h.channels = h.acode < 8 ? h.acode + 1 : 2;
+    h.bits_per_sample = kBits[h.bps_code];
+    // the coded number (stream.rs:1244-1262): the bits of the first byte behind its leading ones, then 6 per byte
+    uint32_t ones = 0;
+    while (d[4] & (0x80 >> ones)) ones++;
+    h.number = ones ? d[4] & (0x7Fu >> ones) : d[4];
+    for (uint32_t i = 1; i < ones; i++) h.number = h.number << 6 | (d[4 + i] & 0x3F);
+    // the rate's own bytes are the last of the header in front of the CRC-8
+    const uint8_t *tail = d + h.header_bytes - 1;
+    if (h.rcode < 12) h.sample_rate = kRate[h.rcode];
+    else if (h.rcode == 12) h.sample_rate = tail[-1] * 1000u;
+    else h.sample_rate = ((uint32_t)tail[-2] << 8 | tail[-1]) * (h.rcode == 14 ? 10u : 1u);
+}
+
+void summarise_raw_frames(const flacgpu_frame_record *frames, size_t n, size_t len, flacgpu_raw_stream &summary) {
+    summary.frames = (uint32_t)n;
+    summary.uniform = n > 0;
+    summary.skipped_bytes = 0;
+    summary.gaps = 0;
+    uint64_t at = 0;
+    for (size_t i = 0; i < n; i++) {
+        const flacgpu_frame_record &f = frames[i];
+        if (f.sample_rate != frames[0].sample_rate || f.channels != frames[0].channels ||
+            f.bits_per_sample != frames[0].bits_per_sample)
+            summary.uniform = 0;
+        if (f.byte_offset > at) {
+            summary.skipped_bytes += f.byte_offset - at;
+            summary.gaps++;
+        }
+        at = f.byte_offset + f.bytes;
+    }
+    if (len > at) {
+        summary.skipped_bytes += len - at;
+        summary.gaps++;
+    }
+}
+
+void scan_raw_frames(const uint8_t *data, size_t len, std::vector<flacgpu_frame_record> &frames,
+                     flacgpu_raw_stream &summary) {
+    const uint16_t *const T = crc16_table();
+    // the candidates: a header that parses, with a sample rate and a sample size of its own
+    std::vector<size_t> cand;
+    std::vector<HostFrameInfo> head;
+    for (size_t q = 0; q < len; q++) {
+        HostFrameInfo h;
+        if (data[q] == 0xFF && host_parse_frame_info(data + q, len - q, h) && h.rcode != 0 && h.bps_code != 0) {
+            cand.push_back(q);
+            head.push_back(h);
+        }
+    }
+    frames.clear();
+    uint64_t out = 0;
+    size_t cursor = 0;
+    for (size_t i = 0; i < cand.size(); i++) {
+        const size_t s = cand[i];
+        if (s < cursor) continue;
+        const HostFrameInfo &h = head[i];
+        const size_t min_end = s + h.header_bytes + 2 + h.channels;
+        // with init 0 and no final XOR, bytes [q-2, q) are the CRC-16 of [s, q-2) exactly when the CRC-16 of [s, q) is 0
+        uint16_t crc = 0;
+        size_t at = s, end = 0;
+        for (size_t j = i + 1; j < cand.size() && !end; j++) {
+            for (; at < cand[j]; at++) crc = crc16_step(T, crc, data[at]);
+            if (cand[j] >= min_end && crc == 0) end = cand[j];
+        }
+        if (!end) {   // the frame ends with the input
+            for (; at < len; at++) crc = crc16_step(T, crc, data[at]);
+            if (len - s >= 2 && crc == 0) end = len;
+        }
+        if (!end) continue;   // no end: passed over, the walk goes on behind it
+        flacgpu_frame_record f{};
+        f.byte_offset = s;
+        f.number = h.number;
+        f.out_offset = out;
+        f.bytes = (uint32_t)(end - s);
+        f.block_size = h.n;
+        f.sample_rate = h.sample_rate;
+        f.channels = h.channels;
+        f.bits_per_sample = h.bits_per_sample;
+        f.assignment = h.acode;
+        f.blocking = h.blocking;
+        frames.push_back(f);
+        out += (uint64_t)h.n * h.channels;
+        cursor = end;
+    }
+    summary = flacgpu_raw_stream{};
+    summarise_raw_frames(frames.data(), frames.size(), len, summary);
+}
+
 void scan_frames(const uint8_t *data, size_t len, size_t pos, uint32_t min_frame, flacgpu_stream_info *info, FrameScan &scan) {
     const uint16_t *const T = crc16_table();   // taken once: the inner loop is one table step per byte
     size_t p = pos;

@@ -22,6 +22,20 @@ struct HostFrameHead {
 // FrameHeader::parse (stream.rs:214-240) + CRC-8 on `avail` bytes
 bool host_parse_header(const uint8_t *d, size_t avail, HostFrameHead &h);
 
+// host_parse_header's answer and the rest of the header: what a frame says about itself when no STREAMINFO does
+struct HostFrameInfo : HostFrameHead {
+    uint32_t rcode = 0;            // sample-rate code (0: "as STREAMINFO")
+    uint32_t sample_rate = 0;      // codes 1-11 from the table, 12 a kHz byte, 13 Hz, 14 tens of Hz; 0 for code 0
+    uint32_t channels = 0;         // from the assignment code
+    uint32_t bits_per_sample = 0;  // from the sample-size code; 0 for code 0
+    uint64_t number = 0;           // the coded frame or sample number (1-7 bytes)
+};
+// host_parse_header (same acceptance, same fields) plus the fields above
+bool host_parse_frame_info(const uint8_t *d, size_t avail, HostFrameInfo &h);
+// the fields above alone, of a header that host_parse_header has accepted with these header_bytes and this acode /
+// bps_code in `h` (the batch decoder's walk: the device scan has accepted the header already)
+void host_frame_fields(const uint8_t *d, HostFrameInfo &h);
+
 struct FrameScan {
     std::vector<uint64_t> off;   // [frames + 1] frame starts, then where the scan stopped
     std::vector<uint32_t> n;     // [frames] block sizes
@@ -29,6 +43,14 @@ struct FrameScan {
 // The frames of data[pos, len), by the rule of DESIGN.md "The scan finds the host scan's frames, for any bytes"; fills
 // info->frames, decoded_samples and bad_frames (1: the scan lost synchronisation) for the channels `info` names.
 void scan_frames(const uint8_t *data, size_t len, size_t pos, uint32_t min_frame, flacgpu_stream_info *info, FrameScan &scan);
+
+// The kept frames of a raw frame stream data[0, len) -- bare frames, no fLaC marker, no STREAMINFO -- by the rule of
+// DESIGN.md "Raw frame streams": `frames` gets one record per kept frame in position order (stream 0, out_offset the
+// running sum of block_size * channels, status 0), `summary` the counts (first_frame 0).
+void scan_raw_frames(const uint8_t *data, size_t len, std::vector<flacgpu_frame_record> &frames,
+                     flacgpu_raw_stream &summary);
+// `summary`'s frames, uniform flag, skipped_bytes and gaps from the stream's kept frames (first_frame is left alone)
+void summarise_raw_frames(const flacgpu_frame_record *frames, size_t n, size_t len, flacgpu_raw_stream &summary);
 
 // The decoded frames (at least one), planar [frame][channel][ldb], interleaved into `out` (may be null) and hashed as
 // ceil(bps / 8)-byte little-endian samples (decode.rs:1282 verify): fills info->decoded_md5 and info->md5_status.

@@ -11,6 +11,9 @@
 //                        in offset order, holding the header's fields and A = P x^(-8 q) (below)
 //   K_s4 k_link          lane per candidate s: the first later candidate q that ends frame s (distance, blocking bit,
 //                        CRC(s, q) == 0), or the slot's end, or none
+// Raw frame streams (no metadata: a slot is the whole input; DESIGN.md "Raw frame streams") run the same kernels with two
+// of their own: K_r1 k_scan_subset behind K_s1 drops the candidates that leave their sample rate or sample size to a
+// STREAMINFO, and K_r2 k_link_raw stands in for K_s4 with the raw end rule.  K_s2 and K_s3 (P64, A, slot_pend) are shared.
 // With init 0 and no final XOR, bytes [q-2, q) are the CRC-16 of [s, q-2) exactly when CRC(s, q) == 0, and
 // CRC(s, q) = P(q) ^ P(s) x^(8 (q - s)) mod P with P(k) = CRC-16 of the region's bytes [0, k).  x is invertible mod P,
 // so CRC(s, q) == 0 exactly when A(q) == A(s) with A(k) = P(k) x^(-8 k): one comparison per tested pair.
@@ -352,6 +355,58 @@ __global__ void __launch_bounds__(WG) k_link(ScanParams p) {
     int32_t link = LINK_NONE;
     for (uint32_t j = i + 1; j < end; j++) {
         if (p.cand_crc[j] != A || (p.cand_info[j] >> 24) != blocking || p.cand_pos[j] - pos < min_len) continue;
+        link = (int32_t)j;
+        break;
+    }
+    if (link == LINK_NONE && sl.base + sl.len - pos >= 2 && p.slot_pend[s] == A) link = LINK_END;
+    p.link[i] = link;
+}
+
+// ---- raw frame streams ----
+// K_r1: lane per block, behind K_s1 and in front of K_s2.  A raw stream's frame must say its own sample rate and sample
+// size (FrameHeader::read_subset, stream.rs:672, 1161): candidates whose codes for either are 0 leave the bitmap, and
+// the workgroup's candidates are counted again.  A candidate has at least 6 bytes of its stream behind it (K_s1).
+__global__ void __launch_bounds__(WG) k_scan_subset(ScanParams p) {
+    __shared__ uint32_t scnt[WG / 64];
+    const uint32_t tid = threadIdx.x;
+    const uint64_t b = (uint64_t)blockIdx.x * WG + tid;
+    uint32_t cnt = 0;
+    if (b < p.n_blocks) {
+        uint64_t m = p.mask[b], t = m;
+        const uint8_t *blk = p.bytes + b * 64;
+        while (t) {
+            const uint32_t j = (uint32_t)__builtin_ctzll(t);
+            t &= t - 1;
+            if ((blk[j + 2] & 15u) == 0 || ((blk[j + 3] >> 1) & 7u) == 0) m &= ~(1ull << j);
+        }
+        p.mask[b] = m;
+        cnt = (uint32_t)__builtin_popcountll(m);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
+    if ((tid & 63) == 0) scnt[tid >> 6] = cnt;
+    __syncthreads();
+    if (tid == WG - 1) p.wg_cnt[blockIdx.x] = scnt[0] + scnt[1] + scnt[2] + scnt[3];
+}
+
+// K_r2: lane per candidate.  The raw end rule: frame s ends at the first later candidate q >= s + header_bytes + 2 +
+// channels(s) with CRC(s, q) == 0 -- the channels are those of s's own assignment code (byte 3 of its header), the
+// blocking bit of q is not compared and there is no minimum frame size: every frame stands alone --; failing that, with
+// the input when its last two bytes are that CRC; failing that, nowhere (the host walk passes such a candidate over).
+__global__ void __launch_bounds__(WG) k_link_raw(ScanParams p) {
+    const uint32_t i = blockIdx.x * WG + threadIdx.x;
+    if (i >= p.n_cand) return;
+    const uint32_t s = p.cand_slot[i];
+    const ScanSlot sl = p.slots[s];
+    const uint32_t end = s + 1 < p.n_slots ? p.slot_cand0[s + 1] : p.n_cand;
+    const uint64_t pos = p.cand_pos[i];
+    const uint32_t hb = (p.cand_info[i] >> 16) & 0xFFu;
+    const uint32_t acode = p.bytes[pos + 3] >> 4;
+    const uint64_t min_len = hb + 2u + (acode < 8 ? acode + 1u : 2u);
+    const uint32_t A = p.cand_crc[i];
+    int32_t link = LINK_NONE;
+    for (uint32_t j = i + 1; j < end; j++) {
+        if (p.cand_crc[j] != A || p.cand_pos[j] - pos < min_len) continue;
         link = (int32_t)j;
         break;
     }

@@ -1,8 +1,11 @@
 """Verification of FLAC files on the GPU, the counterpart of the reference's `decode::verify` (decode.rs:1282-1310):
 every frame must be found and parse with a correct CRC-16, and the MD5 of the decoded samples is compared with
-STREAMINFO's.  Many files go through one batch (gpu.decode_many)."""
+STREAMINFO's.  Many files go through one batch (gpu.decode_many).  FlacStreamReader / FrameBuf are the counterpart of
+`decode::FlacStreamReader` (decode.rs:1099-1268): the reader of what encode.FlacStreamWriter writes."""
 import enum
 import os
+
+import numpy as np
 
 from . import gpu
 
@@ -49,3 +52,76 @@ def verify(path, device=-1):
     if isinstance(r, Exception):
         raise r
     return r
+
+
+class FrameBuf:
+    """One decoded frame of a raw frame stream (decode.rs:1099 FrameBuf): `samples` is interleaved int32
+    [block_size * channels], with the parameters its own header gave."""
+    __slots__ = ("samples", "sample_rate", "channels", "bits_per_sample")
+
+    def __init__(self, samples, sample_rate, channels, bits_per_sample):
+        self.samples = np.asarray(samples, dtype=np.int32)
+        self.sample_rate, self.channels, self.bits_per_sample = int(sample_rate), int(channels), int(bits_per_sample)
+
+    def __eq__(self, other):
+        return (isinstance(other, FrameBuf) and np.array_equal(self.samples, other.samples) and
+                (self.sample_rate, self.channels, self.bits_per_sample) ==
+                (other.sample_rate, other.channels, other.bits_per_sample))
+
+    def __repr__(self):
+        return "FrameBuf(%d samples, %d Hz, %d channel(s), %d bits)" % (
+            self.samples.size, self.sample_rate, self.channels, self.bits_per_sample)
+
+
+class FlacStreamReader:
+    """Reads the frames of a raw frame stream -- what encode.FlacStreamWriter writes: bare subset frames, no fLaC marker,
+    no STREAMINFO -- one FrameBuf per read() (decode.rs:1142 FlacStreamReader).  The whole input is decoded in one GPU
+    batch on first use.  Frames are found by the rule of DESIGN.md "Raw frame streams": bytes that belong to no whole
+    frame are skipped, where the reference reports an error at the point of damage."""
+
+    def __init__(self, data, device=-1):
+        self._data = data.read() if hasattr(data, "read") else bytes(data)
+        self._device = device
+        self._frames = None
+        self._next = 0
+
+    def _decode(self):
+        if self._frames is None:
+            self._pcm, self._frames, raw = gpu.decode_frames([self._data], device=self._device, out="host")
+            self._skipped_bytes, self._gaps = int(raw[0].skipped_bytes), int(raw[0].gaps)
+            self._data = None
+
+    @property
+    def skipped_bytes(self):
+        """Bytes of the input that belong to no whole frame (decodes the input on first use)."""
+        self._decode()
+        return self._skipped_bytes
+
+    @property
+    def gaps(self):
+        """Maximal runs of skipped bytes: leading, between frames, trailing (decodes the input on first use)."""
+        self._decode()
+        return self._gaps
+
+    def read(self):
+        """The next FrameBuf.  Raises DecodeError for a frame that was found but does not decode (the read after that
+        goes on with the next frame) and EOFError behind the last frame (decode.rs:1195)."""
+        self._decode()
+        if self._next >= len(self._frames):
+            raise EOFError("no more frames")
+        f = self._frames[self._next]
+        self._next += 1
+        if f["status"]:
+            raise DecodeError("the frame at byte %d %s" % (f["byte_offset"], " and ".join(
+                w for bit, w in ((1, "does not parse"), (2, "has a wrong CRC-16")) if f["status"] & bit)))
+        at, count = int(f["out_offset"]), int(f["block_size"]) * int(f["channels"])
+        return FrameBuf(self._pcm[at:at + count], f["sample_rate"], f["channels"], f["bits_per_sample"])
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        try:
+            return self.read()
+        except EOFError:
+            raise StopIteration from None

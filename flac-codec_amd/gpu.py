@@ -408,6 +408,27 @@ def scan_stream_host(data):
     return info, offsets, sizes
 
 
+FRAME_DTYPE = np.dtype([(name, np.dtype(ct).str) for name, ct in _lib.FrameRecord._fields_])   # flacgpu_frame_record
+
+
+def scan_frames_host(data):
+    """flacgpu_scan_frames_host: the kept frames of a raw frame stream (bare frames, no fLaC marker, no STREAMINFO) by
+    the rule of DESIGN.md "Raw frame streams", on the host alone (no GPU needed).  Returns (frames, RawStream): a
+    structured array of FRAME_DTYPE records and the summary."""
+    L = _lib.lib()
+    data = bytes(data)
+    n, raw = C.c_uint32(0), _lib.RawStream()
+    rc = L.flacgpu_scan_frames_host(data, len(data), None, 0, C.byref(n), C.byref(raw))   # the count
+    if rc:
+        raise GpuError(rc, "flacgpu_scan_frames_host")
+    frames = np.zeros(n.value, dtype=FRAME_DTYPE)
+    rc = L.flacgpu_scan_frames_host(data, len(data), frames.ctypes.data_as(C.POINTER(_lib.FrameRecord)), n.value,
+                                    C.byref(n), C.byref(raw))
+    if rc:
+        raise GpuError(rc, "flacgpu_scan_frames_host")
+    return frames, raw
+
+
 class DecodedStream:
     """One stream of a decode_many batch: rc (what flacgpu_decode_stream returns for it), info (StreamInfo), offset
     (first element in the flat output) and pcm (a [samples, channels] view of the flat output, or the
@@ -459,6 +480,47 @@ class Decoder:
         if rc:
             raise GpuError(rc, "flacgpu_decoder_scan")
         return recs, total.value
+
+    def scan_frames(self, blobs):
+        """flacgpu_decoder_scan_frames: a batch of raw frame streams (bare frames, no metadata; a byte range of a
+        file).  Returns (records, total int32 samples of the uniform streams, raw, frames): `records` serve decode,
+        decode_as and decode_windows as scan's do, `raw` is the _lib.RawStream array, `frames` the structured array
+        (FRAME_DTYPE) of every kept frame of the batch, whose last out_offset + block_size * channels is the element
+        count decode_frames writes."""
+        L = _lib.lib()
+        blobs = [b if isinstance(b, bytes) else bytes(b) for b in blobs]
+        n = len(blobs)
+        ptrs = (C.c_void_p * max(n, 1))()
+        lens = (C.c_size_t * max(n, 1))()
+        keep = []
+        for i, b in enumerate(blobs):
+            cp = C.c_char_p(b)
+            keep.append(cp)
+            ptrs[i] = C.cast(cp, C.c_void_p).value
+            lens[i] = len(b)
+        recs = (_lib.DecodedStream * max(n, 1))()
+        raw = (_lib.RawStream * max(n, 1))()
+        n_frames, elements, total = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        rc = L.flacgpu_decoder_scan_frames(self._h, ptrs, lens, n, recs, raw, C.byref(n_frames), C.byref(elements),
+                                           C.byref(total))
+        if rc:
+            raise GpuError(rc, "flacgpu_decoder_scan_frames")
+        frames = np.zeros(n_frames.value, dtype=FRAME_DTYPE)
+        rc = L.flacgpu_decoder_frame_records(self._h, frames.ctypes.data_as(C.POINTER(_lib.FrameRecord)), frames.size)
+        if rc:
+            raise GpuError(rc, "flacgpu_decoder_frame_records")
+        self.raw_elements = elements.value
+        return recs, total.value, raw, frames
+
+    def decode_frames(self, out_ptr, out_cap, flags, frames):
+        """flacgpu_decoder_decode_frames: every kept frame of the raw scan into the int32 buffer at out_ptr (device or
+        host address); `frames` (the structured array scan_frames returned, or one of its size) gets the records with
+        status filled."""
+        rc = _lib.lib().flacgpu_decoder_decode_frames(self._h, out_ptr, out_cap, flags,
+                                                      frames.ctypes.data_as(C.POINTER(_lib.FrameRecord)), frames.size)
+        if rc:
+            raise GpuError(rc, "flacgpu_decoder_decode_frames")
+        return frames
 
     def decode(self, out_ptr, out_cap, flags, recs):
         """flacgpu_decoder_decode into the int32 buffer at out_ptr (device or host address)."""
@@ -573,8 +635,42 @@ def _decode_many_as(dec, recs, n, out, flags, dtype, layout, pad_to, pad_channel
     return buf, streams
 
 
+def decode_frames(blobs, device=-1, out="device", decoder=None):
+    """Decode every whole frame of a batch of raw frame streams (bare FLAC frames without metadata, as FlacStreamWriter
+    writes them, or a byte range cut out of a file) in one GPU call: flacgpu_decoder_scan_frames +
+    flacgpu_decoder_decode_frames.  The frames' sample rate, channels and sample size may differ from one to the next.
+
+    Returns (samples, frames, raw): `samples` is flat int32 -- a torch tensor on the GPU for out="device", a numpy array
+    for out="host" --, frame f being samples[out_offset : out_offset + block_size * channels] as [block_size, channels];
+    `frames` is a numpy structured array of the records (FRAME_DTYPE; status != 0: the frame did not decode and its
+    samples are undefined), ordered by input, then position; raw[i] is the _lib.RawStream summary of input i."""
+    if out not in ("device", "host"):
+        raise ValueError("out must be 'device' or 'host'")
+    if out == "device":
+        import torch
+
+        torch.cuda.init()   # torch's HIP runtime first, as in decode_many
+    own = decoder is None
+    dec = Decoder(device) if own else decoder
+    try:
+        _, _, raw, frames = dec.scan_frames(blobs)
+        total = dec.raw_elements
+        if out == "device":
+            dev = dec.device if dec.device >= 0 else torch.cuda.current_device()
+            flat = torch.empty(total, dtype=torch.int32, device=f"cuda:{dev}")
+            torch.cuda.synchronize(dev)
+            dec.decode_frames(flat.data_ptr() if total else None, total, _lib.DECODE_OUT_DEVICE, frames)
+        else:
+            flat = np.empty(total, dtype=np.int32)
+            dec.decode_frames(flat.ctypes.data if total else None, total, 0, frames)
+    finally:
+        if own:
+            dec.close()
+    return flat, frames, list(raw)[:len(blobs)]
+
+
 def decode_many(blobs, device=-1, out="device", verify_md5=True, decoder=None, dtype="int32", layout="flat",
-                pad_to=None, pad_channels=None):
+                pad_to=None, pad_channels=None, raw=False):
     """Decode many FLAC streams in one GPU call (flacgpu_decoder_scan + flacgpu_decoder_decode).
 
     Returns (flat, streams): `flat` holds every stream's interleaved int32 samples one after another -- a torch tensor
@@ -588,7 +684,12 @@ def decode_many(blobs, device=-1, out="device", verify_md5=True, decoder=None, d
     (sample * 2^-(bps - 1)) converts in the same kernel pass (flacgpu_decoder_decode_as).  layout="padded" returns
     (batch, streams): `batch` is [B, C, T], planar and zero-padded, with T = pad_to or the longest stream and C = pad_channels or the most channels;
     streams[i].pcm is the view batch[i, :channels, :decoded_samples], and the lengths vector a padded batch goes with
-    is [s.info.decoded_samples for s in streams].  A stream with rc != 0 is a row of zeros."""
+    is [s.info.decoded_samples for s in streams].  A stream with rc != 0 is a row of zeros.
+
+    raw=True takes the inputs as raw frame streams (no fLaC marker, no STREAMINFO; flacgpu_decoder_scan_frames): a stream
+    whose whole frames share one sample rate, channel count and sample size decodes as a regular one (md5_status 2:
+    there is no MD5 to compare with), one whose frames differ has rc -2 (decode_frames serves it), one without a whole
+    frame rc -1.  With decoder= the scan stays on the handle for a following decode_windows."""
     if out not in ("device", "host"):
         raise ValueError("out must be 'device' or 'host'")
     if dtype not in _DTYPES or layout not in ("flat", "padded"):
@@ -602,7 +703,7 @@ def decode_many(blobs, device=-1, out="device", verify_md5=True, decoder=None, d
     own = decoder is None
     dec = Decoder(device) if own else decoder
     try:
-        recs, total = dec.scan(blobs)
+        recs, total = dec.scan_frames(blobs)[:2] if raw else dec.scan(blobs)
         flags = 0 if verify_md5 else _lib.DECODE_NO_MD5
         if (dtype, layout) != ("int32", "flat"):
             return _decode_many_as(dec, recs, len(blobs), out, flags, dtype, layout, pad_to, pad_channels)

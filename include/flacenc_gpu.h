@@ -632,6 +632,64 @@ int flacgpu_decoder_decode_windows(flacgpu_decoder *d, void *out, size_t out_cap
 int flacgpu_window_frames(const uint32_t *frame_n, uint32_t n_frames, uint64_t start, uint64_t length, uint32_t *first,
                           uint32_t *count, uint64_t *skip);
 
+/* ---- batch decoder: raw frame streams (bare frames, no fLaC marker, no STREAMINFO) ----------------------------------
+ * What FlacStreamWriter / flacenc_stream_writer emits, and what a byte range cut out of the middle of a .flac file is:
+ * frames whose "subset" headers carry their own sample rate, channels and sample size, which may change from frame to
+ * frame.  The scan needs no metadata, skips to the first whole frame and resynchronises after damage (DESIGN.md 4b
+ * "Raw frame streams" states the rule): a position is a candidate when a frame header with a CRC-8 parses there and
+ * neither its sample-rate code nor its sample-size code is 0; a candidate's frame ends at the first later candidate
+ * at least header + 2 + channels bytes on that the frame's CRC-16 precedes, or with the input when its last two bytes
+ * are that CRC-16; a candidate without an end is passed over.  Bytes in no kept frame are skipped_bytes, each maximal
+ * run of them one gap.  A frame is recognised by the header behind it: damage to a frame's header also costs the frame
+ * in front of it.  A whole frame that is no candidate (its header leaves the rate or the sample size to a STREAMINFO)
+ * is never a record of its own, and it does not break the CRC-16 of what precedes it: the record of the frame in front
+ * runs on to the next candidate, so its `bytes` spans both frames, and decode_frames gives it status bit 0.
+ *   scan_frames_host  the rule on the host alone, one input, no device needed.  `frames` may be NULL (the count alone);
+ *                     with cap < *n_frames nothing is written and FLACGPU_ERR_BUFFER_TOO_SMALL returned.  len == 0 is
+ *                     valid (data may be NULL then): 0 frames.  stream and first_frame are 0.
+ *   scan_frames       the same frames for every input of a batch, found on the device; replaces the handle's scanned
+ *                     batch as scan does.  records are ordered by stream, then position; out_offset is the running sum
+ *                     of block_size * channels over the batch's kept frames, *total_elements its end.  raw[i] (may be
+ *                     NULL) summarises stream i.  streams[i] is filled so that decode, decode_as, plan_output,
+ *                     plan_windows and decode_windows work exactly as after scan: a UNIFORM stream (frames > 0, all of
+ *                     one sample rate, channel count and sample size) has rc FLACGPU_OK, info from its first frame (min /
+ *                     max block over its frames), total_samples 0 and md5 all zero (an MD5 pass reports md5_status 2 with
+ *                     decoded_md5 filled), bad_frames 0; a stream whose frames differ has rc FLACGPU_ERR_UNSUPPORTED,
+ *                     one without a kept frame FLACGPU_ERR_INVALID_ARG, and both are absent from those calls (zero rows,
+ *                     no samples).  out_offset and *total_samples lay out the uniform streams alone.
+ *   frame_records     the records of the last scan_frames (cap >= *total_frames, else FLACGPU_ERR_BUFFER_TOO_SMALL).
+ *   decode_frames     decodes EVERY kept frame of the batch, uniform stream or not: frame f is [block_size][channels]
+ *                     interleaved int32 at out_offset, in host memory or (FLACGPU_DECODE_OUT_DEVICE, the only flag)
+ *                     device memory.  records (cap entries, >= total_frames) receives the scan's records with status
+ *                     filled: bit 0 the frame did not parse, bit 1 its CRC-16 is wrong; the samples of such a frame are
+ *                     undefined.  A refused call (no raw scan, buffers too small, unknown flag) writes nothing.
+ * decode, decode_as, decode_windows and decode_frames may follow one another in any order on one scan_frames. */
+typedef struct {            /* 64 bytes */
+    uint64_t byte_offset;   /* first byte of the frame in its stream's input */
+    uint64_t number;        /* coded frame number (blocking 0) or sample number (blocking 1) */
+    uint64_t out_offset;    /* first element of the frame in decode_frames' output */
+    uint32_t stream, bytes; /* input index; header .. CRC-16 inclusive */
+    uint32_t block_size, sample_rate;
+    uint32_t channels, bits_per_sample;
+    uint32_t assignment, blocking;
+    uint32_t status, reserved; /* 0 after the scan; after decode_frames bit 0: did not parse, bit 1: CRC-16 wrong */
+} flacgpu_frame_record;
+typedef struct {            /* 32 bytes */
+    uint64_t first_frame;   /* index of the stream's first record */
+    uint64_t skipped_bytes;
+    uint32_t frames, gaps;
+    uint32_t uniform;       /* 1: frames > 0 and all share sample_rate, channels, bits_per_sample */
+    uint32_t reserved;
+} flacgpu_raw_stream;
+int flacgpu_scan_frames_host(const uint8_t *data, size_t len, flacgpu_frame_record *frames, size_t cap,
+                             uint32_t *n_frames, flacgpu_raw_stream *summary);
+int flacgpu_decoder_scan_frames(flacgpu_decoder *d, const uint8_t *const *data, const size_t *len, uint32_t n_streams,
+                                flacgpu_decoded_stream *streams, flacgpu_raw_stream *raw,
+                                uint64_t *total_frames, uint64_t *total_elements, uint64_t *total_samples);
+int flacgpu_decoder_frame_records(flacgpu_decoder *d, flacgpu_frame_record *records, size_t cap);
+int flacgpu_decoder_decode_frames(flacgpu_decoder *d, int32_t *out, size_t out_cap_elements, uint32_t flags,
+                                  flacgpu_frame_record *records, size_t cap);
+
 /* ---- the encoder's ingest pass: a device tensor -> interleaved int32 the encoder reads in place ----------------------
  * The device half of flacenc_encode_many_device (include/flacenc_stream.h), the mirror image of
  * flacgpu_decoder_decode_as: a batch of streams of one shape held in device memory as int32, int16, packed 24-bit or float32, planar and

@@ -11,6 +11,16 @@ over flacgpu_decode_stream and the oracle's CPU decoder on one core; writes prof
     python tools/decode_many_probe.py --formats --s24 [--out profiles/r12_s24.json] [--reps 15] [--shrink 4]
     python tools/decode_many_probe.py --windows [--workloads tracks,clips] [--out profiles/r10_decode_windows.json]
                                              [--reps 15] [--kernels-only]
+    python tools/decode_many_probe.py --raw --label this_1 [--out profiles/r13_raw_frames.json] [--reps 15]
+    python tools/decode_many_probe.py --raw --label parent --package-root DIR   (the regular leg only)
+    python tools/decode_many_probe.py --raw --label this_2          (in this order: this build, parent, this build)
+    python tools/decode_many_probe.py --raw --kernels-only          (one warm call per leg, for rocprofv3)
+
+--raw (flacgpu_decoder_scan_frames): on the clips, device output, no MD5, handle warm, the wall time of (regular) scan +
+decode of the files as they are and (raw) scan_frames + decode of the same files with the fLaC marker and metadata
+removed; both must give the same PCM, and its SHA-256 must be the same under every label.  Every leg reads the shader
+clock before and after.  The parent's build runs the regular leg alone; once this_1, parent and this_2 are in the file,
+`verdict` holds the parent's min-max spread (the allowance) and whether each of this build's medians lies inside it.
 
 --formats (flacgpu_decoder_decode_as): on the clips, device output, no MD5, handle warm, the wall time of one
 scan + decode call into (a) what a caller of flacgpu_decoder_decode does -- interleaved int32, then torch ops to the
@@ -310,6 +320,73 @@ def s24(args):
     print(json.dumps(rec, indent=1), flush=True)
 
 
+def raw_frames(args):
+    """The --raw leg (see the module docstring)."""
+    import hashlib
+
+    import torch
+
+    from flac_codec_amd import _lib
+    from flac_codec_amd.gpu import Decoder, decode_many, scan_stream_host
+
+    blobs = make_blobs("clips")
+    has_raw = hasattr(Decoder, "scan_frames") and args.label != "parent"
+    dec = Decoder(0)
+    legs = {"regular_scan_decode": lambda: decode_many(blobs, out="device", verify_md5=False, decoder=dec)[0]}
+    if has_raw:
+        bare = [b[int(scan_stream_host(b)[1][0]):] for b in blobs]   # from the first frame on
+        legs["raw_scan_frames_decode"] = lambda: decode_many(bare, out="device", verify_md5=False, decoder=dec,
+                                                             raw=True)[0]
+    if args.kernels_only:
+        for fn in legs.values():
+            fn()
+            fn()
+        torch.cuda.synchronize()
+        dec.close()
+        return
+    res = {"tool": "tools/decode_many_probe.py --raw", "workload": "clips: 1024 x 10 s, 16 kHz mono 16-bit",
+           "device_output": True, "md5": False, "order": [], "runs": {}}
+    if os.path.exists(args.out):
+        with open(args.out) as f:
+            res = json.load(f)
+    pcm = legs["regular_scan_decode"]()
+    rec = {"build_id": _lib.build_id(), "pcm_sha256": hashlib.sha256(pcm.cpu().numpy().tobytes()).hexdigest(),
+           "legs": {}}
+    if has_raw:
+        assert torch.equal(pcm, legs["raw_scan_frames_decode"]())   # identical PCM
+    for other in res["runs"].values():
+        assert other["pcm_sha256"] == rec["pcm_sha256"]             # and under every label
+    del pcm
+    for name, fn in legs.items():
+        fn()
+        torch.cuda.synchronize()   # warm: buffers grown, code loaded
+        sclk_before = _sclk_mhz()
+        times = []
+        for _ in range(args.reps):
+            t0 = time.perf_counter()
+            out = fn()
+            torch.cuda.synchronize()
+            times.append(time.perf_counter() - t0)
+        rec["legs"][name] = dict(_spread(times), sclk_mhz_before=sclk_before, sclk_mhz_after=_sclk_mhz())
+        del out
+    dec.close()
+    res["runs"][args.label] = rec
+    res["order"].append(args.label)
+    runs = res["runs"]
+    if all(k in runs for k in ("this_1", "parent", "this_2")):
+        allow = runs["parent"]["legs"]["regular_scan_decode"]
+        inside = lambda leg: allow["min_s"] <= leg["median_s"] <= allow["max_s"]   # noqa: E731
+        res["verdict"] = {"allowance_parent_min_s": allow["min_s"], "allowance_parent_max_s": allow["max_s"],
+                          "parent_median_s": allow["median_s"]}
+        for label in ("this_1", "this_2"):
+            for name, leg in runs[label]["legs"].items():
+                res["verdict"][f"{label}.{name}"] = {"median_s": leg["median_s"], "inside_parent_spread": inside(leg),
+                                                     "over_parent_median": leg["median_s"] / allow["median_s"]}
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps({args.label: rec, "verdict": res.get("verdict")}, indent=1), flush=True)
+
+
 def windows(args):
     """The --windows leg (see the module docstring)."""
     import torch
@@ -432,7 +509,7 @@ def merge_stats(args):
                                "avg_ms": float(r["AverageNs"]) / 1e6}
     mine = {k: v for k, v in rows.items() if any(s in k for s in ("k_scan_", "k_link", "k_decode_many", "k_frame_crc",
                                                                    "k_finish_many", "k_md5_many", "k_finish_as",
-                                                                   "k_pad_rows", "k_finish_window"))}
+                                                                   "k_pad_rows", "k_finish_window"))}   # (k_scan_ and k_link cover the raw kernels)
     res.setdefault("kernel_stats", {})[args.stats_label] = mine
     with open(args.out, "w") as f:
         json.dump(res, f, indent=1)
@@ -447,6 +524,7 @@ def main():
     ap.add_argument("--formats", action="store_true", help="the output-format leg: profiles/r09_decode_formats.json")
     ap.add_argument("--windows", action="store_true", help="the random-crop leg: profiles/r10_decode_windows.json")
     ap.add_argument("--s24", action="store_true", help="with --formats: the packed 24-bit leg, profiles/r12_s24.json")
+    ap.add_argument("--raw", action="store_true", help="the raw frame stream leg: profiles/r13_raw_frames.json")
     ap.add_argument("--shrink", type=int, default=1, help="--s24: divide the clip count")
     ap.add_argument("--label", default="this", help="--formats: the run's name in the file (parent: the default int32 "
                     "leg only; any other name: every leg)")
@@ -457,7 +535,8 @@ def main():
     ap.add_argument("--kernels-only", action="store_true", help="one warm decode per workload (for rocprofv3)")
     args = ap.parse_args()
     if not args.out:
-        args.out = os.path.join(ROOT, "profiles", "r10_decode_windows.json" if args.windows else
+        args.out = os.path.join(ROOT, "profiles", "r13_raw_frames.json" if args.raw else
+                                "r10_decode_windows.json" if args.windows else
                                 "r12_s24.json" if args.s24 else
                                 "r09_decode_formats.json" if args.formats else "r07_decode_many.json")
     if args.windows and args.workloads == "clips,tracks,hour":
@@ -469,6 +548,8 @@ def main():
     import torch
 
     torch.cuda.init()   # before the library's first HIP call (else torch sees no GPU)
+    if args.raw:
+        return raw_frames(args)
     if args.formats and args.s24:
         return s24(args)
     if args.formats:
