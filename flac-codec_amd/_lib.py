@@ -20,6 +20,8 @@ DECODE_NO_MD5 = 2
 SAMPLE_I32, SAMPLE_I16, SAMPLE_F32 = 0, 1, 2   # flacgpu_out_format.dtype
 SAMPLE_S24 = 24   # packed 3-byte little-endian elements
 LAYOUT_FLAT, LAYOUT_PADDED = 0, 1              # flacgpu_out_format.layout
+SCAN_SPECULATIVE = 1    # flacgpu_*_scan_frames*_ex flags: end a frame that no header ends by its own bits
+FRAME_SPECULATIVE = 1   # FrameRecord.reserved bit 0: the frame was ended that way
 
 
 class GpuOptions(C.Structure):
@@ -246,6 +248,11 @@ def _load():
     L.flacgpu_decoder_scan_frames.argtypes = [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_uint32,
                                               C.POINTER(DecodedStream), C.POINTER(RawStream), C.POINTER(C.c_uint64),
                                               C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.flacgpu_scan_frames_host_ex.argtypes = [C.c_char_p, C.c_size_t, C.c_uint32, C.POINTER(FrameRecord), C.c_size_t,
+                                              C.POINTER(C.c_uint32), C.POINTER(RawStream)]
+    L.flacgpu_decoder_scan_frames_ex.argtypes = [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_uint32, C.c_uint32,
+                                                 C.POINTER(DecodedStream), C.POINTER(RawStream), C.POINTER(C.c_uint64),
+                                                 C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.flacgpu_decoder_frame_records.argtypes = [vp, C.POINTER(FrameRecord), C.c_size_t]
     L.flacgpu_decoder_decode_frames.argtypes = [vp, vp, C.c_size_t, C.c_uint32, C.POINTER(FrameRecord), C.c_size_t]
     L.flacgpu_pack_plans.argtypes = [vp, ip, C.c_uint32, C.c_uint32, C.POINTER(FramePlan), C.POINTER(SubframePlan),

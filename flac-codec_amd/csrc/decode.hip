@@ -81,11 +81,16 @@ int flacgpu_scan_stream_host(const uint8_t *data, size_t len, flacgpu_stream_inf
 // The raw-frame rule (host/flac_stream.cpp scan_raw_frames) for one input, without a device.
 int flacgpu_scan_frames_host(const uint8_t *data, size_t len, flacgpu_frame_record *frames, size_t cap,
                              uint32_t *n_frames, flacgpu_raw_stream *summary) {
-    if ((!data && len) || !n_frames || !summary) return FLACGPU_ERR_INVALID_ARG;
+    return flacgpu_scan_frames_host_ex(data, len, 0, frames, cap, n_frames, summary);
+}
+
+int flacgpu_scan_frames_host_ex(const uint8_t *data, size_t len, uint32_t flags, flacgpu_frame_record *frames, size_t cap,
+                                uint32_t *n_frames, flacgpu_raw_stream *summary) {
+    if ((!data && len) || !n_frames || !summary || (flags & ~FLACGPU_SCAN_SPECULATIVE)) return FLACGPU_ERR_INVALID_ARG;
     *n_frames = 0;
     std::vector<flacgpu_frame_record> found;
     flacgpu_raw_stream sum{};
-    flacenc::scan_raw_frames(data, len, found, sum);
+    flacenc::scan_raw_frames(data, len, flags, found, sum);
     *n_frames = sum.frames;
     if (frames && cap < found.size()) {
         g_last_error = "output buffer too small";

@@ -4,6 +4,7 @@
 // and kernels/decode_many.inc (decode, CRC-16, finish, MD5); the subframe decoder is decode.inc's, unchanged.
 #include "kernels/types.h"
 #include "kernels/sample_types.h"
+#include "kernels/frame_extent.h"
 #include "flac_stream.h"
 
 #include <stdlib.h>
@@ -19,9 +20,15 @@ namespace {
 #include "kernels/decode.inc"
 #include "kernels/crc16.inc"
 #include "kernels/frame_scan.inc"
+#include "kernels/spec_end.inc"
 #include "kernels/decode_many.inc"
 
 constexpr uint32_t kSlotTail = 64;   // zero bytes behind every stream's region (at least)
+// k_scan_blocks reads 16 bytes of look-ahead behind a block, and k_scan_emit (slot_pend) and k_spec_end (the CRC test of
+// an extent that ends with the region) take the prefix of the block that holds the region's END: with a tail of at
+// least one block that block lies inside the stream's own slot, its prefix covers the slot's bytes alone, and the
+// bit reader's cap (the slot's end - 4) lies in zeros.
+static_assert(kSlotTail >= 64, "the block behind a region's last byte must belong to the region's slot");
 
 // a buffer that only grows: device memory, or pinned host memory
 template <bool PINNED> struct GrowBuf {
@@ -49,6 +56,7 @@ struct flacgpu_decoder {
     GrowBuf<true> staging;   // pinned: the batch buffer on its way up
     DevBuf bytes, slots, mask, plocal, wg_cnt, wg_tail, wg_off, wg_carry;
     DevBuf cand_pos, cand_info, cand_crc, cand_slot, slot_cand0, slot_pend, link;
+    DevBuf spec_len;   // FLACGPU_SCAN_SPECULATIVE alone: allocated by the first scan that asks for it
     DevBuf frames, scratch, codes, counts, jobs, digest, out_stage;
     DevBuf md5_stage, pad_out, pad_streams;   // decode_as: interleaved int32 for the MD5, padded layout tables
     DevBuf win_frames, win_desc;              // decode_windows: the selected frames (d->frames stays the scan's)
@@ -79,11 +87,12 @@ struct flacgpu_decoder {
 namespace {
 // The device half of a scan: uploads every slot's bytes in one copy (zero tails, 64 bytes of look-ahead) and runs the
 // scan kernels; leaves the candidates' positions, records and links and every slot's first candidate on the host.
-// `at` = the end of the last slot.  raw: the scan of raw frame streams (k_scan_subset, k_link_raw).
+// `at` = the end of the last slot.  raw: the scan of raw frame streams (k_scan_subset, k_link_raw).  cspec (raw, under
+// FLACGPU_SCAN_SPECULATIVE; else null): the own extents of the candidates without a link (k_spec_end), 0: none.
 int device_scan(flacgpu_decoder *d, const uint8_t *const *data, const std::vector<ScanSlot> &slots,
                 const std::vector<size_t> &region_at, const std::vector<uint32_t> &slot_stream, uint64_t at, bool raw,
                 std::vector<uint64_t> &cpos, std::vector<uint32_t> &cinfo, std::vector<int32_t> &clink,
-                std::vector<uint32_t> &cand0, uint32_t *n_cand_out) {
+                std::vector<uint32_t> &cand0, uint32_t *n_cand_out, std::vector<uint32_t> *cspec = nullptr) {
     const uint32_t S = (uint32_t)slots.size();
     const std::string who = raw ? "flacgpu_decoder_scan_frames" : "flacgpu_decoder_scan";
     // the bit reader indexes dwords with 32 bits
@@ -143,6 +152,8 @@ int device_scan(flacgpu_decoder *d, const uint8_t *const *data, const std::vecto
     if (int rc = d->cand_crc.ensure(4 * nc)) return rc;
     if (int rc = d->cand_slot.ensure(4 * nc)) return rc;
     if (int rc = d->link.ensure(4 * nc)) return rc;
+    if (cspec)
+        if (int rc = d->spec_len.ensure(4 * nc)) return rc;
     p.cand_pos = d->cand_pos.as<uint64_t>();
     p.cand_info = d->cand_info.as<uint32_t>();
     p.cand_crc = d->cand_crc.as<uint32_t>();
@@ -152,11 +163,14 @@ int device_scan(flacgpu_decoder *d, const uint8_t *const *data, const std::vecto
     hipLaunchKernelGGL(k_scan_emit, dim3(n_wg), dim3(WG), 0, d->st, p);
     if (n_cand && raw) hipLaunchKernelGGL(k_link_raw, dim3((n_cand + WG - 1) / WG), dim3(WG), 0, d->st, p);
     else if (n_cand) hipLaunchKernelGGL(k_link, dim3((n_cand + WG - 1) / WG), dim3(WG), 0, d->st, p);
+    if (n_cand && cspec)
+        hipLaunchKernelGGL(k_spec_end, dim3((n_cand + 63) / 64), dim3(64), 0, d->st, p, d->spec_len.as<uint32_t>());
     HIP_TRY(hipGetLastError());
     try {
         cpos.resize(n_cand);
         cinfo.resize(n_cand);
         clink.resize(n_cand);
+        if (cspec) cspec->resize(n_cand);
     } catch (const std::bad_alloc &) {
         g_last_error = who + ": out of host memory";
         return FLACGPU_ERR_UNSUPPORTED;
@@ -165,6 +179,8 @@ int device_scan(flacgpu_decoder *d, const uint8_t *const *data, const std::vecto
         HIP_TRY(hipMemcpyAsync(cpos.data(), p.cand_pos, 8 * (size_t)n_cand, hipMemcpyDeviceToHost, d->st));
         HIP_TRY(hipMemcpyAsync(cinfo.data(), p.cand_info, 4 * (size_t)n_cand, hipMemcpyDeviceToHost, d->st));
         HIP_TRY(hipMemcpyAsync(clink.data(), p.link, 4 * (size_t)n_cand, hipMemcpyDeviceToHost, d->st));
+        if (cspec)   // with the links, in the same submission
+            HIP_TRY(hipMemcpyAsync(cspec->data(), d->spec_len.p, 4 * (size_t)n_cand, hipMemcpyDeviceToHost, d->st));
     }
     HIP_TRY(hipMemcpyAsync(cand0.data(), p.slot_cand0, 4 * (size_t)S, hipMemcpyDeviceToHost, d->st));
     HIP_TRY(hipStreamSynchronize(d->st));
@@ -275,11 +291,13 @@ int scan_impl(flacgpu_decoder *d, const uint8_t *const *data, const size_t *len,
 }
 
 // flacgpu_decoder_scan_frames behind its argument checks: a slot is a whole input, the device finds the candidates and
-// their ends by the raw rule, and the host walks them with a cursor (DESIGN.md "Raw frame streams").
-int scan_raw_impl(flacgpu_decoder *d, const uint8_t *const *data, const size_t *len, uint32_t n) {
+// their ends by the raw rule, and the host walks them with a cursor (DESIGN.md "Raw frame streams").  Under
+// FLACGPU_SCAN_SPECULATIVE a candidate without a link ends where its own extent does, if it has one.
+int scan_raw_impl(flacgpu_decoder *d, const uint8_t *const *data, const size_t *len, uint32_t n, uint32_t flags) {
+    const bool spec = flags & FLACGPU_SCAN_SPECULATIVE;
     std::vector<ScanSlot> slots;
     std::vector<size_t> region_at;
-    std::vector<uint32_t> slot_stream, cinfo, cand0;
+    std::vector<uint32_t> slot_stream, cinfo, cand0, cspec;
     std::vector<uint64_t> cpos;
     std::vector<int32_t> clink;
     uint64_t at = 0;
@@ -310,7 +328,8 @@ int scan_raw_impl(flacgpu_decoder *d, const uint8_t *const *data, const size_t *
     d->n_slots = S;
     uint32_t n_cand = 0;
     if (S)
-        if (int rc = device_scan(d, data, slots, region_at, slot_stream, at, true, cpos, cinfo, clink, cand0, &n_cand))
+        if (int rc = device_scan(d, data, slots, region_at, slot_stream, at, true, cpos, cinfo, clink, cand0, &n_cand,
+                                 spec ? &cspec : nullptr))
             return rc;
     // ---- host walk, stream by stream: the candidates in ascending order, those below the cursor ignored, one without
     // an end passed over, one with an end kept and the cursor moved to that end.  A kept frame's record is read from
@@ -335,8 +354,9 @@ int scan_raw_impl(flacgpu_decoder *d, const uint8_t *const *data, const size_t *
                 const uint64_t slot_end = (uint32_t)s + 1 < S ? slots[s + 1].base : at;
                 uint64_t cursor = sl.base;
                 for (uint32_t c = cand0[s]; c < c_end; c++) {
-                    if (cpos[c] < cursor || clink[c] == LINK_NONE) continue;
-                    const uint64_t end = clink[c] == LINK_END ? sl.base + sl.len : cpos[clink[c]];
+                    const bool own = clink[c] == LINK_NONE && spec && cspec[c];
+                    if (cpos[c] < cursor || (clink[c] == LINK_NONE && !own)) continue;
+                    const uint64_t end = own ? cpos[c] + cspec[c] : clink[c] == LINK_END ? sl.base + sl.len : cpos[clink[c]];
                     flacenc::HostFrameInfo h;   // the header was accepted by K_s1: its record, and the rest from its bytes
                     h.n = (cinfo[c] & 0xFFFFu) + 1u;
                     h.header_bytes = (cinfo[c] >> 16) & 0xFFu;
@@ -356,6 +376,7 @@ int scan_raw_impl(flacgpu_decoder *d, const uint8_t *const *data, const size_t *
                     f.bits_per_sample = h.bits_per_sample;
                     f.assignment = h.acode;
                     f.blocking = h.blocking;
+                    f.reserved = own ? FLACGPU_FRAME_SPECULATIVE : 0u;
                     ManyFrame m{};
                     m.start = cpos[c];
                     m.end = end;
@@ -847,11 +868,19 @@ int flacgpu_decoder_scan(flacgpu_decoder *d, const uint8_t *const *data, const s
 int flacgpu_decoder_scan_frames(flacgpu_decoder *d, const uint8_t *const *data, const size_t *len, uint32_t n_streams,
                                 flacgpu_decoded_stream *streams, flacgpu_raw_stream *raw, uint64_t *total_frames,
                                 uint64_t *total_elements, uint64_t *total_samples) {
-    if (!d || (n_streams && (!data || !len || !streams)) || !total_frames || !total_elements || !total_samples)
+    return flacgpu_decoder_scan_frames_ex(d, data, len, n_streams, 0, streams, raw, total_frames, total_elements,
+                                          total_samples);
+}
+
+int flacgpu_decoder_scan_frames_ex(flacgpu_decoder *d, const uint8_t *const *data, const size_t *len, uint32_t n_streams,
+                                   uint32_t flags, flacgpu_decoded_stream *streams, flacgpu_raw_stream *raw,
+                                   uint64_t *total_frames, uint64_t *total_elements, uint64_t *total_samples) {
+    if (!d || (n_streams && (!data || !len || !streams)) || !total_frames || !total_elements || !total_samples ||
+        (flags & ~FLACGPU_SCAN_SPECULATIVE))
         return FLACGPU_ERR_INVALID_ARG;
     d->scanned = d->raw = false;
     DeviceGuard guard(d->device);
-    if (int rc = scan_raw_impl(d, data, len, n_streams)) return rc;
+    if (int rc = scan_raw_impl(d, data, len, n_streams, flags)) return rc;
     index_frames(d);
     d->scanned = d->raw = true;
     if (n_streams) memcpy(streams, d->res.data(), sizeof(flacgpu_decoded_stream) * n_streams);

@@ -3,9 +3,49 @@
 #include <algorithm>
 #include <cstring>
 
+#include "../kernels/frame_extent.h"
 #include "checksums.h"
 
 namespace flacenc {
+namespace {
+// frame_extent's bit source over data[0, len): MSB first, the bytes behind `len` read as 0
+struct ByteBits {
+    const uint8_t *d;
+    size_t len;
+    uint64_t p = 0;
+    uint32_t byte(size_t i) const { return i < len ? d[i] : 0u; }
+    uint32_t pos() const { return (uint32_t)p; }
+    void seek(uint32_t bit) { p = bit; }
+    uint32_t get(uint32_t n) {   // 1 <= n <= 32: five bytes hold the 7 odd bits in front and the n
+        const size_t b = (size_t)(p >> 3);
+        uint64_t v = 0;
+        for (size_t i = 0; i < 5; i++) v = v << 8 | byte(b + i);
+        v = (v >> (40 - (uint32_t)(p & 7) - n)) & (((uint64_t)1 << n) - 1);
+        p += n;
+        return (uint32_t)v;
+    }
+    uint32_t zeros(uint32_t limit) {
+        uint32_t q = 0;
+        for (;;) {
+            const uint32_t odd = (uint32_t)(p & 7);
+            const uint32_t cur = (byte((size_t)(p >> 3)) << odd) & 0xFFu;
+            if (cur) {
+                const uint32_t z = (uint32_t)__builtin_clz(cur) - 24u;
+                p += z + 1;
+                return q + z;
+            }
+            q += 8 - odd;
+            p += 8 - odd;
+            if (p > limit) return q;   // no 1 bit inside the window
+        }
+    }
+    void rice(uint32_t k, uint32_t limit) {
+        zeros(limit);
+        p += k;
+    }
+};
+}  // namespace
+
 const char *parse_metadata(const uint8_t *data, size_t len, flacgpu_stream_info *info, uint32_t *min_frame,
                            size_t *frames_at) {
     memset(info, 0, sizeof *info);
@@ -134,7 +174,18 @@ void summarise_raw_frames(const flacgpu_frame_record *frames, size_t n, size_t l
     }
 }
 
-void scan_raw_frames(const uint8_t *data, size_t len, std::vector<flacgpu_frame_record> &frames,
+size_t raw_frame_extent(const uint8_t *data, size_t len, const HostFrameInfo &h) {
+    const uint16_t *const T = crc16_table();
+    ByteBits bits{data, len};
+    const size_t e = frame_extent(bits, h.header_bytes, h.n, h.acode, h.bits_per_sample,
+                                  std::min<uint64_t>(len, kFrameExtentWindow));
+    if (!e) return 0;
+    uint16_t crc = 0;
+    for (size_t i = 0; i < e; i++) crc = crc16_step(T, crc, data[i]);   // e <= the window <= len
+    return crc == 0 ? e : 0;
+}
+
+void scan_raw_frames(const uint8_t *data, size_t len, uint32_t flags, std::vector<flacgpu_frame_record> &frames,
                      flacgpu_raw_stream &summary) {
     const uint16_t *const T = crc16_table();
     // the candidates: a header that parses, with a sample rate and a sample size of its own
@@ -166,6 +217,13 @@ void scan_raw_frames(const uint8_t *data, size_t len, std::vector<flacgpu_frame_
             for (; at < len; at++) crc = crc16_step(T, crc, data[at]);
             if (len - s >= 2 && crc == 0) end = len;
         }
+        uint32_t own = 0;
+        if (!end && (flags & FLACGPU_SCAN_SPECULATIVE)) {   // no header ends it: its own extent
+            if (const size_t e = raw_frame_extent(data + s, len - s, h)) {
+                end = s + e;
+                own = FLACGPU_FRAME_SPECULATIVE;
+            }
+        }
         if (!end) continue;   // no end: passed over, the walk goes on behind it
         flacgpu_frame_record f{};
         f.byte_offset = s;
@@ -178,6 +236,7 @@ void scan_raw_frames(const uint8_t *data, size_t len, std::vector<flacgpu_frame_
         f.bits_per_sample = h.bits_per_sample;
         f.assignment = h.acode;
         f.blocking = h.blocking;
+        f.reserved = own;
         frames.push_back(f);
         out += (uint64_t)h.n * h.channels;
         cursor = end;

@@ -46,9 +46,14 @@ void scan_frames(const uint8_t *data, size_t len, size_t pos, uint32_t min_frame
 
 // The kept frames of a raw frame stream data[0, len) -- bare frames, no fLaC marker, no STREAMINFO -- by the rule of
 // DESIGN.md "Raw frame streams": `frames` gets one record per kept frame in position order (stream 0, out_offset the
-// running sum of block_size * channels, status 0), `summary` the counts (first_frame 0).
-void scan_raw_frames(const uint8_t *data, size_t len, std::vector<flacgpu_frame_record> &frames,
+// running sum of block_size * channels, status 0), `summary` the counts (first_frame 0).  flags: FLACGPU_SCAN_SPECULATIVE
+// gives a candidate that no header and not the input's end ends its own extent (raw_frame_extent); such a record has
+// FLACGPU_FRAME_SPECULATIVE in `reserved`.
+void scan_raw_frames(const uint8_t *data, size_t len, uint32_t flags, std::vector<flacgpu_frame_record> &frames,
                      flacgpu_raw_stream &summary);
+// The length of the frame at data[0] with the accepted header `h`, found by its own bits (kernels/frame_extent.h) inside
+// min(len, 4 MiB) and confirmed by its CRC-16; 0: none.  Every read is bounded by len.
+size_t raw_frame_extent(const uint8_t *data, size_t len, const HostFrameInfo &h);
 // `summary`'s frames, uniform flag, skipped_bytes and gaps from the stream's kept frames (first_frame is left alone)
 void summarise_raw_frames(const flacgpu_frame_record *frames, size_t n, size_t len, flacgpu_raw_stream &summary);
 

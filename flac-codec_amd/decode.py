@@ -77,17 +77,21 @@ class FlacStreamReader:
     """Reads the frames of a raw frame stream -- what encode.FlacStreamWriter writes: bare subset frames, no fLaC marker,
     no STREAMINFO -- one FrameBuf per read() (decode.rs:1142 FlacStreamReader).  The whole input is decoded in one GPU
     batch on first use.  Frames are found by the rule of DESIGN.md "Raw frame streams": bytes that belong to no whole
-    frame are skipped, where the reference reports an error at the point of damage."""
+    frame are skipped, where the reference reports an error at the point of damage.  speculative=True ends a frame that
+    no header ends by its own bits (FLACGPU_SCAN_SPECULATIVE): as the reference does, a frame is then decoded from its
+    own bits and kept when the header behind it is damaged or cut off."""
 
-    def __init__(self, data, device=-1):
+    def __init__(self, data, device=-1, speculative=False):
         self._data = data.read() if hasattr(data, "read") else bytes(data)
         self._device = device
+        self._speculative = speculative
         self._frames = None
         self._next = 0
 
     def _decode(self):
         if self._frames is None:
-            self._pcm, self._frames, raw = gpu.decode_frames([self._data], device=self._device, out="host")
+            self._pcm, self._frames, raw = gpu.decode_frames([self._data], device=self._device, out="host",
+                                                              speculative=self._speculative)
             self._skipped_bytes, self._gaps = int(raw[0].skipped_bytes), int(raw[0].gaps)
             self._data = None
 

@@ -411,21 +411,23 @@ def scan_stream_host(data):
 FRAME_DTYPE = np.dtype([(name, np.dtype(ct).str) for name, ct in _lib.FrameRecord._fields_])   # flacgpu_frame_record
 
 
-def scan_frames_host(data):
-    """flacgpu_scan_frames_host: the kept frames of a raw frame stream (bare frames, no fLaC marker, no STREAMINFO) by
+def scan_frames_host(data, speculative=False):
+    """flacgpu_scan_frames_host_ex: the kept frames of a raw frame stream (bare frames, no fLaC marker, no STREAMINFO) by
     the rule of DESIGN.md "Raw frame streams", on the host alone (no GPU needed).  Returns (frames, RawStream): a
-    structured array of FRAME_DTYPE records and the summary."""
+    structured array of FRAME_DTYPE records and the summary.  speculative=True (FLACGPU_SCAN_SPECULATIVE): a frame that
+    no header ends is ended by its own bits, and its record has _lib.FRAME_SPECULATIVE in `reserved`."""
     L = _lib.lib()
     data = bytes(data)
+    flags = _lib.SCAN_SPECULATIVE if speculative else 0
     n, raw = C.c_uint32(0), _lib.RawStream()
-    rc = L.flacgpu_scan_frames_host(data, len(data), None, 0, C.byref(n), C.byref(raw))   # the count
+    rc = L.flacgpu_scan_frames_host_ex(data, len(data), flags, None, 0, C.byref(n), C.byref(raw))   # the count
     if rc:
-        raise GpuError(rc, "flacgpu_scan_frames_host")
+        raise GpuError(rc, "flacgpu_scan_frames_host_ex")
     frames = np.zeros(n.value, dtype=FRAME_DTYPE)
-    rc = L.flacgpu_scan_frames_host(data, len(data), frames.ctypes.data_as(C.POINTER(_lib.FrameRecord)), n.value,
-                                    C.byref(n), C.byref(raw))
+    rc = L.flacgpu_scan_frames_host_ex(data, len(data), flags, frames.ctypes.data_as(C.POINTER(_lib.FrameRecord)),
+                                       n.value, C.byref(n), C.byref(raw))
     if rc:
-        raise GpuError(rc, "flacgpu_scan_frames_host")
+        raise GpuError(rc, "flacgpu_scan_frames_host_ex")
     return frames, raw
 
 
@@ -481,12 +483,13 @@ class Decoder:
             raise GpuError(rc, "flacgpu_decoder_scan")
         return recs, total.value
 
-    def scan_frames(self, blobs):
-        """flacgpu_decoder_scan_frames: a batch of raw frame streams (bare frames, no metadata; a byte range of a
+    def scan_frames(self, blobs, speculative=False):
+        """flacgpu_decoder_scan_frames_ex: a batch of raw frame streams (bare frames, no metadata; a byte range of a
         file).  Returns (records, total int32 samples of the uniform streams, raw, frames): `records` serve decode,
         decode_as and decode_windows as scan's do, `raw` is the _lib.RawStream array, `frames` the structured array
         (FRAME_DTYPE) of every kept frame of the batch, whose last out_offset + block_size * channels is the element
-        count decode_frames writes."""
+        count decode_frames writes.  speculative=True (FLACGPU_SCAN_SPECULATIVE): a frame that no header ends is ended
+        by its own bits, and its record has _lib.FRAME_SPECULATIVE in `reserved`."""
         L = _lib.lib()
         blobs = [b if isinstance(b, bytes) else bytes(b) for b in blobs]
         n = len(blobs)
@@ -501,10 +504,10 @@ class Decoder:
         recs = (_lib.DecodedStream * max(n, 1))()
         raw = (_lib.RawStream * max(n, 1))()
         n_frames, elements, total = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-        rc = L.flacgpu_decoder_scan_frames(self._h, ptrs, lens, n, recs, raw, C.byref(n_frames), C.byref(elements),
-                                           C.byref(total))
+        rc = L.flacgpu_decoder_scan_frames_ex(self._h, ptrs, lens, n, _lib.SCAN_SPECULATIVE if speculative else 0, recs,
+                                              raw, C.byref(n_frames), C.byref(elements), C.byref(total))
         if rc:
-            raise GpuError(rc, "flacgpu_decoder_scan_frames")
+            raise GpuError(rc, "flacgpu_decoder_scan_frames_ex")
         frames = np.zeros(n_frames.value, dtype=FRAME_DTYPE)
         rc = L.flacgpu_decoder_frame_records(self._h, frames.ctypes.data_as(C.POINTER(_lib.FrameRecord)), frames.size)
         if rc:
@@ -635,7 +638,7 @@ def _decode_many_as(dec, recs, n, out, flags, dtype, layout, pad_to, pad_channel
     return buf, streams
 
 
-def decode_frames(blobs, device=-1, out="device", decoder=None):
+def decode_frames(blobs, device=-1, out="device", decoder=None, speculative=False):
     """Decode every whole frame of a batch of raw frame streams (bare FLAC frames without metadata, as FlacStreamWriter
     writes them, or a byte range cut out of a file) in one GPU call: flacgpu_decoder_scan_frames +
     flacgpu_decoder_decode_frames.  The frames' sample rate, channels and sample size may differ from one to the next.
@@ -643,7 +646,8 @@ def decode_frames(blobs, device=-1, out="device", decoder=None):
     Returns (samples, frames, raw): `samples` is flat int32 -- a torch tensor on the GPU for out="device", a numpy array
     for out="host" --, frame f being samples[out_offset : out_offset + block_size * channels] as [block_size, channels];
     `frames` is a numpy structured array of the records (FRAME_DTYPE; status != 0: the frame did not decode and its
-    samples are undefined), ordered by input, then position; raw[i] is the _lib.RawStream summary of input i."""
+    samples are undefined), ordered by input, then position; raw[i] is the _lib.RawStream summary of input i.
+    speculative=True scans with FLACGPU_SCAN_SPECULATIVE (Decoder.scan_frames)."""
     if out not in ("device", "host"):
         raise ValueError("out must be 'device' or 'host'")
     if out == "device":
@@ -653,7 +657,7 @@ def decode_frames(blobs, device=-1, out="device", decoder=None):
     own = decoder is None
     dec = Decoder(device) if own else decoder
     try:
-        _, _, raw, frames = dec.scan_frames(blobs)
+        _, _, raw, frames = dec.scan_frames(blobs, speculative)
         total = dec.raw_elements
         if out == "device":
             dev = dec.device if dec.device >= 0 else torch.cuda.current_device()
@@ -670,7 +674,7 @@ def decode_frames(blobs, device=-1, out="device", decoder=None):
 
 
 def decode_many(blobs, device=-1, out="device", verify_md5=True, decoder=None, dtype="int32", layout="flat",
-                pad_to=None, pad_channels=None, raw=False):
+                pad_to=None, pad_channels=None, raw=False, speculative=False):
     """Decode many FLAC streams in one GPU call (flacgpu_decoder_scan + flacgpu_decoder_decode).
 
     Returns (flat, streams): `flat` holds every stream's interleaved int32 samples one after another -- a torch tensor
@@ -689,13 +693,16 @@ def decode_many(blobs, device=-1, out="device", verify_md5=True, decoder=None, d
     raw=True takes the inputs as raw frame streams (no fLaC marker, no STREAMINFO; flacgpu_decoder_scan_frames): a stream
     whose whole frames share one sample rate, channel count and sample size decodes as a regular one (md5_status 2:
     there is no MD5 to compare with), one whose frames differ has rc -2 (decode_frames serves it), one without a whole
-    frame rc -1.  With decoder= the scan stays on the handle for a following decode_windows."""
+    frame rc -1.  With decoder= the scan stays on the handle for a following decode_windows.  speculative=True (with
+    raw=True alone) scans with FLACGPU_SCAN_SPECULATIVE: a frame whose successor's header is damaged or cut off is kept."""
     if out not in ("device", "host"):
         raise ValueError("out must be 'device' or 'host'")
     if dtype not in _DTYPES or layout not in ("flat", "padded"):
         raise ValueError("dtype must be 'int32', 'int16', 'int24' or 'float32' and layout 'flat' or 'padded'")
     if layout == "flat" and (pad_to is not None or pad_channels is not None):
         raise ValueError("pad_to and pad_channels go with layout='padded'")
+    if speculative and not raw:
+        raise ValueError("speculative goes with raw=True")
     if out == "device":
         import torch
 
@@ -703,7 +710,7 @@ def decode_many(blobs, device=-1, out="device", verify_md5=True, decoder=None, d
     own = decoder is None
     dec = Decoder(device) if own else decoder
     try:
-        recs, total = dec.scan_frames(blobs)[:2] if raw else dec.scan(blobs)
+        recs, total = dec.scan_frames(blobs, speculative)[:2] if raw else dec.scan(blobs)
         flags = 0 if verify_md5 else _lib.DECODE_NO_MD5
         if (dtype, layout) != ("int32", "flat"):
             return _decode_many_as(dec, recs, len(blobs), out, flags, dtype, layout, pad_to, pad_channels)

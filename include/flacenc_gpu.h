@@ -663,7 +663,36 @@ int flacgpu_window_frames(const uint32_t *frame_n, uint32_t n_frames, uint64_t s
  *                     device memory.  records (cap entries, >= total_frames) receives the scan's records with status
  *                     filled: bit 0 the frame did not parse, bit 1 its CRC-16 is wrong; the samples of such a frame are
  *                     undefined.  A refused call (no raw scan, buffers too small, unknown flag) writes nothing.
- * decode, decode_as, decode_windows and decode_frames may follow one another in any order on one scan_frames. */
+ * decode, decode_as, decode_windows and decode_frames may follow one another in any order on one scan_frames.
+ *
+ * scan_frames_host_ex / scan_frames_ex take `flags`: 0 makes them the two functions above (which call them with 0), an
+ * unknown flag gives FLACGPU_ERR_INVALID_ARG and nothing is written.  FLACGPU_SCAN_SPECULATIVE changes one step of the
+ * rule: a candidate s that has no end by the two tests above is not passed over at once but gets its OWN EXTENT, found
+ * from its own bits (DESIGN.md 4b "A frame's own extent"; csrc/kernels/frame_extent.h):
+ *   window     W = min(len - s, 2^22) bytes; bit positions count from s, and a read that would pass bit 8 W means no
+ *              extent.  4 MiB holds any frame of 8 channels x 65535 samples x 32 bits coded VERBATIM; a frame larger
+ *              than that is not found by its own bits.
+ *   subframes  from bit 8 * header_bytes(s), with n, the assignment, channels and bps of s's own header; per coded
+ *              channel sbps = bps (+ 1 for the side channel: assignment 8 channel 1, 9 channel 0, 10 channel 1): a pad
+ *              bit that must be 0, 6 bits of type, a wasted flag; if set, wasted = the zeros before the next 1 bit, + 1,
+ *              and wasted >= sbps fails; eb = sbps - wasted.
+ *   bodies     type 0: eb bits; type 1: n * eb bits; types 8-12: order = type - 8, types 32-63: order = type - 31, every
+ *              other type fails; order > n fails; order * eb bits of warm-up; LPC only: 4 bits precision - 1 (precision
+ *              16 fails), 5 bits of signed shift (negative fails), order * precision bits.
+ *   residual   2 bits method (> 1 fails), 4 bits po; plen = n >> po, failing when plen < order or (plen << po) != n; per
+ *              partition a parameter of 4 (method 0) or 5 (method 1) bits; all ones is an escape: 5 bits w, then
+ *              count * w bits; otherwise count Rice codes (zeros, a 1, parameter bits); count = plen, less order in the
+ *              first partition.
+ *   frame end  the bits up to the next byte boundary must be 0, then 16 bits follow: e = s + pos / 8, and [s, e) is the
+ *              extent if its CRC-16, stored CRC included, is 0.
+ * These are the tests under which decode_frames accepts a frame, with the end unknown: a frame kept this way never gets
+ * status bit 0.  It is a kept frame [s, e) like any other, the cursor moves to e, and its record has
+ * FLACGPU_FRAME_SPECULATIVE in `reserved`.  A candidate that has an end by the two tests keeps that end (the whole
+ * non-subset frame swallowed by the frame in front stays as described), and everything else -- candidates, minimum
+ * distance, the walk, skipped_bytes, gaps, uniform -- stands.  Damage to a frame's header then costs that frame alone,
+ * and the last whole frame of a byte range is kept when less than a header of the next one follows. */
+#define FLACGPU_SCAN_SPECULATIVE 1u  /* scan flag: end a frame that no header ends by its own bits */
+#define FLACGPU_FRAME_SPECULATIVE 1u /* flacgpu_frame_record.reserved bit 0: the frame was ended by its own bits */
 typedef struct {            /* 64 bytes */
     uint64_t byte_offset;   /* first byte of the frame in its stream's input */
     uint64_t number;        /* coded frame number (blocking 0) or sample number (blocking 1) */
@@ -672,7 +701,8 @@ typedef struct {            /* 64 bytes */
     uint32_t block_size, sample_rate;
     uint32_t channels, bits_per_sample;
     uint32_t assignment, blocking;
-    uint32_t status, reserved; /* 0 after the scan; after decode_frames bit 0: did not parse, bit 1: CRC-16 wrong */
+    uint32_t status, reserved; /* 0 after the scan; after decode_frames bit 0: did not parse, bit 1: CRC-16 wrong;
+                                * reserved: 0, or FLACGPU_FRAME_SPECULATIVE under FLACGPU_SCAN_SPECULATIVE */
 } flacgpu_frame_record;
 typedef struct {            /* 32 bytes */
     uint64_t first_frame;   /* index of the stream's first record */
@@ -686,6 +716,11 @@ int flacgpu_scan_frames_host(const uint8_t *data, size_t len, flacgpu_frame_reco
 int flacgpu_decoder_scan_frames(flacgpu_decoder *d, const uint8_t *const *data, const size_t *len, uint32_t n_streams,
                                 flacgpu_decoded_stream *streams, flacgpu_raw_stream *raw,
                                 uint64_t *total_frames, uint64_t *total_elements, uint64_t *total_samples);
+int flacgpu_scan_frames_host_ex(const uint8_t *data, size_t len, uint32_t flags, flacgpu_frame_record *frames, size_t cap,
+                                uint32_t *n_frames, flacgpu_raw_stream *summary);
+int flacgpu_decoder_scan_frames_ex(flacgpu_decoder *d, const uint8_t *const *data, const size_t *len, uint32_t n_streams,
+                                   uint32_t flags, flacgpu_decoded_stream *streams, flacgpu_raw_stream *raw,
+                                   uint64_t *total_frames, uint64_t *total_elements, uint64_t *total_samples);
 int flacgpu_decoder_frame_records(flacgpu_decoder *d, flacgpu_frame_record *records, size_t cap);
 int flacgpu_decoder_decode_frames(flacgpu_decoder *d, int32_t *out, size_t out_cap_elements, uint32_t flags,
                                   flacgpu_frame_record *records, size_t cap);

@@ -15,12 +15,26 @@ over flacgpu_decode_stream and the oracle's CPU decoder on one core; writes prof
     python tools/decode_many_probe.py --raw --label parent --package-root DIR   (the regular leg only)
     python tools/decode_many_probe.py --raw --label this_2          (in this order: this build, parent, this build)
     python tools/decode_many_probe.py --raw --kernels-only          (one warm call per leg, for rocprofv3)
+    python tools/decode_many_probe.py --raw --speculative --label this_1 [--out profiles/r14_speculative.json]
+    python tools/decode_many_probe.py --raw --speculative --label parent --package-root DIR   (both flag-off legs)
+    python tools/decode_many_probe.py --raw --speculative --label this_2
+    python tools/decode_many_probe.py --raw --speculative --kernels-only
 
 --raw (flacgpu_decoder_scan_frames): on the clips, device output, no MD5, handle warm, the wall time of (regular) scan +
 decode of the files as they are and (raw) scan_frames + decode of the same files with the fLaC marker and metadata
 removed; both must give the same PCM, and its SHA-256 must be the same under every label.  Every leg reads the shader
 clock before and after.  The parent's build runs the regular leg alone; once this_1, parent and this_2 are in the file,
 `verdict` holds the parent's min-max spread (the allowance) and whether each of this build's medians lies inside it.
+
+--raw --speculative (FLACGPU_SCAN_SPECULATIVE): the same two legs -- the parent's build, which has the raw scan, runs
+both, and the verdict holds each flag-off leg of this build to the parent's spread of the same leg; they are timed
+first, before the process has done anything the parent's does not -- and behind them a third, the raw leg with
+speculative=True, whose PCM must be the same again.  The record names the candidates without a link, which k_spec_end
+walks, as this probe's own model of K_r2's rule counts them on the host (clean input: the rare false candidates and the
+last frame's look-alikes); the device's link array is not read.  A fourth leg gives the walk something to do: the same
+clips with byte 0 of every second frame zeroed, under the flag, which must keep exactly the other frames -- all by their
+own bits but a stream's last.  (In the --kernels-only run k_spec_end's shortest calls are the clean input's and its
+longest the damaged one's.)
 
 --formats (flacgpu_decoder_decode_as): on the clips, device output, no MD5, handle warm, the wall time of one
 scan + decode call into (a) what a caller of flacgpu_decoder_decode does -- interleaved int32, then torch ops to the
@@ -320,6 +334,44 @@ def s24(args):
     print(json.dumps(rec, indent=1), flush=True)
 
 
+def _gf_mul(a, b):   # a * b modulo the CRC-16 polynomial, over GF(2)
+    r = 0
+    for i in range(15, -1, -1):
+        r = ((r << 1) ^ 0x8005) & 0xFFFF if r & 0x8000 else (r << 1) & 0xFFFF
+        if (b >> i) & 1:
+            r ^= a
+    return r
+
+
+def _gf_xpow(e):     # x^e
+    r, sq = 1, 2
+    while e:
+        if e & 1:
+            r = _gf_mul(r, sq)
+        sq, e = _gf_mul(sq, sq), e >> 1
+    return r
+
+
+def unlinked_candidates(blob):
+    """The candidates of the raw scan of `blob` that K_r2 (k_link_raw) leaves without a link -- those k_spec_end walks --
+    by the scan's identity: frame [s, q) has a right CRC-16 exactly when A(q) == A(s), A(k) = P(k) x^(-8 k)."""
+    import _oracle as orc
+    import _raw_frames as rf
+
+    heads = rf.candidates(blob)
+    order = sorted(heads)
+    A, P, at = {}, 0, 0
+    for q in order + [len(blob)]:
+        P = _gf_mul(P, _gf_xpow(8 * (q - at) % 32767)) ^ orc.crc16(blob[at:q])
+        A[q], at = _gf_mul(P, _gf_xpow(-8 * q % 32767)), q
+    none = 0
+    for i, s in enumerate(order):
+        lo = s + heads[s]["header_bytes"] + 2 + heads[s]["channels"]
+        linked = any(q >= lo and A[q] == A[s] for q in order[i + 1:]) or (len(blob) - s >= 2 and A[len(blob)] == A[s])
+        none += not linked
+    return none, len(order)
+
+
 def raw_frames(args):
     """The --raw leg (see the module docstring)."""
     import hashlib
@@ -330,22 +382,45 @@ def raw_frames(args):
     from flac_codec_amd.gpu import Decoder, decode_many, scan_stream_host
 
     blobs = make_blobs("clips")
-    has_raw = hasattr(Decoder, "scan_frames") and args.label != "parent"
+    has_raw = hasattr(Decoder, "scan_frames") and (args.speculative or args.label != "parent")
+    has_spec = args.speculative and args.label != "parent"
     dec = Decoder(0)
     legs = {"regular_scan_decode": lambda: decode_many(blobs, out="device", verify_md5=False, decoder=dec)[0]}
     if has_raw:
         bare = [b[int(scan_stream_host(b)[1][0]):] for b in blobs]   # from the first frame on
         legs["raw_scan_frames_decode"] = lambda: decode_many(bare, out="device", verify_md5=False, decoder=dec,
                                                              raw=True)[0]
+    spec_legs = {}
+    if has_spec:
+        spec_legs["raw_scan_frames_decode_speculative"] = lambda: decode_many(
+            bare, out="device", verify_md5=False, decoder=dec, raw=True, speculative=True)[0]
+        spec_legs["raw_damaged_scan_frames_decode_speculative"] = lambda: decode_many(
+            damaged_batch(), out="device", verify_md5=False, decoder=dec, raw=True, speculative=True)[0]
+    made = {}
+
+    def damaged_batch():   # built on first use: behind the flag-off legs' timing
+        if not made:
+            cache, pairs = {}, []
+            for b, whole in zip(bare, blobs):
+                if b not in cache:
+                    offsets = scan_stream_host(whole)[1]
+                    d = bytearray(b)
+                    for off in offsets[1::2]:
+                        d[int(off) - int(offsets[0])] = 0
+                    cache[b] = (bytes(d), len(offsets) - len(offsets) // 2)
+                pairs.append(cache[b])
+            made["blobs"], made["undamaged"] = [d for d, _ in pairs], sum(n for _, n in pairs)
+        return made["blobs"]
+
     if args.kernels_only:
-        for fn in legs.values():
+        for fn in list(legs.values()) + list(spec_legs.values()):
             fn()
             fn()
         torch.cuda.synchronize()
         dec.close()
         return
-    res = {"tool": "tools/decode_many_probe.py --raw", "workload": "clips: 1024 x 10 s, 16 kHz mono 16-bit",
-           "device_output": True, "md5": False, "order": [], "runs": {}}
+    res = {"tool": "tools/decode_many_probe.py --raw" + (" --speculative" if args.speculative else ""),
+           "workload": "clips: 1024 x 10 s, 16 kHz mono 16-bit", "device_output": True, "md5": False, "order": [], "runs": {}}
     if os.path.exists(args.out):
         with open(args.out) as f:
             res = json.load(f)
@@ -356,32 +431,59 @@ def raw_frames(args):
         assert torch.equal(pcm, legs["raw_scan_frames_decode"]())   # identical PCM
     for other in res["runs"].values():
         assert other["pcm_sha256"] == rec["pcm_sha256"]             # and under every label
+
+    def timed(legs):
+        for name, fn in legs.items():
+            fn()
+            torch.cuda.synchronize()   # warm: buffers grown, code loaded
+            sclk_before = _sclk_mhz()
+            times = []
+            for _ in range(args.reps):
+                t0 = time.perf_counter()
+                out = fn()
+                torch.cuda.synchronize()
+                times.append(time.perf_counter() - t0)
+            rec["legs"][name] = dict(_spread(times), sclk_mhz_before=sclk_before, sclk_mhz_after=_sclk_mhz())
+            del out
+
+    # The flag-off legs first, in a process that has done nothing the parent's has not: no speculative scan, no damaged
+    # batch, no spec_len.  Everything of the flag comes behind them.
+    timed(legs)
+    if has_spec:
+        assert torch.equal(pcm, spec_legs["raw_scan_frames_decode_speculative"]())
+        damaged = damaged_batch()
+        counts = {}
+        for b in set(bare) | set(damaged):   # the batch repeats a few distinct streams
+            counts[b] = unlinked_candidates(b)
+        # counted by this probe's model of K_r2's rule (unlinked_candidates), not read from the device's link array
+        rec["candidates"] = sum(counts[b][1] for b in bare)
+        rec["candidates_without_link_by_the_probes_model"] = sum(counts[b][0] for b in bare)
+        _, streams = decode_many(damaged, out="device", verify_md5=False, decoder=dec, raw=True, speculative=True)
+        assert sum(s.info.frames for s in streams) == made["undamaged"] and all(s.rc == 0 for s in streams)
+        _, streams = decode_many(damaged, out="device", verify_md5=False, decoder=dec, raw=True)
+        rec["damaged"] = {"frames_kept_with_the_flag": made["undamaged"],
+                          "frames_kept_without_it": int(sum(s.info.frames for s in streams)),
+                          "candidates": sum(counts[b][1] for b in damaged),
+                          "candidates_without_link_by_the_probes_model": sum(counts[b][0] for b in damaged)}
+        timed(spec_legs)
     del pcm
-    for name, fn in legs.items():
-        fn()
-        torch.cuda.synchronize()   # warm: buffers grown, code loaded
-        sclk_before = _sclk_mhz()
-        times = []
-        for _ in range(args.reps):
-            t0 = time.perf_counter()
-            out = fn()
-            torch.cuda.synchronize()
-            times.append(time.perf_counter() - t0)
-        rec["legs"][name] = dict(_spread(times), sclk_mhz_before=sclk_before, sclk_mhz_after=_sclk_mhz())
-        del out
     dec.close()
     res["runs"][args.label] = rec
     res["order"].append(args.label)
     runs = res["runs"]
     if all(k in runs for k in ("this_1", "parent", "this_2")):
         allow = runs["parent"]["legs"]["regular_scan_decode"]
-        inside = lambda leg: allow["min_s"] <= leg["median_s"] <= allow["max_s"]   # noqa: E731
+        inside = lambda leg, allow: allow["min_s"] <= leg["median_s"] <= allow["max_s"]   # noqa: E731
         res["verdict"] = {"allowance_parent_min_s": allow["min_s"], "allowance_parent_max_s": allow["max_s"],
                           "parent_median_s": allow["median_s"]}
         for label in ("this_1", "this_2"):
             for name, leg in runs[label]["legs"].items():
-                res["verdict"][f"{label}.{name}"] = {"median_s": leg["median_s"], "inside_parent_spread": inside(leg),
-                                                     "over_parent_median": leg["median_s"] / allow["median_s"]}
+                if name.endswith("_speculative"):   # no leg of the parent's to hold it to
+                    continue
+                # a leg the parent ran is held to the parent's spread of that leg; else (r13) to the regular leg's
+                ref = runs["parent"]["legs"].get(name, allow)
+                res["verdict"][f"{label}.{name}"] = {"median_s": leg["median_s"], "inside_parent_spread": inside(leg, ref),
+                                                     "over_parent_median": leg["median_s"] / ref["median_s"]}
     with open(args.out, "w") as f:
         json.dump(res, f, indent=1)
     print(json.dumps({args.label: rec, "verdict": res.get("verdict")}, indent=1), flush=True)
@@ -509,7 +611,7 @@ def merge_stats(args):
                                "avg_ms": float(r["AverageNs"]) / 1e6}
     mine = {k: v for k, v in rows.items() if any(s in k for s in ("k_scan_", "k_link", "k_decode_many", "k_frame_crc",
                                                                    "k_finish_many", "k_md5_many", "k_finish_as",
-                                                                   "k_pad_rows", "k_finish_window"))}   # (k_scan_ and k_link cover the raw kernels)
+                                                                   "k_pad_rows", "k_finish_window", "k_spec_end"))}   # (k_scan_ and k_link cover the raw kernels)
     res.setdefault("kernel_stats", {})[args.stats_label] = mine
     with open(args.out, "w") as f:
         json.dump(res, f, indent=1)
@@ -525,6 +627,8 @@ def main():
     ap.add_argument("--windows", action="store_true", help="the random-crop leg: profiles/r10_decode_windows.json")
     ap.add_argument("--s24", action="store_true", help="with --formats: the packed 24-bit leg, profiles/r12_s24.json")
     ap.add_argument("--raw", action="store_true", help="the raw frame stream leg: profiles/r13_raw_frames.json")
+    ap.add_argument("--speculative", action="store_true",
+                    help="with --raw: add the FLACGPU_SCAN_SPECULATIVE leg, profiles/r14_speculative.json")
     ap.add_argument("--shrink", type=int, default=1, help="--s24: divide the clip count")
     ap.add_argument("--label", default="this", help="--formats: the run's name in the file (parent: the default int32 "
                     "leg only; any other name: every leg)")
@@ -535,7 +639,8 @@ def main():
     ap.add_argument("--kernels-only", action="store_true", help="one warm decode per workload (for rocprofv3)")
     args = ap.parse_args()
     if not args.out:
-        args.out = os.path.join(ROOT, "profiles", "r13_raw_frames.json" if args.raw else
+        args.out = os.path.join(ROOT, "profiles", "r14_speculative.json" if args.raw and args.speculative else
+                                "r13_raw_frames.json" if args.raw else
                                 "r10_decode_windows.json" if args.windows else
                                 "r12_s24.json" if args.s24 else
                                 "r09_decode_formats.json" if args.formats else "r07_decode_many.json")
