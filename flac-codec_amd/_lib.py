@@ -22,6 +22,7 @@ SAMPLE_S24 = 24   # packed 3-byte little-endian elements
 LAYOUT_FLAT, LAYOUT_PADDED = 0, 1              # flacgpu_out_format.layout
 SCAN_SPECULATIVE = 1    # flacgpu_*_scan_frames*_ex flags: end a frame that no header ends by its own bits
 FRAME_SPECULATIVE = 1   # FrameRecord.reserved bit 0: the frame was ended that way
+TL_PLACED, TL_DROPPED, TL_CONCEALED = 1, 2, 4   # TimelineFrame.flags (FLACGPU_TL_*)
 
 
 class GpuOptions(C.Structure):
@@ -140,6 +141,18 @@ class RawStream(C.Structure):
                 ("gaps", C.c_uint32), ("uniform", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class TimelineFrame(C.Structure):
+    """flacgpu_timeline_frame: one record's place on its stream's timeline (16 bytes)."""
+    _fields_ = [("at", C.c_uint64), ("flags", C.c_uint32), ("status", C.c_uint32)]
+
+
+class TimelineResult(C.Structure):
+    """flacgpu_timeline_result: one stream's timeline (56 bytes)."""
+    _fields_ = [("rc", C.c_int32), ("placed", C.c_uint32), ("dropped", C.c_uint32), ("concealed", C.c_uint32),
+                ("gaps", C.c_uint32), ("reserved", C.c_uint32), ("first_sample", C.c_uint64),
+                ("timeline_samples", C.c_uint64), ("gap_samples", C.c_uint64), ("concealed_samples", C.c_uint64)]
+
+
 class ShardCounters(C.Structure):
     """flacgpu_shard_counters: the four integers that cross shards of a stream (include/flacenc_gpu.h)."""
     _fields_ = [("frames", C.c_uint64), ("bytes", C.c_uint64), ("min_frame", C.c_uint64), ("max_frame", C.c_uint64)]
@@ -255,6 +268,14 @@ def _load():
                                                  C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.flacgpu_decoder_frame_records.argtypes = [vp, C.POINTER(FrameRecord), C.c_size_t]
     L.flacgpu_decoder_decode_frames.argtypes = [vp, vp, C.c_size_t, C.c_uint32, C.POINTER(FrameRecord), C.c_size_t]
+    L.flacgpu_timeline_host.argtypes = [C.POINTER(FrameRecord), C.c_size_t, C.POINTER(TimelineFrame), C.c_size_t,
+                                        C.POINTER(TimelineResult)]
+    L.flacgpu_timeline_piece_bytes.argtypes = []
+    L.flacgpu_timeline_piece_bytes.restype = C.c_uint32
+    L.flacgpu_decoder_plan_timeline.argtypes = [vp, C.POINTER(OutFormat), C.POINTER(TimelineResult),
+                                                C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.flacgpu_decoder_decode_timeline.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(OutFormat), C.c_uint32,
+                                                  C.POINTER(TimelineResult), C.POINTER(TimelineFrame), C.c_size_t]
     L.flacgpu_pack_plans.argtypes = [vp, ip, C.c_uint32, C.c_uint32, C.POINTER(FramePlan), C.POINTER(SubframePlan),
                                      C.c_uint64, C.c_uint32]
     L.flacgpu_host_alloc.argtypes = [C.c_size_t]

@@ -101,6 +101,20 @@ int flacgpu_scan_frames_host_ex(const uint8_t *data, size_t len, uint32_t flags,
     return FLACGPU_OK;
 }
 
+int flacgpu_timeline_host(const flacgpu_frame_record *records, size_t n_records, flacgpu_timeline_frame *frames_out,
+                          size_t cap, flacgpu_timeline_result *result) {
+    if ((!records && n_records) || !result) return FLACGPU_ERR_INVALID_ARG;
+    if (frames_out && cap < n_records) {
+        g_last_error = "output buffer too small";
+        return FLACGPU_ERR_BUFFER_TOO_SMALL;
+    }
+    if (const char *why = flacenc::timeline_of_records(records, n_records, frames_out, *result))
+        g_last_error = std::string("flacgpu_timeline_host: ") + why;
+    return FLACGPU_OK;
+}
+
+uint32_t flacgpu_timeline_piece_bytes(void) { return FLACGPU_TIMELINE_PIECE_BYTES; }
+
 // Decodes a whole FLAC stream held in host memory: the host finds the frame boundaries (scan_stream), the GPU decodes the
 // frames in parallel, one lane per frame, re-checks every CRC-16 and undoes the stereo decorrelation; the host compares
 // the MD5 of the decoded PCM with STREAMINFO's (decode.rs:1282 `verify`, 1388-1436 read_frame, 1494-1856).

@@ -60,6 +60,7 @@ struct flacgpu_decoder {
     DevBuf frames, scratch, codes, counts, jobs, digest, out_stage;
     DevBuf md5_stage, pad_out, pad_streams;   // decode_as: interleaved int32 for the MD5, padded layout tables
     DevBuf win_frames, win_desc;              // decode_windows: the selected frames (d->frames stays the scan's)
+    DevBuf tl_runs, tl_mask;                  // decode_timeline: the fill runs; the mask on its way to host memory
     // the scanned batch
     bool scanned = false;
     std::vector<flacgpu_decoded_stream> res;
@@ -796,6 +797,246 @@ int decode_windows_impl(flacgpu_decoder *d, void *out, uint64_t out_bytes, const
     }
     return FLACGPU_OK;
 }
+
+// ---- frames on a timeline ----
+// The rule for every stream of the raw scan: results[i], and (frames != nullptr) every record's place.  `who` names the
+// call in the last-error text, which is set for the first refused stream.
+void timeline_streams(const flacgpu_decoder *d, flacgpu_timeline_result *results, flacgpu_timeline_frame *frames,
+                      const char *who) {
+    bool noted = false;
+    for (size_t i = 0; i < d->raw_streams.size(); i++) {
+        const flacgpu_raw_stream &rs = d->raw_streams[i];
+        const char *why = flacenc::timeline_of_records(d->records.data() + rs.first_frame, rs.frames,
+                                                       frames ? frames + rs.first_frame : nullptr, results[i]);
+        if (why && !noted) {
+            g_last_error = std::string(who) + ": stream " + std::to_string(i) + ": " + why;
+            noted = true;
+        }
+    }
+}
+
+// plan_timeline's checks of `fmt` against the streams' timelines; the bytes of `out` and of the mask
+int timeline_check(const flacgpu_decoder *d, const flacgpu_out_format *fmt, const flacgpu_timeline_result *results,
+                   const std::string &who, uint64_t *out_bytes, uint64_t *mask_bytes) {
+    const uint32_t n = (uint32_t)d->raw_streams.size();
+    if (!sample_type_known(fmt->dtype) || fmt->layout != FLACGPU_LAYOUT_PADDED || fmt->reserved) {
+        g_last_error = who + ": unknown dtype, a layout other than PADDED, or reserved not 0";
+        return FLACGPU_ERR_INVALID_ARG;
+    }
+    for (uint32_t i = 0; i < n; i++) {
+        if (results[i].rc != FLACGPU_OK) continue;
+        const flacgpu_frame_record &r0 = d->records[d->raw_streams[i].first_frame];
+        if (r0.channels > fmt->channels_padded || results[i].timeline_samples > fmt->samples_padded) {
+            g_last_error = who + ": stream " + std::to_string(i) + " (" + std::to_string(r0.channels) + " channels, " +
+                           std::to_string(results[i].timeline_samples) +
+                           " samples on its timeline) does not fit channels_padded x samples_padded";
+            return FLACGPU_ERR_INVALID_ARG;
+        }
+    }
+    for (uint32_t i = 0; i < n && sample_type_max_bits(fmt->dtype); i++) {
+        if (results[i].rc != FLACGPU_OK) continue;
+        const flacgpu_frame_record &r0 = d->records[d->raw_streams[i].first_frame];
+        if (r0.bits_per_sample > sample_type_max_bits(fmt->dtype)) {
+            g_last_error = who + ": " + sample_type_name(fmt->dtype) + " output, but stream " + std::to_string(i) + " has " +
+                           std::to_string(r0.bits_per_sample) + " bits per sample";
+            return FLACGPU_ERR_UNSUPPORTED;
+        }
+    }
+    uint64_t bytes = 0, mbytes = 0;
+    if (__builtin_mul_overflow((uint64_t)n * fmt->channels_padded, fmt->samples_padded, &bytes) ||
+        __builtin_mul_overflow(bytes, (uint64_t)sample_type_bytes(fmt->dtype), &bytes) ||
+        __builtin_mul_overflow((uint64_t)n, fmt->samples_padded, &mbytes)) {
+        g_last_error = who + ": the padded batch exceeds 2^64 bytes";
+        return FLACGPU_ERR_UNSUPPORTED;
+    }
+    *out_bytes = bytes;
+    if (mask_bytes) *mask_bytes = mbytes;
+    return FLACGPU_OK;
+}
+
+// `count` elements of `es` bytes from element `first`, cut into pieces of at most kFillPiece bytes: every cut lies a
+// multiple of 16 bytes behind the run's first byte, so that only the run's own two ends are not whole 16-byte groups
+void push_runs(std::vector<FillRun> &runs, uint64_t first, uint64_t count, uint32_t es, uint32_t cond, uint32_t value) {
+    const uint64_t per = kFillPiece / es;
+    for (uint64_t done = 0; done < count; done += per)
+        runs.push_back(FillRun{first + done, (uint32_t)std::min(per, count - done), cond, value, 0});
+}
+
+template <uint32_t ES>
+void launch_fill(flacgpu_decoder *d, size_t first, size_t count, void *dst) {
+    if (!count) return;
+    hipLaunchKernelGGL(k_fill_runs<ES>, dim3((uint32_t)count), dim3(WG), 0, d->st, d->tl_runs.as<const FillRun>() + first,
+                       d->counts.as<const uint32_t>(), static_cast<uint8_t *>(dst));
+}
+void launch_fill_samples(flacgpu_decoder *d, uint32_t dtype, size_t first, size_t count, void *dst) {
+    if (dtype == FLACGPU_SAMPLE_I16) launch_fill<2>(d, first, count, dst);
+    else if (dtype == FLACGPU_SAMPLE_S24) launch_fill<3>(d, first, count, dst);
+    else launch_fill<4>(d, first, count, dst);
+}
+
+// flacgpu_decoder_decode_timeline behind its checks (out_bytes > 0): `results` and `tl` (every record's place) are the
+// rule's; fills concealed / status.  The placed frames of the streams with rc == 0 are decoded through decode_windows'
+// kernels, one "window" per frame, so that the counts come out per frame; k_fill_runs zeroes the gaps beside them and,
+// behind k_finish_window and decided by those counts on the device, the frames that did not decode.
+int decode_timeline_impl(flacgpu_decoder *d, void *out, uint64_t out_bytes, uint8_t *mask, uint64_t mask_bytes,
+                         const flacgpu_out_format &fmt, uint32_t flags, flacgpu_timeline_result *results,
+                         std::vector<flacgpu_timeline_frame> &tl) {
+    DeviceGuard guard(d->device);
+    const uint32_t n = (uint32_t)d->raw_streams.size(), Cp = fmt.channels_padded;
+    const uint32_t es = (uint32_t)sample_type_bytes(fmt.dtype);
+    const uint64_t T = fmt.samples_padded;
+    if ((uint64_t)n * Cp > 0x7FFFFFFFull) {
+        g_last_error = "flacgpu_decoder_decode_timeline: more than 2^31 - 1 padded rows";
+        return FLACGPU_ERR_UNSUPPORTED;
+    }
+    // ---- host: the placed frames, compact, with scratch of their own; the runs in four groups -- sample gaps, the
+    // mask's unconditional runs, the samples' concealment, the mask's concealment
+    std::vector<ManyFrame> sel;
+    std::vector<WinFrame> desc;
+    std::vector<size_t> sel_record;
+    std::vector<PadStream> pad(n);
+    std::vector<FillRun> gap_runs, mask_runs, hide_runs, mask_hide_runs, runs;
+    uint64_t scratch_total = 0;
+    try {
+        sel.reserve(tl.size());
+        desc.reserve(tl.size());
+        sel_record.reserve(tl.size());
+        hide_runs.reserve(tl.size());
+        for (uint32_t i = 0; i < n; i++) {
+            pad[i] = PadStream{0, 0, 0};
+            if (results[i].rc != FLACGPU_OK) {
+                if (mask) push_runs(mask_runs, (uint64_t)i * T, T, 1, FILL_ALWAYS, 0);
+                continue;
+            }
+            const flacgpu_raw_stream &rs = d->raw_streams[i];
+            const uint32_t C = d->records[rs.first_frame].channels;
+            const uint64_t row = (uint64_t)i * Cp * T;
+            pad[i] = PadStream{results[i].timeline_samples, C, 0};
+            uint64_t end = 0;   // row position behind the last placed frame
+            for (size_t k = rs.first_frame; k < rs.first_frame + rs.frames; k++) {
+                if (!(tl[k].flags & FLACGPU_TL_PLACED)) continue;
+                const uint64_t at = tl[k].at;
+                if (at > end) {
+                    for (uint32_t c = 0; c < C; c++) push_runs(gap_runs, row + c * T + end, at - end, es, FILL_ALWAYS, 0);
+                    if (mask) push_runs(mask_runs, (uint64_t)i * T + end, at - end, 1, FILL_ALWAYS, 0);
+                }
+                const uint32_t j = (uint32_t)sel.size();
+                ManyFrame fr = d->raw_tab[k];
+                WinFrame wf{};
+                wf.row = row;
+                wf.at = at;
+                wf.keep_first = 0;
+                wf.keep_last = fr.n;
+                wf.channels = fr.channels;
+                wf.bps = fr.bps;
+                wf.window = j;
+                fr.slot = j;   // k_frame_crc counts per frame
+                fr.out = 0;
+                fr.scratch = scratch_total;
+                scratch_total += (uint64_t)fr.channels * ((fr.n + 3u) & ~3u);
+                sel.push_back(fr);
+                desc.push_back(wf);
+                sel_record.push_back(k);
+                for (uint32_t c = 0; c < C; c++) push_runs(hide_runs, row + c * T + at, fr.n, es, j, 0);
+                if (mask) {
+                    push_runs(mask_runs, (uint64_t)i * T + at, fr.n, 1, FILL_ALWAYS, 1);
+                    push_runs(mask_hide_runs, (uint64_t)i * T + at, fr.n, 1, j, 0);
+                }
+                end = at + fr.n;
+            }
+            if (mask) push_runs(mask_runs, (uint64_t)i * T + end, T - end, 1, FILL_ALWAYS, 0);
+        }
+        runs.reserve(gap_runs.size() + mask_runs.size() + hide_runs.size() + mask_hide_runs.size());
+        for (const auto *g : {&gap_runs, &mask_runs, &hide_runs, &mask_hide_runs}) runs.insert(runs.end(), g->begin(), g->end());
+    } catch (const std::bad_alloc &) {
+        g_last_error = "flacgpu_decoder_decode_timeline: out of host memory";
+        return FLACGPU_ERR_UNSUPPORTED;
+    }
+    if (sel.size() > 0x7FFFFFFFull || runs.size() > 0x7FFFFFFFull) {
+        g_last_error = "flacgpu_decoder_decode_timeline: more than 2^31 - 1 placed frames or fill runs";
+        return FLACGPU_ERR_UNSUPPORTED;
+    }
+    const uint32_t F = (uint32_t)sel.size();
+    const bool to_device = flags & FLACGPU_DECODE_OUT_DEVICE;
+    void *dst = out;
+    uint8_t *mdst = mask;
+    if (!to_device) {
+        if (int rc = d->out_stage.ensure(out_bytes)) return rc;
+        dst = d->out_stage.p;
+        if (mask) {
+            if (int rc = d->tl_mask.ensure(mask_bytes)) return rc;
+            mdst = d->tl_mask.as<uint8_t>();
+        }
+    }
+    if (int rc = d->pad_streams.ensure(sizeof(PadStream) * n)) return rc;
+    if (int rc = d->counts.ensure(8 * (size_t)std::max<uint32_t>(F, 1))) return rc;
+    if (!runs.empty())
+        if (int rc = d->tl_runs.ensure(sizeof(FillRun) * runs.size())) return rc;
+    if (F) {   // scratch by the placed frames, not by the batch
+        if (int rc = d->win_frames.ensure(sizeof(ManyFrame) * F)) return rc;
+        if (int rc = d->win_desc.ensure(sizeof(WinFrame) * F)) return rc;
+        if (int rc = d->scratch.ensure(4 * scratch_total)) return rc;
+        if (int rc = d->codes.ensure(4 * (size_t)F)) return rc;
+    }
+    HIP_TRY(hipMemcpyAsync(d->pad_streams.p, pad.data(), sizeof(PadStream) * n, hipMemcpyHostToDevice, d->st));
+    if (!runs.empty())
+        HIP_TRY(hipMemcpyAsync(d->tl_runs.p, runs.data(), sizeof(FillRun) * runs.size(), hipMemcpyHostToDevice, d->st));
+    HIP_TRY(hipMemsetAsync(d->counts.p, 0, 8 * (size_t)std::max<uint32_t>(F, 1), d->st));
+    // rows' tails, absent channels and refused streams; the gaps; the mask's 0s and 1s as if every frame decoded
+    if (out_bytes) launch_pad_rows(fmt.dtype, n * Cp, d->st, d->pad_streams.as<const PadStream>(), Cp, T, dst);
+    size_t at = 0;
+    launch_fill_samples(d, fmt.dtype, at, gap_runs.size(), dst);
+    at += gap_runs.size();
+    launch_fill<1>(d, at, mask_runs.size(), mdst);
+    at += mask_runs.size();
+    if (F) {
+        HIP_TRY(hipMemcpyAsync(d->win_frames.p, sel.data(), sizeof(ManyFrame) * F, hipMemcpyHostToDevice, d->st));
+        HIP_TRY(hipMemcpyAsync(d->win_desc.p, desc.data(), sizeof(WinFrame) * F, hipMemcpyHostToDevice, d->st));
+        const ManyFrame *frames = d->win_frames.as<const ManyFrame>();
+        const uint32_t lanes = 32;   // as decode_impl launches it
+        hipLaunchKernelGGL(k_decode_many<32>, dim3((F + lanes - 1) / lanes), dim3(lanes), 0, d->st,
+                           d->bytes.as<const uint32_t>(), frames, F, d->scratch.as<int32_t>(), d->codes.as<uint32_t>());
+        hipLaunchKernelGGL(k_frame_crc, dim3(F), dim3(64), 0, d->st, d->bytes.as<const uint8_t>(), frames,
+                           d->counts.as<uint32_t>());
+        const auto k = fmt.dtype == FLACGPU_SAMPLE_I16   ? k_finish_window<DT_I16>
+                       : fmt.dtype == FLACGPU_SAMPLE_F32 ? k_finish_window<DT_F32>
+                       : fmt.dtype == FLACGPU_SAMPLE_S24 ? k_finish_window<DT_S24>
+                                                         : k_finish_window<DT_I32>;
+        hipLaunchKernelGGL(k, dim3(F), dim3(WG), 0, d->st, frames, d->win_desc.as<const WinFrame>(),
+                           d->scratch.as<const int32_t>(), d->codes.as<const uint32_t>(), static_cast<uint8_t *>(dst), T,
+                           d->counts.as<uint32_t>());
+        // the concealment: behind the kernels that count, on their stream
+        launch_fill_samples(d, fmt.dtype, at, hide_runs.size(), dst);
+        at += hide_runs.size();
+        launch_fill<1>(d, at, mask_hide_runs.size(), mdst);
+    }
+    HIP_TRY(hipGetLastError());
+    std::vector<uint32_t> counts;
+    try {   // no exception crosses the C ABI; the kernels are waited for before the return
+        counts.resize(2 * (size_t)F);
+    } catch (const std::bad_alloc &) {
+        (void)hipStreamSynchronize(d->st);
+        g_last_error = "flacgpu_decoder_decode_timeline: out of host memory";
+        return FLACGPU_ERR_UNSUPPORTED;
+    }
+    if (F) HIP_TRY(hipMemcpyAsync(counts.data(), d->counts.p, 8 * (size_t)F, hipMemcpyDeviceToHost, d->st));
+    if (!to_device) {
+        HIP_TRY(hipMemcpyAsync(out, dst, out_bytes, hipMemcpyDeviceToHost, d->st));
+        if (mask && mask_bytes) HIP_TRY(hipMemcpyAsync(mask, mdst, mask_bytes, hipMemcpyDeviceToHost, d->st));
+    }
+    HIP_TRY(hipStreamSynchronize(d->st));   // the tables leave scope behind this
+    for (uint32_t j = 0; j < F; j++) {
+        const size_t k = sel_record[j];
+        const uint32_t status = (counts[2 * (size_t)j] ? 1u : 0u) | (counts[2 * (size_t)j + 1] ? 2u : 0u);
+        tl[k].status = status;
+        if (!status) continue;
+        tl[k].flags |= FLACGPU_TL_CONCEALED;
+        flacgpu_timeline_result &r = results[d->records[k].stream];
+        r.concealed++;
+        r.concealed_samples += d->records[k].block_size;
+    }
+    return FLACGPU_OK;
+}
 }  // namespace
 
 // k_md5_many for the encoder's ingest pass (ingest.hip): one job per ingested stream, no digest to compare with
@@ -920,6 +1161,60 @@ int flacgpu_decoder_decode_frames(flacgpu_decoder *d, int32_t *out, size_t out_c
         return FLACGPU_ERR_BUFFER_TOO_SMALL;
     }
     return decode_frames_impl(d, out, flags, records);
+}
+
+int flacgpu_decoder_plan_timeline(flacgpu_decoder *d, const flacgpu_out_format *fmt, flacgpu_timeline_result *results,
+                                  uint64_t *out_bytes, uint64_t *mask_bytes) {
+    if (!d || !fmt || !out_bytes) return FLACGPU_ERR_INVALID_ARG;
+    *out_bytes = 0;
+    if (mask_bytes) *mask_bytes = 0;
+    if (!d->scanned || !d->raw) {
+        g_last_error = "flacgpu_decoder_plan_timeline: no scanned batch of raw frame streams";
+        return FLACGPU_ERR_INVALID_ARG;
+    }
+    if (!d->raw_streams.empty() && !results) return FLACGPU_ERR_INVALID_ARG;
+    timeline_streams(d, results, nullptr, "flacgpu_decoder_plan_timeline");
+    return timeline_check(d, fmt, results, "flacgpu_decoder_plan_timeline", out_bytes, mask_bytes);
+}
+
+int flacgpu_decoder_decode_timeline(flacgpu_decoder *d, void *out, size_t out_cap_bytes, uint8_t *mask,
+                                    size_t mask_cap_bytes, const flacgpu_out_format *fmt, uint32_t flags,
+                                    flacgpu_timeline_result *results, flacgpu_timeline_frame *frames, size_t frames_cap) {
+    if (!d || !fmt || (flags & ~FLACGPU_DECODE_OUT_DEVICE)) return FLACGPU_ERR_INVALID_ARG;
+    if (!d->scanned || !d->raw) {
+        g_last_error = "flacgpu_decoder_decode_timeline: no scanned batch of raw frame streams";
+        return FLACGPU_ERR_INVALID_ARG;
+    }
+    const size_t n = d->raw_streams.size(), R = d->records.size();
+    if (n && !results) return FLACGPU_ERR_INVALID_ARG;
+    std::vector<flacgpu_timeline_result> res;
+    std::vector<flacgpu_timeline_frame> tl;
+    try {   // a refused call writes nothing: the rule runs on copies
+        res.resize(n);
+        tl.resize(R);
+    } catch (const std::bad_alloc &) {
+        g_last_error = "flacgpu_decoder_decode_timeline: out of host memory";
+        return FLACGPU_ERR_UNSUPPORTED;
+    }
+    timeline_streams(d, res.data(), tl.data(), "flacgpu_decoder_decode_timeline");
+    const std::string note = g_last_error;   // the first refused stream, if any: what an accepted call leaves
+    uint64_t out_bytes = 0, mask_bytes = 0;
+    if (int rc = timeline_check(d, fmt, res.data(), "flacgpu_decoder_decode_timeline", &out_bytes, &mask_bytes)) return rc;
+    if ((out_bytes && (!out || out_cap_bytes < out_bytes)) || (mask && mask_cap_bytes < mask_bytes) ||
+        (frames && frames_cap < R)) {
+        g_last_error = "output buffer too small";
+        return FLACGPU_ERR_BUFFER_TOO_SMALL;
+    }
+    if (reinterpret_cast<uintptr_t>(out) % sample_type_align(fmt->dtype)) {
+        g_last_error = "flacgpu_decoder_decode_timeline: out is not aligned to its element size";
+        return FLACGPU_ERR_INVALID_ARG;
+    }
+    if (out_bytes || (mask && mask_bytes))
+        if (int rc = decode_timeline_impl(d, out, out_bytes, mask, mask_bytes, *fmt, flags, res.data(), tl)) return rc;
+    if (n) memcpy(results, res.data(), sizeof(flacgpu_timeline_result) * n);
+    if (frames && R) memcpy(frames, tl.data(), sizeof(flacgpu_timeline_frame) * R);
+    g_last_error = note;
+    return FLACGPU_OK;
 }
 
 int flacgpu_decoder_decode(flacgpu_decoder *d, int32_t *out, size_t out_cap_samples, uint32_t flags,

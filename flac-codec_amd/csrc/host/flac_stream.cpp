@@ -245,6 +245,59 @@ void scan_raw_frames(const uint8_t *data, size_t len, uint32_t flags, std::vecto
     summarise_raw_frames(frames.data(), frames.size(), len, summary);
 }
 
+const char *timeline_of_records(const flacgpu_frame_record *records, size_t n, flacgpu_timeline_frame *frames_out,
+                                flacgpu_timeline_result &result) {
+    result = flacgpu_timeline_result{};
+    for (size_t k = 0; frames_out && k < n; k++) frames_out[k] = flacgpu_timeline_frame{};
+    const auto refuse = [&](int rc, const char *why) {
+        result.rc = rc;
+        return why;
+    };
+    if (!n) return refuse(FLACGPU_ERR_INVALID_ARG, "no whole frame");
+    const flacgpu_frame_record &r0 = records[0];
+    for (size_t k = 1; k < n; k++)
+        if (records[k].sample_rate != r0.sample_rate || records[k].channels != r0.channels ||
+            records[k].bits_per_sample != r0.bits_per_sample)
+            return refuse(FLACGPU_ERR_UNSUPPORTED, "frames differ in sample rate, channels or sample size");
+    for (size_t k = 1; k < n; k++)
+        if (records[k].blocking != r0.blocking)
+            return refuse(FLACGPU_ERR_UNSUPPORTED, "frames differ in blocking strategy");
+    const uint64_t B = r0.block_size;
+    if (!r0.blocking) {
+        for (size_t k = 0; k + 1 < n; k++)
+            if (records[k].block_size != B)
+                return refuse(FLACGPU_ERR_UNSUPPORTED,
+                              "fixed blocking, but a frame before the last has another block size than the first");
+        if (records[n - 1].block_size > B)
+            return refuse(FLACGPU_ERR_UNSUPPORTED, "fixed blocking, but the last frame is larger than the block size");
+    }
+    // numbers reach 2^36 and block sizes 2^16: no product or sum of a scanned record leaves 64 bits
+    const auto position = [&](const flacgpu_frame_record &r) { return r0.blocking ? r.number : r.number * B; };
+    const uint64_t origin = position(r0);
+    uint64_t end = origin;
+    for (size_t k = 0; k < n; k++) {
+        const uint64_t p = position(records[k]);
+        const bool placed = k == 0 || p >= end;
+        if (placed) {
+            if (p > end) {
+                result.gaps++;
+                result.gap_samples += p - end;
+            }
+            end = p + records[k].block_size;
+            result.placed++;
+        } else {
+            result.dropped++;
+        }
+        if (frames_out) {
+            frames_out[k].at = placed ? p - origin : 0;
+            frames_out[k].flags = placed ? FLACGPU_TL_PLACED : FLACGPU_TL_DROPPED;
+        }
+    }
+    result.first_sample = origin;
+    result.timeline_samples = end - origin;
+    return nullptr;
+}
+
 void scan_frames(const uint8_t *data, size_t len, size_t pos, uint32_t min_frame, flacgpu_stream_info *info, FrameScan &scan) {
     const uint16_t *const T = crc16_table();   // taken once: the inner loop is one table step per byte
     size_t p = pos;

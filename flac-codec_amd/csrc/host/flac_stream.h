@@ -57,6 +57,12 @@ size_t raw_frame_extent(const uint8_t *data, size_t len, const HostFrameInfo &h)
 // `summary`'s frames, uniform flag, skipped_bytes and gaps from the stream's kept frames (first_frame is left alone)
 void summarise_raw_frames(const flacgpu_frame_record *frames, size_t n, size_t len, flacgpu_raw_stream &summary);
 
+// The timeline of one stream's kept frames (include/flacenc_gpu.h "raw frame streams on a timeline" states the rule):
+// `result` is filled; frames_out (may be null, n entries) gets every record's place -- at, PLACED or DROPPED, status 0 --
+// or zeros for a refused stream.  Returns nullptr, or why the stream is refused (result.rc says how).
+const char *timeline_of_records(const flacgpu_frame_record *records, size_t n, flacgpu_timeline_frame *frames_out,
+                                flacgpu_timeline_result &result);
+
 // The decoded frames (at least one), planar [frame][channel][ldb], interleaved into `out` (may be null) and hashed as
 // ceil(bps / 8)-byte little-endian samples (decode.rs:1282 verify): fills info->decoded_md5 and info->md5_status.
 void finish_stream(const int32_t *planar, size_t ldb, const std::vector<uint32_t> &frame_n, int32_t *out,

@@ -14,6 +14,9 @@
 //   K_d6 k_pad_rows      workgroup per (stream, channel row) of a padded batch: zeroes what no frame writes
 //   K_d7 k_finish_window workgroup per selected frame of a sample window (flacgpu_decoder_decode_windows): k_finish_as's
 //                        arithmetic and conversions on the part of the frame the window keeps, into the window's rows
+//   K_d8 k_fill_runs     workgroup per run of a timeline (flacgpu_decoder_decode_timeline): a byte value over a run of
+//                        elements that begins and ends anywhere in a row -- the gaps, and, decided by the per-frame
+//                        counts, the frames that did not decode; the mask likewise
 
 struct ManyFrame {
     uint64_t start, end;   // byte offsets in the batch buffer: header .. CRC-16 inclusive
@@ -429,4 +432,52 @@ __global__ void __launch_bounds__(WG) k_finish_window(const ManyFrame *__restric
     for (uint32_t c = 0; c < w.channels; c++)
         store_elems<ES>(out + (w.row + (uint64_t)c * samples_padded + w.at) * ES, w.keep_last - w.keep_first, threadIdx.x,
                       WG, [&](uint32_t i) { return sample_bits<DT>(frame_sample(rows, ldb, acode, i, c), bps); });
+}
+
+// ---- frames on a timeline (flacgpu_decoder_decode_timeline) ----
+// One run of a fill: `count` elements of ES bytes from element `first` of the output, every byte of them `value`
+// (0 for samples; 0 or 1 for the mask, whose elements are bytes).  cond == FILL_ALWAYS: the run is always written (a gap,
+// a row's tail in the mask, the 1s of a placed frame); else it is written only when frame `cond` of the compact table did
+// not parse or failed its CRC-16 (counts[2 cond] / counts[2 cond + 1], as decode_frames reads them): the concealment.
+// The host cuts a run into pieces of at most kFillPiece bytes (FLACGPU_TIMELINE_PIECE_BYTES) before it gets here.
+constexpr uint32_t FILL_ALWAYS = 0xFFFFFFFFu;
+constexpr uint32_t kFillPiece = FLACGPU_TIMELINE_PIECE_BYTES;
+static_assert(kFillPiece % 48 == 0, "a piece is whole elements of 2, 3 and 4 bytes and whole 16-byte groups");
+struct FillRun {
+    uint64_t first;   // element index in the output
+    uint32_t count;   // elements; count * ES <= kFillPiece
+    uint32_t cond;    // FILL_ALWAYS, or the frame whose counts decide
+    uint32_t value;   // the byte
+    uint32_t reserved;
+};
+// K_d8 k_fill_runs  workgroup per run, k_pad_rows' shape: single elements up to the first 16-byte boundary (ES == 1 and
+// ES == 3: single bytes, such a run begins and ends at any byte), 16 bytes per lane, consecutive lanes consecutive
+// groups, single elements behind the last whole group.  Exactly the run's bytes are written: its neighbours belong to
+// other workgroups and to k_finish_window and k_pad_rows.  `out` is ES-aligned for ES == 2 and 4, hence so is every run,
+// and head and tail are whole elements.
+template <uint32_t ES>
+__global__ void __launch_bounds__(WG) k_fill_runs(const FillRun *__restrict__ runs, const uint32_t *__restrict__ counts,
+                                                  uint8_t *__restrict__ out) {
+    const FillRun r = runs[blockIdx.x];
+    if (r.cond != FILL_ALWAYS && (counts[2 * (size_t)r.cond] | counts[2 * (size_t)r.cond + 1]) == 0) return;
+    uint8_t *p = out + r.first * ES;
+    const uint32_t bytes = r.count * ES;
+    const uint32_t w = (r.value & 0xFFu) * 0x01010101u;
+    const uint32_t head = min(bytes, (16u - (uint32_t)(reinterpret_cast<uintptr_t>(p) & 15u)) & 15u);
+    const uint32_t nv = (bytes - head) / 16u, tail_at = head + nv * 16u;
+    constexpr bool BYTES = ES == 1 || ES == 3;
+    if (BYTES) {
+        if (threadIdx.x < head) p[threadIdx.x] = (uint8_t)w;
+    } else if (threadIdx.x * ES < head) {
+        if (ES == 2) reinterpret_cast<uint16_t *>(p)[threadIdx.x] = (uint16_t)w;
+        else reinterpret_cast<uint32_t *>(p)[threadIdx.x] = w;
+    }
+    uint4 *body = reinterpret_cast<uint4 *>(p + head);
+    for (uint32_t v = threadIdx.x; v < nv; v += WG) body[v] = make_uint4(w, w, w, w);
+    if (BYTES) {
+        if (threadIdx.x < bytes - tail_at) p[tail_at + threadIdx.x] = (uint8_t)w;
+    } else if (threadIdx.x * ES < bytes - tail_at) {
+        if (ES == 2) reinterpret_cast<uint16_t *>(p + tail_at)[threadIdx.x] = (uint16_t)w;
+        else reinterpret_cast<uint32_t *>(p + tail_at)[threadIdx.x] = w;
+    }
 }

@@ -431,6 +431,29 @@ def scan_frames_host(data, speculative=False):
     return frames, raw
 
 
+TIMELINE_FRAME_DTYPE = np.dtype([(name, np.dtype(ct).str) for name, ct in _lib.TimelineFrame._fields_])
+
+
+def timeline_piece_bytes():
+    """flacgpu_timeline_piece_bytes: the most bytes one workgroup of the timeline's fill kernel writes."""
+    return int(_lib.lib().flacgpu_timeline_piece_bytes())
+
+
+def scan_timeline_host(records):
+    """flacgpu_timeline_host: the timeline rule (include/flacenc_gpu.h "raw frame streams on a timeline") for the records
+    of one stream -- a FRAME_DTYPE array as scan_frames_host returns it -- on the host alone (no GPU needed).  Returns
+    (TimelineResult, frames): `frames` is a TIMELINE_FRAME_DTYPE array, one entry per record (at, flags, status)."""
+    records = np.ascontiguousarray(records, dtype=FRAME_DTYPE)
+    frames = np.zeros(records.size, dtype=TIMELINE_FRAME_DTYPE)
+    result = _lib.TimelineResult()
+    rc = _lib.lib().flacgpu_timeline_host(records.ctypes.data_as(C.POINTER(_lib.FrameRecord)), records.size,
+                                          frames.ctypes.data_as(C.POINTER(_lib.TimelineFrame)), frames.size,
+                                          C.byref(result))
+    if rc:
+        raise GpuError(rc, "flacgpu_timeline_host")
+    return result, frames
+
+
 class DecodedStream:
     """One stream of a decode_many batch: rc (what flacgpu_decode_stream returns for it), info (StreamInfo), offset
     (first element in the flat output) and pcm (a [samples, channels] view of the flat output, or the
@@ -454,6 +477,7 @@ class Decoder:
             raise GpuError(rc, "flacgpu_decoder_create")
         self._h = h
         self.device = device
+        self.n_raw_streams = self.n_raw_frames = 0   # of the last scan_frames
 
     def close(self):
         if self._h:
@@ -513,6 +537,7 @@ class Decoder:
         if rc:
             raise GpuError(rc, "flacgpu_decoder_frame_records")
         self.raw_elements = elements.value
+        self.n_raw_streams, self.n_raw_frames = n, int(n_frames.value)
         return recs, total.value, raw, frames
 
     def decode_frames(self, out_ptr, out_cap, flags, frames):
@@ -524,6 +549,31 @@ class Decoder:
         if rc:
             raise GpuError(rc, "flacgpu_decoder_decode_frames")
         return frames
+
+    def plan_timeline(self, fmt, check=True):
+        """flacgpu_decoder_plan_timeline for the handle's last raw scan: (results, out_bytes, mask_bytes), `results` the
+        _lib.TimelineResult array of the scan's streams.  check=False returns (results, None, None) for a format the
+        call refuses instead of raising: the results are filled either way, and pad_to is sized from them."""
+        results = (_lib.TimelineResult * max(self.n_raw_streams, 1))()
+        need, mask = C.c_uint64(0), C.c_uint64(0)
+        rc = _lib.lib().flacgpu_decoder_plan_timeline(self._h, C.byref(fmt), results, C.byref(need), C.byref(mask))
+        if rc and check:
+            raise GpuError(rc, "flacgpu_decoder_plan_timeline")
+        return (results, None, None) if rc else (results, need.value, mask.value)
+
+    def decode_timeline(self, out_ptr, out_cap_bytes, mask_ptr, mask_cap_bytes, fmt, flags, frames=None):
+        """flacgpu_decoder_decode_timeline of the last raw scan into the buffers at out_ptr and mask_ptr (both device or
+        both host addresses; mask_ptr may be None).  Returns (results, frames): the _lib.TimelineResult array and a
+        TIMELINE_FRAME_DTYPE array with one entry per record of the scan."""
+        results = (_lib.TimelineResult * max(self.n_raw_streams, 1))()
+        if frames is None:
+            frames = np.zeros(self.n_raw_frames, dtype=TIMELINE_FRAME_DTYPE)
+        rc = _lib.lib().flacgpu_decoder_decode_timeline(self._h, out_ptr, out_cap_bytes, mask_ptr, mask_cap_bytes,
+                                                        C.byref(fmt), flags, results,
+                                                        frames.ctypes.data_as(C.POINTER(_lib.TimelineFrame)), frames.size)
+        if rc:
+            raise GpuError(rc, "flacgpu_decoder_decode_timeline")
+        return results, frames
 
     def decode(self, out_ptr, out_cap, flags, recs):
         """flacgpu_decoder_decode into the int32 buffer at out_ptr (device or host address)."""
@@ -738,6 +788,62 @@ def decode_many(blobs, device=-1, out="device", verify_md5=True, decoder=None, d
             pcm = flat[r.out_offset:r.out_offset + info.decoded_samples * ch].reshape(-1, ch)
         streams.append(DecodedStream(r.rc, info, r.out_offset, pcm))
     return flat, streams
+
+
+def decode_timeline(blobs, dtype="float32", pad_to=None, pad_channels=None, out="device", speculative=False, mask=True,
+                    decoder=None, device=-1):
+    """Decode a batch of raw frame streams (a lossy transport's frames, a byte range of a file) onto their timelines:
+    every whole frame is put where its coded frame or sample number says it belongs, and what is lost -- a gap between
+    two frames, a frame that does not decode -- is zero (flacgpu_decoder_scan_frames_ex + flacgpu_decoder_decode_timeline).
+
+    Returns (batch, mask, results, frames): `batch` is [B, C, T], planar and zero-padded, in `dtype` as for decode_many
+    ("int24": uint8 [B, C, T, 3]) -- a torch tensor on the GPU for out="device", a numpy array for out="host" -- with
+    T = pad_to or the longest timeline and C = pad_channels or the most channels; `mask` is uint8 [B, T], 1 where a
+    decoded sample stands (None with mask=False); results[i] is the _lib.TimelineResult of stream i (rc != 0: the stream
+    has no timeline and is a row of zeros; first_sample: the position of batch[i, :, 0] in the stream); `frames` is a
+    TIMELINE_FRAME_DTYPE array beside the scan's records (Decoder.scan_frames(...)[3])."""
+    if out not in ("device", "host"):
+        raise ValueError("out must be 'device' or 'host'")
+    if dtype not in _DTYPES:
+        raise ValueError("dtype must be 'int32', 'int16', 'int24' or 'float32'")
+    if out == "device":
+        import torch
+
+        torch.cuda.init()   # torch's HIP runtime first, as in decode_many
+    own = decoder is None
+    dec = Decoder(device) if own else decoder
+    try:
+        _, _, raw, records = dec.scan_frames(blobs, speculative)
+        n = len(blobs)
+        fmt = _lib.OutFormat(_DTYPES[dtype], _lib.LAYOUT_PADDED, pad_channels or 0, 0, pad_to or 0)
+        if pad_to is None or pad_channels is None:   # the batch's own maxima, from the plan
+            plan = dec.plan_timeline(fmt, check=False)[0]
+            ok = [i for i in range(n) if plan[i].rc == 0]
+            if pad_to is None:
+                fmt.samples_padded = max([plan[i].timeline_samples for i in ok], default=0)
+            if pad_channels is None:
+                fmt.channels_padded = max([int(records["channels"][raw[i].first_frame]) for i in ok], default=0)
+        _, need, mask_need = dec.plan_timeline(fmt)   # refuses before anything is allocated
+        array_dtype, shape = _element_array(dtype, (n, fmt.channels_padded, fmt.samples_padded))
+        mshape = (n, fmt.samples_padded)
+        if out == "device":
+            dev = dec.device if dec.device >= 0 else torch.cuda.current_device()
+            buf = torch.empty(shape, dtype=getattr(torch, array_dtype), device=f"cuda:{dev}")
+            m = torch.empty(mshape, dtype=torch.uint8, device=f"cuda:{dev}") if mask else None
+            torch.cuda.synchronize(dev)
+            results, frames = dec.decode_timeline(buf.data_ptr() if need else None, need,
+                                                  m.data_ptr() if mask and mask_need else None, mask_need if mask else 0,
+                                                  fmt, _lib.DECODE_OUT_DEVICE)
+        else:
+            buf = np.empty(shape, dtype=array_dtype)
+            m = np.empty(mshape, dtype=np.uint8) if mask else None
+            results, frames = dec.decode_timeline(buf.ctypes.data if need else None, need,
+                                                  m.ctypes.data if mask and mask_need else None, mask_need if mask else 0,
+                                                  fmt, 0)
+    finally:
+        if own:
+            dec.close()
+    return buf, m, list(results)[:n], frames
 
 
 def decode_windows(decoder, recs, windows, dtype="float32", out="device", pad_to=None, pad_channels=None):

@@ -725,6 +725,74 @@ int flacgpu_decoder_frame_records(flacgpu_decoder *d, flacgpu_frame_record *reco
 int flacgpu_decoder_decode_frames(flacgpu_decoder *d, int32_t *out, size_t out_cap_elements, uint32_t flags,
                                   flacgpu_frame_record *records, size_t cap);
 
+/* ---- batch decoder: raw frame streams on a timeline, lost frames zero-filled -----------------------------------------
+ * The kept frames of every stream of a raw scan, each put where its coded number says it belongs; what no frame covers
+ * is zero, and so is a frame that does not decode.  The rule (DESIGN.md 4b "Timeline"), for the records r_0 .. r_{m-1}
+ * of one stream in scan order:
+ *   status    rc of the stream: m == 0 FLACGPU_ERR_INVALID_ARG; records that differ in sample rate, channels or sample
+ *             size, or in `blocking`, FLACGPU_ERR_UNSUPPORTED; blocking 0 with m >= 2 and B = r_0.block_size: some r_k,
+ *             k < m - 1, with block_size != B, or r_{m-1}.block_size > B, FLACGPU_ERR_UNSUPPORTED (a stream whose frame
+ *             numbers count frames, not time: FlacStreamWriter called with different lengths).  A refused stream is all
+ *             zero in the output and the mask and does not fail the call; flacgpu_last_error names the first such
+ *             stream and its reason after a call that returns FLACGPU_OK.
+ *   position  p_k = number_k (blocking 1) or number_k * B (blocking 0; B = r_0.block_size), in 64 bits.
+ *   walk      r_0 is PLACED, origin = p_0, end = p_0 + n_0.  For k = 1 ..: p_k < end: the frame is DROPPED (a duplicate,
+ *             a re-ordered frame, a wrapped number) and not decoded; else it is PLACED at row position at_k = p_k -
+ *             origin, and end = p_k + n_k.  first_sample = origin, timeline_samples = end - origin; gaps is the number
+ *             of maximal runs of row positions in [0, timeline_samples) that no placed frame covers, gap_samples their
+ *             sum.
+ *   conceal   a placed frame whose decode_frames status would not be 0 is CONCEALED: its n_k samples are zero in every
+ *             channel.  The device decides this from its own per-frame counts; the host learns it afterwards.
+ *   output    FLACGPU_LAYOUT_PADDED alone: [n_streams][channels_padded][samples_padded] in fmt->dtype with decode_as's
+ *             conversions.  Element [i][c][t] is the sample at at_k <= t < at_k + n_k of a placed, unconcealed frame for
+ *             c < channels; every other element is zero.  mask (may be NULL): uint8 [n_streams][samples_padded], 1
+ *             exactly where channel 0 holds a decoded sample.  After FLACGPU_OK every byte of out_bytes and mask_bytes
+ *             is defined, whatever the buffers held before.  No MD5 is computed.
+ *   timeline_host   the rule for one stream's records on the host alone (no device, no handle).  frames_out (may be
+ *                   NULL; cap >= n_records, else FLACGPU_ERR_BUFFER_TOO_SMALL and nothing written) gets one entry per
+ *                   record: at, flags PLACED or DROPPED, status 0 (all zero for a refused stream).  The stream's status
+ *                   is result->rc; the call itself fails only for NULL arguments.
+ *   plan_timeline   the checks and the sizes for the handle's last raw scan; launches nothing.  results (n_streams of
+ *                   the scan) is filled first, also when the call is then refused, so that the caller sizes the tensor
+ *                   from timeline_samples.  Refused: no raw scan, unknown dtype, reserved != 0, a layout other than
+ *                   PADDED, samples_padded below the longest timeline_samples or channels_padded below the most channels
+ *                   of an rc == 0 stream (FLACGPU_ERR_INVALID_ARG); I16 with an rc == 0 stream of more than 16 bits, S24
+ *                   with one of more than 24 (FLACGPU_ERR_UNSUPPORTED, flacgpu_last_error names the stream).
+ *                   *mask_bytes (may be NULL) = n_streams * samples_padded.
+ *   decode_timeline plan_timeline's checks, then the decode.  flags: FLACGPU_DECODE_OUT_DEVICE alone; mask lives where
+ *                   out lives.  frames (may be NULL; frames_cap >= the scan's total_frames) gets one entry per record of
+ *                   the batch: timeline_host's, with FLACGPU_TL_CONCEALED and the decode_frames status of a placed
+ *                   frame.  A refused call (the above, out_cap_bytes / mask_cap_bytes / frames_cap too small:
+ *                   FLACGPU_ERR_BUFFER_TOO_SMALL, a misaligned out) writes nothing.  Device scratch is sized by the
+ *                   placed frames.  It may follow or precede decode, decode_as, decode_windows and decode_frames on one
+ *                   scan, in any order.
+ * Gaps and concealed frames are zeroed on the device by runs of at most FLACGPU_TIMELINE_PIECE_BYTES bytes, one
+ * workgroup each (flacgpu_timeline_piece_bytes returns the constant the library was built with). */
+#define FLACGPU_TL_PLACED    1u
+#define FLACGPU_TL_DROPPED   2u
+#define FLACGPU_TL_CONCEALED 4u  /* with PLACED, after a decode */
+#define FLACGPU_TIMELINE_PIECE_BYTES 12288u
+typedef struct {            /* 16 bytes */
+    uint64_t at;            /* row position of a placed frame's first sample; 0 otherwise */
+    uint32_t flags;         /* FLACGPU_TL_*; 0 for every frame of a refused stream */
+    uint32_t status;        /* decode_timeline, placed frames: decode_frames' status bits; else 0 */
+} flacgpu_timeline_frame;
+typedef struct {            /* 56 bytes */
+    int32_t  rc;            /* the stream's status */
+    uint32_t placed, dropped, concealed, gaps;
+    uint32_t reserved;
+    uint64_t first_sample;  /* origin: the position of row element 0 */
+    uint64_t timeline_samples, gap_samples, concealed_samples;
+} flacgpu_timeline_result;
+int flacgpu_timeline_host(const flacgpu_frame_record *records, size_t n_records, flacgpu_timeline_frame *frames_out,
+                          size_t cap, flacgpu_timeline_result *result);
+uint32_t flacgpu_timeline_piece_bytes(void);
+int flacgpu_decoder_plan_timeline(flacgpu_decoder *d, const flacgpu_out_format *fmt, flacgpu_timeline_result *results,
+                                  uint64_t *out_bytes, uint64_t *mask_bytes);
+int flacgpu_decoder_decode_timeline(flacgpu_decoder *d, void *out, size_t out_cap_bytes, uint8_t *mask,
+                                    size_t mask_cap_bytes, const flacgpu_out_format *fmt, uint32_t flags,
+                                    flacgpu_timeline_result *results, flacgpu_timeline_frame *frames, size_t frames_cap);
+
 /* ---- the encoder's ingest pass: a device tensor -> interleaved int32 the encoder reads in place ----------------------
  * The device half of flacenc_encode_many_device (include/flacenc_stream.h), the mirror image of
  * flacgpu_decoder_decode_as: a batch of streams of one shape held in device memory as int32, int16, packed 24-bit or float32, planar and

@@ -20,6 +20,16 @@ over flacgpu_decode_stream and the oracle's CPU decoder on one core; writes prof
     python tools/decode_many_probe.py --raw --speculative --label this_2
     python tools/decode_many_probe.py --raw --speculative --kernels-only
 
+    python tools/decode_many_probe.py --timeline --label this_1 [--out profiles/r16_timeline.json] [--reps 15]
+    python tools/decode_many_probe.py --timeline --label parent --package-root DIR   (the decode_as leg only)
+    python tools/decode_many_probe.py --timeline --label this_2
+    python tools/decode_many_probe.py --timeline --kernels-only
+
+--timeline (flacgpu_decoder_decode_timeline): on the clips with the metadata stripped, float32, device output, handle
+warm, the wall time of scan_frames + decode_as (padded; the parent's call for such a batch) and of scan_frames +
+decode_timeline with the mask, undamaged and with one frame in 50 removed by a fixed seed.  The undamaged timeline is
+held to the parent's own min-max spread of its decode_as leg; the damaged leg has no parent and is reported as it is.
+
 --raw (flacgpu_decoder_scan_frames): on the clips, device output, no MD5, handle warm, the wall time of (regular) scan +
 decode of the files as they are and (raw) scan_frames + decode of the same files with the fLaC marker and metadata
 removed; both must give the same PCM, and its SHA-256 must be the same under every label.  Every leg reads the shader
@@ -489,6 +499,107 @@ def raw_frames(args):
     print(json.dumps({args.label: rec, "verdict": res.get("verdict")}, indent=1), flush=True)
 
 
+def timeline(args):
+    """The --timeline leg (see the module docstring)."""
+    import hashlib
+    import random
+
+    import torch
+
+    from flac_codec_amd import _lib, gpu
+    from flac_codec_amd.gpu import Decoder, decode_many, scan_frames_host, scan_stream_host
+
+    blobs = make_blobs("clips")
+    bare = [b[int(scan_stream_host(b)[1][0]):] for b in blobs]   # from the first frame on
+    has_tl = hasattr(gpu, "decode_timeline") and args.label != "parent"
+    dec = Decoder(0)
+    legs = {"raw_scan_frames_decode_as": lambda: decode_many(bare, out="device", verify_md5=False, decoder=dec, raw=True,
+                                                             dtype="float32", layout="padded")[0]}
+    tl_legs = {}
+    made = {}
+
+    def damaged_batch():   # one frame in 50 removed, by a fixed seed; built behind the legs the parent has too
+        if not made:
+            rng, cache = random.Random(20261019), {}
+            for b in bare:
+                if b not in cache:
+                    recs = scan_frames_host(b)[0]
+                    lost = {k for k in range(len(recs)) if rng.randrange(50) == 0} or {len(recs) // 2}
+                    cache[b] = (b"".join(b[int(r["byte_offset"]):int(r["byte_offset"]) + int(r["bytes"])]
+                                         for k, r in enumerate(recs) if k not in lost), len(recs), len(lost))
+            made["blobs"] = [cache[b][0] for b in bare]
+            made["frames"] = sum(cache[b][1] for b in bare)
+            made["lost"] = sum(cache[b][2] for b in bare)
+        return made["blobs"]
+
+    if has_tl:
+        tl_legs["timeline_undamaged"] = lambda: gpu.decode_timeline(bare, decoder=dec)[:2]
+        tl_legs["timeline_one_frame_in_50_lost"] = lambda: gpu.decode_timeline(damaged_batch(), decoder=dec)[:2]
+    if args.kernels_only:
+        for fn in list(legs.values()) + list(tl_legs.values()):
+            fn()
+            fn()
+        torch.cuda.synchronize()
+        dec.close()
+        return
+    res = {"tool": "tools/decode_many_probe.py --timeline", "workload": "clips: 1024 x 10 s, 16 kHz mono 16-bit, metadata "
+           "stripped", "device_output": True, "dtype": "float32", "mask": True, "order": [], "runs": {}}
+    if os.path.exists(args.out):
+        with open(args.out) as f:
+            res = json.load(f)
+    pcm = legs["raw_scan_frames_decode_as"]()
+    rec = {"build_id": _lib.build_id(), "pcm_sha256": hashlib.sha256(pcm.cpu().numpy().tobytes()).hexdigest(), "legs": {}}
+    for other in res["runs"].values():
+        assert other["pcm_sha256"] == rec["pcm_sha256"]   # the same samples under every label
+
+    def timed(legs):
+        for name, fn in legs.items():
+            fn()
+            torch.cuda.synchronize()   # warm: buffers grown, code loaded
+            sclk_before = _sclk_mhz()
+            times = []
+            for _ in range(args.reps):
+                t0 = time.perf_counter()
+                out = fn()
+                torch.cuda.synchronize()
+                times.append(time.perf_counter() - t0)
+            rec["legs"][name] = dict(_spread(times), sclk_mhz_before=sclk_before, sclk_mhz_after=_sclk_mhz())
+            del out
+
+    timed(legs)   # first, in a process that has done nothing the parent's has not
+    if has_tl:
+        batch, mask, results, _ = gpu.decode_timeline(bare, decoder=dec)
+        assert torch.equal(batch, pcm) and all(r.rc == 0 and r.gaps == 0 for r in results)   # identical samples
+        assert int(mask.sum()) == sum(r.timeline_samples for r in results)
+        damaged = damaged_batch()
+        batch, mask, results, frames = gpu.decode_timeline(damaged, decoder=dec)
+        assert all(r.rc == 0 for r in results) and len(frames) == made["frames"] - made["lost"]
+        rec["damaged"] = {"frames": made["frames"], "frames_removed": made["lost"],
+                          "gaps": int(sum(r.gaps for r in results)), "gap_samples": int(sum(r.gap_samples for r in results)),
+                          "timeline_samples": int(sum(r.timeline_samples for r in results)),
+                          "mask_ones": int(mask.sum())}
+        del batch, mask
+        timed(tl_legs)
+    del pcm
+    dec.close()
+    res["runs"][args.label] = rec
+    res["order"].append(args.label)
+    runs = res["runs"]
+    if all(k in runs for k in ("this_1", "parent", "this_2")):
+        allow = runs["parent"]["legs"]["raw_scan_frames_decode_as"]
+        res["verdict"] = {"allowance_parent_min_s": allow["min_s"], "allowance_parent_max_s": allow["max_s"],
+                          "parent_median_s": allow["median_s"]}
+        for label in ("this_1", "this_2"):
+            for name in ("raw_scan_frames_decode_as", "timeline_undamaged"):   # the damaged leg has no parent
+                leg = runs[label]["legs"][name]
+                res["verdict"][f"{label}.{name}"] = {
+                    "median_s": leg["median_s"], "inside_parent_spread": allow["min_s"] <= leg["median_s"] <= allow["max_s"],
+                    "over_parent_median": leg["median_s"] / allow["median_s"]}
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps({args.label: rec, "verdict": res.get("verdict")}, indent=1), flush=True)
+
+
 def windows(args):
     """The --windows leg (see the module docstring)."""
     import torch
@@ -611,7 +722,8 @@ def merge_stats(args):
                                "avg_ms": float(r["AverageNs"]) / 1e6}
     mine = {k: v for k, v in rows.items() if any(s in k for s in ("k_scan_", "k_link", "k_decode_many", "k_frame_crc",
                                                                    "k_finish_many", "k_md5_many", "k_finish_as",
-                                                                   "k_pad_rows", "k_finish_window", "k_spec_end"))}   # (k_scan_ and k_link cover the raw kernels)
+                                                                   "k_pad_rows", "k_finish_window", "k_spec_end",
+                                                                   "k_fill_runs"))}   # (k_scan_ and k_link cover the raw kernels)
     res.setdefault("kernel_stats", {})[args.stats_label] = mine
     with open(args.out, "w") as f:
         json.dump(res, f, indent=1)
@@ -629,6 +741,7 @@ def main():
     ap.add_argument("--raw", action="store_true", help="the raw frame stream leg: profiles/r13_raw_frames.json")
     ap.add_argument("--speculative", action="store_true",
                     help="with --raw: add the FLACGPU_SCAN_SPECULATIVE leg, profiles/r14_speculative.json")
+    ap.add_argument("--timeline", action="store_true", help="the timeline leg: profiles/r16_timeline.json")
     ap.add_argument("--shrink", type=int, default=1, help="--s24: divide the clip count")
     ap.add_argument("--label", default="this", help="--formats: the run's name in the file (parent: the default int32 "
                     "leg only; any other name: every leg)")
@@ -639,7 +752,8 @@ def main():
     ap.add_argument("--kernels-only", action="store_true", help="one warm decode per workload (for rocprofv3)")
     args = ap.parse_args()
     if not args.out:
-        args.out = os.path.join(ROOT, "profiles", "r14_speculative.json" if args.raw and args.speculative else
+        args.out = os.path.join(ROOT, "profiles", "r16_timeline.json" if args.timeline else
+                                "r14_speculative.json" if args.raw and args.speculative else
                                 "r13_raw_frames.json" if args.raw else
                                 "r10_decode_windows.json" if args.windows else
                                 "r12_s24.json" if args.s24 else
@@ -653,6 +767,8 @@ def main():
     import torch
 
     torch.cuda.init()   # before the library's first HIP call (else torch sees no GPU)
+    if args.timeline:
+        return timeline(args)
     if args.raw:
         return raw_frames(args)
     if args.formats and args.s24:
