@@ -62,7 +62,8 @@ extern "C" void flacgpu_early_download_counters(uint64_t *queued, uint64_t *with
 // compute_best_order's estimate (encode.rs:3675: ln(err / 2n) / 2 ln 2 = log2(sigma) - 0.5) lies 2.5-2.9 bits per sample under
 // what Rice coding makes of the residual, so 3 bits defer only candidates that are then decided by the bound (measured,
 // profiles/r05_defer_fixed.json: 0.6 % of the deferred candidates of the high-order input take the re-read, none of SURVEY's
-// input defers at all; at 2 bits every candidate of SURVEY's input deferred and re-read: +11 % on the kernel)
+// input defers at all; at 2 bits every candidate of SURVEY's input deferred and re-read: +11 % on the kernel).  With the tight
+// bound (profiles/leaf_bound_tight.json) SURVEY's input defers at these 3 bits and every deferred candidate is decided.
 static constexpr uint32_t kDeferMargin16 = 48;
 static constexpr uint32_t kDeferWords = DEFER_SLOTS * DEFER_SLOT_WORDS;   // Params::defer_stats
 static constexpr uint32_t kTurnWords = 4;   // Params::turn_counter words in front of the counters (16-byte aligned counters behind them)
@@ -81,7 +82,7 @@ Knobs read_knobs() {
     k.no_frame64 = on("FLACGPU_NO_FRAME64");
     k.early_download = on("FLACGPU_EARLY_DOWNLOAD");
     if (const char *e = getenv("FLACGPU_CAND_GRID")) k.cand_grid = (uint32_t)atoi(e);
-    // A/B: Params::defer_fixed (0 never, 1 by the estimate, 2 whenever LPC parameters exist) and its margin in 1/16 bit per
+    // A/B: Params::defer_fixed (0 never, 1 by the estimate, 2 / 3 whenever LPC parameters exist) and its margin in 1/16 bit per
     // sample -- neither changes a byte of output
     if (const char *e = getenv("FLACGPU_DEFER_FIXED")) k.defer_fixed = atoi(e);
     if (const char *e = getenv("FLACGPU_DEFER_MARGIN16")) k.defer_margin16 = atoi(e);

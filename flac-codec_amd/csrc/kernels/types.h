@@ -130,8 +130,11 @@ struct Params {
     // LOWER BOUND of the FIXED residual block's size follows at any partition order (wave_cand_fixed.inc).  When K4's size
     // estimate of the LPC candidate (LpcParams::est8, 1/8 bit per sample) undercuts that bound by defer_margin16 / 16 bit per
     // sample, the wave runs the LPC half first; an exact lpc_bits < bound then DECIDES encode.rs:2929-2934 for LPC without
-    // tree or count, otherwise the wave builds the tree, re-fetches its samples and counts after all.  0: never (A/B), 1: by
-    // the estimate, 2: whenever LPC parameters exist (TEST: every undecided candidate takes the re-fetch).
+    // tree or count, otherwise the wave builds the tree, re-fetches its samples and counts after all.  Where the leaf sums'
+    // bound does not reach the estimate but a bound one bit per residual higher would, the wave takes one more pass over its
+    // FIXED residual for the TIGHT bound (two exact quotient sums per leaf, wave_cand_fixed.inc).  0: never (A/B), 1: by
+    // the estimate, 2: whenever LPC parameters exist, on the leaf sums' bound (TEST: every undecided candidate takes the
+    // re-fetch), 3: the same on the tight bound (TEST).
     // defer_stats: {waves that deferred, of those: re-fetched}, cumulative.
     uint32_t defer_fixed, defer_margin16;
     uint32_t *defer_stats;   // [DEFER_SLOTS][DEFER_SLOT_WORDS]: the pair {deferred, re-fetched} per slot
@@ -238,7 +241,7 @@ struct Knobs {
     bool has_tie_band = false, has_tie_perturb = false;
     double tie_band = 0.0, tie_perturb = 0.0;   // TEST
     uint32_t fir_suspect_bits = 0;      // TEST: Params::fir_suspect_bits, 0: default (30)
-    int defer_fixed = -1;               // FLACGPU_DEFER_FIXED: 0 / 1 / 2 (Params::defer_fixed); -1: default (1)
+    int defer_fixed = -1;               // FLACGPU_DEFER_FIXED: 0 / 1 / 2 / 3 (Params::defer_fixed); -1: default (1)
     int defer_margin16 = -1;            // FLACGPU_DEFER_MARGIN16: Params::defer_margin16; -1: default
 };
 Knobs read_knobs();   // flacenc_gpu.hip

@@ -321,6 +321,36 @@ __device__ __forceinline__ WaveRice wave_rice_exact_gen(const RiceTree &t, Src s
     w.ok = !__any(wide);
     return w;
 }
+// Params::defer_fixed, the TIGHT bound (wave_cand_fixed.inc): one pass over the regenerated FIXED residual of the lane's leaf for
+// ysum = sum (t >> sh) and odd = the number of odd quotients among them, so that sum (t >> (sh + 1)) = (ysum - odd) / 2 is
+// exact as well -- two neighbouring Rice parameters from one shift per sample.  The quotients' low bits are collected 32 to a
+// register (v_alignbit_b32 shifts one in at the top) and counted twice per pass.  sh is per lane; warm-up entries count as zero.
+template <int SPL, int MAXORD, class Src>
+__device__ __forceinline__ void wave_leaf_quotients(Src src, uint32_t order, uint32_t sh, uint32_t &ysum, uint32_t &odd) {
+    static_assert(SPL % 32 == 0, "the low bits are counted 32 at a time");
+    const bool lane0 = (threadIdx.x & 63) == 0;
+    uint32_t acc = 0, low = 0, cnt = 0;
+    src.reset();
+#pragma unroll
+    for (int e = 0; e < SPL; e++) {
+        int32_t r = src.resid(e);
+        if (e < MAXORD) r = (lane0 && (uint32_t)e < order) ? 0 : r;  // warm-up: no residual
+        // (the fold commutes with the arithmetic shift: r < 0 is ~t, and ~t >> sh = ~(t >> sh))
+        const uint32_t y = (uint32_t)((r >> sh) ^ (r >> 31));
+        acc += y;
+        // (as an opaque instruction: the builtin is a funnel shift the optimiser sees through -- it rebuilds the 32 bits as
+        // a tree of and / shift / or over all 64 quotients, which are then alive together)
+        asm("v_alignbit_b32 %0, %1, %0, 1" : "+v"(low) : "v"(y));
+        if ((e & 31) == 31) cnt += (uint32_t)__builtin_popcount(low);
+        if ((e & 7) == 7) {
+            // pin the partial sum: left alone, the quotients are kept (in scratch) and added up behind the pass
+            asm volatile("" : "+v"(acc));
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    ysum = acc;
+    odd = cnt;
+}
 // first pass over a stored residual: fold in place, sum |r| of this lane (= sum_t + neg)
 // SIGNS (Params::hand_meta): a[e] keeps r's sign in bit 31 beside t (t < 2^31; one v_and_or_b32 per sample) -- zigzag(r) is then
 // a[e] rotated left by one, which is what k_frame64 makes of the words the winning wave hands over

@@ -121,27 +121,81 @@
         }
         const uint64_t reach64 = (uint64_t)fixed_head + 10u + (uint64_t)kt * N + ((2 * stot) >> kt);
         const uint32_t reach = reach64 > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)reach64;
-        if (p.defer_fixed == 2 || need <= reach) {
+        // The TIGHT bound (whole leaves of 64 samples; tests/test_leaf_bound_tight_math.py, the same arithmetic in numpy in
+        // tests/_leaf_bound_tight.py): the leaf sums cannot know sum (u mod 2^k) and give away half a bit per residual, as much
+        // as LPC gains over FIXED on a low-order signal.  Where the bound above does not get there, one more pass over the
+        // FIXED residual gives the leaf's quotient sums at its own k (the rule's, from its sum) and at k - 1 EXACTLY
+        // (wave_leaf_quotients): the leaf's cost at those two is known, at k + 1 it is at least c (k + 2) + ceil((Q - c) / 2)
+        // (a quotient halves to no less than (q - 1) / 2), further up no less than that (Q <= 2 c under the rule's k), at
+        // k - 1 - d at least c (k - d) + 2^d Q' (a quotient at least doubles per step down; the d that minimises it: the first
+        // with 2^d Q' >= c); an escaped partition costs its leaf more than c (k + 3) >= the exact cost at k (its escape_bits
+        // are ilog2 of a sum >= S, plus 2), the 31-bit fallback 31 c.  The minimum of these bounds the leaf under ANY
+        // parameter, and a partition of several leaves has one parameter: it costs at least the sum of their minima.
+        // It can reach one bit per residual above the leaf sums' bound (Q <= 2 S / 2^k, where that one has 2 S / 2^k - c).
+        constexpr bool TIGHT = SPL == 64;
+        const uint32_t reach_t = TIGHT ? (reach > 0xFFFFFFFFu - N ? 0xFFFFFFFFu : reach + N) : reach;
+        if (p.defer_fixed >= 2 || need <= reach_t) {
             // (an opaque copy of the leaf sum, made HERE: otherwise the per-lane part below is speculated above the two
             // wave-uniform tests and every candidate pays for it)
             uint32_t fl_lo = (uint32_t)fleaf, fl_hi = (uint32_t)(fleaf >> 32);
             asm volatile("" : "+v"(fl_lo), "+v"(fl_hi));
             const uint64_t fl = ((uint64_t)fl_hi << 32) | fl_lo;
             const uint32_t lcnt = (uint32_t)SPL - (lane == 0 ? forder : 0u);
-            uint32_t lbl;
+            uint32_t lbl, k = 0;
             if (fl >> 40) {
                 lbl = 0u;   // (no such sums from <= 32-bit residuals of 64 samples)
             } else if (fl <= (uint64_t)lcnt) {
                 lbl = (uint32_t)(2 * fl);
             } else {
                 const uint32_t bs = 64u - (uint32_t)__clzll((long long)fl), bc = 32u - (uint32_t)__builtin_clz(lcnt);
-                uint32_t k = bs > bc ? bs - bc - 1 : 0;
+                k = bs > bc ? bs - bc - 1 : 0;
                 k += (((uint64_t)lcnt << k) < fl) ? 1u : 0u;
                 k += (((uint64_t)lcnt << k) < fl) ? 1u : 0u;
                 lbl = k * lcnt + (uint32_t)((2 * fl) >> k) - 6u;   // (ceil(0.0861 * 64) = 6; k c >= 12 here)
             }
-            const uint32_t lb0 = fixed_head + 10u + wave_total_u32(lbl);
-            if (p.defer_fixed == 2 || need <= lb0) {   // (2, TEST: every candidate with LPC parameters)
+            uint32_t lb0 = fixed_head + 10u + wave_total_u32(lbl);
+            // (2, TEST: every candidate with LPC parameters, on the leaf sums' bound; 3, TEST: the same on the tight one)
+            bool go = p.defer_fixed == 2 || (p.defer_fixed == 1 && need <= lb0);
+            if constexpr (TIGHT) {
+                if (!go) {   // wave-uniform (1: need <= reach_t holds here)
+                    const uint32_t rice_max = p.use_rice2 ? 31u : 15u;
+                    const uint32_t sh = k >= 2u ? k - 2u : 0u;
+                    uint32_t ys = 0, odd = 0;
+                    switch (forder) {
+                    case 0: wave_leaf_quotients<SPL, 4>(FixedSrc<0, SPL>{x, h}, 0, sh, ys, odd); break;
+                    case 1: wave_leaf_quotients<SPL, 4>(FixedSrc<1, SPL>{x, h}, 1, sh, ys, odd); break;
+                    case 2: wave_leaf_quotients<SPL, 4>(FixedSrc<2, SPL>{x, h}, 2, sh, ys, odd); break;
+                    case 3: wave_leaf_quotients<SPL, 4>(FixedSrc<3, SPL>{x, h}, 3, sh, ys, odd); break;
+                    default: wave_leaf_quotients<SPL, 4>(FixedSrc<4, SPL>{x, h}, 4, sh, ys, odd); break;
+                    }
+                    // k >= 2: ys = sum (u >> (k - 1)), odd its odd terms; k < 2: ys = sum t, and sum u = S + sum t
+                    const uint32_t s32 = (uint32_t)fl;
+                    const uint32_t q0 = k >= 2u ? (ys - odd) >> 1 : k == 1u ? ys : s32 + ys;    // sum (u >> k)
+                    const uint32_t qm = k >= 2u ? ys : s32 + ys;                                // sum (u >> (k - 1)), k >= 1
+                    uint32_t lt = lcnt * (k + 1u) + q0;
+                    if (k + 1u < rice_max) {
+                        const uint32_t up = q0 > lcnt ? (q0 - lcnt + 1u) >> 1 : 0u;
+                        lt = min(lt, lcnt * (k + 2u) + up);
+                    }
+                    if (k >= 1u) {
+                        // the first d with qm << d >= c, at most k - 1 (qm = 0: k - 1)
+                        const uint32_t bq = 32u - (uint32_t)__builtin_clz(qm | 1u), bc = 32u - (uint32_t)__builtin_clz(lcnt);
+                        uint32_t d = bc > bq ? bc - bq : 0u;
+                        d += ((qm << d) < lcnt) ? 1u : 0u;
+                        d = qm == 0u ? k - 1u : min(d, k - 1u);
+                        lt = min(lt, lcnt * (k - d) + (qm << d));
+                    }
+                    // (an all-zero leaf costs nothing; a leaf whose rule asks for an escape, or with an impossible sum,
+                    // keeps the leaf sums' bound; no leaf costs more than in the 31-bit fallback partition)
+                    if (s32 == 0u && fl_hi == 0u) lt = 0u;
+                    if (k >= rice_max || (fl >> 40)) lt = lbl;
+                    lt = min(lt, 31u * lcnt);
+                    const uint32_t lbt = fixed_head + 10u + wave_total_u32(lt);
+                    lb0 = max(lb0, lbt);
+                    go = p.defer_fixed == 3 || need <= lb0;
+                }
+            }
+            if (go) {
                 defer = true;
                 fixed_lb = lb0;
             }

@@ -112,7 +112,8 @@ def mix(blocks):
 
 
 def pick_cand(blocks, taps, fixed_subs):
-    """representative path of a candidate wave: the order statistics, ONE exact FIXED pass (the t >> (k-1) form of
+    """representative path of a candidate wave: the order statistics, ONE pass over the FIXED residual (the exact count in
+    the t >> (k-1) form, or the tight bound's quotient pass in its place where the kernel has one, of
     the fixed order the data mostly takes: `fixed_subs` subtractions per sample), ONE FIR instantiation (`taps`
     64-bit multiply-adds per sample), the fold / exact pass of the LPC residual, and every small block once"""
     chosen = []
@@ -134,9 +135,13 @@ def pick_cand(blocks, taps, fixed_subs):
         if big and n["v_lshrrev_b32_e32"] >= 60 and n["v_xor_b32_e32"] < 8 and subs < 8 and n["v_add3_u32"] >= 16:
             chosen.append((name, ins, inner))                # exact pass over the stored (folded) residual
             continue
-        if big and n["v_xor_b32_e32"] >= 60 and n["v_ashrrev_i32_e32"] >= 60:   # an exact FIXED pass
+        if big and n["v_xor_b32_e32"] >= 60 and n["v_ashrrev_i32_e32"] >= 60:   # an exact FIXED pass, or the tight bound's
+            # quotient pass (one v_alignbit_b32 per sample): where the kernel can defer, the bench's candidates are decided by
+            # the bound -- they run the quotient pass and skip the exact one (profiles/leaf_bound_tight.json)
+            quotients = n["v_alignbit_b32"] >= 60
+            has_quotients = any(Counter(t.split()[0] for t in i2)["v_alignbit_b32"] >= 60 for _, i2, _ in blocks)
             # K subtractions per sample (the first sample of a lane saves one), shift form without v_lshlrev (k >= 1)
-            if abs(subs - 64 * fixed_subs) <= 2 and n["v_lshlrev_b32_e32"] < 8:
+            if abs(subs - 64 * fixed_subs) <= 2 and n["v_lshlrev_b32_e32"] < 8 and quotients == has_quotients:
                 chosen.append((name, ins, inner))
             continue
         if big and (n["v_or3_b32"] >= 16 or n["v_lshlrev_b32_e32"] >= 60):

@@ -69,11 +69,13 @@ def main():
         mid_side, exhaustive = bool(rng.integers(2)), bool(rng.integers(2))
         for k in ("FLACGPU_DEFER_FIXED",):
             os.environ.pop(k, None)
-        mode = int(rng.integers(4))
+        mode = int(rng.integers(5))
         if mode == 0:
             os.environ["FLACGPU_DEFER_FIXED"] = "2"
         elif mode == 1:
             os.environ["FLACGPU_DEFER_FIXED"] = "0"
+        elif mode == 4:
+            os.environ["FLACGPU_DEFER_FIXED"] = "3"   # every candidate defers on the tight bound
         nmax = int(rng.integers(1, 40))
         an = GpuAnalyzer(B, 6, max_lpc, mid_side, exhaustive, 2, 0.5, bps, 2, max_frames=nmax)
         oopts = orc_options_for(B, 6, max_lpc, mid_side, exhaustive)
