@@ -266,6 +266,14 @@ def _load():
     L.flacgpu_decoder_scan_frames_ex.argtypes = [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_uint32, C.c_uint32,
                                                  C.POINTER(DecodedStream), C.POINTER(RawStream), C.POINTER(C.c_uint64),
                                                  C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.flacgpu_decoder_scan_device.argtypes = [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_uint32, vp,
+                                              C.POINTER(DecodedStream), C.POINTER(C.c_uint64)]
+    L.flacgpu_decoder_scan_frames_device.argtypes = [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_uint32,
+                                                     C.c_uint32, vp, C.POINTER(DecodedStream), C.POINTER(RawStream),
+                                                     C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.flacgpu_decoder_slot_bytes.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_uint64)]
+    L.flacgpu_meta_walk_host.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(StreamInfo), C.POINTER(C.c_uint32),
+                                         C.POINTER(C.c_uint64)]
     L.flacgpu_decoder_frame_records.argtypes = [vp, C.POINTER(FrameRecord), C.c_size_t]
     L.flacgpu_decoder_decode_frames.argtypes = [vp, vp, C.c_size_t, C.c_uint32, C.POINTER(FrameRecord), C.c_size_t]
     L.flacgpu_timeline_host.argtypes = [C.POINTER(FrameRecord), C.c_size_t, C.POINTER(TimelineFrame), C.c_size_t,

@@ -1,10 +1,12 @@
 // decode_many.hip -- batch decoder: many FLAC streams in one call, metadata parsed by flacgpu_decode_stream's parser
 // (host/flac_stream.cpp), frames found and decoded, samples hashed (MD5) on the device (include/flacenc_gpu.h "batch decoder").
 // One of the translation units of libflacenc_amd.so (gfx950 only).  Kernels: kernels/frame_scan.inc (frame discovery)
-// and kernels/decode_many.inc (decode, CRC-16, finish, MD5); the subframe decoder is decode.inc's, unchanged.
+// and kernels/decode_many.inc (decode, CRC-16, finish, MD5); the subframe decoder is decode.inc's, unchanged.  Streams
+// that already lie in device memory come in through kernels/gather.inc (DESIGN.md 4b "Device-resident input").
 #include "kernels/types.h"
 #include "kernels/sample_types.h"
 #include "kernels/frame_extent.h"
+#include "kernels/meta_walk.h"
 #include "flac_stream.h"
 
 #include <stdlib.h>
@@ -21,6 +23,7 @@ namespace {
 #include "kernels/crc16.inc"
 #include "kernels/frame_scan.inc"
 #include "kernels/spec_end.inc"
+#include "kernels/gather.inc"
 #include "kernels/decode_many.inc"
 
 constexpr uint32_t kSlotTail = 64;   // zero bytes behind every stream's region (at least)
@@ -29,6 +32,17 @@ constexpr uint32_t kSlotTail = 64;   // zero bytes behind every stream's region 
 // least one block that block lies inside the stream's own slot, its prefix covers the slot's bytes alone, and the
 // bit reader's cap (the slot's end - 4) lies in zeros.
 static_assert(kSlotTail >= 64, "the block behind a region's last byte must belong to the region's slot");
+// k_cand_heads reads five aligned dwords from the last dword boundary at or before a candidate, and a candidate is a
+// byte of its region: at most kHeadBytes + 3 bytes behind the region's last byte, inside the slot's tail
+static_assert(kSlotTail >= kHeadBytes + 4, "a candidate's head lies inside its slot");
+
+// Where a scan's bytes lie.  Host memory goes through the pinned staging and one upload (the first door); device memory
+// of the decoder's device is gathered into the slot buffer by k_gather_slots, and the little the host has to see of it
+// -- the metadata of a regular stream, the headers of a raw stream's candidates -- comes down as small tables.
+struct ScanInput {
+    const uint8_t *const *data;   // [n_streams]
+    bool device;
+};
 
 // a buffer that only grows: device memory, or pinned host memory
 template <bool PINNED> struct GrowBuf {
@@ -53,7 +67,10 @@ using DevBuf = GrowBuf<false>;
 struct flacgpu_decoder {
     int device = 0;
     hipStream_t st = nullptr;
-    GrowBuf<true> staging;   // pinned: the batch buffer on its way up
+    hipEvent_t ev = nullptr;   // the device door's wait for the caller's stream: created by the first device scan
+    GrowBuf<true> staging;   // pinned: the batch buffer on its way up (host scans alone)
+    DevBuf dev_src, meta, gather_src, cand_head;   // device scans alone: sources, metadata records, regions, headers
+    uint64_t slot_bytes = 0;   // bytes of `bytes` the last scan defined: its slots and the look-ahead; 0: no slot
     DevBuf bytes, slots, mask, plocal, wg_cnt, wg_tail, wg_off, wg_carry;
     DevBuf cand_pos, cand_info, cand_crc, cand_slot, slot_cand0, slot_pend, link;
     DevBuf spec_len;   // FLACGPU_SCAN_SPECULATIVE alone: allocated by the first scan that asks for it
@@ -86,16 +103,20 @@ struct flacgpu_decoder {
 };
 
 namespace {
-// The device half of a scan: uploads every slot's bytes in one copy (zero tails, 64 bytes of look-ahead) and runs the
-// scan kernels; leaves the candidates' positions, records and links and every slot's first candidate on the host.
-// `at` = the end of the last slot.  raw: the scan of raw frame streams (k_scan_subset, k_link_raw).  cspec (raw, under
-// FLACGPU_SCAN_SPECULATIVE; else null): the own extents of the candidates without a link (k_spec_end), 0: none.
-int device_scan(flacgpu_decoder *d, const uint8_t *const *data, const std::vector<ScanSlot> &slots,
+// The device half of a scan: fills every slot (zero tails, 64 bytes of look-ahead) -- host input in one upload, device
+// input with k_gather_slots -- and runs the scan kernels; leaves the candidates' positions, records and links and every
+// slot's first candidate on the host.  `at` = the end of the last slot.  raw: the scan of raw frame streams
+// (k_scan_subset, k_link_raw).  cspec (raw, under FLACGPU_SCAN_SPECULATIVE; else null): the own extents of the candidates
+// without a link (k_spec_end), 0: none.  cheads (device input of a raw scan; else null): the 16 bytes at every candidate
+// (k_cand_heads), downloaded with the links.
+int device_scan(flacgpu_decoder *d, const ScanInput &in, const std::vector<ScanSlot> &slots,
                 const std::vector<size_t> &region_at, const std::vector<uint32_t> &slot_stream, uint64_t at, bool raw,
                 std::vector<uint64_t> &cpos, std::vector<uint32_t> &cinfo, std::vector<int32_t> &clink,
-                std::vector<uint32_t> &cand0, uint32_t *n_cand_out, std::vector<uint32_t> *cspec = nullptr) {
+                std::vector<uint32_t> &cand0, uint32_t *n_cand_out, std::vector<uint32_t> *cspec = nullptr,
+                std::vector<uint8_t> *cheads = nullptr) {
     const uint32_t S = (uint32_t)slots.size();
-    const std::string who = raw ? "flacgpu_decoder_scan_frames" : "flacgpu_decoder_scan";
+    const uint8_t *const *data = in.data;
+    const std::string who = std::string(raw ? "flacgpu_decoder_scan_frames" : "flacgpu_decoder_scan") + (in.device ? "_device" : "");
     // the bit reader indexes dwords with 32 bits
     if (at + 64 > ((uint64_t)1 << 34)) {
         g_last_error = who + ": the batch's frames exceed 16 GiB";
@@ -105,15 +126,28 @@ int device_scan(flacgpu_decoder *d, const uint8_t *const *data, const std::vecto
     const uint64_t n_wg64 = (n_blocks + WG - 1) / WG;
     if (n_wg64 > 0xFFFFFFFFull) return FLACGPU_ERR_UNSUPPORTED;
     const uint32_t n_wg = (uint32_t)n_wg64;
-    // ---- one upload: every region into the pinned staging, zero tails, 64 bytes of look-ahead
     const size_t buf_bytes = at + 64;
-    if (int rc = d->staging.ensure(buf_bytes)) return rc;
-    uint8_t *stg = d->staging.as<uint8_t>();
-    for (uint32_t s = 0; s < S; s++) {
-        const uint64_t b = slots[s].base, l = slots[s].len;
-        const uint64_t e = s + 1 < S ? slots[s + 1].base : buf_bytes;
-        memcpy(stg + b, data[slot_stream[s]] + region_at[s], l);
-        memset(stg + b + l, 0, e - b - l);
+    uint8_t *stg = nullptr;
+    std::vector<const uint8_t *> srcs;   // device input: every region's first byte
+    if (in.device) {
+        try {
+            srcs.resize(S);
+        } catch (const std::bad_alloc &) {
+            g_last_error = who + ": out of host memory";
+            return FLACGPU_ERR_UNSUPPORTED;
+        }
+        for (uint32_t s = 0; s < S; s++) srcs[s] = data[slot_stream[s]] + region_at[s];
+        if (int rc = d->gather_src.ensure(sizeof(const uint8_t *) * S)) return rc;
+    } else {
+        // ---- one upload: every region into the pinned staging, zero tails, 64 bytes of look-ahead
+        if (int rc = d->staging.ensure(buf_bytes)) return rc;
+        stg = d->staging.as<uint8_t>();
+        for (uint32_t s = 0; s < S; s++) {
+            const uint64_t b = slots[s].base, l = slots[s].len;
+            const uint64_t e = s + 1 < S ? slots[s + 1].base : buf_bytes;
+            memcpy(stg + b, data[slot_stream[s]] + region_at[s], l);
+            memset(stg + b + l, 0, e - b - l);
+        }
     }
     if (int rc = d->bytes.ensure(buf_bytes)) return rc;
     if (int rc = d->slots.ensure(sizeof(ScanSlot) * S)) return rc;
@@ -125,8 +159,16 @@ int device_scan(flacgpu_decoder *d, const uint8_t *const *data, const std::vecto
     if (int rc = d->wg_carry.ensure(2 * n_wg)) return rc;
     if (int rc = d->slot_cand0.ensure(4 * S)) return rc;
     if (int rc = d->slot_pend.ensure(4 * S)) return rc;
-    HIP_TRY(hipMemcpyAsync(d->bytes.p, stg, buf_bytes, hipMemcpyHostToDevice, d->st));
+    d->slot_bytes = buf_bytes;
+    if (!in.device) HIP_TRY(hipMemcpyAsync(d->bytes.p, stg, buf_bytes, hipMemcpyHostToDevice, d->st));
     HIP_TRY(hipMemcpyAsync(d->slots.p, slots.data(), sizeof(ScanSlot) * S, hipMemcpyHostToDevice, d->st));
+    if (in.device) {   // the gather: every byte of [0, buf_bytes), a lane per 16-byte group
+        HIP_TRY(hipMemcpyAsync(d->gather_src.p, srcs.data(), sizeof(const uint8_t *) * S, hipMemcpyHostToDevice, d->st));
+        const uint64_t n_groups = buf_bytes / 16;   // buf_bytes is a multiple of 64, at most 2^34: the grid fits
+        hipLaunchKernelGGL(k_gather_slots, dim3((uint32_t)((n_groups + WG - 1) / WG)), dim3(WG), 0, d->st,
+                           d->bytes.as<uint8_t>(), d->slots.as<const ScanSlot>(), d->gather_src.as<const uint8_t *const>(),
+                           S, n_blocks, n_groups);
+    }
     ScanParams p{};
     p.bytes = d->bytes.as<uint8_t>();
     p.slots = d->slots.as<ScanSlot>();
@@ -155,6 +197,8 @@ int device_scan(flacgpu_decoder *d, const uint8_t *const *data, const std::vecto
     if (int rc = d->link.ensure(4 * nc)) return rc;
     if (cspec)
         if (int rc = d->spec_len.ensure(4 * nc)) return rc;
+    if (cheads)
+        if (int rc = d->cand_head.ensure(kHeadBytes * nc)) return rc;
     p.cand_pos = d->cand_pos.as<uint64_t>();
     p.cand_info = d->cand_info.as<uint32_t>();
     p.cand_crc = d->cand_crc.as<uint32_t>();
@@ -166,12 +210,16 @@ int device_scan(flacgpu_decoder *d, const uint8_t *const *data, const std::vecto
     else if (n_cand) hipLaunchKernelGGL(k_link, dim3((n_cand + WG - 1) / WG), dim3(WG), 0, d->st, p);
     if (n_cand && cspec)
         hipLaunchKernelGGL(k_spec_end, dim3((n_cand + 63) / 64), dim3(64), 0, d->st, p, d->spec_len.as<uint32_t>());
+    if (n_cand && cheads)
+        hipLaunchKernelGGL(k_cand_heads, dim3((n_cand + WG - 1) / WG), dim3(WG), 0, d->st, p.bytes, p.cand_pos, n_cand,
+                           d->cand_head.as<uint4>());
     HIP_TRY(hipGetLastError());
     try {
         cpos.resize(n_cand);
         cinfo.resize(n_cand);
         clink.resize(n_cand);
         if (cspec) cspec->resize(n_cand);
+        if (cheads) cheads->resize(kHeadBytes * (size_t)n_cand);
     } catch (const std::bad_alloc &) {
         g_last_error = who + ": out of host memory";
         return FLACGPU_ERR_UNSUPPORTED;
@@ -182,6 +230,8 @@ int device_scan(flacgpu_decoder *d, const uint8_t *const *data, const std::vecto
         HIP_TRY(hipMemcpyAsync(clink.data(), p.link, 4 * (size_t)n_cand, hipMemcpyDeviceToHost, d->st));
         if (cspec)   // with the links, in the same submission
             HIP_TRY(hipMemcpyAsync(cspec->data(), d->spec_len.p, 4 * (size_t)n_cand, hipMemcpyDeviceToHost, d->st));
+        if (cheads)
+            HIP_TRY(hipMemcpyAsync(cheads->data(), d->cand_head.p, kHeadBytes * (size_t)n_cand, hipMemcpyDeviceToHost, d->st));
     }
     HIP_TRY(hipMemcpyAsync(cand0.data(), p.slot_cand0, 4 * (size_t)S, hipMemcpyDeviceToHost, d->st));
     HIP_TRY(hipStreamSynchronize(d->st));
@@ -189,10 +239,40 @@ int device_scan(flacgpu_decoder *d, const uint8_t *const *data, const std::vecto
     return FLACGPU_OK;
 }
 
-int scan_impl(flacgpu_decoder *d, const uint8_t *const *data, const size_t *len, uint32_t n) {
+// The metadata of device input: k_meta_walk's record of every stream, on the host.  A null pointer or a zero length
+// is handed to the kernel as no bytes, and is not dereferenced.
+int device_meta_walk(flacgpu_decoder *d, const uint8_t *const *data, const size_t *len, uint32_t n,
+                     std::vector<MetaRecord> &meta) {
+    std::vector<DevSource> src;
+    try {
+        src.resize(n);
+        meta.resize(n);
+    } catch (const std::bad_alloc &) {
+        g_last_error = "flacgpu_decoder_scan_device: out of host memory";
+        return FLACGPU_ERR_UNSUPPORTED;
+    }
+    if (!n) return FLACGPU_OK;
+    for (uint32_t i = 0; i < n; i++) src[i] = data[i] && len[i] ? DevSource{data[i], len[i]} : DevSource{nullptr, 0};
+    if (int rc = d->dev_src.ensure(sizeof(DevSource) * n)) return rc;
+    if (int rc = d->meta.ensure(sizeof(MetaRecord) * n)) return rc;
+    HIP_TRY(hipMemcpyAsync(d->dev_src.p, src.data(), sizeof(DevSource) * n, hipMemcpyHostToDevice, d->st));
+    hipLaunchKernelGGL(k_meta_walk, dim3((n + 63) / 64), dim3(64), 0, d->st, d->dev_src.as<const DevSource>(), n,
+                       d->meta.as<MetaRecord>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(meta.data(), d->meta.p, sizeof(MetaRecord) * n, hipMemcpyDeviceToHost, d->st));
+    HIP_TRY(hipStreamSynchronize(d->st));
+    return FLACGPU_OK;
+}
+
+int scan_impl(flacgpu_decoder *d, const ScanInput &in, const size_t *len, uint32_t n) {
+    const uint8_t *const *data = in.data;
     d->res.assign(n, flacgpu_decoded_stream{});
     d->slot_of.assign(n, -1);
     d->frame_tab.clear();
+    d->slot_bytes = 0;
+    std::vector<MetaRecord> meta;   // device input: the walk was done where the bytes lie
+    if (in.device)
+        if (int rc = device_meta_walk(d, data, len, n, meta)) return rc;
     // ---- host: metadata, slot layout
     std::vector<ScanSlot> slots;
     std::vector<size_t> region_at;   // first byte of the frame region in the caller's buffer
@@ -202,7 +282,8 @@ int scan_impl(flacgpu_decoder *d, const uint8_t *const *data, const size_t *len,
         flacgpu_decoded_stream &r = d->res[i];
         uint32_t min_frame = 0;
         size_t pos = 0;
-        const char *why = flacenc::parse_metadata(data ? data[i] : nullptr, len ? len[i] : 0, &r.info, &min_frame, &pos);
+        const char *why = in.device ? flacenc::metadata_of_record(meta[i], &r.info, &min_frame, &pos)
+                                    : flacenc::parse_metadata(data ? data[i] : nullptr, len ? len[i] : 0, &r.info, &min_frame, &pos);
         r.rc = why ? FLACGPU_ERR_INVALID_ARG : FLACGPU_OK;
         if (r.rc != FLACGPU_OK || pos >= len[i]) continue;   // no frame region: 0 frames, nothing bad
         ScanSlot s;
@@ -224,7 +305,7 @@ int scan_impl(flacgpu_decoder *d, const uint8_t *const *data, const size_t *len,
     std::vector<int32_t> clink;
     uint32_t n_cand = 0;
     if (S) {
-        if (int rc = device_scan(d, data, slots, region_at, slot_stream, at, false, cpos, cinfo, clink, cand0, &n_cand))
+        if (int rc = device_scan(d, in, slots, region_at, slot_stream, at, false, cpos, cinfo, clink, cand0, &n_cand))
             return rc;
         // ---- host walk: follow the links from each region's first byte (the host scan's lost-sync rule: a frame
         // without an end is not taken, and nothing behind it is decoded)
@@ -294,8 +375,11 @@ int scan_impl(flacgpu_decoder *d, const uint8_t *const *data, const size_t *len,
 // flacgpu_decoder_scan_frames behind its argument checks: a slot is a whole input, the device finds the candidates and
 // their ends by the raw rule, and the host walks them with a cursor (DESIGN.md "Raw frame streams").  Under
 // FLACGPU_SCAN_SPECULATIVE a candidate without a link ends where its own extent does, if it has one.
-int scan_raw_impl(flacgpu_decoder *d, const uint8_t *const *data, const size_t *len, uint32_t n, uint32_t flags) {
+int scan_raw_impl(flacgpu_decoder *d, const ScanInput &in, const size_t *len, uint32_t n, uint32_t flags) {
+    const uint8_t *const *data = in.data;
     const bool spec = flags & FLACGPU_SCAN_SPECULATIVE;
+    std::vector<uint8_t> cheads;   // device input: the candidates' headers (k_cand_heads)
+    d->slot_bytes = 0;
     std::vector<ScanSlot> slots;
     std::vector<size_t> region_at;
     std::vector<uint32_t> slot_stream, cinfo, cand0, cspec;
@@ -329,12 +413,12 @@ int scan_raw_impl(flacgpu_decoder *d, const uint8_t *const *data, const size_t *
     d->n_slots = S;
     uint32_t n_cand = 0;
     if (S)
-        if (int rc = device_scan(d, data, slots, region_at, slot_stream, at, true, cpos, cinfo, clink, cand0, &n_cand,
-                                 spec ? &cspec : nullptr))
+        if (int rc = device_scan(d, in, slots, region_at, slot_stream, at, true, cpos, cinfo, clink, cand0, &n_cand,
+                                 spec ? &cspec : nullptr, in.device ? &cheads : nullptr))
             return rc;
     // ---- host walk, stream by stream: the candidates in ascending order, those below the cursor ignored, one without
     // an end passed over, one with an end kept and the cursor moved to that end.  A kept frame's record is read from
-    // its own header in the staging copy of the bytes.
+    // its own header: in the staging copy of the bytes, or (device input) in the downloaded table of headers.
     std::vector<ManyFrame> &all = d->raw_tab;   // decode_frames' table
     all.clear();
     d->raw_tab_uploaded = false;
@@ -362,9 +446,10 @@ int scan_raw_impl(flacgpu_decoder *d, const uint8_t *const *data, const size_t *
                     h.n = (cinfo[c] & 0xFFFFu) + 1u;
                     h.header_bytes = (cinfo[c] >> 16) & 0xFFu;
                     h.blocking = cinfo[c] >> 24;
-                    h.acode = stg[cpos[c] + 3] >> 4;
-                    h.bps_code = (stg[cpos[c] + 3] >> 1) & 7;
-                    flacenc::host_frame_fields(stg + cpos[c], h);
+                    const uint8_t *head = in.device ? cheads.data() + kHeadBytes * (size_t)c : stg + cpos[c];
+                    h.acode = head[3] >> 4;
+                    h.bps_code = (head[3] >> 1) & 7;
+                    flacenc::host_frame_fields(head, h);   // reads header_bytes <= kHeadBytes bytes
                     flacgpu_frame_record f{};
                     f.byte_offset = cpos[c] - sl.base;
                     f.number = h.number;
@@ -1089,8 +1174,69 @@ void flacgpu_decoder_destroy(flacgpu_decoder *d) {
     if (d->st) (void)hipStreamSynchronize(d->st);
     if (d->st) (void)hipStreamDestroy(d->st);
     d->st = nullptr;
+    if (d->ev) (void)hipEventDestroy(d->ev);
+    d->ev = nullptr;
     delete d;   // the buffers free themselves, on the decoder's device
     if (prev >= 0) (void)hipSetDevice(prev);
+}
+
+// The four scans behind their argument checks: the host door and the device door differ in `in` alone.
+static int scan_call(flacgpu_decoder *d, const ScanInput &in, const size_t *len, uint32_t n_streams,
+                     flacgpu_decoded_stream *streams, uint64_t *total_samples) {
+    if (int rc = scan_impl(d, in, len, n_streams)) return rc;
+    index_frames(d);
+    d->scanned = true;
+    if (n_streams) memcpy(streams, d->res.data(), sizeof(flacgpu_decoded_stream) * n_streams);
+    *total_samples = d->total;
+    return FLACGPU_OK;
+}
+
+static int scan_frames_call(flacgpu_decoder *d, const ScanInput &in, const size_t *len, uint32_t n_streams, uint32_t flags,
+                            flacgpu_decoded_stream *streams, flacgpu_raw_stream *raw, uint64_t *total_frames,
+                            uint64_t *total_elements, uint64_t *total_samples) {
+    if (int rc = scan_raw_impl(d, in, len, n_streams, flags)) return rc;
+    index_frames(d);
+    d->scanned = d->raw = true;
+    if (n_streams) memcpy(streams, d->res.data(), sizeof(flacgpu_decoded_stream) * n_streams);
+    if (n_streams && raw) memcpy(raw, d->raw_streams.data(), sizeof(flacgpu_raw_stream) * n_streams);
+    *total_frames = d->records.size();
+    *total_elements = d->raw_elements;
+    *total_samples = d->total;
+    return FLACGPU_OK;
+}
+
+// The device door's own checks, before anything is launched: every stream with bytes (a null pointer or a zero length
+// is never looked at) must be device memory of the decoder's device -- pinned or managed memory is not --, and where
+// the runtime knows the allocation, [d_data[i], d_data[i] + len[i]) must lie inside it.  Then the decoder's stream is
+// made to wait for `stream` (NULL: the legacy default stream), so that the first read of the sources is ordered after it.
+static int open_device_door(flacgpu_decoder *d, const uint8_t *const *d_data, const size_t *len, uint32_t n_streams,
+                            void *stream, const char *who) {
+    for (uint32_t i = 0; i < n_streams; i++) {
+        if (!d_data[i] || !len[i]) continue;
+        hipPointerAttribute_t attr{};
+        const hipError_t e = hipPointerGetAttributes(&attr, d_data[i]);
+        if (e != hipSuccess) (void)hipGetLastError();   // ordinary host memory is an error to the runtime, not to us
+        if (e != hipSuccess || attr.type != hipMemoryTypeDevice || attr.isManaged || attr.device != d->device) {
+            g_last_error = std::string(who) + ": stream " + std::to_string(i) + " is not device memory of device " +
+                           std::to_string(d->device);
+            return FLACGPU_ERR_INVALID_ARG;
+        }
+        hipDeviceptr_t base = nullptr;
+        size_t size = 0;
+        if (hipMemGetAddressRange(&base, &size, const_cast<uint8_t *>(d_data[i])) != hipSuccess) {
+            (void)hipGetLastError();   // an allocation the runtime cannot size: the attributes above are the check
+            continue;
+        }
+        const uintptr_t p = reinterpret_cast<uintptr_t>(d_data[i]), b = reinterpret_cast<uintptr_t>(base);
+        if (p < b || len[i] > size || p - b > size - len[i]) {
+            g_last_error = std::string(who) + ": stream " + std::to_string(i) + " reaches past the end of its allocation";
+            return FLACGPU_ERR_INVALID_ARG;
+        }
+    }
+    if (!d->ev) HIP_TRY(hipEventCreateWithFlags(&d->ev, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(d->ev, static_cast<hipStream_t>(stream)));
+    HIP_TRY(hipStreamWaitEvent(d->st, d->ev, 0));
+    return FLACGPU_OK;
 }
 
 int flacgpu_decoder_scan(flacgpu_decoder *d, const uint8_t *const *data, const size_t *len, uint32_t n_streams,
@@ -1098,12 +1244,19 @@ int flacgpu_decoder_scan(flacgpu_decoder *d, const uint8_t *const *data, const s
     if (!d || (n_streams && (!data || !len || !streams)) || !total_samples) return FLACGPU_ERR_INVALID_ARG;
     d->scanned = d->raw = false;
     DeviceGuard guard(d->device);
-    if (int rc = scan_impl(d, data, len, n_streams)) return rc;
-    index_frames(d);
-    d->scanned = true;
-    if (n_streams) memcpy(streams, d->res.data(), sizeof(flacgpu_decoded_stream) * n_streams);
-    *total_samples = d->total;
-    return FLACGPU_OK;
+    return scan_call(d, ScanInput{data, false}, len, n_streams, streams, total_samples);
+}
+
+int flacgpu_decoder_scan_device(flacgpu_decoder *d, const uint8_t *const *d_data, const size_t *len, uint32_t n_streams,
+                                void *stream, flacgpu_decoded_stream *streams, uint64_t *total_samples) {
+    if (!d || (n_streams && (!d_data || !len || !streams)) || !total_samples) {
+        g_last_error = "flacgpu_decoder_scan_device: a NULL handle or a missing array";
+        return FLACGPU_ERR_INVALID_ARG;
+    }
+    d->scanned = d->raw = false;
+    DeviceGuard guard(d->device);
+    if (int rc = open_device_door(d, d_data, len, n_streams, stream, "flacgpu_decoder_scan_device")) return rc;
+    return scan_call(d, ScanInput{d_data, true}, len, n_streams, streams, total_samples);
 }
 
 int flacgpu_decoder_scan_frames(flacgpu_decoder *d, const uint8_t *const *data, const size_t *len, uint32_t n_streams,
@@ -1121,14 +1274,57 @@ int flacgpu_decoder_scan_frames_ex(flacgpu_decoder *d, const uint8_t *const *dat
         return FLACGPU_ERR_INVALID_ARG;
     d->scanned = d->raw = false;
     DeviceGuard guard(d->device);
-    if (int rc = scan_raw_impl(d, data, len, n_streams, flags)) return rc;
-    index_frames(d);
-    d->scanned = d->raw = true;
-    if (n_streams) memcpy(streams, d->res.data(), sizeof(flacgpu_decoded_stream) * n_streams);
-    if (n_streams && raw) memcpy(raw, d->raw_streams.data(), sizeof(flacgpu_raw_stream) * n_streams);
-    *total_frames = d->records.size();
-    *total_elements = d->raw_elements;
-    *total_samples = d->total;
+    return scan_frames_call(d, ScanInput{data, false}, len, n_streams, flags, streams, raw, total_frames, total_elements,
+                            total_samples);
+}
+
+int flacgpu_decoder_scan_frames_device(flacgpu_decoder *d, const uint8_t *const *d_data, const size_t *len,
+                                       uint32_t n_streams, uint32_t flags, void *stream, flacgpu_decoded_stream *streams,
+                                       flacgpu_raw_stream *raw, uint64_t *total_frames, uint64_t *total_elements,
+                                       uint64_t *total_samples) {
+    if (!d || (n_streams && (!d_data || !len || !streams)) || !total_frames || !total_elements || !total_samples ||
+        (flags & ~FLACGPU_SCAN_SPECULATIVE)) {
+        g_last_error = "flacgpu_decoder_scan_frames_device: a NULL handle, a missing array or an unknown flag";
+        return FLACGPU_ERR_INVALID_ARG;
+    }
+    d->scanned = d->raw = false;
+    DeviceGuard guard(d->device);
+    if (int rc = open_device_door(d, d_data, len, n_streams, stream, "flacgpu_decoder_scan_frames_device")) return rc;
+    return scan_frames_call(d, ScanInput{d_data, true}, len, n_streams, flags, streams, raw, total_frames, total_elements,
+                            total_samples);
+}
+
+int flacgpu_decoder_slot_bytes(flacgpu_decoder *d, uint8_t *out, size_t cap, uint64_t *bytes) {
+    if (!d || !bytes) return FLACGPU_ERR_INVALID_ARG;
+    if (!d->scanned) {
+        g_last_error = "flacgpu_decoder_slot_bytes: no scanned batch";
+        return FLACGPU_ERR_INVALID_ARG;
+    }
+    *bytes = d->slot_bytes;
+    if (cap < d->slot_bytes) {
+        g_last_error = "output buffer too small";
+        return FLACGPU_ERR_BUFFER_TOO_SMALL;
+    }
+    if (!d->slot_bytes) return FLACGPU_OK;
+    if (!out) return FLACGPU_ERR_INVALID_ARG;
+    DeviceGuard guard(d->device);
+    HIP_TRY(hipMemcpyAsync(out, d->bytes.p, d->slot_bytes, hipMemcpyDeviceToHost, d->st));
+    HIP_TRY(hipStreamSynchronize(d->st));
+    return FLACGPU_OK;
+}
+
+int flacgpu_meta_walk_host(const uint8_t *data, size_t len, flacgpu_stream_info *info, uint32_t *min_frame,
+                           uint64_t *frames_at) {
+    if (!info || !min_frame || !frames_at) return FLACGPU_ERR_INVALID_ARG;
+    *frames_at = 0;
+    MetaRecord rec;
+    meta_walk(data, len, rec);   // the function k_meta_walk runs, compiled for the host
+    size_t pos = 0;
+    if (const char *why = flacenc::metadata_of_record(rec, info, min_frame, &pos)) {
+        if (*why) g_last_error = why;
+        return FLACGPU_ERR_INVALID_ARG;
+    }
+    *frames_at = pos;
     return FLACGPU_OK;
 }
 

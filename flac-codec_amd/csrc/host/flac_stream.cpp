@@ -46,40 +46,36 @@ struct ByteBits {
 };
 }  // namespace
 
-const char *parse_metadata(const uint8_t *data, size_t len, flacgpu_stream_info *info, uint32_t *min_frame,
-                           size_t *frames_at) {
+void streaminfo_fields(const uint8_t *b, flacgpu_stream_info *info, uint32_t *min_frame) {
+    info->min_block = b[0] << 8 | b[1];   // metadata/mod.rs:1599-1630
+    info->max_block = b[2] << 8 | b[3];
+    *min_frame = b[4] << 16 | b[5] << 8 | b[6];
+    info->sample_rate = (uint32_t)b[10] << 12 | (uint32_t)b[11] << 4 | b[12] >> 4;
+    info->channels = ((b[12] >> 1) & 7) + 1;
+    info->bits_per_sample = (((uint32_t)b[12] & 1) << 4 | b[13] >> 4) + 1;
+    info->total_samples = ((uint64_t)(b[13] & 15) << 32) | (uint64_t)b[14] << 24 | (uint64_t)b[15] << 16 |
+                          (uint64_t)b[16] << 8 | b[17];
+    memcpy(info->md5, b + 18, 16);
+}
+
+const char *metadata_of_record(const MetaRecord &rec, flacgpu_stream_info *info, uint32_t *min_frame, size_t *frames_at) {
     memset(info, 0, sizeof *info);
     *min_frame = 0;
-    if (!data || len < 42 || memcmp(data, "fLaC", 4) != 0) return "not a FLAC stream (no fLaC marker)";
-    size_t pos = 4;
-    bool have_si = false;
-    for (;;) {   // metadata blocks (metadata/mod.rs:257-266): last flag + type, 24-bit length
-        if (pos + 4 > len) return "";
-        const bool last = data[pos] & 0x80;
-        const uint32_t type = data[pos] & 0x7F;
-        const size_t blen = (size_t)data[pos + 1] << 16 | (size_t)data[pos + 2] << 8 | data[pos + 3];
-        pos += 4;
-        if (pos + blen > len) return "";
-        if (type == 0 && blen == 34) {   // STREAMINFO, metadata/mod.rs:1599-1630
-            const uint8_t *b = data + pos;
-            info->min_block = b[0] << 8 | b[1];
-            info->max_block = b[2] << 8 | b[3];
-            *min_frame = b[4] << 16 | b[5] << 8 | b[6];
-            info->sample_rate = (uint32_t)b[10] << 12 | (uint32_t)b[11] << 4 | b[12] >> 4;
-            info->channels = ((b[12] >> 1) & 7) + 1;
-            info->bits_per_sample = (((uint32_t)b[12] & 1) << 4 | b[13] >> 4) + 1;
-            info->total_samples = ((uint64_t)(b[13] & 15) << 32) | (uint64_t)b[14] << 24 | (uint64_t)b[15] << 16 |
-                                  (uint64_t)b[16] << 8 | b[17];
-            memcpy(info->md5, b + 18, 16);
-            have_si = true;
-        }
-        pos += blen;
-        if (last) break;
-    }
-    if (!have_si || info->channels > 8 || info->bits_per_sample > 32 || info->max_block < 1)
+    if (!(rec.status & META_MARKER)) return "not a FLAC stream (no fLaC marker)";
+    if (rec.status & META_HAVE_SI) streaminfo_fields(rec.si, info, min_frame);
+    if (!(rec.status & META_COMPLETE)) return "";
+    if (!(rec.status & META_HAVE_SI) || info->channels > 8 || info->bits_per_sample > 32 || info->max_block < 1)
         return "no usable STREAMINFO block";
-    *frames_at = pos;
+    *frames_at = (size_t)rec.frames_at;
     return nullptr;
+}
+
+// the metadata blocks (metadata/mod.rs:257-266) are walked by kernels/meta_walk.h, which the device shares
+const char *parse_metadata(const uint8_t *data, size_t len, flacgpu_stream_info *info, uint32_t *min_frame,
+                           size_t *frames_at) {
+    MetaRecord rec;
+    meta_walk(data, len, rec);
+    return metadata_of_record(rec, info, min_frame, frames_at);
 }
 
 bool host_parse_header(const uint8_t *d, size_t avail, HostFrameHead &h) {

@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "../kernels/meta_walk.h"
 #include "flacenc_gpu.h"
 
 namespace flacenc {
@@ -15,6 +16,12 @@ namespace flacenc {
 // to the caller): the last-error text, "" for a truncated block list, which sets none.
 const char *parse_metadata(const uint8_t *data, size_t len, flacgpu_stream_info *info, uint32_t *min_frame,
                            size_t *frames_at);
+// parse_metadata in its two halves.  The walk over the block list is meta_walk (kernels/meta_walk.h, shared with the
+// device: k_meta_walk fills the same record for a stream that lies in device memory); metadata_of_record is everything
+// behind it -- `info`, *min_frame, *frames_at and the return value exactly as parse_metadata gives them for the bytes
+// the record was walked from.  streaminfo_fields reads the 34 bytes of a STREAMINFO block.
+void streaminfo_fields(const uint8_t *b, flacgpu_stream_info *info, uint32_t *min_frame);
+const char *metadata_of_record(const MetaRecord &rec, flacgpu_stream_info *info, uint32_t *min_frame, size_t *frames_at);
 
 struct HostFrameHead {
     uint32_t n = 0, header_bytes = 0, blocking = 0, acode = 0, bps_code = 0;

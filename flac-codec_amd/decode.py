@@ -32,9 +32,15 @@ def _result(rec):
 
 def verify_many(paths, device=-1):
     """One result per path, in order: a Verified, or the DecodeError / OSError of that file (returned, not raised, so
-    that one bad file does not hide the others).  The readable files are verified in one GPU batch."""
+    that one bad file does not hide the others).  The readable files are verified in one GPU batch.  An entry may also
+    be a stream that already lies in device memory (a 1-D uint8 CUDA tensor, gpu.Decoder.scan): then every entry must
+    be one, and none is read from disk."""
     blobs, results = [], []
     for p in paths:
+        if gpu.is_device_blob(p):
+            blobs.append(p)
+            results.append(None)
+            continue
         try:
             with open(os.fspath(p), "rb") as f:
                 blobs.append(f.read())

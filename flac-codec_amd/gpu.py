@@ -454,6 +454,11 @@ def scan_timeline_host(records):
     return result, frames
 
 
+def is_device_blob(b):
+    """True for a torch tensor (a stream handed over in device memory), without importing torch for bytes."""
+    return hasattr(b, "data_ptr") and hasattr(b, "is_cuda")
+
+
 class DecodedStream:
     """One stream of a decode_many batch: rc (what flacgpu_decode_stream returns for it), info (StreamInfo), offset
     (first element in the flat output) and pcm (a [samples, channels] view of the flat output, or the
@@ -477,6 +482,7 @@ class Decoder:
             raise GpuError(rc, "flacgpu_decoder_create")
         self._h = h
         self.device = device
+        self.device_index = device if device >= 0 else L.flacgpu_current_device()   # -1: the creator's current device
         self.n_raw_streams = self.n_raw_frames = 0   # of the last scan_frames
 
     def close(self):
@@ -487,51 +493,85 @@ class Decoder:
     def __del__(self):
         self.close()
 
-    def scan(self, blobs):
-        """flacgpu_decoder_scan: returns (records, total int32 samples)."""
-        L = _lib.lib()
-        blobs = [b if isinstance(b, bytes) else bytes(b) for b in blobs]
+    def _sources(self, blobs, stream):
+        """The pointer and length arrays of a scan's inputs: (ptrs, lens, n, keep, stream).  `stream` is None for host
+        bytes, else the hipStream_t (an integer, 0: the legacy default stream) the device scan is ordered after."""
+        blobs = list(blobs)
+        on_device = [is_device_blob(b) for b in blobs]
+        if any(on_device) and not all(on_device):
+            raise ValueError("a batch is all device tensors or all host bytes, not a mix")
         n = len(blobs)
         ptrs = (C.c_void_p * max(n, 1))()
         lens = (C.c_size_t * max(n, 1))()
+        if n and on_device[0]:
+            import torch
+
+            dev = self.device_index
+            for i, b in enumerate(blobs):
+                if not b.is_cuda or b.device.index != dev:
+                    raise ValueError(f"blob {i} lies on {b.device}, the decoder on cuda:{dev}")
+                if b.dtype != torch.uint8 or b.dim() != 1 or not b.is_contiguous():
+                    raise ValueError(f"blob {i} must be a contiguous 1-D torch.uint8 tensor")
+                ptrs[i] = b.data_ptr() if b.numel() else None
+                lens[i] = b.numel()
+            if stream is None:
+                stream = torch.cuda.current_stream(dev)
+            return ptrs, lens, n, blobs, int(getattr(stream, "cuda_stream", stream) or 0)
+        if stream is not None:
+            raise ValueError("stream goes with device tensors")
         keep = []   # the bytes objects' own buffers, no copy; alive until the scan has uploaded them
         for i, b in enumerate(blobs):
+            b = b if isinstance(b, bytes) else bytes(b)
             cp = C.c_char_p(b)
             keep.append(cp)
             ptrs[i] = C.cast(cp, C.c_void_p).value
             lens[i] = len(b)
+        return ptrs, lens, n, keep, None
+
+    def scan(self, blobs, stream=None):
+        """flacgpu_decoder_scan: returns (records, total int32 samples).  `blobs` are bytes, or -- all of them -- 1-D
+        contiguous torch.uint8 tensors on the decoder's device (views into one shard tensor, say), which are scanned
+        where they lie (flacgpu_decoder_scan_device), ordered after `stream` (default: torch's current stream on that
+        device).  The tensors may be freed or overwritten once the call returns."""
+        L = _lib.lib()
+        ptrs, lens, n, keep, st = self._sources(blobs, stream)
         recs = (_lib.DecodedStream * max(n, 1))()
         total = C.c_uint64(0)
-        rc = L.flacgpu_decoder_scan(self._h, ptrs, lens, n, recs, C.byref(total))
+        if st is None:
+            rc, who = L.flacgpu_decoder_scan(self._h, ptrs, lens, n, recs, C.byref(total)), "flacgpu_decoder_scan"
+        else:
+            rc = L.flacgpu_decoder_scan_device(self._h, ptrs, lens, n, C.c_void_p(st), recs, C.byref(total))
+            who = "flacgpu_decoder_scan_device"
+        del keep
         if rc:
-            raise GpuError(rc, "flacgpu_decoder_scan")
+            raise GpuError(rc, who)
         return recs, total.value
 
-    def scan_frames(self, blobs, speculative=False):
+    def scan_frames(self, blobs, speculative=False, stream=None):
         """flacgpu_decoder_scan_frames_ex: a batch of raw frame streams (bare frames, no metadata; a byte range of a
         file).  Returns (records, total int32 samples of the uniform streams, raw, frames): `records` serve decode,
         decode_as and decode_windows as scan's do, `raw` is the _lib.RawStream array, `frames` the structured array
         (FRAME_DTYPE) of every kept frame of the batch, whose last out_offset + block_size * channels is the element
         count decode_frames writes.  speculative=True (FLACGPU_SCAN_SPECULATIVE): a frame that no header ends is ended
-        by its own bits, and its record has _lib.FRAME_SPECULATIVE in `reserved`."""
+        by its own bits, and its record has _lib.FRAME_SPECULATIVE in `reserved`.  Device tensors and `stream` as for
+        scan (flacgpu_decoder_scan_frames_device)."""
         L = _lib.lib()
-        blobs = [b if isinstance(b, bytes) else bytes(b) for b in blobs]
-        n = len(blobs)
-        ptrs = (C.c_void_p * max(n, 1))()
-        lens = (C.c_size_t * max(n, 1))()
-        keep = []
-        for i, b in enumerate(blobs):
-            cp = C.c_char_p(b)
-            keep.append(cp)
-            ptrs[i] = C.cast(cp, C.c_void_p).value
-            lens[i] = len(b)
+        ptrs, lens, n, keep, st = self._sources(blobs, stream)
         recs = (_lib.DecodedStream * max(n, 1))()
         raw = (_lib.RawStream * max(n, 1))()
         n_frames, elements, total = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-        rc = L.flacgpu_decoder_scan_frames_ex(self._h, ptrs, lens, n, _lib.SCAN_SPECULATIVE if speculative else 0, recs,
-                                              raw, C.byref(n_frames), C.byref(elements), C.byref(total))
+        flags = _lib.SCAN_SPECULATIVE if speculative else 0
+        if st is None:
+            rc = L.flacgpu_decoder_scan_frames_ex(self._h, ptrs, lens, n, flags, recs, raw, C.byref(n_frames),
+                                                  C.byref(elements), C.byref(total))
+            who = "flacgpu_decoder_scan_frames_ex"
+        else:
+            rc = L.flacgpu_decoder_scan_frames_device(self._h, ptrs, lens, n, flags, C.c_void_p(st), recs, raw,
+                                                      C.byref(n_frames), C.byref(elements), C.byref(total))
+            who = "flacgpu_decoder_scan_frames_device"
+        del keep
         if rc:
-            raise GpuError(rc, "flacgpu_decoder_scan_frames_ex")
+            raise GpuError(rc, who)
         frames = np.zeros(n_frames.value, dtype=FRAME_DTYPE)
         rc = L.flacgpu_decoder_frame_records(self._h, frames.ctypes.data_as(C.POINTER(_lib.FrameRecord)), frames.size)
         if rc:
@@ -539,6 +579,21 @@ class Decoder:
         self.raw_elements = elements.value
         self.n_raw_streams, self.n_raw_frames = n, int(n_frames.value)
         return recs, total.value, raw, frames
+
+    def slot_bytes(self):
+        """flacgpu_decoder_slot_bytes: the decoder's slot buffer as the last scan left it (every frame region at a
+        64-byte boundary, zero tails, 64 bytes of look-ahead), as bytes.  For tests: host and device scans of the same
+        bytes build the same buffer."""
+        L = _lib.lib()
+        need = C.c_uint64(0)
+        rc = L.flacgpu_decoder_slot_bytes(self._h, None, 0, C.byref(need))
+        if rc and rc != -5:
+            raise GpuError(rc, "flacgpu_decoder_slot_bytes")
+        buf = np.empty(need.value, dtype=np.uint8)
+        rc = L.flacgpu_decoder_slot_bytes(self._h, buf.ctypes.data if buf.size else None, buf.size, C.byref(need))
+        if rc:
+            raise GpuError(rc, "flacgpu_decoder_slot_bytes")
+        return buf.tobytes()
 
     def decode_frames(self, out_ptr, out_cap, flags, frames):
         """flacgpu_decoder_decode_frames: every kept frame of the raw scan into the int32 buffer at out_ptr (device or

@@ -725,6 +725,47 @@ int flacgpu_decoder_frame_records(flacgpu_decoder *d, flacgpu_frame_record *reco
 int flacgpu_decoder_decode_frames(flacgpu_decoder *d, int32_t *out, size_t out_cap_elements, uint32_t flags,
                                   flacgpu_frame_record *records, size_t cap);
 
+/* ---- batch decoder: streams that already lie in device memory -------------------------------------------------------
+ * The scans' second front door, for compressed bytes that are born or delivered in device memory: the frames
+ * flacgpu_encode_device leaves there (flacgpu_device_buffer 4 and 5), a shard broadcast into every rank's GPU, a shard
+ * tensor loaded onto the device.  The bytes never travel to the host: a kernel gathers them into the decoder's own
+ * buffer, and only small tables come down (a regular stream's STREAMINFO, the headers of a raw stream's candidates).
+ *   scan_device         = flacgpu_decoder_scan for the same bytes in host memory: every field of every streams[i] and
+ *                         *total_samples.
+ *   scan_frames_device  = flacgpu_decoder_scan_frames_ex for the same bytes and flags: streams, raw, the totals and every
+ *                         flacgpu_frame_record.
+ * The handle is then in the state the host call leaves it in, and every later call on it (decode, decode_as,
+ * decode_windows, decode_frames, plan_timeline, decode_timeline) writes the same bytes and records.  The 16 GiB limit,
+ * a NULL pointer or a zero length per stream, and the stream without a frame region behave as there.
+ * d_data and len are HOST arrays of n_streams entries.  d_data[i] is a device pointer on the decoder's device, of any
+ * alignment: views into one shard buffer are the expected use.  An entry that is NULL or has len[i] == 0 is never
+ * dereferenced or looked at.  `stream` is a hipStream_t: the first read of the sources is ordered after the work queued
+ * on it so far (NULL: the legacy default stream, as for flacenc_encode_many_device).  The calls are synchronous and the
+ * decoder keeps its own copy: the sources may be reused or freed on return.  A handle that only sees device scans
+ * allocates no pinned staging.
+ * Refused with FLACGPU_ERR_INVALID_ARG before anything is launched, flacgpu_last_error naming the stream where there is
+ * one: d == NULL, a missing array, an unknown flag, or an entry with bytes that hipPointerGetAttributes does not report
+ * as device memory of the decoder's device (pinned host memory and managed memory are not device memory) or that
+ * reaches past the end of its allocation.  A refused call leaves the handle without a scanned batch, as a failed host
+ * scan does.
+ *   slot_bytes      downloads the decoder's slot buffer as the last scan left it, whichever door it came through: every
+ *                   stream's frame region at a 64-byte boundary, zeros up to the next one, 64 bytes of look-ahead.
+ *                   *bytes is its size (0: the batch has no frame region) also when cap is short
+ *                   (FLACGPU_ERR_BUFFER_TOO_SMALL, nothing written).  For tests: the two doors must build the same bytes.
+ *   meta_walk_host  the metadata walk scan_device runs on the device (csrc/kernels/meta_walk.h), compiled for the host: the
+ *                   return value, `info` (the STREAMINFO fields; everything else 0) and *frames_at (the first byte behind
+ *                   the metadata, 0 when refused) that flacgpu_scan_stream_host gives for the metadata of the same bytes;
+ *                   *min_frame is STREAMINFO's minimum frame size.  Makes no HIP call and needs no device. */
+int flacgpu_decoder_scan_device(flacgpu_decoder *d, const uint8_t *const *d_data, const size_t *len, uint32_t n_streams,
+                                void *stream, flacgpu_decoded_stream *streams, uint64_t *total_samples);
+int flacgpu_decoder_scan_frames_device(flacgpu_decoder *d, const uint8_t *const *d_data, const size_t *len,
+                                       uint32_t n_streams, uint32_t flags, void *stream, flacgpu_decoded_stream *streams,
+                                       flacgpu_raw_stream *raw, uint64_t *total_frames, uint64_t *total_elements,
+                                       uint64_t *total_samples);
+int flacgpu_decoder_slot_bytes(flacgpu_decoder *d, uint8_t *out, size_t cap, uint64_t *bytes);
+int flacgpu_meta_walk_host(const uint8_t *data, size_t len, flacgpu_stream_info *info, uint32_t *min_frame,
+                           uint64_t *frames_at);
+
 /* ---- batch decoder: raw frame streams on a timeline, lost frames zero-filled -----------------------------------------
  * The kept frames of every stream of a raw scan, each put where its coded number says it belongs; what no frame covers
  * is zero, and so is a frame that does not decode.  The rule (DESIGN.md 4b "Timeline"), for the records r_0 .. r_{m-1}

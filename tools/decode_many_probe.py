@@ -57,6 +57,15 @@ the spread over --reps that this probe sees).
 that a WAV writer then needs, against (b) one decode_many(dtype="int24", out="host"); both must give the same bytes.
 Device output: the int32 call against the int24 call, with the bytes each holds.
 
+--device-input (flacgpu_decoder_scan_device): the clips and the tracks in one batch, the scan alone, handle warm, median
+and min to max of 15 runs, the shader clock read before and after each leg: (a) the bytes in host memory through
+flacgpu_decoder_scan; (b) the same bytes resident in device memory through flacgpu_decoder_scan_device; (c) for bytes
+born on the device, a download into pinned memory plus the host scan, to set against (b); and a plain device-to-device
+copy of the same byte count (torch's copy_, a hipMemcpyAsync), the yardstick for the gather kernel, whose own time a
+`rocprofv3 --kernel-trace --stats` run of `--device-input --kernels-only` gives (--merge-stats puts it into the
+record as kernel_stats and gather_effective_gbps).  --label this_1 / parent (with --package-root, leg (a) alone) / this_2 in
+that order add the guard on the host door: profiles/r15_device_input.json.
+
 --windows (flacgpu_decoder_decode_windows): on a resident scan (scanned once, outside the timed part), device output,
 no MD5, handle warm, the wall time of one round of random crops -- one crop of 5 s (tracks) or 1 s (clips) per stream
 at seeded random positions -- as (a) what a caller without windows does: decode_as float32 PADDED of the whole batch,
@@ -600,6 +609,100 @@ def timeline(args):
     print(json.dumps({args.label: rec, "verdict": res.get("verdict")}, indent=1), flush=True)
 
 
+def device_input(args):
+    """The --device-input leg (see the module docstring)."""
+    import hashlib
+
+    import torch
+
+    from flac_codec_amd import _lib
+    from flac_codec_amd.gpu import Decoder
+
+    L = _lib.lib()
+    has_door = hasattr(L, "flacgpu_decoder_scan_device") and args.label != "parent"
+    blobs = make_blobs("clips") + make_blobs("tracks")
+    n = len(blobs)
+    data = b"".join(blobs)
+    offs = np.cumsum([0] + [len(b) for b in blobs])
+    lens = (C.c_size_t * n)(*[len(b) for b in blobs])
+    recs, total = (_lib.DecodedStream * n)(), C.c_uint64(0)
+    shard = torch.from_numpy(np.frombuffer(data, dtype=np.uint8).copy()).to("cuda:0")
+    down = torch.empty(len(data), dtype=torch.uint8).pin_memory()   # (c): where the download lands
+    host = np.frombuffer(data, dtype=np.uint8)
+    hptrs = (C.c_void_p * n)(*[host.ctypes.data + int(o) for o in offs[:-1]])
+    pptrs = (C.c_void_p * n)(*[down.data_ptr() + int(o) for o in offs[:-1]])
+    dptrs = (C.c_void_p * n)(*[shard.data_ptr() + int(o) for o in offs[:-1]])
+    copy = torch.empty_like(shard)
+    dec = Decoder(0)
+
+    def host_scan(ptrs=hptrs):
+        assert L.flacgpu_decoder_scan(dec._h, ptrs, lens, n, recs, C.byref(total)) == 0
+
+    def device_scan():
+        assert L.flacgpu_decoder_scan_device(dec._h, dptrs, lens, n, None, recs, C.byref(total)) == 0
+
+    def download_then_host_scan():
+        down.copy_(shard)   # D2H into pinned memory, synchronous
+        host_scan(pptrs)
+
+    def plain_d2d():
+        copy.copy_(shard)
+
+    if args.kernels_only:   # for rocprofv3 --kernel-trace --stats: a warm call, then three traced ones per door
+        for _ in range(4):
+            device_scan()
+            host_scan()
+        dec.close()
+        return
+    legs = {"a_host_bytes_host_scan": host_scan}
+    if has_door:
+        legs.update({"b_device_bytes_device_scan": device_scan, "c_device_bytes_download_host_scan": download_then_host_scan,
+                     "plain_d2d_copy_of_the_bytes": plain_d2d})
+    res = {"tool": "tools/decode_many_probe.py --device-input", "workload": "clips (1024 x 10 s, 16 kHz mono 16-bit) + "
+           "tracks (256 x 3 min, 44.1 kHz stereo 16-bit) in one batch, the scan alone, handle warm",
+           "streams": n, "compressed_bytes": len(data), "order": [], "runs": {}}
+    if os.path.exists(args.out):
+        with open(args.out) as f:
+            res = json.load(f)
+    host_scan()
+    rec = {"build_id": _lib.build_id(), "records_sha256": hashlib.sha256(bytes(recs)).hexdigest(), "legs": {}}
+    for other in res["runs"].values():
+        assert other["records_sha256"] == rec["records_sha256"]   # the same scan under every label
+    if has_door:
+        device_scan()
+        assert hashlib.sha256(bytes(recs)).hexdigest() == rec["records_sha256"]   # and through the device door
+    for name, fn in legs.items():
+        fn()
+        torch.cuda.synchronize()   # warm: buffers grown, code loaded
+        sclk_before = _sclk_mhz()
+        times = []
+        for _ in range(args.reps):
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            times.append(time.perf_counter() - t0)
+        rec["legs"][name] = dict(_spread(times), sclk_mhz_before=sclk_before, sclk_mhz_after=_sclk_mhz())
+    if has_door:
+        d2d = rec["legs"]["plain_d2d_copy_of_the_bytes"]["median_s"]
+        rec["plain_d2d_gbps"] = len(data) / d2d / 1e9
+    dec.close()
+    res["runs"][args.label] = rec
+    res["order"].append(args.label)
+    runs = res["runs"]
+    if all(k in runs for k in ("this_1", "parent", "this_2")):   # the host door must cost what it cost
+        allow = runs["parent"]["legs"]["a_host_bytes_host_scan"]
+        res["host_door_guard"] = {"parent_median_s": allow["median_s"], "parent_min_s": allow["min_s"],
+                                  "parent_max_s": allow["max_s"]}
+        for label in ("this_1", "this_2"):
+            leg = runs[label]["legs"]["a_host_bytes_host_scan"]
+            res["host_door_guard"][label] = {"median_s": leg["median_s"],
+                                             "inside_parent_spread": allow["min_s"] <= leg["median_s"] <= allow["max_s"],
+                                             "over_parent_median": leg["median_s"] / allow["median_s"]}
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps({args.label: rec, "host_door_guard": res.get("host_door_guard")}, indent=1), flush=True)
+
+
 def windows(args):
     """The --windows leg (see the module docstring)."""
     import torch
@@ -723,8 +826,12 @@ def merge_stats(args):
     mine = {k: v for k, v in rows.items() if any(s in k for s in ("k_scan_", "k_link", "k_decode_many", "k_frame_crc",
                                                                    "k_finish_many", "k_md5_many", "k_finish_as",
                                                                    "k_pad_rows", "k_finish_window", "k_spec_end",
-                                                                   "k_fill_runs"))}   # (k_scan_ and k_link cover the raw kernels)
+                                                                   "k_fill_runs", "k_gather_slots", "k_meta_walk",
+                                                                   "k_cand_heads"))}   # (k_scan_ and k_link cover the raw kernels)
     res.setdefault("kernel_stats", {})[args.stats_label] = mine
+    gather = [v for k, v in mine.items() if "k_gather_slots" in k]
+    if gather and "compressed_bytes" in res:   # --device-input: the gather against the plain copy
+        res["gather_effective_gbps"] = res["compressed_bytes"] / (gather[0]["avg_ms"] * 1e-3) / 1e9
     with open(args.out, "w") as f:
         json.dump(res, f, indent=1)
     print(json.dumps(mine, indent=1))
@@ -734,7 +841,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workloads", default="clips,tracks,hour")
     ap.add_argument("--out")
-    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--reps", type=int, help="timed runs per leg (default 3; --device-input: 15)")
+    ap.add_argument("--device-input", action="store_true",
+                    help="the device-resident input leg: profiles/r15_device_input.json")
     ap.add_argument("--formats", action="store_true", help="the output-format leg: profiles/r09_decode_formats.json")
     ap.add_argument("--windows", action="store_true", help="the random-crop leg: profiles/r10_decode_windows.json")
     ap.add_argument("--s24", action="store_true", help="with --formats: the packed 24-bit leg, profiles/r12_s24.json")
@@ -751,8 +860,11 @@ def main():
     ap.add_argument("--stats-label", default="run")
     ap.add_argument("--kernels-only", action="store_true", help="one warm decode per workload (for rocprofv3)")
     args = ap.parse_args()
+    if args.reps is None:
+        args.reps = 15 if args.device_input else 3
     if not args.out:
-        args.out = os.path.join(ROOT, "profiles", "r16_timeline.json" if args.timeline else
+        args.out = os.path.join(ROOT, "profiles", "r15_device_input.json" if args.device_input else
+                                "r16_timeline.json" if args.timeline else
                                 "r14_speculative.json" if args.raw and args.speculative else
                                 "r13_raw_frames.json" if args.raw else
                                 "r10_decode_windows.json" if args.windows else
@@ -767,6 +879,8 @@ def main():
     import torch
 
     torch.cuda.init()   # before the library's first HIP call (else torch sees no GPU)
+    if args.device_input:
+        return device_input(args)
     if args.timeline:
         return timeline(args)
     if args.raw:
