@@ -352,8 +352,9 @@ __device__ __forceinline__ void wave_leaf_quotients(Src src, uint32_t order, uin
     odd = cnt;
 }
 // first pass over a stored residual: fold in place, sum |r| of this lane (= sum_t + neg)
-// SIGNS (Params::hand_meta): a[e] keeps r's sign in bit 31 beside t (t < 2^31; one v_and_or_b32 per sample) -- zigzag(r) is then
-// a[e] rotated left by one, which is what k_frame64 makes of the words the winning wave hands over
+// SIGNS (Params::hand_meta): a[e] keeps r's sign in bit 31 beside t (t < 2^31; one merging instruction per sample) -- zigzag(r)
+// is then a[e] rotated left by one, which is what k_frame64 makes of the words the winning wave hands over.  Samples go in
+// pairs: the second one's t exists only inside the pair's sum
 template <int SPL, int MAXORD, bool SIGNS = false>
 __device__ __forceinline__ void wave_rice_fold(int32_t (&a)[SPL], uint32_t order, uint64_t &sum_t, uint32_t &neg) {
     const bool lane0 = (threadIdx.x & 63) == 0;
@@ -362,8 +363,8 @@ __device__ __forceinline__ void wave_rice_fold(int32_t (&a)[SPL], uint32_t order
     // count of negatives is the negated sum -- written as `neg -= s` the compiler forms a second value (r >>> 31)
     // per sample for it
     int32_t sacc = 0;
-    uint32_t top = 0x80000000u;
-    if constexpr (SIGNS) asm volatile("" : "+s"(top));   // (an SGPR operand: VOP3 takes no literal)
+    uint32_t top = 0x80000000u, low = 0x7FFFFFFFu;
+    if constexpr (SIGNS) asm volatile("" : "+s"(top), "+s"(low));   // (SGPR operands: VOP3 takes no literal)
 #pragma unroll
     for (int e = 0; e < SPL; e += 2) {
         int32_t r0 = a[e], r1 = a[e + 1];
@@ -372,20 +373,28 @@ __device__ __forceinline__ void wave_rice_fold(int32_t (&a)[SPL], uint32_t order
         if (e + 1 < MAXORD) r1 = (lane0 && (uint32_t)(e + 1) < order) ? 0 : r1;
         int32_t s0 = r0 >> 31, s1 = r1 >> 31;
         asm volatile("" : "+v"(s0), "+v"(s1));   // (keeps them the values the xor below uses)
-        const uint32_t t0 = (uint32_t)(r0 ^ s0), t1 = (uint32_t)(r1 ^ s1);
+        uint32_t t0 = (uint32_t)(r0 ^ s0), tt;
         if constexpr (SIGNS) {
             // (formed HERE, over r's register: left to the compiler the merge is sunk to the word's next use, and r, t and
             // the merged word of every sample are alive together)
-            asm volatile("v_and_or_b32 %0, %0, %2, %3\n\tv_and_or_b32 %1, %1, %2, %4"
-                         : "+v"(r0), "+v"(r1) : "s"(top), "v"(t0), "v"(t1));
+            // Only the merged words stay, so the pair's second t is never formed: t0 + t1 = (r1 ^ s1) + t0 is one
+            // v_xad_u32 over t0's register, and the second merged word t1 | (r1 & 2^31) = r1 ^ (s1 & 0x7FFFFFFF) one
+            // v_bitop3_b32 (truth table 0x78 = a ^ (b & c)) -- tests/test_xad_fold_math.py
+            asm volatile("v_and_or_b32 %0, %0, %3, %2\n\t"
+                         "v_xad_u32 %2, %1, %5, %2\n\t"
+                         "v_bitop3_b32 %1, %1, %5, %4 bitop3:0x78"
+                         : "+v"(r0), "+v"(r1), "+v"(t0) : "s"(top), "s"(low), "v"(s1));
             a[e] = r0;
             a[e + 1] = r1;
+            tt = t0;
         } else {
+            const uint32_t t1 = (uint32_t)(r1 ^ s1);
             a[e] = (int32_t)t0;
             a[e + 1] = (int32_t)t1;
+            tt = t0 + t1;
         }
         sacc += s0 + s1;
-        sum_t += t0 + t1;  // each < 2^31
+        sum_t += tt;  // each t < 2^31
         if ((e & 7) == 6) {
             // pin the partial count: left alone, the 64 sign terms are all kept and summed at the end of the pass
             // (64 more live registers)

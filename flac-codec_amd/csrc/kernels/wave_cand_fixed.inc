@@ -3,18 +3,25 @@
 // for the one-wave-per-candidate kernels, wave_cand_split.inc for the FIXED waves of the split kernel).
 // In scope: p, lane, x[SPL] (shifted), h[4], wasted, bps_eff, N, SPL.  Leaves forder, fw, fixed_bits, fixed_ok.
     // ---- FIXED: abs sums of the iterated differences over [4, n) (encode.rs:3039-3073).
-    // Values are biased by 2^30 (unsigned), |a - b| + acc is one v_sad_u32.  The u32 partial sums are
+    // Values are biased (unsigned), |a - b| + acc is one v_sad_u32 of two values with the SAME bias.  The samples and
+    // the first differences carry 2^30.  The second and third differences are formed as (p ^ 0x7FFFFFFF) + d, one
+    // v_xad_u32 instead of a subtraction and a re-bias: p ^ 0x7FFFFFFF = -p - 1 + 2^31 (mod 2^32), so the result is
+    // d - p + (2^31 - 1) whatever bias d and p share, and it carries 2^31 - 1 itself -- as its predecessor does, so the
+    // v_sad_u32 of the two and the next level's xad hold.  |d_K| < 2^(24 + K) <= 2^27 keeps d_K + 2^31 - 1 inside u32
+    // (tests/test_xad_fold_math.py: the same arithmetic in numpy).  The u32 partial sums are
     // flushed as late as the candidate width allows (<= 25 bits: |d_K| < 2^(24 + K), so 64 terms of
     // orders 0..2, 32 of order 3 and 16 of order 4 stay below 2^32).
     constexpr uint32_t BIAS = 1u << 30;
+    uint32_t flip = 0x7FFFFFFFu;
+    asm volatile("" : "+s"(flip));   // (an SGPR operand: VOP3 takes no literal)
     uint64_t sm[5] = {0, 0, 0, 0, 0}, leaf[5];
     uint32_t w1 = 0, w2 = 0, w3 = 0;
     {
         const uint32_t hb0 = (uint32_t)h[0] + BIAS, hb1 = (uint32_t)h[1] + BIAS, hb2 = (uint32_t)h[2] + BIAS,
                        hb3 = (uint32_t)h[3] + BIAS;
         const uint32_t d1m3 = hb1 - hb0 + BIAS, d1m2 = hb2 - hb1 + BIAS, d1m1 = hb3 - hb2 + BIAS;
-        const uint32_t d2m2 = d1m2 - d1m3 + BIAS, d2m1 = d1m1 - d1m2 + BIAS;
-        uint32_t p0 = hb3, p1 = d1m1, p2 = d2m1, p3 = d2m1 - d2m2 + BIAS;
+        const uint32_t d2m2 = (d1m3 ^ flip) + d1m2, d2m1 = (d1m2 ^ flip) + d1m1;   // bias 2^31 - 1 from here on
+        uint32_t p0 = hb3, p1 = d1m1, p2 = d2m1, p3 = (d2m2 ^ flip) + d2m1;
         uint32_t a0 = 0, a1 = 0, a2 = 0, a3 = 0, a4 = 0;
         asm volatile("" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4));
         uint32_t c0 = 0, c1 = 0, c2 = 0, c3 = 0, c4 = 0;  // contributions of samples 0..3
@@ -24,7 +31,7 @@
             // (the first difference from the UNBIASED previous sample, which is in a register anyway: one
             // instruction instead of a subtraction and a re-bias)
             const uint32_t d1 = xb - (uint32_t)(e ? x[e ? e - 1 : 0] : h[3]);
-            const uint32_t d2 = d1 - p1 + BIAS, d3 = d2 - p2 + BIAS;
+            const uint32_t d2 = (p1 ^ flip) + d1, d3 = (p2 ^ flip) + d2;
             a0 = __usad(xb, BIAS, a0);
             a1 = __usad(xb, p0, a1);
             a2 = __usad(d1, p1, a2);

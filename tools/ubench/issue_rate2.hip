@@ -12,7 +12,7 @@
 enum { ADD = 0, SUB, XOR, ASHR, LSHR_V, MOV, ADD_LIT, SAD, ADD3, OR3, BITOP3, MAD_I64, MAD_I24, LSHL_ADD_U64, ASHR_I64, ALIGNBIT,
        CNDMASK_S, MOV_DPP, ADD_DPP, READLANE, MUL_F64, ADD_F64, FMA_F64, CVT_F64_I32, MAX_I32, MUL_LO, PERM, SNOP, DS_READ_B128,
        MAD_I64_CHAIN, MIX_FIR, AND, OR, LSHL, CMP_VCC, CMP_SGPR, ADD_CO, ADDC, SUBREV, MIN_U32, MUL_I24, ADD_E64_S, BFE_U32, LSHL_ADD,
-       AND_OR, MOV_B64, READFIRST, WRITELANE, LDEXP_F64, NOT, SUB_CO, MIX_AB, MIX_STATS, MIX_AAB, NOPS };
+       AND_OR, MOV_B64, READFIRST, WRITELANE, LDEXP_F64, NOT, SUB_CO, MIX_AB, MIX_STATS, MIX_AAB, XAD, MIX_STATS_XAD, NOPS };
 template <int OP> __global__ void __launch_bounds__(256) k(uint32_t *out, uint64_t *cyc, uint32_t seed) {
     uint32_t a[REP], b = (seed ^ threadIdx.x) & 0x3ff8, c = seed * 3 + 1;
     uint64_t w[REP];
@@ -75,6 +75,7 @@ template <int OP> __global__ void __launch_bounds__(256) k(uint32_t *out, uint64
             if (OP == WRITELANE) asm volatile("v_writelane_b32 %0, s14, 3" : "+v"(a[i]) : : "s14");
             if (OP == LDEXP_F64) asm volatile("v_ldexp_f64 %0, %0, %1" : "+v"(w[i]) : "v"(b));
             if (OP == NOT) asm volatile("v_not_b32 %0, %0" : "+v"(a[i]));
+            if (OP == XAD) asm volatile("v_xad_u32 %0, %1, %2, %0" : "+v"(a[i]) : "v"(b), "v"(c));
             // mixes of a fast-class (v_add_u32) and a full-cost (v_sad_u32) instruction: alternating, 2:1, and the
             // order statistics' own pattern (7 fast + 5 sad per sample, here 16 = 9 + 7)
             if (OP == MIX_AB) {
@@ -89,6 +90,13 @@ template <int OP> __global__ void __launch_bounds__(256) k(uint32_t *out, uint64
                 if (i == 1 || i == 3 || i == 5 || i == 8 || i == 10 || i == 12 || i == 14) asm volatile("v_sad_u32 %0, %1, %2, %0" : "+v"(a[i]) : "v"(b), "v"(c));
                 else if (i & 1) asm volatile("v_sub_u32 %0, %1, %0" : "+v"(a[i]) : "v"(b));
                 else asm volatile("v_add_u32 %0, 0x40000000, %0" : "+v"(a[i]));
+            }
+            // the order statistics with the second and third differences as v_xad_u32: per sample 2 fast + 2 xad + 5 sad
+            // (here 16 = 4 + 3 + 9)
+            if (OP == MIX_STATS_XAD) {
+                if (i == 0 || i == 4 || i == 8 || i == 12) asm volatile("v_sub_u32 %0, %1, %0" : "+v"(a[i]) : "v"(b));
+                else if (i == 2 || i == 7 || i == 13) asm volatile("v_xad_u32 %0, %1, %2, %0" : "+v"(a[i]) : "v"(b), "v"(c));
+                else asm volatile("v_sad_u32 %0, %1, %2, %0" : "+v"(a[i]) : "v"(b), "v"(c));
             }
             // a dependent chain of 64-bit multiply-adds, the shape of the in-place FIR (one accumulator per output)
             if (OP == MAD_I64_CHAIN) asm volatile("v_mad_i64_i32 %0, s[10:11], %1, %2, %0" : "+v"(w[0]) : "v"(a[i]), "v"(c) : "s10", "s11");
@@ -148,6 +156,7 @@ int main(int argc, char **argv) {
     R(MUL_I24, "v_mul_i32_i24") R(ADD_E64_S, "v_add_u32_e64_sgpr") R(BFE_U32, "v_bfe_u32") R(LSHL_ADD, "v_lshl_add_u32")
     R(AND_OR, "v_and_or_b32") R(MOV_B64, "v_mov_b64") R(READFIRST, "v_readfirstlane_b32") R(WRITELANE, "v_writelane_b32")
     R(LDEXP_F64, "v_ldexp_f64") R(MIX_AB, "mix_add_sad_1to1") R(MIX_AAB, "mix_add_sad_2to1") R(MIX_STATS, "mix_stats_9fast_7sad")
+    R(XAD, "v_xad_u32") R(MIX_STATS_XAD, "mix_stats_4fast_3xad_9sad")
     fprintf(js, "\n]}\n");
     fclose(js);
     return 0;
