@@ -15,6 +15,7 @@
 #include <algorithm>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 namespace {
@@ -103,17 +104,48 @@ struct flacgpu_decoder {
 };
 
 namespace {
+// A scan's slots in the batch buffer: one per stream with a frame region, 64-byte aligned, a zero tail behind each.
+struct SlotLayout {
+    std::vector<ScanSlot> slots;
+    std::vector<size_t> region_at;       // first byte of the frame region in the caller's buffer
+    std::vector<uint32_t> slot_stream;   // slot -> stream
+    uint64_t at = 0;                     // the end of the last slot
+    // the new slot's index
+    uint32_t add(uint32_t stream, size_t region, uint64_t len, uint32_t channels, uint32_t min_frame) {
+        ScanSlot s{};
+        s.base = at;
+        s.len = len;
+        s.block0 = at / 64;
+        s.channels = channels;
+        s.min_frame = min_frame;
+        slots.push_back(s);
+        region_at.push_back(region);
+        slot_stream.push_back(stream);
+        at += (len + kSlotTail + 63) & ~(uint64_t)63;
+        return (uint32_t)slots.size() - 1;
+    }
+    uint64_t end_of(uint32_t s) const { return s + 1 < slots.size() ? slots[s + 1].base : at; }
+};
+
+// What a device scan leaves on the host: the candidates' positions, records and links, and every slot's first candidate.
+// spec (raw, under FLACGPU_SCAN_SPECULATIVE; else empty): the own extents of the candidates without a link (k_spec_end),
+// 0: none.  heads (device input of a raw scan; else empty): the 16 bytes at every candidate (k_cand_heads).
+struct Candidates {
+    std::vector<uint64_t> pos;
+    std::vector<uint32_t> info, cand0, spec;
+    std::vector<int32_t> link;
+    std::vector<uint8_t> heads;
+    uint32_t n = 0;
+    uint32_t end_of(uint32_t s) const { return s + 1 < cand0.size() ? cand0[s + 1] : n; }
+};
+
 // The device half of a scan: fills every slot (zero tails, 64 bytes of look-ahead) -- host input in one upload, device
-// input with k_gather_slots -- and runs the scan kernels; leaves the candidates' positions, records and links and every
-// slot's first candidate on the host.  `at` = the end of the last slot.  raw: the scan of raw frame streams
-// (k_scan_subset, k_link_raw).  cspec (raw, under FLACGPU_SCAN_SPECULATIVE; else null): the own extents of the candidates
-// without a link (k_spec_end), 0: none.  cheads (device input of a raw scan; else null): the 16 bytes at every candidate
-// (k_cand_heads), downloaded with the links.
-int device_scan(flacgpu_decoder *d, const ScanInput &in, const std::vector<ScanSlot> &slots,
-                const std::vector<size_t> &region_at, const std::vector<uint32_t> &slot_stream, uint64_t at, bool raw,
-                std::vector<uint64_t> &cpos, std::vector<uint32_t> &cinfo, std::vector<int32_t> &clink,
-                std::vector<uint32_t> &cand0, uint32_t *n_cand_out, std::vector<uint32_t> *cspec = nullptr,
-                std::vector<uint8_t> *cheads = nullptr) {
+// input with k_gather_slots -- and runs the scan kernels; the candidates come down into `c`.  raw: the scan of raw frame
+// streams (k_scan_subset, k_link_raw), with the extents and the headers it asks for.
+int device_scan(flacgpu_decoder *d, const ScanInput &in, const SlotLayout &lay, bool raw, bool want_spec, bool want_heads,
+                Candidates &c) {
+    const std::vector<ScanSlot> &slots = lay.slots;
+    const uint64_t at = lay.at;
     const uint32_t S = (uint32_t)slots.size();
     const uint8_t *const *data = in.data;
     const std::string who = std::string(raw ? "flacgpu_decoder_scan_frames" : "flacgpu_decoder_scan") + (in.device ? "_device" : "");
@@ -136,7 +168,7 @@ int device_scan(flacgpu_decoder *d, const ScanInput &in, const std::vector<ScanS
             g_last_error = who + ": out of host memory";
             return FLACGPU_ERR_UNSUPPORTED;
         }
-        for (uint32_t s = 0; s < S; s++) srcs[s] = data[slot_stream[s]] + region_at[s];
+        for (uint32_t s = 0; s < S; s++) srcs[s] = data[lay.slot_stream[s]] + lay.region_at[s];
         if (int rc = d->gather_src.ensure(sizeof(const uint8_t *) * S)) return rc;
     } else {
         // ---- one upload: every region into the pinned staging, zero tails, 64 bytes of look-ahead
@@ -144,8 +176,8 @@ int device_scan(flacgpu_decoder *d, const ScanInput &in, const std::vector<ScanS
         stg = d->staging.as<uint8_t>();
         for (uint32_t s = 0; s < S; s++) {
             const uint64_t b = slots[s].base, l = slots[s].len;
-            const uint64_t e = s + 1 < S ? slots[s + 1].base : buf_bytes;
-            memcpy(stg + b, data[slot_stream[s]] + region_at[s], l);
+            const uint64_t e = s + 1 < S ? slots[s + 1].base : buf_bytes;   // the last: the look-ahead too
+            memcpy(stg + b, data[lay.slot_stream[s]] + lay.region_at[s], l);
             memset(stg + b + l, 0, e - b - l);
         }
     }
@@ -195,9 +227,9 @@ int device_scan(flacgpu_decoder *d, const ScanInput &in, const std::vector<ScanS
     if (int rc = d->cand_crc.ensure(4 * nc)) return rc;
     if (int rc = d->cand_slot.ensure(4 * nc)) return rc;
     if (int rc = d->link.ensure(4 * nc)) return rc;
-    if (cspec)
+    if (want_spec)
         if (int rc = d->spec_len.ensure(4 * nc)) return rc;
-    if (cheads)
+    if (want_heads)
         if (int rc = d->cand_head.ensure(kHeadBytes * nc)) return rc;
     p.cand_pos = d->cand_pos.as<uint64_t>();
     p.cand_info = d->cand_info.as<uint32_t>();
@@ -208,34 +240,35 @@ int device_scan(flacgpu_decoder *d, const ScanInput &in, const std::vector<ScanS
     hipLaunchKernelGGL(k_scan_emit, dim3(n_wg), dim3(WG), 0, d->st, p);
     if (n_cand && raw) hipLaunchKernelGGL(k_link_raw, dim3((n_cand + WG - 1) / WG), dim3(WG), 0, d->st, p);
     else if (n_cand) hipLaunchKernelGGL(k_link, dim3((n_cand + WG - 1) / WG), dim3(WG), 0, d->st, p);
-    if (n_cand && cspec)
+    if (n_cand && want_spec)
         hipLaunchKernelGGL(k_spec_end, dim3((n_cand + 63) / 64), dim3(64), 0, d->st, p, d->spec_len.as<uint32_t>());
-    if (n_cand && cheads)
+    if (n_cand && want_heads)
         hipLaunchKernelGGL(k_cand_heads, dim3((n_cand + WG - 1) / WG), dim3(WG), 0, d->st, p.bytes, p.cand_pos, n_cand,
                            d->cand_head.as<uint4>());
     HIP_TRY(hipGetLastError());
     try {
-        cpos.resize(n_cand);
-        cinfo.resize(n_cand);
-        clink.resize(n_cand);
-        if (cspec) cspec->resize(n_cand);
-        if (cheads) cheads->resize(kHeadBytes * (size_t)n_cand);
+        c.pos.resize(n_cand);
+        c.info.resize(n_cand);
+        c.link.resize(n_cand);
+        c.cand0.resize(S);
+        if (want_spec) c.spec.resize(n_cand);
+        if (want_heads) c.heads.resize(kHeadBytes * (size_t)n_cand);
     } catch (const std::bad_alloc &) {
         g_last_error = who + ": out of host memory";
         return FLACGPU_ERR_UNSUPPORTED;
     }
     if (n_cand) {
-        HIP_TRY(hipMemcpyAsync(cpos.data(), p.cand_pos, 8 * (size_t)n_cand, hipMemcpyDeviceToHost, d->st));
-        HIP_TRY(hipMemcpyAsync(cinfo.data(), p.cand_info, 4 * (size_t)n_cand, hipMemcpyDeviceToHost, d->st));
-        HIP_TRY(hipMemcpyAsync(clink.data(), p.link, 4 * (size_t)n_cand, hipMemcpyDeviceToHost, d->st));
-        if (cspec)   // with the links, in the same submission
-            HIP_TRY(hipMemcpyAsync(cspec->data(), d->spec_len.p, 4 * (size_t)n_cand, hipMemcpyDeviceToHost, d->st));
-        if (cheads)
-            HIP_TRY(hipMemcpyAsync(cheads->data(), d->cand_head.p, kHeadBytes * (size_t)n_cand, hipMemcpyDeviceToHost, d->st));
+        HIP_TRY(hipMemcpyAsync(c.pos.data(), p.cand_pos, 8 * (size_t)n_cand, hipMemcpyDeviceToHost, d->st));
+        HIP_TRY(hipMemcpyAsync(c.info.data(), p.cand_info, 4 * (size_t)n_cand, hipMemcpyDeviceToHost, d->st));
+        HIP_TRY(hipMemcpyAsync(c.link.data(), p.link, 4 * (size_t)n_cand, hipMemcpyDeviceToHost, d->st));
+        if (want_spec)   // with the links, in the same submission
+            HIP_TRY(hipMemcpyAsync(c.spec.data(), d->spec_len.p, 4 * (size_t)n_cand, hipMemcpyDeviceToHost, d->st));
+        if (want_heads)
+            HIP_TRY(hipMemcpyAsync(c.heads.data(), d->cand_head.p, kHeadBytes * (size_t)n_cand, hipMemcpyDeviceToHost, d->st));
     }
-    HIP_TRY(hipMemcpyAsync(cand0.data(), p.slot_cand0, 4 * (size_t)S, hipMemcpyDeviceToHost, d->st));
+    HIP_TRY(hipMemcpyAsync(c.cand0.data(), p.slot_cand0, 4 * (size_t)S, hipMemcpyDeviceToHost, d->st));
     HIP_TRY(hipStreamSynchronize(d->st));
-    *n_cand_out = n_cand;
+    c.n = n_cand;
     return FLACGPU_OK;
 }
 
@@ -264,6 +297,20 @@ int device_meta_walk(flacgpu_decoder *d, const uint8_t *const *data, const size_
     return FLACGPU_OK;
 }
 
+// The end of both scans: the frame table onto the device, the batch's sizes and its slots' streams into the handle.
+int finish_scan(flacgpu_decoder *d, SlotLayout &lay, uint64_t total, uint64_t scratch_total) {
+    if (!d->frame_tab.empty()) {
+        if (int rc = d->frames.ensure(sizeof(ManyFrame) * d->frame_tab.size())) return rc;
+        HIP_TRY(hipMemcpyAsync(d->frames.p, d->frame_tab.data(), sizeof(ManyFrame) * d->frame_tab.size(),
+                               hipMemcpyHostToDevice, d->st));
+        HIP_TRY(hipStreamSynchronize(d->st));   // frame_tab may change before the copy is done otherwise
+    }
+    d->total = total;
+    d->scratch_total = scratch_total;
+    d->slot_stream.swap(lay.slot_stream);
+    return FLACGPU_OK;
+}
+
 int scan_impl(flacgpu_decoder *d, const ScanInput &in, const size_t *len, uint32_t n) {
     const uint8_t *const *data = in.data;
     d->res.assign(n, flacgpu_decoded_stream{});
@@ -274,10 +321,7 @@ int scan_impl(flacgpu_decoder *d, const ScanInput &in, const size_t *len, uint32
     if (in.device)
         if (int rc = device_meta_walk(d, data, len, n, meta)) return rc;
     // ---- host: metadata, slot layout
-    std::vector<ScanSlot> slots;
-    std::vector<size_t> region_at;   // first byte of the frame region in the caller's buffer
-    std::vector<uint32_t> slot_stream;
-    uint64_t at = 0;
+    SlotLayout lay;
     for (uint32_t i = 0; i < n; i++) {
         flacgpu_decoded_stream &r = d->res[i];
         uint32_t min_frame = 0;
@@ -286,51 +330,35 @@ int scan_impl(flacgpu_decoder *d, const ScanInput &in, const size_t *len, uint32
                                     : flacenc::parse_metadata(data ? data[i] : nullptr, len ? len[i] : 0, &r.info, &min_frame, &pos);
         r.rc = why ? FLACGPU_ERR_INVALID_ARG : FLACGPU_OK;
         if (r.rc != FLACGPU_OK || pos >= len[i]) continue;   // no frame region: 0 frames, nothing bad
-        ScanSlot s;
-        s.base = at;
-        s.len = len[i] - pos;
-        s.block0 = at / 64;
-        s.channels = r.info.channels;
-        s.min_frame = min_frame;
-        d->slot_of[i] = (int32_t)slots.size();
-        slots.push_back(s);
-        region_at.push_back(pos);
-        slot_stream.push_back(i);
-        at += (s.len + kSlotTail + 63) & ~(uint64_t)63;
+        d->slot_of[i] = (int32_t)lay.add(i, pos, len[i] - pos, r.info.channels, min_frame);
     }
-    const uint32_t S = (uint32_t)slots.size();
+    const uint32_t S = (uint32_t)lay.slots.size();
     d->n_slots = S;
-    std::vector<uint64_t> cpos;
-    std::vector<uint32_t> cinfo, cand0(S);
-    std::vector<int32_t> clink;
-    uint32_t n_cand = 0;
     if (S) {
-        if (int rc = device_scan(d, in, slots, region_at, slot_stream, at, false, cpos, cinfo, clink, cand0, &n_cand))
-            return rc;
+        Candidates c;
+        if (int rc = device_scan(d, in, lay, false, false, false, c)) return rc;
         // ---- host walk: follow the links from each region's first byte (the host scan's lost-sync rule: a frame
         // without an end is not taken, and nothing behind it is decoded)
         for (uint32_t s = 0; s < S; s++) {
-            const ScanSlot &sl = slots[s];
-            flacgpu_stream_info &info = d->res[slot_stream[s]].info;
-            const uint32_t c_end = s + 1 < S ? cand0[s + 1] : n_cand;
-            uint32_t i = cand0[s];
+            const ScanSlot &sl = lay.slots[s];
+            flacgpu_stream_info &info = d->res[lay.slot_stream[s]].info;
+            uint32_t i = c.cand0[s];
             uint64_t samples = 0;
             uint32_t F = 0;
-            const uint64_t slot_end = s + 1 < S ? slots[s + 1].base : at;
-            if (i >= c_end || cpos[i] != sl.base) {
+            if (i >= c.end_of(s) || c.pos[i] != sl.base) {
                 info.bad_frames = 1;
             } else {
                 for (;;) {
-                    const int32_t nx = clink[i];
+                    const int32_t nx = c.link[i];
                     if (nx == LINK_NONE) {
                         info.bad_frames = 1;
                         break;
                     }
                     ManyFrame f{};
-                    f.start = cpos[i];
-                    f.end = nx == LINK_END ? sl.base + sl.len : cpos[nx];
-                    f.cap = slot_end - 4;
-                    f.n = (cinfo[i] & 0xFFFFu) + 1u;
+                    f.start = c.pos[i];
+                    f.end = nx == LINK_END ? sl.base + sl.len : c.pos[nx];
+                    f.cap = lay.end_of(s) - 4;
+                    f.n = (c.info[i] & 0xFFFFu) + 1u;
                     f.slot = s;
                     f.channels = info.channels;
                     f.bps = info.bits_per_sample;
@@ -355,21 +383,12 @@ int scan_impl(flacgpu_decoder *d, const ScanInput &in, const size_t *len, uint32
     }
     uint64_t scratch_total = 0;
     for (ManyFrame &f : d->frame_tab) {
-        const flacgpu_decoded_stream &r = d->res[slot_stream[f.slot]];
+        const flacgpu_decoded_stream &r = d->res[lay.slot_stream[f.slot]];
         f.out = r.out_offset + f.out * f.channels;
         f.scratch = scratch_total;
         scratch_total += (uint64_t)f.channels * ((f.n + 3u) & ~3u);
     }
-    if (!d->frame_tab.empty()) {
-        if (int rc = d->frames.ensure(sizeof(ManyFrame) * d->frame_tab.size())) return rc;
-        HIP_TRY(hipMemcpyAsync(d->frames.p, d->frame_tab.data(), sizeof(ManyFrame) * d->frame_tab.size(),
-                               hipMemcpyHostToDevice, d->st));
-        HIP_TRY(hipStreamSynchronize(d->st));   // frame_tab may change before the copy is done otherwise
-    }
-    d->total = total;
-    d->scratch_total = scratch_total;
-    d->slot_stream.swap(slot_stream);
-    return FLACGPU_OK;
+    return finish_scan(d, lay, total, scratch_total);
 }
 
 // flacgpu_decoder_scan_frames behind its argument checks: a slot is a whole input, the device finds the candidates and
@@ -378,14 +397,9 @@ int scan_impl(flacgpu_decoder *d, const ScanInput &in, const size_t *len, uint32
 int scan_raw_impl(flacgpu_decoder *d, const ScanInput &in, const size_t *len, uint32_t n, uint32_t flags) {
     const uint8_t *const *data = in.data;
     const bool spec = flags & FLACGPU_SCAN_SPECULATIVE;
-    std::vector<uint8_t> cheads;   // device input: the candidates' headers (k_cand_heads)
     d->slot_bytes = 0;
-    std::vector<ScanSlot> slots;
-    std::vector<size_t> region_at;
-    std::vector<uint32_t> slot_stream, cinfo, cand0, cspec;
-    std::vector<uint64_t> cpos;
-    std::vector<int32_t> clink;
-    uint64_t at = 0;
+    SlotLayout lay;
+    Candidates c;   // heads (device input): the candidates' headers
     try {   // no exception crosses the C ABI
         d->res.assign(n, flacgpu_decoded_stream{});
         d->slot_of.assign(n, -1);
@@ -394,28 +408,17 @@ int scan_raw_impl(flacgpu_decoder *d, const ScanInput &in, const size_t *len, ui
         d->raw_streams.assign(n, flacgpu_raw_stream{});
         for (uint32_t i = 0; i < n; i++) {
             if (!data[i] || !len[i]) continue;   // nothing to scan: no kept frame
-            ScanSlot s{};
-            s.base = at;
-            s.len = len[i];
-            s.block0 = at / 64;
-            d->slot_of[i] = (int32_t)slots.size();
-            slots.push_back(s);
-            region_at.push_back(0);
-            slot_stream.push_back(i);
-            at += (s.len + kSlotTail + 63) & ~(uint64_t)63;
+            d->slot_of[i] = (int32_t)lay.add(i, 0, len[i], 0, 0);
         }
-        cand0.resize(slots.size());
     } catch (const std::bad_alloc &) {
         g_last_error = "flacgpu_decoder_scan_frames: out of host memory";
         return FLACGPU_ERR_UNSUPPORTED;
     }
-    const uint32_t S = (uint32_t)slots.size();
+    const uint32_t S = (uint32_t)lay.slots.size();
     d->n_slots = S;
-    uint32_t n_cand = 0;
     if (S)
-        if (int rc = device_scan(d, in, slots, region_at, slot_stream, at, true, cpos, cinfo, clink, cand0, &n_cand,
-                                 spec ? &cspec : nullptr, in.device ? &cheads : nullptr))
-            return rc;
+        if (int rc = device_scan(d, in, lay, true, spec, in.device, c)) return rc;
+    const uint32_t n_cand = c.n;
     // ---- host walk, stream by stream: the candidates in ascending order, those below the cursor ignored, one without
     // an end passed over, one with an end kept and the cursor moved to that end.  A kept frame's record is read from
     // its own header: in the staging copy of the bytes, or (device input) in the downloaded table of headers.
@@ -434,28 +437,30 @@ int scan_raw_impl(flacgpu_decoder *d, const ScanInput &in, const size_t *len, ui
             const size_t first = d->records.size();
             const int32_t s = d->slot_of[i];
             if (s >= 0) {
-                const ScanSlot &sl = slots[s];
-                const uint32_t c_end = (uint32_t)s + 1 < S ? cand0[s + 1] : n_cand;
-                const uint64_t slot_end = (uint32_t)s + 1 < S ? slots[s + 1].base : at;
+                const ScanSlot &sl = lay.slots[s];
+                const uint32_t c_end = c.end_of((uint32_t)s);
                 uint64_t cursor = sl.base;
-                for (uint32_t c = cand0[s]; c < c_end; c++) {
-                    const bool own = clink[c] == LINK_NONE && spec && cspec[c];
-                    if (cpos[c] < cursor || (clink[c] == LINK_NONE && !own)) continue;
-                    const uint64_t end = own ? cpos[c] + cspec[c] : clink[c] == LINK_END ? sl.base + sl.len : cpos[clink[c]];
+                for (uint32_t k = c.cand0[s]; k < c_end; k++) {
+                    const uint64_t at = c.pos[k];
+                    const uint32_t cinfo = c.info[k];
+                    const int32_t link = c.link[k];
+                    const bool own = link == LINK_NONE && spec && c.spec[k];
+                    if (at < cursor || (link == LINK_NONE && !own)) continue;
+                    const uint64_t end = own ? at + c.spec[k] : link == LINK_END ? sl.base + sl.len : c.pos[link];
                     flacenc::HostFrameInfo h;   // the header was accepted by K_s1: its record, and the rest from its bytes
-                    h.n = (cinfo[c] & 0xFFFFu) + 1u;
-                    h.header_bytes = (cinfo[c] >> 16) & 0xFFu;
-                    h.blocking = cinfo[c] >> 24;
-                    const uint8_t *head = in.device ? cheads.data() + kHeadBytes * (size_t)c : stg + cpos[c];
+                    h.n = (cinfo & 0xFFFFu) + 1u;
+                    h.header_bytes = (cinfo >> 16) & 0xFFu;
+                    h.blocking = cinfo >> 24;
+                    const uint8_t *head = in.device ? c.heads.data() + kHeadBytes * (size_t)k : stg + at;
                     h.acode = head[3] >> 4;
                     h.bps_code = (head[3] >> 1) & 7;
                     flacenc::host_frame_fields(head, h);   // reads header_bytes <= kHeadBytes bytes
                     flacgpu_frame_record f{};
-                    f.byte_offset = cpos[c] - sl.base;
+                    f.byte_offset = at - sl.base;
                     f.number = h.number;
                     f.out_offset = elements;
                     f.stream = i;
-                    f.bytes = (uint32_t)(end - cpos[c]);
+                    f.bytes = (uint32_t)(end - at);
                     f.block_size = h.n;
                     f.sample_rate = h.sample_rate;
                     f.channels = h.channels;
@@ -464,9 +469,9 @@ int scan_raw_impl(flacgpu_decoder *d, const ScanInput &in, const size_t *len, ui
                     f.blocking = h.blocking;
                     f.reserved = own ? FLACGPU_FRAME_SPECULATIVE : 0u;
                     ManyFrame m{};
-                    m.start = cpos[c];
+                    m.start = at;
                     m.end = end;
-                    m.cap = slot_end - 4;
+                    m.cap = lay.end_of((uint32_t)s) - 4;
                     m.scratch = raw_scratch;
                     m.out = elements;
                     m.n = h.n;
@@ -517,83 +522,163 @@ int scan_raw_impl(flacgpu_decoder *d, const ScanInput &in, const size_t *len, ui
         g_last_error = "flacgpu_decoder_scan_frames: more than 2^31 - 1 frames";
         return FLACGPU_ERR_UNSUPPORTED;
     }
-    if (!d->frame_tab.empty()) {
-        if (int rc = d->frames.ensure(sizeof(ManyFrame) * d->frame_tab.size())) return rc;
-        HIP_TRY(hipMemcpyAsync(d->frames.p, d->frame_tab.data(), sizeof(ManyFrame) * d->frame_tab.size(),
-                               hipMemcpyHostToDevice, d->st));
-        HIP_TRY(hipStreamSynchronize(d->st));   // frame_tab may change before the copy is done otherwise
-    }
-    d->total = total;
-    d->scratch_total = scratch_total;
     d->raw_elements = elements;
     d->raw_scratch = raw_scratch;
-    d->slot_stream.swap(slot_stream);
+    return finish_scan(d, lay, total, scratch_total);
+}
+
+// The frame kernels over one frame table, for every decode call: K_d1 decodes each frame into planar scratch, K_d2 tests
+// its CRC-16, and the finish kernel that the caller launches behind them counts the frames that did not parse.
+// counts[2 k] / counts[2 k + 1]: the frames of pair k that did not parse / whose CRC-16 is wrong, where k is the table's
+// `slot` -- a slot of the scan, a frame or a window.  A table without frames launches nothing; a call without pairs
+// still owns a pair, so that counts.p is memory a kernel may be handed.
+struct FramePass {
+    flacgpu_decoder *d;
+    const ManyFrame *frames = nullptr;   // device memory
+    uint32_t F = 0;
+    size_t pairs = 0;
+
+    // scratch (of scratch_elems samples), codes and counts are there, and the counts are zero on the decoder's stream
+    int open(const ManyFrame *table, uint32_t n_frames, uint64_t scratch_elems, size_t n_pairs) {
+        frames = table;
+        F = n_frames;
+        pairs = n_pairs;
+        const size_t count_bytes = 8 * std::max<size_t>(pairs, 1);
+        if (int rc = d->counts.ensure(count_bytes)) return rc;
+        if (F) {
+            if (int rc = d->scratch.ensure(4 * scratch_elems)) return rc;
+            if (int rc = d->codes.ensure(4 * (size_t)F)) return rc;
+        }
+        HIP_TRY(hipMemsetAsync(d->counts.p, 0, count_bytes, d->st));
+        return FLACGPU_OK;
+    }
+    // K_d1, a lane per frame in waves of 32 lanes (every lane reads and writes cache lines of its own: decode.hip's
+    // launch_decode measured 32 against 64, 16 and 8), and K_d2
+    void launch() const {
+        if (!F) return;
+        const uint32_t lanes = 32;
+        hipLaunchKernelGGL(k_decode_many<32>, dim3((F + lanes - 1) / lanes), dim3(lanes), 0, d->st,
+                           d->bytes.as<const uint32_t>(), frames, F, d->scratch.as<int32_t>(), d->codes.as<uint32_t>());
+        hipLaunchKernelGGL(k_frame_crc, dim3(F), dim3(64), 0, d->st, d->bytes.as<const uint8_t>(), frames,
+                           d->counts.as<uint32_t>());
+    }
+    // The pairs on their way into `counts`, behind everything launched so far: read them after the caller's
+    // synchronisation.  No exception crosses the C ABI; the kernels are waited for before a refusal returns.
+    int fetch(std::vector<uint32_t> &counts, const char *who) const {
+        try {
+            counts.resize(2 * pairs);
+        } catch (const std::bad_alloc &) {
+            (void)hipStreamSynchronize(d->st);
+            g_last_error = std::string(who) + ": out of host memory";
+            return FLACGPU_ERR_UNSUPPORTED;
+        }
+        if (pairs) HIP_TRY(hipMemcpyAsync(counts.data(), d->counts.p, 8 * pairs, hipMemcpyDeviceToHost, d->st));
+        return FLACGPU_OK;
+    }
+};
+// bit 0: the frame of this pair did not parse; bit 1: its CRC-16 is wrong (a pair that counts one frame)
+inline uint32_t pair_status(const std::vector<uint32_t> &counts, size_t k) {
+    return (counts[2 * k] ? 1u : 0u) | (counts[2 * k + 1] ? 2u : 0u);
+}
+
+// Where a call's kernels write: the caller's buffer when that is device memory, else a buffer of the decoder's, which
+// `download` sends to the caller's behind the kernels.  An output without bytes is never staged.
+struct OutStage {
+    void *out = nullptr, *dst = nullptr;
+    size_t bytes = 0;
+    bool staged = false;
+    int open(DevBuf &stage, void *out_, size_t bytes_, bool to_device) {
+        out = dst = out_;
+        bytes = bytes_;
+        staged = !to_device && bytes;
+        if (!staged) return FLACGPU_OK;
+        if (int rc = stage.ensure(bytes)) return rc;
+        dst = stage.p;
+        return FLACGPU_OK;
+    }
+    int download(hipStream_t st) const {
+        if (staged) HIP_TRY(hipMemcpyAsync(out, dst, bytes, hipMemcpyDeviceToHost, st));
+        return FLACGPU_OK;
+    }
+};
+
+// f(std::integral_constant<uint32_t, DT_*>{}) for the FLACGPU_SAMPLE_* value `dtype` (a validated one)
+template <class F> void with_dtype(uint32_t dtype, F f) {
+    if (dtype == FLACGPU_SAMPLE_I16) f(std::integral_constant<uint32_t, DT_I16>{});
+    else if (dtype == FLACGPU_SAMPLE_F32) f(std::integral_constant<uint32_t, DT_F32>{});
+    else if (dtype == FLACGPU_SAMPLE_S24) f(std::integral_constant<uint32_t, DT_S24>{});
+    else f(std::integral_constant<uint32_t, DT_I32>{});
+}
+
+int refuse_rows(const char *who, uint64_t rows) {
+    if (rows <= 0x7FFFFFFFull) return FLACGPU_OK;
+    g_last_error = std::string(who) + ": more than 2^31 - 1 padded rows";
+    return FLACGPU_ERR_UNSUPPORTED;
+}
+
+// ---- what the three plans refuse alike: `who` is the call, the differing words are the caller's ----
+// `what` ("stream 3", "window 3") with `detail` ("2 channels, 100 samples") does not fit the padded batch
+int refuse_fit(const std::string &who, const std::string &what, const std::string &detail) {
+    g_last_error = who + ": " + what + " (" + detail + ") does not fit channels_padded x samples_padded";
+    return FLACGPU_ERR_INVALID_ARG;
+}
+// a stream of `bps` bits per sample does not go into `dtype`
+bool too_wide(uint32_t dtype, uint32_t bps) { return sample_type_max_bits(dtype) && bps > sample_type_max_bits(dtype); }
+int refuse_bits(const std::string &who, uint32_t dtype, uint32_t stream, uint32_t bps) {
+    g_last_error = who + ": " + sample_type_name(dtype) + " output, but stream " + std::to_string(stream) + " has " +
+                   std::to_string(bps) + " bits per sample";
+    return FLACGPU_ERR_UNSUPPORTED;
+}
+// *bytes = rows * row_elems * elem_bytes, refused when that overflows: `what` ("the padded batch exceeds")
+int padded_bytes(const std::string &who, const char *what, uint64_t rows, uint64_t row_elems, uint64_t elem_bytes,
+                 uint64_t *bytes) {
+    uint64_t b = 0;
+    if (__builtin_mul_overflow(rows, row_elems, &b) || __builtin_mul_overflow(b, elem_bytes, &b)) {
+        g_last_error = who + ": " + what + " 2^64 bytes";
+        return FLACGPU_ERR_UNSUPPORTED;
+    }
+    *bytes = b;
     return FLACGPU_OK;
 }
 
-// flacgpu_decoder_decode_frames behind its argument checks: decode's frame kernels over decode_frames' own table, whose
-// slots are the frames, so that counts[2 f] / counts[2 f + 1] say whether frame f parsed and whether its CRC-16 is right.
+// K_d6 over the rows of a padded batch (streams or windows x channels_padded), whose table lies in pad_streams: zeroes
+// what no frame writes.  A batch without an element has no row to launch for.
+void launch_pad_rows(flacgpu_decoder *d, uint32_t rows, const flacgpu_out_format &fmt, void *dst) {
+    if (!rows || !fmt.samples_padded) return;
+    with_dtype(fmt.dtype, [&](auto dt) {
+        hipLaunchKernelGGL(k_pad_rows<elem_bytes<decltype(dt)::value>()>, dim3(rows), dim3(WG), 0, d->st,
+                           d->pad_streams.as<const PadStream>(), fmt.channels_padded, fmt.samples_padded,
+                           static_cast<uint8_t *>(dst));
+    });
+}
+
+// flacgpu_decoder_decode_frames behind its argument checks: the frame pass over decode_frames' own table, whose slots
+// are the frames, so that pair f says whether frame f parsed and whether its CRC-16 is right.
 int decode_frames_impl(flacgpu_decoder *d, int32_t *out, uint32_t flags, flacgpu_frame_record *records) {
     DeviceGuard guard(d->device);
     const uint32_t F = (uint32_t)d->records.size();
-    if (!F) return FLACGPU_OK;
-    const bool to_device = flags & FLACGPU_DECODE_OUT_DEVICE;
-    const size_t out_bytes = 4 * d->raw_elements;
-    int32_t *dst = out;
-    if (!to_device) {
-        if (int rc = d->out_stage.ensure(out_bytes)) return rc;
-        dst = d->out_stage.as<int32_t>();
-    }
-    if (int rc = d->counts.ensure(8 * (size_t)F)) return rc;
-    if (int rc = d->scratch.ensure(4 * d->raw_scratch)) return rc;
-    if (int rc = d->codes.ensure(4 * (size_t)F)) return rc;
+    if (!F) return FLACGPU_OK;   // a call without a record to fill does nothing at all
+    OutStage o;
+    if (int rc = o.open(d->out_stage, out, 4 * d->raw_elements, flags & FLACGPU_DECODE_OUT_DEVICE)) return rc;
     if (!d->raw_tab_uploaded) {   // once per scan: a batch that only goes through decode / decode_as never pays for it
         if (int rc = d->raw_frames.ensure(sizeof(ManyFrame) * (size_t)F)) return rc;
         HIP_TRY(hipMemcpyAsync(d->raw_frames.p, d->raw_tab.data(), sizeof(ManyFrame) * (size_t)F, hipMemcpyHostToDevice, d->st));
         HIP_TRY(hipStreamSynchronize(d->st));
         d->raw_tab_uploaded = true;
     }
-    HIP_TRY(hipMemsetAsync(d->counts.p, 0, 8 * (size_t)F, d->st));
-    const ManyFrame *frames = d->raw_frames.as<const ManyFrame>();
-    const uint32_t lanes = 32;   // as decode_impl launches it
-    hipLaunchKernelGGL(k_decode_many<32>, dim3((F + lanes - 1) / lanes), dim3(lanes), 0, d->st,
-                       d->bytes.as<const uint32_t>(), frames, F, d->scratch.as<int32_t>(), d->codes.as<uint32_t>());
-    hipLaunchKernelGGL(k_frame_crc, dim3(F), dim3(64), 0, d->st, d->bytes.as<const uint8_t>(), frames,
-                       d->counts.as<uint32_t>());
-    hipLaunchKernelGGL(k_finish_many, dim3(F), dim3(WG), 0, d->st, frames, d->scratch.as<const int32_t>(),
-                       d->codes.as<const uint32_t>(), dst, d->counts.as<uint32_t>());
+    FramePass pass{d};
+    if (int rc = pass.open(d->raw_frames.as<const ManyFrame>(), F, d->raw_scratch, F)) return rc;
+    pass.launch();
+    hipLaunchKernelGGL(k_finish_many, dim3(F), dim3(WG), 0, d->st, pass.frames, d->scratch.as<const int32_t>(),
+                       d->codes.as<const uint32_t>(), static_cast<int32_t *>(o.dst), d->counts.as<uint32_t>());
     HIP_TRY(hipGetLastError());
     std::vector<uint32_t> counts;
-    try {   // no exception crosses the C ABI; the kernels are waited for before the return
-        counts.resize(2 * (size_t)F);
-    } catch (const std::bad_alloc &) {
-        (void)hipStreamSynchronize(d->st);
-        g_last_error = "flacgpu_decoder_decode_frames: out of host memory";
-        return FLACGPU_ERR_UNSUPPORTED;
-    }
-    HIP_TRY(hipMemcpyAsync(counts.data(), d->counts.p, 8 * (size_t)F, hipMemcpyDeviceToHost, d->st));
-    if (!to_device) HIP_TRY(hipMemcpyAsync(out, dst, out_bytes, hipMemcpyDeviceToHost, d->st));
+    if (int rc = pass.fetch(counts, "flacgpu_decoder_decode_frames")) return rc;
+    if (int rc = o.download(d->st)) return rc;
     HIP_TRY(hipStreamSynchronize(d->st));
     memcpy(records, d->records.data(), sizeof(flacgpu_frame_record) * F);
-    for (uint32_t f = 0; f < F; f++)
-        records[f].status = (counts[2 * (size_t)f] ? 1u : 0u) | (counts[2 * (size_t)f + 1] ? 2u : 0u);
+    for (uint32_t f = 0; f < F; f++) records[f].status = pair_status(counts, f);
     return FLACGPU_OK;
-}
-
-// k_pad_rows for the element size of `dtype`
-void launch_pad_rows(uint32_t dtype, uint32_t rows, hipStream_t st, const PadStream *streams, uint32_t Cp, uint64_t T,
-                     void *dst) {
-    const auto k = dtype == FLACGPU_SAMPLE_I16 ? k_pad_rows<2> : dtype == FLACGPU_SAMPLE_S24 ? k_pad_rows<3> : k_pad_rows<4>;
-    hipLaunchKernelGGL(k, dim3(rows), dim3(WG), 0, st, streams, Cp, T, static_cast<uint8_t *>(dst));
-}
-
-// the finish kernel of a format other than I32 / FLAT
-template <uint32_t DT, bool PADDED>
-void launch_finish_as(flacgpu_decoder *d, uint32_t F, void *dst, uint64_t samples_padded, int32_t *side) {
-    const auto k = side ? k_finish_as<DT, PADDED, true> : k_finish_as<DT, PADDED, false>;
-    hipLaunchKernelGGL(k, dim3(F), dim3(WG), 0, d->st, d->frames.as<const ManyFrame>(),
-                       d->scratch.as<const int32_t>(), d->codes.as<const uint32_t>(), static_cast<uint8_t *>(dst),
-                       d->pad_out.as<const uint64_t>(), samples_padded, side, d->counts.as<uint32_t>());
 }
 
 // decode_as, before the frame kernels: for PADDED the first element of every frame and the kernel that zeroes what no
@@ -604,10 +689,7 @@ int finish_as_tables(flacgpu_decoder *d, const flacgpu_out_format &fmt, void *ds
     const uint64_t T = fmt.samples_padded;
     const size_t F = d->frame_tab.size();
     if (!n || !Cp || !T) return FLACGPU_OK;
-    if ((uint64_t)n * Cp > 0x7FFFFFFFull) {
-        g_last_error = "flacgpu_decoder_decode_as: more than 2^31 - 1 padded rows";
-        return FLACGPU_ERR_UNSUPPORTED;
-    }
+    if (int rc = refuse_rows("flacgpu_decoder_decode_as", (uint64_t)n * Cp)) return rc;
     std::vector<uint64_t> first(F);
     for (size_t f = 0; f < F; f++) {
         const ManyFrame &fr = d->frame_tab[f];
@@ -626,7 +708,7 @@ int finish_as_tables(flacgpu_decoder *d, const flacgpu_out_format &fmt, void *ds
     if (int rc = d->pad_streams.ensure(sizeof(PadStream) * n)) return rc;
     HIP_TRY(hipMemcpyAsync(d->pad_streams.p, ps.data(), sizeof(PadStream) * n, hipMemcpyHostToDevice, d->st));
     HIP_TRY(hipStreamSynchronize(d->st));   // the tables leave scope
-    launch_pad_rows(fmt.dtype, n * Cp, d->st, d->pad_streams.as<const PadStream>(), Cp, T, dst);
+    launch_pad_rows(d, n * Cp, fmt, dst);
     HIP_TRY(hipGetLastError());
     return FLACGPU_OK;
 }
@@ -638,57 +720,38 @@ int decode_impl(flacgpu_decoder *d, void *out, uint32_t flags, flacgpu_decoded_s
                 const flacgpu_out_format *fmt = nullptr, uint64_t out_bytes = 0) {
     DeviceGuard guard(d->device);
     const uint32_t n = (uint32_t)d->res.size();
-    const uint32_t F = (uint32_t)d->frame_tab.size(), S = d->n_slots;
-    const bool to_device = flags & FLACGPU_DECODE_OUT_DEVICE, md5 = !(flags & FLACGPU_DECODE_NO_MD5);
-    if (!fmt) out_bytes = 4 * d->total;
-    void *dst = out;
-    if (!to_device && out_bytes) {
-        if (int rc = d->out_stage.ensure(out_bytes)) return rc;
-        dst = d->out_stage.p;
-    }
-    const int32_t *hashed = static_cast<const int32_t *>(dst);   // what k_md5_many reads
+    const bool md5 = !(flags & FLACGPU_DECODE_NO_MD5);
+    OutStage o;
+    if (int rc = o.open(d->out_stage, out, fmt ? out_bytes : 4 * d->total, flags & FLACGPU_DECODE_OUT_DEVICE)) return rc;
+    int32_t *side = nullptr;   // decode_as with MD5: the interleaved int32 that k_md5_many reads
     if (fmt) {
-        int32_t *side = nullptr;
         if (md5 && d->total) {
             if (int rc = d->md5_stage.ensure(4 * d->total)) return rc;
             side = d->md5_stage.as<int32_t>();
         }
-        hashed = side;
-        if (int rc = finish_as_tables(d, *fmt, dst)) return rc;
+        if (int rc = finish_as_tables(d, *fmt, o.dst)) return rc;
     }
-    if (int rc = d->counts.ensure(8 * (size_t)std::max<uint32_t>(S, 1))) return rc;
-    HIP_TRY(hipMemsetAsync(d->counts.p, 0, 8 * (size_t)std::max<uint32_t>(S, 1), d->st));
-    if (F) {
-        if (int rc = d->scratch.ensure(4 * d->scratch_total)) return rc;
-        if (int rc = d->codes.ensure(4 * (size_t)F)) return rc;
-        const uint32_t lanes = 32;   // launch_decode_frames' wave size
-        hipLaunchKernelGGL(k_decode_many<32>, dim3((F + lanes - 1) / lanes), dim3(lanes), 0, d->st,
-                           d->bytes.as<const uint32_t>(), d->frames.as<const ManyFrame>(), F, d->scratch.as<int32_t>(),
-                           d->codes.as<uint32_t>());
-        hipLaunchKernelGGL(k_frame_crc, dim3(F), dim3(64), 0, d->st, d->bytes.as<const uint8_t>(),
-                           d->frames.as<const ManyFrame>(), d->counts.as<uint32_t>());
-        if (!fmt) {
-            hipLaunchKernelGGL(k_finish_many, dim3(F), dim3(WG), 0, d->st, d->frames.as<const ManyFrame>(),
-                               d->scratch.as<const int32_t>(), d->codes.as<const uint32_t>(),
-                               static_cast<int32_t *>(dst), d->counts.as<uint32_t>());
-        } else {
-            const bool padded = fmt->layout == FLACGPU_LAYOUT_PADDED;
-            int32_t *side = const_cast<int32_t *>(hashed);
-            const uint64_t T = fmt->samples_padded;
-            if (fmt->dtype == FLACGPU_SAMPLE_I16)
-                padded ? launch_finish_as<DT_I16, true>(d, F, dst, T, side)
-                       : launch_finish_as<DT_I16, false>(d, F, dst, T, side);
-            else if (fmt->dtype == FLACGPU_SAMPLE_F32)
-                padded ? launch_finish_as<DT_F32, true>(d, F, dst, T, side)
-                       : launch_finish_as<DT_F32, false>(d, F, dst, T, side);
-            else if (fmt->dtype == FLACGPU_SAMPLE_S24)
-                padded ? launch_finish_as<DT_S24, true>(d, F, dst, T, side)
-                       : launch_finish_as<DT_S24, false>(d, F, dst, T, side);
-            else   // I32 / FLAT takes the branch above
-                launch_finish_as<DT_I32, true>(d, F, dst, T, side);
-        }
-        HIP_TRY(hipGetLastError());
+    const int32_t *hashed = fmt ? side : static_cast<const int32_t *>(o.dst);
+    FramePass pass{d};
+    if (int rc = pass.open(d->frames.as<const ManyFrame>(), (uint32_t)d->frame_tab.size(), d->scratch_total, d->n_slots))
+        return rc;
+    pass.launch();
+    if (pass.F && !fmt) {
+        hipLaunchKernelGGL(k_finish_many, dim3(pass.F), dim3(WG), 0, d->st, pass.frames, d->scratch.as<const int32_t>(),
+                           d->codes.as<const uint32_t>(), static_cast<int32_t *>(o.dst), d->counts.as<uint32_t>());
+    } else if (pass.F) {
+        const bool padded = fmt->layout == FLACGPU_LAYOUT_PADDED;
+        with_dtype(fmt->dtype, [&](auto dt) {
+            constexpr uint32_t DT = decltype(dt)::value;
+            auto k = side ? k_finish_as<DT, true, true> : k_finish_as<DT, true, false>;
+            if constexpr (DT != DT_I32)   // I32 / FLAT took the branch above: no k_finish_as<DT_I32, false, *> is made
+                if (!padded) k = side ? k_finish_as<DT, false, true> : k_finish_as<DT, false, false>;
+            hipLaunchKernelGGL(k, dim3(pass.F), dim3(WG), 0, d->st, pass.frames, d->scratch.as<const int32_t>(),
+                               d->codes.as<const uint32_t>(), static_cast<uint8_t *>(o.dst), d->pad_out.as<const uint64_t>(),
+                               fmt->samples_padded, side, d->counts.as<uint32_t>());
+        });
     }
+    HIP_TRY(hipGetLastError());
     std::vector<Md5Job> jobs;
     std::vector<uint32_t> job_stream, digest;
     if (md5) {
@@ -715,11 +778,10 @@ int decode_impl(flacgpu_decoder *d, void *out, uint32_t flags, flacgpu_decoded_s
         digest.resize(5 * (size_t)J);
         HIP_TRY(hipMemcpyAsync(digest.data(), d->digest.p, 20 * (size_t)J, hipMemcpyDeviceToHost, d->st));
     }
-    std::vector<uint32_t> counts(2 * (size_t)S);
-    if (S) HIP_TRY(hipMemcpyAsync(counts.data(), d->counts.p, 8 * (size_t)S, hipMemcpyDeviceToHost, d->st));
-    if (!to_device && out_bytes)
-        HIP_TRY(hipMemcpyAsync(out, dst, out_bytes, hipMemcpyDeviceToHost, d->st));
-    HIP_TRY(hipStreamSynchronize(d->st));
+    std::vector<uint32_t> counts;
+    if (int rc = pass.fetch(counts, fmt ? "flacgpu_decoder_decode_as" : "flacgpu_decoder_decode")) return rc;
+    if (int rc = o.download(d->st)) return rc;
+    HIP_TRY(hipStreamSynchronize(d->st));   // the jobs leave scope behind this
     if (n) memcpy(streams, d->res.data(), sizeof(flacgpu_decoded_stream) * n);
     for (uint32_t i = 0; i < n; i++) {
         flacgpu_decoded_stream &r = streams[i];
@@ -776,21 +838,72 @@ void index_frames(flacgpu_decoder *d) {
         d->slot_frame0[s] = std::min(d->slot_frame0[s], d->slot_frame0[s + 1]);
 }
 
+// ---- selected frames: the path that sample windows and timelines share ----
+// The frames a call chose from the scan's tables, compact, with scratch of their own (by the chosen frames, not by the
+// batch), each with the place in a padded row where K_d7 puts what is kept of it.  Its `window` is the pair that counts
+// it: the frame's `slot` for the frame pass.
+struct Selected {
+    std::vector<ManyFrame> sel;
+    std::vector<WinFrame> desc;
+    uint64_t scratch_total = 0;
+    FramePass pass;
+
+    explicit Selected(flacgpu_decoder *d) : pass{d} {}
+    bool too_many() const { return sel.size() > 0x7FFFFFFFull; }
+    // wf: row, at, keep_first, keep_last and window are the caller's
+    void add(ManyFrame fr, WinFrame wf) {
+        wf.channels = fr.channels;
+        wf.bps = fr.bps;
+        fr.slot = wf.window;
+        fr.scratch = scratch_total;
+        scratch_total += (uint64_t)fr.channels * ((fr.n + 3u) & ~3u);
+        sel.push_back(fr);
+        desc.push_back(wf);
+    }
+    // Before any frame, on the decoder's stream: the counts of `pairs` pairs zeroed and K_d6 over the rows of `pad`, whose
+    // samples and channels stand where k_pad_rows reads a stream's: it zeroes what no frame writes.
+    int open(const std::vector<PadStream> &pad, const flacgpu_out_format &fmt, void *dst, size_t pairs) {
+        flacgpu_decoder *d = pass.d;
+        const size_t F = sel.size();
+        if (int rc = d->pad_streams.ensure(sizeof(PadStream) * pad.size())) return rc;
+        if (F) {
+            if (int rc = d->win_frames.ensure(sizeof(ManyFrame) * F)) return rc;
+            if (int rc = d->win_desc.ensure(sizeof(WinFrame) * F)) return rc;
+        }
+        if (int rc = pass.open(d->win_frames.as<const ManyFrame>(), (uint32_t)F, scratch_total, pairs)) return rc;
+        HIP_TRY(hipMemcpyAsync(d->pad_streams.p, pad.data(), sizeof(PadStream) * pad.size(), hipMemcpyHostToDevice, d->st));
+        launch_pad_rows(d, (uint32_t)pad.size() * fmt.channels_padded, fmt, dst);
+        return FLACGPU_OK;
+    }
+    // The frames: their tables onto the device, the frame pass, K_d7.  `pad`, sel and desc are on their way until the
+    // caller has waited for the stream.
+    int run(const flacgpu_out_format &fmt, void *dst) {
+        flacgpu_decoder *d = pass.d;
+        const uint32_t F = pass.F;
+        if (!F) return FLACGPU_OK;
+        HIP_TRY(hipMemcpyAsync(d->win_frames.p, sel.data(), sizeof(ManyFrame) * F, hipMemcpyHostToDevice, d->st));
+        HIP_TRY(hipMemcpyAsync(d->win_desc.p, desc.data(), sizeof(WinFrame) * F, hipMemcpyHostToDevice, d->st));
+        pass.launch();
+        with_dtype(fmt.dtype, [&](auto dt) {
+            hipLaunchKernelGGL(k_finish_window<decltype(dt)::value>, dim3(F), dim3(WG), 0, d->st, pass.frames,
+                               d->win_desc.as<const WinFrame>(), d->scratch.as<const int32_t>(),
+                               d->codes.as<const uint32_t>(), static_cast<uint8_t *>(dst), fmt.samples_padded,
+                               d->counts.as<uint32_t>());
+        });
+        return FLACGPU_OK;
+    }
+};
+
 // flacgpu_decoder_decode_windows behind its argument checks: out_bytes > 0, every window valid for `fmt`
 int decode_windows_impl(flacgpu_decoder *d, void *out, uint64_t out_bytes, const flacgpu_out_format &fmt, uint32_t flags,
                         const flacgpu_window *w, uint32_t n_windows, flacgpu_window_result *results) {
     DeviceGuard guard(d->device);
     const uint32_t Cp = fmt.channels_padded;
     const uint64_t T = fmt.samples_padded;
-    if ((uint64_t)n_windows * Cp > 0x7FFFFFFFull) {
-        g_last_error = "flacgpu_decoder_decode_windows: more than 2^31 - 1 padded rows";
-        return FLACGPU_ERR_UNSUPPORTED;
-    }
-    // ---- host: the frames every window touches, compact, with scratch of their own
-    std::vector<ManyFrame> sel;
-    std::vector<WinFrame> desc;
+    if (int rc = refuse_rows("flacgpu_decoder_decode_windows", (uint64_t)n_windows * Cp)) return rc;
+    // ---- host: the frames every window touches
+    Selected s(d);
     std::vector<PadStream> pad(n_windows);
-    uint64_t scratch_total = 0;
     try {
         for (uint32_t i = 0; i < n_windows; i++) {
             const flacgpu_decoded_stream &r = d->res[w[i].stream];
@@ -798,9 +911,9 @@ int decode_windows_impl(flacgpu_decoder *d, void *out, uint64_t out_bytes, const
             res = flacgpu_window_result{};
             res.rc = r.rc;
             pad[i] = PadStream{0, 0, 0};
-            const int32_t s = d->slot_of[w[i].stream];
-            if (r.rc != FLACGPU_OK || s < 0) continue;
-            const uint32_t f0 = d->slot_frame0[s], nf = d->slot_frame0[s + 1] - f0;
+            const int32_t slot = d->slot_of[w[i].stream];
+            if (r.rc != FLACGPU_OK || slot < 0) continue;
+            const uint32_t f0 = d->slot_frame0[slot], nf = d->slot_frame0[slot + 1] - f0;
             uint32_t first = 0, count = 0;
             uint64_t skip = 0;
             window_frames([&](uint32_t k) { return d->frame_first[f0 + k]; }, nf, r.info.decoded_samples, w[i].start,
@@ -810,71 +923,33 @@ int decode_windows_impl(flacgpu_decoder *d, void *out, uint64_t out_bytes, const
             res.samples = std::min(w[i].length, r.info.decoded_samples - w[i].start);
             pad[i] = PadStream{res.samples, r.info.channels, 0};
             for (uint32_t k = 0; k < count; k++) {
-                ManyFrame fr = d->frame_tab[f0 + first + k];
+                const ManyFrame &fr = d->frame_tab[f0 + first + k];
                 const uint64_t at = d->frame_first[f0 + first + k];   // the frame's first sample in the stream
                 WinFrame wf{};
                 wf.row = (uint64_t)i * Cp * T;
                 wf.keep_first = k ? 0 : (uint32_t)skip;
                 wf.keep_last = (uint32_t)std::min<uint64_t>(fr.n, w[i].start + res.samples - at);
                 wf.at = at + wf.keep_first - w[i].start;
-                wf.channels = fr.channels;
-                wf.bps = fr.bps;
-                wf.window = i;
-                fr.slot = i;   // k_frame_crc counts per window
-                fr.scratch = scratch_total;
-                scratch_total += (uint64_t)fr.channels * ((fr.n + 3u) & ~3u);
-                sel.push_back(fr);
-                desc.push_back(wf);
+                wf.window = i;   // k_frame_crc counts per window
+                s.add(fr, wf);
             }
         }
     } catch (const std::bad_alloc &) {
         g_last_error = "flacgpu_decoder_decode_windows: out of host memory";
         return FLACGPU_ERR_UNSUPPORTED;
     }
-    if (sel.size() > 0x7FFFFFFFull) {
+    if (s.too_many()) {
         g_last_error = "flacgpu_decoder_decode_windows: more than 2^31 - 1 selected frames";
         return FLACGPU_ERR_UNSUPPORTED;
     }
-    const uint32_t F = (uint32_t)sel.size();
-    const bool to_device = flags & FLACGPU_DECODE_OUT_DEVICE;
-    void *dst = out;
-    if (!to_device) {
-        if (int rc = d->out_stage.ensure(out_bytes)) return rc;
-        dst = d->out_stage.p;
-    }
-    if (int rc = d->pad_streams.ensure(sizeof(PadStream) * n_windows)) return rc;
-    if (int rc = d->counts.ensure(8 * (size_t)n_windows)) return rc;
-    if (F) {   // scratch by the selected frames, not by the batch
-        if (int rc = d->win_frames.ensure(sizeof(ManyFrame) * F)) return rc;
-        if (int rc = d->win_desc.ensure(sizeof(WinFrame) * F)) return rc;
-        if (int rc = d->scratch.ensure(4 * scratch_total)) return rc;
-        if (int rc = d->codes.ensure(4 * (size_t)F)) return rc;
-    }
-    HIP_TRY(hipMemcpyAsync(d->pad_streams.p, pad.data(), sizeof(PadStream) * n_windows, hipMemcpyHostToDevice, d->st));
-    HIP_TRY(hipMemsetAsync(d->counts.p, 0, 8 * (size_t)n_windows, d->st));
-    // a window's samples and channels stand where k_pad_rows reads a stream's: it zeroes what no frame writes
-    launch_pad_rows(fmt.dtype, n_windows * Cp, d->st, d->pad_streams.as<const PadStream>(), Cp, T, dst);
-    if (F) {
-        HIP_TRY(hipMemcpyAsync(d->win_frames.p, sel.data(), sizeof(ManyFrame) * F, hipMemcpyHostToDevice, d->st));
-        HIP_TRY(hipMemcpyAsync(d->win_desc.p, desc.data(), sizeof(WinFrame) * F, hipMemcpyHostToDevice, d->st));
-        const ManyFrame *frames = d->win_frames.as<const ManyFrame>();
-        const uint32_t lanes = 32;   // as decode_impl launches it
-        hipLaunchKernelGGL(k_decode_many<32>, dim3((F + lanes - 1) / lanes), dim3(lanes), 0, d->st,
-                           d->bytes.as<const uint32_t>(), frames, F, d->scratch.as<int32_t>(), d->codes.as<uint32_t>());
-        hipLaunchKernelGGL(k_frame_crc, dim3(F), dim3(64), 0, d->st, d->bytes.as<const uint8_t>(), frames,
-                           d->counts.as<uint32_t>());
-        const auto k = fmt.dtype == FLACGPU_SAMPLE_I16   ? k_finish_window<DT_I16>
-                       : fmt.dtype == FLACGPU_SAMPLE_F32 ? k_finish_window<DT_F32>
-                       : fmt.dtype == FLACGPU_SAMPLE_S24 ? k_finish_window<DT_S24>
-                                                         : k_finish_window<DT_I32>;
-        hipLaunchKernelGGL(k, dim3(F), dim3(WG), 0, d->st, frames, d->win_desc.as<const WinFrame>(),
-                           d->scratch.as<const int32_t>(), d->codes.as<const uint32_t>(), static_cast<uint8_t *>(dst), T,
-                           d->counts.as<uint32_t>());
-    }
+    OutStage o;
+    if (int rc = o.open(d->out_stage, out, out_bytes, flags & FLACGPU_DECODE_OUT_DEVICE)) return rc;
+    if (int rc = s.open(pad, fmt, o.dst, n_windows)) return rc;
+    if (int rc = s.run(fmt, o.dst)) return rc;
     HIP_TRY(hipGetLastError());
-    std::vector<uint32_t> counts(2 * (size_t)n_windows);
-    HIP_TRY(hipMemcpyAsync(counts.data(), d->counts.p, 8 * (size_t)n_windows, hipMemcpyDeviceToHost, d->st));
-    if (!to_device) HIP_TRY(hipMemcpyAsync(out, dst, out_bytes, hipMemcpyDeviceToHost, d->st));
+    std::vector<uint32_t> counts;
+    if (int rc = s.pass.fetch(counts, "flacgpu_decoder_decode_windows")) return rc;
+    if (int rc = o.download(d->st)) return rc;
     HIP_TRY(hipStreamSynchronize(d->st));   // the tables leave scope behind this
     for (uint32_t i = 0; i < n_windows; i++) {
         results[i].bad_frames = counts[2 * (size_t)i];
@@ -911,29 +986,21 @@ int timeline_check(const flacgpu_decoder *d, const flacgpu_out_format *fmt, cons
     for (uint32_t i = 0; i < n; i++) {
         if (results[i].rc != FLACGPU_OK) continue;
         const flacgpu_frame_record &r0 = d->records[d->raw_streams[i].first_frame];
-        if (r0.channels > fmt->channels_padded || results[i].timeline_samples > fmt->samples_padded) {
-            g_last_error = who + ": stream " + std::to_string(i) + " (" + std::to_string(r0.channels) + " channels, " +
-                           std::to_string(results[i].timeline_samples) +
-                           " samples on its timeline) does not fit channels_padded x samples_padded";
-            return FLACGPU_ERR_INVALID_ARG;
-        }
+        if (r0.channels > fmt->channels_padded || results[i].timeline_samples > fmt->samples_padded)
+            return refuse_fit(who, "stream " + std::to_string(i), std::to_string(r0.channels) + " channels, " +
+                                  std::to_string(results[i].timeline_samples) + " samples on its timeline");
     }
-    for (uint32_t i = 0; i < n && sample_type_max_bits(fmt->dtype); i++) {
+    for (uint32_t i = 0; i < n; i++) {
         if (results[i].rc != FLACGPU_OK) continue;
         const flacgpu_frame_record &r0 = d->records[d->raw_streams[i].first_frame];
-        if (r0.bits_per_sample > sample_type_max_bits(fmt->dtype)) {
-            g_last_error = who + ": " + sample_type_name(fmt->dtype) + " output, but stream " + std::to_string(i) + " has " +
-                           std::to_string(r0.bits_per_sample) + " bits per sample";
-            return FLACGPU_ERR_UNSUPPORTED;
-        }
+        if (too_wide(fmt->dtype, r0.bits_per_sample)) return refuse_bits(who, fmt->dtype, i, r0.bits_per_sample);
     }
-    uint64_t bytes = 0, mbytes = 0;
-    if (__builtin_mul_overflow((uint64_t)n * fmt->channels_padded, fmt->samples_padded, &bytes) ||
-        __builtin_mul_overflow(bytes, (uint64_t)sample_type_bytes(fmt->dtype), &bytes) ||
-        __builtin_mul_overflow((uint64_t)n, fmt->samples_padded, &mbytes)) {
-        g_last_error = who + ": the padded batch exceeds 2^64 bytes";
-        return FLACGPU_ERR_UNSUPPORTED;
-    }
+    uint64_t bytes = 0, mbytes = 0;   // the caller's stay as they are when either is refused
+    const char *what = "the padded batch exceeds";
+    if (int rc = padded_bytes(who, what, (uint64_t)n * fmt->channels_padded, fmt->samples_padded,
+                              sample_type_bytes(fmt->dtype), &bytes))
+        return rc;
+    if (int rc = padded_bytes(who, what, n, fmt->samples_padded, 1, &mbytes)) return rc;
     *out_bytes = bytes;
     if (mask_bytes) *mask_bytes = mbytes;
     return FLACGPU_OK;
@@ -947,6 +1014,7 @@ void push_runs(std::vector<FillRun> &runs, uint64_t first, uint64_t count, uint3
         runs.push_back(FillRun{first + done, (uint32_t)std::min(per, count - done), cond, value, 0});
 }
 
+// K_d8 over runs [first, first + count) of tl_runs, whose elements have ES bytes
 template <uint32_t ES>
 void launch_fill(flacgpu_decoder *d, size_t first, size_t count, void *dst) {
     if (!count) return;
@@ -954,15 +1022,13 @@ void launch_fill(flacgpu_decoder *d, size_t first, size_t count, void *dst) {
                        d->counts.as<const uint32_t>(), static_cast<uint8_t *>(dst));
 }
 void launch_fill_samples(flacgpu_decoder *d, uint32_t dtype, size_t first, size_t count, void *dst) {
-    if (dtype == FLACGPU_SAMPLE_I16) launch_fill<2>(d, first, count, dst);
-    else if (dtype == FLACGPU_SAMPLE_S24) launch_fill<3>(d, first, count, dst);
-    else launch_fill<4>(d, first, count, dst);
+    with_dtype(dtype, [&](auto dt) { launch_fill<elem_bytes<decltype(dt)::value>()>(d, first, count, dst); });
 }
 
 // flacgpu_decoder_decode_timeline behind its checks (out_bytes > 0): `results` and `tl` (every record's place) are the
-// rule's; fills concealed / status.  The placed frames of the streams with rc == 0 are decoded through decode_windows'
-// kernels, one "window" per frame, so that the counts come out per frame; k_fill_runs zeroes the gaps beside them and,
-// behind k_finish_window and decided by those counts on the device, the frames that did not decode.
+// rule's; fills concealed / status.  The placed frames of the streams with rc == 0 go the way of decode_windows'
+// selected frames, one "window" per frame, so that the counts come out per frame; k_fill_runs zeroes the gaps beside them
+// and, behind k_finish_window and decided by those counts on the device, the frames that did not decode.
 int decode_timeline_impl(flacgpu_decoder *d, void *out, uint64_t out_bytes, uint8_t *mask, uint64_t mask_bytes,
                          const flacgpu_out_format &fmt, uint32_t flags, flacgpu_timeline_result *results,
                          std::vector<flacgpu_timeline_frame> &tl) {
@@ -970,21 +1036,16 @@ int decode_timeline_impl(flacgpu_decoder *d, void *out, uint64_t out_bytes, uint
     const uint32_t n = (uint32_t)d->raw_streams.size(), Cp = fmt.channels_padded;
     const uint32_t es = (uint32_t)sample_type_bytes(fmt.dtype);
     const uint64_t T = fmt.samples_padded;
-    if ((uint64_t)n * Cp > 0x7FFFFFFFull) {
-        g_last_error = "flacgpu_decoder_decode_timeline: more than 2^31 - 1 padded rows";
-        return FLACGPU_ERR_UNSUPPORTED;
-    }
-    // ---- host: the placed frames, compact, with scratch of their own; the runs in four groups -- sample gaps, the
-    // mask's unconditional runs, the samples' concealment, the mask's concealment
-    std::vector<ManyFrame> sel;
-    std::vector<WinFrame> desc;
+    if (int rc = refuse_rows("flacgpu_decoder_decode_timeline", (uint64_t)n * Cp)) return rc;
+    // ---- host: the placed frames; the runs in four groups -- sample gaps, the mask's unconditional runs, the samples'
+    // concealment, the mask's concealment
+    Selected s(d);
     std::vector<size_t> sel_record;
     std::vector<PadStream> pad(n);
     std::vector<FillRun> gap_runs, mask_runs, hide_runs, mask_hide_runs, runs;
-    uint64_t scratch_total = 0;
     try {
-        sel.reserve(tl.size());
-        desc.reserve(tl.size());
+        s.sel.reserve(tl.size());
+        s.desc.reserve(tl.size());
         sel_record.reserve(tl.size());
         hide_runs.reserve(tl.size());
         for (uint32_t i = 0; i < n; i++) {
@@ -1005,22 +1066,16 @@ int decode_timeline_impl(flacgpu_decoder *d, void *out, uint64_t out_bytes, uint
                     for (uint32_t c = 0; c < C; c++) push_runs(gap_runs, row + c * T + end, at - end, es, FILL_ALWAYS, 0);
                     if (mask) push_runs(mask_runs, (uint64_t)i * T + end, at - end, 1, FILL_ALWAYS, 0);
                 }
-                const uint32_t j = (uint32_t)sel.size();
+                const uint32_t j = (uint32_t)s.sel.size();
                 ManyFrame fr = d->raw_tab[k];
+                fr.out = 0;
                 WinFrame wf{};
                 wf.row = row;
                 wf.at = at;
                 wf.keep_first = 0;
                 wf.keep_last = fr.n;
-                wf.channels = fr.channels;
-                wf.bps = fr.bps;
-                wf.window = j;
-                fr.slot = j;   // k_frame_crc counts per frame
-                fr.out = 0;
-                fr.scratch = scratch_total;
-                scratch_total += (uint64_t)fr.channels * ((fr.n + 3u) & ~3u);
-                sel.push_back(fr);
-                desc.push_back(wf);
+                wf.window = j;   // k_frame_crc counts per frame
+                s.add(fr, wf);
                 sel_record.push_back(k);
                 for (uint32_t c = 0; c < C; c++) push_runs(hide_runs, row + c * T + at, fr.n, es, j, 0);
                 if (mask) {
@@ -1037,82 +1092,40 @@ int decode_timeline_impl(flacgpu_decoder *d, void *out, uint64_t out_bytes, uint
         g_last_error = "flacgpu_decoder_decode_timeline: out of host memory";
         return FLACGPU_ERR_UNSUPPORTED;
     }
-    if (sel.size() > 0x7FFFFFFFull || runs.size() > 0x7FFFFFFFull) {
+    if (s.too_many() || runs.size() > 0x7FFFFFFFull) {
         g_last_error = "flacgpu_decoder_decode_timeline: more than 2^31 - 1 placed frames or fill runs";
         return FLACGPU_ERR_UNSUPPORTED;
     }
-    const uint32_t F = (uint32_t)sel.size();
     const bool to_device = flags & FLACGPU_DECODE_OUT_DEVICE;
-    void *dst = out;
-    uint8_t *mdst = mask;
-    if (!to_device) {
-        if (int rc = d->out_stage.ensure(out_bytes)) return rc;
-        dst = d->out_stage.p;
-        if (mask) {
-            if (int rc = d->tl_mask.ensure(mask_bytes)) return rc;
-            mdst = d->tl_mask.as<uint8_t>();
-        }
-    }
-    if (int rc = d->pad_streams.ensure(sizeof(PadStream) * n)) return rc;
-    if (int rc = d->counts.ensure(8 * (size_t)std::max<uint32_t>(F, 1))) return rc;
+    OutStage o, m;   // the samples; the mask, if the caller wants one
+    if (int rc = o.open(d->out_stage, out, out_bytes, to_device)) return rc;
+    if (int rc = m.open(d->tl_mask, mask, mask ? mask_bytes : 0, to_device)) return rc;
     if (!runs.empty())
         if (int rc = d->tl_runs.ensure(sizeof(FillRun) * runs.size())) return rc;
-    if (F) {   // scratch by the placed frames, not by the batch
-        if (int rc = d->win_frames.ensure(sizeof(ManyFrame) * F)) return rc;
-        if (int rc = d->win_desc.ensure(sizeof(WinFrame) * F)) return rc;
-        if (int rc = d->scratch.ensure(4 * scratch_total)) return rc;
-        if (int rc = d->codes.ensure(4 * (size_t)F)) return rc;
-    }
-    HIP_TRY(hipMemcpyAsync(d->pad_streams.p, pad.data(), sizeof(PadStream) * n, hipMemcpyHostToDevice, d->st));
+    // rows' tails, absent channels and refused streams; the gaps; the mask's 0s and 1s as if every frame decoded
+    if (int rc = s.open(pad, fmt, o.dst, s.sel.size())) return rc;
     if (!runs.empty())
         HIP_TRY(hipMemcpyAsync(d->tl_runs.p, runs.data(), sizeof(FillRun) * runs.size(), hipMemcpyHostToDevice, d->st));
-    HIP_TRY(hipMemsetAsync(d->counts.p, 0, 8 * (size_t)std::max<uint32_t>(F, 1), d->st));
-    // rows' tails, absent channels and refused streams; the gaps; the mask's 0s and 1s as if every frame decoded
-    if (out_bytes) launch_pad_rows(fmt.dtype, n * Cp, d->st, d->pad_streams.as<const PadStream>(), Cp, T, dst);
     size_t at = 0;
-    launch_fill_samples(d, fmt.dtype, at, gap_runs.size(), dst);
+    launch_fill_samples(d, fmt.dtype, at, gap_runs.size(), o.dst);
     at += gap_runs.size();
-    launch_fill<1>(d, at, mask_runs.size(), mdst);
+    launch_fill<1>(d, at, mask_runs.size(), m.dst);
     at += mask_runs.size();
-    if (F) {
-        HIP_TRY(hipMemcpyAsync(d->win_frames.p, sel.data(), sizeof(ManyFrame) * F, hipMemcpyHostToDevice, d->st));
-        HIP_TRY(hipMemcpyAsync(d->win_desc.p, desc.data(), sizeof(WinFrame) * F, hipMemcpyHostToDevice, d->st));
-        const ManyFrame *frames = d->win_frames.as<const ManyFrame>();
-        const uint32_t lanes = 32;   // as decode_impl launches it
-        hipLaunchKernelGGL(k_decode_many<32>, dim3((F + lanes - 1) / lanes), dim3(lanes), 0, d->st,
-                           d->bytes.as<const uint32_t>(), frames, F, d->scratch.as<int32_t>(), d->codes.as<uint32_t>());
-        hipLaunchKernelGGL(k_frame_crc, dim3(F), dim3(64), 0, d->st, d->bytes.as<const uint8_t>(), frames,
-                           d->counts.as<uint32_t>());
-        const auto k = fmt.dtype == FLACGPU_SAMPLE_I16   ? k_finish_window<DT_I16>
-                       : fmt.dtype == FLACGPU_SAMPLE_F32 ? k_finish_window<DT_F32>
-                       : fmt.dtype == FLACGPU_SAMPLE_S24 ? k_finish_window<DT_S24>
-                                                         : k_finish_window<DT_I32>;
-        hipLaunchKernelGGL(k, dim3(F), dim3(WG), 0, d->st, frames, d->win_desc.as<const WinFrame>(),
-                           d->scratch.as<const int32_t>(), d->codes.as<const uint32_t>(), static_cast<uint8_t *>(dst), T,
-                           d->counts.as<uint32_t>());
-        // the concealment: behind the kernels that count, on their stream
-        launch_fill_samples(d, fmt.dtype, at, hide_runs.size(), dst);
+    if (int rc = s.run(fmt, o.dst)) return rc;
+    if (s.pass.F) {   // the concealment: behind the kernels that count, on their stream
+        launch_fill_samples(d, fmt.dtype, at, hide_runs.size(), o.dst);
         at += hide_runs.size();
-        launch_fill<1>(d, at, mask_hide_runs.size(), mdst);
+        launch_fill<1>(d, at, mask_hide_runs.size(), m.dst);
     }
     HIP_TRY(hipGetLastError());
     std::vector<uint32_t> counts;
-    try {   // no exception crosses the C ABI; the kernels are waited for before the return
-        counts.resize(2 * (size_t)F);
-    } catch (const std::bad_alloc &) {
-        (void)hipStreamSynchronize(d->st);
-        g_last_error = "flacgpu_decoder_decode_timeline: out of host memory";
-        return FLACGPU_ERR_UNSUPPORTED;
-    }
-    if (F) HIP_TRY(hipMemcpyAsync(counts.data(), d->counts.p, 8 * (size_t)F, hipMemcpyDeviceToHost, d->st));
-    if (!to_device) {
-        HIP_TRY(hipMemcpyAsync(out, dst, out_bytes, hipMemcpyDeviceToHost, d->st));
-        if (mask && mask_bytes) HIP_TRY(hipMemcpyAsync(mask, mdst, mask_bytes, hipMemcpyDeviceToHost, d->st));
-    }
+    if (int rc = s.pass.fetch(counts, "flacgpu_decoder_decode_timeline")) return rc;
+    if (int rc = o.download(d->st)) return rc;
+    if (int rc = m.download(d->st)) return rc;
     HIP_TRY(hipStreamSynchronize(d->st));   // the tables leave scope behind this
-    for (uint32_t j = 0; j < F; j++) {
+    for (uint32_t j = 0; j < s.pass.F; j++) {
         const size_t k = sel_record[j];
-        const uint32_t status = (counts[2 * (size_t)j] ? 1u : 0u) | (counts[2 * (size_t)j + 1] ? 2u : 0u);
+        const uint32_t status = pair_status(counts, j);
         tl[k].status = status;
         if (!status) continue;
         tl[k].flags |= FLACGPU_TL_CONCEALED;
@@ -1443,11 +1456,8 @@ int flacgpu_decoder_plan_output(const flacgpu_out_format *fmt, const flacgpu_dec
     for (uint32_t i = 0; i < n_streams; i++) {
         const flacgpu_decoded_stream &r = streams[i];
         if (r.rc != FLACGPU_OK) continue;
-        if (sample_type_max_bits(fmt->dtype) && r.info.bits_per_sample > sample_type_max_bits(fmt->dtype)) {
-            g_last_error = std::string("flacgpu_decoder_plan_output: ") + sample_type_name(fmt->dtype) + " output, but stream " +
-                           std::to_string(i) + " has " + std::to_string(r.info.bits_per_sample) + " bits per sample";
-            return FLACGPU_ERR_UNSUPPORTED;
-        }
+        if (too_wide(fmt->dtype, r.info.bits_per_sample))
+            return refuse_bits("flacgpu_decoder_plan_output", fmt->dtype, i, r.info.bits_per_sample);
         total += r.info.decoded_samples * r.info.channels;
         any = any || (r.info.decoded_samples && r.info.channels);
     }
@@ -1459,21 +1469,13 @@ int flacgpu_decoder_plan_output(const flacgpu_out_format *fmt, const flacgpu_dec
     for (uint32_t i = 0; i < n_streams && any; i++) {
         const flacgpu_decoded_stream &r = streams[i];
         if (r.rc != FLACGPU_OK) continue;
-        if (r.info.channels > fmt->channels_padded || r.info.decoded_samples > fmt->samples_padded) {
-            g_last_error = "flacgpu_decoder_plan_output: stream " + std::to_string(i) + " (" +
-                           std::to_string(r.info.channels) + " channels, " + std::to_string(r.info.decoded_samples) +
-                           " samples) does not fit channels_padded x samples_padded";
-            return FLACGPU_ERR_INVALID_ARG;
-        }
+        if (r.info.channels > fmt->channels_padded || r.info.decoded_samples > fmt->samples_padded)
+            return refuse_fit("flacgpu_decoder_plan_output", "stream " + std::to_string(i),
+                              std::to_string(r.info.channels) + " channels, " + std::to_string(r.info.decoded_samples) +
+                                  " samples");
     }
-    uint64_t bytes = 0;
-    if (__builtin_mul_overflow((uint64_t)n_streams * fmt->channels_padded, fmt->samples_padded, &bytes) ||
-        __builtin_mul_overflow(bytes, es, &bytes)) {
-        g_last_error = "flacgpu_decoder_plan_output: the padded batch exceeds 2^64 bytes";
-        return FLACGPU_ERR_UNSUPPORTED;
-    }
-    *out_bytes = bytes;
-    return FLACGPU_OK;
+    return padded_bytes("flacgpu_decoder_plan_output", "the padded batch exceeds", (uint64_t)n_streams * fmt->channels_padded,
+                        fmt->samples_padded, es, out_bytes);
 }
 
 int flacgpu_decoder_decode_as(flacgpu_decoder *d, void *out, size_t out_cap_bytes, const flacgpu_out_format *fmt,
@@ -1530,30 +1532,17 @@ int flacgpu_decoder_plan_windows(const flacgpu_out_format *fmt, const flacgpu_de
             return FLACGPU_ERR_INVALID_ARG;
         }
         const flacgpu_decoded_stream &r = streams[w[i].stream];
-        if (w[i].length > fmt->samples_padded || (r.rc == FLACGPU_OK && r.info.channels > fmt->channels_padded)) {
-            g_last_error = "flacgpu_decoder_plan_windows: window " + std::to_string(i) + " (" +
-                           std::to_string(w[i].length) + " samples of stream " + std::to_string(w[i].stream) +
-                           ") does not fit channels_padded x samples_padded";
-            return FLACGPU_ERR_INVALID_ARG;
-        }
+        if (w[i].length > fmt->samples_padded || (r.rc == FLACGPU_OK && r.info.channels > fmt->channels_padded))
+            return refuse_fit("flacgpu_decoder_plan_windows", "window " + std::to_string(i),
+                              std::to_string(w[i].length) + " samples of stream " + std::to_string(w[i].stream));
     }
-    for (uint32_t i = 0; i < n_windows && sample_type_max_bits(fmt->dtype); i++) {
+    for (uint32_t i = 0; i < n_windows; i++) {
         const flacgpu_decoded_stream &r = streams[w[i].stream];
-        if (r.rc == FLACGPU_OK && r.info.bits_per_sample > sample_type_max_bits(fmt->dtype)) {
-            g_last_error = std::string("flacgpu_decoder_plan_windows: ") + sample_type_name(fmt->dtype) + " output, but stream " +
-                           std::to_string(w[i].stream) + " has " + std::to_string(r.info.bits_per_sample) +
-                           " bits per sample";
-            return FLACGPU_ERR_UNSUPPORTED;
-        }
+        if (r.rc == FLACGPU_OK && too_wide(fmt->dtype, r.info.bits_per_sample))
+            return refuse_bits("flacgpu_decoder_plan_windows", fmt->dtype, w[i].stream, r.info.bits_per_sample);
     }
-    uint64_t bytes = 0;
-    if (__builtin_mul_overflow((uint64_t)n_windows * fmt->channels_padded, fmt->samples_padded, &bytes) ||
-        __builtin_mul_overflow(bytes, (uint64_t)sample_type_bytes(fmt->dtype), &bytes)) {
-        g_last_error = "flacgpu_decoder_plan_windows: the windows exceed 2^64 bytes";
-        return FLACGPU_ERR_UNSUPPORTED;
-    }
-    *out_bytes = bytes;
-    return FLACGPU_OK;
+    return padded_bytes("flacgpu_decoder_plan_windows", "the windows exceed", (uint64_t)n_windows * fmt->channels_padded,
+                        fmt->samples_padded, sample_type_bytes(fmt->dtype), out_bytes);
 }
 
 int flacgpu_decoder_decode_windows(flacgpu_decoder *d, void *out, size_t out_cap_bytes, const flacgpu_out_format *fmt,

@@ -271,33 +271,39 @@ struct PadStream {
     uint32_t channels;   // 0 for a stream with rc != 0
     uint32_t reserved;
 };
+// `bytes` bytes from p, every one the low byte of w (w: that byte four times), by one workgroup: single elements of ES
+// bytes up to the first 16-byte boundary (ES == 1 and ES == 3: single bytes, such a run begins and ends at any byte), 16
+// bytes per lane, consecutive lanes consecutive groups, single elements behind the last whole group.  Exactly these
+// bytes are written.  For ES == 2 and 4 p is ES-aligned, so that head and tail are whole elements.  Len: uint64_t for a
+// row of a padded batch, uint32_t for a run of at most kFillPiece bytes.
+template <uint32_t ES, class Len> __device__ __forceinline__ void fill_bytes(uint8_t *p, Len bytes, uint32_t w) {
+    const Len head = min(bytes, (Len)((16u - (uint32_t)(reinterpret_cast<uintptr_t>(p) & 15u)) & 15u));
+    const Len nv = (bytes - head) / 16, tail_at = head + nv * 16;
+    constexpr bool BYTES = ES == 1 || ES == 3;
+    if (BYTES) {
+        if (threadIdx.x < head) p[threadIdx.x] = (uint8_t)w;
+    } else if (threadIdx.x * ES < head) {
+        if (ES == 2) reinterpret_cast<uint16_t *>(p)[threadIdx.x] = (uint16_t)w;
+        else reinterpret_cast<uint32_t *>(p)[threadIdx.x] = w;
+    }
+    uint4 *body = reinterpret_cast<uint4 *>(p + head);
+    for (Len v = threadIdx.x; v < nv; v += WG) body[v] = make_uint4(w, w, w, w);
+    if (BYTES) {
+        if (threadIdx.x < bytes - tail_at) p[tail_at + threadIdx.x] = (uint8_t)w;
+    } else if (threadIdx.x * ES < bytes - tail_at) {
+        if (ES == 2) reinterpret_cast<uint16_t *>(p + tail_at)[threadIdx.x] = (uint16_t)w;
+        else reinterpret_cast<uint32_t *>(p + tail_at)[threadIdx.x] = w;
+    }
+}
 // Workgroup per (stream, channel row): zeroes [decoded_samples, samples_padded) of a channel the stream has and the
-// whole row of one it has not.  Elements up to the first 16-byte boundary, 16 bytes per lane, elements (ES == 3, the
-// packed 24-bit elements: single bytes on both sides, a row begins and ends at any byte).
+// whole row of one it has not (fill_bytes: a row of packed 24-bit elements begins and ends at any byte).
 template <uint32_t ES>
 __global__ void __launch_bounds__(WG) k_pad_rows(const PadStream *__restrict__ streams, uint32_t channels_padded,
                                                  uint64_t samples_padded, uint8_t *__restrict__ out) {
     const uint32_t s = blockIdx.x / channels_padded, c = blockIdx.x % channels_padded;
     const PadStream ps = streams[s];
     const uint64_t from = c < ps.channels ? ps.samples : 0;
-    uint8_t *p = out + ((uint64_t)blockIdx.x * samples_padded + from) * ES;
-    const uint64_t bytes = (samples_padded - from) * ES;
-    const uint64_t head = min(bytes, (uint64_t)((16u - (uint32_t)(reinterpret_cast<uintptr_t>(p) & 15u)) & 15u));
-    const uint64_t nv = (bytes - head) / 16, tail_at = head + nv * 16;
-    if (ES == 3) {
-        if (threadIdx.x < head) p[threadIdx.x] = 0;
-    } else if (threadIdx.x * ES < head) {
-        if (ES == 2) reinterpret_cast<uint16_t *>(p)[threadIdx.x] = 0;
-        else reinterpret_cast<uint32_t *>(p)[threadIdx.x] = 0;
-    }
-    uint4 *body = reinterpret_cast<uint4 *>(p + head);
-    for (uint64_t v = threadIdx.x; v < nv; v += WG) body[v] = make_uint4(0, 0, 0, 0);
-    if (ES == 3) {
-        if (threadIdx.x < bytes - tail_at) p[tail_at + threadIdx.x] = 0;
-    } else if (threadIdx.x * ES < bytes - tail_at) {
-        if (ES == 2) reinterpret_cast<uint16_t *>(p + tail_at)[threadIdx.x] = 0;
-        else reinterpret_cast<uint32_t *>(p + tail_at)[threadIdx.x] = 0;
-    }
+    fill_bytes<ES, uint64_t>(out + ((uint64_t)blockIdx.x * samples_padded + from) * ES, (samples_padded - from) * ES, 0u);
 }
 
 // ---- MD5 (RFC 1321) ----
@@ -450,34 +456,13 @@ struct FillRun {
     uint32_t value;   // the byte
     uint32_t reserved;
 };
-// K_d8 k_fill_runs  workgroup per run, k_pad_rows' shape: single elements up to the first 16-byte boundary (ES == 1 and
-// ES == 3: single bytes, such a run begins and ends at any byte), 16 bytes per lane, consecutive lanes consecutive
-// groups, single elements behind the last whole group.  Exactly the run's bytes are written: its neighbours belong to
-// other workgroups and to k_finish_window and k_pad_rows.  `out` is ES-aligned for ES == 2 and 4, hence so is every run,
-// and head and tail are whole elements.
+// K_d8 k_fill_runs  workgroup per run, k_pad_rows' shape (fill_bytes).  Exactly the run's bytes are written: its
+// neighbours belong to other workgroups and to k_finish_window and k_pad_rows.  `out` is ES-aligned for ES == 2 and 4,
+// hence so is every run.
 template <uint32_t ES>
 __global__ void __launch_bounds__(WG) k_fill_runs(const FillRun *__restrict__ runs, const uint32_t *__restrict__ counts,
                                                   uint8_t *__restrict__ out) {
     const FillRun r = runs[blockIdx.x];
     if (r.cond != FILL_ALWAYS && (counts[2 * (size_t)r.cond] | counts[2 * (size_t)r.cond + 1]) == 0) return;
-    uint8_t *p = out + r.first * ES;
-    const uint32_t bytes = r.count * ES;
-    const uint32_t w = (r.value & 0xFFu) * 0x01010101u;
-    const uint32_t head = min(bytes, (16u - (uint32_t)(reinterpret_cast<uintptr_t>(p) & 15u)) & 15u);
-    const uint32_t nv = (bytes - head) / 16u, tail_at = head + nv * 16u;
-    constexpr bool BYTES = ES == 1 || ES == 3;
-    if (BYTES) {
-        if (threadIdx.x < head) p[threadIdx.x] = (uint8_t)w;
-    } else if (threadIdx.x * ES < head) {
-        if (ES == 2) reinterpret_cast<uint16_t *>(p)[threadIdx.x] = (uint16_t)w;
-        else reinterpret_cast<uint32_t *>(p)[threadIdx.x] = w;
-    }
-    uint4 *body = reinterpret_cast<uint4 *>(p + head);
-    for (uint32_t v = threadIdx.x; v < nv; v += WG) body[v] = make_uint4(w, w, w, w);
-    if (BYTES) {
-        if (threadIdx.x < bytes - tail_at) p[tail_at + threadIdx.x] = (uint8_t)w;
-    } else if (threadIdx.x * ES < bytes - tail_at) {
-        if (ES == 2) reinterpret_cast<uint16_t *>(p + tail_at)[threadIdx.x] = (uint16_t)w;
-        else reinterpret_cast<uint32_t *>(p + tail_at)[threadIdx.x] = w;
-    }
+    fill_bytes<ES, uint32_t>(out + r.first * ES, r.count * ES, (r.value & 0xFFu) * 0x01010101u);
 }

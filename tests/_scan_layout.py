@@ -2,8 +2,8 @@
 fall in its 64-byte blocks, its workgroups of WG blocks, k_scan_carry's runs of workgroups and the order of x modulo the
 CRC-16 polynomial -- for test_scan_layout_host.py (CPU) and test_gpu_scan_layout.py (GPU) (TEST INFRASTRUCTURE ONLY).
 
-The layout rule (decode_many.hip, scan_impl / scan_raw_impl): a stream with a frame region owns a SLOT; slot s begins at
-the previous slot's base + ((len + kSlotTail + 63) & ~63); block0 = base / 64; a block's workgroup is block // WG;
+The layout rule (decode_many.hip, SlotLayout::add for scan_impl and scan_raw_impl): a stream with a frame region owns a
+SLOT; slot s begins at the previous slot's base + ((len + kSlotTail + 63) & ~63); block0 = base / 64; a block's workgroup is block // WG;
 n_wg = ceil(blocks / WG); k_scan_carry's lane t walks per = ceil(n_wg / WG) workgroups.  The region of a regular stream
 is the bytes behind its metadata, that of a raw stream the whole input; a stream without a region owns no slot.  WG and
 kSlotTail are read from the sources: a change to either re-aims the cases or breaks them (test_scan_layout_host.py

@@ -24,6 +24,8 @@ over flacgpu_decode_stream and the oracle's CPU decoder on one core; writes prof
     python tools/decode_many_probe.py --timeline --label parent --package-root DIR   (the decode_as leg only)
     python tools/decode_many_probe.py --timeline --label this_2
     python tools/decode_many_probe.py --timeline --kernels-only
+    python tools/decode_many_probe.py --raw|--timeline --label parent --package-root DIR --parent-all-legs   (a parent that
+                                             has every leg of the mode: each is then held to the parent's own spread of it)
 
 --timeline (flacgpu_decoder_decode_timeline): on the clips with the metadata stripped, float32, device output, handle
 warm, the wall time of scan_frames + decode_as (padded; the parent's call for such a batch) and of scan_frames +
@@ -210,6 +212,11 @@ def _sclk_mhz():
         return None
     m = re.search(r"sclk clock level.*?\((\d+)Mhz\)", out)
     return int(m.group(1)) if m else None
+
+
+def parent_only(args):
+    """True when this run times only the legs that the parent of the pull request a mode was written for had."""
+    return args.label == "parent" and not args.parent_all_legs
 
 
 def _spread(times):
@@ -401,8 +408,8 @@ def raw_frames(args):
     from flac_codec_amd.gpu import Decoder, decode_many, scan_stream_host
 
     blobs = make_blobs("clips")
-    has_raw = hasattr(Decoder, "scan_frames") and (args.speculative or args.label != "parent")
-    has_spec = args.speculative and args.label != "parent"
+    has_raw = hasattr(Decoder, "scan_frames") and (args.speculative or not parent_only(args))
+    has_spec = args.speculative and not parent_only(args)
     dec = Decoder(0)
     legs = {"regular_scan_decode": lambda: decode_many(blobs, out="device", verify_md5=False, decoder=dec)[0]}
     if has_raw:
@@ -497,11 +504,12 @@ def raw_frames(args):
                           "parent_median_s": allow["median_s"]}
         for label in ("this_1", "this_2"):
             for name, leg in runs[label]["legs"].items():
-                if name.endswith("_speculative"):   # no leg of the parent's to hold it to
+                if name.endswith("_speculative") and name not in runs["parent"]["legs"]:   # no leg of the parent's
                     continue
                 # a leg the parent ran is held to the parent's spread of that leg; else (r13) to the regular leg's
                 ref = runs["parent"]["legs"].get(name, allow)
                 res["verdict"][f"{label}.{name}"] = {"median_s": leg["median_s"], "inside_parent_spread": inside(leg, ref),
+                                                     "parent_min_s": ref["min_s"], "parent_max_s": ref["max_s"],
                                                      "over_parent_median": leg["median_s"] / ref["median_s"]}
     with open(args.out, "w") as f:
         json.dump(res, f, indent=1)
@@ -520,7 +528,7 @@ def timeline(args):
 
     blobs = make_blobs("clips")
     bare = [b[int(scan_stream_host(b)[1][0]):] for b in blobs]   # from the first frame on
-    has_tl = hasattr(gpu, "decode_timeline") and args.label != "parent"
+    has_tl = hasattr(gpu, "decode_timeline") and not parent_only(args)
     dec = Decoder(0)
     legs = {"raw_scan_frames_decode_as": lambda: decode_many(bare, out="device", verify_md5=False, decoder=dec, raw=True,
                                                              dtype="float32", layout="padded")[0]}
@@ -599,11 +607,16 @@ def timeline(args):
         res["verdict"] = {"allowance_parent_min_s": allow["min_s"], "allowance_parent_max_s": allow["max_s"],
                           "parent_median_s": allow["median_s"]}
         for label in ("this_1", "this_2"):
-            for name in ("raw_scan_frames_decode_as", "timeline_undamaged"):   # the damaged leg has no parent
-                leg = runs[label]["legs"][name]
+            for name, leg in runs[label]["legs"].items():
+                # a leg the parent ran is held to the parent's spread of that leg; else (r16) the undamaged timeline to
+                # the decode_as leg's, and the damaged one, which has no parent, to nothing
+                ref = runs["parent"]["legs"].get(name, allow if name == "timeline_undamaged" else None)
+                if ref is None:
+                    continue
                 res["verdict"][f"{label}.{name}"] = {
-                    "median_s": leg["median_s"], "inside_parent_spread": allow["min_s"] <= leg["median_s"] <= allow["max_s"],
-                    "over_parent_median": leg["median_s"] / allow["median_s"]}
+                    "median_s": leg["median_s"], "inside_parent_spread": ref["min_s"] <= leg["median_s"] <= ref["max_s"],
+                    "parent_min_s": ref["min_s"], "parent_max_s": ref["max_s"],
+                    "over_parent_median": leg["median_s"] / ref["median_s"]}
     with open(args.out, "w") as f:
         json.dump(res, f, indent=1)
     print(json.dumps({args.label: rec, "verdict": res.get("verdict")}, indent=1), flush=True)
@@ -854,6 +867,9 @@ def main():
     ap.add_argument("--shrink", type=int, default=1, help="--s24: divide the clip count")
     ap.add_argument("--label", default="this", help="--formats: the run's name in the file (parent: the default int32 "
                     "leg only; any other name: every leg)")
+    ap.add_argument("--parent-all-legs", action="store_true",
+                    help="--raw, --timeline: with --label parent, time every leg of the mode (a parent that has them all); "
+                    "the verdict then holds each leg to the parent's spread of the same leg")
     ap.add_argument("--package-root", help="--formats: measure the flac_codec_amd of this checkout, not of this one")
     ap.add_argument("--oracle-seconds", type=float, default=20.0)
     ap.add_argument("--merge-stats")
