@@ -29,6 +29,7 @@
 //         generic: k_zero + k_pack + k_crc
 //   N3    k_decode (decode.inc)  decode.rs:1388-1856 read_frame .. predict, one lane per subframe
 #include "kernels/types.h"
+#include "batch_route.h"
 #include "lpc_host.h"
 
 #include <ctype.h>
@@ -42,6 +43,7 @@
 #include <atomic>
 #include <cmath>
 #include <chrono>
+#include <functional>
 #include <mutex>
 #include <thread>
 #include <string>
@@ -104,6 +106,9 @@ namespace {
 #include "kernels/decide_emit.inc"
 }  // namespace
 using namespace flacgpu_k;
+using flacenc_route::Route;
+using flacenc_route::RouteBatch;
+using flacenc_route::RouteContext;
 
 struct flacgpu_ctx;
 static uint32_t *defer_stats_of(const flacgpu_ctx *c);
@@ -146,7 +151,7 @@ struct flacgpu_ctx {
     uint32_t ties_resolved = 0;     // candidates re-decided on the host for the last analysis
     uint32_t fir_rechecked = 0;     // candidate waves of the last analysis that asked for the checked FIR re-run
                                     // (Params::check_fir) and got it
-    uint32_t last_n_fast = 0;       // frames of the last analysis that took the wave kernels
+    Route route;                    // which kernels the batch in hand runs (host/batch_route.h), decided when it arrived
     uint64_t last_first_frame = 0;  // arguments of the last frame assembly (re-run after a re-decision)
     uint32_t last_rate = 0;
     uint32_t *h_stats = nullptr;    // pinned copy of the 4 counters (asynchronous host path)
@@ -173,7 +178,7 @@ struct flacgpu_ctx {
     uint64_t packed_cap = 0;        // bytes
     bool packed_valid = false;
     bool resid_valid = false;       // d_resid holds the rows of the last analysed batch
-    // a batch cut into frame ranges by flacgpu_encode_device (chunk_frames): analyze_impl / pack_impl launch their kernels for
+    // a batch cut into frame ranges by flacgpu_encode_device (Route::range_frames): analyze_impl / pack_impl launch their kernels for
     // frames [rng_f0, rng_f0 + rng_cnt) only; rng_cnt == 0: the whole batch
     uint32_t rng_f0 = 0, rng_cnt = 0;
     uint32_t flat_lo = 0, flat_hi = 0;    // samples [flat_lo, flat_hi) of a full block lie under window values of exactly 1.0
@@ -386,16 +391,6 @@ const char *const kKernelNames[FLACGPU_N_KERNELS] = {
     "k_fir",          "k_decide",       "k_emit",  "k_layout",   "k_pack",
     "k_crc",          "k_cand64"};
 
-bool wave_block_size(uint32_t B) {
-    switch (B) {
-#define X(n, spl) case n:
-        FLACGPU_WAVE_SIZES(X)
-#undef X
-        return true;
-    default: return false;
-    }
-}
-
 }  // namespace
 
 extern "C" {
@@ -470,8 +465,15 @@ int flacgpu_create(const flacgpu_options *o, uint32_t bps, uint32_t channels, in
 static int create_impl(flacgpu_ctx *c, const flacgpu_options *o) {
     const uint32_t max_frames = c->max_frames, channels = c->channels, bps = c->bps;
     c->ldb = (o->block_size + 3u) & ~3u;
-    c->stereo4 = (channels == 2 && bps < 32) ? 1u : 0u;  // side needs bps+1 <= 32 (encode.rs:2715)
-    c->ncand = c->stereo4 ? 4u : channels;
+    c->knobs = read_knobs();
+    c->env_no_direct = c->knobs.no_direct;
+    if (c->knobs.has_tie_band) c->tie_band = c->knobs.tie_band;            // test knobs
+    if (c->knobs.has_tie_perturb) c->tie_perturb = c->knobs.tie_perturb;
+    // (the candidate slots, and which of the optional buffers the routes of this shape can use)
+    const RouteContext shape = flacenc_route::route_context(channels, bps, o->block_size, o->max_lpc_order, o->max_partition_order,
+                                                            o->exhaustive_channel_correlation != 0, c->knobs);
+    c->stereo4 = shape.stereo4;
+    c->ncand = shape.ncand;
     const size_t F = max_frames, B = o->block_size, C = channels, NC = c->ncand;
     const size_t slack = 64;
 #define ALLOC(ptr, count) HIP_TRY(hipMalloc((void **)&(ptr), sizeof(*(ptr)) * (count)))
@@ -488,7 +490,7 @@ static int create_impl(flacgpu_ctx *c, const flacgpu_options *o) {
     ALLOC(c->d_out, F * C);
     ALLOC(c->d_lpc, F * NC);
     ALLOC(c->d_finfo, F);
-    if (c->stereo4 && B == FN && o->max_lpc_order > 0 && !read_knobs().no_hand) {   // (c->knobs is filled further down)
+    if (shape.has_hand) {
         ALLOC(c->d_hand, F * 2);
         HIP_TRY(hipMemset(c->d_hand, 0, sizeof(uint32_t) * F * 2));
     }
@@ -505,14 +507,10 @@ static int create_impl(flacgpu_ctx *c, const flacgpu_options *o) {
     ALLOC(c->d_frame_off, F + 1);
     ALLOC(c->d_tile_sync, F / 1024 + 2);
     HIP_TRY(hipMemset(c->d_tile_sync, 0, sizeof(unsigned long long) * (F / 1024 + 2)));
-    if (channels >= 5) ALLOC(c->d_edges, F * channels);
+    if (shape.has_edges) ALLOC(c->d_edges, F * channels);
     if (B > LDS_BLOCK_LIMIT) ALLOC(c->d_big, F * NC * (size_t)big_scratch_ints((uint32_t)B));
     ALLOC(c->d_ties, F * NC);
     if (c->stereo4 && !o->exhaustive_channel_correlation) ALLOC(c->d_abs, F * 4);
-    c->knobs = read_knobs();
-    c->env_no_direct = c->knobs.no_direct;
-    if (c->knobs.has_tie_band) c->tie_band = c->knobs.tie_band;            // test knobs
-    if (c->knobs.has_tie_perturb) c->tie_perturb = c->knobs.tie_perturb;
 #undef ALLOC
     // non-blocking: contexts must not synchronise with each other through the legacy null stream
     HIP_TRY(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
@@ -657,30 +655,30 @@ static int resolve_stream(flacgpu_ctx *c, void *stream, hipStream_t *out) {
     return FLACGPU_OK;
 }
 
+// The route of a batch (host/batch_route.h): the context's shape, knobs and tunings as they stand now, and the call.
 // packed_bytes != 0: the PCM sits in c->d_in as interleaved little-endian samples of that many bytes
-// Whether a batch of interleaved i32 PCM can be analysed and assembled in place (Params::inter): stereo with
-// the four L/R/M/S candidates of <= 24-bit samples, whole blocks of one of the wave block lengths (4096; 1024 / 1152 /
-// 2048 / 2304 with LPC order <= 16 -- the persistent candidate kernel stages the interleaved frame once per frame in
-// LDS; the non-persistent one read it once per candidate wave and lost to the split pass, 0.114 -> 0.172 ms at 1152
-// samples), and every stage on its wave kernel -- none of the knobs that select an older or generic kernel (they read
-// Params::planar).
-static bool direct_input_ok(const flacgpu_ctx *c, const Params &p, uint32_t last_len) {
-    const Knobs &kn = c->knobs;
-    const bool off = kn.no_direct || kn.no_w64 || kn.experiment_mfma_ac || kn.no_fused_pack || kn.no_frame64;
-    const uint32_t B = p.block_size;
-    const bool block_ok = B == FN || (wave_block_size(B) && p.max_lpc_order <= 16 && !kn.no_direct_short);
-    return !off && c->stereo4 && c->channels == 2 && c->bps <= 24 && block_ok && last_len == B &&
-           p.max_po <= 6 && p.ac_split != 2 &&
-           (size_t)frame_fb_words(p.channels, c->bps, B) * sizeof(int32_t) <= 150 * 1024;
+static RouteContext route_context_of(const flacgpu_ctx *c) {
+    RouteContext rc = flacenc_route::route_context(c->channels, c->bps, c->opts.block_size, c->opts.max_lpc_order,
+                                                   c->opts.max_partition_order, c->opts.exhaustive_channel_correlation != 0, c->knobs);
+    rc.lag_split = c->lag_split;
+    rc.two_ranges = c->two_ranges;
+    rc.chunk_samples = c->chunk_samples;
+    rc.chunk_auto = c->chunk_auto;
+    rc.timing = c->timing;
+    return rc;
 }
-
-// interleaved INDEPENDENT channels whose batch k_autocorr4's producers read themselves (Params::split_src; analyze_impl adds
-// the conditions on the call: layout, alignment, no stream-width upload)
-static bool split_input_ok(const flacgpu_ctx *c, const Params &p, uint32_t last_len) {
-    const uint32_t B = p.block_size;
-    return !c->stereo4 && c->channels >= 1 && c->ncand == c->channels && p.max_lpc_order >= 1 && p.max_lpc_order <= 16 && B == FN &&
-           last_len == B && p.ac_split != 2 && (c->bps <= 25u) && p.max_po <= 6 &&
-           !(c->knobs.no_direct || c->knobs.no_w64 || c->knobs.experiment_mfma_ac);
+static bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
+static Route route_of(const flacgpu_ctx *c, bool pcm_aligned16, int layout, uint32_t n_frames, uint32_t last_len,
+                      uint32_t packed_bytes = 0, bool segments_in_place_wanted = false, bool whole_call = false) {
+    RouteBatch b;
+    b.n_frames = n_frames;
+    b.last_len = last_len;
+    b.layout = layout;
+    b.aligned16 = pcm_aligned16;
+    b.packed_bytes = packed_bytes;
+    b.segments_in_place_wanted = segments_in_place_wanted;
+    b.whole_call = whole_call;
+    return flacenc_route::plan_route(route_context_of(c), b);
 }
 
 // k_layout's tiles find each other through PackParams::tile_sync, whose words carry the launch's 24-bit epoch: a new
@@ -722,14 +720,40 @@ static int ensure_planar(flacgpu_ctx *c) {
     return FLACGPU_OK;
 }
 
+// given: the batch's route where the caller has asked plan_route already (flacgpu_encode_device, the segment entries)
 static int analyze_impl(flacgpu_ctx *c, const int32_t *d_pcm, int layout, uint32_t n_frames,
-                        uint32_t last_len, hipStream_t st, uint32_t packed_bytes);
+                        uint32_t last_len, hipStream_t st, uint32_t packed_bytes, const Route *given = nullptr);
 
 // A batch that is NOT made of segments begins: the per-frame tables of an earlier flacgpu_encode_segments* batch on this
 // context (frame numbers, addresses, the segments ensure_planar would walk) must not reach its frame assembly or verifier.
 static void begin_plain_batch(flacgpu_ctx *c) {
     c->seg_active = c->seg_pending = c->seg_direct = false;
     c->segs.clear();
+}
+
+static void launch_candidates_and_decide(flacgpu_ctx *c, const Params &p, const Params &pf, const Params &pg, bool ranged,
+                                         hipStream_t st, const std::function<void(int)> &begin);
+
+// A batch has been submitted on `st`: what every later entry point reads about it.  only_copy: the caller's buffer where the
+// kernels read it in place and wrote no planar rows (ensure_planar fills them on demand); analysed: LPC order ties may be
+// waiting for the host's re-decision (resolve_order_ties); packed: the frames were assembled in the same go.
+static void batch_submitted(flacgpu_ctx *c, const Params &p, const Route &r, hipStream_t st, const int32_t *only_copy,
+                            bool analysed, bool packed) {
+    c->last_frames = p.n_frames;
+    c->last_len = p.last_len;
+    c->last_params = p;
+    c->last_stream = st;
+    c->route = r;
+    c->resid_valid = false;
+    c->planar_valid = only_copy == nullptr;
+    c->direct_src = only_copy;
+    c->packed_valid = packed;
+    if (analysed) {
+        c->ties_checked = p.max_lpc_order == 0;
+        c->ties_resolved = 0;
+        c->fir_rechecked = 0;
+    }
+    c->drained = false;
 }
 
 int flacgpu_analyze_device(flacgpu_ctx *c, const int32_t *d_pcm, int layout, uint32_t n_frames,
@@ -745,7 +769,7 @@ int flacgpu_analyze_device(flacgpu_ctx *c, const int32_t *d_pcm, int layout, uin
 }
 
 static int analyze_impl(flacgpu_ctx *c, const int32_t *d_pcm, int layout, uint32_t n_frames,
-                        uint32_t last_len, hipStream_t st, uint32_t packed_bytes) {
+                        uint32_t last_len, hipStream_t st, uint32_t packed_bytes, const Route *given) {
     if (!c || !d_pcm || n_frames == 0 || n_frames > c->max_frames || last_len == 0 ||
         last_len > c->opts.block_size || (layout != 0 && layout != 1)) {
         g_last_error = "invalid analyze arguments";
@@ -795,76 +819,37 @@ static int analyze_impl(flacgpu_ctx *c, const int32_t *d_pcm, int layout, uint32
         mark(k);
     };
 
+    const Route r = given ? *given : route_of(c, aligned16(d_pcm), layout, n_frames, last_len, packed_bytes);
     const uint32_t ncb = n_frames * c->ncand;
-    const bool ranged = c->rng_cnt != 0;                 // (flacgpu_encode_device checked that this batch can be cut)
+    const bool ranged = c->rng_cnt != 0;                 // (flacgpu_encode_device: a route with range_frames != 0)
     const uint32_t rf0 = ranged ? c->rng_f0 : 0u, rcnt = ranged ? c->rng_cnt : n_frames;
     const bool first_range = rf0 == 0;
     if (first_range) HIP_TRY(hipMemsetAsync(c->d_stats_base, 0, sizeof(uint32_t) * (kTurnWords + 4 + (size_t)ncb), st));  // + d_orbits
-    // DIRECT input: interleaved i32 stereo PCM of whole 4096-sample blocks is read in place by the
-    // autocorrelation, candidate and frame kernels (no K0 split; the ORs come out of k_autocorr4, so
-    // k_candinfo runs after it) -- see kernels/autocorr.inc.  The caller's buffer is then the only copy of
-    // the input: it must stay valid until the batch's results were fetched (include/flacenc_gpu.h).
-    // the in-place kernels fetch 16-byte pieces (vector loads, LDS-DMA): a batch that does not start on a 16-byte boundary
-    // (a view into a larger device buffer) takes the copying K0 path, whose loads are dwords
-    const bool aligned16 = ((uintptr_t)d_pcm & 15u) == 0;
-    const bool direct = !packed_bytes && aligned16 && layout == FLACGPU_LAYOUT_INTERLEAVED && direct_input_ok(c, p, last_len);
-    c->planar_valid = !direct;
-    c->direct_src = direct ? d_pcm : nullptr;
+    // The input (Route::Input).  DIRECT_STEREO and SPLIT_XPOSE leave the caller's buffer the only copy of the input: it must
+    // stay valid until the batch's results were fetched (include/flacenc_gpu.h).  In place, the ORs come out of k_autocorr4,
+    // so k_candinfo runs after it -- see kernels/autocorr.inc.
+    const bool direct = r.input == Route::DIRECT_STEREO, xpose = r.input == Route::SPLIT_XPOSE;
+    const bool split = r.input == Route::SPLIT || xpose;
     if (direct) p.inter = d_pcm;
-    // the winners' LPC residuals handed from k_cand64p to k_frame64 (Params::hand_meta): 4096-sample direct stereo frames with
-    // LPC -- the candidate kernel's instantiations that keep the frame's image through the turn
-    if (direct && B == FN && p.max_lpc_order > 0 && c->d_hand) p.hand_meta = c->d_hand;
-    if (direct && c->seg_active && c->seg_direct) p.inter_tab = c->d_seg_ptr;   // (frames found through the table; d_pcm = the first segment)
+    if (r.hand) p.hand_meta = c->d_hand;
+    if (r.segments_in_place) p.inter_tab = c->d_seg_ptr;   // (frames found through the table; d_pcm = the first segment)
+    if (split) {
+        p.split_src = d_pcm;
+        p.split_dst = (c->channels == 1 || xpose) ? nullptr : c->d_planar;
+        p.xpose = xpose ? 1u : 0u;
+        if (c->channels == 1) p.planar = d_pcm;   // [frame][B] with ldb == B
+    }
     c->abs_valid = false;
     if (c->d_abs && first_range) HIP_TRY(hipMemsetAsync(c->d_abs, 0, sizeof(unsigned long long) * 4 * n_frames, st));
     // K0 (+ OR of every candidate's samples -> wasted bits)
-    // (one channel: interleaved and planar are the same bytes -- no copy either)
-    const bool planar_direct = !packed_bytes && aligned16 && (layout == FLACGPU_LAYOUT_PLANAR || c->channels == 1) && (B % 4 == 0) &&
-                               last_len == B && !c->knobs.no_direct;
-    // Independent channels, interleaved, with LPC: k_autocorr4's producers split the batch into the planar rows while
-    // they read it (Params::split_src) -- the K0 pass (8 B per sample at the HBM roofline) disappears.  Needs every
-    // frame on the wave kernels (no generic-path frame reads the rows before the autocorrelation has written them).
-    // (one channel: the input is its own planar row -- nothing to split, but the ORs still come out of the
-    // autocorrelation instead of a k_orbits pass over the batch)
-    const bool split = !direct && !packed_bytes && aligned16 && (layout == FLACGPU_LAYOUT_INTERLEAVED || c->channels == 1) &&
-                       (c->channels >= 2 || planar_direct) && split_input_ok(c, p, last_len);
-    // 3, 4, 6 or 8 channels: the candidate and subframe kernels read the interleaved batch in place as well (load_lane_xpose: a
-    // workgroup fetches a whole frame -- or half of a 6- or 8-channel one -- together) -- the planar rows, half of the
-    // autocorrelation kernel's HBM traffic, are not written at all; like a DIRECT stereo batch, the caller's buffer is then
-    // the only copy of the input.  (Whole frames of 5 or 6 channels in one workgroup: measured -- five or six 152-register
-    // waves do not pack onto the four SIMDs, the candidate and subframe kernels lose more (0.09 -> 0.13-0.15, 0.15 ->
-    // 0.25-0.27 ms per 67 M samples) than the autocorrelation gains (0.21 -> 0.14); 5 and 7 channels keep the rows.)
-    // (6, 8 channels: k_sub64, which needs its edge records; 3, 4: k_frame64)
-    // (>= 8-bit samples: the transposing buffer lies in the LDS image areas of the frame kernels, sized by the sample width)
-    const uint32_t C_ = c->channels;
-    // (the frames must then be assembled by k_frame64 / k_sub64 too -- pack_impl's f64w gates --: the generic k_emit / k_pack
-    // read the planar rows, which this path never writes)
-    const bool xpose = split && !c->knobs.no_xpose && !c->knobs.no_fused_pack && !c->knobs.no_frame64 && c->bps >= 8 &&
-                       (C_ == 3 || C_ == 4 || ((C_ == 8 || C_ == 6) && c->d_edges));
-    if (split) {
-        p.split_src = d_pcm;
-        if (c->seg_active && c->seg_direct) p.inter_tab = c->d_seg_ptr;   // (segments: every frame's address from the table)
-        p.split_dst = (c->channels == 1 || xpose) ? nullptr : c->d_planar;
-        p.xpose = xpose ? 1u : 0u;
-        if (c->channels == 1) p.planar = d_pcm;   // [frame][B] with ldb == B (planar_direct)
-        if (xpose) {
-            c->planar_valid = false;
-            c->direct_src = d_pcm;
-        }
-    }
-    if (c->seg_active && c->seg_direct && !direct && !split) {
-        g_last_error = "internal: a batch of segments was announced as read in place, but the analysis takes a copying path";
-        return FLACGPU_ERR_UNSUPPORTED;
-    }
-    if (!direct && !split) begin(0);
-    bool have_orbits = direct || split;
-    if (direct || split) {
-    } else if (packed_bytes) {
+    if (!r.in_place()) begin(0);
+    bool have_orbits = true;
+    if (r.input == Route::K0_PACKED) {
         launch_k0_packed(c, packed_bytes, n_frames, last_len, st);
-        have_orbits = true;
-    } else if (planar_direct) {
+    } else if (r.input == Route::PLANAR_IN_PLACE) {
         p.planar = d_pcm;  // [frame][ch][B] with ldb == B
-    } else {
+        have_orbits = false;
+    } else if (r.input == Route::K0_COPY) {
         have_orbits = launch_k0(c, d_pcm, layout, n_frames, last_len, 0, n_frames, st);
     }
     if (!have_orbits)
@@ -876,35 +861,21 @@ static int analyze_impl(flacgpu_ctx *c, const int32_t *d_pcm, int layout, uint32
         if (direct) hipLaunchKernelGGL(k_stereo_stats_t<true>, dim3(n_frames), dim3(WG), 0, st, p);
         else hipLaunchKernelGGL(k_stereo_stats_t<false>, dim3(n_frames), dim3(WG), 0, st, p);
     }
-    if (!direct && !split)
+    if (!r.in_place())
         hipLaunchKernelGGL(k_candinfo, dim3((ncb + WG - 1) / WG), dim3(WG), 0, st, p, c->d_orbits,
                            c->abs_valid ? c->d_abs : nullptr);
-    // blocks of exactly 4096 samples take the register-resident kernels; anything else (other
-    // block sizes, a short last frame, candidates wider than 25 bits) the generic LDS ones
-    const bool narrow = c->bps + (c->stereo4 ? 1u : 0u) <= 25u;
-    // wave-per-candidate kernel (FIXED + LPC analysis of a candidate in one wave, after the LPC
-    // parameters are known): block lengths 64 x {16, 18, 32, 36, 64}, LPC order <= 16
-    const bool w64 = narrow && wave_block_size(B) && (p.max_lpc_order <= 16 || B == FN) && p.max_po <= 6 &&
-                     !c->knobs.no_w64;
-    const uint32_t n_fast = w64 ? ((last_len == B) ? n_frames : n_frames - 1) : 0;
+    // frames [0, fast_analysis) take the wave-per-candidate kernel, the rest (other block sizes, a short last frame,
+    // candidates wider than 25 bits) the generic LDS ones; a range is all fast
     Params pf = p, pg = p;
-    pf.f0 = 0;
-    pf.fcount = n_fast;
-    pg.f0 = n_fast;
-    pg.fcount = n_frames - n_fast;
-    if (ranged) {
-        if (n_fast != n_frames || !(direct || split)) {
-            g_last_error = "internal: a ranged batch must run the in-place wave kernels on every frame";
-            return FLACGPU_ERR_UNSUPPORTED;
-        }
-        pf.f0 = rf0;
-        pf.fcount = rcnt;
-    }
+    pf.f0 = rf0;
+    pf.fcount = ranged ? rcnt : r.fast_analysis;
+    pg.f0 = r.fast_analysis;
+    pg.fcount = n_frames - r.fast_analysis;
     const bool lpc = p.max_lpc_order > 0;
     // Otherwise the FIXED analysis and the autocorrelation -> Levinson chain, which only share
     // their input, run concurrently on two HIP streams (fork after k_candinfo, join before
     // k_fir).  With per-kernel timing enabled everything is serialised on one stream.
-    const bool fork = lpc && !c->timing && !(w64 && pg.fcount == 0);
+    const bool fork = lpc && !c->timing && pg.fcount != 0;
     hipStream_t sf = fork ? c->aux_stream : st;
     if (fork) {
         HIP_TRY(hipEventRecord(c->ev_fork, st));
@@ -919,56 +890,27 @@ static int analyze_impl(flacgpu_ctx *c, const int32_t *d_pcm, int layout, uint32
     if (lpc) {
         const uint32_t H = ((p.max_lpc_order + 1) + 3u) & ~3u;
         begin(3);
+        // the whole blocks (of this range) in one launch, the in-place kernels with K4 in their tail; a short last frame
+        // in one of its own
         const uint32_t full = (last_len == B) ? n_frames : n_frames - 1;
-        bool k4_done = false;   // the direct autocorrelation kernels run K4 in their tail (whole blocks only: one launch)
-        if (ranged) k4_done = dispatch_autocorr(H, p, c->knobs, rf0, rcnt, B, c->d_window_full, st);
-        else if (full) k4_done = dispatch_autocorr(H, p, c->knobs, 0, full, B, c->d_window_full, st);
-        if (full != n_frames) k4_done = dispatch_autocorr(H, p, c->knobs, full, 1, last_len, c->d_window_last, st) && k4_done;
-        if (!k4_done || full != n_frames) {
-            if (ranged) {
-                g_last_error = "internal: a ranged batch needs K4 inside the autocorrelation kernel";
-                return FLACGPU_ERR_UNSUPPORTED;
-            }
+        const uint32_t ac_n = ranged ? rcnt : full;
+        if (ac_n && dispatch_autocorr(H, p, c->knobs, rf0, ac_n, B, c->d_window_full, st) != r.k4_in_autocorr) {
+            g_last_error = "internal: the autocorrelation launcher and the route disagree about K4";
+            return FLACGPU_ERR_UNSUPPORTED;
+        }
+        if (full != n_frames) (void)dispatch_autocorr(H, p, c->knobs, full, 1, last_len, c->d_window_last, st);
+        if (!r.k4_in_autocorr || full != n_frames) {
             begin(4);
             launch_lpc(p, (ncb + 63) / 64, st);
         }
         if (fork) HIP_TRY(hipStreamWaitEvent(st, c->ev_join, 0));
-        if (pg.fcount) {
-            begin(5);
-            if (B > LDS_BLOCK_LIMIT) hipLaunchKernelGGL(k_fir_t<true>, dim3(pg.fcount * c->ncand), dim3(WG), 0, st, pg);
-            else hipLaunchKernelGGL(k_fir_t<false>, dim3(pg.fcount * c->ncand), dim3(WG), dyn2, st, pg);
-        }
     }
-    bool decided = false;   // the persistent stereo kernels choose the channel assignment themselves
-    if (w64 && pf.fcount) {
-        begin(11);
-        decided = launch_cand64(pf, c->knobs, B, (pf.fcount * c->ncand + 3) / 4, st);
-    }
-    if (!decided && ranged) {
-        begin(6);
-        hipLaunchKernelGGL(k_decide, dim3(pf.fcount), dim3(64), 0, st, pf);
-    } else if (!decided) {
-        begin(6);
-        hipLaunchKernelGGL(k_decide, dim3(n_frames), dim3(64), 0, st, p);
-    } else if (pg.fcount) {
-        begin(6);
-        hipLaunchKernelGGL(k_decide, dim3(pg.fcount), dim3(64), 0, st, pg);
-    }
-    c->last_n_fast = ranged ? n_frames : pf.fcount;
-    c->ties_checked = !lpc;
-    c->ties_resolved = 0;
-    c->fir_rechecked = 0;
+    launch_candidates_and_decide(c, p, pf, pg, ranged, st, begin);
     // the residual rows (k_emit) are produced lazily: flacgpu_fetch(residuals) / host packing
     // need them, the device-side packer recomputes residuals in registers instead
-    c->resid_valid = false;
     if (c->timing) (void)hipEventRecord(c->ev[evi], st);
     HIP_TRY(hipGetLastError());
-    c->last_frames = n_frames;
-    c->last_len = last_len;
-    c->last_params = p;
-    c->last_stream = st;
-    c->drained = false;
-    c->packed_valid = false;
+    batch_submitted(c, p, r, st, (direct || xpose) ? d_pcm : nullptr, true, false);
     if (c->timing) {
         HIP_TRY(hipStreamSynchronize(st));
         for (auto &m : c->last_ms) m = 0.f;
@@ -979,6 +921,32 @@ static int analyze_impl(flacgpu_ctx *c, const int32_t *d_pcm, int layout, uint32
         }
     }
     return FLACGPU_OK;
+}
+
+// The candidate stage and the channel assignment, for a first analysis and for the re-run after a host re-decision:
+// the generic FIR of frames pg, the wave-per-candidate kernel (FIXED + LPC analysis of a candidate in one wave, after
+// the LPC parameters are known) of frames pf, and k_decide for whatever the persistent stereo kernels did not decide
+// themselves.  begin(k): the timing mark in front of kernel slot k.
+static void launch_candidates_and_decide(flacgpu_ctx *c, const Params &p, const Params &pf, const Params &pg, bool ranged,
+                                         hipStream_t st, const std::function<void(int)> &begin) {
+    const uint32_t B = p.block_size;
+    if (p.max_lpc_order > 0 && pg.fcount) {
+        begin(5);
+        const size_t dyn2 = (2 * (size_t)B + B / 16 + 16) * sizeof(int32_t);
+        if (B > LDS_BLOCK_LIMIT) hipLaunchKernelGGL(k_fir_t<true>, dim3(pg.fcount * c->ncand), dim3(WG), 0, st, pg);
+        else hipLaunchKernelGGL(k_fir_t<false>, dim3(pg.fcount * c->ncand), dim3(WG), dyn2, st, pg);
+    }
+    bool decided = false;   // the persistent stereo kernels choose the channel assignment themselves
+    if (pf.fcount) {
+        begin(11);
+        decided = launch_cand64(pf, c->knobs, B, (pf.fcount * c->ncand + 3) / 4, st);
+    }
+    const Params &pd = !decided ? (ranged ? pf : p) : pg;   // (undecided: the range's frames, or the whole batch)
+    const uint32_t nd = !decided ? (ranged ? pf.fcount : p.n_frames) : pg.fcount;
+    if (nd) {
+        begin(6);
+        hipLaunchKernelGGL(k_decide, dim3(nd), dim3(64), 0, st, pd);
+    }
 }
 
 static int pack_impl(flacgpu_ctx *c, uint64_t first_frame_number, uint32_t sample_rate, hipStream_t st,
@@ -1038,21 +1006,12 @@ static int resolve_order_ties(flacgpu_ctx *c) {
         HIP_TRY(hipStreamSynchronize(st));   // `h` is a local
     }
     // candidate stage + assignment again (k_fixed's results are still in place)
-    const uint32_t B = p.block_size;
     Params pf = p, pg = p;
     pf.f0 = 0;
-    pf.fcount = c->last_n_fast;
-    pg.f0 = c->last_n_fast;
-    pg.fcount = p.n_frames - c->last_n_fast;
-    const size_t dyn2 = (2 * (size_t)B + B / 16 + 16) * sizeof(int32_t);
-    if (pg.fcount) {
-        if (B > LDS_BLOCK_LIMIT) hipLaunchKernelGGL(k_fir_t<true>, dim3(pg.fcount * c->ncand), dim3(WG), 0, st, pg);
-        else hipLaunchKernelGGL(k_fir_t<false>, dim3(pg.fcount * c->ncand), dim3(WG), dyn2, st, pg);
-    }
-    bool decided = false;
-    if (pf.fcount) decided = launch_cand64(pf, c->knobs, B, (pf.fcount * c->ncand + 3) / 4, st);
-    if (!decided) hipLaunchKernelGGL(k_decide, dim3(p.n_frames), dim3(64), 0, st, p);
-    else if (pg.fcount) hipLaunchKernelGGL(k_decide, dim3(pg.fcount), dim3(64), 0, st, pg);
+    pf.fcount = c->route.fast_analysis;
+    pg.f0 = c->route.fast_analysis;
+    pg.fcount = p.n_frames - c->route.fast_analysis;
+    launch_candidates_and_decide(c, p, pf, pg, false, st, [](int) {});
     HIP_TRY(hipGetLastError());
     c->resid_valid = false;
     c->ties_resolved = n_ties;
@@ -1165,35 +1124,20 @@ static int pack_impl(flacgpu_ctx *c, uint64_t first_frame_number, uint32_t sampl
     // from the PCM, CRC-16 from LDS, one write of the finished bytes); any other frame goes
     // through k_emit (residual rows) -> k_pack (one workgroup per subframe, zero-filled output,
     // atomic OR at shared words) -> k_crc
+    // (which frames: Route::fast_pack; a range is all fast)
     const uint32_t B = p.block_size;
-    const bool narrow = c->bps + (c->stereo4 ? 1u : 0u) <= 25u;
-    uint32_t fbw = frame_fb_words(p.channels, c->bps, B);
-    if (c->stereo4 && p.exhaustive) fbw = std::min(fbw, frame_fb_words_exhaustive_stereo(c->bps, B));
-    // wave per subframe: block lengths 64 x {16, 18, 32, 36, 64}; orders 17..32 and 5..8 channels
-    // for 4096-sample blocks only (and not both)
-    const bool f64w = narrow && wave_block_size(B) &&
-                      (p.max_lpc_order <= 16 || (B == FN && p.channels <= 4)) &&
-                      (p.channels <= 4 || B == FN) && p.max_po <= 6 &&
-                      (size_t)fbw * sizeof(int32_t) <= 150 * 1024 &&
-                      !c->knobs.no_fused_pack && !c->knobs.no_frame64;
-    const uint32_t n_fast = f64w ? (p.last_len == B ? p.n_frames : p.n_frames - 1) : 0;
+    const uint32_t n_fast = c->route.fast_pack;
     const bool fused = n_fast != 0;
     Params pf = p, pg = p;
-    pf.f0 = 0;
-    pf.fcount = n_fast;
+    pf.f0 = ranged ? c->rng_f0 : 0u;
+    pf.fcount = ranged ? c->rng_cnt : n_fast;
     pg.f0 = n_fast;
     pg.fcount = p.n_frames - n_fast;
-    if (ranged) {
-        if (n_fast != p.n_frames) {
-            g_last_error = "internal: a ranged batch must be assembled by the wave kernels";
-            return FLACGPU_ERR_UNSUPPORTED;
-        }
-        pf.f0 = c->rng_f0;
-        pf.fcount = c->rng_cnt;
-    }
+    uint32_t fbw = frame_fb_words(p.channels, c->bps, B);   // k_frame64's LDS image
+    if (c->stereo4 && p.exhaustive) fbw = std::min(fbw, frame_fb_words_exhaustive_stereo(c->bps, B));
     // host output: k_frame64 only ever stores (dwords inside a frame, bytes at its ends), so it can write
     // over PCIe into pinned memory; the generic packer builds its frames with atomic ORs and cannot
-    c->out_in_host = c->host_out && pf.fcount && pg.fcount == 0 && c->host_out_cap >= c->packed_cap;
+    c->out_in_host = c->host_out && c->route.host_out_possible && c->host_out_cap >= c->packed_cap;
     if (c->out_in_host) q.out_words = reinterpret_cast<uint32_t *>(c->host_out);
     if (pg.fcount) launch_zero(q, p.n_frames, st);
     if (c->timing) (void)hipEventRecord(ev[1], st);
@@ -1237,7 +1181,7 @@ int flacgpu_set_tuning(flacgpu_ctx *c, int key, int value) {
     switch (key) {
     case FLACGPU_TUNE_TWO_RANGES: c->two_ranges = value != 0; return FLACGPU_OK;
     case FLACGPU_TUNE_CHUNK_MSAMPLES:
-        c->chunk_samples = value <= 0 ? 0u : (uint32_t)std::min(value, 2047) << 20;
+        c->chunk_samples = flacenc_route::chunk_samples_of(value);
         c->chunk_auto = false;
         return FLACGPU_OK;
     case FLACGPU_TUNE_COPY_INPUT:
@@ -1261,28 +1205,6 @@ int flacgpu_set_tuning(flacgpu_ctx *c, int key, int value) {
     return FLACGPU_ERR_INVALID_ARG;
 }
 
-// Frames per range when flacgpu_encode_device cuts a batch (0: it does not).  Only batches whose every frame runs the
-// in-place wave kernels with K4 inside the autocorrelation kernel are cut -- the conditions of `direct` / `split` in
-// analyze_impl, whole 4096-sample blocks, exhaustive channel choice (the fast one sums the whole batch first).
-static uint32_t chunk_frames(const flacgpu_ctx *c, const int32_t *d_pcm, int layout, uint32_t n_frames, uint32_t last_len) {
-    const uint32_t B = c->opts.block_size;
-    const Knobs &kn = c->knobs;
-    if (!c->chunk_samples || c->timing || c->lag_split == 2 || B != FN || last_len != B || layout != FLACGPU_LAYOUT_INTERLEAVED) return 0;
-    if (c->chunk_auto && !c->stereo4) return 0;   // independent channels: only on request (config 4: no gain measured)
-    if (((uintptr_t)d_pcm & 15u) || kn.no_direct || kn.no_w64 || kn.experiment_mfma_ac || kn.no_fused_pack || kn.no_frame64)
-        return 0;
-    const uint32_t lo = c->opts.max_lpc_order;
-    if (lo < 1 || lo > 16 || c->opts.max_partition_order > 6 || c->bps + (c->stereo4 ? 1u : 0u) > 25u) return 0;
-    if (c->stereo4 ? !(c->channels == 2 && c->bps <= 24 && c->opts.exhaustive_channel_correlation && c->ncand == 4)
-                   : !(c->channels >= 2 && c->ncand == c->channels))
-        return 0;
-    if ((size_t)frame_fb_words(c->channels, c->bps, B) * sizeof(int32_t) > 150 * 1024) return 0;
-    const uint64_t per_frame = (uint64_t)B * c->channels;
-    uint32_t chunk = (uint32_t)(c->chunk_samples / per_frame) & ~63u;   // whole candidate groups of the autocorrelation
-    if (chunk < 256 || n_frames < chunk + chunk / 2) return 0;          // (nothing to cut, or ranges too small to fill the chip)
-    return chunk;
-}
-
 // Analysis + frame assembly of one batch in one call.  With FLACGPU_TUNE_TWO_RANGES set, when
 // every frame takes the wave kernels (4096-sample blocks, order <= 16, <= 4 channels), the batch
 // is cut into two frame ranges that run
@@ -1296,41 +1218,27 @@ int flacgpu_encode_device(flacgpu_ctx *c, const int32_t *d_pcm, int layout, uint
                           void *stream) {
     if (!c) return FLACGPU_ERR_INVALID_ARG;
     CTX_GUARD(c);
+    if (!d_pcm) {
+        g_last_error = "invalid encode arguments";
+        return FLACGPU_ERR_INVALID_ARG;
+    }
     const uint32_t B = c->opts.block_size;
-    const uint32_t fbw = frame_fb_words(c->channels, c->bps, B);
-    const bool eligible =
-        d_pcm && n_frames >= 256 && n_frames <= c->max_frames && last_len == B && wave_block_size(B) &&
-        (c->bps + (c->stereo4 ? 1u : 0u) <= 25u) &&
-        (c->opts.max_lpc_order <= 16 || (B == FN && c->channels <= 4)) &&
-        c->opts.max_partition_order <= 6 && (c->channels <= 4 || B == FN) && (layout == 0 || layout == 1) &&
-        (size_t)fbw * sizeof(int32_t) <= 150 * 1024 && !c->timing &&
-        !c->knobs.no_w64 && !c->knobs.no_fused_pack && !c->knobs.no_frame64 &&
-        c->two_ranges;
+    const Route route = route_of(c, aligned16(d_pcm), layout, n_frames, last_len, 0, false, true);
     hipStream_t st0;
     if (int rc = resolve_stream(c, stream, &st0)) return rc;
-    if (!eligible) {
-        if (!d_pcm) {
-            g_last_error = "invalid encode arguments";
-            return FLACGPU_ERR_INVALID_ARG;
-        }
-        // A batch of more samples than the chip's last-level cache likes (256 MiB of Infinity Cache: the candidate and
-        // frame kernels re-read what the autocorrelation just streamed) is run range by range -- the whole kernel chain for
-        // ~64 Mi samples at a time, each range's frame offsets continuing from the one before (k_layout): a stereo batch of
-        // 16384 frames (134 M samples) runs 9 % faster as two ranges of 8192 (profiles/r04_chunk_ab.json; 8-channel batches
-        // of 8192 frames as four ranges: no difference, so independent channels are cut only when the tuning asks).
-        const uint32_t chunk = chunk_frames(c, d_pcm, layout, n_frames, last_len);
-        if (chunk) {
+    if (!route.two_ranges || n_frames > c->max_frames) {   // (too many frames: analyze_impl says so)
+        if (route.range_frames) {   // the whole kernel chain range by range, each range's frame offsets continuing from the one before
             int rc = FLACGPU_OK;
-            for (uint32_t f0 = 0; f0 < n_frames && rc == FLACGPU_OK; f0 += chunk) {
+            for (uint32_t f0 = 0; f0 < n_frames && rc == FLACGPU_OK; f0 += route.range_frames) {
                 c->rng_f0 = f0;
-                c->rng_cnt = std::min(chunk, n_frames - f0);
-                rc = analyze_impl(c, d_pcm, layout, n_frames, last_len, st0, 0);
+                c->rng_cnt = std::min(route.range_frames, n_frames - f0);
+                rc = analyze_impl(c, d_pcm, layout, n_frames, last_len, st0, 0, &route);
                 if (rc == FLACGPU_OK) rc = pack_impl(c, first_frame_number, sample_rate, st0, nullptr);
             }
             c->rng_f0 = c->rng_cnt = 0;
             return rc;
         }
-        if (int rc = analyze_impl(c, d_pcm, layout, n_frames, last_len, st0, 0)) return rc;
+        if (int rc = analyze_impl(c, d_pcm, layout, n_frames, last_len, st0, 0, &route)) return rc;
         return pack_impl(c, first_frame_number, sample_rate, st0, nullptr);
     }
     hipStream_t st1 = c->aux_stream;
@@ -1344,7 +1252,7 @@ int flacgpu_encode_device(flacgpu_ctx *c, const int32_t *d_pcm, int layout, uint
     q.frame_off = c->d_frame_off;
     q.cap_bytes = c->packed_cap;
     // (planar rows are read in place unless the caller asked for a copy: FLACGPU_TUNE_COPY_INPUT / FLACGPU_NO_DIRECT)
-    const bool planar_direct = (layout == FLACGPU_LAYOUT_PLANAR) && (B % 4 == 0) && !c->knobs.no_direct && ((uintptr_t)d_pcm & 15u) == 0;
+    const bool planar_direct = route.input == Route::PLANAR_IN_PLACE;
     if (planar_direct) p.planar = d_pcm;
     HIP_TRY(hipMemsetAsync(c->d_stats_base, 0, sizeof(uint32_t) * (kTurnWords + 4 + (size_t)n_frames * c->ncand), st0));  // + d_orbits
     HIP_TRY(hipEventRecord(c->ev_fork, st0));
@@ -1352,7 +1260,7 @@ int flacgpu_encode_device(flacgpu_ctx *c, const int32_t *d_pcm, int layout, uint
     const uint32_t h = ((n_frames / 2) + 15u) & ~15u;  // 16 frames = one autocorrelation wave group
     const bool lpc = p.max_lpc_order > 0;
     const uint32_t H = ((p.max_lpc_order + 1) + 3u) & ~3u;
-    const size_t l64 = (size_t)fbw * sizeof(int32_t);
+    const size_t l64 = (size_t)frame_fb_words(c->channels, c->bps, B) * sizeof(int32_t);
     for (int half = 0; half < 2; half++) {
         hipStream_t st = half ? st1 : st0;
         Params r = p;
@@ -1380,18 +1288,7 @@ int flacgpu_encode_device(flacgpu_ctx *c, const int32_t *d_pcm, int layout, uint
     HIP_TRY(hipEventRecord(c->ev_join, st1));
     HIP_TRY(hipStreamWaitEvent(st0, c->ev_join, 0));
     HIP_TRY(hipGetLastError());
-    c->resid_valid = false;
-    c->planar_valid = true;
-    c->direct_src = nullptr;
-    c->last_frames = n_frames;
-    c->last_len = last_len;
-    c->last_params = p;
-    c->last_stream = st0;
-    c->packed_valid = true;
-    c->last_n_fast = n_frames;
-    c->ties_checked = !lpc;
-    c->ties_resolved = 0;
-    c->fir_rechecked = 0;
+    batch_submitted(c, p, route, st0, nullptr, true, true);
     c->last_first_frame = first_frame_number;
     c->last_rate = sample_rate;
     return FLACGPU_OK;
@@ -1401,6 +1298,14 @@ int flacgpu_encode_device(flacgpu_ctx *c, const int32_t *d_pcm, int layout, uint
 // batch (the kernels' launches and their serial walk over a block are paid once, not once per stream).  Frame f of the batch
 // is frame f - f0(s) of its segment s; its frame number and, for direct stereo input read in place, its address come from
 // per-frame tables (PackParams::frame_numbers, Params::inter_tab).
+static int ensure_segment_tables(flacgpu_ctx *c) {   // (allocated by the first segments call of the context)
+    const size_t F = c->max_frames;
+    if (c->d_seg_fn) return FLACGPU_OK;
+    HIP_TRY(hipMalloc((void **)&c->d_seg_fn, sizeof(uint64_t) * F));
+    HIP_TRY(hipMalloc((void **)&c->d_seg_ptr, sizeof(int32_t *) * F));
+    HIP_TRY(hipHostMalloc((void **)&c->h_seg, sizeof(uint64_t) * 2 * F, hipHostMallocDefault));
+    return FLACGPU_OK;
+}
 static int segments_common(flacgpu_ctx *c, const flacgpu_segment *segs, uint32_t n_segs, bool on_device, uint32_t sample_rate,
                            hipStream_t st) {
     const uint32_t B = c->opts.block_size;
@@ -1417,21 +1322,19 @@ static int segments_common(flacgpu_ctx *c, const flacgpu_segment *segs, uint32_t
         return FLACGPU_ERR_INVALID_ARG;
     }
     const size_t F = c->max_frames;
-    if (!c->d_seg_fn) {
-        HIP_TRY(hipMalloc((void **)&c->d_seg_fn, sizeof(uint64_t) * F));
-        HIP_TRY(hipMalloc((void **)&c->d_seg_ptr, sizeof(int32_t *) * F));
-        HIP_TRY(hipHostMalloc((void **)&c->h_seg, sizeof(uint64_t) * 2 * F, hipHostMallocDefault));
-    }
+    if (int rc = ensure_segment_tables(c)) return rc;
     // the staging arrays and the device tables of the batch before are free once BOTH streams are idle: the one this call
     // runs on and the one the context's last batch (or its re-assembly after a host re-decision) was submitted to
     HIP_TRY(hipStreamSynchronize(st));
     if (int rc = ctx_sync(c)) return rc;
     const size_t frame_ints = (size_t)B * c->channels;
-    Params probe;
-    fill_params(c, (uint32_t)total, B, probe);
-    // read in place (stereo: Params::inter; 2..8 independent channels: Params::split_src) or gathered into d_in
-    bool direct = on_device && (direct_input_ok(c, probe, B) || (c->channels >= 2 && split_input_ok(c, probe, B)));
-    for (uint32_t i = 0; i < n_segs && direct; i++) direct = ((uintptr_t)segs[i].pcm & 15u) == 0;
+    // read in place (stereo: Params::inter; 2..8 independent channels: Params::split_src) where the route grants it,
+    // otherwise gathered into d_in and routed as one plain batch there
+    bool all_aligned = true;
+    for (uint32_t i = 0; i < n_segs; i++) all_aligned = all_aligned && aligned16(segs[i].pcm);
+    Route route = route_of(c, all_aligned, FLACGPU_LAYOUT_INTERLEAVED, (uint32_t)total, B, 0, on_device);
+    const bool direct = route.segments_in_place;
+    if (!direct) route = route_of(c, aligned16(c->d_in), FLACGPU_LAYOUT_INTERLEAVED, (uint32_t)total, B);
     uint64_t *fn = c->h_seg;
     const int32_t **ptr = reinterpret_cast<const int32_t **>(c->h_seg + F);
     uint32_t f = 0;
@@ -1451,7 +1354,7 @@ static int segments_common(flacgpu_ctx *c, const flacgpu_segment *segs, uint32_t
     c->seg_pending = true;
     c->seg_direct = direct;
     c->rng_f0 = c->rng_cnt = 0;
-    if (int rc = analyze_impl(c, direct ? segs[0].pcm : c->d_in, FLACGPU_LAYOUT_INTERLEAVED, (uint32_t)total, B, st, 0)) {
+    if (int rc = analyze_impl(c, direct ? segs[0].pcm : c->d_in, FLACGPU_LAYOUT_INTERLEAVED, (uint32_t)total, B, st, 0, &route)) {
         c->seg_pending = false;   // (refused before the analysis took the announcement)
         return rc;
     }
@@ -1549,14 +1452,14 @@ int flacgpu_pack_plans(flacgpu_ctx *c, const int32_t *pcm, uint32_t n_frames, ui
     HIP_TRY(hipMemcpyAsync(c->d_out, subs, sizeof(*subs) * n_frames * C, hipMemcpyHostToDevice, st));
     Params p;
     fill_params(c, n_frames, last_len, p);
-    c->last_params = p;
-    c->last_frames = n_frames;
-    c->last_len = last_len;
-    c->last_stream = st;
-    c->resid_valid = false;
-    c->planar_valid = true;
-    c->direct_src = nullptr;
-    c->packed_valid = false;
+    // (the route of a batch whose input was copied into planar rows, as above: only its frame assembly is run)
+    RouteContext rc = route_context_of(c);
+    rc.knobs.no_direct = true;
+    RouteBatch rb;
+    rb.n_frames = n_frames;
+    rb.last_len = last_len;
+    rb.aligned16 = aligned16(c->d_in);
+    batch_submitted(c, p, flacenc_route::plan_route(rc, rb), st, nullptr, false, false);
     HIP_TRY(hipStreamSynchronize(st));   // the host arrays may go away
     c->host_out = nullptr;
     c->out_in_host = false;
@@ -1746,12 +1649,7 @@ int flacgpu_encode_segments_packed_async_host(flacgpu_ctx *c, const uint8_t *pcm
         return FLACGPU_ERR_INVALID_ARG;
     }
     CTX_GUARD(c);
-    const size_t F = c->max_frames;
-    if (!c->d_seg_fn) {
-        HIP_TRY(hipMalloc((void **)&c->d_seg_fn, sizeof(uint64_t) * F));
-        HIP_TRY(hipMalloc((void **)&c->d_seg_ptr, sizeof(int32_t *) * F));
-        HIP_TRY(hipHostMalloc((void **)&c->h_seg, sizeof(uint64_t) * 2 * F, hipHostMallocDefault));
-    }
+    if (int rc = ensure_segment_tables(c)) return rc;
     if (!c->drained) {   // (the table's staging copy of the batch before must be free; one batch per context at a time)
         if (int rc = ctx_sync(c)) return rc;
         HIP_TRY(hipStreamSynchronize(c->own_stream));

@@ -15,7 +15,7 @@ namespace {
 
 namespace flacgpu_k {
 void launch_frame64_direct(const Params &p, const PackParams &q, uint32_t B, uint32_t frames, size_t lds, hipStream_t st) {
-    // the wave block lengths (flacenc_gpu.hip: direct_input_ok); LPC order > 16 with 4096-sample blocks only
+    // the wave block lengths (host/batch_route.cpp: DIRECT_STEREO); LPC order > 16 with 4096-sample blocks only
     switch (B) {
     case 2304: launch_frame64_nt<128, 36, 16, true>(p, q, frames, lds, st); break;
     case 2048: launch_frame64_nt<128, 32, 16, true>(p, q, frames, lds, st); break;

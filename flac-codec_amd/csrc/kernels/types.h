@@ -12,10 +12,10 @@
 #include <type_traits>
 
 #include "flacenc_gpu.h"
+#include "shape.h"   // MAXP, FN, LDS_BLOCK_LIMIT, frame_fb_words, the wave block lengths, Knobs
 
 
 constexpr int WG = 256;          // threads per workgroup (4 wave64)
-constexpr int MAXP = 6;          // max effective partition order (64 partitions, encode.rs:3756)
 constexpr int NLEAF = 1 << MAXP;
 constexpr int NNODE = 2 * NLEAF - 1;
 
@@ -163,15 +163,11 @@ __device__ __forceinline__ const int32_t *split_frame(const Params &p, uint32_t 
     return p.inter_tab ? p.inter_tab[frame] : p.split_src + (size_t)frame * frame_dwords;
 }
 
-// largest block the generic kernels keep whole in LDS (k_fixed / k_fir: two arrays of it); larger
-// blocks (up to 65535, encode.rs:1418-1423) use per-workgroup arrays in HBM instead
-constexpr uint32_t LDS_BLOCK_LIMIT = 16384;
 __host__ __device__ constexpr uint32_t big_scratch_ints(uint32_t block_size) {
     return 2u * (block_size + block_size / 16u + 16u) + 64u;   // x[n] | r[n] with the RIDX padding
 }
 constexpr uint32_t DEFER_SLOTS = 64, DEFER_SLOT_WORDS = 16;   // Params::defer_stats: workgroup w adds to slot w % 64 (a 64-byte line each)
 constexpr int AC_LD = 36;        // row stride of the ac buffer (max lag group count rounded up)
-constexpr uint32_t FN = 4096;    // the block length of every preset but `fast`
 
 struct PackParams {
     uint64_t first_frame_number;
@@ -203,47 +199,6 @@ __host__ __device__ constexpr uint32_t pack_sb_words(uint32_t block_size) {
     return ((block_size * 33u / 32u + 32u) + 3u) & ~3u;
 }
 
-// words of LDS a whole frame of 4096-sample subframes may need (VERBATIM everywhere + header +
-// CRC-16 + one guard word for the funnel shifts); multiple of 4 words
-__host__ __device__ constexpr uint32_t frame_fb_words(uint32_t channels, uint32_t bps, uint32_t n = FN) {
-    return (((16u + 2u) * 8u + channels * (n * (bps + 1u) + 64u) + 31u) / 32u + 2u + 3u) & ~3u;
-}
-
-
-// Stereo frames whose channel assignment is chosen EXHAUSTIVELY (first minimum of the candidate pairs' bit counts,
-// encode.rs:2747-2786): the chosen pair is never larger than L + R, and a chosen subframe never larger than its
-// VERBATIM form, so the frame body is bounded by two bps-bit VERBATIM subframes -- not by the bps + 1 bits of a side
-// channel.  For 24-bit stereo that is 24.6 KB instead of 25.6 KB of LDS per k_frame64 workgroup: six workgroups per
-// CU instead of five.  (The fast channel choice picks its pair before any bit count exists: frame_fb_words.)
-__host__ __device__ constexpr uint32_t frame_fb_words_exhaustive_stereo(uint32_t bps, uint32_t n = FN) {
-    return (((16u + 2u) * 8u + 2u * (n * bps + 64u) + 31u) / 32u + 2u + 3u) & ~3u;
-}
-
-// block lengths the wave kernels are instantiated for: 64 lanes x SPL samples
-#define FLACGPU_WAVE_SIZES(X) X(4096, 64) X(2304, 36) X(2048, 32) X(1152, 18) X(1024, 16)
-
-// Every FLACGPU_* environment knob, resolved ONCE per context (flacgpu_create; flacenc_gpu.hip read_knobs) -- the
-// dispatch path never calls getenv.  The A/B selectors keep an older or generic kernel reachable for measurements
-// and parity tests; the TEST knobs (tie_band, tie_perturb, experiment_mfma_ac, fir_suspect_bits) are honoured only
-// when FLACGPU_TEST_KNOBS=1 is set as well.  Every one of them is exercised by a test, a tool or a bench leg
-// ("Environment selectors"; tests/test_knob_inventory.py keeps that list honest).
-struct Knobs {
-    bool no_direct = false, no_w64 = false, no_fused_pack = false, no_frame64 = false,
-         early_download = false,   // the frames' D2H copy queued before the sizes are known (FLACGPU_EARLY_DOWNLOAD)
-         no_hand = false,          // A/B: Params::hand_meta off (FLACGPU_NO_HAND)
-         no_direct_short = false,  // A/B: 1024 / 1152 / 2048 / 2304-sample blocks through K0 + k_cand64 (FLACGPU_NO_DIRECT_SHORT)
-         no_ac_fma = false,        // A/B: every autocorrelation term a multiply and an add (FLACGPU_NO_AC_FMA)
-         no_xpose = false,         // A/B: 4 / 8 interleaved channels split into planar rows by k_autocorr4 instead of read in place (FLACGPU_NO_XPOSE)
-         no_cand_pair = false;     // A/B: four waves per frame also for the fast channel choice without LPC (FLACGPU_NO_CAND_PAIR)
-    bool force_fir_check = false;       // A/B + TEST: every candidate takes the exact ResidualOverflow test first (FLACGPU_FIR_CHECK)
-    uint32_t cand_grid = 0;             // resident workgroups of the persistent candidate kernels, 0: default
-    bool experiment_mfma_ac = false;    // TEST: the re-associating MFMA autocorrelation (not bit-exact)
-    bool has_tie_band = false, has_tie_perturb = false;
-    double tie_band = 0.0, tie_perturb = 0.0;   // TEST
-    uint32_t fir_suspect_bits = 0;      // TEST: Params::fir_suspect_bits, 0: default (30)
-    int defer_fixed = -1;               // FLACGPU_DEFER_FIXED: 0 / 1 / 2 / 3 (Params::defer_fixed); -1: default (1)
-    int defer_margin16 = -1;            // FLACGPU_DEFER_MARGIN16: Params::defer_margin16; -1: default
-};
 Knobs read_knobs();   // flacenc_gpu.hip
 
 // ---- launchers (one per kernel family; defined in the .hip file that holds the kernels) ----
