@@ -113,6 +113,18 @@ class DeviceJob(C.Structure):
                 ("out_len", C.c_size_t), ("status", C.c_int32), ("altered", C.c_uint32), ("md5", C.c_uint8 * 16)]
 
 
+class DeviceOutJob(C.Structure):
+    """flacenc_device_out_job: one stream of flacenc_encode_many_device_out; its file goes to bytes
+    [out_offset, out_offset + out_cap) of the call's device buffer."""
+    _fields_ = [("in_offset", C.c_uint64), ("samples", C.c_uint64), ("out_offset", C.c_uint64), ("out_cap", C.c_uint64),
+                ("out_len", C.c_uint64), ("status", C.c_int32), ("altered", C.c_uint32), ("md5", C.c_uint8 * 16)]
+
+
+class PlaceRun(C.Structure):
+    """flacgpu_place_run: one byte run of flacgpu_place_frames / flacgpu_place_runs_host."""
+    _fields_ = [("src", C.c_uint64), ("dst", C.c_uint64), ("n", C.c_uint64)]
+
+
 DEVICE_NO_MD5 = 1   # FLACENC_DEVICE_NO_MD5
 
 

@@ -7,6 +7,7 @@
 #include "kernels/sample_types.h"
 #include "kernels/frame_extent.h"
 #include "kernels/meta_walk.h"
+#include "kernels/byte_shift.h"
 #include "flac_stream.h"
 
 #include <stdlib.h>

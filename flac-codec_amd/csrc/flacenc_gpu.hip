@@ -29,6 +29,7 @@
 //         generic: k_zero + k_pack + k_crc
 //   N3    k_decode (decode.inc)  decode.rs:1388-1856 read_frame .. predict, one lane per subframe
 #include "kernels/types.h"
+#include "kernels/place_rule.h"
 #include "batch_route.h"
 #include "lpc_host.h"
 
@@ -177,7 +178,14 @@ struct flacgpu_ctx {
     uint32_t layout_epoch = 0;
     uint64_t packed_cap = 0;        // bytes
     bool packed_valid = false;
-    bool resid_valid = false;       // d_resid holds the rows of the last analysed batch
+    // flacgpu_frame_offsets / flacgpu_place_frames: the packed bytes of the batch in hand once they are final (total_valid),
+    // and the run table's pinned and device copies, kept between calls; ev_place: the last placement has run
+    uint64_t packed_total = 0;
+    bool total_valid = false, place_pending = false;
+    PlaceRun *h_runs = nullptr, *d_runs = nullptr;
+    uint32_t runs_cap = 0;
+    hipEvent_t ev_place = nullptr;
+    bool resid_valid = false;      // d_resid holds the rows of the last analysed batch
     // a batch cut into frame ranges by flacgpu_encode_device (Route::range_frames): analyze_impl / pack_impl launch their kernels for
     // frames [rng_f0, rng_f0 + rng_cnt) only; rng_cnt == 0: the whole batch
     uint32_t rng_f0 = 0, rng_cnt = 0;
@@ -558,6 +566,9 @@ void flacgpu_destroy(flacgpu_ctx *c) {
     if (c->d_seg_ptr) (void)hipFree(c->d_seg_ptr);
     if (c->h_seg) (void)hipHostFree(c->h_seg);
     (void)hipFree(c->d_edges);
+    (void)hipFree(c->d_runs);
+    if (c->h_runs) (void)hipHostFree(c->h_runs);
+    if (c->ev_place) (void)hipEventDestroy(c->ev_place);
     (void)hipFree(c->d_decoded); (void)hipFree(c->d_verify); (void)hipFree(c->d_big);
     if (c->aux_stream) (void)hipStreamDestroy(c->aux_stream);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
@@ -748,6 +759,7 @@ static void batch_submitted(flacgpu_ctx *c, const Params &p, const Route &r, hip
     c->planar_valid = only_copy == nullptr;
     c->direct_src = only_copy;
     c->packed_valid = packed;
+    c->total_valid = false;
     if (analysed) {
         c->ties_checked = p.max_lpc_order == 0;
         c->ties_resolved = 0;
@@ -1162,6 +1174,7 @@ static int pack_impl(flacgpu_ctx *c, uint64_t first_frame_number, uint32_t sampl
     if (c->timing) (void)hipEventRecord(ev[3], st);
     HIP_TRY(hipGetLastError());
     c->packed_valid = true;
+    c->total_valid = false;
     c->last_stream = st;
     c->drained = false;
     if (c->timing) {
@@ -1408,6 +1421,68 @@ int flacgpu_fetch_frames(flacgpu_ctx *c, uint8_t *out, size_t cap, uint64_t *off
         return FLACGPU_OK;
     }
     if (int rc = copy_sync(c, out, c->d_packed, bytes, hipMemcpyDeviceToHost)) return rc;
+    return FLACGPU_OK;
+}
+
+// flacgpu_fetch_frames up to and including the download of the offsets; the frame bytes stay where they are
+int flacgpu_frame_offsets(flacgpu_ctx *c, uint64_t *offsets, uint64_t *total) {
+    if (!c || !c->packed_valid) {
+        g_last_error = "flacgpu_frame_offsets: nothing packed";
+        return FLACGPU_ERR_INVALID_ARG;
+    }
+    CTX_GUARD(c);
+    const size_t F = c->last_frames;
+    if (int rc = ctx_sync(c)) return rc;
+    if (int rc = resolve_order_ties(c)) return rc;
+    if (offsets) {
+        if (int rc = copy_sync(c, offsets, c->d_frame_off, sizeof(uint64_t) * (F + 1), hipMemcpyDeviceToHost)) return rc;
+        c->packed_total = offsets[F];
+    } else if (int rc = copy_sync(c, &c->packed_total, c->d_frame_off + F, sizeof(uint64_t), hipMemcpyDeviceToHost)) {
+        return rc;
+    }
+    c->total_valid = true;
+    if (total) *total = c->packed_total;
+    return FLACGPU_OK;
+}
+
+int flacgpu_place_frames(flacgpu_ctx *c, const flacgpu_place_run *runs, uint32_t n_runs) {
+    if (!c || !c->packed_valid || c->out_in_host || (n_runs && !runs)) {
+        g_last_error = "flacgpu_place_frames: nothing packed in device memory, or no run table";
+        return FLACGPU_ERR_INVALID_ARG;
+    }
+    if (!c->total_valid)   // (the frames are final only behind the re-decisions: flacgpu_resolve)
+        if (int rc = flacgpu_frame_offsets(c, nullptr, nullptr)) return rc;
+    for (uint32_t i = 0; i < n_runs; i++) {
+        uint64_t end = 0, dend = 0;
+        if (__builtin_add_overflow(runs[i].src, runs[i].n, &end) || end > c->packed_total ||
+            __builtin_add_overflow(runs[i].dst, runs[i].n, &dend) || (runs[i].n && !runs[i].dst)) {
+            g_last_error = "flacgpu_place_frames: run " + std::to_string(i) + " reaches past the packed frames, or has no destination";
+            return FLACGPU_ERR_INVALID_ARG;
+        }
+    }
+    if (!n_runs) return FLACGPU_OK;
+    CTX_GUARD(c);
+    hipStream_t st = ctx_stream(c);
+    if (!c->ev_place) HIP_TRY(hipEventCreateWithFlags(&c->ev_place, hipEventDisableTiming));
+    if (c->place_pending) HIP_TRY(hipEventSynchronize(c->ev_place));   // the call before has run: both tables are free again
+    c->place_pending = false;
+    if (n_runs > c->runs_cap) {   // (grown rarely: the tables are kept between calls)
+        HIP_TRY(hipStreamSynchronize(st));
+        if (c->h_runs) (void)hipHostFree(c->h_runs);
+        (void)hipFree(c->d_runs);
+        c->h_runs = c->d_runs = nullptr;
+        c->runs_cap = 0;
+        const size_t cap = std::max<size_t>(64, (size_t)n_runs + n_runs / 2);
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->h_runs), sizeof(PlaceRun) * cap, hipHostMallocDefault));
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->d_runs), sizeof(PlaceRun) * cap));
+        c->runs_cap = (uint32_t)std::min<size_t>(cap, 0xFFFFFFFFu);
+    }
+    const uint64_t groups = place_table(runs, n_runs, reinterpret_cast<uintptr_t>(c->d_packed), 0, c->h_runs);
+    HIP_TRY(hipMemcpyAsync(c->d_runs, c->h_runs, sizeof(PlaceRun) * (size_t)n_runs, hipMemcpyHostToDevice, st));
+    c->drained = false;
+    if (int rc = launch_place_runs(c->d_runs, n_runs, groups, st)) return rc;
+    HIP_TRY(hipEventRecord(c->ev_place, st));
+    c->place_pending = true;
     return FLACGPU_OK;
 }
 

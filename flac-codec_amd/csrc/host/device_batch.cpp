@@ -1,6 +1,9 @@
 // device_batch.cpp -- flacenc_encode_many_device: a batch of streams of one shape held in DEVICE memory (int32, int16, packed
 // 24-bit or float32; planar and padded, or interleaved and flat) -> finished .flac files in the callers' host buffers, the samples
-// never visiting the host.  The mirror image of flacgpu_decoder_decode_as.
+// never visiting the host.  The mirror image of flacgpu_decoder_decode_as.  flacenc_encode_many_device_out is the same loop
+// (encode_impl, below) with the files left in DEVICE memory, in slots of one buffer of the caller's: there a retired batch's
+// frames are not fetched but placed by k_place_runs (flacgpu_frame_offsets + flacgpu_place_frames) beside the next batch's
+// analysis, and the headers, built on the host, go up in one copy and to their places in one launch (flacgpu_ingest_place).
 //
 //   * plan (pure host code): the checks, the elements the tensor must hold, the staging bytes;
 //   * ingest (ingest.hip, kernels/ingest.inc): one kernel pass converts the tensor by ingest_sample (kernels/ingest_rule.h)
@@ -23,6 +26,7 @@
 #include <mutex>
 #include <numeric>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../kernels/ingest_rule.h"
@@ -84,9 +88,10 @@ int refuse(int rc, const std::string &why) {
     return rc;
 }
 
-// The checks of plan / encode; staging_off (may be null) receives every stream's first int32 in the staging buffer.
+// The checks of plan / encode (Job: flacenc_device_job or flacenc_device_out_job); staging_off (may be null) receives every stream's first int32 in the staging buffer.
+template <class Job>
 int plan_impl(const flacenc_options *o, const flacenc_tensor_format *fmt, uint32_t bps, uint32_t channels,
-              const flacenc_device_job *jobs, size_t n_jobs, uint64_t *in_elements, uint64_t *staging_elements,
+              const Job *jobs, size_t n_jobs, uint64_t *in_elements, uint64_t *staging_elements,
               std::vector<uint64_t> *staging_off) {
     if (!o || !fmt || (!jobs && n_jobs)) return refuse(FLACENC_ERR_INVALID_ARG, "a null argument");
     if (int e = options_error(*o)) return e;
@@ -144,7 +149,10 @@ struct Stream {
     size_t hlen = 0;                // bytes in front of the first frame
     uint64_t pos = 0;               // bytes of the frames placed so far
     std::vector<uint32_t> sizes;    // per frame
-    std::vector<uint8_t> tail_bytes;
+    std::vector<uint8_t> tail_bytes;   // host output: the short last block's frame until the header is written
+    size_t tail_len = 0;               // its size
+    bool tail_done = false;            // ... is known
+    bool tail_placed = false;          // device output: it is in its place
 };
 struct CopyJob {
     const uint8_t *src;
@@ -163,6 +171,39 @@ void run_copies(const std::vector<CopyJob> &cj) {
     const unsigned helpers = (unsigned)std::min<size_t>({bytes >> 20, cj.size() ? cj.size() - 1 : 0, (size_t)std::min(usable_cpus(), 8u) - 1});
     run_parallel(helpers, work);
 }
+
+// where a stream's file begins: a host address (flacenc_device_job) or a device address (flacenc_device_out_job: never
+// dereferenced here)
+inline bool has_place(const flacenc_device_job &j) { return j.out != nullptr; }
+inline bool has_place(const flacenc_device_out_job &) { return true; }
+inline uint8_t *place_of(const flacenc_device_job &j, uint8_t *) { return j.out; }
+inline uint8_t *place_of(const flacenc_device_out_job &j, uint8_t *d_out) { return d_out + j.out_offset; }
+inline uint64_t address(const uint8_t *p) { return (uint64_t)reinterpret_cast<uintptr_t>(p); }
+
+// The slots of flacenc_device_out_plan: every one inside [0, d_out_bytes), no two with bytes overlapping.
+int slots_error(const flacenc_device_out_job *jobs, size_t n_jobs, size_t d_out_bytes) {
+    const auto refuse_slot = [](const std::string &why) {
+        set_last_error("flacenc_device_out_plan: " + why);
+        return FLACENC_ERR_INVALID_ARG;
+    };
+    std::vector<std::pair<uint64_t, uint64_t>> spans;   // [first byte, end) of every slot that holds bytes
+    for (size_t i = 0; i < n_jobs; i++) {
+        uint64_t end = 0;
+        if (__builtin_add_overflow(jobs[i].out_offset, jobs[i].out_cap, &end))
+            return refuse_slot("stream " + std::to_string(i) + ": out_offset + out_cap overflows");
+        if (end > d_out_bytes) return refuse_slot("stream " + std::to_string(i) + ": its slot reaches past d_out_bytes");
+        if (jobs[i].out_cap) spans.emplace_back(jobs[i].out_offset, end);
+    }
+    std::sort(spans.begin(), spans.end());
+    for (size_t k = 1; k < spans.size(); k++)
+        if (spans[k].first < spans[k - 1].second) return refuse_slot("two slots overlap");
+    return 0;
+}
+
+template <class Job>
+int encode_impl(const flacenc_options *opts, const void *d_pcm, const flacenc_tensor_format *fmt, uint32_t sample_rate,
+                uint32_t bits_per_sample, uint32_t channels, Job *jobs, size_t n_jobs, uint8_t *d_out, uint32_t flags,
+                void *stream, const std::vector<uint64_t> &staging_off, uint64_t staging_elements);
 
 }  // namespace
 
@@ -204,6 +245,51 @@ int flacenc_encode_many_device(const flacenc_options *opts, const void *d_pcm, c
         set_last_error("flacenc_encode_many_device: unknown flags, no tensor, or a tensor not aligned to its element size");
         return FLACENC_ERR_INVALID_ARG;
     }
+    return encode_impl(opts, d_pcm, fmt, sample_rate, bits_per_sample, channels, jobs, n_jobs, nullptr, flags, stream, staging_off,
+                       staging_elements);
+}
+
+int flacenc_device_out_plan(const flacenc_options *opts, const flacenc_tensor_format *fmt, uint32_t bits_per_sample,
+                            uint32_t channels, const flacenc_device_out_job *jobs, size_t n_jobs, size_t d_out_bytes,
+                            size_t *in_elements, size_t *staging_bytes) {
+    uint64_t in = 0, st = 0;
+    if (int rc = plan_impl(opts, fmt, bits_per_sample, channels, jobs, n_jobs, &in, &st, nullptr)) return rc;
+    if (int rc = slots_error(jobs, n_jobs, d_out_bytes)) return rc;
+    if (in_elements) *in_elements = (size_t)in;
+    if (staging_bytes) *staging_bytes = (size_t)(4 * st);
+    return 0;
+}
+
+int flacenc_encode_many_device_out(const flacenc_options *opts, const void *d_pcm, const flacenc_tensor_format *fmt,
+                                   uint32_t sample_rate, uint32_t bits_per_sample, uint32_t channels,
+                                   flacenc_device_out_job *jobs, size_t n_jobs, void *d_out, size_t d_out_bytes, uint32_t flags,
+                                   void *stream) {
+    uint64_t in_elements = 0, staging_elements = 0;
+    std::vector<uint64_t> staging_off;
+    if (int rc = plan_impl(opts, fmt, bits_per_sample, channels, jobs, n_jobs, &in_elements, &staging_elements, &staging_off))
+        return rc;
+    if (int rc = slots_error(jobs, n_jobs, d_out_bytes)) return rc;
+    if ((flags & ~FLACENC_DEVICE_NO_MD5) || (in_elements && !d_pcm) || (d_out_bytes && !d_out) ||
+        reinterpret_cast<uintptr_t>(d_pcm) % sample_type_align(fmt->dtype)) {
+        set_last_error("flacenc_encode_many_device_out: unknown flags, no tensor, no output buffer, or a tensor not aligned to its "
+                       "element size");
+        return FLACENC_ERR_INVALID_ARG;
+    }
+    return encode_impl(opts, d_pcm, fmt, sample_rate, bits_per_sample, channels, jobs, n_jobs, static_cast<uint8_t *>(d_out), flags,
+                       stream, staging_off, staging_elements);
+}
+
+}  // extern "C"
+
+namespace {
+
+// The loop of both entry points, behind their checks.  Job = flacenc_device_job: every file to jobs[i].out in host memory.
+// Job = flacenc_device_out_job: every file to d_out + jobs[i].out_offset in device memory.
+template <class Job>
+int encode_impl(const flacenc_options *opts, const void *d_pcm, const flacenc_tensor_format *fmt, uint32_t sample_rate,
+                uint32_t bits_per_sample, uint32_t channels, Job *jobs, size_t n_jobs, uint8_t *d_out, uint32_t flags,
+                void *stream, const std::vector<uint64_t> &staging_off, uint64_t staging_elements) {
+    constexpr bool kDeviceOut = std::is_same<Job, flacenc_device_out_job>::value;
     const flacenc_options &o = *opts;
     const uint32_t B = o.block_size, ch = channels, bps = bits_per_sample;
     const size_t per = (size_t)B * ch;
@@ -215,12 +301,12 @@ int flacenc_encode_many_device(const flacenc_options *opts, const void *d_pcm, c
     std::vector<Stream> st(n_jobs);
     std::map<uint64_t, std::pair<int, size_t>> header_memo;   // (streams of one length share their header's size)
     for (size_t i = 0; i < n_jobs; i++) {
-        flacenc_device_job &j = jobs[i];
+        Job &j = jobs[i];
         j.out_len = 0;
         j.status = 0;
         j.altered = 0;
         std::memset(j.md5, 0, 16);
-        if (!j.samples || !j.out) {
+        if (!j.samples || !has_place(j)) {
             j.status = FLACENC_ERR_INVALID_ARG;
             continue;
         }
@@ -294,6 +380,7 @@ int flacenc_encode_many_device(const flacenc_options *opts, const void *d_pcm, c
         };
         std::vector<uint64_t> off;
         std::vector<CopyJob> cj;
+        std::vector<flacgpu_place_run> runs;
         int rc = whole_rc ? FLACGPU_ERR_HIP : submit(0);
         for (size_t b = 0; b < batches.size() && !rc; b++) {
             if (b + 1 < batches.size()) rc = submit(b + 1);   // its kernels run while batch b's frames are fetched
@@ -303,21 +390,29 @@ int flacenc_encode_many_device(const flacenc_options *opts, const void *d_pcm, c
             for (const PlanSeg &p : batches[b]) frames += p.n;
             off.assign((size_t)frames + 1, 0);
             uint64_t total = 0;
-            rc = flacgpu_fetch_frames(s.ctx, s.out, s.out_cap, off.data(), &total);
+            // host output: the frames cross the link; device output: only their sizes do
+            rc = kDeviceOut ? flacgpu_frame_offsets(s.ctx, off.data(), &total)
+                            : flacgpu_fetch_frames(s.ctx, s.out, s.out_cap, off.data(), &total);
             if (rc) break;
             cj.clear();
+            runs.clear();
             uint32_t f = 0;
             for (const PlanSeg &p : batches[b]) {
                 Stream &sm = st[p.stream];
-                flacenc_device_job &j = jobs[p.stream];
+                Job &j = jobs[p.stream];
                 const uint64_t bytes = off[f + p.n] - off[f];
                 for (uint32_t k = 0; k < p.n; k++) sm.sizes[p.first + k] = (uint32_t)(off[f + k + 1] - off[f + k]);
+                uint8_t *const to = place_of(j, d_out) + sm.hlen + sm.pos;
                 if (sm.hlen + sm.pos + bytes > j.out_cap) fail(p.stream, FLACENC_ERR_IO);
-                else if (!j.status) cj.push_back(CopyJob{s.out + off[f], j.out + sm.hlen + sm.pos, (size_t)bytes});
+                else if (j.status) ;
+                else if (kDeviceOut) runs.push_back(flacgpu_place_run{off[f], address(to), bytes});
+                else cj.push_back(CopyJob{s.out + off[f], to, (size_t)bytes});
                 sm.pos += bytes;
                 f += p.n;
             }
-            run_copies(cj);
+            // (device output: the kernel runs on this context's stream, beside batch b + 1's analysis on the other's)
+            if (kDeviceOut) rc = flacgpu_place_frames(s.ctx, runs.data(), (uint32_t)runs.size());
+            else run_copies(cj);
         }
         if (rc && !whole_rc) whole_rc = gpu_error(rc);
         for (size_t k = 0; k < have; k++) {
@@ -352,10 +447,18 @@ int flacenc_encode_many_device(const flacenc_options *opts, const void *d_pcm, c
             const PooledContext &s = slot[t % 2];
             Stream &sm = st[tails[t]];
             uint64_t total = 0, off2[2] = {0, 0};
-            rc = flacgpu_fetch_frames(s.ctx, s.out, s.out_cap, off2, &total);
+            rc = kDeviceOut ? flacgpu_frame_offsets(s.ctx, off2, &total) : flacgpu_fetch_frames(s.ctx, s.out, s.out_cap, off2, &total);
             if (rc) break;
             sm.sizes[sm.whole] = (uint32_t)total;
-            sm.tail_bytes.assign(s.out, s.out + total);
+            sm.tail_len = (size_t)total;
+            sm.tail_done = true;
+            if (!kDeviceOut) {
+                sm.tail_bytes.assign(s.out, s.out + total);
+            } else if (sm.hlen + sm.pos + total <= jobs[tails[t]].out_cap) {   // (else: FLACENC_ERR_IO where the header is built)
+                const flacgpu_place_run run{0, address(place_of(jobs[tails[t]], d_out) + sm.hlen + sm.pos), total};
+                rc = flacgpu_place_frames(s.ctx, &run, 1);
+                sm.tail_placed = !rc;
+            }
         }
         const int tail_rc = rc ? gpu_error(rc) : 0;
         for (size_t k = 0; k < have; k++) {
@@ -364,34 +467,59 @@ int flacenc_encode_many_device(const flacenc_options *opts, const void *d_pcm, c
         }
         if (tail_rc)
             for (size_t i : tails)
-                if (st[i].tail_bytes.empty()) fail(i, tail_rc);
+                if (!st[i].tail_done || (kDeviceOut && !st[i].tail_placed && !jobs[i].status)) fail(i, tail_rc);
     }
 
     // ---- the digests, then every stream's metadata and its last frame
     std::vector<uint32_t> altered(n_jobs);
     std::vector<uint8_t> digests(16 * n_jobs, 0);
     if (int rc = flacgpu_ingest_finish(ing, altered.data(), md5 ? digests.data() : nullptr)) return fail_all(gpu_error(rc));
+    // device output: the headers are built one behind another in a pinned buffer of the ingest handle's
+    uint8_t *headers = nullptr;
+    size_t headers_len = 0;
+    std::vector<flacgpu_place_run> header_runs;
+    if (kDeviceOut) {
+        size_t sum = 0;
+        for (size_t i = 0; i < n_jobs; i++)
+            if (!jobs[i].status) sum += st[i].hlen;
+        if (int rc = flacgpu_ingest_scratch(ing, sum, &headers)) return fail_all(gpu_error(rc));
+    }
     for (size_t i = 0; i < n_jobs; i++) {
-        flacenc_device_job &j = jobs[i];
+        Job &j = jobs[i];
         j.altered = altered[i];
         std::memcpy(j.md5, &digests[16 * i], 16);
         if (j.status) continue;
         Stream &s = st[i];
         size_t hlen = 0;
         const uint32_t last_len = s.tail ? s.tail : B;
+        uint8_t *const to = place_of(j, d_out);
         int rc = flacenc_stream_header(&o, sample_rate, bps, ch, j.samples, j.md5, s.sizes.size(), s.sizes.data(), last_len,
-                                       j.out, j.out_cap, &hlen);
+                                       kDeviceOut ? headers + headers_len : to, kDeviceOut ? s.hlen : (size_t)j.out_cap, &hlen);
         if (!rc && hlen != s.hlen) rc = FLACENC_ERR_IO;   // (cannot happen: the header's size is fixed at `new`)
-        if (rc || s.hlen + s.pos + s.tail_bytes.size() > j.out_cap) {
+        if (rc || s.hlen + s.pos + s.tail_len > j.out_cap) {
             fail(i, rc && rc != FLACENC_ERR_INVALID_ARG ? rc : FLACENC_ERR_IO);
             continue;
         }
-        if (!s.tail_bytes.empty()) std::memcpy(j.out + s.hlen + s.pos, s.tail_bytes.data(), s.tail_bytes.size());
-        j.out_len = s.hlen + s.pos + s.tail_bytes.size();
+        if (kDeviceOut) {
+            header_runs.push_back(flacgpu_place_run{headers_len, address(to), s.hlen});
+            headers_len += s.hlen;
+        } else if (s.tail_len) {
+            std::memcpy(to + s.hlen + s.pos, s.tail_bytes.data(), s.tail_len);
+        }
+        j.out_len = s.hlen + s.pos + s.tail_len;
     }
+    if (kDeviceOut)   // one upload, one launch, and the handle's stream waited for: the files are complete
+        if (int rc = flacgpu_ingest_place(ing, headers_len, header_runs.data(), (uint32_t)header_runs.size())) {
+            const int e = gpu_error(rc);
+            for (size_t i = 0; i < n_jobs; i++)
+                if (!jobs[i].status) {
+                    jobs[i].status = e;
+                    jobs[i].out_len = 0;
+                }
+        }
     for (size_t i = 0; i < n_jobs; i++)
         if (jobs[i].status) return jobs[i].status;
     return 0;
 }
 
-}  // extern "C"
+}  // namespace

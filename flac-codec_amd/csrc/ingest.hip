@@ -4,6 +4,7 @@
 // One of the translation units of libflacenc_amd.so (gfx950 only).
 #include "kernels/types.h"
 #include "kernels/ingest_rule.h"
+#include "kernels/place_rule.h"
 #include "kernels/sample_types.h"
 
 #include <string.h>
@@ -48,6 +49,9 @@ struct flacgpu_ingest {
     hipEvent_t ev = nullptr;
     GrowBuf<false> staging, streams, altered, jobs, digest;
     GrowBuf<true> table, results;   // pinned: the tables on their way up, altered counts and digests on their way down
+    // flacgpu_ingest_place: the callers' pieces and the run table, pinned and on the device
+    GrowBuf<true> piece_host, run_host;
+    GrowBuf<false> piece_dev, run_dev;
     uint32_t n = 0;
     bool md5 = false, pending = false;
 };
@@ -200,5 +204,38 @@ int flacgpu_ingest_finish(flacgpu_ingest *g, uint32_t *altered, uint8_t *md5) {
         if (altered) altered[i] = res[i];
         if (md5 && g->md5) memcpy(md5 + 16 * (size_t)i, res + g->n + 5 * (size_t)i, 16);
     }
+    return FLACGPU_OK;
+}
+
+int flacgpu_ingest_scratch(flacgpu_ingest *g, size_t bytes, uint8_t **pinned) {
+    if (!g || !pinned) return FLACGPU_ERR_INVALID_ARG;
+    DeviceGuard guard(g->device);
+    if (int rc = g->piece_host.ensure(std::max<size_t>(bytes, 64))) return rc;
+    *pinned = g->piece_host.as<uint8_t>();
+    return FLACGPU_OK;
+}
+
+int flacgpu_ingest_place(flacgpu_ingest *g, size_t bytes, const flacgpu_place_run *runs, uint32_t n_runs) {
+    if (!g || (n_runs && !runs) || bytes > g->piece_host.cap) return FLACGPU_ERR_INVALID_ARG;
+    for (uint32_t i = 0; i < n_runs; i++) {
+        uint64_t end = 0, dend = 0;
+        if (__builtin_add_overflow(runs[i].src, runs[i].n, &end) || end > bytes ||
+            __builtin_add_overflow(runs[i].dst, runs[i].n, &dend) || (runs[i].n && !runs[i].dst)) {
+            g_last_error = "flacgpu_ingest_place: run " + std::to_string(i) + " reaches past the uploaded bytes, or has no destination";
+            return FLACGPU_ERR_INVALID_ARG;
+        }
+    }
+    if (!n_runs) return FLACGPU_OK;
+    DeviceGuard guard(g->device);
+    // (a 16-byte group that holds a byte of the scratch must lie inside the allocation: hipMalloc's alignment, and 16 spare)
+    if (int rc = g->piece_dev.ensure(std::max<size_t>(bytes + 16, 64))) return rc;
+    if (int rc = g->run_host.ensure(sizeof(PlaceRun) * (size_t)n_runs)) return rc;
+    if (int rc = g->run_dev.ensure(sizeof(PlaceRun) * (size_t)n_runs)) return rc;
+    PlaceRun *tab = g->run_host.as<PlaceRun>();
+    const uint64_t groups = place_table(runs, n_runs, reinterpret_cast<uintptr_t>(g->piece_dev.p), 0, tab);
+    HIP_TRY(hipMemcpyAsync(g->piece_dev.p, g->piece_host.p, bytes, hipMemcpyHostToDevice, g->st));
+    HIP_TRY(hipMemcpyAsync(g->run_dev.p, tab, sizeof(PlaceRun) * (size_t)n_runs, hipMemcpyHostToDevice, g->st));
+    if (int rc = flacgpu_k::launch_place_runs(g->run_dev.as<const PlaceRun>(), n_runs, groups, g->st)) return rc;
+    HIP_TRY(hipStreamSynchronize(g->st));
     return FLACGPU_OK;
 }

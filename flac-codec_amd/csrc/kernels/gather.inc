@@ -1,6 +1,6 @@
 // gather.inc -- the batch decoder's second front door (DESIGN.md 4b "Device-resident input"): streams that already lie
 // in device memory.  Included inside decode_many.hip's anonymous namespace, after frame_scan.inc (ScanSlot,
-// slot_of_block) and kernels/meta_walk.h.  Three kernels, none with LDS, atomics or scratch:
+// slot_of_block), kernels/meta_walk.h and kernels/byte_shift.h.  Three kernels, none with LDS, atomics or scratch:
 //   K_g1 k_meta_walk     lane per stream: the metadata chain of a regular stream, walked where it lies (meta_walk)
 //   K_g2 k_gather_slots  lane per 16-byte group of the batch buffer: builds the slots from the sources, zero tails and
 //                        look-ahead included -- the device's stand-in for the host door's staging copy and upload
@@ -20,28 +20,7 @@ __global__ void __launch_bounds__(64) k_meta_walk(const DevSource *__restrict__ 
     meta_walk(src[i].data, src[i].len, out[i]);
 }
 
-// 16 bytes, as four little-endian dwords, from the eight dwords w at byte offset a (< 16)
-__device__ __forceinline__ uint32_t pick4(uint32_t q, uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3) {
-    return q == 0 ? w0 : q == 1 ? w1 : q == 2 ? w2 : w3;
-}
-// the 16 bytes at byte offset a (< 16) of the 32 bytes lo, hi, as four little-endian dwords.  Dword q + k is taken by
-// selects and the odd bytes by v_alignbyte: no register is indexed by a lane's value, so nothing goes to scratch.
-__device__ __forceinline__ uint4 shift_group(const uint4 lo, const uint4 hi, uint32_t a) {
-    const uint32_t q = a >> 2, r = a & 3u;
-    const uint32_t t0 = pick4(q, lo.x, lo.y, lo.z, lo.w), t1 = pick4(q, lo.y, lo.z, lo.w, hi.x);
-    const uint32_t t2 = pick4(q, lo.z, lo.w, hi.x, hi.y), t3 = pick4(q, lo.w, hi.x, hi.y, hi.z);
-    const uint32_t t4 = pick4(q, hi.x, hi.y, hi.z, hi.w);
-    uint4 v;
-    v.x = __builtin_amdgcn_alignbyte(t1, t0, r);
-    v.y = __builtin_amdgcn_alignbyte(t2, t1, r);
-    v.z = __builtin_amdgcn_alignbyte(t3, t2, r);
-    v.w = __builtin_amdgcn_alignbyte(t4, t3, r);
-    return v;
-}
-// the low `keep` (0 .. 4) bytes of a dword
-__device__ __forceinline__ uint32_t keep_bytes(uint32_t v, int64_t keep) {
-    return keep >= 4 ? v : keep <= 0 ? 0u : v & ((1u << (8 * (uint32_t)keep)) - 1u);
-}
+// pick4, shift_group, keep_bytes: kernels/byte_shift.h (shared with k_place_runs)
 
 // K_g2: lane per destination 16-byte group; consecutive lanes store consecutive groups, one uint4 each.  `src[s]` is
 // the first byte of slot s's region in the caller's memory.  Every byte of the n_groups groups is written: the region's

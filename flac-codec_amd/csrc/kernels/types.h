@@ -253,4 +253,10 @@ struct Md5JobRec {
 };
 void launch_md5_many(const int32_t *samples, const Md5JobRec *jobs, uint32_t n_jobs, uint32_t *digest, hipStream_t st);
 }  // namespace flacgpu_k
+// place.hip: k_place_runs over a table that place_table (kernels/place_rule.h) built, already in device memory; n_groups
+// is place_table's return value (0: nothing is launched).  FLACGPU_OK, or an error with g_last_error set.
+struct PlaceRun;
+namespace flacgpu_k {
+int launch_place_runs(const PlaceRun *d_runs, uint32_t n_runs, uint64_t n_groups, hipStream_t st);
+}  // namespace flacgpu_k
 #endif

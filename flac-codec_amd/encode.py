@@ -192,6 +192,12 @@ def _stream_lib():
                                                 C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
         L.flacenc_encode_many_device.argtypes = [po, vp, pf, C.c_uint32, C.c_uint32, C.c_uint32,
                                                  C.POINTER(_lib.DeviceJob), C.c_size_t, C.c_uint32, vp]
+        L.flacenc_device_out_plan.argtypes = [po, pf, C.c_uint32, C.c_uint32, C.POINTER(_lib.DeviceOutJob), C.c_size_t,
+                                              C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+        L.flacenc_encode_many_device_out.argtypes = [po, vp, pf, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                     C.POINTER(_lib.DeviceOutJob), C.c_size_t, vp, C.c_size_t, C.c_uint32, vp]
+        L.flacgpu_place_runs_host.argtypes = [C.POINTER(_lib.PlaceRun), C.c_uint32]
+        L.flacgpu_place_workgroup.restype = C.c_uint32
         L.flacenc_ingest_sample.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int)]
         L.flacenc_ingest_sample.restype = C.c_int32
         L.flacenc_worst_case_bytes.restype = C.c_size_t
@@ -580,6 +586,7 @@ class BatchEncoder:
         batches (flacenc_encode_many_coalesced: many SMALL streams)."""
         self._opts, self._threads, self._devices, self._coalesce = options, threads, devices, coalesce
         self._bufs = []
+        self._shard = None   # encode_device(out="device"): the reused device buffer of the files
 
     def prepare(self, streams, sample_rate, bits_per_sample, channels):
         """The job array of a call (what a C caller would hold): arrays pinned in a handle, output buffers sized for the
@@ -633,12 +640,9 @@ class BatchEncoder:
         self.run(h)
         return self.results(h, copy)
 
-    def prepare_device(self, tensor, lengths, bits_per_sample, dtype=None, offsets=None, channels=None):
-        """The job array of an encode_device call: a [B, C, T] tensor is a PADDED batch of B streams of C channels,
-        stream i of lengths[i] (default T) samples; with `offsets` the tensor is FLAT, stream i interleaved from element
-        offsets[i].  dtype="int24": uint8 with a trailing axis of 3.  Output buffers sized for the worst case and reused
-        by later calls."""
-        L = _stream_lib()
+    @staticmethod
+    def _device_batch(tensor, lengths, dtype, offsets, channels):
+        """What an encode_device call's tensor holds: (streams, offsets, lengths, channels, format)."""
         if dtype not in (None, "int24"):
             raise ValueError("dtype must be None (the tensor's own: int16, int32 or float32) or 'int24'")
         if not tensor.is_contiguous() or not tensor.is_cuda:
@@ -671,6 +675,15 @@ class BatchEncoder:
             fmt = _lib.OutFormat(code, _lib.LAYOUT_FLAT, 0, 0, 0)
         if len(lengths) != n:
             raise ValueError("one length per stream")
+        return n, offsets, lengths, channels, fmt
+
+    def prepare_device(self, tensor, lengths, bits_per_sample, dtype=None, offsets=None, channels=None):
+        """The job array of an encode_device call: a [B, C, T] tensor is a PADDED batch of B streams of C channels,
+        stream i of lengths[i] (default T) samples; with `offsets` the tensor is FLAT, stream i interleaved from element
+        offsets[i].  dtype="int24": uint8 with a trailing axis of 3.  Output buffers sized for the worst case and reused
+        by later calls."""
+        L = _stream_lib()
+        n, offsets, lengths, channels, fmt = self._device_batch(tensor, lengths, dtype, offsets, channels)
         jobs = (_lib.DeviceJob * max(n, 1))()
         co = self._opts._c_options()
         for i, samples in enumerate(lengths):
@@ -700,8 +713,57 @@ class BatchEncoder:
                                             sample_rate, bits_per_sample, channels, jobs, n,
                                             0 if verify_md5 else _lib.DEVICE_NO_MD5, stream or None)
 
+    def prepare_device_out(self, tensor, lengths, bits_per_sample, dtype=None, offsets=None, channels=None, shard=None,
+                           slots=None):
+        """The job array of an encode_device(out="device") call (the tensor as in prepare_device) and the device buffer
+        the files go to.  Without `slots`: a torch.uint8 shard of this encoder's on the tensor's device, reused by later
+        calls, with one slot of flacenc_worst_case_bytes per stream, one behind another.  slots=[(offset, cap), ...]
+        with shard= (a contiguous 1-D uint8 tensor on the tensor's device): the caller's buffer and slots."""
+        import torch
+
+        L = _stream_lib()
+        n, offsets, lengths, channels, fmt = self._device_batch(tensor, lengths, dtype, offsets, channels)
+        co = self._opts._c_options()
+        if slots is None:
+            if shard is not None:
+                raise ValueError("shard= goes with slots=")
+            slots, total = [], 0
+            for samples in lengths:
+                cap = int(L.flacenc_worst_case_bytes(C.byref(co), bits_per_sample, max(channels, 1), samples))
+                slots.append((total, cap))
+                total += cap
+            if self._shard is None or self._shard.device != tensor.device or self._shard.numel() < total:
+                self._shard = torch.empty(max(total, 1), dtype=torch.uint8, device=tensor.device)
+            shard = self._shard
+        else:
+            if (shard is None or not shard.is_cuda or shard.device != tensor.device or shard.dtype != torch.uint8
+                    or shard.dim() != 1 or not shard.is_contiguous()):
+                raise ValueError("slots= takes shard=, a contiguous 1-D uint8 tensor on the tensor's device")
+            slots = [(int(o), int(c)) for o, c in slots]
+            if len(slots) != n or any(o < 0 or c < 0 for o, c in slots):
+                raise ValueError("one (offset, cap) slot per stream")
+        jobs = (_lib.DeviceOutJob * max(n, 1))()
+        for i in range(n):
+            jobs[i].in_offset, jobs[i].samples = offsets[i], lengths[i]
+            jobs[i].out_offset, jobs[i].out_cap = slots[i]
+        return (jobs, n, co, fmt, channels, shard)
+
+    def run_device_out(self, handle, tensor, sample_rate, bits_per_sample, verify_md5=True, stream=None):
+        """One call of flacenc_encode_many_device_out on a prepared job array; returns its return code, as run_device."""
+        import torch
+
+        L = _stream_lib()
+        jobs, n, co, fmt, channels, shard = handle
+        if stream is None:
+            stream = torch.cuda.current_stream(tensor.device).cuda_stream
+        if co.device < 0:
+            co.device = tensor.device.index
+        return L.flacenc_encode_many_device_out(C.byref(co), tensor.data_ptr() if tensor.numel() else None, C.byref(fmt),
+                                                sample_rate, bits_per_sample, channels, jobs, n, shard.data_ptr(),
+                                                shard.numel(), 0 if verify_md5 else _lib.DEVICE_NO_MD5, stream or None)
+
     def encode_device(self, tensor, lengths=None, sample_rate=44100, bits_per_sample=16, verify_md5=True, copy=True,
-                      dtype=None, offsets=None, channels=None):
+                      dtype=None, offsets=None, channels=None, out="host", shard=None, slots=None):
         """A batch of streams held on the GPU -> .flac bytes, the samples never visiting the host
         (flacenc_encode_many_device).  tensor: contiguous [B, C, T] torch tensor on the GPU, int16 (x >> (16 - bps)),
         int32 (clamped to bps bits) or float32 (x * 2^(bps - 1), rounded to nearest even, clamped; NaN -> 0); with
@@ -711,13 +773,29 @@ class BatchEncoder:
         and stream i is [lengths[i]][channels] interleaved from element offsets[i]; what lies between is never read.
         Runs behind the work queued on the tensor's current torch stream and returns when the files are complete.  verify_md5=False leaves STREAMINFO's MD5 zero
         ("unknown") and skips the hash kernel.  self.last_altered: per stream, the elements that were clamped, NaN or
-        (int16, int24) lost non-zero low bits; self.last_md5: the digests."""
-        h = self.prepare_device(tensor, lengths, bits_per_sample, dtype, offsets, channels)
-        rc = self.run_device(h, tensor, sample_rate, bits_per_sample, verify_md5)
+        (int16, int24) lost non-zero low bits; self.last_md5: the digests; self.last_status: every stream's status.
+        out="device" (flacenc_encode_many_device_out): the files stay on the GPU, in one uint8 shard tensor of this
+        encoder's that later calls reuse (so the views of one call are valid until the next) -- one worst-case slot per
+        stream, one behind another -- and the call returns the list of 1-D views shard[o : o + out_len], which
+        Decoder.scan and decode_many take as they are; only frame sizes, digests and headers cross the link.
+        slots=[(offset, cap), ...] with shard= puts the files into the caller's own uint8 tensor instead: no byte
+        outside [offset, offset + out_len) of a stream is written."""
+        if out not in ("host", "device"):
+            raise ValueError("out must be 'host' or 'device'")
+        if out == "host":
+            if shard is not None or slots is not None:
+                raise ValueError("shard= and slots= go with out='device'")
+            h = self.prepare_device(tensor, lengths, bits_per_sample, dtype, offsets, channels)
+            rc = self.run_device(h, tensor, sample_rate, bits_per_sample, verify_md5)
+        else:
+            h = self.prepare_device_out(tensor, lengths, bits_per_sample, dtype, offsets, channels, shard, slots)
+            rc = self.run_device_out(h, tensor, sample_rate, bits_per_sample, verify_md5)
         jobs, n = h[0], h[1]
         self.last_altered = [int(jobs[i].altered) for i in range(n)]
         self.last_status = [int(jobs[i].status) for i in range(n)]
         self.last_md5 = [bytes(jobs[i].md5) for i in range(n)]
         _check(rc)
+        if out == "device":
+            return [h[5][int(jobs[i].out_offset): int(jobs[i].out_offset) + int(jobs[i].out_len)] for i in range(n)]
         views = [self._bufs[i][: jobs[i].out_len] for i in range(n)]
         return [v.tobytes() for v in views] if copy else views

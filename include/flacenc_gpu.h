@@ -266,6 +266,29 @@ int flacgpu_encode_device(flacgpu_ctx *ctx, const int32_t *d_pcm, int layout, ui
  * FLACGPU_ERR_BUFFER_TOO_SMALL is returned. */
 int flacgpu_fetch_frames(flacgpu_ctx *ctx, uint8_t *out, size_t cap, uint64_t *offsets,
                          uint64_t *total);
+/* ---- frames that stay on the device (DESIGN.md 4c "Device-resident output") ----
+ * flacgpu_frame_offsets: flacgpu_fetch_frames without the frame bytes.  Waits for the context's stream, re-decides what
+ * flacgpu_resolve re-decides, and downloads the n_frames + 1 byte offsets of the packed frames (offsets, may be NULL;
+ * *total, may be NULL, = offsets[n_frames]).  Synchronous.
+ * flacgpu_place_frames: copies runs of the packed frame bytes to places in device memory, on the context's own stream
+ * (k_place_runs: csrc/kernels/place_rule.h).  Run i takes the n bytes at byte `src` of the packed buffer
+ * (flacgpu_device_buffer 4) to the device address `dst`; src, dst and n have any alignment, n may be 0.  Exactly the bytes
+ * [dst, dst + n) are written; runs of one call must not overlap in their destinations.  Asynchronous: stream order
+ * makes the copy finish before the context's next batch overwrites the packed buffer, and flacgpu_wait waits for it.
+ * FLACGPU_ERR_INVALID_ARG (nothing is launched) when nothing is packed, the frames were assembled into a host buffer,
+ * or a run reaches past the packed bytes.  The run table travels through buffers the context keeps between calls. */
+typedef struct {
+    uint64_t src;   /* flacgpu_place_frames: byte offset into the packed buffer; flacgpu_place_runs_host: an address */
+    uint64_t dst;   /* an address */
+    uint64_t n;     /* bytes */
+} flacgpu_place_run;
+int flacgpu_frame_offsets(flacgpu_ctx *ctx, uint64_t *offsets, uint64_t *total);
+int flacgpu_place_frames(flacgpu_ctx *ctx, const flacgpu_place_run *runs, uint32_t n_runs);
+/* The copy rule of k_place_runs run over HOST memory, one destination group after another in the kernel's lane order: a
+ * test hook (no device is touched).  src and dst are host addresses.  flacgpu_place_workgroup: the kernel's lanes per
+ * workgroup. */
+int flacgpu_place_runs_host(const flacgpu_place_run *runs, uint32_t n_runs);
+uint32_t flacgpu_place_workgroup(void);
 /* analyze + pack + fetch in one synchronous call on host PCM: the whole of the reference's
  * `Encoder::encode` loop for a batch of blocks, minus stream bookkeeping. */
 int flacgpu_encode_frames(flacgpu_ctx *ctx, const int32_t *pcm, int layout, uint32_t n_frames,
@@ -866,6 +889,15 @@ int flacgpu_ingest_submit(flacgpu_ingest *g, const void *d_pcm, const flacgpu_ou
                           uint32_t channels, const flacgpu_ingest_stream *streams, uint32_t n_streams,
                           uint64_t staging_elements, uint32_t flags, void *stream, int32_t **d_staging);
 int flacgpu_ingest_finish(flacgpu_ingest *g, uint32_t *altered, uint8_t *md5);
+/* Small host-built pieces (the streams' headers) to their places in device memory, for flacenc_encode_many_device_out:
+ *   scratch  *pinned = a pinned host buffer of the handle's that holds at least `bytes` bytes (valid until the next
+ *            scratch call), for the caller to fill;
+ *   place    uploads its first `bytes` bytes in ONE copy into device scratch the handle keeps, then ONE k_place_runs launch
+ *            copies run i's n bytes from byte `src` of that scratch to the device address `dst` (exactly [dst, dst + n) is
+ *            written), on the handle's stream; returns when the copies are complete.  FLACGPU_ERR_INVALID_ARG when a
+ *            run reaches past `bytes`. */
+int flacgpu_ingest_scratch(flacgpu_ingest *g, size_t bytes, uint8_t **pinned);
+int flacgpu_ingest_place(flacgpu_ingest *g, size_t bytes, const flacgpu_place_run *runs, uint32_t n_runs);
 
 /* EXPERIMENT, not on the product path: recomputes the autocorrelation of the last analysed
  * batch on the f64 matrix cores (v_mfma_f64_16x16x4_f64, block-Gram form), times that kernel,

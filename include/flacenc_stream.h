@@ -252,6 +252,37 @@ int flacenc_device_batch_plan(const flacenc_options *opts, const flacenc_tensor_
 int flacenc_encode_many_device(const flacenc_options *opts, const void *d_pcm, const flacenc_tensor_format *fmt,
                                uint32_t sample_rate, uint32_t bits_per_sample, uint32_t channels, flacenc_device_job *jobs,
                                size_t n_jobs, uint32_t flags, void *stream);
+/* ---- ... and the finished .flac files left in DEVICE memory too (DESIGN.md 4c "Device-resident output") ----
+ * flacenc_encode_many_device with a back door: stream i's file goes to bytes [out_offset, out_offset + out_cap) of `d_out`,
+ * its SLOT, in device memory (on the tensor's device); only frame sizes, digests and the streams' headers cross the link.
+ * The slots may start at any byte, come in any order and leave gaps; two slots that hold bytes (out_cap > 0) must not overlap.
+ * A stream with status == 0 occupies [out_offset, out_offset + out_len) with exactly the bytes flacenc_encode_many_device
+ * writes for the same tensor, options and flags; status, altered and md5 are that call's too (a stream without samples:
+ * FLACENC_ERR_INVALID_ARG; a slot smaller than the header, or one the frames overflow: FLACENC_ERR_IO in that job's status,
+ * the other streams unaffected).  A failed stream's slot holds undefined bytes.  No byte of d_out outside the slots is ever
+ * written, and no byte of a slot behind out_len for a stream that succeeded: the frames are placed by k_place_runs
+ * (csrc/kernels/place_rule.h: 16-byte stores for whole aligned groups, byte stores at a run's edges), batch by batch beside
+ * the next batch's analysis, and the headers -- built on the host once the digests are there -- go up in one copy and to
+ * their places in one launch of the same kernel.  Synchronous: the files are complete when the call returns, and d_pcm may
+ * be reused; the work is ordered after `stream` as in flacenc_encode_many_device.
+ * plan is pure host code: flacenc_device_batch_plan's checks, and FLACENC_ERR_INVALID_ARG for a slot that reaches past
+ * d_out_bytes, out_offset + out_cap overflowing, or two slots with out_cap > 0 that overlap.  encode runs the same checks
+ * first: a refused call launches nothing and writes nothing. */
+typedef struct {
+    uint64_t in_offset, samples;   /* as flacenc_device_job */
+    uint64_t out_offset, out_cap;  /* the stream's slot: bytes [out_offset, out_offset + out_cap) of d_out */
+    uint64_t out_len;              /* out */
+    int32_t status;
+    uint32_t altered;
+    uint8_t md5[16];
+} flacenc_device_out_job;
+int flacenc_device_out_plan(const flacenc_options *opts, const flacenc_tensor_format *fmt, uint32_t bits_per_sample,
+                            uint32_t channels, const flacenc_device_out_job *jobs, size_t n_jobs, size_t d_out_bytes,
+                            size_t *in_elements, size_t *staging_bytes);
+int flacenc_encode_many_device_out(const flacenc_options *opts, const void *d_pcm, const flacenc_tensor_format *fmt,
+                                   uint32_t sample_rate, uint32_t bits_per_sample, uint32_t channels,
+                                   flacenc_device_out_job *jobs, size_t n_jobs, void *d_out, size_t d_out_bytes, uint32_t flags,
+                                   void *stream);
 /* The conversion rule on the host, one element: raw_bits holds the element's bits (I16: in the low half; S24: in the low 24 bits, bits
  * 24-31 are ignored).  *altered
  * (may be NULL) = 1 when the element was changed beyond rounding.  A combination plan refuses (unknown type, bps outside

@@ -11,7 +11,16 @@ k_ingest, k_md5_many and the one-frame tail calls).
 
 --int24: the packed 24-bit leg instead, on 1024 clips of 10 s, 48 kHz stereo 24-bit held as [B, C, T, 3] uint8 (divided
 by --shrink): (a) the caller widens the bytes to int32 in torch and calls encode_device on that, (b)
-encode_device(dtype="int24"); identical files asserted.  Merged into profiles/r12_s24.json under "encoder"."""
+encode_device(dtype="int24"); identical files asserted.  Merged into profiles/r12_s24.json under "encoder".
+
+--out-device: what encode_device(out="device") saves a caller who wants the FILES on the GPU, on the two workloads above:
+(a) encode_device to host buffers followed by the upload of the files into one device tensor -- what such a caller does
+without it -- and (b) encode_device(out="device"); identical bytes asserted, handle warm, median and min-max of --repeats,
+sclk before and after each leg.  Every workload's record also holds "host_output", encode_device to host buffers alone: the
+figure to compare between builds.  Writes profiles/r18_device_out.json.  With --kernels: one encode_device(out="device")
+call per workload and nothing else (k_place_runs' share, under rocprofv3 as above).
+--host-only (with --out-device): the "host_output" leg alone, merged into the record under "host_output_of" / --label; with
+--root DIR the package of another checkout built beside this one (the parent commit) is measured by the same code."""
 import argparse
 import json
 import os
@@ -101,6 +110,61 @@ def int24_leg(a):
     print(json.dumps(r, indent=1))
 
 
+def out_device_leg(a):
+    import torch
+    from flac_codec_amd import _lib
+    from flac_codec_amd.encode import BatchEncoder, Options
+
+    res = {}
+    if os.path.exists(a.out):
+        with open(a.out) as f:
+            res = json.load(f)
+    if not a.host_only:
+        res = {"tool": "tools/encode_device_probe.py --out-device", "build_id": _lib.build_id(), "shrink": a.shrink,
+               "workloads": {}, "host_output_of": res.get("host_output_of", {})}
+    for name, w in WORKLOADS.items():
+        if a.only and name != a.only:
+            continue
+        t = make_batch(w, a.shrink)
+        enc = BatchEncoder(Options.default())
+        kw = dict(sample_rate=w["rate"], bits_per_sample=16)
+
+        def host_output():
+            return enc.encode_device(t, None, copy=False, **kw)
+
+        def host_then_upload():
+            return torch.from_numpy(np.concatenate(host_output())).cuda()
+
+        def device_output():
+            return enc.encode_device(t, None, out="device", **kw)
+
+        if a.kernels:
+            device_output()
+            continue
+        legs = [("host_output", host_output)]
+        if not a.host_only:
+            assert torch.equal(host_then_upload(), torch.cat(device_output())), f"{name}: the two legs differ"
+            legs += [("a_encode_device_then_upload", host_then_upload), ("b_encode_device_out_device", device_output)]
+        r = {"streams": t.shape[0], "samples": t.numel(), "file_bytes": int(sum(v.size for v in host_output()))}
+        for k, fn in legs:
+            before = sclk()   # around every leg: a clock change between the legs shows
+            r[k] = dict(timed(fn, a.repeats), sclk_before=before, sclk_after=sclk())
+            r[k]["gsamples_per_s"] = r["samples"] / r[k]["median_ms"] / 1e6
+        if a.host_only:
+            res.setdefault("host_output_of", {}).setdefault(a.label, {"build_id": _lib.build_id()})[name] = r["host_output"]
+        else:
+            res["workloads"][name] = r
+        print(name, json.dumps(r))
+        del t
+        torch.cuda.empty_cache()
+    if a.kernels:
+        return
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print("wrote", a.out)
+
+
 def timed(fn, repeats):
     import torch
 
@@ -122,14 +186,23 @@ def main():
     ap.add_argument("--only", default=None, help="one workload's name")
     ap.add_argument("--kernels", action="store_true")
     ap.add_argument("--int24", action="store_true", help="the packed 24-bit leg: profiles/r12_s24.json")
+    ap.add_argument("--out-device", action="store_true", help="files left on the GPU: profiles/r18_device_out.json")
+    ap.add_argument("--host-only", action="store_true", help="with --out-device: the host-output leg alone")
+    ap.add_argument("--label", default="this_build", help="with --host-only: the record's name")
+    ap.add_argument("--root", default=None, help="measure the package of another checkout")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    a.out = a.out or os.path.join(ROOT, "profiles", "r12_s24.json" if a.int24 else "r11_encode_device.json")
+    a.out = a.out or os.path.join(ROOT, "profiles", "r12_s24.json" if a.int24 else
+                                  "r18_device_out.json" if a.out_device else "r11_encode_device.json")
+    if a.root:   # (the package is imported below, never before this line)
+        sys.path.insert(0, os.path.abspath(a.root))
     import torch
 
     torch.cuda.init()
     if a.int24:
         return int24_leg(a)
+    if a.out_device:
+        return out_device_leg(a)
     from flac_codec_amd import _lib
     from flac_codec_amd.encode import BatchEncoder, Options
 
