@@ -128,6 +128,29 @@ class PlaceRun(C.Structure):
 DEVICE_NO_MD5 = 1   # FLACENC_DEVICE_NO_MD5
 
 
+class SessionChunk(C.Structure):
+    """flacenc_session_chunk: one stream's part of a flacenc_device_session_write call."""
+    _fields_ = [("in_offset", C.c_uint64), ("samples", C.c_uint64), ("out", C.c_void_p), ("out_cap", C.c_size_t),
+                ("out_len", C.c_size_t), ("status", C.c_int32), ("altered", C.c_uint32)]
+
+
+class SessionFinal(C.Structure):
+    """flacenc_session_final: one stream's header, short last frame, status, altered count and MD5 at finalize."""
+    _fields_ = [("header", C.c_void_p), ("header_cap", C.c_size_t), ("header_len", C.c_size_t), ("tail", C.c_void_p),
+                ("tail_cap", C.c_size_t), ("tail_len", C.c_size_t), ("status", C.c_int32), ("altered", C.c_uint32),
+                ("md5", C.c_uint8 * 16)]
+
+
+class Md5Piece(C.Structure):
+    """flacgpu_md5_piece: `count` int32 samples from element `off`, appended to chain `chain` (flacgpu_md5_chains_update)."""
+    _fields_ = [("chain", C.c_uint32), ("reserved", C.c_uint32), ("off", C.c_uint64), ("count", C.c_uint64)]
+
+
+class Md5State(C.Structure):
+    """flacgpu_md5_state: one resumable MD5 chain in host memory (flacgpu_md5_init_host / feed_host / final_host)."""
+    _fields_ = [("h", C.c_uint32 * 4), ("len", C.c_uint64), ("buf", C.c_uint8 * 64)]
+
+
 class Window(C.Structure):
     """flacgpu_window: samples [start, start + length) per channel of one scanned stream."""
     _fields_ = [("stream", C.c_uint32), ("reserved", C.c_uint32), ("start", C.c_uint64), ("length", C.c_uint64)]
@@ -360,6 +383,17 @@ def _load():
     L.flacgpu_rccl_available.argtypes = []
     L.flacgpu_rccl_allgather_counters.argtypes = [vp, vp, sc, sc, C.c_uint32, C.POINTER(C.c_uint32),
                                                   C.POINTER(C.c_uint32)]
+    L.flacgpu_md5_chains_create.argtypes = [C.c_int, C.c_uint32, C.POINTER(vp)]
+    L.flacgpu_md5_chains_destroy.argtypes = [vp]
+    L.flacgpu_md5_chains_destroy.restype = None
+    L.flacgpu_md5_chains_update.argtypes = [vp, vp, C.POINTER(Md5Piece), C.c_uint32, C.c_uint32, vp]
+    L.flacgpu_md5_chains_final.argtypes = [vp, C.c_void_p]
+    L.flacgpu_md5_stage_bytes.argtypes = []
+    L.flacgpu_md5_stage_bytes.restype = C.c_uint32
+    L.flacgpu_md5_init_host.argtypes = [C.POINTER(Md5State)]
+    L.flacgpu_md5_init_host.restype = None
+    L.flacgpu_md5_feed_host.argtypes = [C.POINTER(Md5State), C.c_void_p, C.c_uint64, C.c_uint32]
+    L.flacgpu_md5_final_host.argtypes = [C.POINTER(Md5State), C.c_void_p]
     L.flacgpu_build_id.argtypes = []
     L.flacgpu_build_id.restype = C.c_char_p
     return L

@@ -19,6 +19,8 @@
 //   * a stream's short last block: a one-frame flacgpu_encode_device call on the staging pointer (two one-frame contexts
 //     in rotation), as coalesce.cpp does from host PCM;
 //   * everything in front of the first frame: flacenc_stream_header, as in coalesce.cpp.
+// The whole-block loop (encode_whole_blocks, device_blocks.h) is shared with the chunk-by-chunk sessions of
+// device_session.cpp.
 #include <algorithm>
 #include <atomic>
 #include <cstring>
@@ -31,6 +33,7 @@
 
 #include "../kernels/ingest_rule.h"
 #include "../kernels/sample_types.h"
+#include "device_blocks.h"
 #include "host_internal.h"
 
 using namespace flacenc_host;
@@ -79,10 +82,7 @@ struct IngestPool {
     }
 };
 
-int gpu_error(int rc) {
-    set_last_error(std::string("gpu: ") + flacgpu_last_error());
-    return rc == FLACGPU_ERR_UNSUPPORTED ? FLACENC_ERR_UNSUPPORTED : FLACENC_ERR_GPU;
-}
+int gpu_error(int rc) { return device_gpu_error(rc); }
 int refuse(int rc, const std::string &why) {
     set_last_error("flacenc_device_batch_plan: " + why);
     return rc;
@@ -357,47 +357,17 @@ int encode_impl(const flacenc_options *opts, const void *d_pcm, const flacenc_te
     for (size_t i = 0; i < n_jobs; i++) whole[i] = jobs[i].status ? 0 : st[i].whole;
     uint32_t batch_cap = 0;
     const std::vector<std::vector<PlanSeg>> batches = plan_stream_batches(whole, o.batch_frames, per, &batch_cap);
-    int whole_rc = 0;
-    if (!batches.empty()) {
-        PooledContext slot[2] = {};
-        const size_t n_slots = std::min<size_t>(2, batches.size());
-        size_t have = 0;
-        for (; have < n_slots; have++)
-            if (int rc = pooled_context_take(g, bps, ch, batch_cap, device, &slot[have])) {
-                whole_rc = gpu_error(rc);
-                break;
-            }
-        const auto submit = [&](size_t b) {
-            std::vector<flacgpu_segment> gs(batches[b].size());
-            for (size_t k = 0; k < gs.size(); k++) {
-                const PlanSeg &p = batches[b][k];
-                gs[k].pcm = d_staging + staging_off[p.stream] + p.first * per;
-                gs[k].n_frames = p.n;
-                gs[k].reserved = 0;
-                gs[k].first_frame_number = p.first;
-            }
-            return flacgpu_encode_segments_device(slot[b % 2].ctx, gs.data(), (uint32_t)gs.size(), sample_rate, nullptr);
-        };
-        std::vector<uint64_t> off;
-        std::vector<CopyJob> cj;
-        std::vector<flacgpu_place_run> runs;
-        int rc = whole_rc ? FLACGPU_ERR_HIP : submit(0);
-        for (size_t b = 0; b < batches.size() && !rc; b++) {
-            if (b + 1 < batches.size()) rc = submit(b + 1);   // its kernels run while batch b's frames are fetched
-            if (rc) break;
-            const PooledContext &s = slot[b % 2];
-            uint32_t frames = 0;
-            for (const PlanSeg &p : batches[b]) frames += p.n;
-            off.assign((size_t)frames + 1, 0);
-            uint64_t total = 0;
-            // host output: the frames cross the link; device output: only their sizes do
-            rc = kDeviceOut ? flacgpu_frame_offsets(s.ctx, off.data(), &total)
-                            : flacgpu_fetch_frames(s.ctx, s.out, s.out_cap, off.data(), &total);
-            if (rc) break;
+    std::vector<CopyJob> cj;
+    std::vector<flacgpu_place_run> runs;
+    const int whole_rc = encode_whole_blocks(
+        g, bps, ch, device, sample_rate, batches, batch_cap, !kDeviceOut,
+        [&](const PlanSeg &p) { return d_staging + staging_off[p.stream] + p.first * per; },
+        [&](const PlanSeg &p) { return p.first; },
+        [&](const PooledContext &s, const std::vector<PlanSeg> &batch, const std::vector<uint64_t> &off) {
             cj.clear();
             runs.clear();
             uint32_t f = 0;
-            for (const PlanSeg &p : batches[b]) {
+            for (const PlanSeg &p : batch) {
                 Stream &sm = st[p.stream];
                 Job &j = jobs[p.stream];
                 const uint64_t bytes = off[f + p.n] - off[f];
@@ -410,19 +380,14 @@ int encode_impl(const flacenc_options *opts, const void *d_pcm, const flacenc_te
                 sm.pos += bytes;
                 f += p.n;
             }
-            // (device output: the kernel runs on this context's stream, beside batch b + 1's analysis on the other's)
-            if (kDeviceOut) rc = flacgpu_place_frames(s.ctx, runs.data(), (uint32_t)runs.size());
-            else run_copies(cj);
-        }
-        if (rc && !whole_rc) whole_rc = gpu_error(rc);
-        for (size_t k = 0; k < have; k++) {
-            (void)flacgpu_wait(slot[k].ctx);   // (a batch submitted before a failure: nothing of this call may be in flight)
-            pooled_context_give(g, bps, ch, batch_cap, device, slot[k]);
-        }
-        if (whole_rc)
-            for (size_t i = 0; i < n_jobs; i++)
-                if (whole[i]) fail(i, whole_rc);
-    }
+            // (device output: the kernel runs on this context's stream, beside the next batch's analysis on the other's)
+            if (kDeviceOut) return flacgpu_place_frames(s.ctx, runs.data(), (uint32_t)runs.size());
+            run_copies(cj);
+            return (int)FLACGPU_OK;
+        });
+    if (whole_rc)
+        for (size_t i = 0; i < n_jobs; i++)
+            if (whole[i]) fail(i, whole_rc);
 
     // ---- the short last blocks: one frame each, two one-frame contexts in rotation
     std::vector<size_t> tails;

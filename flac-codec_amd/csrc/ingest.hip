@@ -239,3 +239,27 @@ int flacgpu_ingest_place(flacgpu_ingest *g, size_t bytes, const flacgpu_place_ru
     HIP_TRY(hipStreamSynchronize(g->st));
     return FLACGPU_OK;
 }
+
+int flacgpu_ingest_move(flacgpu_ingest *g, const flacgpu_place_run *runs, uint32_t n_runs) {
+    if (!g || (n_runs && !runs)) return FLACGPU_ERR_INVALID_ARG;
+    for (uint32_t i = 0; i < n_runs; i++) {
+        uint64_t end = 0;
+        if (runs[i].n && (!runs[i].src || !runs[i].dst || __builtin_add_overflow(runs[i].src, runs[i].n, &end) ||
+                          __builtin_add_overflow(runs[i].dst, runs[i].n, &end))) {
+            g_last_error = "flacgpu_ingest_move: run " + std::to_string(i) + " has no source or destination, or wraps round";
+            return FLACGPU_ERR_INVALID_ARG;
+        }
+    }
+    if (!n_runs) return FLACGPU_OK;
+    DeviceGuard guard(g->device);
+    if (int rc = g->run_host.ensure(sizeof(PlaceRun) * (size_t)n_runs)) return rc;
+    if (int rc = g->run_dev.ensure(sizeof(PlaceRun) * (size_t)n_runs)) return rc;
+    PlaceRun *tab = g->run_host.as<PlaceRun>();
+    const uint64_t groups = place_table(runs, n_runs, 0, 0, tab);
+    HIP_TRY(hipMemcpyAsync(g->run_dev.p, tab, sizeof(PlaceRun) * (size_t)n_runs, hipMemcpyHostToDevice, g->st));
+    if (int rc = flacgpu_k::launch_place_runs(g->run_dev.as<const PlaceRun>(), n_runs, groups, g->st)) return rc;
+    HIP_TRY(hipStreamSynchronize(g->st));
+    return FLACGPU_OK;
+}
+
+void *flacgpu_ingest_stream_of(flacgpu_ingest *g) { return g ? static_cast<void *>(g->st) : nullptr; }

@@ -196,6 +196,18 @@ def _stream_lib():
                                               C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
         L.flacenc_encode_many_device_out.argtypes = [po, vp, pf, C.c_uint32, C.c_uint32, C.c_uint32,
                                                      C.POINTER(_lib.DeviceOutJob), C.c_size_t, vp, C.c_size_t, C.c_uint32, vp]
+        L.flacenc_device_session_plan.argtypes = [po, C.c_uint32, C.c_uint32, C.c_size_t, C.c_uint64, C.c_uint32,
+                                                  C.POINTER(C.c_size_t)]
+        L.flacenc_device_session_open.argtypes = [po, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.c_size_t,
+                                                  C.c_uint64, C.c_uint32, C.POINTER(vp)]
+        L.flacenc_device_session_header_len.argtypes = [vp, C.c_size_t]
+        L.flacenc_device_session_header_len.restype = C.c_size_t
+        L.flacenc_device_session_write.argtypes = [vp, vp, pf, C.POINTER(_lib.SessionChunk), vp]
+        L.flacenc_device_session_finalize.argtypes = [vp, C.POINTER(_lib.SessionFinal)]
+        L.flacenc_device_session_close.argtypes = [vp]
+        L.flacenc_device_session_close.restype = None
+        L.flacenc_release_pools.argtypes = []
+        L.flacenc_release_pools.restype = None
         L.flacgpu_place_runs_host.argtypes = [C.POINTER(_lib.PlaceRun), C.c_uint32]
         L.flacgpu_place_workgroup.restype = C.c_uint32
         L.flacenc_ingest_sample.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int)]
@@ -799,3 +811,118 @@ class BatchEncoder:
             return [h[5][int(jobs[i].out_offset): int(jobs[i].out_offset) + int(jobs[i].out_len)] for i in range(n)]
         views = [self._bufs[i][: jobs[i].out_len] for i in range(n)]
         return [v.tobytes() for v in views] if copy else views
+
+    def open_device_session(self, totals, sample_rate, bits_per_sample, channels, max_chunk, verify_md5=True, keep=True,
+                            device=None):
+        """A DeviceSession: the streams of encode_device taken chunk by chunk (flacenc_device_session_*).  totals:
+        every stream's length per channel, declared now; max_chunk: the most samples per channel one write brings for
+        one stream.  device: the HIP ordinal (default: the options', else the current one)."""
+        return DeviceSession(self._opts, totals, sample_rate, bits_per_sample, channels, max_chunk, verify_md5, keep, device)
+
+
+class DeviceSession:
+    """n streams of one shape, produced on the GPU piece by piece, -> .flac files (flacenc_device_session_*): write()
+    takes the next chunk of every stream in the tensor forms encode_device takes and returns the frames that chunk
+    completes; finalize() returns the files -- byte for byte what encode_device gives for the concatenated samples.
+    A context manager: leaving the block closes the session."""
+
+    def __init__(self, options, totals, sample_rate, bits_per_sample, channels, max_chunk, verify_md5=True, keep=True,
+                 device=None):
+        L = _stream_lib()
+        self._co = options._c_options()
+        if device is not None:
+            self._co.device = int(device)
+        self._totals = [int(t) for t in totals]
+        self._n, self._bps, self._channels, self._keep = len(self._totals), bits_per_sample, channels, keep
+        self._block = int(self._co.block_size)
+        self._pending = [0] * self._n   # samples carried towards the next block, as the library counts them
+        self._parts = [[] for _ in range(self._n)]
+        self._bufs = []
+        self._h = C.c_void_p()
+        arr = (C.c_uint64 * max(self._n, 1))(*self._totals)
+        _check(L.flacenc_device_session_open(C.byref(self._co), sample_rate, bits_per_sample, channels, arr, self._n,
+                                             int(max_chunk), 0 if verify_md5 else _lib.DEVICE_NO_MD5, C.byref(self._h)))
+        self.last_status = [0] * self._n
+        self.last_altered = [0] * self._n
+        self.last_md5 = [bytes(16)] * self._n
+
+    def header_len(self, i):
+        return int(_stream_lib().flacenc_device_session_header_len(self._h, i))
+
+    def write(self, tensor, lengths=None, dtype=None, offsets=None):
+        """The next chunk of every stream (lengths[i] samples of stream i, 0 allowed; the tensor as in encode_device)
+        -> list[bytes]: the frames this write completes, per stream.  Runs behind the tensor's current torch stream and
+        returns when the tensor may be reused.  self.last_status / self.last_altered: this write's (a stream whose
+        status is not 0 is dead -- its later chunks are ignored -- and the others go on; finalize() raises for it)."""
+        import torch
+
+        L = _stream_lib()
+        n, offsets, lengths, channels, fmt = BatchEncoder._device_batch(tensor, lengths, dtype, offsets, self._channels)
+        if n != self._n or channels != self._channels:
+            raise ValueError("one chunk per stream of the session, of the session's channel count")
+        chunks = (_lib.SessionChunk * max(n, 1))()
+        for i in range(n):
+            blocks = (self._pending[i] + lengths[i]) // self._block
+            cap = int(L.flacenc_worst_case_bytes(C.byref(self._co), self._bps, channels, blocks * self._block)) if blocks else 0
+            if i >= len(self._bufs):
+                self._bufs.append(np.empty(max(cap, 1), dtype=np.uint8))
+            elif self._bufs[i].size < cap:
+                self._bufs[i] = np.empty(cap, dtype=np.uint8)
+            chunks[i].in_offset, chunks[i].samples = offsets[i], lengths[i]
+            chunks[i].out, chunks[i].out_cap = self._bufs[i].ctypes.data, self._bufs[i].size
+        stream = torch.cuda.current_stream(tensor.device).cuda_stream
+        rc = L.flacenc_device_session_write(self._h, tensor.data_ptr() if tensor.numel() else None, C.byref(fmt), chunks,
+                                            stream or None)
+        _check(rc)   # refused as a whole: no chunk field was written and the session is as it was
+        self.last_status = [int(chunks[i].status) for i in range(n)]
+        self.last_altered = [int(chunks[i].altered) for i in range(n)]
+        out = []
+        for i in range(n):
+            if not self.last_status[i]:
+                self._pending[i] = (self._pending[i] + lengths[i]) % self._block
+            out.append(self._bufs[i][: chunks[i].out_len].tobytes())
+            if self._keep:
+                self._parts[i].append(out[-1])
+        return out
+
+    def finalize(self):
+        """-> list[bytes], the whole files (keep=True), or (headers, tails) for a session opened with keep=False.
+        self.last_status, self.last_altered (summed over the writes) and self.last_md5 as for encode_device."""
+        L = _stream_lib()
+        n = self._n
+        finals = (_lib.SessionFinal * max(n, 1))()
+        tail_cap = int(L.flacenc_worst_case_bytes(C.byref(self._co), self._bps, self._channels, self._block))
+        bufs = []
+        for i in range(n):
+            hb = np.empty(max(self.header_len(i), 1), dtype=np.uint8)
+            tb = np.empty(tail_cap, dtype=np.uint8)
+            bufs.append((hb, tb))
+            finals[i].header, finals[i].header_cap = hb.ctypes.data, hb.size
+            finals[i].tail, finals[i].tail_cap = tb.ctypes.data, tb.size
+        rc = L.flacenc_device_session_finalize(self._h, finals)
+        self.last_status = [int(finals[i].status) for i in range(n)]
+        self.last_altered = [int(finals[i].altered) for i in range(n)]
+        self.last_md5 = [bytes(finals[i].md5) for i in range(n)]
+        _check(rc)
+        headers = [bufs[i][0][: finals[i].header_len].tobytes() for i in range(n)]
+        tails = [bufs[i][1][: finals[i].tail_len].tobytes() for i in range(n)]
+        if not self._keep:
+            return headers, tails
+        return [headers[i] + b"".join(self._parts[i]) + tails[i] for i in range(n)]
+
+    def close(self):
+        if self._h:
+            _stream_lib().flacenc_device_session_close(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

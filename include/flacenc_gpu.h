@@ -898,6 +898,51 @@ int flacgpu_ingest_finish(flacgpu_ingest *g, uint32_t *altered, uint8_t *md5);
  *            run reaches past `bytes`. */
 int flacgpu_ingest_scratch(flacgpu_ingest *g, size_t bytes, uint8_t **pinned);
 int flacgpu_ingest_place(flacgpu_ingest *g, size_t bytes, const flacgpu_place_run *runs, uint32_t n_runs);
+/* Device-to-device runs for flacenc_device_session_write (the carried samples of every stream to the staging buffer's
+ * other half): ONE k_place_runs launch over `runs`, whose src and dst are both device ADDRESSES (exactly [dst, dst + n) is
+ * written, [src, src + n) read; no run's source may overlap any run's destination), on the handle's stream; returns when
+ * the copies are complete.  The caller orders it behind whatever still reads the destinations. */
+int flacgpu_ingest_move(flacgpu_ingest *g, const flacgpu_place_run *runs, uint32_t n_runs);
+/* The handle's stream (a hipStream_t), for work that must run in order with the handle's own. */
+void *flacgpu_ingest_stream_of(flacgpu_ingest *g);
+
+/* ---- resumable MD5 chains: a stream's MD5 taken piece by piece, on the device ------------------------------------------
+ * k_md5_many starts every chain from the initial state and pads at the end of its call; these chains keep {h[4], the
+ * 64-bit byte length, up to 63 buffered message bytes} per chain in device memory between calls, so that a stream can be
+ * hashed in as many pieces as it arrives in (flacenc_device_session_write).  The rule -- how a piece's samples and the
+ * buffered bytes become 64-byte blocks, what stays buffered, the padding -- is csrc/kernels/md5_feed_rule.h, one set of
+ * functions for both sides; the kernel (csrc/kernels/md5_chain.inc, one wave per piece) loads a window of
+ * flacgpu_md5_stage_bytes() message bytes with coalesced 16-byte loads, parks its blocks in LDS, and one lane consumes them.
+ *   create   n_chains chains at the initial state, on `device` (< 0: the current one).
+ *   update   piece p appends `count` int32 samples, from element `off` of d_samples, to chain `chain`; every sample gives
+ *            its low `width` bytes, little-endian (what k_md5_many reads).  Asynchronous on `stream` (a hipStream_t; NULL:
+ *            the legacy default stream); every call on one handle must use one stream, or streams the caller has ordered.
+ *            At most one piece per chain and call (a chain is serial).  A duplicate chain, a chain >= n_chains, reserved
+ *            != 0, a count above 2^58 or a width outside 1..4: FLACGPU_ERR_INVALID_ARG, nothing launched, no state
+ *            changed.  count == 0 changes nothing.  No byte of d_samples outside a piece's [off, off + count) is read.
+ *   final    pads every chain, downloads the digests (md5_out: [n_chains][16]) and leaves every chain at the initial
+ *            state; ordered after every update so far; synchronous.  A chain never fed: the MD5 of the empty message.
+ * flacgpu_md5_init_host / feed_host / final_host run the same rule over host memory on a caller-owned state; they touch
+ * no device.  final_host leaves the state initial again. */
+typedef struct flacgpu_md5_chains flacgpu_md5_chains;
+typedef struct {
+    uint32_t chain, reserved;
+    uint64_t off, count;
+} flacgpu_md5_piece;
+typedef struct {
+    uint32_t h[4];
+    uint64_t len;
+    uint8_t buf[64];
+} flacgpu_md5_state;
+int flacgpu_md5_chains_create(int device, uint32_t n_chains, flacgpu_md5_chains **out);
+void flacgpu_md5_chains_destroy(flacgpu_md5_chains *c);
+int flacgpu_md5_chains_update(flacgpu_md5_chains *c, const int32_t *d_samples, const flacgpu_md5_piece *pieces,
+                              uint32_t n_pieces, uint32_t width, void *stream);
+int flacgpu_md5_chains_final(flacgpu_md5_chains *c, uint8_t *md5_out);
+uint32_t flacgpu_md5_stage_bytes(void);
+void flacgpu_md5_init_host(flacgpu_md5_state *state);
+int flacgpu_md5_feed_host(flacgpu_md5_state *state, const int32_t *samples, uint64_t count, uint32_t width);
+int flacgpu_md5_final_host(flacgpu_md5_state *state, uint8_t md5[16]);
 
 /* EXPERIMENT, not on the product path: recomputes the autocorrelation of the last analysed
  * batch on the f64 matrix cores (v_mfma_f64_16x16x4_f64, block-Gram form), times that kernel,

@@ -219,8 +219,8 @@ int flacenc_encode_many_devices(const flacenc_options *opts, flacenc_job *jobs, 
  * What happens: one ingest pass writes interleaved int32 into a staging buffer of the library's (staging_bytes = 4 x the
  * sum over the streams of samples x channels rounded up to 4; this version always ingests -- reading an aligned FLAT I32
  * batch in place is a follow-up); the MD5 of every stream is taken on the device (k_md5_many: one lane per stream, about
- * 15 MB/s per stream -- fine for many clips, poor for one long stream; a faster chain is out of scope, and
- * FLACENC_DEVICE_NO_MD5 is the way round it today); runs of whole blocks of several streams go through
+ * 15 MB/s per stream -- fine for many clips, poor for one long stream; FLACENC_DEVICE_NO_MD5 is the way round it in this
+ * call, and the sessions below hash with the staged resumable chain of flacgpu_md5_chains_*); runs of whole blocks of several streams go through
  * flacgpu_encode_segments_device in batches planned as flacenc_encode_many_coalesced plans them, on two pooled contexts in
  * rotation (one batch's kernels run while the other's frames travel to pinned memory); a stream's short last block is a
  * one-frame flacgpu_encode_device call on the staging buffer; everything in front of the first frame is
@@ -283,6 +283,70 @@ int flacenc_encode_many_device_out(const flacenc_options *opts, const void *d_pc
                                    uint32_t sample_rate, uint32_t bits_per_sample, uint32_t channels,
                                    flacenc_device_out_job *jobs, size_t n_jobs, void *d_out, size_t d_out_bytes, uint32_t flags,
                                    void *stream);
+/* ---- ... and the same batch taken CHUNK BY CHUNK: sessions (DESIGN.md 4c "Sessions") ---------------------------------------
+ * flacenc_encode_many_device needs every stream whole; a session takes n_streams streams of one shape in as many writes as
+ * the samples come into being in, as FlacSampleWriter::write / finalize do for one stream on the host (encode.rs:487, 558,
+ * 624).  The contract: for every stream that succeeds,
+ *     header || frames of write 1 || ... || frames of write k || tail
+ * is byte for byte the file flacenc_encode_many_device writes for the concatenated samples with the same options and
+ * flags, and md5 and altered are that call's too.
+ *   plan      pure host code: refuses what flacenc_device_batch_plan refuses for the shape (options, channels, bits per
+ *             sample, stream count), max_chunk == 0 and unknown flags; *device_bytes = what the session holds in device
+ *             memory for its whole life: a staging buffer of two halves, in each of which stream i owns room for
+ *             block_size - 1 carried samples and a chunk of max_chunk (both rounded up to 16 bytes), and 128 bytes of MD5
+ *             chain state and tables per stream.  (The analysis contexts are the pooled ones of the one-shot calls.)
+ *   open      totals[i] = stream i's length per channel, declared now: everything in front of the first frame then has
+ *             its final size (flacenc_stream_header builds it at finalize), as for FlacSampleWriter::new with a known
+ *             total.  totals[i] == 0 (FLACENC_ERR_INVALID_ARG) or a total / option the reference's `new` refuses makes
+ *             stream i dead from the start; the session opens for the others.  flags: FLACENC_DEVICE_NO_MD5.
+ *   header_len  bytes in front of stream i's first frame (0 for a stream dead at open).
+ *   write     chunks[i] = the next `samples` samples per channel of stream i (0: none this time) in `d_pcm`, which `fmt`
+ *             describes exactly as for flacenc_encode_many_device with jobs[i] = {in_offset, samples}; type and layout may
+ *             differ from write to write.  The chunks are ingested, the MD5 chains fed (flacgpu_md5_chains_update, beside
+ *             the analysis), every block that the carried samples and the chunk complete is encoded, and those frames go,
+ *             in order, to chunks[i].out (host memory; out_len = their size, 0 when no block was completed; altered = this
+ *             chunk's count).  Synchronous: d_pcm may be reused on return.  Refused as a whole with
+ *             FLACENC_ERR_INVALID_ARG -- nothing launched, no chunk field written, the session unchanged -- for a chunk
+ *             longer than max_chunk, a chunk that would pass its stream's total, or anything flacenc_device_batch_plan
+ *             refuses for this tensor.  An `out` too small for this write's frames: FLACENC_ERR_IO in that chunk's status,
+ *             and the stream is dead: its later chunks are ignored and get the same status; the others are unaffected.
+ *             Returns 0 when the call ran -- every stream's own outcome is in its chunk's status -- or the refusal.
+ *   finalize  every stream's short last block (one-frame path) to finals[i].tail, everything in front of the first frame
+ *             to finals[i].header; altered = the sum over all writes.  A stream that has not received its total:
+ *             FLACENC_ERR_SAMPLE_COUNT_MISMATCH (encode.rs:2083), nothing written for it.  header_cap or tail_cap too
+ *             small: FLACENC_ERR_IO.  Returns 0 or the first failing stream's status.  A second finalize, and a write
+ *             after finalize: FLACENC_ERR_FINALIZED.
+ *   close     frees everything; legal at any time, also on NULL.
+ * A GPU error in any call is sticky: every later write and finalize returns it.  A session is not thread-safe; several
+ * sessions, and one-shot calls beside them, do not disturb one another, nor does flacenc_release_pools(). */
+typedef struct flacenc_device_session flacenc_device_session;
+typedef struct {
+    uint64_t in_offset;      /* FLAT: first element of the chunk in d_pcm; PADDED: ignored */
+    uint64_t samples;        /* per channel, <= max_chunk; 0: nothing for this stream */
+    uint8_t *out;            /* caller-owned host buffer for the frames this write completes */
+    size_t out_cap, out_len;
+    int32_t status;
+    uint32_t altered;
+} flacenc_session_chunk;
+typedef struct {
+    uint8_t *header;         /* caller-owned host buffers */
+    size_t header_cap, header_len;
+    uint8_t *tail;
+    size_t tail_cap, tail_len;
+    int32_t status;
+    uint32_t altered;
+    uint8_t md5[16];
+} flacenc_session_final;
+int flacenc_device_session_plan(const flacenc_options *opts, uint32_t bits_per_sample, uint32_t channels, size_t n_streams,
+                                uint64_t max_chunk, uint32_t flags, size_t *device_bytes);
+int flacenc_device_session_open(const flacenc_options *opts, uint32_t sample_rate, uint32_t bits_per_sample,
+                                uint32_t channels, const uint64_t *totals, size_t n_streams, uint64_t max_chunk,
+                                uint32_t flags, flacenc_device_session **session);
+size_t flacenc_device_session_header_len(const flacenc_device_session *session, size_t i);
+int flacenc_device_session_write(flacenc_device_session *session, const void *d_pcm, const flacenc_tensor_format *fmt,
+                                 flacenc_session_chunk *chunks, void *stream);
+int flacenc_device_session_finalize(flacenc_device_session *session, flacenc_session_final *finals);
+void flacenc_device_session_close(flacenc_device_session *session);
 /* The conversion rule on the host, one element: raw_bits holds the element's bits (I16: in the low half; S24: in the low 24 bits, bits
  * 24-31 are ignored).  *altered
  * (may be NULL) = 1 when the element was changed beyond rounding.  A combination plan refuses (unknown type, bps outside

@@ -19,6 +19,14 @@ without it -- and (b) encode_device(out="device"); identical bytes asserted, han
 sclk before and after each leg.  Every workload's record also holds "host_output", encode_device to host buffers alone: the
 figure to compare between builds.  Writes profiles/r18_device_out.json.  With --kernels: one encode_device(out="device")
 call per workload and nothing else (k_place_runs' share, under rocprofv3 as above).
+--session: what a DeviceSession (flacenc_device_session_*) costs beside the one-shot call, on the two workloads above:
+(a) encode_device on the whole tensor, with and without the MD5 -- the yardstick, and the figure to compare between builds
+-- and (b) a session fed the same tensor in 1 s chunks (views of it made contiguous outside the timed region), with and
+without the MD5; identical files asserted, handle warm, median and min-max of --repeats, sclk before and after each leg.
+Writes profiles/r19_session.json.  --one-shot-only (with --session): leg (a) alone, merged into the record under
+"one_shot_of" / --label; with --root DIR the package of another checkout (the parent commit) is measured by the same code.
+With --kernels: per workload one one-shot call and one session, then ONE stream of 3 min stereo through both, and nothing
+else -- k_md5_chain beside k_md5_many on the same staged samples, under rocprofv3 as above.
 --host-only (with --out-device): the "host_output" leg alone, merged into the record under "host_output_of" / --label; with
 --root DIR the package of another checkout built beside this one (the parent commit) is measured by the same code."""
 import argparse
@@ -165,6 +173,72 @@ def out_device_leg(a):
     print("wrote", a.out)
 
 
+def session_leg(a):
+    import torch
+    from flac_codec_amd import _lib
+    from flac_codec_amd.encode import BatchEncoder, Options
+
+    res = {}
+    if os.path.exists(a.out):
+        with open(a.out) as f:
+            res = json.load(f)
+    if not a.one_shot_only:
+        res = {"tool": "tools/encode_device_probe.py --session", "build_id": _lib.build_id(), "shrink": a.shrink,
+               "workloads": {}, "one_shot_of": res.get("one_shot_of", {})}
+    shapes = dict(WORKLOADS)
+    if a.kernels:
+        shapes["one_track_3min_44k1_stereo"] = dict(n=1, samples=3 * 60 * 44100, channels=2, rate=44100)
+    for name, w in shapes.items():
+        if a.only and name != a.only:
+            continue
+        t = make_batch(w, 1 if w["n"] == 1 else a.shrink)
+        enc = BatchEncoder(Options.default())
+        n, ch, T, rate = t.shape[0], t.shape[1], t.shape[2], w["rate"]
+
+        def one_shot(md5=True):
+            return enc.encode_device(t, None, sample_rate=rate, bits_per_sample=16, verify_md5=md5, copy=False)
+
+        def session(md5=True):
+            with enc.open_device_session([T] * n, rate, 16, ch, max_chunk=rate, verify_md5=md5) as ses:
+                for piece in chunks:
+                    ses.write(piece)
+                return ses.finalize()
+
+        if a.kernels:
+            chunks = [t[:, :, at:at + rate].contiguous() for at in range(0, T, rate)]
+            one_shot()
+            session()
+            del t, chunks
+            torch.cuda.empty_cache()
+            continue
+        legs = [("a_one_shot", one_shot), ("a_one_shot_no_md5", lambda: one_shot(False))]
+        if not a.one_shot_only:
+            chunks = [t[:, :, at:at + rate].contiguous() for at in range(0, T, rate)]   # (a second copy of the batch)
+            assert [bytes(v) for v in one_shot()] == session(), f"{name}: the two legs differ"
+            assert [bytes(v) for v in one_shot(False)] == session(False), f"{name}: the two legs differ without MD5"
+            legs += [("b_session_1s_chunks", session), ("b_session_1s_chunks_no_md5", lambda: session(False))]
+        r = {"streams": n, "samples": t.numel(), "writes": (T + rate - 1) // rate}
+        for k, fn in legs:
+            before = sclk()   # around every leg: a clock change between the legs shows
+            r[k] = dict(timed(fn, a.repeats), sclk_before=before, sclk_after=sclk())
+            r[k]["gsamples_per_s"] = r["samples"] / r[k]["median_ms"] / 1e6
+        if a.one_shot_only:
+            res.setdefault("one_shot_of", {}).setdefault(a.label, {"build_id": _lib.build_id()})[name] = {
+                k: r[k] for k in ("a_one_shot", "a_one_shot_no_md5")}
+        else:
+            res["workloads"][name] = r
+        print(name, json.dumps(r))
+        del t
+        chunks = None
+        torch.cuda.empty_cache()
+    if a.kernels:
+        return
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print("wrote", a.out)
+
+
 def timed(fn, repeats):
     import torch
 
@@ -188,12 +262,15 @@ def main():
     ap.add_argument("--int24", action="store_true", help="the packed 24-bit leg: profiles/r12_s24.json")
     ap.add_argument("--out-device", action="store_true", help="files left on the GPU: profiles/r18_device_out.json")
     ap.add_argument("--host-only", action="store_true", help="with --out-device: the host-output leg alone")
-    ap.add_argument("--label", default="this_build", help="with --host-only: the record's name")
+    ap.add_argument("--session", action="store_true", help="a session fed 1 s chunks: profiles/r19_session.json")
+    ap.add_argument("--one-shot-only", action="store_true", help="with --session: the one-shot legs alone")
+    ap.add_argument("--label", default="this_build", help="with --host-only / --one-shot-only: the record's name")
     ap.add_argument("--root", default=None, help="measure the package of another checkout")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     a.out = a.out or os.path.join(ROOT, "profiles", "r12_s24.json" if a.int24 else
-                                  "r18_device_out.json" if a.out_device else "r11_encode_device.json")
+                                  "r18_device_out.json" if a.out_device else
+                                  "r19_session.json" if a.session else "r11_encode_device.json")
     if a.root:   # (the package is imported below, never before this line)
         sys.path.insert(0, os.path.abspath(a.root))
     import torch
@@ -203,6 +280,8 @@ def main():
         return int24_leg(a)
     if a.out_device:
         return out_device_leg(a)
+    if a.session:
+        return session_leg(a)
     from flac_codec_amd import _lib
     from flac_codec_amd.encode import BatchEncoder, Options
 
