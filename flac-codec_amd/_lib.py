@@ -201,6 +201,11 @@ class Segment(C.Structure):
     _fields_ = [("pcm", C.c_void_p), ("n_frames", C.c_uint32), ("reserved", C.c_uint32), ("first_frame_number", C.c_uint64)]
 
 
+class RaggedFrame(C.Structure):
+    """flacgpu_ragged_frame: one frame of any length 1 .. block_size in a ragged batch (include/flacenc_gpu.h)."""
+    _fields_ = [("pcm", C.c_void_p), ("samples", C.c_uint32), ("reserved", C.c_uint32), ("frame_number", C.c_uint64)]
+
+
 class GpuStats(C.Structure):
     _fields_ = [
         ("frames", C.c_uint32),
@@ -358,6 +363,11 @@ def _load():
                                           C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.flacgpu_encode_segments_packed_async_host.argtypes = [vp, C.c_void_p, C.c_uint32, C.POINTER(Segment), C.c_uint32,
                                                             C.c_uint32, C.c_void_p, C.c_size_t]
+    L.flacgpu_encode_ragged_device.argtypes = [vp, C.POINTER(RaggedFrame), C.c_uint32, C.c_uint32, vp]
+    u32p = C.POINTER(C.c_uint32)
+    L.flacgpu_ragged_plan.argtypes = [C.POINTER(GpuOptions), u32p, C.c_uint32, u32p, u32p, u32p, C.POINTER(C.c_uint64)]
+    L.flacgpu_ragged_pool_uploads.argtypes = [vp]
+    L.flacgpu_ragged_pool_uploads.restype = C.c_uint64
     sc = C.POINTER(ShardCounters)
     u64p = C.POINTER(C.c_uint64)
     L.flacgpu_merge_counters.argtypes = [sc, C.c_uint32, sc, u64p]

@@ -135,6 +135,15 @@ bool dispatch_autocorr(uint32_t H, const Params &p_in, const Knobs &kn, uint32_t
     }
     return false;
 }
+void launch_autocorr_ragged(uint32_t H, const Params &p, hipStream_t st) {
+    const dim3 grid((p.n_frames * p.ncand + 63) / 64);
+#define AC_RAGGED(h) case h: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_autocorr_ragged<h, 4>), grid, dim3(WG), 0, st, p); break;
+    switch (H) {
+        AC_RAGGED(4) AC_RAGGED(8) AC_RAGGED(12) AC_RAGGED(16) AC_RAGGED(20) AC_RAGGED(24) AC_RAGGED(28) AC_RAGGED(32)
+    default: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_autocorr_ragged<36, 4>), grid, dim3(WG), 0, st, p); break;
+    }
+#undef AC_RAGGED
+}
 void launch_autocorr_mfma(const Params &p, uint32_t blocks, uint32_t n, const double *win, double *ac,
                           hipStream_t st) {
     hipLaunchKernelGGL(k_autocorr_mfma, dim3(blocks), dim3(WG), 0, st, p, n, win, ac);

@@ -32,6 +32,7 @@
 #include "kernels/place_rule.h"
 #include "batch_route.h"
 #include "lpc_host.h"
+#include "ragged_plan.h"
 
 #include <ctype.h>
 #include <math.h>
@@ -80,6 +81,7 @@ Knobs read_knobs() {
     k.no_ac_fma = on("FLACGPU_NO_AC_FMA");
     k.no_hand = on("FLACGPU_NO_HAND");   // A/B: k_frame64 fetches the samples and runs the FIR again (Params::hand_meta off)
     k.no_direct_short = on("FLACGPU_NO_DIRECT_SHORT");   // A/B: the shorter wave block lengths through K0 + k_cand64
+    k.no_ragged = on("FLACGPU_NO_RAGGED");   // A/B: the device front ends' short last blocks one one-frame call each (host/device_blocks.h)
     k.no_w64 = on("FLACGPU_NO_W64");
     k.no_fused_pack = on("FLACGPU_NO_FUSED_PACK");
     k.no_frame64 = on("FLACGPU_NO_FRAME64");
@@ -143,6 +145,20 @@ struct flacgpu_ctx {
     bool seg_pending = false;   // the next analyze_impl belongs to a segments call
     bool seg_active = false;    // the batch in hand is made of segments (frame numbers from d_seg_fn)
     bool seg_direct = false;    // ... read in place (Params::inter_tab)
+    // a RAGGED batch (flacgpu_encode_ragged_device): the per-frame tables (Params::frame_n, frame_win; frame numbers in
+    // d_seg_fn), their pinned staging copy, the run table that gathers the frames into d_in, and the window pool -- kept
+    // between calls: rag_pool_at lists the pool's windows (length, offset in doubles), and a batch whose every length has
+    // one there uploads nothing
+    uint32_t *d_rag_tab = nullptr, *h_rag_tab = nullptr;      // [2][max_frames]: lengths, window offsets
+    PlaceRun *d_rag_runs = nullptr, *h_rag_runs = nullptr;    // [max_frames]
+    double *d_rag_pool = nullptr;
+    uint64_t rag_pool_cap = 0;                                 // doubles
+    std::vector<std::pair<uint32_t, uint32_t>> rag_pool_at;    // sorted by length
+    std::vector<double> rag_pool_host;                         // the upload's source (valid until the next upload)
+    uint64_t rag_pool_uploads = 0;                             // (flacgpu_ragged_pool_uploads: what a test of the reuse reads)
+    std::vector<uint32_t> rag_n;                               // the batch in hand's lengths (host re-decision, fetch_decoded)
+    bool rag_pending = false, rag_active = false;              // as seg_pending / seg_active
+    const uint32_t *k0_frame_n = nullptr;                      // launch_k0's length table: d_rag_tab for a ragged batch
     bool drained = false;       // nothing of this context is in flight (its last batch was waited for, nothing submitted since):
                                 // the asynchronous entries then skip their hipStreamSynchronize -- with more streams than
                                 // hardware queues a synchronise of an IDLE stream still waits behind the other streams' work
@@ -330,21 +346,21 @@ bool launch_k0(flacgpu_ctx *c, const int32_t *d_pcm, int layout, uint32_t n_fram
     if (layout == FLACGPU_LAYOUT_INTERLEAVED && c->channels == 2) {
         unsigned long long *abs = (c->d_abs && c->ncand == 4) ? c->d_abs : nullptr;   // (zeroed by the caller)
         hipLaunchKernelGGL(k_deinterleave2, grid, dim3(WG), 0, st, (const int2 *)d_pcm, c->d_planar, B, c->ldb,
-                           n_frames, last_len, c->d_orbits, c->ncand, f0, abs);
+                           n_frames, last_len, c->d_orbits, c->ncand, f0, abs, c->k0_frame_n);
         c->abs_valid = abs != nullptr;
         return true;
     }
     if (layout == FLACGPU_LAYOUT_INTERLEAVED && c->ncand == c->channels) {
         switch (c->channels) {
 #define X(C) case C: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_deinterleave_n<C>), grid, dim3(WG), 0, st, d_pcm, \
-                                        c->d_planar, B, c->ldb, n_frames, last_len, c->d_orbits, f0); return true;
+                                        c->d_planar, B, c->ldb, n_frames, last_len, c->d_orbits, f0, c->k0_frame_n); return true;
             X(1) X(3) X(4) X(5) X(6) X(7) X(8)
 #undef X
         default: break;
         }
     }
     hipLaunchKernelGGL(k_deinterleave, grid, dim3(WG), 0, st, d_pcm, c->d_planar, c->channels, B, c->ldb,
-                       n_frames, last_len, layout == FLACGPU_LAYOUT_PLANAR, f0);
+                       n_frames, last_len, layout == FLACGPU_LAYOUT_PLANAR, f0, c->k0_frame_n);
     return false;
 }
 
@@ -565,6 +581,9 @@ void flacgpu_destroy(flacgpu_ctx *c) {
     if (c->d_seg_fn) (void)hipFree(c->d_seg_fn);
     if (c->d_seg_ptr) (void)hipFree(c->d_seg_ptr);
     if (c->h_seg) (void)hipHostFree(c->h_seg);
+    (void)hipFree(c->d_rag_tab); (void)hipFree(c->d_rag_runs); (void)hipFree(c->d_rag_pool);
+    if (c->h_rag_tab) (void)hipHostFree(c->h_rag_tab);
+    if (c->h_rag_runs) (void)hipHostFree(c->h_rag_runs);
     (void)hipFree(c->d_edges);
     (void)hipFree(c->d_runs);
     if (c->h_runs) (void)hipHostFree(c->h_runs);
@@ -739,6 +758,8 @@ static int analyze_impl(flacgpu_ctx *c, const int32_t *d_pcm, int layout, uint32
 // context (frame numbers, addresses, the segments ensure_planar would walk) must not reach its frame assembly or verifier.
 static void begin_plain_batch(flacgpu_ctx *c) {
     c->seg_active = c->seg_pending = c->seg_direct = false;
+    c->rag_active = c->rag_pending = false;
+    c->k0_frame_n = nullptr;
     c->segs.clear();
 }
 
@@ -793,12 +814,17 @@ static int analyze_impl(flacgpu_ctx *c, const int32_t *d_pcm, int layout, uint32
         if (c->seg_pending) {
             c->seg_active = true;
             c->seg_pending = false;
+            c->rag_active = c->rag_pending;   // (a ragged batch announces itself as a segments batch does: frame numbers from d_seg_fn)
+            c->rag_pending = false;
+            c->k0_frame_n = c->rag_active ? c->d_rag_tab : nullptr;
         } else {
             begin_plain_batch(c);
         }
     }
     const uint32_t B = c->opts.block_size;
+    const bool ragged = c->rag_active;   // (its lengths were checked by flacenc_ragged::plan, its windows lie in the pool)
     // the reference collects partitions into ArrayVec<_, 64> and panics beyond (encode.rs:3880)
+    if (!ragged)
     for (uint32_t n : {n_frames > 1 ? B : last_len, last_len}) {
         uint32_t tz = (uint32_t)__builtin_ctz(n);
         if ((tz < c->opts.max_partition_order ? tz : c->opts.max_partition_order) > (uint32_t)MAXP) {
@@ -806,12 +832,17 @@ static int analyze_impl(flacgpu_ctx *c, const int32_t *d_pcm, int layout, uint32
             return FLACGPU_ERR_UNSUPPORTED;
         }
     }
-    if (last_len != B && last_len != c->window_last_len) {
+    if (!ragged && last_len != B && last_len != c->window_last_len) {
         if (int rc = upload_window(c, last_len, c->d_window_last, st)) return rc;
         c->window_last_len = last_len;
     }
     Params p;
     fill_params(c, n_frames, last_len, p);
+    if (ragged) {
+        p.frame_n = c->d_rag_tab;
+        p.frame_win = c->d_rag_tab + c->max_frames;
+        p.window_pool = c->d_rag_pool;
+    }
     c->host_out = nullptr;   // a new batch: frames go to d_packed unless flacgpu_encode_packed_async_host says otherwise
     c->out_in_host = false;
 
@@ -904,13 +935,15 @@ static int analyze_impl(flacgpu_ctx *c, const int32_t *d_pcm, int layout, uint32
         begin(3);
         // the whole blocks (of this range) in one launch, the in-place kernels with K4 in their tail; a short last frame
         // in one of its own
-        const uint32_t full = (last_len == B) ? n_frames : n_frames - 1;
+        // (a ragged batch: every frame in ONE launch of the kernel that takes each candidate's length and window from the tables)
+        const uint32_t full = ragged ? 0u : (last_len == B) ? n_frames : n_frames - 1;
         const uint32_t ac_n = ranged ? rcnt : full;
+        if (ragged) launch_autocorr_ragged(H, p, st);
         if (ac_n && dispatch_autocorr(H, p, c->knobs, rf0, ac_n, B, c->d_window_full, st) != r.k4_in_autocorr) {
             g_last_error = "internal: the autocorrelation launcher and the route disagree about K4";
             return FLACGPU_ERR_UNSUPPORTED;
         }
-        if (full != n_frames) (void)dispatch_autocorr(H, p, c->knobs, full, 1, last_len, c->d_window_last, st);
+        if (full != n_frames && !ragged) (void)dispatch_autocorr(H, p, c->knobs, full, 1, last_len, c->d_window_last, st);
         if (!r.k4_in_autocorr || full != n_frames) {
             begin(4);
             launch_lpc(p, (ncb + 63) / 64, st);
@@ -1011,7 +1044,8 @@ static int resolve_order_ties(flacgpu_ctx *c) {
             if (int rc = copy_sync(c, &info, c->d_cinfo + idx, sizeof info, hipMemcpyDeviceToHost)) return rc;
         }
         const uint32_t frame = idx / p.ncand;
-        const uint32_t n = (frame + 1 == p.n_frames) ? p.last_len : p.block_size;
+        const uint32_t n = (c->rag_active && frame < c->rag_n.size()) ? c->rag_n[frame]   // (frame_len()'s rule on the host)
+                           : (frame + 1 == p.n_frames) ? p.last_len : p.block_size;
         flacenc::HostLpc h;
         flacenc::lpc_from_autocorr(row, p.max_lpc_order, n, info.bps, &h);
         HIP_TRY(hipMemcpyAsync(c->d_lpc + idx, &h, sizeof h, hipMemcpyHostToDevice, st));
@@ -1392,6 +1426,135 @@ int flacgpu_encode_segments(flacgpu_ctx *c, const flacgpu_segment *segs, uint32_
     }
     return flacgpu_fetch_frames(c, out, cap, offsets, total);
 }
+
+// ---- a RAGGED batch: frames of any length 1 .. block_size, of any streams of the context's shape, analysed and assembled as
+// ONE batch on the generic kernels (Params::frame_n).  What a front end's short last blocks need: one call for the tails of
+// a whole batch of streams instead of one one-frame call each.
+int flacgpu_ragged_plan(const flacgpu_options *opts, const uint32_t *samples, uint32_t n_frames, uint32_t *window_of,
+                        uint32_t *distinct, uint32_t *n_distinct, uint64_t *pool_doubles) {
+    if (!opts) {
+        g_last_error = "flacgpu_ragged_plan: no options";
+        return FLACGPU_ERR_INVALID_ARG;
+    }
+    static_assert(flacenc_ragged::kInvalidArg == FLACGPU_ERR_INVALID_ARG && flacenc_ragged::kUnsupported == FLACGPU_ERR_UNSUPPORTED,
+                  "the plan's codes are the ABI's");
+    return flacenc_ragged::plan(opts->block_size, opts->max_partition_order, samples, n_frames, window_of, distinct, n_distinct,
+                                pool_doubles, &g_last_error);
+}
+
+static int ensure_ragged_tables(flacgpu_ctx *c) {   // (allocated by the first ragged call of the context)
+    const size_t F = c->max_frames;
+    if (c->d_rag_tab) return FLACGPU_OK;
+    HIP_TRY(hipHostMalloc((void **)&c->h_rag_tab, sizeof(uint32_t) * 2 * F, hipHostMallocDefault));
+    HIP_TRY(hipHostMalloc((void **)&c->h_rag_runs, sizeof(PlaceRun) * F, hipHostMallocDefault));
+    HIP_TRY(hipMalloc((void **)&c->d_rag_runs, sizeof(PlaceRun) * F));
+    HIP_TRY(hipMalloc((void **)&c->d_rag_tab, sizeof(uint32_t) * 2 * F));
+    return FLACGPU_OK;
+}
+
+int flacgpu_encode_ragged_device(flacgpu_ctx *c, const flacgpu_ragged_frame *frames, uint32_t n_frames, uint32_t sample_rate,
+                                 void *stream) {
+    if (!c) return FLACGPU_ERR_INVALID_ARG;
+    if (!frames || n_frames == 0 || n_frames > c->max_frames) {
+        g_last_error = "flacgpu_encode_ragged_device: no frames, or more than the context was created for";
+        return FLACGPU_ERR_INVALID_ARG;
+    }
+    // every check before anything is launched or any state of the batch in hand is touched
+    std::vector<uint32_t> lens(n_frames), win_of(n_frames), distinct(n_frames);
+    for (uint32_t f = 0; f < n_frames; f++) {
+        if (!frames[f].pcm || ((uintptr_t)frames[f].pcm & 3u) || frames[f].reserved) {
+            g_last_error = "flacgpu_encode_ragged_device: frame " + std::to_string(f) + ": no PCM, PCM not 4-byte aligned, or reserved != 0";
+            return FLACGPU_ERR_INVALID_ARG;
+        }
+        lens[f] = frames[f].samples;
+    }
+    uint32_t n_distinct = 0;
+    uint64_t pool_doubles = 0;
+    if (int rc = flacenc_ragged::plan(c->opts.block_size, c->opts.max_partition_order, lens.data(), n_frames, win_of.data(),
+                                      distinct.data(), &n_distinct, &pool_doubles, &g_last_error))
+        return rc;
+    CTX_GUARD(c);
+    hipStream_t st;
+    if (int rc = resolve_stream(c, stream, &st)) return rc;
+    if (int rc = ensure_segment_tables(c)) return rc;   // (frame numbers: the segments' table)
+    if (int rc = ensure_ragged_tables(c)) return rc;
+    // the staging arrays and the device tables of the batch before are free once BOTH streams are idle (segments_common)
+    HIP_TRY(hipStreamSynchronize(st));
+    if (int rc = ctx_sync(c)) return rc;
+    const size_t F = c->max_frames, B = c->opts.block_size, C = c->channels;
+    // ---- the window pool: kept between calls; a batch whose every length has a window there uploads nothing
+    auto pool_find = [&](uint32_t n) -> const std::pair<uint32_t, uint32_t> * {
+        auto it = std::lower_bound(c->rag_pool_at.begin(), c->rag_pool_at.end(), std::make_pair(n, 0u));
+        return (it != c->rag_pool_at.end() && it->first == n) ? &*it : nullptr;
+    };
+    bool have_all = true;
+    for (uint32_t d = 0; d < n_distinct && have_all; d++) have_all = pool_find(distinct[d]) != nullptr;
+    if (!have_all) {   // this batch's plan becomes the pool: one window per distinct length in first-appearance order, one copy
+        if (pool_doubles > c->rag_pool_cap) {
+            (void)hipFree(c->d_rag_pool);
+            c->d_rag_pool = nullptr;
+            c->rag_pool_cap = 0;
+            c->rag_pool_at.clear();
+            const uint64_t cap = pool_doubles + pool_doubles / 2;
+            HIP_TRY(hipMalloc((void **)&c->d_rag_pool, sizeof(double) * cap));
+            c->rag_pool_cap = cap;
+        }
+        c->rag_pool_at.clear();
+        c->rag_pool_host.assign((size_t)pool_doubles, 0.0);
+        std::vector<double> w;
+        uint64_t at = 0;
+        for (uint32_t d = 0; d < n_distinct; d++) {
+            // on the host: cos() on the device is not the host's, and the bytes would differ (window_generate)
+            window_generate(c->opts.window_kind, c->opts.window_param, distinct[d], w);
+            memcpy(c->rag_pool_host.data() + at, w.data(), sizeof(double) * distinct[d]);
+            c->rag_pool_at.emplace_back(distinct[d], (uint32_t)at);
+            at += (uint64_t)distinct[d] + flacenc_ragged::kWindowPad;   // (<= 65535 lengths of <= 65535 + 64 doubles: < 2^32)
+        }
+        std::sort(c->rag_pool_at.begin(), c->rag_pool_at.end());
+        HIP_TRY(hipMemcpyAsync(c->d_rag_pool, c->rag_pool_host.data(), sizeof(double) * (size_t)pool_doubles, hipMemcpyHostToDevice, st));
+        c->rag_pool_uploads++;
+    }
+    // ---- the per-frame tables, and the frames' samples to the heads of their slots of d_in in ONE launch (k_place_runs)
+    uint32_t *hn = c->h_rag_tab, *hw = c->h_rag_tab + F;
+    uint64_t *fn = c->h_seg;
+    uint64_t groups = 0;
+    for (uint32_t f = 0; f < n_frames; f++) {
+        hn[f] = lens[f];
+        hw[f] = pool_find(lens[f])->second;
+        fn[f] = frames[f].frame_number;
+        PlaceRun &r = c->h_rag_runs[f];
+        r.src = reinterpret_cast<uintptr_t>(frames[f].pcm);
+        r.dst = reinterpret_cast<uintptr_t>(c->d_in + (size_t)f * B * C);
+        r.n = (uint64_t)lens[f] * C * sizeof(int32_t);
+        r.group0 = groups;
+        groups += place_groups(r.dst, r.n);
+    }
+    HIP_TRY(hipMemcpyAsync(c->d_rag_tab, hn, sizeof(uint32_t) * n_frames, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(c->d_rag_tab + F, hw, sizeof(uint32_t) * n_frames, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(c->d_seg_fn, fn, sizeof(uint64_t) * n_frames, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(c->d_rag_runs, c->h_rag_runs, sizeof(PlaceRun) * n_frames, hipMemcpyHostToDevice, st));
+    if (int rc = launch_place_runs(c->d_rag_runs, n_frames, groups, st)) return rc;
+    c->rag_n = lens;
+    c->segs.clear();
+    c->seg_pending = true;
+    c->rag_pending = true;
+    c->seg_direct = false;
+    c->rng_f0 = c->rng_cnt = 0;
+    RouteBatch rb;
+    rb.n_frames = n_frames;
+    rb.last_len = lens[n_frames - 1];
+    rb.layout = FLACGPU_LAYOUT_INTERLEAVED;
+    rb.ragged = true;
+    const Route route = flacenc_route::plan_route(route_context_of(c), rb);
+    if (int rc = analyze_impl(c, c->d_in, FLACGPU_LAYOUT_INTERLEAVED, n_frames, lens[n_frames - 1], st, 0, &route)) {
+        c->seg_pending = c->rag_pending = false;   // (refused before the analysis took the announcement)
+        return rc;
+    }
+    return pack_impl(c, frames[0].frame_number, sample_rate, st, nullptr);
+}
+
+// how often this context has uploaded its ragged window pool (a test of the pool's reuse reads it)
+uint64_t flacgpu_ragged_pool_uploads(const flacgpu_ctx *c) { return c ? c->rag_pool_uploads : 0; }
 
 int flacgpu_fetch_frames(flacgpu_ctx *c, uint8_t *out, size_t cap, uint64_t *offsets,
                          uint64_t *total) {
@@ -1880,7 +2043,7 @@ int flacgpu_wait(flacgpu_ctx *c) {
 int flacgpu_experiment_mfma_autocorr(flacgpu_ctx *c, float *kernel_ms, uint32_t *compared,
                                      uint32_t *params_differ, double *max_rel_err) {
     if (!c || c->last_frames == 0 || c->opts.max_lpc_order == 0 || c->opts.max_lpc_order > 16 ||
-        c->last_len != c->opts.block_size) {
+        c->last_len != c->opts.block_size || c->rag_active) {
         g_last_error = "mfma experiment: needs an analysed batch of full blocks with 1 <= max_lpc_order <= 16";
         return FLACGPU_ERR_INVALID_ARG;
     }
@@ -2005,7 +2168,7 @@ int flacgpu_fetch_decoded(flacgpu_ctx *c, int32_t *interleaved) {
     if (int rc = copy_sync(c, planar.data(), c->d_decoded, sizeof(int32_t) * planar.size(), hipMemcpyDeviceToHost)) return rc;
     size_t o = 0;
     for (size_t f = 0; f < F; f++) {
-        const size_t n = (f + 1 == F) ? c->last_len : B;
+        const size_t n = (c->rag_active && f < c->rag_n.size()) ? c->rag_n[f] : (f + 1 == F) ? c->last_len : B;
         for (size_t i = 0; i < n; i++)
             for (size_t ch = 0; ch < C; ch++) interleaved[o++] = planar[(f * C + ch) * ldb + i];
     }

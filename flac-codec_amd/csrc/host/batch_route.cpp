@@ -31,6 +31,9 @@ bool fits_lds(uint32_t fb_words) { return (size_t)fb_words * sizeof(int32_t) <= 
 
 Route plan_route(const RouteContext &c, const RouteBatch &b) {
     Route r;
+    // a ragged batch: every frame on the generic kernels (analysis and assembly), its samples gathered into the context's
+    // input buffer and split by K0 -- nothing read in place, nothing cut, no host output
+    if (b.ragged) return r;
     const Knobs &kn = c.knobs;
     const uint32_t B = c.block_size, C_ = c.channels, n_frames = b.n_frames;
     const bool whole_blocks = b.last_len == B;

@@ -40,6 +40,7 @@ struct RouteBatch {
     uint32_t packed_bytes = 0;       // != 0: stream-width little-endian samples in the context's input buffer
     bool segments_in_place_wanted = false;   // a batch of device segments that would rather not be gathered
     bool whole_call = false;         // flacgpu_encode_device: analysis and assembly in one call, so the batch may be cut
+    bool ragged = false;             // every frame has a length of its own (flacgpu_encode_ragged_device; last_len: the last frame's)
 };
 
 struct Route {

@@ -16,8 +16,10 @@
 //   * whole blocks: batches of segments planned as flacenc_encode_many_coalesced plans them (plan_stream_batches), on two
 //     pooled contexts in rotation -- batch i + 1 is submitted before batch i's frames are fetched into its pinned buffer,
 //     so one batch's kernels run while the other's frames cross the link -- and copied once to their places in `out`;
-//   * a stream's short last block: a one-frame flacgpu_encode_device call on the staging pointer (two one-frame contexts
-//     in rotation), as coalesce.cpp does from host PCM;
+//   * the streams' short last blocks: ragged batches (flacgpu_encode_ragged_device) on the staging pointers, each of up
+//     to a pooled context's frames -- all the tails of a call of up to a few thousand streams in ONE batch
+//     (encode_tail_blocks, device_blocks.h).  FLACGPU_NO_RAGGED=1 keeps the loop this replaced, a one-frame
+//     flacgpu_encode_device call per stream on two one-frame contexts in rotation (what coalesce.cpp does from host PCM);
 //   * everything in front of the first frame: flacenc_stream_header, as in coalesce.cpp.
 // The whole-block loop (encode_whole_blocks, device_blocks.h) is shared with the chunk-by-chunk sessions of
 // device_session.cpp.
@@ -33,6 +35,7 @@
 
 #include "../kernels/ingest_rule.h"
 #include "../kernels/sample_types.h"
+#include "../kernels/shape.h"   // Knobs
 #include "device_blocks.h"
 #include "host_internal.h"
 
@@ -207,8 +210,23 @@ int encode_impl(const flacenc_options *opts, const void *d_pcm, const flacenc_te
 
 }  // namespace
 
+Knobs read_knobs();   // flacenc_gpu.hip: every FLACGPU_* selector is read there
+
 namespace flacenc_host {
 void release_device_batch_pool() { IngestPool::get().release_all(); }
+
+bool tails_one_by_one() {
+    static const bool v = read_knobs().no_ragged;   // (once: knobs do not change under a running process)
+    return v;
+}
+namespace {
+thread_local uint64_t g_tail_frames = 0, g_tail_batches = 0;
+}
+void tail_stats_reset() { g_tail_frames = g_tail_batches = 0; }
+void tail_stats_add(uint64_t frames, uint64_t batches) {
+    g_tail_frames += frames;
+    g_tail_batches += batches;
+}
 }  // namespace flacenc_host
 
 extern "C" {
@@ -221,6 +239,11 @@ int32_t flacenc_ingest_sample(uint32_t sample_type, uint32_t raw_bits, uint32_t 
         v = ingest_sample(sample_type, raw_bits, bits_per_sample, &a);
     if (altered) *altered = a;
     return v;
+}
+
+void flacenc_device_tail_stats(uint64_t *tail_frames, uint64_t *tail_batches) {
+    if (tail_frames) *tail_frames = flacenc_host::g_tail_frames;
+    if (tail_batches) *tail_batches = flacenc_host::g_tail_batches;
 }
 
 int flacenc_device_batch_plan(const flacenc_options *opts, const flacenc_tensor_format *fmt, uint32_t bits_per_sample,
@@ -236,6 +259,7 @@ int flacenc_device_batch_plan(const flacenc_options *opts, const flacenc_tensor_
 int flacenc_encode_many_device(const flacenc_options *opts, const void *d_pcm, const flacenc_tensor_format *fmt,
                                uint32_t sample_rate, uint32_t bits_per_sample, uint32_t channels, flacenc_device_job *jobs,
                                size_t n_jobs, uint32_t flags, void *stream) {
+    tail_stats_reset();   // (flacenc_device_tail_stats: this call's, also when it is refused or ends before its tails)
     uint64_t in_elements = 0, staging_elements = 0;
     std::vector<uint64_t> staging_off;
     if (int rc = plan_impl(opts, fmt, bits_per_sample, channels, jobs, n_jobs, &in_elements, &staging_elements, &staging_off))
@@ -264,6 +288,7 @@ int flacenc_encode_many_device_out(const flacenc_options *opts, const void *d_pc
                                    uint32_t sample_rate, uint32_t bits_per_sample, uint32_t channels,
                                    flacenc_device_out_job *jobs, size_t n_jobs, void *d_out, size_t d_out_bytes, uint32_t flags,
                                    void *stream) {
+    tail_stats_reset();
     uint64_t in_elements = 0, staging_elements = 0;
     std::vector<uint64_t> staging_off;
     if (int rc = plan_impl(opts, fmt, bits_per_sample, channels, jobs, n_jobs, &in_elements, &staging_elements, &staging_off))
@@ -389,47 +414,43 @@ int encode_impl(const flacenc_options *opts, const void *d_pcm, const flacenc_te
         for (size_t i = 0; i < n_jobs; i++)
             if (whole[i]) fail(i, whole_rc);
 
-    // ---- the short last blocks: one frame each, two one-frame contexts in rotation
+    // ---- the short last blocks: ragged batches of up to a pooled context's frames (encode_tail_blocks; under
+    // FLACGPU_NO_RAGGED one frame each on two one-frame contexts in rotation).  Host output: the batch is fetched once and
+    // every tail copied out; device output: all its tails placed by ONE flacgpu_place_frames call, one run per tail
     std::vector<size_t> tails;
+    std::vector<TailFrame> tail_frames;
     for (size_t i = 0; i < n_jobs; i++)
-        if (!jobs[i].status && st[i].tail) tails.push_back(i);
+        if (!jobs[i].status && st[i].tail) {
+            tails.push_back(i);
+            tail_frames.push_back(TailFrame{d_staging + staging_off[i] + st[i].whole * per, st[i].tail, st[i].whole});
+        }
     if (!tails.empty()) {
-        PooledContext slot[2] = {};
-        const size_t n_slots = std::min<size_t>(2, tails.size());
-        size_t have = 0;
-        int rc = 0;
-        for (; have < n_slots && !rc; have++) rc = pooled_context_take(g, bps, ch, 1u, device, &slot[have]);
-        if (rc) have--;
-        const auto submit = [&](size_t t) {
-            const size_t i = tails[t];
-            return flacgpu_encode_device(slot[t % 2].ctx, d_staging + staging_off[i] + st[i].whole * per,
-                                         FLACGPU_LAYOUT_INTERLEAVED, 1, st[i].tail, st[i].whole, sample_rate, nullptr);
-        };
-        if (!rc) rc = submit(0);
-        for (size_t t = 0; t < tails.size() && !rc; t++) {
-            if (t + 1 < tails.size()) rc = submit(t + 1);
-            if (rc) break;
-            const PooledContext &s = slot[t % 2];
-            Stream &sm = st[tails[t]];
-            uint64_t total = 0, off2[2] = {0, 0};
-            rc = kDeviceOut ? flacgpu_frame_offsets(s.ctx, off2, &total) : flacgpu_fetch_frames(s.ctx, s.out, s.out_cap, off2, &total);
-            if (rc) break;
-            sm.sizes[sm.whole] = (uint32_t)total;
-            sm.tail_len = (size_t)total;
-            sm.tail_done = true;
-            if (!kDeviceOut) {
-                sm.tail_bytes.assign(s.out, s.out + total);
-            } else if (sm.hlen + sm.pos + total <= jobs[tails[t]].out_cap) {   // (else: FLACENC_ERR_IO where the header is built)
-                const flacgpu_place_run run{0, address(place_of(jobs[tails[t]], d_out) + sm.hlen + sm.pos), total};
-                rc = flacgpu_place_frames(s.ctx, &run, 1);
-                sm.tail_placed = !rc;
-            }
-        }
-        const int tail_rc = rc ? gpu_error(rc) : 0;
-        for (size_t k = 0; k < have; k++) {
-            (void)flacgpu_wait(slot[k].ctx);
-            pooled_context_give(g, bps, ch, 1u, device, slot[k]);
-        }
+        std::vector<size_t> placing;
+        const int tail_rc = encode_tail_blocks(
+            g, bps, ch, device, sample_rate, tail_frames, !kDeviceOut, false,
+            [&](const PooledContext &s, size_t t0, size_t count, const std::vector<uint64_t> &off) {
+                runs.clear();
+                placing.clear();
+                for (size_t k = 0; k < count; k++) {
+                    const size_t i = tails[t0 + k];
+                    Stream &sm = st[i];
+                    const uint64_t total = off[k + 1] - off[k];
+                    sm.sizes[sm.whole] = (uint32_t)total;
+                    sm.tail_len = (size_t)total;
+                    sm.tail_done = true;
+                    if (!kDeviceOut) {
+                        sm.tail_bytes.assign(s.out + off[k], s.out + off[k + 1]);
+                    } else if (sm.hlen + sm.pos + total <= jobs[i].out_cap) {   // (else: FLACENC_ERR_IO where the header is built)
+                        runs.push_back(flacgpu_place_run{off[k], address(place_of(jobs[i], d_out) + sm.hlen + sm.pos), total});
+                        placing.push_back(i);
+                    }
+                }
+                if (!kDeviceOut || runs.empty()) return (int)FLACGPU_OK;
+                const int rc = flacgpu_place_frames(s.ctx, runs.data(), (uint32_t)runs.size());
+                if (!rc)
+                    for (size_t i : placing) st[i].tail_placed = true;
+                return rc;
+            });
         if (tail_rc)
             for (size_t i : tails)
                 if (!st[i].tail_done || (kDeviceOut && !st[i].tail_placed && !jobs[i].status)) fail(i, tail_rc);

@@ -277,6 +277,7 @@ int flacenc_device_session_write(flacenc_device_session *s, const void *d_pcm, c
 }
 
 int flacenc_device_session_finalize(flacenc_device_session *s, flacenc_session_final *finals) {
+    tail_stats_reset();   // (flacenc_device_tail_stats: this call's, also when it is refused)
     if (!s || (!finals && !s->st.empty())) return refuse(FLACENC_ERR_INVALID_ARG, "a null argument");
     if (s->finalized) return refuse(FLACENC_ERR_FINALIZED, "finalize after finalize");
     if (s->gpu_rc) return s->gpu_rc;
@@ -294,40 +295,31 @@ int flacenc_device_session_finalize(flacenc_device_session *s, flacenc_session_f
         f.status = m.status;
         if (!m.status && m.carry) tails.push_back(i);
     }
-    // ---- the short last blocks: one frame each, two one-frame contexts in rotation (as the one-shot call)
+    // ---- the short last blocks: one frame each, two one-frame contexts in rotation (encode_tail_blocks, device_blocks.h,
+    // with one_by_one set).  NOT as ragged batches like the one-shot call: with them the 256-tracks session measured above
+    // the parent commit's maximum (DESIGN.md 4c "Short last blocks as one batch", the regression condition), and a front
+    // end whose leg fails that condition keeps the one-frame loop
     if (!tails.empty()) {
-        PooledContext slot[2] = {};
-        const size_t n_slots = std::min<size_t>(2, tails.size());
-        size_t have = 0;
-        int rc = 0;
-        for (; have < n_slots && !rc; have++) rc = pooled_context_take(s->g, s->bps, ch, 1u, s->device, &slot[have]);
-        if (rc) have--;
-        const auto submit = [&](size_t t) {
-            const Stream &m = s->st[tails[t]];
-            return flacgpu_encode_device(slot[t % 2].ctx, s->d_staging + s->place(tails[t], s->half) - (size_t)m.carry * ch,
-                                         FLACGPU_LAYOUT_INTERLEAVED, 1, m.carry, m.sizes.size(), s->sample_rate, nullptr);
-        };
-        if (!rc) rc = submit(0);
-        for (size_t t = 0; t < tails.size() && !rc; t++) {
-            if (t + 1 < tails.size()) rc = submit(t + 1);
-            if (rc) break;
-            const PooledContext &c = slot[t % 2];
-            flacenc_session_final &f = finals[tails[t]];
-            uint64_t total = 0, off2[2] = {0, 0};
-            rc = flacgpu_fetch_frames(c.ctx, c.out, c.out_cap, off2, &total);
-            if (rc) break;
-            if (!f.tail || total > f.tail_cap) {
-                s->st[tails[t]].status = f.status = FLACENC_ERR_IO;
-                continue;
-            }
-            std::memcpy(f.tail, c.out, (size_t)total);
-            f.tail_len = (size_t)total;
+        std::vector<TailFrame> tail_frames;
+        for (size_t i : tails) {
+            const Stream &m = s->st[i];
+            tail_frames.push_back(TailFrame{s->d_staging + s->place(i, s->half) - (size_t)m.carry * ch, m.carry, m.sizes.size()});
         }
-        const int tail_rc = rc ? device_gpu_error(rc) : 0;
-        for (size_t k = 0; k < have; k++) {
-            (void)flacgpu_wait(slot[k].ctx);
-            pooled_context_give(s->g, s->bps, ch, 1u, s->device, slot[k]);
-        }
+        const int tail_rc = encode_tail_blocks(
+            s->g, s->bps, ch, s->device, s->sample_rate, tail_frames, true, true,
+            [&](const PooledContext &c, size_t t0, size_t count, const std::vector<uint64_t> &off) {
+                for (size_t k = 0; k < count; k++) {
+                    flacenc_session_final &f = finals[tails[t0 + k]];
+                    const uint64_t total = off[k + 1] - off[k];
+                    if (!f.tail || total > f.tail_cap) {
+                        s->st[tails[t0 + k]].status = f.status = FLACENC_ERR_IO;
+                        continue;
+                    }
+                    std::memcpy(f.tail, c.out + off[k], (size_t)total);
+                    f.tail_len = (size_t)total;
+                }
+                return (int)FLACGPU_OK;
+            });
         if (tail_rc) s->gpu_rc = tail_rc;
     }
     // ---- the digests, then every stream's metadata

@@ -942,6 +942,148 @@ k_autocorr2(Params p, uint32_t frame0, uint32_t nframes, uint32_t n, const doubl
 }
 
 // ---------------------------------------------------------------------------------
+// K3 for a RAGGED batch (Params::frame_n): k_autocorr2's scheme -- 64 candidates per workgroup, lane = candidate, wave = lag
+// group, the samples through LDS tiles -- with every candidate's length n and window taken from the per-frame tables.
+//   * One workgroup keeps 64 candidates of MIXED lengths; nothing is ordered by length on the host.  The tile loop runs to
+//     the group's longest frame (nmax, the same in all four waves: each holds the same 64 candidates).
+//   * A lane past its own n adds NOTHING: its terms are skipped by the per-sample guard of ac_block_w (base + s < n), never
+//     formed and added as zeros -- so each lag's sum is the reference's left fold over i < n, one multiply and one add per
+//     term, in exactly the instruction sequence k_autocorr2 runs for a batch whose frames all have this n (there the guard
+//     is the short last tile's).  The -0.0 start and the order of the adds are ac_wave's.
+//   * The window value is per lane (window_pool + frame_win[frame] + i), read only for i < n; beyond, the converted sample
+//     is 0.0 and is never used.  The staged rows are read up to the tile's end like k_autocorr2's (planar rows, < ldb).
+//   * A tile that every lane of the wave has in full takes the unguarded blocks (wave-uniform test).
+// ---------------------------------------------------------------------------------
+template <int H, int A, int LG, int KB, int LDT, int LDW, int NW>
+__device__ __forceinline__ void ac_wave_ragged(const Params &p, int32_t (*tile)[AC_MAXROWS * LDT], double *wt) {
+    constexpr int TS = H * KB;          // samples per tile
+    constexpr int Q = TS / 4;           // int4 per row per tile
+    constexpr int NT = 64 * NW;         // threads per workgroup
+    constexpr int NLOAD = (AC_MAXROWS * Q + NT - 1) / NT;
+    constexpr int CW = (TS + NW - 1) / NW;  // columns converted per wave
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t total = p.n_frames * p.ncand;
+    const uint32_t cand0 = blockIdx.x * 64;
+    const uint32_t last_c = cand0 + 63 < total ? cand0 + 63 : total - 1;
+    const bool live = cand0 + lane < total;
+    const uint32_t cc = live ? cand0 + lane : last_c;
+    const uint32_t f_lo = cand0 / p.ncand, f_hi = last_c / p.ncand;
+    const uint32_t frame = cc / p.ncand;
+    const uint32_t cand = cc % p.ncand;
+    const uint32_t nrows = (f_hi - f_lo + 1) * p.channels;
+    const int32_t *gbase = p.planar + (size_t)f_lo * p.channels * p.ldb;
+    const uint32_t n = p.frame_n[frame];                       // this lane's frame length
+    const double *__restrict__ win = p.window_pool + p.frame_win[frame];
+    uint32_t nmax = n;                                         // the longest frame of the group
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const uint32_t o = (uint32_t)__shfl_xor((int)nmax, off, 64);
+        nmax = o > nmax ? o : nmax;
+    }
+    nmax = (uint32_t)__builtin_amdgcn_readfirstlane((int)nmax);
+    // this lane's two source rows inside the staged set
+    uint32_t ca = cand, cb = cand;
+    int mode = 0;
+    if (p.stereo4) {
+        if (cand >= 2) { ca = 0; cb = 1; mode = cand == 2 ? 1 : 2; }
+    }
+    const uint32_t ra = (frame - f_lo) * p.channels + ca;
+    const uint32_t rb = (frame - f_lo) * p.channels + cb;
+    const CandInfo ci = p.cinfo[(size_t)frame * p.ncand + cand];
+    const uint32_t wasted = (ci.active && !ci.is_const) ? ci.wasted : 0;
+
+    double hist[H], acc[LG];
+#pragma unroll
+    for (int k = 0; k < LG; k++) acc[k] = -0.0;  // f64 `sum()` identity
+#pragma unroll
+    for (int s = 0; s < H; s++) hist[s] = 0.0;
+
+    const uint32_t ntiles = (nmax + TS - 1) / TS;
+    int4 stage[NLOAD];
+    auto fetch = [&](uint32_t t) {
+#pragma unroll
+        for (int k = 0; k < NLOAD; k++) {
+            const uint32_t idx = tid + k * NT;
+            const uint32_t r = idx / Q, c4 = idx - r * Q;
+            const uint32_t col = t * TS + 4 * c4;
+            stage[k] = (r < nrows && col < p.ldb)
+                           ? *reinterpret_cast<const int4 *>(gbase + (size_t)r * p.ldb + col)
+                           : make_int4(0, 0, 0, 0);
+        }
+    };
+    auto commit = [&](uint32_t buf) {
+#pragma unroll
+        for (int k = 0; k < NLOAD; k++) {
+            const uint32_t idx = tid + k * NT;
+            const uint32_t r = idx / Q, c4 = idx - r * Q;
+            if (r < AC_MAXROWS) *reinterpret_cast<int4 *>(&tile[buf][r * LDT + 4 * c4]) = stage[k];
+        }
+    };
+    fetch(0);
+    commit(0);
+    __syncthreads();
+    double *tw = wt + lane * LDW;  // this lane's candidate row of windowed samples
+    for (uint32_t t = 0; t < ntiles; t++) {
+        const uint32_t buf = t & 1;
+        const uint32_t tbase = t * TS;
+        if (t + 1 < ntiles) fetch(t + 1);
+        {   // wave `wave` converts columns [wave*CW, wave*CW + CW) of all 64 candidates
+            const int32_t *ta = &tile[buf][ra * LDT];
+            const int32_t *tb = &tile[buf][rb * LDT];
+#pragma unroll
+            for (int c = 0; c < CW; c++) {
+                const uint32_t col = wave * CW + c;
+                if (col < (uint32_t)TS) {
+                    const uint32_t i = tbase + col;
+                    double v = 0.0;
+                    if (i < n) v = (double)(combine(mode, ta[col], tb[col]) >> wasted) * win[i];
+                    tw[col] = v;
+                }
+            }
+        }
+        __syncthreads();
+        if (t > 0 && __all(tbase + TS <= n)) {   // (wave-uniform)
+#pragma unroll 1
+            for (int b = 0; b < KB; b++)
+                ac_block_w<H, A, LG, false, false>(hist, acc, tw, b * H, tbase + b * H, n);
+        } else {
+#pragma unroll 1
+            for (int b = 0; b < KB; b++) {
+                const uint32_t base = tbase + b * H;
+                if (base >= nmax) break;
+                if (base == 0) ac_block_w<H, A, LG, true, true>(hist, acc, tw, b * H, base, n);
+                else ac_block_w<H, A, LG, false, true>(hist, acc, tw, b * H, base, n);
+            }
+        }
+        if (t + 1 < ntiles) commit(buf ^ 1);
+        __syncthreads();
+    }
+    if (live) {
+        double *out = p.ac + ((size_t)frame * p.ncand + cand) * AC_LD + A;
+#pragma unroll
+        for (int k = 0; k < LG; k++) out[k] = acc[k];
+    }
+}
+
+template <int H, int NW>
+__global__ void __launch_bounds__(64 * NW)
+k_autocorr_ragged(Params p) {
+    static_assert(NW == 4, "four lag-group waves");
+    constexpr int LG = H / NW;       // lags per wave (lag group)
+    constexpr int KB = (AC_TILE / H) > 0 ? (AC_TILE / H) : 1;
+    constexpr int LDT = H * KB + 4;  // int row stride: 16-byte aligned rows
+    constexpr int LDW = H * KB + 1;  // f64 row stride: odd => lanes (= rows) hit distinct banks
+    __shared__ __attribute__((aligned(16))) int32_t tile[2][AC_MAXROWS * LDT];
+    __shared__ double wt[64 * LDW];
+    switch (threadIdx.x >> 6) {
+    case 0: ac_wave_ragged<H, 0 * LG, LG, KB, LDT, LDW, NW>(p, tile, wt); break;
+    case 1: ac_wave_ragged<H, 1 * LG, LG, KB, LDT, LDW, NW>(p, tile, wt); break;
+    case 2: ac_wave_ragged<H, 2 * LG, LG, KB, LDT, LDW, NW>(p, tile, wt); break;
+    default: ac_wave_ragged<H, 3 * LG, LG, KB, LDT, LDW, NW>(p, tile, wt); break;
+    }
+}
+
+// ---------------------------------------------------------------------------------
 // EXPERIMENT (not on the product path): autocorrelation on the f64 matrix cores.
 // Block-Gram form: with X[a][m] = w[16 a + m] (a = 0..n/16-1, m = 0..15),
 //   G1 = X^T X            (pairs inside one 16-sample block)

@@ -2,6 +2,7 @@
 // Included inside the anonymous namespace of every kernel translation unit (after kernels/types.h).
 
 __device__ __forceinline__ uint32_t frame_len(const Params &p, uint32_t frame) {
+    if (p.frame_n) return p.frame_n[frame];   // a ragged batch (Params::frame_n)
     return (frame + 1 == p.n_frames) ? p.last_len : p.block_size;
 }
 

@@ -5,13 +5,20 @@
 // K0: de-interleave (audio.rs:190-199)  [pcm_frame][ch] -> [flac_frame][ch][ldb]
 // also used to re-stride planar input whose block size is not a multiple of 4
 // ---------------------------------------------------------------------------------
+// the frame length rule of frame_len() (common.inc) for the kernels that take no Params; frame_n: a ragged batch's table
+__device__ __forceinline__ uint32_t k0_frame_len(const uint32_t *frame_n, uint32_t frame, uint32_t n_frames, uint32_t last_len,
+                                                 uint32_t block_size) {
+    if (frame_n) return frame_n[frame];
+    return (frame + 1 == n_frames) ? last_len : block_size;
+}
+
 __global__ void __launch_bounds__(WG) k_deinterleave(const int32_t *__restrict__ in,
                                                      int32_t *__restrict__ out, uint32_t channels,
                                                      uint32_t block_size, uint32_t ldb,
                                                      uint32_t n_frames, uint32_t last_len,
-                                                     int planar_in, uint32_t f0) {
+                                                     int planar_in, uint32_t f0, const uint32_t *__restrict__ frame_n) {
     const uint32_t frame = f0 + blockIdx.y;
-    const uint32_t n = (frame + 1 == n_frames) ? last_len : block_size;
+    const uint32_t n = k0_frame_len(frame_n, frame, n_frames, last_len, block_size);
     const size_t in_base = (size_t)frame * block_size * channels;
     int32_t *o = out + (size_t)frame * channels * ldb;
     for (uint32_t i = blockIdx.x * WG + threadIdx.x; i < n; i += gridDim.x * WG) {
@@ -31,9 +38,10 @@ __global__ void __launch_bounds__(WG) k_deinterleave2(const int2 *__restrict__ i
                                                       uint32_t block_size, uint32_t ldb,
                                                       uint32_t n_frames, uint32_t last_len,
                                                       uint32_t *__restrict__ orbits, uint32_t ncand,
-                                                      uint32_t f0, unsigned long long *__restrict__ abs_sums) {
+                                                      uint32_t f0, unsigned long long *__restrict__ abs_sums,
+                                                      const uint32_t *__restrict__ frame_n) {
     const uint32_t frame = f0 + blockIdx.y;
-    const uint32_t n = (frame + 1 == n_frames) ? last_len : block_size;
+    const uint32_t n = k0_frame_len(frame_n, frame, n_frames, last_len, block_size);
     const int2 *src = in + (size_t)frame * block_size;
     int32_t *o = out + (size_t)frame * 2 * ldb;
     uint32_t ol = 0, orr = 0, om = 0, os = 0;
@@ -114,9 +122,10 @@ template <int C>
 __global__ void __launch_bounds__(WG) k_deinterleave_n(const int32_t *__restrict__ in,
                                                        int32_t *__restrict__ out, uint32_t block_size,
                                                        uint32_t ldb, uint32_t n_frames, uint32_t last_len,
-                                                       uint32_t *__restrict__ orbits, uint32_t f0) {
+                                                       uint32_t *__restrict__ orbits, uint32_t f0,
+                                                       const uint32_t *__restrict__ frame_n) {
     const uint32_t frame = f0 + blockIdx.y;
-    const uint32_t n = (frame + 1 == n_frames) ? last_len : block_size;
+    const uint32_t n = k0_frame_len(frame_n, frame, n_frames, last_len, block_size);
     const int32_t *src = in + (size_t)frame * block_size * C;
     int32_t *o = out + (size_t)frame * C * ldb;
     uint32_t acc[C];
@@ -169,7 +178,7 @@ __global__ void __launch_bounds__(WG) k_deinterleave_packed(const uint32_t *__re
     constexpr bool S4 = C == 2;                  // L, R, mid, side candidates (bps <= 24 < 32)
     constexpr int NC = S4 ? 4 : C;
     const uint32_t frame = f0 + blockIdx.y;
-    const uint32_t n = (frame + 1 == n_frames) ? last_len : block_size;
+    const uint32_t n = (frame + 1 == n_frames) ? last_len : block_size;   // (a ragged batch's samples are int32: it never comes this way)
     const uint32_t *src = in + (size_t)frame * ((size_t)block_size * ND / 4);
     int32_t *o = out + (size_t)frame * C * ldb;
     uint32_t acc[NC];

@@ -151,6 +151,14 @@ struct Params {
     // is FIXED / CONSTANT / VERBATIM, or whose wave had to re-fetch its samples for the exact FIXED count, gets 0 and takes
     // k_frame64's own path.
     uint32_t *hand_meta;   // [frame][2]
+    // A RAGGED batch (flacgpu_encode_ragged_device): every frame has a length of its own -- frame_len(p, frame) is
+    // frame_n[frame] -- and its window lies at window_pool + frame_win[frame] (one window per distinct length, each followed
+    // by 64 zero doubles).  Every frame runs the generic kernels; its samples lie at the head of its block_size slot.
+    // frame_n == nullptr (every other batch): n_frames - 1 whole blocks and a last frame of last_len.
+    // (At the END: no other field moves.)
+    const uint32_t *frame_n;
+    const uint32_t *frame_win;
+    const double *window_pool;
 };
 
 
@@ -216,6 +224,8 @@ bool launch_cand64_direct_short(const Params &p, const Knobs &kn, uint32_t B, ui
 // returns true when the kernel also ran K4 in its tail (the DIRECT and SPLIT k_autocorr4 instantiations): no launch_lpc then
 bool dispatch_autocorr(uint32_t H, const Params &p, const Knobs &kn, uint32_t frame0, uint32_t nframes, uint32_t n,
                        const double *win, hipStream_t st);
+// a RAGGED batch (Params::frame_n): every frame of the batch in one launch, each candidate with its frame's length and window
+void launch_autocorr_ragged(uint32_t H, const Params &p, hipStream_t st);
 void launch_autocorr_mfma(const Params &p, uint32_t blocks, uint32_t n, const double *win, double *ac,
                           hipStream_t st);
 // pack.hip

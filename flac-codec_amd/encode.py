@@ -208,6 +208,8 @@ def _stream_lib():
         L.flacenc_device_session_close.restype = None
         L.flacenc_release_pools.argtypes = []
         L.flacenc_release_pools.restype = None
+        L.flacenc_device_tail_stats.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.flacenc_device_tail_stats.restype = None
         L.flacgpu_place_runs_host.argtypes = [C.POINTER(_lib.PlaceRun), C.c_uint32]
         L.flacgpu_place_workgroup.restype = C.c_uint32
         L.flacenc_ingest_sample.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_int)]

@@ -137,6 +137,22 @@ class GpuAnalyzer:
         if rc:
             raise GpuError(rc, "flacgpu_encode_segments_device")
 
+    def encode_ragged_device(self, frames, sample_rate, stream=None):
+        """frames: [(device pointer, samples, frame_number), ...] -- frames of any length 1 .. block_size, of any streams of
+        this context's shape, encoded as ONE batch (flacgpu_encode_ragged_device); asynchronous (fetch_frames() for the
+        result).  Every frame's bytes are those of a one-frame encode_device call."""
+        tab = (_lib.RaggedFrame * max(len(frames), 1))()
+        for i, (ptr, n, number) in enumerate(frames):
+            tab[i].pcm, tab[i].samples, tab[i].reserved, tab[i].frame_number = ptr, n, 0, number
+        rc = _lib.lib().flacgpu_encode_ragged_device(self._h, tab, len(frames), sample_rate, C.c_void_p(stream or 0))
+        if rc:
+            raise GpuError(rc, "flacgpu_encode_ragged_device")
+        self.last_frames = len(frames)
+
+    def ragged_pool_uploads(self):
+        """How often this context has uploaded its ragged window pool (a batch whose lengths are all in the pool uploads none)."""
+        return int(_lib.lib().flacgpu_ragged_pool_uploads(self._h))
+
     def pack_plans(self, pcm, n_frames, last_frame_len, plans, subframes, first_frame_number, sample_rate):
         """flacgpu_pack_plans: device-side frame assembly of caller-supplied decisions.  Returns (bytes, offsets)."""
         a = np.ascontiguousarray(pcm, dtype=np.int32)
@@ -686,6 +702,23 @@ def window_frames(frame_sizes, start, length):
     if rc:
         raise GpuError(rc, "flacgpu_window_frames")
     return first.value, count.value, skip.value
+
+
+def ragged_plan(samples, block_size, max_partition_order):
+    """flacgpu_ragged_plan: the checks of a ragged batch (GpuAnalyzer.encode_ragged_device) and the layout of its window
+    pool, for frames of these lengths under these options.  Returns (window_of[n_frames], distinct lengths in
+    first-appearance order, pool_doubles); raises GpuError for a batch the encoder would refuse.  Needs no GPU."""
+    lens = np.ascontiguousarray(samples, dtype=np.uint32)
+    n = int(lens.size)
+    o = GpuOptions(block_size, max_partition_order, 0, 0, 0, 0, 0, 0.0)
+    u32p = C.POINTER(C.c_uint32)
+    window_of, distinct = np.zeros(max(n, 1), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.uint32)
+    nd, pool = C.c_uint32(0), C.c_uint64(0)
+    rc = _lib.lib().flacgpu_ragged_plan(C.byref(o), lens.ctypes.data_as(u32p) if n else None, n, window_of.ctypes.data_as(u32p),
+                                        distinct.ctypes.data_as(u32p), C.byref(nd), C.byref(pool))
+    if rc:
+        raise GpuError(rc, "flacgpu_ragged_plan")
+    return [int(v) for v in window_of[:n]], [int(v) for v in distinct[:nd.value]], int(pool.value)
 
 
 def window_array(windows):

@@ -380,7 +380,8 @@ uint32_t flacgpu_pipeline_depth(const flacgpu_pipeline *p);
  * (256 frames of 24-bit stereo run at 0.3 of the per-sample rate of 8192).  Here runs of WHOLE blocks of several streams of
  * the context's shape (bits per sample, channels, options) form one batch: segment s contributes n_frames frames numbered
  * first_frame_number, first_frame_number + 1, ...; the frames come out concatenated in segment order (offsets: one entry per
- * frame of the batch plus the end).  A stream's short last block is not a segment: it goes through flacgpu_encode_frames.
+ * frame of the batch plus the end).  A stream's short last block is not a segment: it goes through flacgpu_encode_frames, or,
+ * with the short last blocks of many streams at once, through flacgpu_encode_ragged_device (below).
  *   flacgpu_encode_segments_device  PCM resident in device memory, asynchronous like flacgpu_encode_device (results through
  *                                   flacgpu_fetch_frames / flacgpu_device_buffer).  Every shape flacgpu_analyze_device reads in
  *                                   place -- interleaved stereo of 4096-, 2304-, 2048-, 1152- or 1024-sample blocks (<= 24
@@ -401,6 +402,37 @@ int flacgpu_encode_segments_device(flacgpu_ctx *ctx, const flacgpu_segment *segm
                                    uint32_t sample_rate, void *stream);
 int flacgpu_encode_segments(flacgpu_ctx *ctx, const flacgpu_segment *segments, uint32_t n_segments, uint32_t sample_rate,
                             uint8_t *out, size_t cap, uint64_t *offsets, uint64_t *total);
+/* ---- a RAGGED batch: frames of ANY length 1 .. block_size, of any streams of the context's shape, as one batch ------------
+ * What the short last blocks of many streams need: one call for all of them instead of one one-frame call each.
+ *   flacgpu_encode_ragged_device  asynchronous like flacgpu_encode_segments_device; results through flacgpu_fetch_frames,
+ *       flacgpu_frame_offsets / flacgpu_place_frames and flacgpu_verify_device, one offset per frame plus the end.  Frame
+ *       f's bytes are exactly what flacgpu_encode_device(ctx1, frames[f].pcm, FLACGPU_LAYOUT_INTERLEAVED, 1,
+ *       frames[f].samples, frames[f].frame_number, sample_rate, ...) produces on a one-frame context with the same options,
+ *       whatever the other frames of the batch are and whatever order they come in.  The samples are copied into the
+ *       context's input buffer by the call's first kernel: the caller's buffers must stay valid until that has run (any
+ *       fetch entry waits for it), not longer.  Every frame runs the generic kernels, a whole block included.
+ *       Refused before anything is launched, the context's last batch left as it was: n_frames == 0 or more than the
+ *       context's max_frames, a frame without PCM, samples == 0 or > block_size (FLACGPU_ERR_INVALID_ARG); a frame whose
+ *       effective partition order min(ctz(samples), max_partition_order) exceeds 6 (FLACGPU_ERR_UNSUPPORTED, the rule of a
+ *       short last frame everywhere; flacgpu_last_error names the first such frame).
+ *   flacgpu_ragged_plan           the same checks and the layout of the call's window pool, on the host alone (no device, no
+ *       context): one window per DISTINCT length in first-appearance order, each followed by 64 zero doubles.  Any out
+ *       pointer may be NULL; window_of[n_frames] gets every frame's index among the distinct lengths, distinct[] (room for
+ *       n_frames) the lengths, *pool_doubles = sum(n + 64) over them.  Nothing is written for a refused batch. */
+typedef struct {
+    const int32_t *pcm;      /* device memory: `samples` interleaved sample groups of the context's channel count; any 4-byte alignment */
+    uint32_t samples;        /* per channel, 1 .. block_size */
+    uint32_t reserved;       /* 0 */
+    uint64_t frame_number;   /* the number coded into this frame's header */
+} flacgpu_ragged_frame;
+int flacgpu_encode_ragged_device(flacgpu_ctx *ctx, const flacgpu_ragged_frame *frames, uint32_t n_frames,
+                                 uint32_t sample_rate, void *stream);
+int flacgpu_ragged_plan(const flacgpu_options *opts, const uint32_t *samples, uint32_t n_frames,
+                        uint32_t *window_of, uint32_t *distinct, uint32_t *n_distinct, uint64_t *pool_doubles);
+/* how often the context has uploaded its ragged window pool so far: a batch whose every length has a window in the pool
+ * the context keeps uploads none (for tests of that reuse) */
+uint64_t flacgpu_ragged_pool_uploads(const flacgpu_ctx *ctx);
+
 /* The asynchronous, stream-width form (r06): what a front end that coalesces many streams needs to keep the link busy.  The
  * segments' whole blocks lie BACK TO BACK in `pcm_le` (pinned memory; int32 when bytes_per_sample == 4, else the little-endian
  * ceil(bps / 8)-byte samples of flacgpu_encode_packed_async -- the byte string update_md5 hashes, encode.rs:1292-1318) in

@@ -347,6 +347,12 @@ int flacenc_device_session_write(flacenc_device_session *session, const void *d_
                                  flacenc_session_chunk *chunks, void *stream);
 int flacenc_device_session_finalize(flacenc_device_session *session, flacenc_session_final *finals);
 void flacenc_device_session_close(flacenc_device_session *session);
+/* The short last blocks of the calling thread's last flacenc_encode_many_device[_out] or flacenc_device_session_finalize
+ * call (zero when that call was refused or had none): how many were encoded, and in how many batches.  The one-shot calls
+ * send them through flacgpu_encode_ragged_device as ragged batches of up to a pooled context's frames (one batch for up to
+ * 4096 mono clips); a session's finalize, and every call with FLACGPU_NO_RAGGED=1 in the environment, runs one one-frame
+ * flacgpu_encode_device call each (tail_batches == tail_frames) -- the bytes are the same.  Either may be NULL. */
+void flacenc_device_tail_stats(uint64_t *tail_frames, uint64_t *tail_batches);
 /* The conversion rule on the host, one element: raw_bits holds the element's bits (I16: in the low half; S24: in the low 24 bits, bits
  * 24-31 are ignored).  *altered
  * (may be NULL) = 1 when the element was changed beyond rounding.  A combination plan refuses (unknown type, bps outside

@@ -211,13 +211,16 @@ def session_leg(a):
             del t, chunks
             torch.cuda.empty_cache()
             continue
-        legs = [("a_one_shot", one_shot), ("a_one_shot_no_md5", lambda: one_shot(False))]
+        legs = [] if a.session_only else [("a_one_shot", one_shot), ("a_one_shot_no_md5", lambda: one_shot(False))]
         if not a.one_shot_only:
             chunks = [t[:, :, at:at + rate].contiguous() for at in range(0, T, rate)]   # (a second copy of the batch)
-            assert [bytes(v) for v in one_shot()] == session(), f"{name}: the two legs differ"
-            assert [bytes(v) for v in one_shot(False)] == session(False), f"{name}: the two legs differ without MD5"
+            if not a.session_only:
+                assert [bytes(v) for v in one_shot()] == session(), f"{name}: the two legs differ"
+                assert [bytes(v) for v in one_shot(False)] == session(False), f"{name}: the two legs differ without MD5"
             legs += [("b_session_1s_chunks", session), ("b_session_1s_chunks_no_md5", lambda: session(False))]
-        r = {"streams": n, "samples": t.numel(), "writes": (T + rate - 1) // rate}
+        # (FLACGPU_NO_RAGGED=1 in the environment: the short last blocks one one-frame call each, as before r20 -- the A/B leg)
+        r = {"streams": n, "samples": t.numel(), "writes": (T + rate - 1) // rate, "samples_per_stream": T,
+             "no_ragged": bool(os.environ.get("FLACGPU_NO_RAGGED"))}
         for k, fn in legs:
             before = sclk()   # around every leg: a clock change between the legs shows
             r[k] = dict(timed(fn, a.repeats), sclk_before=before, sclk_after=sclk())
@@ -264,13 +267,20 @@ def main():
     ap.add_argument("--host-only", action="store_true", help="with --out-device: the host-output leg alone")
     ap.add_argument("--session", action="store_true", help="a session fed 1 s chunks: profiles/r19_session.json")
     ap.add_argument("--one-shot-only", action="store_true", help="with --session: the one-shot legs alone")
+    ap.add_argument("--session-only", action="store_true",
+                    help="with --session: the session legs alone (no one-shot legs, no comparison of the files): repeated A/B runs")
     ap.add_argument("--label", default="this_build", help="with --host-only / --one-shot-only: the record's name")
+    ap.add_argument("--no-tail", action="store_true",
+                    help="cut every stream to whole 4096-sample blocks (clips: 159 744 samples): the call without its tail phase")
     ap.add_argument("--root", default=None, help="measure the package of another checkout")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     a.out = a.out or os.path.join(ROOT, "profiles", "r12_s24.json" if a.int24 else
                                   "r18_device_out.json" if a.out_device else
                                   "r19_session.json" if a.session else "r11_encode_device.json")
+    if a.no_tail:
+        for w in WORKLOADS.values():
+            w["samples"] -= w["samples"] % 4096
     if a.root:   # (the package is imported below, never before this line)
         sys.path.insert(0, os.path.abspath(a.root))
     import torch
