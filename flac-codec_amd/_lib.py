@@ -129,7 +129,8 @@ DEVICE_NO_MD5 = 1   # FLACENC_DEVICE_NO_MD5
 
 
 class SessionChunk(C.Structure):
-    """flacenc_session_chunk: one stream's part of a flacenc_device_session_write call."""
+    """flacenc_session_chunk: one stream's part of a flacenc_device_session_write call, or of a
+    flacenc_device_stream_writer_write call (out then receives the stream's one raw frame)."""
     _fields_ = [("in_offset", C.c_uint64), ("samples", C.c_uint64), ("out", C.c_void_p), ("out_cap", C.c_size_t),
                 ("out_len", C.c_size_t), ("status", C.c_int32), ("altered", C.c_uint32)]
 

@@ -427,7 +427,7 @@ int encode_impl(const flacenc_options *opts, const void *d_pcm, const flacenc_te
     if (!tails.empty()) {
         std::vector<size_t> placing;
         const int tail_rc = encode_tail_blocks(
-            g, bps, ch, device, sample_rate, tail_frames, !kDeviceOut, false,
+            g, bps, ch, device, sample_rate, tail_frames, !kDeviceOut, false, true,
             [&](const PooledContext &s, size_t t0, size_t count, const std::vector<uint64_t> &off) {
                 runs.clear();
                 placing.clear();

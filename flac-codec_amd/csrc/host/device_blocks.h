@@ -76,7 +76,7 @@ int encode_whole_blocks(const flacgpu_options &g, uint32_t bps, uint32_t ch, int
 // ---- the streams' SHORT LAST BLOCKS (device_batch.cpp, DESIGN.md 4c "Short last blocks as one batch") ----
 struct TailFrame {
     const int32_t *pcm;   // device address of the block's first sample (interleaved int32)
-    uint32_t samples;     // per channel, 1 .. block_size - 1
+    uint32_t samples;     // per channel, 1 .. block_size - 1 (the device stream writer's frames: up to block_size)
     uint64_t number;      // the frame number: the stream's whole blocks
 };
 // FLACGPU_NO_RAGGED (read_knobs(), read once per process): the tails one by one, a one-frame flacgpu_encode_device call each
@@ -100,6 +100,8 @@ inline uint32_t tail_ctx_frames(size_t n_tails, size_t samples_per_block) {
 // when one batch does not hold them all: batch b + 1 is submitted before batch b is retired, as for the whole blocks.
 //   one_by_one       the caller's choice of the one-frame loop instead (a one-frame flacgpu_encode_device call per tail on
 //                    two one-frame contexts in rotation); FLACGPU_NO_RAGGED=1 forces it for every caller
+//   count_stats      the batches count into flacenc_device_tail_stats (the one-shot calls and a session's finalize); a
+//                    caller whose frames are no stream's short last block (device_stream_writer.cpp) leaves the stats alone
 //   retire(slot, t0, count, off)   tails [t0, t0 + count) are complete in `slot` (frames_to_host: their frames lie in
 //                    slot.out; else only the offsets were fetched): off[k] .. off[k + 1] is tail t0 + k; returns a FLACGPU
 //                    code
@@ -107,7 +109,8 @@ inline uint32_t tail_ctx_frames(size_t n_tails, size_t samples_per_block) {
 // when it returns.
 template <class Retire>
 int encode_tail_blocks(const flacgpu_options &g, uint32_t bps, uint32_t ch, int device, uint32_t sample_rate,
-                       const std::vector<TailFrame> &tails, bool frames_to_host, bool one_by_one, Retire retire) {
+                       const std::vector<TailFrame> &tails, bool frames_to_host, bool one_by_one, bool count_stats,
+                       Retire retire) {
     if (tails.empty()) return 0;
     const bool single = one_by_one || tails_one_by_one();
     const uint32_t ctx_frames = single ? 1u : tail_ctx_frames(tails.size(), (size_t)g.block_size * ch);
@@ -140,7 +143,7 @@ int encode_tail_blocks(const flacgpu_options &g, uint32_t bps, uint32_t ch, int 
         rc = frames_to_host ? flacgpu_fetch_frames(s.ctx, s.out, s.out_cap, off.data(), &total)
                             : flacgpu_frame_offsets(s.ctx, off.data(), &total);
         if (rc) break;
-        tail_stats_add(count_of(b), 1);
+        if (count_stats) tail_stats_add(count_of(b), 1);
         rc = retire(s, b * ctx_frames, count_of(b), off);
     }
     const int tail_rc = rc ? device_gpu_error(rc) : 0;

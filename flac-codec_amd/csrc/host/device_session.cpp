@@ -13,7 +13,11 @@
 //     than a block -- after the contexts that read the old half have been waited for and before the next submit;
 //   * MD5: the ingest runs without FLACGPU_INGEST_MD5, and the chunk at A_i is appended to the stream's resumable chain
 //     (flacgpu_md5_chains_update) on the handle's stream, beside the analysis; finalize pads and downloads;
-//   * finalize: the short last block through the one-frame path, the header from flacenc_stream_header.
+//   * finalize: the short last block through the one-frame path, the header from flacenc_stream_header;
+//   * a stream opened WITHOUT a total (flacenc_device_session_open_ex, total_known[i] == 0) is FlacSampleWriter::new(..,
+//     None): no placeholder SEEKTABLE in front of its frames, no bound on what it may be fed, and at finalize the header
+//     of flacenc_stream_header_unknown_total with total = the samples received.  Its frames and tail are a known-total
+//     stream's: nothing in a frame depends on the total.
 #include <algorithm>
 #include <cstring>
 #include <new>
@@ -68,8 +72,11 @@ int plan_shape(const flacenc_options *o, uint32_t bps, uint32_t channels, size_t
     return 0;
 }
 
+constexpr uint64_t kMaxSamples = 68719476736ull;   // Encoder::MAX_SAMPLES, encode.rs:1880
+
 struct Stream {
     uint64_t total = 0, fed = 0;    // samples per channel: declared, received
+    bool known = true;              // the total was declared at open (false: `total` is unused)
     uint32_t carry = 0;             // c_i: pending samples in front of A_i in the half in use
     size_t hlen = 0;
     int status = 0;                 // sticky
@@ -110,11 +117,20 @@ int flacenc_device_session_plan(const flacenc_options *opts, uint32_t bits_per_s
 int flacenc_device_session_open(const flacenc_options *opts, uint32_t sample_rate, uint32_t bits_per_sample,
                                 uint32_t channels, const uint64_t *totals, size_t n_streams, uint64_t max_chunk,
                                 uint32_t flags, flacenc_device_session **session) {
+    return flacenc_device_session_open_ex(opts, sample_rate, bits_per_sample, channels, totals, nullptr, n_streams, max_chunk,
+                                          flags, session);
+}
+
+int flacenc_device_session_open_ex(const flacenc_options *opts, uint32_t sample_rate, uint32_t bits_per_sample,
+                                   uint32_t channels, const uint64_t *totals, const uint8_t *total_known, size_t n_streams,
+                                   uint64_t max_chunk, uint32_t flags, flacenc_device_session **session) {
     if (!session) return refuse(FLACENC_ERR_INVALID_ARG, "a null argument");
     *session = nullptr;
     Layout l;
     if (int rc = plan_shape(opts, bits_per_sample, channels, n_streams, max_chunk, flags, &l)) return rc;
-    if (!totals && n_streams) return refuse(FLACENC_ERR_INVALID_ARG, "a null argument");
+    bool any_known = !total_known;
+    for (size_t i = 0; total_known && i < n_streams; i++) any_known |= total_known[i] != 0;
+    if (!totals && n_streams && any_known) return refuse(FLACENC_ERR_INVALID_ARG, "a null argument");
     flacenc_device_session *s = new (std::nothrow) flacenc_device_session();
     if (!s) return refuse(FLACENC_ERR_UNSUPPORTED, "out of memory");
     s->o = *opts;
@@ -131,17 +147,20 @@ int flacenc_device_session_open(const flacenc_options *opts, uint32_t sample_rat
     std::vector<uint64_t> most(n_streams, 0);   // the blocks one write can complete
     for (size_t i = 0; i < n_streams; i++) {
         Stream &m = s->st[i];
-        m.total = totals[i];
-        if (!m.total) {
+        m.known = !total_known || total_known[i];
+        m.total = m.known ? totals[i] : 0;
+        if (m.known && !m.total) {
             m.status = FLACENC_ERR_INVALID_ARG;
             continue;
         }
-        if (int rc = stream_header_len(s->o, sample_rate, bits_per_sample, channels, m.total, &m.hlen)) {
+        if (int rc = stream_header_len(s->o, sample_rate, bits_per_sample, channels, m.total, &m.hlen, m.known)) {
             m.status = rc;
             m.hlen = 0;
             continue;
         }
-        most[i] = std::min<uint64_t>((max_chunk + B - 1) / B + 1, (m.total + B - 1) / B);
+        // (without a total only max_chunk bounds what one write completes)
+        most[i] = (max_chunk + B - 1) / B + 1;
+        if (m.known) most[i] = std::min<uint64_t>(most[i], (m.total + B - 1) / B);
     }
     (void)plan_stream_batches(most, s->o.batch_frames, (size_t)B * channels, &s->ctx_frames);
     int rc = flacgpu_ingest_create(s->device, &s->ing);
@@ -173,7 +192,7 @@ int flacenc_device_session_write(flacenc_device_session *s, const void *d_pcm, c
     for (size_t i = 0; i < n; i++) {
         const Stream &m = s->st[i];
         if (chunks[i].samples > s->max_chunk) return refuse(FLACENC_ERR_INVALID_ARG, "chunk " + std::to_string(i) + " is longer than max_chunk");
-        if (!m.status && chunks[i].samples > m.total - m.fed)
+        if (!m.status && m.known && chunks[i].samples > m.total - m.fed)
             return refuse(FLACENC_ERR_INVALID_ARG, "chunk " + std::to_string(i) + " passes the stream's declared total");
         jobs[i] = flacenc_device_job{};
         jobs[i].in_offset = chunks[i].in_offset;
@@ -291,7 +310,10 @@ int flacenc_device_session_finalize(flacenc_device_session *s, flacenc_session_f
         f.header_len = f.tail_len = 0;
         f.altered = (uint32_t)std::min<uint64_t>(m.altered, 0xFFFFFFFFull);
         std::memset(f.md5, 0, 16);
-        if (!m.status && m.fed != m.total) m.status = FLACENC_ERR_SAMPLE_COUNT_MISMATCH;
+        if (!m.status && m.known && m.fed != m.total) m.status = FLACENC_ERR_SAMPLE_COUNT_MISMATCH;
+        // Encoder::finalize_inner without a total (encode.rs:2088-2097)
+        if (!m.status && !m.known && m.fed >= kMaxSamples) m.status = FLACENC_ERR_EXCESSIVE_TOTAL_SAMPLES;
+        if (!m.status && !m.known && !m.fed) m.status = FLACENC_ERR_NO_SAMPLES;
         f.status = m.status;
         if (!m.status && m.carry) tails.push_back(i);
     }
@@ -306,7 +328,7 @@ int flacenc_device_session_finalize(flacenc_device_session *s, flacenc_session_f
             tail_frames.push_back(TailFrame{s->d_staging + s->place(i, s->half) - (size_t)m.carry * ch, m.carry, m.sizes.size()});
         }
         const int tail_rc = encode_tail_blocks(
-            s->g, s->bps, ch, s->device, s->sample_rate, tail_frames, true, true,
+            s->g, s->bps, ch, s->device, s->sample_rate, tail_frames, true, true, true,
             [&](const PooledContext &c, size_t t0, size_t count, const std::vector<uint64_t> &off) {
                 for (size_t k = 0; k < count; k++) {
                     flacenc_session_final &f = finals[tails[t0 + k]];
@@ -345,10 +367,14 @@ int flacenc_device_session_finalize(flacenc_device_session *s, flacenc_session_f
         std::vector<uint32_t> sizes = m.sizes;
         if (m.carry) sizes.push_back((uint32_t)f.tail_len);
         size_t hlen = 0;
-        int rc = f.header ? flacenc_stream_header(&s->o, s->sample_rate, s->bps, ch, m.total, f.md5, sizes.size(), sizes.data(),
-                                                  m.carry ? m.carry : B, f.header, f.header_cap, &hlen)
-                          : FLACENC_ERR_IO;
-        if (!rc && hlen != m.hlen) rc = FLACENC_ERR_IO;   // (cannot happen: the header's size is fixed at open)
+        int rc = FLACENC_ERR_IO;
+        if (f.header && m.known)
+            rc = flacenc_stream_header(&s->o, s->sample_rate, s->bps, ch, m.total, f.md5, sizes.size(), sizes.data(),
+                                       m.carry ? m.carry : B, f.header, f.header_cap, &hlen);
+        else if (f.header)
+            rc = flacenc_stream_header_unknown_total(&s->o, s->sample_rate, s->bps, ch, f.md5, sizes.size(), sizes.data(),
+                                                     m.carry ? m.carry : B, f.header, f.header_cap, &hlen);
+        if (!rc && hlen != m.hlen) rc = FLACENC_ERR_IO;   // (cannot happen: the header's size is fixed at open, with or without a total)
         if (rc) {
             m.status = f.status = rc != FLACENC_ERR_INVALID_ARG ? rc : FLACENC_ERR_IO;
             f.tail_len = 0;

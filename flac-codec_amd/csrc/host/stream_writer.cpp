@@ -1445,17 +1445,17 @@ int flacenc_encode_many_devices(const flacenc_options *opts_in, flacenc_job *job
 // PADDING) exactly as a writer that had produced frames of these sizes would leave them at finalize
 // (Encoder::new + encode's seek points + finalize_inner, encode.rs:1882-1980, 1999-2003, 2024-2110):
 // what the owner of a stream whose frame ranges were encoded elsewhere (other GPUs) needs.
-int flacenc_stream_header(const flacenc_options *opts, uint32_t sample_rate, uint32_t bits_per_sample,
-                          uint32_t channels, uint64_t total_pcm_frames, const uint8_t md5[16], uint64_t n_frames,
-                          const uint32_t *frame_sizes, uint32_t last_frame_len, uint8_t *out, size_t cap,
-                          size_t *len) {
+static int stream_header_impl(const flacenc_options *opts, uint32_t sample_rate, uint32_t bits_per_sample,
+                              uint32_t channels, bool has_total, uint64_t total_pcm_frames, const uint8_t md5[16],
+                              uint64_t n_frames, const uint32_t *frame_sizes, uint32_t last_frame_len, uint8_t *out,
+                              size_t cap, size_t *len) {
     if (!opts || !md5 || !frame_sizes || !len || n_frames == 0 || last_frame_len == 0 ||
         last_frame_len > opts->block_size)
         return FLACENC_ERR_INVALID_ARG;
     if (bits_per_sample < 1 || bits_per_sample > 32) return FLACENC_ERR_INVALID_BITS_PER_SAMPLE;
     flacenc_writer w;
     w.header_only = true;
-    if (int rc = w.init(*opts, sample_rate, bits_per_sample, channels, true, total_pcm_frames, nullptr)) return rc;
+    if (int rc = w.init(*opts, sample_rate, bits_per_sample, channels, has_total, total_pcm_frames, nullptr)) return rc;
     const uint32_t B = opts->block_size;
     for (uint64_t f = 0; f < n_frames; f++) {
         const uint32_t n = (f + 1 == n_frames) ? last_frame_len : B;
@@ -1476,6 +1476,32 @@ int flacenc_stream_header(const flacenc_options *opts, uint32_t sample_rate, uin
     if (!out || cap < w.metadata_len) return FLACENC_ERR_INVALID_ARG;
     std::memcpy(out, w.sink.mem.data(), w.metadata_len);
     return 0;
+}
+
+int flacenc_stream_header(const flacenc_options *opts, uint32_t sample_rate, uint32_t bits_per_sample,
+                          uint32_t channels, uint64_t total_pcm_frames, const uint8_t md5[16], uint64_t n_frames,
+                          const uint32_t *frame_sizes, uint32_t last_frame_len, uint8_t *out, size_t cap,
+                          size_t *len) {
+    return stream_header_impl(opts, sample_rate, bits_per_sample, channels, true, total_pcm_frames, md5, n_frames, frame_sizes,
+                              last_frame_len, out, cap, len);
+}
+
+// The same for a writer created WITHOUT a total (FlacSampleWriter::new(.., None), encode.rs:1909-1939: no placeholder
+// SEEKTABLE), as finalize leaves it: the seek points carved out of PADDING when they fit (encode.rs:2029-2076), the total
+// filled in from the frames (encode.rs:2088-2097).
+int flacenc_stream_header_unknown_total(const flacenc_options *opts, uint32_t sample_rate, uint32_t bits_per_sample,
+                                        uint32_t channels, const uint8_t md5[16], uint64_t n_frames,
+                                        const uint32_t *frame_sizes, uint32_t last_frame_len, uint8_t *out, size_t cap,
+                                        size_t *len) {
+    return stream_header_impl(opts, sample_rate, bits_per_sample, channels, false, 0, md5, n_frames, frame_sizes, last_frame_len,
+                              out, cap, len);
+}
+
+int flacenc_stream_header_len(const flacenc_options *opts, uint32_t sample_rate, uint32_t bits_per_sample, uint32_t channels,
+                              int has_total, uint64_t total_pcm_frames, size_t *len) {
+    if (!opts || !len) return FLACENC_ERR_INVALID_ARG;
+    if (bits_per_sample < 1 || bits_per_sample > 32) return FLACENC_ERR_INVALID_BITS_PER_SAMPLE;
+    return flacenc_host::stream_header_len(*opts, sample_rate, bits_per_sample, channels, total_pcm_frames, len, has_total != 0);
 }
 
 // The 34 bytes of a STREAMINFO block body (metadata/mod.rs:1599-1630, 1740-1760) as the writers
@@ -1554,16 +1580,7 @@ int flacenc_stream_writer_write(flacenc_stream_writer *w, uint32_t rate, uint32_
     if (channels > 8) return FLACENC_ERR_EXCESSIVE_CHANNELS;
     const size_t n = count / channels;
     if (n == 0 || n > 65535) return FLACENC_ERR_INVALID_BLOCK_SIZE;
-    {  // SampleRate::try_from + "Streaminfo => NonSubsetSampleRate"
-        bool named = false;
-        for (uint32_t r : {88200u, 176400u, 192000u, 8000u, 16000u, 22050u, 24000u, 32000u, 44100u, 48000u, 96000u})
-            named |= (r == rate);
-        bool coded = named || (rate % 1000 == 0 && rate / 1000 < 255) ||
-                     (rate % 10 == 0 && rate / 10 < 65535) || rate < 65535;
-        if (!coded) return rate < (1u << 20) ? FLACENC_ERR_NON_SUBSET_SAMPLE_RATE : FLACENC_ERR_INVALID_SAMPLE_RATE;
-    }
-    if (!(bps == 8 || bps == 12 || bps == 16 || bps == 20 || bps == 24 || bps == 32))
-        return FLACENC_ERR_NON_SUBSET_BITS_PER_SAMPLE;
+    if (int e = flacenc_host::subset_frame_error(rate, bps)) return e;
     uint32_t cap = 16;
     while (cap < n) cap <<= 1;
     cap = std::min<uint32_t>(cap, FLACGPU_MAX_BLOCK_SIZE);
@@ -1613,13 +1630,26 @@ int options_error(const flacenc_options &o) { return ::options_error(o); }
 flacgpu_options gpu_options(const flacenc_options &o, uint32_t block_size) { return ::gpu_options(o, block_size); }
 void pack_le(const int32_t *s, size_t count, unsigned width, uint8_t *d) { ::pack_le(s, count, width, d); }
 int stream_header_len(const flacenc_options &o, uint32_t sample_rate, uint32_t bits_per_sample, uint32_t channels,
-                      uint64_t total_pcm_frames, size_t *len) {
+                      uint64_t total_pcm_frames, size_t *len, bool has_total) {
     flacenc_writer w;
     w.header_only = true;
-    const int rc = w.init(o, sample_rate, bits_per_sample, channels, true, total_pcm_frames, nullptr);
+    const int rc = w.init(o, sample_rate, bits_per_sample, channels, has_total, total_pcm_frames, nullptr);
     w.finalized = true;   // (nothing to flush: the destructor must not try)
     if (!rc && len) *len = w.metadata_len;
     return rc;
+}
+int subset_frame_error(uint32_t rate, uint32_t bps) {
+    {  // SampleRate::try_from + "Streaminfo => NonSubsetSampleRate"
+        bool named = false;
+        for (uint32_t r : {88200u, 176400u, 192000u, 8000u, 16000u, 22050u, 24000u, 32000u, 44100u, 48000u, 96000u})
+            named |= (r == rate);
+        bool coded = named || (rate % 1000 == 0 && rate / 1000 < 255) ||
+                     (rate % 10 == 0 && rate / 10 < 65535) || rate < 65535;
+        if (!coded) return rate < (1u << 20) ? FLACENC_ERR_NON_SUBSET_SAMPLE_RATE : FLACENC_ERR_INVALID_SAMPLE_RATE;
+    }
+    if (!(bps == 8 || bps == 12 || bps == 16 || bps == 20 || bps == 24 || bps == 32))
+        return FLACENC_ERR_NON_SUBSET_BITS_PER_SAMPLE;
+    return 0;
 }
 void run_parallel(unsigned helpers, const std::function<void()> &fn) { WorkerPool::get().run(helpers, fn); }
 void set_last_error(const std::string &text) { g_err = text; }

@@ -200,12 +200,26 @@ def _stream_lib():
                                                   C.POINTER(C.c_size_t)]
         L.flacenc_device_session_open.argtypes = [po, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.c_size_t,
                                                   C.c_uint64, C.c_uint32, C.POINTER(vp)]
+        L.flacenc_device_session_open_ex.argtypes = [po, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64),
+                                                     C.POINTER(C.c_uint8), C.c_size_t, C.c_uint64, C.c_uint32, C.POINTER(vp)]
         L.flacenc_device_session_header_len.argtypes = [vp, C.c_size_t]
         L.flacenc_device_session_header_len.restype = C.c_size_t
         L.flacenc_device_session_write.argtypes = [vp, vp, pf, C.POINTER(_lib.SessionChunk), vp]
         L.flacenc_device_session_finalize.argtypes = [vp, C.POINTER(_lib.SessionFinal)]
         L.flacenc_device_session_close.argtypes = [vp]
         L.flacenc_device_session_close.restype = None
+        L.flacenc_device_stream_writer_plan.argtypes = [po, C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, C.c_uint32,
+                                                        C.POINTER(C.c_size_t)]
+        L.flacenc_device_stream_writer_open.argtypes = [po, C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, C.c_uint32,
+                                                        C.POINTER(C.c_uint64), C.POINTER(vp)]
+        L.flacenc_device_stream_writer_write.argtypes = [vp, vp, pf, C.POINTER(_lib.SessionChunk), vp]
+        L.flacenc_device_stream_writer_frame_number.argtypes = [vp, C.c_size_t]
+        L.flacenc_device_stream_writer_frame_number.restype = C.c_uint64
+        L.flacenc_device_stream_writer_close.argtypes = [vp]
+        L.flacenc_device_stream_writer_close.restype = None
+        L.flacenc_stream_header_unknown_total.argtypes = [po, C.c_uint32, C.c_uint32, C.c_uint32, C.c_char_p, C.c_uint64,
+                                                          C.POINTER(C.c_uint32), C.c_uint32, vp, C.c_size_t,
+                                                          C.POINTER(C.c_size_t)]
         L.flacenc_release_pools.argtypes = []
         L.flacenc_release_pools.restype = None
         L.flacenc_device_tail_stats.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
@@ -815,17 +829,34 @@ class BatchEncoder:
         return [v.tobytes() for v in views] if copy else views
 
     def open_device_session(self, totals, sample_rate, bits_per_sample, channels, max_chunk, verify_md5=True, keep=True,
-                            device=None):
+                            device=None, n_streams=None):
         """A DeviceSession: the streams of encode_device taken chunk by chunk (flacenc_device_session_*).  totals:
-        every stream's length per channel, declared now; max_chunk: the most samples per channel one write brings for
+        every stream's length per channel, declared now -- None for a stream whose length is not known yet
+        (FlacSampleWriter::new with None: its header has no placeholder SEEKTABLE, finalize fills in the total); with
+        totals=None, n_streams=k opens k such streams.  max_chunk: the most samples per channel one write brings for
         one stream.  device: the HIP ordinal (default: the options', else the current one)."""
+        if totals is None:
+            if n_streams is None:
+                raise ValueError("totals=None takes n_streams")
+            totals = [None] * int(n_streams)
+        elif n_streams is not None and int(n_streams) != len(totals):
+            raise ValueError("n_streams differs from len(totals)")
         return DeviceSession(self._opts, totals, sample_rate, bits_per_sample, channels, max_chunk, verify_md5, keep, device)
+
+    def open_device_stream_writer(self, n_streams, sample_rate, bits_per_sample, channels, max_block, first_numbers=None,
+                                  device=None):
+        """A DeviceStreamWriter: n_streams streams of one shape on the GPU -> raw subset frames, one per stream and
+        write (flacenc_device_stream_writer_*).  max_block: the most samples per channel one write brings for one
+        stream, at most 65535.  first_numbers: every stream's first frame number (default 0)."""
+        return DeviceStreamWriter(self._opts, n_streams, sample_rate, bits_per_sample, channels, max_block, first_numbers,
+                                  device)
 
 
 class DeviceSession:
     """n streams of one shape, produced on the GPU piece by piece, -> .flac files (flacenc_device_session_*): write()
     takes the next chunk of every stream in the tensor forms encode_device takes and returns the frames that chunk
     completes; finalize() returns the files -- byte for byte what encode_device gives for the concatenated samples.
+    A total of None: the stream's length is not known yet, and its file is FlacSampleWriter's with total_samples=None.
     A context manager: leaving the block closes the session."""
 
     def __init__(self, options, totals, sample_rate, bits_per_sample, channels, max_chunk, verify_md5=True, keep=True,
@@ -834,16 +865,22 @@ class DeviceSession:
         self._co = options._c_options()
         if device is not None:
             self._co.device = int(device)
-        self._totals = [int(t) for t in totals]
+        self._totals = [None if t is None else int(t) for t in totals]
         self._n, self._bps, self._channels, self._keep = len(self._totals), bits_per_sample, channels, keep
         self._block = int(self._co.block_size)
         self._pending = [0] * self._n   # samples carried towards the next block, as the library counts them
         self._parts = [[] for _ in range(self._n)]
         self._bufs = []
         self._h = C.c_void_p()
-        arr = (C.c_uint64 * max(self._n, 1))(*self._totals)
-        _check(L.flacenc_device_session_open(C.byref(self._co), sample_rate, bits_per_sample, channels, arr, self._n,
-                                             int(max_chunk), 0 if verify_md5 else _lib.DEVICE_NO_MD5, C.byref(self._h)))
+        arr = (C.c_uint64 * max(self._n, 1))(*[t or 0 for t in self._totals])
+        flags = 0 if verify_md5 else _lib.DEVICE_NO_MD5
+        if any(t is None for t in self._totals):
+            known = (C.c_uint8 * max(self._n, 1))(*[int(t is not None) for t in self._totals])
+            _check(L.flacenc_device_session_open_ex(C.byref(self._co), sample_rate, bits_per_sample, channels, arr, known,
+                                                    self._n, int(max_chunk), flags, C.byref(self._h)))
+        else:
+            _check(L.flacenc_device_session_open(C.byref(self._co), sample_rate, bits_per_sample, channels, arr, self._n,
+                                                 int(max_chunk), flags, C.byref(self._h)))
         self.last_status = [0] * self._n
         self.last_altered = [0] * self._n
         self.last_md5 = [bytes(16)] * self._n
@@ -915,6 +952,87 @@ class DeviceSession:
     def close(self):
         if self._h:
             _stream_lib().flacenc_device_session_close(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeviceStreamWriter:
+    """n streams of one shape, produced on the GPU piece by piece, -> raw subset FLAC frames without metadata
+    (flacenc_device_stream_writer_*; FlacStreamWriter for a batch in device memory): write() takes up to max_block
+    samples of every stream in the tensor forms encode_device takes and returns ONE frame per stream that brought
+    samples, numbered with that stream's own count -- what decode_frames, decode_timeline and FlacStreamReader read.
+    A context manager: leaving the block closes the writer."""
+
+    def __init__(self, options, n_streams, sample_rate, bits_per_sample, channels, max_block, first_numbers=None,
+                 device=None):
+        L = _stream_lib()
+        self._co = options._c_options()
+        if device is not None:
+            self._co.device = int(device)
+        self._n, self._bps, self._channels, self._max_block = int(n_streams), bits_per_sample, channels, int(max_block)
+        self._bufs = []
+        self._h = C.c_void_p()
+        first = None
+        if first_numbers is not None:
+            if len(first_numbers) != self._n:
+                raise ValueError("one first frame number per stream")
+            first = (C.c_uint64 * max(self._n, 1))(*[int(v) for v in first_numbers])
+        _check(L.flacenc_device_stream_writer_open(C.byref(self._co), sample_rate, bits_per_sample, channels, self._n,
+                                                   self._max_block, first, C.byref(self._h)))
+        self.last_status = [0] * self._n
+        self.last_altered = [0] * self._n
+
+    @property
+    def frame_numbers(self):
+        """Every stream's next frame number."""
+        L = _stream_lib()
+        return [int(L.flacenc_device_stream_writer_frame_number(self._h, i)) for i in range(self._n)]
+
+    def write(self, tensor, lengths, dtype=None, offsets=None):
+        """lengths[i] samples of stream i (0: none this time; at most max_block; the tensor as in encode_device) ->
+        list[bytes]: every stream's frame, b"" for a stream without samples.  Runs behind the tensor's current torch
+        stream and returns when the tensor may be reused.  A write the library refuses as a whole raises and changes
+        nothing.  self.last_status / self.last_altered: this write's, per stream (a stream whose status is not 0 got
+        no frame number and may be written again)."""
+        import torch
+
+        L = _stream_lib()
+        n, offsets, lengths, channels, fmt = BatchEncoder._device_batch(tensor, lengths, dtype, offsets, self._channels)
+        if n != self._n or channels != self._channels:
+            raise ValueError("one chunk per stream of the writer, of the writer's channel count")
+        chunks = (_lib.SessionChunk * max(n, 1))()
+        for i in range(n):
+            # a frame at its largest: header <= 16 bytes, CRC-16, every subframe VERBATIM at bps + 1 bits with a header
+            # byte and a wasted-bits escape
+            cap = 18 + 2 * channels + (lengths[i] * channels * (self._bps + 1) + 7) // 8 if lengths[i] > 0 else 0
+            if i >= len(self._bufs):
+                self._bufs.append(np.empty(max(cap, 1), dtype=np.uint8))
+            elif self._bufs[i].size < cap:
+                self._bufs[i] = np.empty(cap, dtype=np.uint8)
+            chunks[i].in_offset, chunks[i].samples = offsets[i], lengths[i]
+            chunks[i].out, chunks[i].out_cap = self._bufs[i].ctypes.data, self._bufs[i].size
+        stream = torch.cuda.current_stream(tensor.device).cuda_stream
+        rc = L.flacenc_device_stream_writer_write(self._h, tensor.data_ptr() if tensor.numel() else None, C.byref(fmt),
+                                                  chunks, stream or None)
+        _check(rc)   # refused as a whole: no chunk field was written and no number advanced
+        self.last_status = [int(chunks[i].status) for i in range(n)]
+        self.last_altered = [int(chunks[i].altered) for i in range(n)]
+        return [self._bufs[i][: chunks[i].out_len].tobytes() for i in range(n)]
+
+    def close(self):
+        if self._h:
+            _stream_lib().flacenc_device_stream_writer_close(self._h)
             self._h = C.c_void_p()
 
     def __enter__(self):

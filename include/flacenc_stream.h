@@ -317,6 +317,18 @@ int flacenc_encode_many_device_out(const flacenc_options *opts, const void *d_pc
  *             small: FLACENC_ERR_IO.  Returns 0 or the first failing stream's status.  A second finalize, and a write
  *             after finalize: FLACENC_ERR_FINALIZED.
  *   close     frees everything; legal at any time, also on NULL.
+ *   open_ex   open with `total_known`, one entry per stream, for streams whose length is NOT known when they start (a
+ *             generative model's steps, a capture loop).  total_known == NULL is open, exactly.  total_known[i] == 0:
+ *             stream i has no declared total and totals[i] is ignored (totals may be NULL when no stream has one); known
+ *             and unknown streams mix freely.  Such a stream is FlacSampleWriter::new(.., None) (encode.rs:1909-1939):
+ *             header_len is the size without a placeholder SEEKTABLE, and stays that at finalize, where the seek table is
+ *             carved out of the PADDING block when it fits (encode.rs:2029-2076); write has no "passes the declared total"
+ *             refusal; finalize gives FLACENC_ERR_NO_SAMPLES (encode.rs:2090) for a stream that never received a sample,
+ *             nothing written for it, FLACENC_ERR_EXCESSIVE_TOTAL_SAMPLES at 2^36 samples or more, and otherwise builds
+ *             the header with total = the samples received (flacenc_stream_header_unknown_total).  Frames, tail, md5
+ *             and altered are a known-total stream's.  The contract: header || frames of every write || tail is byte for
+ *             byte the file of flacenc_sample_writer_new(.., has_total = 0, ..) fed the same samples.
+ *             FLACENC_ERR_SAMPLE_COUNT_MISMATCH remains a known-total stream's error.
  * A GPU error in any call is sticky: every later write and finalize returns it.  A session is not thread-safe; several
  * sessions, and one-shot calls beside them, do not disturb one another, nor does flacenc_release_pools(). */
 typedef struct flacenc_device_session flacenc_device_session;
@@ -342,6 +354,9 @@ int flacenc_device_session_plan(const flacenc_options *opts, uint32_t bits_per_s
 int flacenc_device_session_open(const flacenc_options *opts, uint32_t sample_rate, uint32_t bits_per_sample,
                                 uint32_t channels, const uint64_t *totals, size_t n_streams, uint64_t max_chunk,
                                 uint32_t flags, flacenc_device_session **session);
+int flacenc_device_session_open_ex(const flacenc_options *opts, uint32_t sample_rate, uint32_t bits_per_sample,
+                                   uint32_t channels, const uint64_t *totals, const uint8_t *total_known, size_t n_streams,
+                                   uint64_t max_chunk, uint32_t flags, flacenc_device_session **session);
 size_t flacenc_device_session_header_len(const flacenc_device_session *session, size_t i);
 int flacenc_device_session_write(flacenc_device_session *session, const void *d_pcm, const flacenc_tensor_format *fmt,
                                  flacenc_session_chunk *chunks, void *stream);
@@ -353,6 +368,53 @@ void flacenc_device_session_close(flacenc_device_session *session);
  * 4096 mono clips); a session's finalize, and every call with FLACGPU_NO_RAGGED=1 in the environment, runs one one-frame
  * flacgpu_encode_device call each (tail_batches == tail_frames) -- the bytes are the same.  Either may be NULL. */
 void flacenc_device_tail_stats(uint64_t *tail_frames, uint64_t *tail_batches);
+/* ---- a device stream writer: ONE RAW FRAME per stream per call (DESIGN.md 4c "Device stream writer") -------------------------
+ * FlacStreamWriter::write (encode.rs:1094-1274; flacenc_stream_writer_write below is the host form) for n_streams streams of
+ * one shape whose samples lie in device memory: header-less subset frames, the input of flacgpu_decoder's raw frame streams.
+ * No metadata and no MD5.
+ *   plan      pure host code.  Refuses, in FlacStreamWriter's order and with its codes: invalid options (the OptionsError;
+ *             opts->block_size is validated but otherwise ignored, as in FlacStreamWriter::new), bits per sample outside
+ *             1..32 (FLACENC_ERR_NON_SUBSET_BITS_PER_SAMPLE), channels outside 1..8 (FLACENC_ERR_EXCESSIVE_CHANNELS),
+ *             max_block outside 1..65535 (FLACENC_ERR_INVALID_BLOCK_SIZE), a sample rate no subset frame header codes
+ *             (FLACENC_ERR_NON_SUBSET_SAMPLE_RATE; from 2^20 on FLACENC_ERR_INVALID_SAMPLE_RATE), bits per sample other
+ *             than 8, 12, 16, 20, 24, 32 (FLACENC_ERR_NON_SUBSET_BITS_PER_SAMPLE); then what flacenc_device_batch_plan
+ *             refuses for the shape (the stream count).  *device_bytes = the writer's staging buffer: per stream
+ *             max_block * channels int32 elements rounded up to 16 bytes.  (The analysis contexts are the pooled ones, of
+ *             block size max(16, max_block): a max_block of 1..15 is served by contexts of 16, as in the host writer.)
+ *   open      the same checks; first_numbers[i] = stream i's first frame number (NULL: all 0; above 2^36 - 1:
+ *             FLACENC_ERR_EXCESSIVE_FRAME_NUMBER).  The staging buffer is allocated here, at its final size: a buffer the
+ *             device cannot hold is open's error (FLACENC_ERR_GPU), not a later write's.
+ *   write     chunks[i].samples in 0..max_block samples per channel of stream i in `d_pcm`, described by `fmt`, in_offset
+ *             and samples exactly as for flacenc_device_session_write.  Every stream with samples > 0 gets exactly ONE frame
+ *             of that many samples, numbered with the stream's count, in chunks[i].out (out_len = its size; altered = the
+ *             chunk's count), and its count advances by one; a stream with 0 samples gets nothing and its count stays.  The
+ *             frame is byte for byte flacenc_stream_writer_write's for the same samples, options and frame number.  All
+ *             frames of a call, whatever their lengths, are one ragged batch (flacgpu_encode_ragged_device; several when a
+ *             pooled context does not hold them all); FLACGPU_NO_RAGGED=1 takes one one-frame call each, the same bytes.
+ *             Synchronous: d_pcm may be reused on return.  Refused as a whole -- nothing launched, no chunk field written,
+ *             no count advanced: a chunk longer than max_block and anything flacenc_device_batch_plan refuses for the tensor
+ *             (FLACENC_ERR_INVALID_ARG / _UNSUPPORTED), a frame whose effective partition order min(ctz(samples),
+ *             max_partition_order) exceeds 6 (FLACENC_ERR_UNSUPPORTED; flacenc_last_error names the stream).  Errors of
+ *             one stream, in its chunk's status: an `out` too small FLACENC_ERR_IO -- the count is NOT advanced, as when
+ *             the host writer's sink fails, and the stream stays usable: the same chunk written again with room gives the
+ *             frame with the same number; a stream whose count stands at 2^36 - 1 gets its frame and
+ *             FLACENC_ERR_EXCESSIVE_FRAME_NUMBER, the count staying, as in flacenc_stream_writer_write.  Returns 0 when the
+ *             call ran, or the refusal.  A failure of the device is sticky: every later write returns it.  (Arguments a
+ *             flacgpu_* call refuses -- none is left once the checks above have passed -- are that call's error alone.)
+ *   frame_number  stream i's next frame number (0 for an i out of range).
+ *   close     frees everything; legal on NULL.
+ * flacenc_device_tail_stats is not touched by a writer's calls.  A writer is not thread-safe; several writers, sessions
+ * and one-shot calls beside one another do not disturb one another. */
+typedef struct flacenc_device_stream_writer flacenc_device_stream_writer;
+int flacenc_device_stream_writer_plan(const flacenc_options *opts, uint32_t sample_rate, uint32_t bits_per_sample,
+                                      uint32_t channels, size_t n_streams, uint32_t max_block, size_t *device_bytes);
+int flacenc_device_stream_writer_open(const flacenc_options *opts, uint32_t sample_rate, uint32_t bits_per_sample,
+                                      uint32_t channels, size_t n_streams, uint32_t max_block, const uint64_t *first_numbers,
+                                      flacenc_device_stream_writer **writer);
+int flacenc_device_stream_writer_write(flacenc_device_stream_writer *writer, const void *d_pcm,
+                                       const flacenc_tensor_format *fmt, flacenc_session_chunk *chunks, void *stream);
+uint64_t flacenc_device_stream_writer_frame_number(const flacenc_device_stream_writer *writer, size_t i);
+void flacenc_device_stream_writer_close(flacenc_device_stream_writer *writer);
 /* The conversion rule on the host, one element: raw_bits holds the element's bits (I16: in the low half; S24: in the low 24 bits, bits
  * 24-31 are ignored).  *altered
  * (may be NULL) = 1 when the element was changed beyond rounding.  A combination plan refuses (unknown type, bps outside
@@ -398,6 +460,15 @@ int flacenc_stream_header(const flacenc_options *opts, uint32_t sample_rate, uin
                           uint32_t channels, uint64_t total_pcm_frames, const uint8_t md5[16], uint64_t n_frames,
                           const uint32_t *frame_sizes, uint32_t last_frame_len, uint8_t *out, size_t cap,
                           size_t *len);
+/* The same for a writer created WITHOUT a total (flacenc_sample_writer_new(.., has_total = 0, ..); FlacSampleWriter::new
+ * with None, encode.rs:1909-1939): no placeholder SEEKTABLE; the seek points go into the PADDING block when it has room
+ * for them (behind it, the padding shrunk by their size; encode.rs:2029-2076), else there are none; STREAMINFO's total is
+ * the frames' own, (n_frames - 1) * block_size + last_frame_len (FLACENC_ERR_EXCESSIVE_TOTAL_SAMPLES from 2^36 on).  The
+ * size does not depend on the frames.  Pure host code. */
+int flacenc_stream_header_unknown_total(const flacenc_options *opts, uint32_t sample_rate, uint32_t bits_per_sample,
+                                        uint32_t channels, const uint8_t md5[16], uint64_t n_frames,
+                                        const uint32_t *frame_sizes, uint32_t last_frame_len, uint8_t *out, size_t cap,
+                                        size_t *len);
 
 /* The 34-byte STREAMINFO body exactly as the writers serialise it (metadata/mod.rs:1599-1630). */
 int flacenc_streaminfo_bytes(uint32_t min_block, uint32_t max_block, uint32_t min_frame, uint32_t max_frame,

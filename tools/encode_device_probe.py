@@ -28,7 +28,14 @@ Writes profiles/r19_session.json.  --one-shot-only (with --session): leg (a) alo
 With --kernels: per workload one one-shot call and one session, then ONE stream of 3 min stereo through both, and nothing
 else -- k_md5_chain beside k_md5_many on the same staged samples, under rocprofv3 as above.
 --host-only (with --out-device): the "host_output" leg alone, merged into the record under "host_output_of" / --label; with
---root DIR the package of another checkout built beside this one (the parent commit) is measured by the same code."""
+--root DIR the package of another checkout built beside this one (the parent commit) is measured by the same code.
+--session --unknown-total: the session legs (--session-only is implied) and beside them the same session opened WITHOUT the
+streams' totals (flacenc_device_session_open_ex), with and without the MD5; the two sessions' files must hold the same
+bytes from the first frame on.  Writes profiles/r21_unknown_length.json under "session".
+--stream-writer: a DeviceStreamWriter (flacenc_device_stream_writer_*) on 64 streams of 16-bit mono at 24 kHz, 1920 samples
+(80 ms) a write, 50 writes: median and min-max of ONE write over the 50 (the first, which creates the contexts, apart),
+sclk before and after; the frames of the first run go back through gpu.decode_frames and are compared.  Merged into
+profiles/r21_unknown_length.json under "stream_writer"."""
 import argparse
 import json
 import os
@@ -198,8 +205,8 @@ def session_leg(a):
         def one_shot(md5=True):
             return enc.encode_device(t, None, sample_rate=rate, bits_per_sample=16, verify_md5=md5, copy=False)
 
-        def session(md5=True):
-            with enc.open_device_session([T] * n, rate, 16, ch, max_chunk=rate, verify_md5=md5) as ses:
+        def session(md5=True, known=True):
+            with enc.open_device_session([T if known else None] * n, rate, 16, ch, max_chunk=rate, verify_md5=md5) as ses:
                 for piece in chunks:
                     ses.write(piece)
                 return ses.finalize()
@@ -218,6 +225,12 @@ def session_leg(a):
                 assert [bytes(v) for v in one_shot()] == session(), f"{name}: the two legs differ"
                 assert [bytes(v) for v in one_shot(False)] == session(False), f"{name}: the two legs differ without MD5"
             legs += [("b_session_1s_chunks", session), ("b_session_1s_chunks_no_md5", lambda: session(False))]
+            if a.unknown_total:
+                for md5 in (True, False):   # another header, the same bytes from the first frame on
+                    for f, g in zip(session(md5), session(md5, False)):
+                        assert f[first_frame(f):] == g[first_frame(g):] and len(f) > len(g), f"{name}: the frames differ"
+                legs += [("c_session_unknown_total", lambda: session(True, False)),
+                         ("c_session_unknown_total_no_md5", lambda: session(False, False))]
         # (FLACGPU_NO_RAGGED=1 in the environment: the short last blocks one one-frame call each, as before r20 -- the A/B leg)
         r = {"streams": n, "samples": t.numel(), "writes": (T + rate - 1) // rate, "samples_per_stream": T,
              "no_ragged": bool(os.environ.get("FLACGPU_NO_RAGGED"))}
@@ -236,10 +249,85 @@ def session_leg(a):
         torch.cuda.empty_cache()
     if a.kernels:
         return
+    if a.unknown_total:   # one record for both of r21's legs
+        whole = {}
+        if os.path.exists(a.out):
+            with open(a.out) as f:
+                whole = json.load(f)
+        res["tool"] += " --unknown-total"
+        res.pop("one_shot_of", None)
+        whole["session"] = res
+        res = whole
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(res, f, indent=1)
     print("wrote", a.out)
+
+
+def stream_writer_leg(a):
+    import torch
+    from flac_codec_amd import _lib, gpu
+    from flac_codec_amd.encode import BatchEncoder, Options
+
+    n, rate, packet, writes = max(1, 64 // a.shrink), 24000, 1920, 50
+    t = make_batch(dict(n=n, samples=packet * writes, channels=1, rate=rate), 1)
+    chunks = [t[:, :, at:at + packet].contiguous() for at in range(0, packet * writes, packet)]
+    enc = BatchEncoder(Options.default())
+    runs = []   # [run][write] ms
+    before = sclk()
+    for run in range(a.repeats + 1):
+        frames, ts = [[] for _ in range(n)], []
+        with enc.open_device_stream_writer(n, rate, 16, 1, max_block=packet) as w:
+            for piece in chunks:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                out = w.write(piece, [packet] * n)
+                ts.append((time.perf_counter() - t0) * 1e3)
+                for k in range(n):
+                    frames[k].append(out[k])
+            assert w.frame_numbers == [writes] * n
+        if run == 0:   # (warm: contexts, pinned buffers, staging) the frames decode back to what went in
+            flat, records, raw = gpu.decode_frames([b"".join(f) for f in frames], out="host")
+            assert all(r.frames == writes and r.skipped_bytes == 0 for r in raw) and not records["status"].any()
+            want = torch.clamp(torch.round(t.double() * 32768.0), -32768, 32767).to(torch.int32)[:, 0, :].cpu().numpy()
+            assert np.array_equal(flat.reshape(n, packet * writes), want), "the decoded frames differ from the tensor"
+            file_bytes = sum(len(f) for per in frames for f in per)
+            continue
+        runs.append(ts)
+    after = sclk()
+    if a.kernels:
+        return
+    every = [v for ts in runs for v in ts[1:]]   # (a run's first write takes the contexts from the pool)
+    r = {"tool": "tools/encode_device_probe.py --stream-writer", "build_id": _lib.build_id(),
+         "workload": f"{n} streams, 16-bit mono {rate} Hz, {packet} samples a write, {writes} writes", "streams": n,
+         "samples_per_write": n * packet, "frame_bytes_per_run": file_bytes, "runs": len(runs),
+         "no_ragged": bool(os.environ.get("FLACGPU_NO_RAGGED")),
+         "per_write_ms": {"median": statistics.median(every), "min": min(every), "max": max(every), "writes": len(every)},
+         "first_write_of_a_run_ms": {"median": statistics.median(ts[0] for ts in runs), "min": min(ts[0] for ts in runs),
+                                     "max": max(ts[0] for ts in runs)},
+         "per_run_ms": {"median": statistics.median(sum(ts) for ts in runs), "min": min(sum(ts) for ts in runs),
+                        "max": max(sum(ts) for ts in runs)},
+         "sclk_before": before, "sclk_after": after}
+    r["realtime_factor"] = packet / rate * 1e3 / r["per_write_ms"]["median"]   # 80 ms of audio per stream and write
+    res = {}
+    if os.path.exists(a.out):
+        with open(a.out) as f:
+            res = json.load(f)
+    res["stream_writer_no_ragged" if r["no_ragged"] else "stream_writer"] = r
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(r, indent=1))
+
+
+def first_frame(data):
+    """where a .flac file's first frame starts: behind the last metadata block"""
+    pos = 4
+    while True:
+        last, size = data[pos] & 0x80, int.from_bytes(data[pos + 1:pos + 4], "big")
+        pos += 4 + size
+        if last:
+            return pos
 
 
 def timed(fn, repeats):
@@ -269,13 +357,19 @@ def main():
     ap.add_argument("--one-shot-only", action="store_true", help="with --session: the one-shot legs alone")
     ap.add_argument("--session-only", action="store_true",
                     help="with --session: the session legs alone (no one-shot legs, no comparison of the files): repeated A/B runs")
+    ap.add_argument("--unknown-total", action="store_true",
+                    help="with --session: the same session without declared totals beside it: profiles/r21_unknown_length.json")
+    ap.add_argument("--stream-writer", action="store_true", help="a DeviceStreamWriter's write: profiles/r21_unknown_length.json")
     ap.add_argument("--label", default="this_build", help="with --host-only / --one-shot-only: the record's name")
     ap.add_argument("--no-tail", action="store_true",
                     help="cut every stream to whole 4096-sample blocks (clips: 159 744 samples): the call without its tail phase")
     ap.add_argument("--root", default=None, help="measure the package of another checkout")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    a.out = a.out or os.path.join(ROOT, "profiles", "r12_s24.json" if a.int24 else
+    if a.unknown_total:
+        a.session_only = True
+    a.out = a.out or os.path.join(ROOT, "profiles", "r21_unknown_length.json" if a.unknown_total or a.stream_writer else
+                                  "r12_s24.json" if a.int24 else
                                   "r18_device_out.json" if a.out_device else
                                   "r19_session.json" if a.session else "r11_encode_device.json")
     if a.no_tail:
@@ -290,6 +384,8 @@ def main():
         return int24_leg(a)
     if a.out_device:
         return out_device_leg(a)
+    if a.stream_writer:
+        return stream_writer_leg(a)
     if a.session:
         return session_leg(a)
     from flac_codec_amd import _lib
