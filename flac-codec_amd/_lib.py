@@ -177,6 +177,17 @@ class RawStream(C.Structure):
                 ("gaps", C.c_uint32), ("uniform", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class SessionTiming(C.Structure):
+    """flacgpu_session_timing: where the host's time went in a decoder session's last feed, in milliseconds."""
+    _fields_ = [(name, C.c_double) for name in ("stage_ms", "to_first_sync_ms", "to_second_sync_ms", "scan_rest_ms",
+                                                "walk_ms", "table_upload_ms")]
+
+
+class SessionSlotSrc(C.Structure):
+    """flacgpu_session_slot_src: one slot's held tail and new chunk, for flacgpu_session_slots_host."""
+    _fields_ = [("tail", C.c_void_p), ("tail_len", C.c_uint64), ("chunk", C.c_void_p), ("chunk_len", C.c_uint64)]
+
+
 class TimelineFrame(C.Structure):
     """flacgpu_timeline_frame: one record's place on its stream's timeline (16 bytes)."""
     _fields_ = [("at", C.c_uint64), ("flags", C.c_uint32), ("status", C.c_uint32)]
@@ -315,6 +326,25 @@ def _load():
     L.flacgpu_decoder_slot_bytes.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_uint64)]
     L.flacgpu_meta_walk_host.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(StreamInfo), C.POINTER(C.c_uint32),
                                          C.POINTER(C.c_uint64)]
+    u8p, szp, q = C.POINTER(C.c_uint8), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)
+    feed_out = [C.POINTER(DecodedStream), C.POINTER(RawStream), q, q, q]
+    L.flacgpu_decoder_session_open.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(vp)]
+    L.flacgpu_decoder_session_feed.argtypes = [vp, C.POINTER(C.c_void_p), szp, u8p] + feed_out
+    L.flacgpu_decoder_session_feed_device.argtypes = [vp, C.POINTER(C.c_void_p), szp, u8p, vp] + feed_out
+    L.flacgpu_decoder_session_finish.argtypes = [vp] + feed_out
+    L.flacgpu_decoder_session_pending.argtypes = [vp, q, q]
+    L.flacgpu_decoder_session_last_feed_timing.argtypes = [vp, C.POINTER(SessionTiming)]
+    L.flacgpu_decoder_session_decoder.argtypes = [vp]
+    L.flacgpu_decoder_session_decoder.restype = vp
+    L.flacgpu_decoder_session_close.argtypes = [vp]
+    L.flacgpu_decoder_session_close.restype = None
+    L.flacgpu_session_host_open.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(vp)]
+    L.flacgpu_session_host_feed.argtypes = [vp, C.POINTER(C.c_void_p), szp, u8p, C.POINTER(FrameRecord), C.c_size_t,
+                                            C.POINTER(RawStream), q, q]
+    L.flacgpu_session_host_finish.argtypes = [vp, C.POINTER(FrameRecord), C.c_size_t, C.POINTER(RawStream), q]
+    L.flacgpu_session_host_close.argtypes = [vp]
+    L.flacgpu_session_host_close.restype = None
+    L.flacgpu_session_slots_host.argtypes = [C.POINTER(SessionSlotSrc), C.c_uint32, vp, C.c_size_t, q]
     L.flacgpu_decoder_frame_records.argtypes = [vp, C.POINTER(FrameRecord), C.c_size_t]
     L.flacgpu_decoder_decode_frames.argtypes = [vp, vp, C.c_size_t, C.c_uint32, C.POINTER(FrameRecord), C.c_size_t]
     L.flacgpu_timeline_host.argtypes = [C.POINTER(FrameRecord), C.c_size_t, C.POINTER(TimelineFrame), C.c_size_t,

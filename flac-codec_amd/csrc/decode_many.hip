@@ -8,12 +8,15 @@
 #include "kernels/frame_extent.h"
 #include "kernels/meta_walk.h"
 #include "kernels/byte_shift.h"
+#include "kernels/session_slots_rule.h"
 #include "flac_stream.h"
+#include "session_rule.h"
 
 #include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
+#include <chrono>
 #include <new>
 #include <string>
 #include <type_traits>
@@ -26,6 +29,7 @@ namespace {
 #include "kernels/frame_scan.inc"
 #include "kernels/spec_end.inc"
 #include "kernels/gather.inc"
+#include "kernels/session.inc"
 #include "kernels/decode_many.inc"
 
 constexpr uint32_t kSlotTail = 64;   // zero bytes behind every stream's region (at least)
@@ -102,6 +106,10 @@ struct flacgpu_decoder {
     bool raw_tab_uploaded = false;
     DevBuf raw_frames;
     uint64_t raw_elements = 0, raw_scratch = 0;
+    bool session = false;   // owned by a flacgpu_decoder_session: the scan calls and destroy are refused
+    // the last device_scan, seconds: from its start to the end of its first synchronisation (the candidate count), and
+    // from there to the end of its second (the candidates); read by a session's flacgpu_decoder_session_last_feed_timing
+    double scan_sync_s[2] = {0, 0};
 };
 
 namespace {
@@ -140,16 +148,27 @@ struct Candidates {
     uint32_t end_of(uint32_t s) const { return s + 1 < cand0.size() ? cand0[s + 1] : n; }
 };
 
+// A decoder session's feed (kernels/session.inc): every slot is built by k_session_slots from `srcs` (device addresses),
+// and the links are k_link_session's under `info`; both tables have one entry per slot and go up into the two buffers.
+struct SessionFill {
+    const SessionSrc *srcs;
+    const SessionSlot *info;
+    DevBuf *src_tab, *info_tab;
+};
+
 // The device half of a scan: fills every slot (zero tails, 64 bytes of look-ahead) -- host input in one upload, device
-// input with k_gather_slots -- and runs the scan kernels; the candidates come down into `c`.  raw: the scan of raw frame
-// streams (k_scan_subset, k_link_raw), with the extents and the headers it asks for.
+// input with k_gather_slots, a session's feed (fill != null; `in` is not looked at) with k_session_slots -- and runs the
+// scan kernels; the candidates come down into `c`.  raw: the scan of raw frame streams (k_scan_subset, k_link_raw or a
+// session's k_link_session), with the extents and the headers it asks for.
 int device_scan(flacgpu_decoder *d, const ScanInput &in, const SlotLayout &lay, bool raw, bool want_spec, bool want_heads,
-                Candidates &c) {
+                Candidates &c, const SessionFill *fill = nullptr) {
     const std::vector<ScanSlot> &slots = lay.slots;
     const uint64_t at = lay.at;
     const uint32_t S = (uint32_t)slots.size();
     const uint8_t *const *data = in.data;
-    const std::string who = std::string(raw ? "flacgpu_decoder_scan_frames" : "flacgpu_decoder_scan") + (in.device ? "_device" : "");
+    const auto t_begin = std::chrono::steady_clock::now();   // (scan_sync_s: three clock reads a scan)
+    const std::string who = fill ? std::string("flacgpu_decoder_session_feed")
+                                 : std::string(raw ? "flacgpu_decoder_scan_frames" : "flacgpu_decoder_scan") + (in.device ? "_device" : "");
     // the bit reader indexes dwords with 32 bits
     if (at + 64 > ((uint64_t)1 << 34)) {
         g_last_error = who + ": the batch's frames exceed 16 GiB";
@@ -162,7 +181,10 @@ int device_scan(flacgpu_decoder *d, const ScanInput &in, const SlotLayout &lay, 
     const size_t buf_bytes = at + 64;
     uint8_t *stg = nullptr;
     std::vector<const uint8_t *> srcs;   // device input: every region's first byte
-    if (in.device) {
+    if (fill) {
+        if (int rc = fill->src_tab->ensure(sizeof(SessionSrc) * S)) return rc;
+        if (int rc = fill->info_tab->ensure(sizeof(SessionSlot) * S)) return rc;
+    } else if (in.device) {
         try {
             srcs.resize(S);
         } catch (const std::bad_alloc &) {
@@ -193,9 +215,16 @@ int device_scan(flacgpu_decoder *d, const ScanInput &in, const SlotLayout &lay, 
     if (int rc = d->slot_cand0.ensure(4 * S)) return rc;
     if (int rc = d->slot_pend.ensure(4 * S)) return rc;
     d->slot_bytes = buf_bytes;
-    if (!in.device) HIP_TRY(hipMemcpyAsync(d->bytes.p, stg, buf_bytes, hipMemcpyHostToDevice, d->st));
+    if (!fill && !in.device) HIP_TRY(hipMemcpyAsync(d->bytes.p, stg, buf_bytes, hipMemcpyHostToDevice, d->st));
     HIP_TRY(hipMemcpyAsync(d->slots.p, slots.data(), sizeof(ScanSlot) * S, hipMemcpyHostToDevice, d->st));
-    if (in.device) {   // the gather: every byte of [0, buf_bytes), a lane per 16-byte group
+    if (fill) {   // tail and chunk into every slot: every byte of [0, buf_bytes), a lane per 16-byte group
+        HIP_TRY(hipMemcpyAsync(fill->src_tab->p, fill->srcs, sizeof(SessionSrc) * S, hipMemcpyHostToDevice, d->st));
+        HIP_TRY(hipMemcpyAsync(fill->info_tab->p, fill->info, sizeof(SessionSlot) * S, hipMemcpyHostToDevice, d->st));
+        const uint64_t n_groups = buf_bytes / 16;
+        hipLaunchKernelGGL(k_session_slots, dim3((uint32_t)((n_groups + WG - 1) / WG)), dim3(WG), 0, d->st,
+                           d->bytes.as<uint8_t>(), d->slots.as<const ScanSlot>(), fill->src_tab->as<const SessionSrc>(), S,
+                           n_blocks, n_groups);
+    } else if (in.device) {   // the gather: every byte of [0, buf_bytes), a lane per 16-byte group
         HIP_TRY(hipMemcpyAsync(d->gather_src.p, srcs.data(), sizeof(const uint8_t *) * S, hipMemcpyHostToDevice, d->st));
         const uint64_t n_groups = buf_bytes / 16;   // buf_bytes is a multiple of 64, at most 2^34: the grid fits
         hipLaunchKernelGGL(k_gather_slots, dim3((uint32_t)((n_groups + WG - 1) / WG)), dim3(WG), 0, d->st,
@@ -222,6 +251,7 @@ int device_scan(flacgpu_decoder *d, const ScanInput &in, const SlotLayout &lay, 
     uint32_t n_cand = 0;
     HIP_TRY(hipMemcpyAsync(&n_cand, d->wg_off.as<uint32_t>() + n_wg, 4, hipMemcpyDeviceToHost, d->st));
     HIP_TRY(hipStreamSynchronize(d->st));
+    const auto t_count = std::chrono::steady_clock::now();
     const size_t nc = std::max<uint32_t>(n_cand, 1);
     if (int rc = d->cand_pos.ensure(8 * nc)) return rc;
     if (int rc = d->cand_info.ensure(4 * nc)) return rc;
@@ -239,7 +269,10 @@ int device_scan(flacgpu_decoder *d, const ScanInput &in, const SlotLayout &lay, 
     p.link = d->link.as<int32_t>();
     p.n_cand = n_cand;
     hipLaunchKernelGGL(k_scan_emit, dim3(n_wg), dim3(WG), 0, d->st, p);
-    if (n_cand && raw) hipLaunchKernelGGL(k_link_raw, dim3((n_cand + WG - 1) / WG), dim3(WG), 0, d->st, p);
+    if (n_cand && fill)
+        hipLaunchKernelGGL(k_link_session, dim3((n_cand + WG - 1) / WG), dim3(WG), 0, d->st, p,
+                           fill->info_tab->as<const SessionSlot>());
+    else if (n_cand && raw) hipLaunchKernelGGL(k_link_raw, dim3((n_cand + WG - 1) / WG), dim3(WG), 0, d->st, p);
     else if (n_cand) hipLaunchKernelGGL(k_link, dim3((n_cand + WG - 1) / WG), dim3(WG), 0, d->st, p);
     if (n_cand && want_spec)
         hipLaunchKernelGGL(k_spec_end, dim3((n_cand + 63) / 64), dim3(64), 0, d->st, p, d->spec_len.as<uint32_t>());
@@ -269,6 +302,8 @@ int device_scan(flacgpu_decoder *d, const ScanInput &in, const SlotLayout &lay, 
     }
     HIP_TRY(hipMemcpyAsync(c.cand0.data(), p.slot_cand0, 4 * (size_t)S, hipMemcpyDeviceToHost, d->st));
     HIP_TRY(hipStreamSynchronize(d->st));
+    d->scan_sync_s[0] = std::chrono::duration<double>(t_count - t_begin).count();
+    d->scan_sync_s[1] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_count).count();
     c.n = n_cand;
     return FLACGPU_OK;
 }
@@ -392,6 +427,83 @@ int scan_impl(flacgpu_decoder *d, const ScanInput &in, const size_t *len, uint32
     return finish_scan(d, lay, total, scratch_total);
 }
 
+// The running sizes of a raw scan's two layouts: decode_frames' (every kept frame) and the regular batch calls' (the
+// uniform streams alone).
+struct RawTotals {
+    uint64_t elements = 0, raw_scratch = 0, total = 0, scratch_total = 0;
+};
+
+// A kept frame [at, end) of stream i (positions in the batch buffer; slot_end: the end of its slot): its record, with
+// byte_offset as given, and its entry in decode_frames' table.  The header was accepted by K_s1: n, header_bytes and the
+// blocking bit come from its candidate record, the rest from the header's bytes `head` (header_bytes <= kHeadBytes).
+void keep_raw_frame(flacgpu_decoder *d, uint32_t i, uint64_t at, uint64_t end, uint64_t slot_end, uint64_t byte_offset,
+                    uint32_t cinfo, const uint8_t *head, bool own, RawTotals &tot) {
+    flacenc::HostFrameInfo h;
+    h.n = (cinfo & 0xFFFFu) + 1u;
+    h.header_bytes = (cinfo >> 16) & 0xFFu;
+    h.blocking = cinfo >> 24;
+    h.acode = head[3] >> 4;
+    h.bps_code = (head[3] >> 1) & 7;
+    flacenc::host_frame_fields(head, h);
+    flacgpu_frame_record f{};
+    f.byte_offset = byte_offset;
+    f.number = h.number;
+    f.out_offset = tot.elements;
+    f.stream = i;
+    f.bytes = (uint32_t)(end - at);
+    f.block_size = h.n;
+    f.sample_rate = h.sample_rate;
+    f.channels = h.channels;
+    f.bits_per_sample = h.bits_per_sample;
+    f.assignment = h.acode;
+    f.blocking = h.blocking;
+    f.reserved = own ? FLACGPU_FRAME_SPECULATIVE : 0u;
+    ManyFrame m{};
+    m.start = at;
+    m.end = end;
+    m.cap = slot_end - 4;
+    m.scratch = tot.raw_scratch;
+    m.out = tot.elements;
+    m.n = h.n;
+    m.slot = (uint32_t)d->records.size();   // the frame kernels count per slot: per frame here
+    m.channels = h.channels;
+    m.bps = h.bits_per_sample;
+    d->records.push_back(f);
+    d->raw_tab.push_back(m);
+    tot.elements += (uint64_t)h.n * h.channels;
+    tot.raw_scratch += (uint64_t)h.channels * ((h.n + 3u) & ~3u);
+}
+
+// Stream i's place in the regular batch calls, from its `count` records from `first` on (slot s): a uniform stream joins
+// frame_tab and the uniform streams' layout, any other is absent from those calls.
+void join_regular(flacgpu_decoder *d, uint32_t i, int32_t s, size_t first, size_t count, bool uniform, RawTotals &tot) {
+    flacgpu_decoded_stream &r = d->res[i];
+    r.out_offset = tot.total;
+    if (!uniform) {
+        r.rc = count ? FLACGPU_ERR_UNSUPPORTED : FLACGPU_ERR_INVALID_ARG;
+        return;
+    }
+    const flacgpu_frame_record &f0 = d->records[first];
+    r.info.sample_rate = f0.sample_rate;
+    r.info.channels = f0.channels;
+    r.info.bits_per_sample = f0.bits_per_sample;
+    r.info.min_block = r.info.max_block = f0.block_size;
+    r.info.frames = (uint32_t)count;
+    for (size_t k = first; k < first + count; k++) {
+        const flacgpu_frame_record &f = d->records[k];
+        r.info.min_block = std::min(r.info.min_block, f.block_size);
+        r.info.max_block = std::max(r.info.max_block, f.block_size);
+        ManyFrame m = d->raw_tab[k];
+        m.slot = (uint32_t)s;
+        m.out = tot.total + r.info.decoded_samples * f.channels;
+        m.scratch = tot.scratch_total;
+        tot.scratch_total += (uint64_t)m.channels * ((m.n + 3u) & ~3u);
+        d->frame_tab.push_back(m);
+        r.info.decoded_samples += f.block_size;
+    }
+    tot.total += r.info.decoded_samples * r.info.channels;
+}
+
 // flacgpu_decoder_scan_frames behind its argument checks: a slot is a whole input, the device finds the candidates and
 // their ends by the raw rule, and the host walks them with a cursor (DESIGN.md "Raw frame streams").  Under
 // FLACGPU_SCAN_SPECULATIVE a candidate without a link ends where its own extent does, if it has one.
@@ -427,13 +539,12 @@ int scan_raw_impl(flacgpu_decoder *d, const ScanInput &in, const size_t *len, ui
     all.clear();
     d->raw_tab_uploaded = false;
     const uint8_t *stg = d->staging.as<const uint8_t>();
-    uint64_t elements = 0, total = 0, raw_scratch = 0, scratch_total = 0;
+    RawTotals tot;
     try {
         d->records.reserve(n_cand);   // a kept frame is a candidate
         all.reserve(n_cand);
         d->frame_tab.reserve(n_cand);
         for (uint32_t i = 0; i < n; i++) {
-            flacgpu_decoded_stream &r = d->res[i];
             flacgpu_raw_stream &sum = d->raw_streams[i];
             const size_t first = d->records.size();
             const int32_t s = d->slot_of[i];
@@ -448,72 +559,15 @@ int scan_raw_impl(flacgpu_decoder *d, const ScanInput &in, const size_t *len, ui
                     const bool own = link == LINK_NONE && spec && c.spec[k];
                     if (at < cursor || (link == LINK_NONE && !own)) continue;
                     const uint64_t end = own ? at + c.spec[k] : link == LINK_END ? sl.base + sl.len : c.pos[link];
-                    flacenc::HostFrameInfo h;   // the header was accepted by K_s1: its record, and the rest from its bytes
-                    h.n = (cinfo & 0xFFFFu) + 1u;
-                    h.header_bytes = (cinfo >> 16) & 0xFFu;
-                    h.blocking = cinfo >> 24;
                     const uint8_t *head = in.device ? c.heads.data() + kHeadBytes * (size_t)k : stg + at;
-                    h.acode = head[3] >> 4;
-                    h.bps_code = (head[3] >> 1) & 7;
-                    flacenc::host_frame_fields(head, h);   // reads header_bytes <= kHeadBytes bytes
-                    flacgpu_frame_record f{};
-                    f.byte_offset = at - sl.base;
-                    f.number = h.number;
-                    f.out_offset = elements;
-                    f.stream = i;
-                    f.bytes = (uint32_t)(end - at);
-                    f.block_size = h.n;
-                    f.sample_rate = h.sample_rate;
-                    f.channels = h.channels;
-                    f.bits_per_sample = h.bits_per_sample;
-                    f.assignment = h.acode;
-                    f.blocking = h.blocking;
-                    f.reserved = own ? FLACGPU_FRAME_SPECULATIVE : 0u;
-                    ManyFrame m{};
-                    m.start = at;
-                    m.end = end;
-                    m.cap = lay.end_of((uint32_t)s) - 4;
-                    m.scratch = raw_scratch;
-                    m.out = elements;
-                    m.n = h.n;
-                    m.slot = (uint32_t)d->records.size();   // the frame kernels count per slot: per frame here
-                    m.channels = h.channels;
-                    m.bps = h.bits_per_sample;
-                    d->records.push_back(f);
-                    all.push_back(m);
-                    elements += (uint64_t)h.n * h.channels;
-                    raw_scratch += (uint64_t)h.channels * ((h.n + 3u) & ~3u);
+                    keep_raw_frame(d, i, at, end, lay.end_of((uint32_t)s), at - sl.base, cinfo, head, own, tot);
                     cursor = end;
                 }
             }
             const size_t count = d->records.size() - first;
             flacenc::summarise_raw_frames(d->records.data() + first, count, len[i], sum);
             sum.first_frame = first;
-            // ---- the stream's place in the regular batch calls
-            r.out_offset = total;
-            if (!sum.uniform) {
-                r.rc = count ? FLACGPU_ERR_UNSUPPORTED : FLACGPU_ERR_INVALID_ARG;
-                continue;
-            }
-            const flacgpu_frame_record &f0 = d->records[first];
-            r.info.sample_rate = f0.sample_rate;
-            r.info.channels = f0.channels;
-            r.info.bits_per_sample = f0.bits_per_sample;
-            r.info.min_block = r.info.max_block = f0.block_size;
-            r.info.frames = (uint32_t)count;
-            for (size_t k = first; k < first + count; k++) {
-                const flacgpu_frame_record &f = d->records[k];
-                r.info.min_block = std::min(r.info.min_block, f.block_size);
-                r.info.max_block = std::max(r.info.max_block, f.block_size);
-                ManyFrame m = all[k];
-                m.slot = (uint32_t)s;
-                m.out = total + r.info.decoded_samples * f.channels;
-                m.scratch = scratch_total;
-                scratch_total += (uint64_t)m.channels * ((m.n + 3u) & ~3u);
-                d->frame_tab.push_back(m);
-                r.info.decoded_samples += f.block_size;
-            }
-            total += r.info.decoded_samples * r.info.channels;
+            join_regular(d, i, s, first, count, sum.uniform, tot);
         }
     } catch (const std::bad_alloc &) {
         g_last_error = "flacgpu_decoder_scan_frames: out of host memory";
@@ -523,9 +577,166 @@ int scan_raw_impl(flacgpu_decoder *d, const ScanInput &in, const size_t *len, ui
         g_last_error = "flacgpu_decoder_scan_frames: more than 2^31 - 1 frames";
         return FLACGPU_ERR_UNSUPPORTED;
     }
-    d->raw_elements = elements;
-    d->raw_scratch = raw_scratch;
-    return finish_scan(d, lay, total, scratch_total);
+    d->raw_elements = tot.elements;
+    d->raw_scratch = tot.raw_scratch;
+    return finish_scan(d, lay, tot.total, tot.scratch_total);
+}
+}  // namespace
+
+// A decoder session (include/flacenc_gpu.h "sessions that take raw frame streams chunk by chunk"; DESIGN.md 4b "Decoder
+// sessions").  The decoder's batch buffer and `other` take turns: a feed builds its slots in the one while the held tails
+// still lie in the other.
+struct flacgpu_decoder_session {
+    struct Stream {
+        uint64_t base = 0;   // offset of the first held byte from the stream's first byte
+        uint64_t held = 0;   // bytes not decided yet
+        uint64_t at = 0;     // where they lie in the decoder's batch buffer
+        flacenc::SessionCount count;
+    };
+    flacgpu_decoder *d = nullptr;
+    std::vector<Stream> streams;
+    uint32_t W = 0;
+    uint64_t fed = 0;
+    bool finished = false, dead = false;   // dead: a call failed half way; every further call is refused
+    flacgpu_session_timing timing{};       // of the last feed or finish
+    DevBuf other, chunks, src_tab, info_tab;
+};
+
+namespace {
+// One feed behind its argument checks (finish: no bytes, every stream flushed).  chunk[i]: DEVICE address of stream i's
+// new bytes (null: none), len[i] their count.  The slots are tail + chunk, built and scanned on the device; the host
+// walks the links as scan_raw_impl does, stops at the first LINK_HOLD and keeps the session's counts.
+int session_step(flacgpu_decoder_session *ses, const uint8_t *const *chunk, const uint64_t *len, const uint8_t *flush,
+                 bool finish) {
+    flacgpu_decoder *d = ses->d;
+    const uint32_t n = (uint32_t)ses->streams.size();
+    SlotLayout lay;
+    Candidates c;
+    std::vector<SessionSrc> srcs;
+    std::vector<SessionSlot> info;
+    const uint8_t *const tails = d->bytes.as<const uint8_t>();   // `other` from the swap below on
+    // the feed's layout and the decoder's new per-stream tables, in locals: a call refused below has touched neither the
+    // session nor its decoder, whose last feed can still be decoded
+    std::vector<flacgpu_decoded_stream> res;
+    std::vector<int32_t> slot_of;
+    std::vector<flacgpu_raw_stream> raw_streams;
+    try {
+        res.assign(n, flacgpu_decoded_stream{});
+        slot_of.assign(n, -1);
+        raw_streams.assign(n, flacgpu_raw_stream{});
+        for (uint32_t i = 0; i < n; i++) {
+            const flacgpu_decoder_session::Stream &st = ses->streams[i];
+            const uint64_t fresh = chunk && chunk[i] ? len[i] : 0;
+            if (!(st.held + fresh)) continue;   // nothing held, nothing new
+            slot_of[i] = (int32_t)lay.add(i, 0, st.held + fresh, 0, 0);
+            srcs.push_back(SessionSrc{reinterpret_cast<uint64_t>(tails + st.at), st.held,
+                                      fresh ? reinterpret_cast<uint64_t>(chunk[i]) : 0, fresh});
+            info.push_back(SessionSlot{finish || (flush && flush[i]) ? 1u : 0u, ses->W});
+        }
+    } catch (const std::bad_alloc &) {
+        g_last_error = "flacgpu_decoder_session_feed: out of host memory";
+        return FLACGPU_ERR_UNSUPPORTED;
+    }
+    const uint32_t S = (uint32_t)lay.slots.size();
+    if (lay.at + 64 > ((uint64_t)1 << 34)) {   // device_scan's limit, before anything has changed
+        g_last_error = "flacgpu_decoder_session_feed: the feed's slots exceed 16 GiB";
+        return FLACGPU_ERR_UNSUPPORTED;
+    }
+    // ---- from here on the feed is under way (nothing below up to the scan allocates)
+    d->scanned = d->raw = false;
+    d->res.swap(res);
+    d->slot_of.swap(slot_of);
+    d->raw_streams.swap(raw_streams);
+    d->frame_tab.clear();
+    d->records.clear();
+    d->n_slots = S;
+    d->slot_bytes = 0;
+    ses->dead = true;   // until the feed is through: a failure from here on leaves the tails in neither buffer for certain
+    std::swap(d->bytes.p, ses->other.p);
+    std::swap(d->bytes.cap, ses->other.cap);
+    const auto t0 = std::chrono::steady_clock::now();
+    if (S) {
+        const SessionFill fill{srcs.data(), info.data(), &ses->src_tab, &ses->info_tab};
+        if (int rc = device_scan(d, ScanInput{nullptr, true}, lay, true, false, true, c, &fill)) return rc;
+    } else {
+        d->scan_sync_s[0] = d->scan_sync_s[1] = 0;
+    }
+    const auto t1 = std::chrono::steady_clock::now();
+    std::vector<ManyFrame> &all = d->raw_tab;
+    all.clear();
+    d->raw_tab_uploaded = false;
+    RawTotals tot;
+    try {
+        d->records.reserve(c.n);
+        all.reserve(c.n);
+        d->frame_tab.reserve(c.n);
+        for (uint32_t i = 0; i < n; i++) {
+            flacgpu_decoder_session::Stream &st = ses->streams[i];
+            const size_t first = d->records.size();
+            const int32_t s = d->slot_of[i];
+            if (s >= 0) {
+                const ScanSlot &sl = lay.slots[s];
+                const uint64_t slot_end = sl.base + sl.len;
+                const uint32_t c_end = c.end_of((uint32_t)s);
+                uint64_t cursor = sl.base, hold = slot_end;
+                for (uint32_t k = c.cand0[s]; k < c_end; k++) {
+                    const uint64_t at = c.pos[k];
+                    const int32_t link = c.link[k];
+                    if (at < cursor || link == LINK_NONE) continue;
+                    if (link == LINK_HOLD) {
+                        hold = at;
+                        break;
+                    }
+                    const uint64_t end = link == LINK_END ? slot_end : c.pos[link];
+                    st.count.skip(at - cursor);
+                    st.count.keep();
+                    keep_raw_frame(d, i, at, end, lay.end_of((uint32_t)s), st.base + (at - sl.base), c.info[k],
+                                   c.heads.data() + kHeadBytes * (size_t)k, false, tot);
+                    cursor = end;
+                }
+                // nothing from L - 15 on is judged in an open segment; a flushed one is decided to its end
+                const uint64_t at_most = sl.base + (sl.len >= flacenc::kSessionHead ? sl.len - flacenc::kSessionHead + 1 : 0);
+                const uint64_t h = info[s].final ? slot_end : std::max(cursor, std::min(hold, at_most));
+                st.count.skip(h - cursor);
+                st.base += h - sl.base;
+                st.held = slot_end - h;
+                st.at = h;
+            }
+            const size_t count = d->records.size() - first;
+            flacgpu_raw_stream &sum = d->raw_streams[i];
+            sum.first_frame = first;
+            sum.skipped_bytes = st.count.skipped;
+            sum.frames = st.count.frames;
+            sum.gaps = st.count.gaps;
+            sum.uniform = count > 0;
+            for (size_t k = first + 1; k < first + count; k++)
+                if (d->records[k].sample_rate != d->records[first].sample_rate ||
+                    d->records[k].channels != d->records[first].channels ||
+                    d->records[k].bits_per_sample != d->records[first].bits_per_sample)
+                    sum.uniform = 0;
+            join_regular(d, i, s, first, count, sum.uniform, tot);
+        }
+    } catch (const std::bad_alloc &) {
+        g_last_error = "flacgpu_decoder_session_feed: out of host memory";
+        return FLACGPU_ERR_UNSUPPORTED;
+    }
+    if (all.size() > 0x7FFFFFFFull) {   // scan_raw_impl's refusal: the frame kernels index frames with 31 bits
+        g_last_error = "flacgpu_decoder_session_feed: more than 2^31 - 1 frames";
+        return FLACGPU_ERR_UNSUPPORTED;
+    }
+    d->raw_elements = tot.elements;
+    d->raw_scratch = tot.raw_scratch;
+    const auto t2 = std::chrono::steady_clock::now();
+    if (int rc = finish_scan(d, lay, tot.total, tot.scratch_total)) return rc;
+    const auto t3 = std::chrono::steady_clock::now();
+    const auto ms = [](std::chrono::steady_clock::duration v) { return std::chrono::duration<double, std::milli>(v).count(); };
+    ses->timing.to_first_sync_ms = d->scan_sync_s[0] * 1e3;
+    ses->timing.to_second_sync_ms = d->scan_sync_s[1] * 1e3;
+    ses->timing.scan_rest_ms = ms(t1 - t0) - ses->timing.to_first_sync_ms - ses->timing.to_second_sync_ms;
+    ses->timing.walk_ms = ms(t2 - t1);
+    ses->timing.table_upload_ms = ms(t3 - t2);
+    ses->dead = false;
+    return FLACGPU_OK;
 }
 
 // The frame kernels over one frame table, for every decode call: K_d1 decodes each frame into planar scratch, K_d2 tests
@@ -1181,7 +1392,7 @@ int flacgpu_decoder_create(int device, flacgpu_decoder **out) {
 }
 
 void flacgpu_decoder_destroy(flacgpu_decoder *d) {
-    if (!d) return;
+    if (!d || d->session) return;   // a session's decoder goes with its session (flacgpu_decoder_session_close)
     int prev = -1;
     (void)hipGetDevice(&prev);
     (void)hipSetDevice(d->device);
@@ -1192,6 +1403,13 @@ void flacgpu_decoder_destroy(flacgpu_decoder *d) {
     d->ev = nullptr;
     delete d;   // the buffers free themselves, on the decoder's device
     if (prev >= 0) (void)hipSetDevice(prev);
+}
+
+// A session's decoder takes its batches from the session's feeds alone: the scan calls leave it as it is.
+static bool session_owned(const flacgpu_decoder *d, const char *who) {
+    if (!d->session) return false;
+    g_last_error = std::string(who) + ": the handle belongs to a decoder session (feed the session instead)";
+    return true;
 }
 
 // The four scans behind their argument checks: the host door and the device door differ in `in` alone.
@@ -1256,6 +1474,7 @@ static int open_device_door(flacgpu_decoder *d, const uint8_t *const *d_data, co
 int flacgpu_decoder_scan(flacgpu_decoder *d, const uint8_t *const *data, const size_t *len, uint32_t n_streams,
                          flacgpu_decoded_stream *streams, uint64_t *total_samples) {
     if (!d || (n_streams && (!data || !len || !streams)) || !total_samples) return FLACGPU_ERR_INVALID_ARG;
+    if (session_owned(d, "flacgpu_decoder_scan")) return FLACGPU_ERR_INVALID_ARG;
     d->scanned = d->raw = false;
     DeviceGuard guard(d->device);
     return scan_call(d, ScanInput{data, false}, len, n_streams, streams, total_samples);
@@ -1267,6 +1486,7 @@ int flacgpu_decoder_scan_device(flacgpu_decoder *d, const uint8_t *const *d_data
         g_last_error = "flacgpu_decoder_scan_device: a NULL handle or a missing array";
         return FLACGPU_ERR_INVALID_ARG;
     }
+    if (session_owned(d, "flacgpu_decoder_scan_device")) return FLACGPU_ERR_INVALID_ARG;
     d->scanned = d->raw = false;
     DeviceGuard guard(d->device);
     if (int rc = open_device_door(d, d_data, len, n_streams, stream, "flacgpu_decoder_scan_device")) return rc;
@@ -1286,6 +1506,7 @@ int flacgpu_decoder_scan_frames_ex(flacgpu_decoder *d, const uint8_t *const *dat
     if (!d || (n_streams && (!data || !len || !streams)) || !total_frames || !total_elements || !total_samples ||
         (flags & ~FLACGPU_SCAN_SPECULATIVE))
         return FLACGPU_ERR_INVALID_ARG;
+    if (session_owned(d, "flacgpu_decoder_scan_frames_ex")) return FLACGPU_ERR_INVALID_ARG;
     d->scanned = d->raw = false;
     DeviceGuard guard(d->device);
     return scan_frames_call(d, ScanInput{data, false}, len, n_streams, flags, streams, raw, total_frames, total_elements,
@@ -1301,6 +1522,7 @@ int flacgpu_decoder_scan_frames_device(flacgpu_decoder *d, const uint8_t *const 
         g_last_error = "flacgpu_decoder_scan_frames_device: a NULL handle, a missing array or an unknown flag";
         return FLACGPU_ERR_INVALID_ARG;
     }
+    if (session_owned(d, "flacgpu_decoder_scan_frames_device")) return FLACGPU_ERR_INVALID_ARG;
     d->scanned = d->raw = false;
     DeviceGuard guard(d->device);
     if (int rc = open_device_door(d, d_data, len, n_streams, stream, "flacgpu_decoder_scan_frames_device")) return rc;
@@ -1324,6 +1546,204 @@ int flacgpu_decoder_slot_bytes(flacgpu_decoder *d, uint8_t *out, size_t cap, uin
     DeviceGuard guard(d->device);
     HIP_TRY(hipMemcpyAsync(out, d->bytes.p, d->slot_bytes, hipMemcpyDeviceToHost, d->st));
     HIP_TRY(hipStreamSynchronize(d->st));
+    return FLACGPU_OK;
+}
+
+int flacgpu_decoder_session_open(int device, uint32_t n_streams, uint32_t max_frame_bytes, uint32_t flags,
+                                 flacgpu_decoder_session **out) {
+    if (!out) return FLACGPU_ERR_INVALID_ARG;
+    *out = nullptr;
+    if (flags || max_frame_bytes < flacenc::kSessionMinW || max_frame_bytes > flacenc::kSessionMaxW) {
+        g_last_error = "flacgpu_decoder_session_open: an unknown flag, or max_frame_bytes outside 16 .. 2^22";
+        return FLACGPU_ERR_INVALID_ARG;
+    }
+    flacgpu_decoder *d = nullptr;
+    if (int rc = flacgpu_decoder_create(device, &d)) return rc;
+    flacgpu_decoder_session *s = new (std::nothrow) flacgpu_decoder_session();
+    try {
+        if (s) s->streams.resize(n_streams);
+    } catch (const std::bad_alloc &) {
+        delete s;
+        s = nullptr;
+    }
+    if (!s) {
+        flacgpu_decoder_destroy(d);
+        g_last_error = "flacgpu_decoder_session_open: out of host memory";
+        return FLACGPU_ERR_UNSUPPORTED;
+    }
+    d->session = true;
+    s->d = d;
+    s->W = max_frame_bytes;
+    *out = s;
+    return FLACGPU_OK;
+}
+
+void flacgpu_decoder_session_close(flacgpu_decoder_session *s) {
+    if (!s) return;
+    flacgpu_decoder *d = s->d;
+    {
+        DeviceGuard guard(d->device);
+        if (d->st) (void)hipStreamSynchronize(d->st);
+        s->other.release();   // on the session's device, as the decoder's own buffers
+        s->chunks.release();
+        s->src_tab.release();
+        s->info_tab.release();
+    }
+    delete s;
+    d->session = false;
+    flacgpu_decoder_destroy(d);
+}
+
+flacgpu_decoder *flacgpu_decoder_session_decoder(flacgpu_decoder_session *s) { return s ? s->d : nullptr; }
+
+int flacgpu_decoder_session_pending(flacgpu_decoder_session *s, uint64_t *held_bytes, uint64_t *fed_bytes) {
+    if (!s || s->dead) return FLACGPU_ERR_INVALID_ARG;
+    for (size_t i = 0; held_bytes && i < s->streams.size(); i++) held_bytes[i] = s->streams[i].held;
+    if (fed_bytes) *fed_bytes = s->fed;
+    return FLACGPU_OK;
+}
+
+// The three feeds behind one set of checks.  door: 0 host memory, 1 device memory, 2 finish.
+static int session_call(flacgpu_decoder_session *s, int door, const uint8_t *const *data, const size_t *len,
+                        const uint8_t *flush, void *stream, flacgpu_decoded_stream *streams, flacgpu_raw_stream *raw,
+                        uint64_t *total_frames, uint64_t *total_elements, uint64_t *total_samples) {
+    static const char *const kWho[3] = {"flacgpu_decoder_session_feed", "flacgpu_decoder_session_feed_device",
+                                        "flacgpu_decoder_session_finish"};
+    const char *who = kWho[door];
+    const uint32_t n = s ? (uint32_t)s->streams.size() : 0;
+    if (!s || (n && ((door != 2 && (!data || !len)) || !streams)) || !total_frames || !total_elements || !total_samples) {
+        g_last_error = std::string(who) + ": a NULL handle or a missing array";
+        return FLACGPU_ERR_INVALID_ARG;
+    }
+    if (s->dead || s->finished) {
+        g_last_error = std::string(who) + (s->dead ? ": an earlier call on this session failed" : ": the session is finished");
+        return FLACGPU_ERR_INVALID_ARG;
+    }
+    flacgpu_decoder *d = s->d;
+    DeviceGuard guard(d->device);
+    const auto t_in = std::chrono::steady_clock::now();
+    std::vector<const uint8_t *> chunk;
+    std::vector<uint64_t> bytes;
+    uint64_t fresh = 0;
+    try {
+        chunk.assign(n, nullptr);
+        bytes.assign(n, 0);
+    } catch (const std::bad_alloc &) {
+        g_last_error = std::string(who) + ": out of host memory";
+        return FLACGPU_ERR_UNSUPPORTED;
+    }
+    if (door == 1) {
+        if (int rc = open_device_door(d, data, len, n, stream, who)) {
+            s->dead = rc == FLACGPU_ERR_HIP;
+            return rc;
+        }
+        for (uint32_t i = 0; i < n; i++)
+            if (data[i] && len[i]) {
+                chunk[i] = data[i];
+                bytes[i] = len[i];
+                fresh += len[i];
+            }
+    } else if (door == 0) {
+        // the chunks alone go up: into the pinned staging at 16-byte boundaries, one copy, and the kernel joins them to
+        // the tails that never left the device
+        for (uint32_t i = 0; i < n; i++)
+            if (data[i] && len[i]) {
+                bytes[i] = len[i];
+                fresh += len[i];
+            }
+        const uint64_t up = fresh + 16 * (uint64_t)n;
+        if (fresh) {
+            int rc = d->staging.ensure(up);
+            if (!rc) rc = s->chunks.ensure(up);
+            if (rc) {
+                s->dead = rc == FLACGPU_ERR_HIP;
+                return rc;
+            }
+            uint8_t *stg = d->staging.as<uint8_t>();
+            uint64_t at = 0;
+            for (uint32_t i = 0; i < n; i++) {
+                if (!bytes[i]) continue;
+                memcpy(stg + at, data[i], bytes[i]);
+                chunk[i] = s->chunks.as<const uint8_t>() + at;
+                at = (at + bytes[i] + 15) & ~(uint64_t)15;
+            }
+            const hipError_t e = hipMemcpyAsync(s->chunks.p, stg, at, hipMemcpyHostToDevice, d->st);
+            if (e != hipSuccess) {
+                s->dead = true;
+                g_last_error = std::string(who) + ": " + hipGetErrorString(e);
+                return FLACGPU_ERR_HIP;
+            }
+        }
+    }
+    const double stage_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_in).count();
+    if (int rc = session_step(s, chunk.data(), bytes.data(), flush, door == 2)) return rc;
+    s->timing.stage_ms = stage_ms;
+    index_frames(d);
+    d->scanned = d->raw = true;
+    s->fed += fresh;
+    s->finished = door == 2;
+    if (n) memcpy(streams, d->res.data(), sizeof(flacgpu_decoded_stream) * n);
+    if (n && raw) memcpy(raw, d->raw_streams.data(), sizeof(flacgpu_raw_stream) * n);
+    *total_frames = d->records.size();
+    *total_elements = d->raw_elements;
+    *total_samples = d->total;
+    return FLACGPU_OK;
+}
+
+int flacgpu_decoder_session_last_feed_timing(flacgpu_decoder_session *s, flacgpu_session_timing *out) {
+    if (!s || !out || s->dead) return FLACGPU_ERR_INVALID_ARG;
+    *out = s->timing;
+    return FLACGPU_OK;
+}
+
+int flacgpu_decoder_session_feed(flacgpu_decoder_session *s, const uint8_t *const *data, const size_t *len,
+                                 const uint8_t *flush, flacgpu_decoded_stream *streams, flacgpu_raw_stream *raw,
+                                 uint64_t *total_frames, uint64_t *total_elements, uint64_t *total_samples) {
+    return session_call(s, 0, data, len, flush, nullptr, streams, raw, total_frames, total_elements, total_samples);
+}
+
+int flacgpu_decoder_session_feed_device(flacgpu_decoder_session *s, const uint8_t *const *d_data, const size_t *len,
+                                        const uint8_t *flush, void *stream, flacgpu_decoded_stream *streams,
+                                        flacgpu_raw_stream *raw, uint64_t *total_frames, uint64_t *total_elements,
+                                        uint64_t *total_samples) {
+    return session_call(s, 1, d_data, len, flush, stream, streams, raw, total_frames, total_elements, total_samples);
+}
+
+int flacgpu_decoder_session_finish(flacgpu_decoder_session *s, flacgpu_decoded_stream *streams, flacgpu_raw_stream *raw,
+                                   uint64_t *total_frames, uint64_t *total_elements, uint64_t *total_samples) {
+    return session_call(s, 2, nullptr, nullptr, nullptr, nullptr, streams, raw, total_frames, total_elements, total_samples);
+}
+
+int flacgpu_session_slots_host(const flacgpu_session_slot_src *srcs, uint32_t n_slots, uint8_t *out, size_t cap,
+                               uint64_t *bytes) {
+    if (!bytes || (n_slots && !srcs)) return FLACGPU_ERR_INVALID_ARG;
+    SlotLayout lay;   // the layout a feed gives its slots
+    std::vector<SessionSrc> tab;
+    try {
+        for (uint32_t i = 0; i < n_slots; i++) {
+            const uint64_t L = srcs[i].tail_len + srcs[i].chunk_len;
+            if (!L) continue;
+            lay.add(i, 0, L, 0, 0);
+            tab.push_back(SessionSrc{reinterpret_cast<uint64_t>(srcs[i].tail), srcs[i].tail_len,
+                                     reinterpret_cast<uint64_t>(srcs[i].chunk), srcs[i].chunk_len});
+        }
+    } catch (const std::bad_alloc &) {
+        return FLACGPU_ERR_UNSUPPORTED;
+    }
+    const uint64_t total = lay.at ? lay.at + 64 : 0;
+    *bytes = total;
+    if (cap < total) {
+        g_last_error = "output buffer too small";
+        return FLACGPU_ERR_BUFFER_TOO_SMALL;
+    }
+    if (!total) return FLACGPU_OK;
+    if (!out) return FLACGPU_ERR_INVALID_ARG;
+    for (uint32_t s = 0; s < tab.size(); s++)   // one "lane" after another, as k_session_slots numbers them
+        for (uint64_t g = lay.slots[s].base / 16; g < lay.end_of(s) / 16; g++) {
+            const uint4 v = session_group(tab[s], g * 16 - lay.slots[s].base);
+            memcpy(out + g * 16, &v, 16);
+        }
+    memset(out + lay.at, 0, 64);   // the look-ahead: the groups from block n_blocks on
     return FLACGPU_OK;
 }
 

@@ -135,3 +135,42 @@ class FlacStreamReader:
             return self.read()
         except EOFError:
             raise StopIteration from None
+
+
+class FlacChunkReader:
+    """One raw frame stream that arrives in pieces cut anywhere -- a socket, a file read piece by piece, the writes of a
+    stream writer --, over gpu.DecoderSession (DESIGN.md 4b "Decoder sessions").  feed(data) returns the frames the bytes
+    so far decide, a list of FrameBuf: without flush a frame comes out once the header behind it has arrived;
+    flush=True says that the bytes so far end on a frame boundary and decides everything.  finish() returns what is
+    left.  No frame may be longer than max_frame_bytes (16 .. 2^22).  A frame that was found but does not decode raises
+    DecodeError; the frames of that feed are lost with it."""
+
+    def __init__(self, device=-1, max_frame_bytes=1 << 20):
+        self._session = gpu.DecoderSession(1, max_frame_bytes, device)
+        self.skipped_bytes = self.gaps = 0   # so far: bytes in no whole frame, and their maximal runs
+
+    def _frames(self, raw):
+        self.skipped_bytes, self.gaps = int(raw[0].skipped_bytes), int(raw[0].gaps)
+        pcm, frames = self._session.decode_frames(out="host")
+        out = []
+        for f in frames:
+            if f["status"]:
+                raise DecodeError("the frame at byte %d %s" % (f["byte_offset"], " and ".join(
+                    w for bit, w in ((1, "does not parse"), (2, "has a wrong CRC-16")) if f["status"] & bit)))
+            at, count = int(f["out_offset"]), int(f["block_size"]) * int(f["channels"])
+            out.append(FrameBuf(pcm[at:at + count], f["sample_rate"], f["channels"], f["bits_per_sample"]))
+        return out
+
+    def feed(self, data, flush=False):
+        return self._frames(self._session.feed([data], flush)[1])
+
+    def finish(self):
+        return self._frames(self._session.finish()[1])
+
+    @property
+    def pending(self):
+        """Bytes fed and not decided yet."""
+        return self._session.pending()[0][0]
+
+    def close(self):
+        self._session.close()

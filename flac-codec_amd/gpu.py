@@ -692,6 +692,137 @@ class Decoder:
         return results
 
 
+class _SessionDecoder(Decoder):
+    """The decoder a DecoderSession owns: every decode call of Decoder works on it; the session destroys it."""
+
+    def __init__(self, handle, device):
+        self._h = handle
+        self.device = device
+        self.device_index = device if device >= 0 else _lib.lib().flacgpu_current_device()
+        self.n_raw_streams = self.n_raw_frames = self.raw_elements = 0
+
+    def close(self):
+        self._h = None
+
+
+class DecoderSession:
+    """flacgpu_decoder_session: `n_streams` raw frame streams fed chunk by chunk, the chunks cut anywhere (DESIGN.md 4b
+    "Decoder sessions").  No frame is longer than `max_frame_bytes` (16 .. 2^22).  The bytes that cannot be judged yet
+    stay in device memory between feeds.  `decoder` is the session's own Decoder: after a feed every decode call works on
+    it, over that feed's frames.  Not thread-safe."""
+
+    def __init__(self, n_streams, max_frame_bytes, device=-1):
+        self._h = None
+        L = _lib.lib()
+        h = C.c_void_p()
+        rc = L.flacgpu_decoder_session_open(device, n_streams, max_frame_bytes, 0, C.byref(h))
+        if rc:
+            raise GpuError(rc, "flacgpu_decoder_session_open")
+        self._h = h
+        self.n_streams = n_streams
+        self.decoder = _SessionDecoder(C.c_void_p(L.flacgpu_decoder_session_decoder(h)), device)
+        self.records = (_lib.DecodedStream * max(n_streams, 1))()   # of the last feed: for decode / decode_as
+        self.frames = np.zeros(0, dtype=FRAME_DTYPE)
+
+    def close(self):
+        if self._h:
+            self.decoder.close()
+            _lib.lib().flacgpu_decoder_session_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def _done(self, rc, who, n_frames, elements):
+        if rc:
+            raise GpuError(rc, who)
+        dec = self.decoder
+        frames = np.zeros(n_frames.value, dtype=FRAME_DTYPE)
+        rc = _lib.lib().flacgpu_decoder_frame_records(dec._h, frames.ctypes.data_as(C.POINTER(_lib.FrameRecord)), frames.size)
+        if rc:
+            raise GpuError(rc, "flacgpu_decoder_frame_records")
+        dec.raw_elements = elements.value
+        dec.n_raw_streams, dec.n_raw_frames = self.n_streams, int(n_frames.value)
+        self.frames = frames
+        return frames, list(self._raw)[:self.n_streams]
+
+    def feed(self, chunks, flush=False, stream=None):
+        """One chunk per stream -- bytes-like, or all of them 1-D torch.uint8 tensors on the session's device (ordered
+        after `stream` as Decoder.scan's are); None or an empty chunk: no bytes for that stream.  flush: True, False or
+        one bool per stream ("what I have fed this stream ends on a frame boundary: decide everything now").  Returns
+        (frames, raw): the records (FRAME_DTYPE) of the frames decided by this feed, byte_offset counting from each
+        stream's first byte, and the streams' _lib.RawStream summaries (frames, skipped_bytes and gaps cumulative)."""
+        chunks = list(chunks)
+        if len(chunks) != self.n_streams:
+            raise ValueError(f"{len(chunks)} chunks for a session of {self.n_streams} streams")
+        if any(is_device_blob(b) for b in chunks if b is not None):
+            import torch
+
+            empty = torch.empty(0, dtype=torch.uint8, device=f"cuda:{self.decoder.device_index}")
+            chunks = [empty if b is None else b for b in chunks]
+        else:
+            chunks = [b"" if b is None else b for b in chunks]
+        ptrs, lens, n, keep, st = self.decoder._sources(chunks, stream)
+        flags = [bool(flush)] * n if isinstance(flush, (bool, int)) else [bool(f) for f in flush]
+        if len(flags) != n:
+            raise ValueError("flush is one bool, or one per stream")
+        fl = (C.c_uint8 * max(n, 1))(*[int(f) for f in flags])
+        self._raw = (_lib.RawStream * max(n, 1))()
+        n_frames, elements, total = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        L = _lib.lib()
+        if st is None:
+            rc = L.flacgpu_decoder_session_feed(self._h, ptrs, lens, fl, self.records, self._raw, C.byref(n_frames),
+                                                C.byref(elements), C.byref(total))
+            who = "flacgpu_decoder_session_feed"
+        else:
+            rc = L.flacgpu_decoder_session_feed_device(self._h, ptrs, lens, fl, C.c_void_p(st), self.records, self._raw,
+                                                       C.byref(n_frames), C.byref(elements), C.byref(total))
+            who = "flacgpu_decoder_session_feed_device"
+        del keep
+        return self._done(rc, who, n_frames, elements)
+
+    def finish(self):
+        """Flushes every stream: (frames, raw) as feed; raw is then every whole stream's summary.  No feed may follow."""
+        self._raw = (_lib.RawStream * max(self.n_streams, 1))()
+        n_frames, elements, total = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        rc = _lib.lib().flacgpu_decoder_session_finish(self._h, self.records, self._raw, C.byref(n_frames),
+                                                       C.byref(elements), C.byref(total))
+        return self._done(rc, "flacgpu_decoder_session_finish", n_frames, elements)
+
+    def pending(self):
+        """(held bytes per stream, bytes fed to the session so far)."""
+        held, fed = (C.c_uint64 * max(self.n_streams, 1))(), C.c_uint64(0)
+        rc = _lib.lib().flacgpu_decoder_session_pending(self._h, held, C.byref(fed))
+        if rc:
+            raise GpuError(rc, "flacgpu_decoder_session_pending")
+        return [int(v) for v in held[:self.n_streams]], int(fed.value)
+
+    def decode_frames(self, out="device"):
+        """The samples of the last feed's frames: (flat int32, frames) as gpu.decode_frames gives them -- frame f is
+        flat[out_offset : out_offset + block_size * channels] as [block_size, channels], status filled."""
+        if out not in ("device", "host"):
+            raise ValueError("out must be 'device' or 'host'")
+        frames = self.frames.copy()
+        return _decode_scanned_frames(self.decoder, frames, out), frames
+
+    def last_feed_timing(self):
+        """flacgpu_decoder_session_last_feed_timing: where the host's time went in the last feed or finish, a dict of
+        milliseconds (stage, to_first_sync, to_second_sync, scan_rest, walk, table_upload)."""
+        t = _lib.SessionTiming()
+        rc = _lib.lib().flacgpu_decoder_session_last_feed_timing(self._h, C.byref(t))
+        if rc:
+            raise GpuError(rc, "flacgpu_decoder_session_last_feed_timing")
+        return {name[:-3]: float(getattr(t, name)) for name, _ in t._fields_}
+
+    def decode_as(self, dtype="float32", layout="padded", pad_to=None, pad_channels=None, out="device", verify_md5=False):
+        """The last feed's frames per stream, as decode_many(raw=True) gives a batch: (flat or [B, C, T] batch, streams).
+        A stream without a frame in this feed, or whose frames of this feed differ, is absent (rc != 0)."""
+        if dtype not in _DTYPES or layout not in ("flat", "padded") or out not in ("device", "host"):
+            raise ValueError("dtype, layout and out as for decode_many")
+        return _decode_many_as(self.decoder, self.records, self.n_streams, out, 0 if verify_md5 else _lib.DECODE_NO_MD5,
+                               dtype, layout, pad_to, pad_channels)
+
+
 def window_frames(frame_sizes, start, length):
     """flacgpu_window_frames: (first, count, skip) of the frames of a stream with these block sizes that samples
     [start, start + length) touch.  Needs no GPU."""
@@ -776,6 +907,24 @@ def _decode_many_as(dec, recs, n, out, flags, dtype, layout, pad_to, pad_channel
     return buf, streams
 
 
+def _decode_scanned_frames(dec, frames, out):
+    """flacgpu_decoder_decode_frames of the raw batch `dec` holds (a scan_frames, or a session's feed) into a new flat
+    int32 buffer -- a torch tensor on the decoder's device for out="device", a numpy array for "host"; `frames` (the
+    batch's records) gets the status filled."""
+    total = dec.raw_elements
+    if out == "device":
+        import torch
+
+        dev = dec.device if dec.device >= 0 else torch.cuda.current_device()
+        flat = torch.empty(total, dtype=torch.int32, device=f"cuda:{dev}")
+        torch.cuda.synchronize(dev)
+        dec.decode_frames(flat.data_ptr() if total else None, total, _lib.DECODE_OUT_DEVICE, frames)
+    else:
+        flat = np.empty(total, dtype=np.int32)
+        dec.decode_frames(flat.ctypes.data if total else None, total, 0, frames)
+    return flat
+
+
 def decode_frames(blobs, device=-1, out="device", decoder=None, speculative=False):
     """Decode every whole frame of a batch of raw frame streams (bare FLAC frames without metadata, as FlacStreamWriter
     writes them, or a byte range cut out of a file) in one GPU call: flacgpu_decoder_scan_frames +
@@ -796,15 +945,7 @@ def decode_frames(blobs, device=-1, out="device", decoder=None, speculative=Fals
     dec = Decoder(device) if own else decoder
     try:
         _, _, raw, frames = dec.scan_frames(blobs, speculative)
-        total = dec.raw_elements
-        if out == "device":
-            dev = dec.device if dec.device >= 0 else torch.cuda.current_device()
-            flat = torch.empty(total, dtype=torch.int32, device=f"cuda:{dev}")
-            torch.cuda.synchronize(dev)
-            dec.decode_frames(flat.data_ptr() if total else None, total, _lib.DECODE_OUT_DEVICE, frames)
-        else:
-            flat = np.empty(total, dtype=np.int32)
-            dec.decode_frames(flat.ctypes.data if total else None, total, 0, frames)
+        flat = _decode_scanned_frames(dec, frames, out)
     finally:
         if own:
             dec.close()

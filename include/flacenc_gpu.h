@@ -821,6 +821,101 @@ int flacgpu_decoder_slot_bytes(flacgpu_decoder *d, uint8_t *out, size_t cap, uin
 int flacgpu_meta_walk_host(const uint8_t *data, size_t len, flacgpu_stream_info *info, uint32_t *min_frame,
                            uint64_t *frames_at);
 
+/* ---- batch decoder: sessions that take raw frame streams chunk by chunk ----------------------------------------------
+ * The receiving end of flacenc_device_stream_writer, of sockets that deliver frame streams in arbitrary pieces, of a file
+ * read piece by piece: n_streams RAW FRAME STREAMS (the rule above, flags 0, never FLACGPU_SCAN_SPECULATIVE), each fed in
+ * chunks cut anywhere.  DESIGN.md 4b "Decoder sessions" states the rule; in short, with W = max_frame_bytes
+ * (16 <= W <= 2^22) and D the concatenation of a stream's chunks so far:
+ *   flush     a feed may mark a stream flushed: "what I have fed ends on a frame boundary; decide everything now, as at
+ *             the end of an input".  Flushes cut D into segments; finish flushes every stream.  Within a segment the
+ *             result is the raw rule applied to the segment's bytes alone, with one clause added: an end e of candidate s
+ *             must have e - s <= W (a following candidate and the segment's end alike).  No frame spans a flush.
+ *   online    with L bytes of the open segment fed, position q is judged once 16 bytes follow it (q <= L - 16).  A
+ *             candidate's link is decided once a judged candidate ends it, or L - 16 >= s + W (it has no end: passed
+ *             over).  The walk stops at the first undecided candidate c at or behind the cursor; the bytes from
+ *             h = max(cursor, min(c, L - 15)) on are HELD (never more than W + 15) and are judged again, in front of the
+ *             next chunk; everything before h is decided and never revisited.  So the frames are a function of the bytes
+ *             and the flush positions, not of where the chunks were cut; without a flush a frame comes out one frame late
+ *             (the header behind it must have arrived).
+ * A session owns a decoder of its own (session_decoder): a scan call on it is refused with FLACGPU_ERR_INVALID_ARG, and
+ * every decode call (decode_frames, frame_records, decode, decode_as, decode_windows, plan_timeline, decode_timeline,
+ * slot_bytes) works on it, over THIS FEED's frames: a feed leaves the handle in the state scan_frames leaves it in for
+ * a batch made of exactly the frames decided in the feed.  The held bytes stay in device memory: a kernel puts them in
+ * front of the next chunk, in the second of two batch buffers that take turns.
+ *   feed         data / len / flush are host arrays of n_streams entries; data[i] is HOST memory.  len[i] == 0 or a NULL
+ *                data[i] means no bytes for stream i in this feed, any number of feeds in a row; flush may be NULL (no
+ *                stream is flushed).  streams, raw and the three totals as scan_frames fills them, with these
+ *                differences: flacgpu_frame_record.byte_offset counts from the stream's first byte since open;
+ *                raw[i].frames, skipped_bytes and gaps are CUMULATIVE since open (a run of skipped bytes that goes on
+ *                from an earlier feed, or across a flush, is one gap, counted when it opens; the held bytes are not
+ *                counted yet), first_frame is the index of the stream's first record of this feed, and uniform and
+ *                streams[i] describe this feed's frames alone (no frame decided in this feed: rc FLACGPU_ERR_INVALID_ARG
+ *                and zero rows).  out_offset lays out this feed's frames.
+ *   feed_device  the same with d_data[i] a device pointer of any alignment on the session's device, checked and ordered
+ *                behind `stream` as scan_frames_device does.  Both doors run the same kernel and build the same slots.
+ *   finish       flushes every stream, without new bytes; afterwards raw[i] is the whole stream's summary.  Every later
+ *                feed or finish is refused.
+ *   pending      held_bytes[i] (n_streams entries, may be NULL): the bytes of stream i not decided yet; *fed_bytes (may
+ *                be NULL): all bytes fed to the session so far.
+ * A refused call (FLACGPU_ERR_INVALID_ARG: a NULL handle or array, max_frame_bytes out of range, flags != 0, a feed after
+ * finish, a device pointer that is not device memory of the session's device) writes nothing and leaves the session as
+ * it was, its decoder included: the frames of the last feed can still be decoded.  So does a feed whose slots (held
+ * bytes + chunks) exceed the scans' 16 GiB limit, and one that cannot allocate its layout (FLACGPU_ERR_UNSUPPORTED).
+ * After a failure further on -- a HIP error, memory running out during the scan or the walk, more than 2^31 - 1 frames
+ * in one feed -- the session refuses every further call.
+ *   session_decoder     the handle belongs to the session and goes with session_close; flacgpu_decoder_destroy does
+ *                       nothing for it.
+ *   last_feed_timing    where the host's time went in the last successful feed or finish (milliseconds, wall clock):
+ *                       stage_ms the argument checks and the chunks' copy into the pinned staging with the upload queued;
+ *                       to_first_sync_ms from the scan's start to the end of its first synchronisation (the candidate
+ *                       count: slots built and scanned on the device); to_second_sync_ms from there to the end of the
+ *                       second (the candidates, links and headers downloaded); scan_rest_ms the rest of the scan call;
+ *                       walk_ms the host walk with its records; table_upload_ms the frame table's upload, which ends
+ *                       with a third synchronisation.  Always taken (six clock reads a feed); no switch.
+ *   session_host_*      the same rule as plain host code, no device needed: the counterpart the device session is tested
+ *                       against.  records (cap entries) receives this feed's records, *total_frames their count; with
+ *                       cap too small FLACGPU_ERR_BUFFER_TOO_SMALL is returned, only *total_frames is written and the
+ *                       session stays as it was.  raw as above; held_bytes (may be NULL) as pending gives it.
+ *   session_slots_host  the per-group rule of the kernel that builds the slots (csrc/kernels/session_slots_rule.h) run
+ *                       over host memory: slot i = srcs[i]'s tail, then its chunk, at a 64-byte boundary (a slot with no byte
+ *                       is left out), zeros up to the next one, 64 bytes of look-ahead, as slot_bytes shows them.
+ *                       *bytes is the size also when cap is short (FLACGPU_ERR_BUFFER_TOO_SMALL, nothing written). */
+typedef struct flacgpu_decoder_session flacgpu_decoder_session;
+typedef struct flacgpu_session_host flacgpu_session_host;
+typedef struct {            /* 48 bytes */
+    double stage_ms, to_first_sync_ms, to_second_sync_ms, scan_rest_ms, walk_ms, table_upload_ms;
+} flacgpu_session_timing;
+typedef struct {
+    const uint8_t *tail;    /* the held bytes, any alignment */
+    uint64_t tail_len;
+    const uint8_t *chunk;   /* the new bytes, any alignment */
+    uint64_t chunk_len;
+} flacgpu_session_slot_src;
+int flacgpu_decoder_session_open(int device, uint32_t n_streams, uint32_t max_frame_bytes, uint32_t flags,
+                                 flacgpu_decoder_session **out);
+int flacgpu_decoder_session_feed(flacgpu_decoder_session *s, const uint8_t *const *data, const size_t *len,
+                                 const uint8_t *flush, flacgpu_decoded_stream *streams, flacgpu_raw_stream *raw,
+                                 uint64_t *total_frames, uint64_t *total_elements, uint64_t *total_samples);
+int flacgpu_decoder_session_feed_device(flacgpu_decoder_session *s, const uint8_t *const *d_data, const size_t *len,
+                                        const uint8_t *flush, void *stream, flacgpu_decoded_stream *streams,
+                                        flacgpu_raw_stream *raw, uint64_t *total_frames, uint64_t *total_elements,
+                                        uint64_t *total_samples);
+int flacgpu_decoder_session_finish(flacgpu_decoder_session *s, flacgpu_decoded_stream *streams, flacgpu_raw_stream *raw,
+                                   uint64_t *total_frames, uint64_t *total_elements, uint64_t *total_samples);
+int flacgpu_decoder_session_pending(flacgpu_decoder_session *s, uint64_t *held_bytes, uint64_t *fed_bytes);
+int flacgpu_decoder_session_last_feed_timing(flacgpu_decoder_session *s, flacgpu_session_timing *out);
+flacgpu_decoder *flacgpu_decoder_session_decoder(flacgpu_decoder_session *s);
+void flacgpu_decoder_session_close(flacgpu_decoder_session *s);
+int flacgpu_session_host_open(uint32_t n_streams, uint32_t max_frame_bytes, flacgpu_session_host **out);
+int flacgpu_session_host_feed(flacgpu_session_host *s, const uint8_t *const *data, const size_t *len, const uint8_t *flush,
+                              flacgpu_frame_record *records, size_t cap, flacgpu_raw_stream *raw, uint64_t *held_bytes,
+                              uint64_t *total_frames);
+int flacgpu_session_host_finish(flacgpu_session_host *s, flacgpu_frame_record *records, size_t cap, flacgpu_raw_stream *raw,
+                                uint64_t *total_frames);
+void flacgpu_session_host_close(flacgpu_session_host *s);
+int flacgpu_session_slots_host(const flacgpu_session_slot_src *srcs, uint32_t n_slots, uint8_t *out, size_t cap,
+                               uint64_t *bytes);
+
 /* ---- batch decoder: raw frame streams on a timeline, lost frames zero-filled -----------------------------------------
  * The kept frames of every stream of a raw scan, each put where its coded number says it belongs; what no frame covers
  * is zero, and so is a frame that does not decode.  The rule (DESIGN.md 4b "Timeline"), for the records r_0 .. r_{m-1}

@@ -26,6 +26,7 @@ over flacgpu_decode_stream and the oracle's CPU decoder on one core; writes prof
     python tools/decode_many_probe.py --timeline --kernels-only
     python tools/decode_many_probe.py --raw|--timeline --label parent --package-root DIR --parent-all-legs   (a parent that
                                              has every leg of the mode: each is then held to the parent's own spread of it)
+    python tools/decode_many_probe.py --session [--out profiles/r22_decoder_session.json] [--reps 15]
 
 --timeline (flacgpu_decoder_decode_timeline): on the clips with the metadata stripped, float32, device output, handle
 warm, the wall time of scan_frames + decode_as (padded; the parent's call for such a batch) and of scan_frames +
@@ -67,6 +68,16 @@ copy of the same byte count (torch's copy_, a hipMemcpyAsync), the yardstick for
 `rocprofv3 --kernel-trace --stats` run of `--device-input --kernels-only` gives (--merge-stats puts it into the
 record as kernel_stats and gather_effective_gbps).  --label this_1 / parent (with --package-root, leg (a) alone) / this_2 in
 that order add the guard on the host door: profiles/r15_device_input.json.
+
+--session (flacgpu_decoder_session_*; DESIGN.md 4b "Decoder sessions"), median and min to max of 15, the shader clock
+read before and after each leg.  Per-feed latency: the device stream writer's workload -- 64 mono 16 kHz streams, one
+frame of 80 ms per stream per feed, the frames written by a device stream writer beforehand -- as feed + decode_frames
+into device memory, with flush=True (each frame out in its own feed) and without (one feed later); the feed and the
+decode are also timed apart, and the feed call's own division (flacgpu_decoder_session_last_feed_timing: staging, the
+scan up to each of its two synchronisations, the host walk, the frame table's upload) is recorded beside them.
+Throughput: the clips, metadata stripped, fed in 1, 4, 16 and 64 pieces (a feed and a decode_frames per piece, then
+finish) against one-shot scan_frames + decode_frames in the same process, identical PCM asserted by SHA-256 over the
+frames in stream order: profiles/r22_decoder_session.json.
 
 --windows (flacgpu_decoder_decode_windows): on a resident scan (scanned once, outside the timed part), device output,
 no MD5, handle warm, the wall time of one round of random crops -- one crop of 5 s (tracks) or 1 s (clips) per stream
@@ -516,6 +527,140 @@ def raw_frames(args):
     print(json.dumps({args.label: rec, "verdict": res.get("verdict")}, indent=1), flush=True)
 
 
+def session(args):
+    """The --session leg (see the module docstring)."""
+    import hashlib
+
+    import torch
+
+    from flac_codec_amd import _lib
+    from flac_codec_amd.encode import BatchEncoder, Options
+    from flac_codec_amd.gpu import Decoder, DecoderSession, decode_frames, scan_stream_host
+
+    sys.path.insert(0, os.path.join(ROOT, "examples"))
+    from stream2flac import one_second
+
+    res = {"tool": "tools/decode_many_probe.py --session", "build_id": _lib.build_id(), "reps": args.reps}
+
+    def leg(times):
+        return dict(_spread(times))
+
+    # ---- per-feed latency: the device stream writer's workload, 64 mono 16 kHz streams, one 80 ms frame per stream
+    n_streams, rate, packet, steps = 64, 16000, 1280, args.reps + 3
+    frames = [[] for _ in range(n_streams)]
+    with BatchEncoder(Options.default()).open_device_stream_writer(n_streams, rate, 16, 1, max_block=packet) as writer:
+        for step in range(steps):
+            chunk = one_second(torch, step, n_streams, 1, packet, rate, "cuda")
+            for k, frame in enumerate(writer.write(chunk, [packet] * n_streams)):
+                frames[k].append(frame)
+    bound = max(len(f) for per in frames for f in per)
+    res["latency"] = {"workload": "64 streams, 16 kHz mono 16-bit, one frame of 80 ms (1280 samples) per stream per feed",
+                      "bytes_per_feed": sum(len(per[0]) for per in frames), "max_frame_bytes": bound,
+                      "stream_writer_write_ms_r21": 0.47, "legs": {}}
+    for name, flush in (("flush", True), ("no_flush", False)):
+        ses = DecoderSession(n_streams, bound, device=0)
+        out = torch.empty(n_streams * packet, dtype=torch.int32, device="cuda:0")
+        torch.cuda.synchronize()
+        feed_t, decode_t, both_t, got, inside = [], [], [], 0, {}
+        sclk_before = None
+        for step in range(steps):
+            if step == 3:
+                sclk_before = _sclk_mhz()   # three feeds warm: buffers grown, code loaded
+            chunks = [per[step] for per in frames]
+            t0 = time.perf_counter()
+            recs, _ = ses.feed(chunks, flush)
+            t1 = time.perf_counter()
+            ses.decoder.decode_frames(out.data_ptr() if len(recs) else None, out.numel() if len(recs) else 0,
+                                      _lib.DECODE_OUT_DEVICE, recs)
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            assert len(recs) == (n_streams if flush or step else 0) and not recs["status"].any()
+            got += len(recs)
+            if step >= 3:
+                for key, v in ses.last_feed_timing().items():   # the C call's own clock reads, milliseconds
+                    inside.setdefault(key, []).append(v * 1e-3)
+                feed_t.append(t1 - t0)
+                decode_t.append(t2 - t1)
+                both_t.append(t2 - t0)
+        res["latency"]["legs"][name] = {"feed_plus_decode_frames": leg(both_t), "feed": leg(feed_t),
+                                        "decode_frames": leg(decode_t),
+                                        "inside_the_feed_call": {key: leg(v) for key, v in inside.items()},
+                                        "sclk_mhz_before": sclk_before,
+                                        "sclk_mhz_after": _sclk_mhz(), "frames": got}
+        ses.close()
+
+    # ---- throughput: the clips, metadata stripped, whole and in pieces
+    blobs = make_blobs("clips")
+    bare = [b[int(scan_stream_host(b)[1][0]):] for b in blobs]
+    del blobs
+    dec = Decoder(0)
+
+    def one_shot():
+        return decode_frames(bare, out="device", decoder=dec)
+
+    flat, recs, _ = one_shot()
+    bound = int(recs["bytes"].max())
+    order = np.lexsort((recs["byte_offset"], recs["stream"]))
+    host = flat.cpu().numpy()
+    sha = hashlib.sha256()
+    for r in recs[order]:
+        sha.update(host[int(r["out_offset"]):int(r["out_offset"]) + int(r["block_size"]) * int(r["channels"])].tobytes())
+    res["throughput"] = {"workload": "clips: 1024 x 10 s, 16 kHz mono 16-bit, metadata stripped",
+                         "bytes": sum(len(b) for b in bare), "frames": int(len(recs)), "max_frame_bytes": bound,
+                         "pcm_sha256": sha.hexdigest(), "legs": {}}
+    total = int(flat.numel())
+    del flat, host
+    sclk = _sclk_mhz()
+    times = []
+    for _ in range(args.reps):
+        t0 = time.perf_counter()
+        one_shot()
+        torch.cuda.synchronize()
+        times.append(time.perf_counter() - t0)
+    res["throughput"]["legs"]["one_shot_scan_frames_decode_frames"] = dict(leg(times), sclk_mhz_before=sclk,
+                                                                           sclk_mhz_after=_sclk_mhz())
+    dec.close()
+    out = torch.empty(total, dtype=torch.int32, device="cuda:0")
+    for pieces in (1, 4, 16, 64):
+        cut = [[b[len(b) * p // pieces:len(b) * (p + 1) // pieces] for p in range(pieces)] for b in bare]
+
+        def run(check):
+            ses = DecoderSession(len(bare), bound, device=0)
+            parts = []
+            for p in range(pieces + 1):
+                recs, _ = ses.finish() if p == pieces else ses.feed([c[p] for c in cut])
+                n = ses.decoder.raw_elements
+                ses.decoder.decode_frames(out.data_ptr() if n else None, n, _lib.DECODE_OUT_DEVICE, recs)
+                if check:
+                    parts.append((recs, out[:n].cpu().numpy()))
+            torch.cuda.synchronize()
+            ses.close()
+            return parts
+
+        parts = run(True)   # warm, and the PCM: every frame once, in stream order
+        keys = np.concatenate([np.stack([r["stream"].astype(np.int64), r["byte_offset"].astype(np.int64), np.full(len(r), i, np.int64),
+                                         np.arange(len(r), dtype=np.int64)], 1)
+                               for i, (r, _) in enumerate(parts)])
+        sha = hashlib.sha256()
+        for _, _, i, k in keys[np.lexsort((keys[:, 1], keys[:, 0]))]:
+            r = parts[i][0][k]
+            assert not r["status"]
+            sha.update(parts[i][1][int(r["out_offset"]):int(r["out_offset"]) + int(r["block_size"]) * int(r["channels"])].tobytes())
+        assert sha.hexdigest() == res["throughput"]["pcm_sha256"] and len(keys) == res["throughput"]["frames"]
+        del parts
+        sclk = _sclk_mhz()
+        times = []
+        for _ in range(args.reps):
+            t0 = time.perf_counter()
+            run(False)
+            times.append(time.perf_counter() - t0)
+        res["throughput"]["legs"][f"session_{pieces}_pieces"] = dict(leg(times), sclk_mhz_before=sclk,
+                                                                     sclk_mhz_after=_sclk_mhz(), identical_pcm=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res, indent=1), flush=True)
+
+
 def timeline(args):
     """The --timeline leg (see the module docstring)."""
     import hashlib
@@ -864,6 +1009,7 @@ def main():
     ap.add_argument("--speculative", action="store_true",
                     help="with --raw: add the FLACGPU_SCAN_SPECULATIVE leg, profiles/r14_speculative.json")
     ap.add_argument("--timeline", action="store_true", help="the timeline leg: profiles/r16_timeline.json")
+    ap.add_argument("--session", action="store_true", help="the decoder session leg: profiles/r22_decoder_session.json")
     ap.add_argument("--shrink", type=int, default=1, help="--s24: divide the clip count")
     ap.add_argument("--label", default="this", help="--formats: the run's name in the file (parent: the default int32 "
                     "leg only; any other name: every leg)")
@@ -877,10 +1023,11 @@ def main():
     ap.add_argument("--kernels-only", action="store_true", help="one warm decode per workload (for rocprofv3)")
     args = ap.parse_args()
     if args.reps is None:
-        args.reps = 15 if args.device_input else 3
+        args.reps = 15 if args.device_input or args.session else 3
     if not args.out:
         args.out = os.path.join(ROOT, "profiles", "r15_device_input.json" if args.device_input else
                                 "r16_timeline.json" if args.timeline else
+                                "r22_decoder_session.json" if args.session else
                                 "r14_speculative.json" if args.raw and args.speculative else
                                 "r13_raw_frames.json" if args.raw else
                                 "r10_decode_windows.json" if args.windows else
@@ -899,6 +1046,8 @@ def main():
         return device_input(args)
     if args.timeline:
         return timeline(args)
+    if args.session:
+        return session(args)
     if args.raw:
         return raw_frames(args)
     if args.formats and args.s24:
