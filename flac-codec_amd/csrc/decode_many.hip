@@ -445,19 +445,7 @@ void keep_raw_frame(flacgpu_decoder *d, uint32_t i, uint64_t at, uint64_t end, u
     h.acode = head[3] >> 4;
     h.bps_code = (head[3] >> 1) & 7;
     flacenc::host_frame_fields(head, h);
-    flacgpu_frame_record f{};
-    f.byte_offset = byte_offset;
-    f.number = h.number;
-    f.out_offset = tot.elements;
-    f.stream = i;
-    f.bytes = (uint32_t)(end - at);
-    f.block_size = h.n;
-    f.sample_rate = h.sample_rate;
-    f.channels = h.channels;
-    f.bits_per_sample = h.bits_per_sample;
-    f.assignment = h.acode;
-    f.blocking = h.blocking;
-    f.reserved = own ? FLACGPU_FRAME_SPECULATIVE : 0u;
+    const flacgpu_frame_record f = flacenc::raw_frame_record(h, i, byte_offset, end - at, tot.elements, own);
     ManyFrame m{};
     m.start = at;
     m.end = end;
@@ -502,6 +490,35 @@ void join_regular(flacgpu_decoder *d, uint32_t i, int32_t s, size_t first, size_
         r.info.decoded_samples += f.block_size;
     }
     tot.total += r.info.decoded_samples * r.info.channels;
+}
+
+// The raw walk (host/raw_walk.h) over slot s's candidates, their ends answered from the tables the device left: the
+// link (k_link_raw, or a session's k_link_session with its LINK_HOLD), and for a candidate without one its own extent
+// where the scan asked for extents (c.spec).  Positions are the batch buffer's.
+template <class Keep>
+flacenc::RawWalk walk_slot(const Candidates &c, const ScanSlot &sl, uint32_t s, Keep keep, flacenc::SessionCount *count = nullptr) {
+    const uint64_t slot_end = sl.base + sl.len;
+    return flacenc::raw_walk(
+        c.pos.data(), c.cand0[s], c.end_of(s), sl.base, slot_end,
+        [&](size_t k, uint64_t at) {
+            const int32_t link = c.link[k];
+            if (link == LINK_HOLD) return flacenc::RawEnd{flacenc::kRawHold, false};
+            if (link == LINK_NONE) return c.spec.empty() || !c.spec[k] ? flacenc::RawEnd{} : flacenc::RawEnd{at + c.spec[k], true};
+            return flacenc::RawEnd{link == LINK_END ? slot_end : c.pos[link], false};
+        },
+        keep, count);
+}
+
+// The end of a raw scan and of a session's feed (`who`): the frame kernels index frames with 31 bits; the sizes of
+// decode_frames' layout; finish_scan.
+int finish_raw_scan(flacgpu_decoder *d, SlotLayout &lay, const RawTotals &tot, const char *who) {
+    if (d->raw_tab.size() > 0x7FFFFFFFull) {
+        g_last_error = std::string(who) + ": more than 2^31 - 1 frames";
+        return FLACGPU_ERR_UNSUPPORTED;
+    }
+    d->raw_elements = tot.elements;
+    d->raw_scratch = tot.raw_scratch;
+    return finish_scan(d, lay, tot.total, tot.scratch_total);
 }
 
 // flacgpu_decoder_scan_frames behind its argument checks: a slot is a whole input, the device finds the candidates and
@@ -550,19 +567,10 @@ int scan_raw_impl(flacgpu_decoder *d, const ScanInput &in, const size_t *len, ui
             const int32_t s = d->slot_of[i];
             if (s >= 0) {
                 const ScanSlot &sl = lay.slots[s];
-                const uint32_t c_end = c.end_of((uint32_t)s);
-                uint64_t cursor = sl.base;
-                for (uint32_t k = c.cand0[s]; k < c_end; k++) {
-                    const uint64_t at = c.pos[k];
-                    const uint32_t cinfo = c.info[k];
-                    const int32_t link = c.link[k];
-                    const bool own = link == LINK_NONE && spec && c.spec[k];
-                    if (at < cursor || (link == LINK_NONE && !own)) continue;
-                    const uint64_t end = own ? at + c.spec[k] : link == LINK_END ? sl.base + sl.len : c.pos[link];
-                    const uint8_t *head = in.device ? c.heads.data() + kHeadBytes * (size_t)k : stg + at;
-                    keep_raw_frame(d, i, at, end, lay.end_of((uint32_t)s), at - sl.base, cinfo, head, own, tot);
-                    cursor = end;
-                }
+                walk_slot(c, sl, (uint32_t)s, [&](size_t k, uint64_t at, uint64_t end, bool own) {
+                    const uint8_t *head = in.device ? c.heads.data() + kHeadBytes * k : stg + at;
+                    keep_raw_frame(d, i, at, end, lay.end_of((uint32_t)s), at - sl.base, c.info[k], head, own, tot);
+                });
             }
             const size_t count = d->records.size() - first;
             flacenc::summarise_raw_frames(d->records.data() + first, count, len[i], sum);
@@ -573,13 +581,7 @@ int scan_raw_impl(flacgpu_decoder *d, const ScanInput &in, const size_t *len, ui
         g_last_error = "flacgpu_decoder_scan_frames: out of host memory";
         return FLACGPU_ERR_UNSUPPORTED;
     }
-    if (all.size() > 0x7FFFFFFFull) {
-        g_last_error = "flacgpu_decoder_scan_frames: more than 2^31 - 1 frames";
-        return FLACGPU_ERR_UNSUPPORTED;
-    }
-    d->raw_elements = tot.elements;
-    d->raw_scratch = tot.raw_scratch;
-    return finish_scan(d, lay, tot.total, tot.scratch_total);
+    return finish_raw_scan(d, lay, tot, "flacgpu_decoder_scan_frames");
 }
 }  // namespace
 
@@ -676,58 +678,29 @@ int session_step(flacgpu_decoder_session *ses, const uint8_t *const *chunk, cons
             const int32_t s = d->slot_of[i];
             if (s >= 0) {
                 const ScanSlot &sl = lay.slots[s];
-                const uint64_t slot_end = sl.base + sl.len;
-                const uint32_t c_end = c.end_of((uint32_t)s);
-                uint64_t cursor = sl.base, hold = slot_end;
-                for (uint32_t k = c.cand0[s]; k < c_end; k++) {
-                    const uint64_t at = c.pos[k];
-                    const int32_t link = c.link[k];
-                    if (at < cursor || link == LINK_NONE) continue;
-                    if (link == LINK_HOLD) {
-                        hold = at;
-                        break;
-                    }
-                    const uint64_t end = link == LINK_END ? slot_end : c.pos[link];
-                    st.count.skip(at - cursor);
-                    st.count.keep();
-                    keep_raw_frame(d, i, at, end, lay.end_of((uint32_t)s), st.base + (at - sl.base), c.info[k],
-                                   c.heads.data() + kHeadBytes * (size_t)k, false, tot);
-                    cursor = end;
-                }
-                // nothing from L - 15 on is judged in an open segment; a flushed one is decided to its end
-                const uint64_t at_most = sl.base + (sl.len >= flacenc::kSessionHead ? sl.len - flacenc::kSessionHead + 1 : 0);
-                const uint64_t h = info[s].final ? slot_end : std::max(cursor, std::min(hold, at_most));
-                st.count.skip(h - cursor);
+                const flacenc::RawWalk w = walk_slot(
+                    c, sl, (uint32_t)s,
+                    [&](size_t k, uint64_t at, uint64_t end, bool) {
+                        keep_raw_frame(d, i, at, end, lay.end_of((uint32_t)s), st.base + (at - sl.base), c.info[k],
+                                       c.heads.data() + kHeadBytes * k, false, tot);
+                    },
+                    &st.count);
+                const uint64_t h = flacenc::session_hold(w, sl.base, sl.len, info[s].final, st.count);
                 st.base += h - sl.base;
-                st.held = slot_end - h;
+                st.held = sl.base + sl.len - h;
                 st.at = h;
             }
             const size_t count = d->records.size() - first;
             flacgpu_raw_stream &sum = d->raw_streams[i];
-            sum.first_frame = first;
-            sum.skipped_bytes = st.count.skipped;
-            sum.frames = st.count.frames;
-            sum.gaps = st.count.gaps;
-            sum.uniform = count > 0;
-            for (size_t k = first + 1; k < first + count; k++)
-                if (d->records[k].sample_rate != d->records[first].sample_rate ||
-                    d->records[k].channels != d->records[first].channels ||
-                    d->records[k].bits_per_sample != d->records[first].bits_per_sample)
-                    sum.uniform = 0;
+            sum = flacenc::session_summary(st.count, first, d->records.data() + first, count);
             join_regular(d, i, s, first, count, sum.uniform, tot);
         }
     } catch (const std::bad_alloc &) {
         g_last_error = "flacgpu_decoder_session_feed: out of host memory";
         return FLACGPU_ERR_UNSUPPORTED;
     }
-    if (all.size() > 0x7FFFFFFFull) {   // scan_raw_impl's refusal: the frame kernels index frames with 31 bits
-        g_last_error = "flacgpu_decoder_session_feed: more than 2^31 - 1 frames";
-        return FLACGPU_ERR_UNSUPPORTED;
-    }
-    d->raw_elements = tot.elements;
-    d->raw_scratch = tot.raw_scratch;
     const auto t2 = std::chrono::steady_clock::now();
-    if (int rc = finish_scan(d, lay, tot.total, tot.scratch_total)) return rc;
+    if (int rc = finish_raw_scan(d, lay, tot, "flacgpu_decoder_session_feed")) return rc;
     const auto t3 = std::chrono::steady_clock::now();
     const auto ms = [](std::chrono::steady_clock::duration v) { return std::chrono::duration<double, std::milli>(v).count(); };
     ses->timing.to_first_sync_ms = d->scan_sync_s[0] * 1e3;
@@ -1423,17 +1396,25 @@ static int scan_call(flacgpu_decoder *d, const ScanInput &in, const size_t *len,
     return FLACGPU_OK;
 }
 
+// What a raw scan and a session's feed hand back once they are through: the batch is indexed and scanned, and the
+// caller gets its streams, their summaries (raw may be null) and the batch's sizes.
+static void publish_raw_scan(flacgpu_decoder *d, flacgpu_decoded_stream *streams, flacgpu_raw_stream *raw,
+                             uint64_t *total_frames, uint64_t *total_elements, uint64_t *total_samples) {
+    const size_t n = d->res.size();
+    index_frames(d);
+    d->scanned = d->raw = true;
+    if (n) memcpy(streams, d->res.data(), sizeof(flacgpu_decoded_stream) * n);
+    if (n && raw) memcpy(raw, d->raw_streams.data(), sizeof(flacgpu_raw_stream) * n);
+    *total_frames = d->records.size();
+    *total_elements = d->raw_elements;
+    *total_samples = d->total;
+}
+
 static int scan_frames_call(flacgpu_decoder *d, const ScanInput &in, const size_t *len, uint32_t n_streams, uint32_t flags,
                             flacgpu_decoded_stream *streams, flacgpu_raw_stream *raw, uint64_t *total_frames,
                             uint64_t *total_elements, uint64_t *total_samples) {
     if (int rc = scan_raw_impl(d, in, len, n_streams, flags)) return rc;
-    index_frames(d);
-    d->scanned = d->raw = true;
-    if (n_streams) memcpy(streams, d->res.data(), sizeof(flacgpu_decoded_stream) * n_streams);
-    if (n_streams && raw) memcpy(raw, d->raw_streams.data(), sizeof(flacgpu_raw_stream) * n_streams);
-    *total_frames = d->records.size();
-    *total_elements = d->raw_elements;
-    *total_samples = d->total;
+    publish_raw_scan(d, streams, raw, total_frames, total_elements, total_samples);
     return FLACGPU_OK;
 }
 
@@ -1678,15 +1659,9 @@ static int session_call(flacgpu_decoder_session *s, int door, const uint8_t *con
     const double stage_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_in).count();
     if (int rc = session_step(s, chunk.data(), bytes.data(), flush, door == 2)) return rc;
     s->timing.stage_ms = stage_ms;
-    index_frames(d);
-    d->scanned = d->raw = true;
     s->fed += fresh;
     s->finished = door == 2;
-    if (n) memcpy(streams, d->res.data(), sizeof(flacgpu_decoded_stream) * n);
-    if (n && raw) memcpy(raw, d->raw_streams.data(), sizeof(flacgpu_raw_stream) * n);
-    *total_frames = d->records.size();
-    *total_elements = d->raw_elements;
-    *total_samples = d->total;
+    publish_raw_scan(d, streams, raw, total_frames, total_elements, total_samples);
     return FLACGPU_OK;
 }
 

@@ -5,6 +5,7 @@
 
 #include "../kernels/frame_extent.h"
 #include "checksums.h"
+#include "raw_walk.h"
 
 namespace flacenc {
 namespace {
@@ -149,15 +150,12 @@ void host_frame_fields(const uint8_t *d, HostFrameInfo &h) {
 
 void summarise_raw_frames(const flacgpu_frame_record *frames, size_t n, size_t len, flacgpu_raw_stream &summary) {
     summary.frames = (uint32_t)n;
-    summary.uniform = n > 0;
+    summary.uniform = raw_frames_uniform(frames, n);
     summary.skipped_bytes = 0;
     summary.gaps = 0;
     uint64_t at = 0;
     for (size_t i = 0; i < n; i++) {
         const flacgpu_frame_record &f = frames[i];
-        if (f.sample_rate != frames[0].sample_rate || f.channels != frames[0].channels ||
-            f.bits_per_sample != frames[0].bits_per_sample)
-            summary.uniform = 0;
         if (f.byte_offset > at) {
             summary.skipped_bytes += f.byte_offset - at;
             summary.gaps++;
@@ -183,60 +181,24 @@ size_t raw_frame_extent(const uint8_t *data, size_t len, const HostFrameInfo &h)
 
 void scan_raw_frames(const uint8_t *data, size_t len, uint32_t flags, std::vector<flacgpu_frame_record> &frames,
                      flacgpu_raw_stream &summary) {
-    const uint16_t *const T = crc16_table();
-    // the candidates: a header that parses, with a sample rate and a sample size of its own
     std::vector<size_t> cand;
     std::vector<HostFrameInfo> head;
-    for (size_t q = 0; q < len; q++) {
-        HostFrameInfo h;
-        if (data[q] == 0xFF && host_parse_frame_info(data + q, len - q, h) && h.rcode != 0 && h.bps_code != 0) {
-            cand.push_back(q);
-            head.push_back(h);
-        }
-    }
+    raw_candidates(data, len, len, cand, head);
     frames.clear();
     uint64_t out = 0;
-    size_t cursor = 0;
-    for (size_t i = 0; i < cand.size(); i++) {
-        const size_t s = cand[i];
-        if (s < cursor) continue;
-        const HostFrameInfo &h = head[i];
-        const size_t min_end = s + h.header_bytes + 2 + h.channels;
-        // with init 0 and no final XOR, bytes [q-2, q) are the CRC-16 of [s, q-2) exactly when the CRC-16 of [s, q) is 0
-        uint16_t crc = 0;
-        size_t at = s, end = 0;
-        for (size_t j = i + 1; j < cand.size() && !end; j++) {
-            for (; at < cand[j]; at++) crc = crc16_step(T, crc, data[at]);
-            if (cand[j] >= min_end && crc == 0) end = cand[j];
-        }
-        if (!end) {   // the frame ends with the input
-            for (; at < len; at++) crc = crc16_step(T, crc, data[at]);
-            if (len - s >= 2 && crc == 0) end = len;
-        }
-        uint32_t own = 0;
-        if (!end && (flags & FLACGPU_SCAN_SPECULATIVE)) {   // no header ends it: its own extent
-            if (const size_t e = raw_frame_extent(data + s, len - s, h)) {
-                end = s + e;
-                own = FLACGPU_FRAME_SPECULATIVE;
-            }
-        }
-        if (!end) continue;   // no end: passed over, the walk goes on behind it
-        flacgpu_frame_record f{};
-        f.byte_offset = s;
-        f.number = h.number;
-        f.out_offset = out;
-        f.bytes = (uint32_t)(end - s);
-        f.block_size = h.n;
-        f.sample_rate = h.sample_rate;
-        f.channels = h.channels;
-        f.bits_per_sample = h.bits_per_sample;
-        f.assignment = h.acode;
-        f.blocking = h.blocking;
-        f.reserved = own;
-        frames.push_back(f);
-        out += (uint64_t)h.n * h.channels;
-        cursor = end;
-    }
+    raw_walk(
+        cand.data(), 0, cand.size(), 0, len,
+        [&](size_t i, uint64_t s) {   // a later candidate or the input's end; else (speculative) the frame's own extent
+            if (const size_t end = raw_end_by_crc(data, len, cand, i, head[i], SIZE_MAX, true)) return RawEnd{end, false};
+            if (flags & FLACGPU_SCAN_SPECULATIVE)
+                if (const size_t e = raw_frame_extent(data + s, len - s, head[i])) return RawEnd{s + e, true};
+            return RawEnd{};   // no end: passed over, the walk goes on behind it
+        },
+        [&](size_t i, uint64_t s, uint64_t end, bool own) {
+            const flacgpu_frame_record f = raw_frame_record(head[i], 0, s, end - s, out, own);
+            frames.push_back(f);
+            out += (uint64_t)head[i].n * head[i].channels;
+        });
     summary = flacgpu_raw_stream{};
     summarise_raw_frames(frames.data(), frames.size(), len, summary);
 }
@@ -251,10 +213,8 @@ const char *timeline_of_records(const flacgpu_frame_record *records, size_t n, f
     };
     if (!n) return refuse(FLACGPU_ERR_INVALID_ARG, "no whole frame");
     const flacgpu_frame_record &r0 = records[0];
-    for (size_t k = 1; k < n; k++)
-        if (records[k].sample_rate != r0.sample_rate || records[k].channels != r0.channels ||
-            records[k].bits_per_sample != r0.bits_per_sample)
-            return refuse(FLACGPU_ERR_UNSUPPORTED, "frames differ in sample rate, channels or sample size");
+    if (!raw_frames_uniform(records, n))
+        return refuse(FLACGPU_ERR_UNSUPPORTED, "frames differ in sample rate, channels or sample size");
     for (size_t k = 1; k < n; k++)
         if (records[k].blocking != r0.blocking)
             return refuse(FLACGPU_ERR_UNSUPPORTED, "frames differ in blocking strategy");

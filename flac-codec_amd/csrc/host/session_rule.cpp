@@ -3,66 +3,30 @@
 #include <algorithm>
 #include <new>
 
-#include "checksums.h"
+#include "raw_walk.h"
 
 namespace flacenc {
 size_t session_decide(const uint8_t *d, size_t L, bool final, uint32_t W, uint64_t base, uint32_t stream,
                       SessionCount &count, std::vector<flacgpu_frame_record> &out, uint64_t *elements) {
-    const uint16_t *const T = crc16_table();
     // the positions judged so far: all of a flushed stream, else those with kSessionHead bytes behind them
     const size_t judged = final ? L : (L >= kSessionHead ? L - kSessionHead + 1 : 0);
     std::vector<size_t> cand;
     std::vector<HostFrameInfo> head;
-    for (size_t q = 0; q < judged; q++) {
-        HostFrameInfo h;
-        if (d[q] == 0xFF && host_parse_frame_info(d + q, L - q, h) && h.rcode != 0 && h.bps_code != 0) {
-            cand.push_back(q);
-            head.push_back(h);
-        }
-    }
-    size_t cursor = 0, hold = L;   // hold: the first candidate whose link is not decided
-    for (size_t i = 0; i < cand.size(); i++) {
-        const size_t s = cand[i];
-        if (s < cursor) continue;
-        const HostFrameInfo &h = head[i];
-        const size_t min_end = s + h.header_bytes + 2 + h.channels;
-        uint16_t crc = 0;   // of [s, at): 0 at an end (flac_stream.cpp scan_raw_frames)
-        size_t at = s, end = 0;
-        for (size_t j = i + 1; j < cand.size() && !end && cand[j] - s <= W; j++) {
-            for (; at < cand[j]; at++) crc = crc16_step(T, crc, d[at]);
-            if (cand[j] >= min_end && crc == 0) end = cand[j];
-        }
-        if (!end && final && L - s >= 2 && L - s <= W) {   // the frame ends with the flushed input
-            for (; at < L; at++) crc = crc16_step(T, crc, d[at]);
-            if (crc == 0) end = L;
-        }
-        if (!end) {
-            if (final || L - s >= (size_t)W + kSessionHead) continue;   // no end within W: passed over
-            hold = s;   // an end may still arrive
-            break;
-        }
-        count.skip(s - cursor);
-        count.keep();
-        flacgpu_frame_record f{};
-        f.byte_offset = base + s;
-        f.number = h.number;
-        f.out_offset = *elements;
-        f.stream = stream;
-        f.bytes = (uint32_t)(end - s);
-        f.block_size = h.n;
-        f.sample_rate = h.sample_rate;
-        f.channels = h.channels;
-        f.bits_per_sample = h.bits_per_sample;
-        f.assignment = h.acode;
-        f.blocking = h.blocking;
-        out.push_back(f);
-        *elements += (uint64_t)h.n * h.channels;
-        cursor = end;
-    }
-    const size_t at_most = L >= kSessionHead ? L - kSessionHead + 1 : 0;   // L - 15: nothing behind it is judged
-    const size_t hpos = final ? L : std::max(cursor, std::min(hold, at_most));
-    count.skip(hpos - cursor);
-    return hpos;
+    raw_candidates(d, L, judged, cand, head);
+    const RawWalk w = raw_walk(
+        cand.data(), 0, cand.size(), 0, L,
+        [&](size_t i, uint64_t s) {
+            if (const size_t end = raw_end_by_crc(d, L, cand, i, head[i], W, final)) return RawEnd{end, false};
+            // no end within W: passed over; in an open stream with less than that behind it, an end may still arrive
+            return RawEnd{final || L - s >= (size_t)W + kSessionHead ? kRawNone : kRawHold, false};
+        },
+        [&](size_t i, uint64_t s, uint64_t end, bool) {
+            const flacgpu_frame_record f = raw_frame_record(head[i], stream, base + s, end - s, *elements, false);
+            out.push_back(f);
+            *elements += (uint64_t)head[i].n * head[i].channels;
+        },
+        &count);
+    return session_hold(w, 0, L, final, count);
 }
 }  // namespace flacenc
 
@@ -115,16 +79,7 @@ static int session_host_step(flacgpu_session_host *s, const uint8_t *const *data
                                                      &elements);
             next[i].base = cur.base + h;
             next[i].held.assign(buf.begin() + h, buf.end());
-            flacgpu_raw_stream &sum = sums[i];
-            sum.first_frame = first;
-            sum.skipped_bytes = next[i].count.skipped;
-            sum.frames = next[i].count.frames;
-            sum.gaps = next[i].count.gaps;
-            sum.uniform = recs.size() > first;
-            for (size_t k = first; k < recs.size(); k++)
-                if (recs[k].sample_rate != recs[first].sample_rate || recs[k].channels != recs[first].channels ||
-                    recs[k].bits_per_sample != recs[first].bits_per_sample)
-                    sum.uniform = 0;
+            sums[i] = flacenc::session_summary(next[i].count, first, recs.data() + first, recs.size() - first);
         }
         *total_frames = recs.size();
         if (recs.size() > cap || (!recs.empty() && !records)) return FLACGPU_ERR_BUFFER_TOO_SMALL;

@@ -1,7 +1,7 @@
 // session_rule.h -- the rule of a decoder session (DESIGN.md 4b "Decoder sessions"): raw frame streams fed chunk by
 // chunk, as plain host code.  Plain C++: no HIP call, no global state; every byte read is bounded by the length given.
 // flacgpu_session_host_* (session_rule.cpp) is this rule over host chunks; the device session (decode_many.hip) finds
-// the links on the device and shares the counts below.
+// the links on the device and runs the same walk with the same counts (raw_walk.h).
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -9,28 +9,10 @@
 
 #include "flac_stream.h"
 #include "flacenc_gpu.h"
+#include "raw_walk.h"
 
 namespace flacenc {
-constexpr uint32_t kSessionHead = 16;              // a position is judged once this many bytes follow it
 constexpr uint32_t kSessionMinW = 16, kSessionMaxW = 1u << 22;   // the bounds of max_frame_bytes
-
-// One stream's cumulative counts.  A gap is a maximal run of bytes in no kept frame over the whole byte string: a run
-// that goes on from the feed before is not counted again.
-struct SessionCount {
-    uint64_t skipped = 0;
-    uint32_t frames = 0, gaps = 0;
-    bool in_gap = false;   // the last decided byte lies in no kept frame
-    void skip(uint64_t n) {
-        if (!n) return;
-        skipped += n;
-        if (!in_gap) gaps++;
-        in_gap = true;
-    }
-    void keep() {
-        frames++;
-        in_gap = false;
-    }
-};
 
 // One feed of one stream: d[0, L) is the held tail followed by the new chunk, `base` the offset of d[0] from the
 // stream's first byte.  The frames decided now are appended to `out` (stream `stream`, out_offset from *elements on,
