@@ -183,6 +183,11 @@ class SessionTiming(C.Structure):
                                                 "walk_ms", "table_upload_ms")]
 
 
+class MetaFeedState(C.Structure):
+    """flacgpu_meta_feed: the resumable metadata walk's state, 104 bytes whatever the chain's length."""
+    _fields_ = [("words", C.c_uint64 * 13)]
+
+
 class SessionSlotSrc(C.Structure):
     """flacgpu_session_slot_src: one slot's held tail and new chunk, for flacgpu_session_slots_host."""
     _fields_ = [("tail", C.c_void_p), ("tail_len", C.c_uint64), ("chunk", C.c_void_p), ("chunk_len", C.c_uint64)]
@@ -345,6 +350,14 @@ def _load():
     L.flacgpu_session_host_close.argtypes = [vp]
     L.flacgpu_session_host_close.restype = None
     L.flacgpu_session_slots_host.argtypes = [C.POINTER(SessionSlotSrc), C.c_uint32, vp, C.c_size_t, q]
+    L.flacgpu_decoder_session_open_container.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(vp)]
+    L.flacgpu_decoder_session_verdict.argtypes = [vp, C.POINTER(DecodedStream)]
+    L.flacgpu_session_host_open_container.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(vp)]
+    L.flacgpu_meta_feed_init_host.argtypes = [C.POINTER(MetaFeedState)]
+    L.flacgpu_meta_feed_init_host.restype = None
+    L.flacgpu_meta_feed_host.argtypes = [C.POINTER(MetaFeedState), C.c_char_p, C.c_size_t, szp]
+    L.flacgpu_meta_feed_result_host.argtypes = [C.POINTER(MetaFeedState), C.c_uint64, C.POINTER(StreamInfo),
+                                                C.POINTER(C.c_uint32), q]
     L.flacgpu_decoder_frame_records.argtypes = [vp, C.POINTER(FrameRecord), C.c_size_t]
     L.flacgpu_decoder_decode_frames.argtypes = [vp, vp, C.c_size_t, C.c_uint32, C.POINTER(FrameRecord), C.c_size_t]
     L.flacgpu_timeline_host.argtypes = [C.POINTER(FrameRecord), C.c_size_t, C.POINTER(TimelineFrame), C.c_size_t,

@@ -7,6 +7,7 @@
 #include "kernels/sample_types.h"
 #include "kernels/frame_extent.h"
 #include "kernels/meta_walk.h"
+#include "kernels/meta_feed_rule.h"
 #include "kernels/byte_shift.h"
 #include "kernels/session_slots_rule.h"
 #include "flac_stream.h"
@@ -107,6 +108,8 @@ struct flacgpu_decoder {
     DevBuf raw_frames;
     uint64_t raw_elements = 0, raw_scratch = 0;
     bool session = false;   // owned by a flacgpu_decoder_session: the scan calls and destroy are refused
+    // a container session's decoder: decode / decode_as hash into the session's MD5 chains (decode_impl), not k_md5_many
+    struct flacgpu_decoder_session *container = nullptr;
     // the last device_scan, seconds: from its start to the end of its first synchronisation (the candidate count), and
     // from there to the end of its second (the candidates); read by a session's flacgpu_decoder_session_last_feed_timing
     double scan_sync_s[2] = {0, 0};
@@ -150,10 +153,12 @@ struct Candidates {
 
 // A decoder session's feed (kernels/session.inc): every slot is built by k_session_slots from `srcs` (device addresses),
 // and the links are k_link_session's under `info`; both tables have one entry per slot and go up into the two buffers.
+// container: a container session's feed -- the regular scan's candidates, linked by k_link_container.
 struct SessionFill {
     const SessionSrc *srcs;
     const SessionSlot *info;
     DevBuf *src_tab, *info_tab;
+    bool container = false;
 };
 
 // The device half of a scan: fills every slot (zero tails, 64 bytes of look-ahead) -- host input in one upload, device
@@ -269,7 +274,10 @@ int device_scan(flacgpu_decoder *d, const ScanInput &in, const SlotLayout &lay, 
     p.link = d->link.as<int32_t>();
     p.n_cand = n_cand;
     hipLaunchKernelGGL(k_scan_emit, dim3(n_wg), dim3(WG), 0, d->st, p);
-    if (n_cand && fill)
+    if (n_cand && fill && fill->container)
+        hipLaunchKernelGGL(k_link_container, dim3((n_cand + WG - 1) / WG), dim3(WG), 0, d->st, p,
+                           fill->info_tab->as<const SessionSlot>());
+    else if (n_cand && fill)
         hipLaunchKernelGGL(k_link_session, dim3((n_cand + WG - 1) / WG), dim3(WG), 0, d->st, p,
                            fill->info_tab->as<const SessionSlot>());
     else if (n_cand && raw) hipLaunchKernelGGL(k_link_raw, dim3((n_cand + WG - 1) / WG), dim3(WG), 0, d->st, p);
@@ -602,6 +610,29 @@ struct flacgpu_decoder_session {
     bool finished = false, dead = false;   // dead: a call failed half way; every further call is refused
     flacgpu_session_timing timing{};       // of the last feed or finish
     DevBuf other, chunks, src_tab, info_tab;
+    // ---- a container session (DESIGN.md 4b "Container sessions"): regular .flac streams, MD5 across feeds ----
+    enum : uint32_t { CS_META = 0, CS_FRAMES = 1, CS_LOST = 2, CS_REFUSED = 3 };
+    struct Container {
+        MetaFeed meta{};             // the metadata walk so far (CS_META)
+        uint32_t phase = CS_META;
+        uint64_t fed = 0;            // bytes fed to this stream
+        flacgpu_stream_info info{};  // metadata_of_record's: STREAMINFO from CS_FRAMES on, what a refused stream reports
+        uint32_t min_frame = 0;
+        // cumulative: the frames decided, their samples per channel, the bytes dropped; bad_frames / bad_crc16 as the
+        // one-shot decode counts them (lost synchronisation, and what the hashing decode of every feed found)
+        uint64_t frames = 0, samples = 0, skipped = 0;
+        uint32_t bad_frames = 0, bad_crc16 = 0;
+        bool in_feed = false;        // the last feed decided frames for this stream
+        bool broken = false;         // such a feed was never hashed: the chain says nothing
+    };
+    bool container = false;
+    std::vector<Container> cs;
+    flacgpu_md5_chains *chains = nullptr;   // one per stream
+    bool hashed = true;           // the last feed's samples are in the chains (or it decided none)
+    bool verdict_given = false;
+    bool meta_on_device = false;  // meta_tab holds every stream's `meta` as it stands here
+    bool meta_fresh = false;      // k_meta_feed ran in the feed under way: its table is this feed's result
+    DevBuf meta_tab, meta_src, meta_used;
 };
 
 namespace {
@@ -708,6 +739,249 @@ int session_step(flacgpu_decoder_session *ses, const uint8_t *const *chunk, cons
     ses->timing.scan_rest_ms = ms(t1 - t0) - ses->timing.to_first_sync_ms - ses->timing.to_second_sync_ms;
     ses->timing.walk_ms = ms(t2 - t1);
     ses->timing.table_upload_ms = ms(t3 - t2);
+    ses->dead = false;
+    return FLACGPU_OK;
+}
+
+// The metadata walk of one feed of a container session (kernels/meta_feed_rule.h): meta[i] is stream i's walk behind this
+// feed's bytes, used[i] how many of them belong to the metadata.  Host chunks (door 0) are walked here; device chunks
+// (door 1) by k_meta_feed where they lie -- the state table stays in device memory from feed to feed, goes up only when a
+// host feed has changed it, and comes down with the counts.  Nothing of the session changes but that table and its flag.
+int container_meta(flacgpu_decoder_session *ses, int door, const uint8_t *const *data, const size_t *len,
+                   std::vector<MetaFeed> &meta, std::vector<uint64_t> &used) {
+    using Ses = flacgpu_decoder_session;
+    flacgpu_decoder *d = ses->d;
+    const uint32_t n = (uint32_t)ses->cs.size();
+    std::vector<DevSource> src;
+    bool any = false;
+    ses->meta_fresh = false;
+    try {
+        meta.resize(n);
+        used.assign(n, 0);
+        src.assign(n, DevSource{nullptr, 0});
+    } catch (const std::bad_alloc &) {
+        g_last_error = "flacgpu_decoder_session_feed: out of host memory";
+        return FLACGPU_ERR_UNSUPPORTED;
+    }
+    for (uint32_t i = 0; i < n; i++) {
+        meta[i] = ses->cs[i].meta;
+        if (door == 2 || ses->cs[i].phase != Ses::CS_META || !data[i] || !len[i]) continue;
+        any = true;
+        if (door == 0) used[i] = meta_feed(meta[i], data[i], len[i]);
+        else src[i] = DevSource{data[i], len[i]};
+    }
+    if (!any) return FLACGPU_OK;
+    if (door == 0) {
+        ses->meta_on_device = false;
+        return FLACGPU_OK;
+    }
+    if (int rc = ses->meta_tab.ensure(sizeof(MetaFeed) * n)) return rc;
+    if (int rc = ses->meta_src.ensure(sizeof(DevSource) * n)) return rc;
+    if (int rc = ses->meta_used.ensure(8 * (size_t)n)) return rc;
+    if (!ses->meta_on_device)
+        HIP_TRY(hipMemcpyAsync(ses->meta_tab.p, meta.data(), sizeof(MetaFeed) * n, hipMemcpyHostToDevice, d->st));
+    ses->meta_on_device = false;   // until the table and this feed's result are known to agree
+    HIP_TRY(hipMemcpyAsync(ses->meta_src.p, src.data(), sizeof(DevSource) * n, hipMemcpyHostToDevice, d->st));
+    hipLaunchKernelGGL(k_meta_feed, dim3((n + 63) / 64), dim3(64), 0, d->st, ses->meta_src.as<const DevSource>(), n,
+                       ses->meta_tab.as<MetaFeed>(), ses->meta_used.as<uint64_t>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(meta.data(), ses->meta_tab.p, sizeof(MetaFeed) * n, hipMemcpyDeviceToHost, d->st));
+    HIP_TRY(hipMemcpyAsync(used.data(), ses->meta_used.p, 8 * (size_t)n, hipMemcpyDeviceToHost, d->st));
+    HIP_TRY(hipStreamSynchronize(d->st));
+    ses->meta_fresh = true;
+    return FLACGPU_OK;
+}
+
+// One feed of a container session behind its argument checks and container_meta (finish: no bytes, the input ends).
+// chunk[i]: DEVICE address of what stream i was fed behind its metadata (null: none), len[i] the count; fed_now[i]: all
+// the bytes it was fed.  A stream in its frame phase gets a slot of tail + chunk with STREAMINFO's channels and
+// min_frame; the device finds the regular scan's candidates and links them by the rule (k_link_container), and the host
+// follows the chain from the cursor (regular_walk, host/raw_walk.h) as scan_impl follows k_link's.  The decoder is left
+// as scan_impl leaves it, for the batch "every STREAMINFO with the frames decided now".
+int container_step(flacgpu_decoder_session *ses, const uint8_t *const *chunk, const uint64_t *len, const uint64_t *fed_now,
+                   const std::vector<MetaFeed> &meta, bool finish) {
+    using Ses = flacgpu_decoder_session;
+    flacgpu_decoder *d = ses->d;
+    const uint32_t n = (uint32_t)ses->streams.size();
+    SlotLayout lay;
+    Candidates c;
+    std::vector<SessionSrc> srcs;
+    std::vector<SessionSlot> info;
+    const uint8_t *const tails = d->bytes.as<const uint8_t>();   // `other` from the swap below on
+    // everything the feed changes, in locals: a call refused below has touched neither the session nor its decoder
+    std::vector<flacgpu_decoded_stream> res;
+    std::vector<int32_t> slot_of;
+    std::vector<flacgpu_raw_stream> raw_streams;
+    std::vector<Ses::Stream> streams;
+    std::vector<Ses::Container> cs;
+    try {
+        res.assign(n, flacgpu_decoded_stream{});
+        slot_of.assign(n, -1);
+        raw_streams.assign(n, flacgpu_raw_stream{});
+        streams = ses->streams;
+        cs = ses->cs;
+        for (uint32_t i = 0; i < n; i++) {
+            Ses::Container &k = cs[i];
+            Ses::Stream &st = streams[i];
+            k.fed += fed_now[i];
+            if (!ses->hashed && k.in_feed) k.broken = true;   // the feed before decided frames that were never hashed
+            k.in_feed = false;
+            if (k.phase == Ses::CS_META) {
+                k.meta = meta[i];
+                if (k.meta.phase == MF_DONE || k.meta.phase == MF_REFUSED || finish) {
+                    MetaRecord rec;
+                    meta_feed_record(k.meta, k.meta.phase == MF_DONE ? k.meta.taken : k.fed, rec);
+                    size_t at = 0;
+                    if (flacenc::metadata_of_record(rec, &k.info, &k.min_frame, &at)) {
+                        k.phase = Ses::CS_REFUSED;
+                    } else {
+                        k.phase = Ses::CS_FRAMES;
+                        st.base = at;
+                    }
+                }
+            }
+            const uint64_t fresh = chunk && chunk[i] ? len[i] : 0;
+            if (k.phase == Ses::CS_FRAMES && st.held + fresh) {
+                slot_of[i] = (int32_t)lay.add(i, 0, st.held + fresh, k.info.channels, k.min_frame);
+                srcs.push_back(SessionSrc{reinterpret_cast<uint64_t>(tails + st.at), st.held,
+                                          fresh ? reinterpret_cast<uint64_t>(chunk[i]) : 0, fresh});
+                info.push_back(SessionSlot{finish ? 1u : 0u, ses->W});
+            } else if (k.phase == Ses::CS_LOST) {
+                k.skipped += fed_now[i];
+            }
+            if (k.phase == Ses::CS_REFUSED) k.skipped = k.fed;
+        }
+    } catch (const std::bad_alloc &) {
+        g_last_error = "flacgpu_decoder_session_feed: out of host memory";
+        return FLACGPU_ERR_UNSUPPORTED;
+    }
+    const uint32_t S = (uint32_t)lay.slots.size();
+    if (lay.at + 64 > ((uint64_t)1 << 34)) {   // device_scan's limit, before anything has changed
+        g_last_error = "flacgpu_decoder_session_feed: the feed's slots exceed 16 GiB";
+        return FLACGPU_ERR_UNSUPPORTED;
+    }
+    // ---- from here on the feed is under way (nothing below up to the scan allocates)
+    d->scanned = d->raw = false;
+    d->res.swap(res);
+    d->slot_of.swap(slot_of);
+    d->raw_streams.swap(raw_streams);
+    d->frame_tab.clear();
+    d->records.clear();
+    d->raw_tab.clear();
+    d->raw_tab_uploaded = false;
+    d->n_slots = S;
+    d->slot_bytes = 0;
+    ses->streams.swap(streams);
+    ses->cs.swap(cs);
+    ses->dead = true;   // until the feed is through
+    std::swap(d->bytes.p, ses->other.p);
+    std::swap(d->bytes.cap, ses->other.cap);
+    const auto t0 = std::chrono::steady_clock::now();
+    if (S) {
+        SessionFill fill{srcs.data(), info.data(), &ses->src_tab, &ses->info_tab};
+        fill.container = true;
+        if (int rc = device_scan(d, ScanInput{nullptr, true}, lay, false, false, false, c, &fill)) return rc;
+    } else {
+        d->scan_sync_s[0] = d->scan_sync_s[1] = 0;
+    }
+    const auto t1 = std::chrono::steady_clock::now();
+    try {
+        d->frame_tab.reserve(c.n);
+        for (uint32_t i = 0; i < n; i++) {
+            Ses::Container &k = ses->cs[i];
+            Ses::Stream &st = ses->streams[i];
+            const size_t first = d->frame_tab.size();
+            const int32_t s = d->slot_of[i];
+            uint64_t samples = 0;
+            if (s >= 0) {
+                const ScanSlot &sl = lay.slots[s];
+                const uint64_t slot_end = sl.base + sl.len;
+                const flacenc::RegularWalk w = flacenc::regular_walk(
+                    c.pos.data(), c.cand0[s], c.end_of((uint32_t)s), sl.base, slot_end,
+                    flacenc::session_judged(sl.base, sl.len, finish),
+                    [&](size_t q, uint64_t) {
+                        const int32_t link = c.link[q];
+                        if (link == LINK_HOLD) return flacenc::RawEnd{flacenc::kRawHold, false};
+                        if (link == LINK_NONE) return flacenc::RawEnd{flacenc::kRawNone, false};
+                        return flacenc::RawEnd{link == LINK_END ? slot_end : c.pos[link], false};
+                    },
+                    [&](size_t q, uint64_t at, uint64_t end) {
+                        ManyFrame f{};
+                        f.start = at;
+                        f.end = end;
+                        f.cap = lay.end_of((uint32_t)s) - 4;
+                        f.n = (c.info[q] & 0xFFFFu) + 1u;
+                        f.slot = (uint32_t)s;
+                        f.channels = k.info.channels;
+                        f.bps = k.info.bits_per_sample;
+                        f.out = samples;   // stream-relative here, made absolute below
+                        d->frame_tab.push_back(f);
+                        samples += f.n;
+                    });
+                st.base += w.cursor - sl.base;
+                if (w.lost) {   // nothing from the cursor on is kept, now or later
+                    k.phase = Ses::CS_LOST;
+                    k.bad_frames++;
+                    k.skipped += slot_end - w.cursor;
+                    st.held = st.at = 0;
+                } else {
+                    st.held = slot_end - w.cursor;
+                    st.at = w.cursor;
+                }
+            }
+            const size_t F = d->frame_tab.size() - first;
+            k.frames += F;
+            k.samples += samples;
+            k.in_feed = F != 0;
+            if (F) {
+                flacgpu_decoded_stream &r = d->res[i];
+                r.rc = FLACGPU_OK;
+                r.info = k.info;
+                r.info.frames = (uint32_t)F;
+                r.info.decoded_samples = samples;
+                r.info.md5_status = 3;   // the MD5 is the session's, across feeds
+            } else {
+                d->res[i].rc = FLACGPU_ERR_INVALID_ARG;
+            }
+            flacgpu_raw_stream &sum = d->raw_streams[i];
+            sum.first_frame = first;
+            sum.frames = (uint32_t)k.frames;
+            sum.skipped_bytes = k.skipped;
+            sum.gaps = k.skipped ? 1 : 0;
+            sum.uniform = k.phase == Ses::CS_FRAMES || k.phase == Ses::CS_LOST;
+        }
+    } catch (const std::bad_alloc &) {
+        g_last_error = "flacgpu_decoder_session_feed: out of host memory";
+        return FLACGPU_ERR_UNSUPPORTED;
+    }
+    if (d->frame_tab.size() > 0x7FFFFFFFull) {
+        g_last_error = "flacgpu_decoder_session_feed: more than 2^31 - 1 frames";
+        return FLACGPU_ERR_UNSUPPORTED;
+    }
+    // ---- output layout, as scan_impl's: streams one after another, interleaved
+    uint64_t total = 0, scratch_total = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        flacgpu_decoded_stream &r = d->res[i];
+        r.out_offset = total;
+        if (r.rc == FLACGPU_OK) total += r.info.decoded_samples * r.info.channels;
+    }
+    for (ManyFrame &f : d->frame_tab) {
+        f.out = d->res[lay.slot_stream[f.slot]].out_offset + f.out * f.channels;
+        f.scratch = scratch_total;
+        scratch_total += (uint64_t)f.channels * ((f.n + 3u) & ~3u);
+    }
+    const auto t2 = std::chrono::steady_clock::now();
+    d->raw_elements = total;
+    d->raw_scratch = 0;
+    if (int rc = finish_scan(d, lay, total, scratch_total)) return rc;
+    const auto t3 = std::chrono::steady_clock::now();
+    const auto ms = [](std::chrono::steady_clock::duration v) { return std::chrono::duration<double, std::milli>(v).count(); };
+    ses->timing.to_first_sync_ms = d->scan_sync_s[0] * 1e3;
+    ses->timing.to_second_sync_ms = d->scan_sync_s[1] * 1e3;
+    ses->timing.scan_rest_ms = ms(t1 - t0) - ses->timing.to_first_sync_ms - ses->timing.to_second_sync_ms;
+    ses->timing.walk_ms = ms(t2 - t1);
+    ses->timing.table_upload_ms = ms(t3 - t2);
+    ses->hashed = d->frame_tab.empty();
     ses->dead = false;
     return FLACGPU_OK;
 }
@@ -906,11 +1180,15 @@ int decode_impl(flacgpu_decoder *d, void *out, uint32_t flags, flacgpu_decoded_s
     DeviceGuard guard(d->device);
     const uint32_t n = (uint32_t)d->res.size();
     const bool md5 = !(flags & FLACGPU_DECODE_NO_MD5);
+    // A container session's decoder hashes across feeds: the first call with MD5 after a feed appends the feed's samples
+    // to the session's chains (`chain`), every other call hashes nothing; k_md5_many (`many`) is the other handles'.
+    flacgpu_decoder_session *const ses = d->container;
+    const bool chain = ses && md5 && !ses->hashed, many = md5 && !ses;
     OutStage o;
     if (int rc = o.open(d->out_stage, out, fmt ? out_bytes : 4 * d->total, flags & FLACGPU_DECODE_OUT_DEVICE)) return rc;
-    int32_t *side = nullptr;   // decode_as with MD5: the interleaved int32 that k_md5_many reads
+    int32_t *side = nullptr;   // decode_as with MD5: the interleaved int32 that k_md5_many / k_md5_chain reads
     if (fmt) {
-        if (md5 && d->total) {
+        if ((many || chain) && d->total) {
             if (int rc = d->md5_stage.ensure(4 * d->total)) return rc;
             side = d->md5_stage.as<int32_t>();
         }
@@ -939,7 +1217,28 @@ int decode_impl(flacgpu_decoder *d, void *out, uint32_t flags, flacgpu_decoded_s
     HIP_TRY(hipGetLastError());
     std::vector<Md5Job> jobs;
     std::vector<uint32_t> job_stream, digest;
-    if (md5) {
+    if (chain) {   // on the decoder's stream, behind the kernel that wrote the samples; no synchronisation of its own
+        std::vector<flacgpu_md5_piece> pieces;
+        std::vector<uint32_t> widths;
+        try {
+            for (uint32_t i = 0; i < n; i++) {
+                const flacgpu_decoded_stream &r = d->res[i];
+                if (r.rc != FLACGPU_OK || !r.info.decoded_samples) continue;
+                pieces.push_back(flacgpu_md5_piece{i, 0, r.out_offset, r.info.decoded_samples * r.info.channels});
+                widths.push_back((r.info.bits_per_sample + 7) / 8);
+            }
+        } catch (const std::bad_alloc &) {
+            (void)hipStreamSynchronize(d->st);
+            g_last_error = "flacgpu_decoder_decode: out of host memory";
+            return FLACGPU_ERR_UNSUPPORTED;
+        }
+        if (int rc = flacgpu_k::md5_chains_update_widths(ses->chains, hashed, pieces.data(), widths.data(),
+                                                         (uint32_t)pieces.size(), d->st)) {
+            (void)hipStreamSynchronize(d->st);
+            return rc;
+        }
+    }
+    if (many) {
         for (uint32_t i = 0; i < n; i++) {
             const flacgpu_decoded_stream &r = d->res[i];
             if (r.rc != FLACGPU_OK) continue;
@@ -975,8 +1274,13 @@ int decode_impl(flacgpu_decoder *d, void *out, uint32_t flags, flacgpu_decoded_s
             r.info.bad_frames += counts[2 * (size_t)s];
             r.info.bad_crc16 = counts[2 * (size_t)s + 1];
         }
-        if (r.rc == FLACGPU_OK && !md5) r.info.md5_status = 3;
+        if (r.rc == FLACGPU_OK && !many) r.info.md5_status = 3;
+        if (chain) {   // the session's counts: what this feed's frames add
+            ses->cs[i].bad_frames += r.info.bad_frames;
+            ses->cs[i].bad_crc16 += r.info.bad_crc16;
+        }
     }
+    if (chain) ses->hashed = true;
     for (uint32_t j = 0; j < J; j++) {
         flacgpu_stream_info &info = streams[job_stream[j]].info;
         memcpy(info.decoded_md5, &digest[5 * (size_t)j], 16);
@@ -1559,9 +1863,79 @@ int flacgpu_decoder_session_open(int device, uint32_t n_streams, uint32_t max_fr
     return FLACGPU_OK;
 }
 
+int flacgpu_decoder_session_open_container(int device, uint32_t n_streams, uint32_t max_frame_bytes,
+                                           flacgpu_decoder_session **out) {
+    if (int rc = flacgpu_decoder_session_open(device, n_streams, max_frame_bytes, 0, out)) return rc;
+    flacgpu_decoder_session *s = *out;
+    *out = nullptr;
+    int rc = FLACGPU_OK;
+    try {
+        s->cs.resize(n_streams);
+        for (flacgpu_decoder_session::Container &k : s->cs) meta_feed_init(k.meta);
+    } catch (const std::bad_alloc &) {
+        g_last_error = "flacgpu_decoder_session_open_container: out of host memory";
+        rc = FLACGPU_ERR_UNSUPPORTED;
+    }
+    if (!rc) rc = flacgpu_md5_chains_create(s->d->device, n_streams, &s->chains);
+    if (rc) {
+        flacgpu_decoder_session_close(s);
+        return rc;
+    }
+    s->container = true;
+    s->d->container = s;
+    *out = s;
+    return FLACGPU_OK;
+}
+
+int flacgpu_decoder_session_verdict(flacgpu_decoder_session *s, flacgpu_decoded_stream *out) {
+    const uint32_t n = s ? (uint32_t)s->streams.size() : 0;
+    if (!s || !s->container || s->dead || !s->finished || s->verdict_given || (n && !out)) {
+        g_last_error = "flacgpu_decoder_session_verdict: no container session, not finished yet, or the verdict was given";
+        return FLACGPU_ERR_INVALID_ARG;
+    }
+    std::vector<uint8_t> digest;
+    std::vector<flacgpu_decoded_stream> res;
+    try {
+        digest.resize(16 * (size_t)n);
+        res.assign(n, flacgpu_decoded_stream{});
+    } catch (const std::bad_alloc &) {
+        g_last_error = "flacgpu_decoder_session_verdict: out of host memory";
+        return FLACGPU_ERR_UNSUPPORTED;
+    }
+    if (int rc = flacgpu_md5_chains_final(s->chains, digest.data())) return rc;   // pads, downloads; synchronous
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const flacgpu_decoder_session::Container &k = s->cs[i];
+        flacgpu_decoded_stream &r = res[i];
+        r.out_offset = total;   // the one-shot batch's layout
+        r.info = k.info;
+        if (k.phase == flacgpu_decoder_session::CS_REFUSED) {
+            r.rc = FLACGPU_ERR_INVALID_ARG;
+            continue;
+        }
+        r.info.frames = (uint32_t)k.frames;
+        r.info.decoded_samples = k.samples;
+        r.info.bad_frames = k.bad_frames;
+        r.info.bad_crc16 = k.bad_crc16;
+        total += k.samples * k.info.channels;
+        if (k.broken || (!s->hashed && k.in_feed)) {   // a feed's frames were never hashed
+            r.info.md5_status = 3;
+            continue;
+        }
+        memcpy(r.info.decoded_md5, &digest[16 * (size_t)i], 16);
+        static const uint8_t zero[16] = {0};
+        r.info.md5_status = !memcmp(k.info.md5, zero, 16) ? 2u : !memcmp(k.info.md5, r.info.decoded_md5, 16) ? 1u : 0u;
+    }
+    if (n) memcpy(out, res.data(), sizeof(flacgpu_decoded_stream) * n);
+    s->verdict_given = true;
+    return FLACGPU_OK;
+}
+
 void flacgpu_decoder_session_close(flacgpu_decoder_session *s) {
     if (!s) return;
     flacgpu_decoder *d = s->d;
+    flacgpu_md5_chains_destroy(s->chains);   // (waits for its updates on the decoder's stream)
+    d->container = nullptr;
     {
         DeviceGuard guard(d->device);
         if (d->st) (void)hipStreamSynchronize(d->st);
@@ -1569,6 +1943,9 @@ void flacgpu_decoder_session_close(flacgpu_decoder_session *s) {
         s->chunks.release();
         s->src_tab.release();
         s->info_tab.release();
+        s->meta_tab.release();
+        s->meta_src.release();
+        s->meta_used.release();
     }
     delete s;
     d->session = false;
@@ -1600,15 +1977,23 @@ static int session_call(flacgpu_decoder_session *s, int door, const uint8_t *con
         g_last_error = std::string(who) + (s->dead ? ": an earlier call on this session failed" : ": the session is finished");
         return FLACGPU_ERR_INVALID_ARG;
     }
+    for (uint32_t i = 0; s->container && flush && i < n; i++)
+        if (flush[i]) {   // a container's sender knows no frame boundary: finish alone ends the input
+            g_last_error = std::string(who) + ": a container session takes no flush";
+            return FLACGPU_ERR_INVALID_ARG;
+        }
     flacgpu_decoder *d = s->d;
     DeviceGuard guard(d->device);
     const auto t_in = std::chrono::steady_clock::now();
     std::vector<const uint8_t *> chunk;
-    std::vector<uint64_t> bytes;
-    uint64_t fresh = 0;
+    std::vector<uint64_t> bytes, fed_now, used;   // fed_now, used: a container session's (all bytes; those of the metadata)
+    std::vector<MetaFeed> meta;
+    uint64_t fresh = 0, fed = 0;
     try {
         chunk.assign(n, nullptr);
         bytes.assign(n, 0);
+        fed_now.assign(n, 0);
+        used.assign(n, 0);
     } catch (const std::bad_alloc &) {
         g_last_error = std::string(who) + ": out of host memory";
         return FLACGPU_ERR_UNSUPPORTED;
@@ -1618,19 +2003,33 @@ static int session_call(flacgpu_decoder_session *s, int door, const uint8_t *con
             s->dead = rc == FLACGPU_ERR_HIP;
             return rc;
         }
+        if (s->container)   // on the decoder's stream, behind the caller's: the metadata is walked where it lies
+            if (int rc = container_meta(s, door, data, len, meta, used)) {
+                s->dead = rc == FLACGPU_ERR_HIP;
+                return rc;
+            }
         for (uint32_t i = 0; i < n; i++)
             if (data[i] && len[i]) {
-                chunk[i] = data[i];
-                bytes[i] = len[i];
-                fresh += len[i];
+                fed_now[i] = len[i];
+                fed += len[i];
+                if (s->container && s->cs[i].phase >= flacgpu_decoder_session::CS_LOST) continue;   // dropped
+                if (len[i] == used[i]) continue;
+                chunk[i] = data[i] + used[i];
+                bytes[i] = len[i] - used[i];
+                fresh += bytes[i];
             }
     } else if (door == 0) {
         // the chunks alone go up: into the pinned staging at 16-byte boundaries, one copy, and the kernel joins them to
         // the tails that never left the device
+        if (s->container)
+            if (int rc = container_meta(s, door, data, len, meta, used)) return rc;
         for (uint32_t i = 0; i < n; i++)
             if (data[i] && len[i]) {
-                bytes[i] = len[i];
-                fresh += len[i];
+                fed_now[i] = len[i];
+                fed += len[i];
+                if (s->container && s->cs[i].phase >= flacgpu_decoder_session::CS_LOST) continue;   // dropped
+                bytes[i] = len[i] - used[i];   // the metadata's bytes never go up
+                fresh += bytes[i];
             }
         const uint64_t up = fresh + 16 * (uint64_t)n;
         if (fresh) {
@@ -1644,7 +2043,7 @@ static int session_call(flacgpu_decoder_session *s, int door, const uint8_t *con
             uint64_t at = 0;
             for (uint32_t i = 0; i < n; i++) {
                 if (!bytes[i]) continue;
-                memcpy(stg + at, data[i], bytes[i]);
+                memcpy(stg + at, data[i] + used[i], bytes[i]);
                 chunk[i] = s->chunks.as<const uint8_t>() + at;
                 at = (at + bytes[i] + 15) & ~(uint64_t)15;
             }
@@ -1657,6 +2056,23 @@ static int session_call(flacgpu_decoder_session *s, int door, const uint8_t *con
         }
     }
     const double stage_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_in).count();
+    if (s->container) {
+        if (door == 2)
+            if (int rc = container_meta(s, door, data, len, meta, used)) return rc;
+        if (int rc = container_step(s, chunk.data(), bytes.data(), fed_now.data(), meta, door == 2)) return rc;
+        if (s->meta_fresh) s->meta_on_device = true;   // the feed is committed: the table is the streams' state
+        s->timing.stage_ms = stage_ms;
+        s->fed += fed;
+        s->finished = door == 2;
+        // what scan leaves: a batch of regular streams (decode_frames, frame_records and the timeline calls refuse it)
+        index_frames(d);
+        d->scanned = true;
+        if (n) memcpy(streams, d->res.data(), sizeof(flacgpu_decoded_stream) * n);
+        if (n && raw) memcpy(raw, d->raw_streams.data(), sizeof(flacgpu_raw_stream) * n);
+        *total_frames = d->frame_tab.size();
+        *total_elements = *total_samples = d->total;
+        return FLACGPU_OK;
+    }
     if (int rc = session_step(s, chunk.data(), bytes.data(), flush, door == 2)) return rc;
     s->timing.stage_ms = stage_ms;
     s->fed += fresh;

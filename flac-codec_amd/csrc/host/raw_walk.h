@@ -84,6 +84,47 @@ static inline uint64_t session_hold(const RawWalk &w, uint64_t begin, uint64_t l
     return h;
 }
 
+// ---- a container session's walk (DESIGN.md 4b "Container sessions") ----
+// A regular stream's frames are a chain from the cursor: the frame at the cursor ends where the next begins, and a
+// cursor that is no candidate, or a frame without an end, loses the stream for good.
+struct RegularWalk {
+    uint64_t cursor;   // the end of the last kept frame (`begin`: none kept): an open stream is held from here
+    bool lost;         // synchronisation was lost at the cursor: nothing from there on is kept, in this feed or later
+};
+
+// The walk over one stream's candidates pos[k0, k1), ascending positions in [begin, limit); the positions below `judged`
+// have been judged (a session judges a position once kSessionHead bytes follow it, or the input has ended).  end_of(k, at)
+// answers for the candidate at the cursor: a position behind it, kRawNone (no end, and none can come) or kRawHold (not
+// decided yet).  keep(k, at, end) is told every kept frame.  The walk stops at `limit`, at a cursor not judged yet, at a
+// held candidate, or where synchronisation is lost.
+template <class Pos, class EndOf, class Keep>
+RegularWalk regular_walk(const Pos *pos, size_t k0, size_t k1, uint64_t begin, uint64_t limit, uint64_t judged,
+                         EndOf end_of, Keep keep) {
+    RegularWalk w{begin, false};
+    size_t k = k0;
+    while (w.cursor < limit && w.cursor < judged) {
+        while (k < k1 && pos[k] < w.cursor) k++;
+        if (k == k1 || pos[k] != w.cursor) {
+            w.lost = true;
+            break;
+        }
+        const RawEnd e = end_of(k, w.cursor);
+        if (e.end == kRawHold) break;
+        if (e.end == kRawNone) {
+            w.lost = true;
+            break;
+        }
+        keep(k, w.cursor, e.end);
+        w.cursor = e.end;
+    }
+    return w;
+}
+
+// the first position of a session's segment [begin, begin + len) that is not judged yet
+static inline uint64_t session_judged(uint64_t begin, uint64_t len, bool final) {
+    return final ? begin + len : begin + (len >= kSessionHead ? len - kSessionHead + 1 : 0);
+}
+
 // The record of a kept frame of `bytes` bytes with the header `h` (status 0)
 static inline flacgpu_frame_record raw_frame_record(const HostFrameInfo &h, uint32_t stream, uint64_t byte_offset,
                                                     uint64_t bytes, uint64_t out_offset, bool own) {

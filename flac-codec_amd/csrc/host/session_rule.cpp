@@ -1,11 +1,57 @@
 #include "session_rule.h"
 
+#include <string.h>
+
 #include <algorithm>
 #include <new>
 
+#include "../kernels/meta_feed_rule.h"
 #include "raw_walk.h"
 
 namespace flacenc {
+RegularWalk container_decide(const uint8_t *d, size_t L, bool final, uint32_t W, const flacgpu_stream_info &info,
+                             uint32_t min_frame, uint64_t base, uint32_t stream, std::vector<flacgpu_frame_record> &out,
+                             uint64_t *elements) {
+    const size_t judged = (size_t)session_judged(0, L, final);
+    // the regular candidate test: every header that parses, those that defer to STREAMINFO included
+    std::vector<size_t> cand;
+    std::vector<HostFrameInfo> head;
+    for (size_t q = 0; q < judged; q++) {
+        HostFrameInfo h;
+        if (d[q] == 0xFF && host_parse_frame_info(d + q, L - q, h)) {
+            cand.push_back(q);
+            head.push_back(h);
+        }
+    }
+    const uint16_t *const T = crc16_table();
+    return regular_walk(
+        cand.data(), 0, cand.size(), 0, L, judged,
+        [&](size_t k, uint64_t s) {
+            const HostFrameInfo &h = head[k];
+            const size_t min_end = s + std::max<size_t>(h.header_bytes + 2 + info.channels, min_frame);
+            uint16_t crc = 0;   // of [s, at)
+            size_t at = s;
+            for (size_t j = k + 1; j < cand.size() && cand[j] - s <= W; j++) {
+                for (; at < cand[j]; at++) crc = crc16_step(T, crc, d[at]);
+                if (cand[j] >= min_end && crc == 0 && head[j].blocking == h.blocking) return RawEnd{cand[j], false};
+            }
+            if (final) {
+                if (L - s < 2 || L - s > W) return RawEnd{kRawNone, false};
+                for (; at < L; at++) crc = crc16_step(T, crc, d[at]);
+                return RawEnd{crc == 0 ? L : kRawNone, false};
+            }
+            // every position up to s + W judged and none fits: no end can come
+            return RawEnd{L - s >= (size_t)W + kSessionHead ? kRawNone : kRawHold, false};
+        },
+        [&](size_t k, uint64_t s, uint64_t end) {
+            HostFrameInfo h = head[k];
+            if (!h.rcode) h.sample_rate = info.sample_rate;
+            if (!h.bps_code) h.bits_per_sample = info.bits_per_sample;
+            out.push_back(raw_frame_record(h, stream, base + s, end - s, *elements, false));
+            *elements += (uint64_t)h.n * h.channels;
+        });
+}
+
 size_t session_decide(const uint8_t *d, size_t L, bool final, uint32_t W, uint64_t base, uint32_t stream,
                       SessionCount &count, std::vector<flacgpu_frame_record> &out, uint64_t *elements) {
     // the positions judged so far: all of a flushed stream, else those with kSessionHead bytes behind them
@@ -35,11 +81,20 @@ struct flacgpu_session_host {
         std::vector<uint8_t> held;   // the bytes that cannot be judged yet
         uint64_t base = 0;           // offset of held[0] from the stream's first byte
         flacenc::SessionCount count;
+        // a container session's (DESIGN.md 4b "Container sessions")
+        MetaFeed meta{};
+        uint32_t phase = 0;         // CS_*
+        uint64_t fed = 0;            // bytes fed to this stream
+        flacgpu_stream_info info{};  // STREAMINFO, from CS_FRAMES on
+        uint32_t min_frame = 0;
     };
     std::vector<Stream> streams;
     uint32_t W = 0;
-    bool finished = false;
+    bool finished = false, container = false;
 };
+namespace {
+enum : uint32_t { CS_META = 0, CS_FRAMES = 1, CS_LOST = 2, CS_REFUSED = 3 };
+}
 
 int flacgpu_session_host_open(uint32_t n_streams, uint32_t max_frame_bytes, flacgpu_session_host **out) {
     if (!out) return FLACGPU_ERR_INVALID_ARG;
@@ -56,6 +111,116 @@ int flacgpu_session_host_open(uint32_t n_streams, uint32_t max_frame_bytes, flac
     return FLACGPU_OK;
 }
 
+int flacgpu_session_host_open_container(uint32_t n_streams, uint32_t max_frame_bytes, flacgpu_session_host **out) {
+    if (int rc = flacgpu_session_host_open(n_streams, max_frame_bytes, out)) return rc;
+    (*out)->container = true;
+    for (flacgpu_session_host::Stream &st : (*out)->streams) meta_feed_init(st.meta);
+    return FLACGPU_OK;
+}
+
+int flacgpu_meta_feed_host(flacgpu_meta_feed *state, const uint8_t *chunk, size_t len, size_t *consumed) {
+    static_assert(sizeof(flacgpu_meta_feed) == sizeof(MetaFeed), "flacgpu_meta_feed is MetaFeed");
+    if (!state || !consumed || (len && !chunk)) return FLACGPU_ERR_INVALID_ARG;
+    MetaFeed m;
+    memcpy(&m, state, sizeof m);
+    if (m.phase > MF_REFUSED || m.have >= kStreamInfoBytes) return FLACGPU_ERR_INVALID_ARG;   // not a state of ours
+    *consumed = (size_t)meta_feed(m, chunk, len);
+    memcpy(state, &m, sizeof m);
+    return FLACGPU_OK;
+}
+
+void flacgpu_meta_feed_init_host(flacgpu_meta_feed *state) {
+    if (!state) return;
+    MetaFeed m;
+    meta_feed_init(m);
+    memcpy(state, &m, sizeof m);
+}
+
+int flacgpu_meta_feed_result_host(const flacgpu_meta_feed *state, uint64_t total_bytes, flacgpu_stream_info *info,
+                                  uint32_t *min_frame, uint64_t *frames_at) {
+    if (!state || !info || !min_frame || !frames_at) return FLACGPU_ERR_INVALID_ARG;
+    *frames_at = 0;
+    MetaFeed m;
+    memcpy(&m, state, sizeof m);
+    MetaRecord rec;
+    meta_feed_record(m, total_bytes, rec);
+    size_t pos = 0;
+    if (flacenc::metadata_of_record(rec, info, min_frame, &pos)) return FLACGPU_ERR_INVALID_ARG;
+    *frames_at = pos;
+    return FLACGPU_OK;
+}
+
+// one feed of a container session into copies of the streams; committed only when the records fit
+static int container_host_step(flacgpu_session_host *s, const uint8_t *const *data, const size_t *len, bool finish,
+                               flacgpu_frame_record *records, size_t cap, flacgpu_raw_stream *raw, uint64_t *held_bytes,
+                               uint64_t *total_frames) {
+    const uint32_t n = (uint32_t)s->streams.size();
+    try {
+        std::vector<flacgpu_session_host::Stream> next(s->streams);
+        std::vector<flacgpu_frame_record> recs;
+        std::vector<flacgpu_raw_stream> sums(n);
+        uint64_t elements = 0;
+        for (uint32_t i = 0; i < n; i++) {
+            flacgpu_session_host::Stream &st = next[i];
+            const uint8_t *chunk = !finish && data[i] && len[i] ? data[i] : nullptr;
+            size_t fresh = chunk ? len[i] : 0;
+            st.fed += fresh;
+            const size_t first = recs.size();
+            if (st.phase == CS_META) {
+                const size_t used = (size_t)meta_feed(st.meta, chunk, fresh);
+                if (st.meta.phase == MF_DONE || st.meta.phase == MF_REFUSED || finish) {
+                    MetaRecord rec;
+                    meta_feed_record(st.meta, st.meta.phase == MF_DONE ? st.meta.taken : st.fed, rec);
+                    size_t at = 0;
+                    if (flacenc::metadata_of_record(rec, &st.info, &st.min_frame, &at)) st.phase = CS_REFUSED;
+                    else {
+                        st.phase = CS_FRAMES;
+                        st.base = at;
+                    }
+                }
+                chunk = chunk ? chunk + used : nullptr;   // metadata bytes are never held
+                fresh -= used;
+            }
+            if (st.phase == CS_FRAMES) {
+                if (fresh) st.held.insert(st.held.end(), chunk, chunk + fresh);
+                const flacenc::RegularWalk w = flacenc::container_decide(st.held.data(), st.held.size(), finish, s->W, st.info,
+                                                                         st.min_frame, st.base, i, recs, &elements);
+                st.count.frames += (uint32_t)(recs.size() - first);
+                st.base += w.cursor;
+                if (w.lost) {
+                    st.phase = CS_LOST;
+                    st.count.skipped = st.held.size() - w.cursor;
+                    st.held.clear();
+                } else {
+                    st.held.erase(st.held.begin(), st.held.begin() + w.cursor);
+                }
+            } else if (st.phase == CS_LOST) {
+                st.count.skipped += fresh;
+            }
+            if (st.phase == CS_REFUSED) st.count.skipped = st.fed;
+            flacgpu_raw_stream &sum = sums[i];
+            sum = flacgpu_raw_stream{};
+            sum.first_frame = first;
+            sum.frames = st.count.frames;
+            sum.skipped_bytes = st.count.skipped;
+            sum.gaps = st.count.skipped ? 1 : 0;
+            sum.uniform = st.phase == CS_FRAMES || st.phase == CS_LOST;
+        }
+        *total_frames = recs.size();
+        if (recs.size() > cap || (!recs.empty() && !records)) return FLACGPU_ERR_BUFFER_TOO_SMALL;
+        for (size_t k = 0; k < recs.size(); k++) records[k] = recs[k];
+        for (uint32_t i = 0; i < n; i++) {
+            if (raw) raw[i] = sums[i];
+            if (held_bytes) held_bytes[i] = next[i].held.size();
+        }
+        s->streams.swap(next);
+        s->finished = finish;
+    } catch (const std::bad_alloc &) {
+        return FLACGPU_ERR_UNSUPPORTED;
+    }
+    return FLACGPU_OK;
+}
+
 // one feed into copies of the streams; committed only when the records fit
 static int session_host_step(flacgpu_session_host *s, const uint8_t *const *data, const size_t *len, const uint8_t *flush,
                              bool finish, flacgpu_frame_record *records, size_t cap, flacgpu_raw_stream *raw,
@@ -63,6 +228,11 @@ static int session_host_step(flacgpu_session_host *s, const uint8_t *const *data
     if (!s || !total_frames || s->finished) return FLACGPU_ERR_INVALID_ARG;
     const uint32_t n = (uint32_t)s->streams.size();
     if (!finish && n && (!data || !len)) return FLACGPU_ERR_INVALID_ARG;
+    if (s->container) {
+        for (uint32_t i = 0; flush && i < n; i++)   // a container's sender knows no frame boundary
+            if (flush[i]) return FLACGPU_ERR_INVALID_ARG;
+        return container_host_step(s, data, len, finish, records, cap, raw, held_bytes, total_frames);
+    }
     try {
         std::vector<flacgpu_session_host::Stream> next(n);
         std::vector<flacgpu_frame_record> recs;

@@ -20,4 +20,11 @@ constexpr uint32_t kSessionMinW = 16, kSessionMaxW = 1u << 22;   // the bounds o
 // held.  final: the stream is flushed, h == L.
 size_t session_decide(const uint8_t *d, size_t L, bool final, uint32_t W, uint64_t base, uint32_t stream,
                       SessionCount &count, std::vector<flacgpu_frame_record> &out, uint64_t *elements);
+
+// The same for a stream of a container session in its frame phase (DESIGN.md 4b "Container sessions": the regular end
+// rule with STREAMINFO's `info` and `min_frame`, bounded by W): d[0] is the cursor.  Returns the walk: d[cursor, L) is
+// held, or (lost) dropped.  A record's sample rate and sample size are STREAMINFO's where its header defers to it.
+RegularWalk container_decide(const uint8_t *d, size_t L, bool final, uint32_t W, const flacgpu_stream_info &info,
+                             uint32_t min_frame, uint64_t base, uint32_t stream, std::vector<flacgpu_frame_record> &out,
+                             uint64_t *elements);
 }  // namespace flacenc

@@ -1,6 +1,8 @@
-// session.inc -- the two kernels of a decoder session (DESIGN.md 4b "Decoder sessions"): raw frame streams that arrive
-// chunk by chunk.  Included inside decode_many.hip's anonymous namespace, after frame_scan.inc (ScanSlot, ScanParams,
-// slot_of_block), gather.inc (kHeadBytes) and kernels/session_slots_rule.h.  Neither kernel has LDS, atomics or scratch:
+// session.inc -- the kernels of the decoder sessions (DESIGN.md 4b "Decoder sessions"): raw frame streams that arrive
+// chunk by chunk; behind them the two of a container session (whole .flac files; "Container sessions").  Included inside
+// decode_many.hip's anonymous namespace, after frame_scan.inc (ScanSlot, ScanParams, slot_of_block), gather.inc
+// (kHeadBytes, DevSource), kernels/session_slots_rule.h and kernels/meta_feed_rule.h.  No kernel here has LDS, atomics or
+// scratch:
 //   K_n1 k_session_slots  lane per 16-byte group of the batch buffer: slot = the stream's held tail (in the session's
 //                         other batch buffer) followed by its new chunk, zero tails and look-ahead included
 //   K_n2 k_link_session   lane per candidate: the raw end rule bounded by W = max_frame_bytes, with "not decided yet"
@@ -69,4 +71,63 @@ __global__ void __launch_bounds__(WG) k_link_session(ScanParams p, const Session
         }
     }
     p.link[i] = link;
+}
+
+// ---- container sessions (DESIGN.md 4b "Container sessions"): regular .flac streams chunk by chunk ----
+//   K_n3 k_link_container  lane per candidate: k_link's rule bounded by W, with "not decided yet"
+//   K_n4 k_meta_feed       lane per stream: the resumable metadata walk over a chunk where it lies
+// Neither has LDS, atomics or scratch.
+
+// K_n3: lane per candidate s of a slot of L bytes, whose candidates are the regular scan's (K_s1: every header that
+// parses).  k_link's rule -- the first later candidate q >= s + max(header_bytes + 2 + channels, min_frame), channels and
+// min_frame the slot's (STREAMINFO's), with s's blocking bit and CRC(s, q) == 0 -- with k_link_session's three changes:
+// q - s <= W; in a slot that is not final only the positions q <= L - kHeadBytes are judged (s behind that: LINK_HOLD, a
+// later candidate behind that ends nothing, the slot's end ends nothing) and s without an end is LINK_NONE only once
+// L - kHeadBytes >= s + W, else LINK_HOLD; a final slot's end is an end of input (LINK_END, within W).
+__global__ void __launch_bounds__(WG) k_link_container(ScanParams p, const SessionSlot *__restrict__ info) {
+    const uint32_t i = blockIdx.x * WG + threadIdx.x;
+    if (i >= p.n_cand) return;
+    const uint32_t s = p.cand_slot[i];
+    const ScanSlot sl = p.slots[s];
+    const SessionSlot si = info[s];
+    const uint32_t end = s + 1 < p.n_slots ? p.slot_cand0[s + 1] : p.n_cand;
+    const uint64_t pos = p.cand_pos[i];
+    const uint64_t judged = si.final ? sl.base + sl.len : sl.base + (sl.len >= kHeadBytes ? sl.len - kHeadBytes + 1 : 0);
+    if (pos >= judged) {
+        p.link[i] = LINK_HOLD;
+        return;
+    }
+    const uint32_t ci = p.cand_info[i];
+    const uint32_t blocking = ci >> 24, hb = (ci >> 16) & 0xFFu;
+    const uint64_t min_len = max(hb + 2u + sl.channels, sl.min_frame);
+    const uint32_t A = p.cand_crc[i];
+    int32_t link = LINK_NONE;
+    for (uint32_t j = i + 1; j < end; j++) {
+        const uint64_t q = p.cand_pos[j];
+        if (q >= judged || q - pos > si.W) break;   // ascending: nothing behind it can end s either
+        if (p.cand_crc[j] != A || (p.cand_info[j] >> 24) != blocking || q - pos < min_len) continue;
+        link = (int32_t)j;
+        break;
+    }
+    if (link == LINK_NONE) {
+        const uint64_t left = sl.base + sl.len - pos;
+        if (si.final) {
+            if (left >= 2 && left <= si.W && p.slot_pend[s] == A) link = LINK_END;
+        } else if (left < (uint64_t)si.W + kHeadBytes) {
+            link = LINK_HOLD;
+        }
+    }
+    p.link[i] = link;
+}
+
+// K_n4: lane per stream that is still in its metadata.  state[i] is the stream's walk so far; the lane runs meta_feed
+// (kernels/meta_feed_rule.h) over the stream's chunk and leaves the state and the count of consumed bytes.  A serial
+// walk of a few dependent byte loads per block -- a block that is no STREAMINFO is passed by count -- and the streams
+// run side by side.  Reads bytes of [data, data + len) alone; a null pointer or a zero length reads nothing.
+__global__ void __launch_bounds__(64) k_meta_feed(const DevSource *__restrict__ src, uint32_t n, MetaFeed *state,
+                                                  uint64_t *__restrict__ consumed) {
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    // on the row itself: its byte arrays are indexed by the walk's own counts, which a copy in registers cannot be
+    consumed[i] = src[i].len ? meta_feed(state[i], src[i].data, src[i].len) : 0;
 }

@@ -269,4 +269,11 @@ struct PlaceRun;
 namespace flacgpu_k {
 int launch_place_runs(const PlaceRun *d_runs, uint32_t n_runs, uint64_t n_groups, hipStream_t st);
 }  // namespace flacgpu_k
+// md5_chain.hip: flacgpu_md5_chains_update for pieces of different sample widths (a container session's streams):
+// width[p] (1..4) is piece p's; the pieces go up in one table grouped by width and k_md5_chain is launched once per
+// width that occurs.  The caller vouches for what update checks (one piece per chain, chain < n_chains, count <= 2^58).
+namespace flacgpu_k {
+int md5_chains_update_widths(flacgpu_md5_chains *c, const int32_t *d_samples, const flacgpu_md5_piece *pieces,
+                             const uint32_t *width, uint32_t n_pieces, hipStream_t st);
+}  // namespace flacgpu_k
 #endif

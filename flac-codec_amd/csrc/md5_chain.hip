@@ -131,6 +131,33 @@ int flacgpu_md5_chains_update(flacgpu_md5_chains *c, const int32_t *d_samples, c
     return FLACGPU_OK;
 }
 
+int flacgpu_k::md5_chains_update_widths(flacgpu_md5_chains *c, const int32_t *d_samples, const flacgpu_md5_piece *pieces,
+                                        const uint32_t *width, uint32_t n_pieces, hipStream_t st) {
+    if (!c || !n_pieces) return FLACGPU_OK;
+    if (n_pieces > c->n || !pieces || !width || !d_samples) return FLACGPU_ERR_INVALID_ARG;
+    uint32_t first[6] = {0, 0, 0, 0, 0, 0};   // pieces of width w: [first[w], first[w + 1]) of the table
+    for (uint32_t p = 0; p < n_pieces; p++) {
+        if (width[p] < 1 || width[p] > 4 || pieces[p].chain >= c->n) return FLACGPU_ERR_INVALID_ARG;
+        first[width[p] + 1]++;
+    }
+    for (uint32_t w = 1; w < 6; w++) first[w] += first[w - 1];
+    DeviceGuard guard(c->device);
+    if (c->table_pending) HIP_TRY(hipEventSynchronize(c->table_up));   // the pinned table is still on its way up
+    c->table_pending = false;
+    uint32_t at[5] = {0, first[1], first[2], first[3], first[4]};
+    for (uint32_t p = 0; p < n_pieces; p++) c->pieces_host[at[width[p]]++] = pieces[p];
+    HIP_TRY(hipMemcpyAsync(c->pieces_dev, c->pieces_host, sizeof(flacgpu_md5_piece) * (size_t)n_pieces, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(c->table_up, st));
+    c->table_pending = true;
+    for (uint32_t w = 1; w <= 4; w++) {
+        const uint32_t count = first[w + 1] - first[w];
+        if (count) hipLaunchKernelGGL(k_md5_chain, dim3(count), dim3(64), 0, st, d_samples, c->pieces_dev + first[w], c->state, w);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->fed, st));
+    return FLACGPU_OK;
+}
+
 int flacgpu_md5_chains_final(flacgpu_md5_chains *c, uint8_t *md5_out) {
     if (!c || (c->n && !md5_out)) return FLACGPU_ERR_INVALID_ARG;
     if (!c->n) return FLACGPU_OK;

@@ -174,3 +174,47 @@ class FlacChunkReader:
 
     def close(self):
         self._session.close()
+
+
+class FlacFileChunkReader:
+    """One regular .flac file that arrives in pieces cut anywhere -- inside the marker, the metadata or a frame --, over
+    a container gpu.DecoderSession (DESIGN.md 4b "Container sessions").  feed(data) returns the PCM the bytes so far
+    decide, an int32 array [samples, channels] (no row while the metadata is under way; a frame comes out once the header
+    behind it has arrived); finish() returns the last samples and settles `info` and `md5_ok`, what `flac -t` would say.
+    No frame may be longer than max_frame_bytes (16 .. 2^22).  Once the stream loses synchronisation nothing more is
+    decoded (info.bad_frames is 1 after finish)."""
+
+    def __init__(self, device=-1, max_frame_bytes=1 << 20):
+        self._session = gpu.DecoderSession(1, max_frame_bytes, device, container=True)
+        self.info = None      # the file's StreamInfo: STREAMINFO's fields once the first frame is out, all of it after finish
+        self.md5_ok = None    # after finish: True / False, None when STREAMINFO holds no MD5 or the file is refused
+        self.rc = None        # after finish: 0, or what the one-shot decode returns for a file it refuses
+
+    def _pcm(self):
+        _, streams = self._session.decode(out="host", verify_md5=True)
+        s = streams[0]
+        if s.rc:
+            return np.zeros((0, self.info.channels if self.info else 0), dtype=np.int32)
+        if self.info is None:
+            self.info = s.info
+        return s.pcm.copy()
+
+    def feed(self, data):
+        self._session.feed([data])
+        return self._pcm()
+
+    def finish(self):
+        self._session.finish()
+        pcm = self._pcm()
+        v = self._session.verdict()[0]
+        self.rc, self.info = v.rc, v.info
+        self.md5_ok = {0: False, 1: True}.get(v.info.md5_status) if v.rc == 0 else None
+        return pcm
+
+    @property
+    def pending(self):
+        """Bytes fed and not decided yet."""
+        return self._session.pending()[0][0]
+
+    def close(self):
+        self._session.close()

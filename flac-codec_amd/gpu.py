@@ -709,15 +709,26 @@ class DecoderSession:
     """flacgpu_decoder_session: `n_streams` raw frame streams fed chunk by chunk, the chunks cut anywhere (DESIGN.md 4b
     "Decoder sessions").  No frame is longer than `max_frame_bytes` (16 .. 2^22).  The bytes that cannot be judged yet
     stay in device memory between feeds.  `decoder` is the session's own Decoder: after a feed every decode call works on
-    it, over that feed's frames.  Not thread-safe."""
+    it, over that feed's frames.  Not thread-safe.
 
-    def __init__(self, n_streams, max_frame_bytes, device=-1):
+    container=True opens a CONTAINER session (DESIGN.md 4b "Container sessions"): the streams are regular .flac files --
+    marker, metadata chain, frames -- whose metadata is walked across feeds and whose frames are decided by the regular
+    rule with STREAMINFO's values.  After a feed the decoder stands as Decoder.scan leaves it (decode, decode_as and
+    decode_windows work; feed and finish return no frame records); the first decode of a feed with MD5 hashes its samples
+    into the session's chains, and verdict() gives every stream's record as the one-shot decode gives it.  flush is not
+    taken."""
+
+    def __init__(self, n_streams, max_frame_bytes, device=-1, container=False):
         self._h = None
         L = _lib.lib()
         h = C.c_void_p()
-        rc = L.flacgpu_decoder_session_open(device, n_streams, max_frame_bytes, 0, C.byref(h))
+        self.container = bool(container)
+        if container:
+            rc = L.flacgpu_decoder_session_open_container(device, n_streams, max_frame_bytes, C.byref(h))
+        else:
+            rc = L.flacgpu_decoder_session_open(device, n_streams, max_frame_bytes, 0, C.byref(h))
         if rc:
-            raise GpuError(rc, "flacgpu_decoder_session_open")
+            raise GpuError(rc, "flacgpu_decoder_session_open_container" if container else "flacgpu_decoder_session_open")
         self._h = h
         self.n_streams = n_streams
         self.decoder = _SessionDecoder(C.c_void_p(L.flacgpu_decoder_session_decoder(h)), device)
@@ -733,10 +744,13 @@ class DecoderSession:
     def __del__(self):
         self.close()
 
-    def _done(self, rc, who, n_frames, elements):
+    def _done(self, rc, who, n_frames, elements, total):
         if rc:
             raise GpuError(rc, who)
         dec = self.decoder
+        self.n_frames, self.total = int(n_frames.value), int(total.value)   # of this feed: frames; decode's int32 samples
+        if self.container:   # a batch of regular streams: no frame records
+            return self.frames, list(self._raw)[:self.n_streams]
         frames = np.zeros(n_frames.value, dtype=FRAME_DTYPE)
         rc = _lib.lib().flacgpu_decoder_frame_records(dec._h, frames.ctypes.data_as(C.POINTER(_lib.FrameRecord)), frames.size)
         if rc:
@@ -779,7 +793,7 @@ class DecoderSession:
                                                        C.byref(n_frames), C.byref(elements), C.byref(total))
             who = "flacgpu_decoder_session_feed_device"
         del keep
-        return self._done(rc, who, n_frames, elements)
+        return self._done(rc, who, n_frames, elements, total)
 
     def finish(self):
         """Flushes every stream: (frames, raw) as feed; raw is then every whole stream's summary.  No feed may follow."""
@@ -787,7 +801,47 @@ class DecoderSession:
         n_frames, elements, total = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
         rc = _lib.lib().flacgpu_decoder_session_finish(self._h, self.records, self._raw, C.byref(n_frames),
                                                        C.byref(elements), C.byref(total))
-        return self._done(rc, "flacgpu_decoder_session_finish", n_frames, elements)
+        return self._done(rc, "flacgpu_decoder_session_finish", n_frames, elements, total)
+
+    def decode(self, out="device", verify_md5=True):
+        """flacgpu_decoder_decode of the last feed's batch: (flat int32, streams) as decode_many gives them -- the
+        streams with a frame decided in this feed, back to back.  In a container session the first call after a feed with
+        verify_md5=True is the one that hashes the feed's samples into the session's MD5 chains."""
+        if out not in ("device", "host"):
+            raise ValueError("out must be 'device' or 'host'")
+        dec, total = self.decoder, self.total
+        flags = 0 if verify_md5 else _lib.DECODE_NO_MD5
+        recs = (_lib.DecodedStream * max(self.n_streams, 1))()
+        if out == "device":
+            import torch
+
+            flat = torch.empty(total, dtype=torch.int32, device=f"cuda:{dec.device_index}")
+            torch.cuda.synchronize(dec.device_index)
+            dec.decode(flat.data_ptr() if total else None, total, flags | _lib.DECODE_OUT_DEVICE, recs)
+        else:
+            flat = np.empty(total, dtype=np.int32)
+            dec.decode(flat.ctypes.data if total else None, total, flags, recs)
+        streams = []
+        for i in range(self.n_streams):
+            r = recs[i]
+            info = _lib.StreamInfo()
+            C.memmove(C.byref(info), C.byref(r.info), C.sizeof(info))
+            pcm = None
+            if r.rc == 0:
+                ch = max(info.channels, 1)
+                pcm = flat[r.out_offset:r.out_offset + info.decoded_samples * ch].reshape(-1, ch)
+            streams.append(DecodedStream(r.rc, info, r.out_offset, pcm))
+        return flat, streams
+
+    def verdict(self):
+        """flacgpu_decoder_session_verdict, once, after finish and the decode that follows it: the list of every
+        stream's _lib.DecodedStream as the one-shot scan + decode of the whole file gives it (rc, STREAMINFO, frames,
+        decoded_samples, bad_frames, bad_crc16, decoded_md5, md5_status; 3: a feed's frames were never hashed)."""
+        out = (_lib.DecodedStream * max(self.n_streams, 1))()
+        rc = _lib.lib().flacgpu_decoder_session_verdict(self._h, out)
+        if rc:
+            raise GpuError(rc, "flacgpu_decoder_session_verdict")
+        return list(out)[:self.n_streams]
 
     def pending(self):
         """(held bytes per stream, bytes fed to the session so far)."""

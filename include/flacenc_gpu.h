@@ -916,6 +916,58 @@ void flacgpu_session_host_close(flacgpu_session_host *s);
 int flacgpu_session_slots_host(const flacgpu_session_slot_src *srcs, uint32_t n_slots, uint8_t *out, size_t cap,
                                uint64_t *bytes);
 
+/* ---- batch decoder: container sessions -- whole .flac files chunk by chunk, MD5 across feeds ---------------------------
+ * A second kind of session, chosen by its entry point: n_streams REGULAR .flac streams (fLaC marker, metadata chain,
+ * frames), each fed in chunks cut anywhere -- inside the marker, a block header, STREAMINFO or a frame.  DESIGN.md 4b
+ * "Container sessions" states the rule; in short, per stream:
+ *   metadata  walked across feeds by the resumable form of the metadata walk (csrc/kernels/meta_feed_rule.h); nothing of
+ *             the chain is buffered but the STREAMINFO block.  A wrong marker or an unusable STREAMINFO refuses the stream
+ *             for good: its rc is the one-shot call's, its later bytes are counted and ignored, the other streams go on.
+ *   frames    from the first byte behind the metadata the frame at the cursor s ends at the FIRST judged
+ *             q >= s + max(header_bytes + 2 + channels, min_frame) where a header parses (the regular candidate test:
+ *             headers that leave rate or sample size to STREAMINFO included) with s's blocking bit, CRC(s, q) == 0 and
+ *             q - s <= W; at finish also at the input's end L when its last two bytes are the frame's CRC-16 and
+ *             L - s <= W.  q is judged once 16 bytes follow it; s is decided once such a q exists or L - 16 >= s + W.
+ *             A cursor that is no candidate, or a frame without an end, LOSES the stream: bad_frames 1, nothing from s on
+ *             is kept, every later byte is dropped and counted as skipped.  There is no resynchronisation.
+ *   no flush  `flush` must be NULL or all zero (FLACGPU_ERR_INVALID_ARG otherwise, nothing changes); finish alone ends
+ *             the input.
+ * With W no smaller than the longest frame the one-shot scan links, the frames, the samples and the final record are those
+ * of flacgpu_decoder_scan + flacgpu_decoder_decode on the concatenation, however the chunks were cut.
+ * After a feed the session's decoder is in the state flacgpu_decoder_scan leaves it in, for a batch whose stream i is
+ * "this STREAMINFO plus the frames decided in this feed": decode, decode_as and decode_windows work on it; decode_frames,
+ * frame_records, plan_timeline and decode_timeline are refused as after scan.  streams[i]: rc 0, `info` from STREAMINFO
+ * with this feed's frames / decoded_samples, md5_status 3; a stream without a frame in this feed is a zero row with rc
+ * FLACGPU_ERR_INVALID_ARG.  raw[i] (may be NULL): cumulative frames and skipped_bytes (bytes dropped after lost
+ * synchronisation, or all bytes of a refused stream), gaps 0 or 1, uniform 1 once STREAMINFO is accepted.
+ * total_frames / total_elements count this feed's frames and their samples x channels.
+ * MD5: the session owns one resumable MD5 chain per stream.  The FIRST decode or decode_as after a feed without
+ * FLACGPU_DECODE_NO_MD5 appends that feed's samples to the chains (on the decoder's stream, behind the kernel that wrote
+ * them) and adds the call's bad_frames / bad_crc16 to the session's counts; later decodes of the same feed append nothing.
+ * A feed that decided frames for a stream and was never hashed breaks that stream's chain: its final md5_status is 3.
+ *   verdict   once, after finish and the decode that follows it: pads the chains and fills, per stream, the record the
+ *             one-shot decode gives (rc, STREAMINFO fields, cumulative frames, decoded_samples, bad_frames, bad_crc16,
+ *             decoded_md5, md5_status: 1 equal, 0 different, 2 STREAMINFO all zero, 3 chain broken).  Before finish, or
+ *             twice: FLACGPU_ERR_INVALID_ARG, nothing written.  On a raw session: FLACGPU_ERR_INVALID_ARG.
+ *   session_host_open_container  the rule as plain host code; feed / finish / close are session_host_*'s.  Records carry
+ *             byte_offset from the stream's first byte, and STREAMINFO's rate and sample size where the header defers.
+ *             raw[i].uniform && raw[i].gaps says the stream lost synchronisation.
+ *   meta_feed_*_host  the resumable metadata walk over host memory on a caller-owned state of 104 bytes: init; feed
+ *             (*consumed: the bytes of the chunk that belong to the metadata -- all of them until the block with the last
+ *             flag ends, 0 afterwards); result: what flacgpu_meta_walk_host gives for the total_bytes fed so far seen as
+ *             one input. */
+typedef struct {
+    uint64_t words[13];
+} flacgpu_meta_feed;
+int flacgpu_decoder_session_open_container(int device, uint32_t n_streams, uint32_t max_frame_bytes,
+                                           flacgpu_decoder_session **out);
+int flacgpu_decoder_session_verdict(flacgpu_decoder_session *s, flacgpu_decoded_stream *out);
+int flacgpu_session_host_open_container(uint32_t n_streams, uint32_t max_frame_bytes, flacgpu_session_host **out);
+void flacgpu_meta_feed_init_host(flacgpu_meta_feed *state);
+int flacgpu_meta_feed_host(flacgpu_meta_feed *state, const uint8_t *chunk, size_t len, size_t *consumed);
+int flacgpu_meta_feed_result_host(const flacgpu_meta_feed *state, uint64_t total_bytes, flacgpu_stream_info *info,
+                                  uint32_t *min_frame, uint64_t *frames_at);
+
 /* ---- batch decoder: raw frame streams on a timeline, lost frames zero-filled -----------------------------------------
  * The kept frames of every stream of a raw scan, each put where its coded number says it belongs; what no frame covers
  * is zero, and so is a frame that does not decode.  The rule (DESIGN.md 4b "Timeline"), for the records r_0 .. r_{m-1}

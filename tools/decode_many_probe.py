@@ -27,6 +27,9 @@ over flacgpu_decode_stream and the oracle's CPU decoder on one core; writes prof
     python tools/decode_many_probe.py --raw|--timeline --label parent --package-root DIR --parent-all-legs   (a parent that
                                              has every leg of the mode: each is then held to the parent's own spread of it)
     python tools/decode_many_probe.py --session [--out profiles/r22_decoder_session.json] [--reps 15]
+    python tools/decode_many_probe.py --session --container [--out profiles/r24_container_session.json] [--reps 15]
+                                             [--workloads clips,hour] [--hour-seconds N]   (container sessions: whole
+                                             .flac files in pieces, MD5 across feeds; see container_session's docstring)
 
 --timeline (flacgpu_decoder_decode_timeline): on the clips with the metadata stripped, float32, device output, handle
 warm, the wall time of scan_frames + decode_as (padded; the parent's call for such a batch) and of scan_frames +
@@ -661,6 +664,159 @@ def session(args):
     print(json.dumps(res, indent=1), flush=True)
 
 
+def container_session(args):
+    """The --session --container leg: container sessions (DESIGN.md 4b "Container sessions"), whole .flac files fed in
+    pieces with the MD5 taken across feeds.  (a) per-feed latency: 64 mono 16 kHz files, one 80 ms frame a feed, feed +
+    decode with MD5, beside a raw session over the same frames (feed + decode_frames) in the same process.  (b)
+    throughput: the workloads of --workloads (default clips,hour; --hour-seconds shortens the one-hour stream) in 1, 16
+    and 64 pieces with MD5 against one-shot scan + decode with and without MD5; the SHA-256 of the PCM in stream order
+    and the digests must be identical.  Median and min-max of --reps, sclk before and after each leg."""
+    import hashlib
+
+    import torch
+
+    from _pcm import synth_fast
+    from flac_codec_amd import _lib
+    from flac_codec_amd.encode import FlacSampleWriter, Options
+    from flac_codec_amd.gpu import Decoder, DecoderSession, scan_stream_host
+
+    res = {"tool": "tools/decode_many_probe.py --session --container", "build_id": _lib.build_id(), "reps": args.reps}
+
+    def leg(times, before):
+        return dict(_spread(times), sclk_mhz_before=before, sclk_mhz_after=_sclk_mhz())
+
+    # ---- (a) per-feed latency
+    n_streams, rate, packet, steps = 64, 16000, 1280, args.reps + 3
+    files = []
+    for k in range(16):
+        pcm = synth_fast(1200 + k, 1, 16, packet * (steps + 1))
+        w = FlacSampleWriter(None, Options.default().block_size(packet), rate, 16, 1, pcm.size)
+        w.write(pcm)
+        w.finalize()
+        files.append(w.getvalue())
+        w.close()
+    cuts = []   # per distinct file: chunk k ends behind frame k (the first holds the metadata too)
+    for b in files:
+        off = [int(v) for v in scan_stream_host(b)[1]]
+        cuts.append(([0] + off[1:steps + 1], off[1:steps + 2], off[0]))
+    bound = max(e - s for c in cuts for s, e in zip([c[2]] + c[1][:-1], c[1]))
+    res["latency"] = {"workload": "64 files, 16 kHz mono 16-bit, one frame of 80 ms (1280 samples) per file per feed",
+                      "max_frame_bytes": bound, "legs": {}}
+    for name in ("container_feed_decode_md5", "raw_feed_decode_frames"):
+        container = name.startswith("container")
+        ses = DecoderSession(n_streams, bound, device=0, container=container)
+        out = torch.empty(n_streams * packet, dtype=torch.int32, device="cuda:0")
+        recs = (_lib.DecodedStream * n_streams)()
+        torch.cuda.synchronize()
+        feed_t, decode_t, both_t, before, frames = [], [], [], None, 0
+        for step in range(steps):
+            if step == 3:
+                before = _sclk_mhz()   # three feeds warm: buffers grown, code loaded
+            chunks = []
+            for i in range(n_streams):
+                starts, ends, first = cuts[i % 16]
+                a = starts[step] if container or step else first   # the raw session gets the frames alone
+                chunks.append(files[i % 16][a:ends[step]])
+            t0 = time.perf_counter()
+            fr, _ = ses.feed(chunks)
+            t1 = time.perf_counter()
+            if container:
+                ses.decoder.decode(out.data_ptr() if ses.total else None, ses.total, _lib.DECODE_OUT_DEVICE, recs)
+                frames += ses.n_frames
+            else:
+                ses.decoder.decode_frames(out.data_ptr() if len(fr) else None, out.numel() if len(fr) else 0,
+                                          _lib.DECODE_OUT_DEVICE, fr)
+                frames += len(fr)
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            if step >= 3:
+                feed_t.append(t1 - t0)
+                decode_t.append(t2 - t1)
+                both_t.append(t2 - t0)
+        assert frames == n_streams * (steps - 1), frames   # without flush a frame comes out one feed late
+        res["latency"]["legs"][name] = {"feed_plus_decode": leg(both_t, before), "feed": dict(_spread(feed_t)),
+                                        "decode": dict(_spread(decode_t)), "frames": frames}
+        ses.close()   # (the files' last frame was never fed: no verdict is asked for)
+
+    # ---- (b) throughput
+    res["throughput"] = {}
+    for wname in args.workloads.split(","):
+        if wname == "hour" and args.hour_seconds:
+            WORKLOADS["hour"] = (1, 1, args.hour_seconds, 48000, 2, 24)
+        blobs = make_blobs(wname)
+        n = len(blobs)
+        dec = Decoder(0)
+        legs = {}
+        one = {}
+        for md5 in (False, True):
+            flags = _lib.DECODE_OUT_DEVICE | (0 if md5 else _lib.DECODE_NO_MD5)
+            recs, total = dec.scan(blobs)
+            out = torch.empty(total, dtype=torch.int32, device="cuda:0")
+            torch.cuda.synchronize()
+            dec.decode(out.data_ptr(), total, flags, recs)   # warm
+            before, times = _sclk_mhz(), []
+            for _ in range(args.reps if not (md5 and wname == "hour") else min(args.reps, 3)):
+                t0 = time.perf_counter()
+                recs, total = dec.scan(blobs)
+                dec.decode(out.data_ptr(), total, flags, recs)
+                times.append(time.perf_counter() - t0)
+            legs["one_shot_scan_decode" + ("_md5" if md5 else "_no_md5")] = leg(times, before)
+            if md5:
+                host = out.cpu().numpy()
+                sha = hashlib.sha256()
+                for r in recs[:n]:
+                    sha.update(host[r.out_offset:r.out_offset + r.info.decoded_samples * r.info.channels].tobytes())
+                one = {"pcm_sha256": sha.hexdigest(), "digests": [bytes(r.info.decoded_md5).hex() for r in recs[:n]],
+                       "frames": [r.info.frames for r in recs[:n]]}
+                assert all(r.rc == 0 and r.info.md5_status == 1 for r in recs[:n])
+                del host
+        dec.close()
+        bound = max(int(np.diff(np.append(scan_stream_host(b)[1], len(b)).astype(np.int64)).max()) for b in set(blobs))
+        for pieces in (1, 16, 64):
+            cut = [[b[len(b) * p // pieces:len(b) * (p + 1) // pieces] for p in range(pieces)] for b in blobs]
+
+            def run(check):
+                ses = DecoderSession(n, bound, device=0, container=True)
+                recs = (_lib.DecodedStream * n)()
+                parts = [[] for _ in range(n)]
+                for p in range(pieces + 1):
+                    ses.finish() if p == pieces else ses.feed([c[p] for c in cut])
+                    ses.decoder.decode(out.data_ptr() if ses.total else None, ses.total, _lib.DECODE_OUT_DEVICE, recs)
+                    if check and ses.total:
+                        host = out[:ses.total].cpu().numpy()
+                        for i in range(n):
+                            if recs[i].rc == 0:
+                                a = recs[i].out_offset
+                                parts[i].append(host[a:a + recs[i].info.decoded_samples * recs[i].info.channels].copy())
+                verdict = ses.verdict()
+                ses.close()
+                return parts, verdict
+
+            parts, verdict = run(True)   # warm, and the PCM and the digests against the one-shot's
+            sha = hashlib.sha256()
+            for per in parts:
+                for a in per:
+                    sha.update(a.tobytes())
+            assert sha.hexdigest() == one["pcm_sha256"], "the session's PCM differs from the one-shot's"
+            assert [bytes(v.info.decoded_md5).hex() for v in verdict] == one["digests"]
+            assert all(v.rc == 0 and v.info.md5_status == 1 for v in verdict) and [v.info.frames for v in verdict] == one["frames"]
+            del parts
+            before, times = _sclk_mhz(), []
+            for _ in range(args.reps):
+                t0 = time.perf_counter()
+                run(False)
+                times.append(time.perf_counter() - t0)
+            legs[f"container_session_{pieces}_pieces_md5"] = dict(leg(times, before), identical_pcm_and_digests=True)
+        n_s, _, secs, rate_w, ch, bps = WORKLOADS[wname]
+        res["throughput"][wname] = {"workload": f"{n_s} x {secs} s, {rate_w} Hz, {ch} ch, {bps} bit", "streams": n,
+                                    "bytes": sum(len(b) for b in blobs), "frames": sum(one["frames"]),
+                                    "max_frame_bytes": bound, "pcm_sha256": one["pcm_sha256"], "legs": legs}
+        del blobs, out
+        with open(args.out, "w") as f:   # after every workload: a later one may run out of time
+            json.dump(res, f, indent=1)
+    print(json.dumps(res, indent=1), flush=True)
+
+
 def timeline(args):
     """The --timeline leg (see the module docstring)."""
     import hashlib
@@ -1010,6 +1166,10 @@ def main():
                     help="with --raw: add the FLACGPU_SCAN_SPECULATIVE leg, profiles/r14_speculative.json")
     ap.add_argument("--timeline", action="store_true", help="the timeline leg: profiles/r16_timeline.json")
     ap.add_argument("--session", action="store_true", help="the decoder session leg: profiles/r22_decoder_session.json")
+    ap.add_argument("--container", action="store_true",
+                    help="with --session: the container session leg, profiles/r24_container_session.json")
+    ap.add_argument("--hour-seconds", type=int, default=0,
+                    help="--session --container: the length of the 'hour' stream in seconds (0: the whole hour)")
     ap.add_argument("--shrink", type=int, default=1, help="--s24: divide the clip count")
     ap.add_argument("--label", default="this", help="--formats: the run's name in the file (parent: the default int32 "
                     "leg only; any other name: every leg)")
@@ -1027,6 +1187,7 @@ def main():
     if not args.out:
         args.out = os.path.join(ROOT, "profiles", "r15_device_input.json" if args.device_input else
                                 "r16_timeline.json" if args.timeline else
+                                "r24_container_session.json" if args.session and args.container else
                                 "r22_decoder_session.json" if args.session else
                                 "r14_speculative.json" if args.raw and args.speculative else
                                 "r13_raw_frames.json" if args.raw else
@@ -1046,6 +1207,10 @@ def main():
         return device_input(args)
     if args.timeline:
         return timeline(args)
+    if args.session and args.container:
+        if args.workloads == "clips,tracks,hour":
+            args.workloads = "clips,hour"
+        return container_session(args)
     if args.session:
         return session(args)
     if args.raw:
