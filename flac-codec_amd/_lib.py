@@ -237,6 +237,13 @@ class GpuStats(C.Structure):
     ]
 
 
+class LpcParams(C.Structure):
+    """K4's record per (frame, candidate) (csrc/kernels/types.h LpcParams; flacgpu_device_buffer 7).  status: 0 ok,
+    1 InsufficientLpcSamples / no candidate, 2 NoBestLpcOrder, 3 ZeroLpCoefficients, 4 LpNegativeShiftError."""
+    _fields_ = [("status", C.c_int32), ("order", C.c_uint8), ("precision", C.c_uint8), ("shift", C.c_uint8),
+                ("est8", C.c_uint8), ("qlp", C.c_int32 * 32)]
+
+
 _lib = None
 
 
@@ -281,6 +288,11 @@ def _load():
     L.flacgpu_resolve.argtypes = [vp]
     L.flacgpu_device_buffer.argtypes = [vp, C.c_int]
     L.flacgpu_device_buffer.restype = vp
+    # test hooks (not in the public header): K4 alone on rows of autocorrelations, and its host restatement on one row
+    u32p = C.POINTER(C.c_uint32)
+    L.flacgpu_test_lpc_rows.argtypes = [vp, C.POINTER(C.c_double), C.c_uint32, u32p, u32p, C.c_uint32, vp, u32p, u32p]
+    L.flacenc_lpc_host_row.argtypes = [C.POINTER(C.c_double), C.c_uint32, C.c_uint32, C.c_uint32, vp]
+    L.flacenc_lpc_host_row.restype = None
     L.flacgpu_set_timing.argtypes = [vp, C.c_int]
     L.flacgpu_get_kernel_ms.argtypes = [vp, C.POINTER(C.c_float * N_KERNELS)]
     L.flacgpu_pack_device.argtypes = [vp, C.c_uint64, C.c_uint32, vp]

@@ -2218,8 +2218,72 @@ void *flacgpu_device_buffer(flacgpu_ctx *c, int which) {
     case 4: return c->d_packed;
     case 5: return c->d_frame_off;
     case 6: return c->d_ac;
+    case 7: return (ctx_sync(c) == FLACGPU_OK && resolve_order_ties(c) == FLACGPU_OK) ? c->d_lpc : nullptr;
     default: return nullptr;
     }
+}
+
+// Test hook (tests/test_gpu_lpc_edges.py; not in the public header): K4 alone on the caller's autocorrelation rows, through
+// launch_lpc with this context's max_lpc_order, log2 table and tie band -- one candidate per "frame", every row with a
+// length and an effective bps of its own (Params::frame_n).  ac: [rows][ld] doubles, lags 0 .. max_lpc_order in front
+// (max_lpc_order < ld <= 36).  lpc_out: [rows] LpcParams records as the kernel left them (136 bytes each, zeroed before the
+// launch; no host re-decision).  tie_rows: [rows], the first counters[1] entries are the rows K4 listed for the host.
+// counters[3]: lpc_failed, order_ties, log2_edge of this launch.  Works on buffers of its own: the context's last batch
+// stays as it is.
+int flacgpu_test_lpc_rows(flacgpu_ctx *c, const double *ac, uint32_t ld, const uint32_t *n, const uint32_t *bps, uint32_t rows,
+                          void *lpc_out, uint32_t *tie_rows, uint32_t *counters) {
+    if (!c || !ac || !n || !bps || !lpc_out || !tie_rows || !counters || rows == 0 || rows > (1u << 20) ||
+        c->opts.max_lpc_order == 0 || ld <= c->opts.max_lpc_order || ld > (uint32_t)AC_LD)
+        return FLACGPU_ERR_INVALID_ARG;
+    CTX_GUARD(c);
+    if (int rc = ctx_sync(c)) return rc;
+    hipStream_t st = c->own_stream;
+    std::vector<double> h_ac((size_t)rows * AC_LD, 0.0);
+    std::vector<CandInfo> h_ci(rows);
+    for (uint32_t r = 0; r < rows; r++) {
+        memcpy(&h_ac[(size_t)r * AC_LD], ac + (size_t)r * ld, sizeof(double) * ld);
+        h_ci[r] = CandInfo{1, 0, (uint8_t)bps[r], 0};
+    }
+    double *d_ac = nullptr;
+    CandInfo *d_ci = nullptr;
+    LpcParams *d_lpc = nullptr;
+    uint32_t *d_n = nullptr, *d_ties = nullptr, *d_stats = nullptr;
+    auto run = [&]() -> int {
+        HIP_TRY(hipMalloc((void **)&d_ac, sizeof(double) * h_ac.size()));
+        HIP_TRY(hipMalloc((void **)&d_ci, sizeof(CandInfo) * rows));
+        HIP_TRY(hipMalloc((void **)&d_lpc, sizeof(LpcParams) * rows));
+        HIP_TRY(hipMalloc((void **)&d_n, sizeof(uint32_t) * rows));
+        HIP_TRY(hipMalloc((void **)&d_ties, sizeof(uint32_t) * rows));
+        HIP_TRY(hipMalloc((void **)&d_stats, sizeof(uint32_t) * 4));
+        HIP_TRY(hipMemcpyAsync(d_ac, h_ac.data(), sizeof(double) * h_ac.size(), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_ci, h_ci.data(), sizeof(CandInfo) * rows, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_n, n, sizeof(uint32_t) * rows, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(d_lpc, 0, sizeof(LpcParams) * rows, st));
+        HIP_TRY(hipMemsetAsync(d_ties, 0xFF, sizeof(uint32_t) * rows, st));
+        HIP_TRY(hipMemsetAsync(d_stats, 0, sizeof(uint32_t) * 4, st));
+        Params p;
+        fill_params(c, rows, c->opts.block_size, p);
+        p.ncand = 1;
+        p.frame_n = d_n;
+        p.cinfo = d_ci;
+        p.ac = d_ac;
+        p.lpc = d_lpc;
+        p.stats = d_stats;
+        p.tie_list = d_ties;
+        p.tie_cap = rows;
+        launch_lpc(p, (rows + 63u) / 64u, st);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(lpc_out, d_lpc, sizeof(LpcParams) * rows, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(tie_rows, d_ties, sizeof(uint32_t) * rows, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(counters, d_stats, sizeof(uint32_t) * 3, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return FLACGPU_OK;
+    };
+    const int rc = run();
+    if (rc != FLACGPU_OK) (void)hipStreamSynchronize(st);
+    (void)hipFree(d_ac); (void)hipFree(d_ci); (void)hipFree(d_lpc);
+    (void)hipFree(d_n); (void)hipFree(d_ties); (void)hipFree(d_stats);
+    return rc;
 }
 
 // Diagnostic: of the last batch's subframes, how many k_cand64p handed to k_frame64 with their residual (Params::hand_meta).

@@ -115,3 +115,9 @@ void lpc_from_autocorr(const double *ac, uint32_t L, uint32_t n, uint32_t bps, H
 }
 
 }  // namespace flacenc
+
+// Test hook (tests/_lpc_edge_matrix.py; not in the public header, needs no device): lpc_from_autocorr on one row.
+// ac[0..=max_order] (max_order 1..32); out: one HostLpc record (136 bytes).
+extern "C" void flacenc_lpc_host_row(const double *ac, uint32_t max_order, uint32_t n, uint32_t bps, void *out) {
+    flacenc::lpc_from_autocorr(ac, max_order, n, bps, static_cast<flacenc::HostLpc *>(out));
+}

@@ -12,6 +12,11 @@ from ._lib import FramePlan, GpuOptions, GpuStats, SubframePlan
 
 LAYOUT_INTERLEAVED, LAYOUT_PLANAR = 0, 1
 
+# _lib.LpcParams as a numpy record (GpuAnalyzer.lpc_params, test_lpc_rows)
+LPC_DTYPE = np.dtype([("status", "<i4"), ("order", "u1"), ("precision", "u1"), ("shift", "u1"), ("est8", "u1"),
+                      ("qlp", "<i4", (32,))])
+assert LPC_DTYPE.itemsize == C.sizeof(_lib.LpcParams)
+
 
 class GpuError(RuntimeError):
     def __init__(self, code, where):
@@ -346,6 +351,45 @@ class GpuAnalyzer:
 
     def device_buffer(self, which):
         return _lib.lib().flacgpu_device_buffer(self._h, which)
+
+    def candidates_per_frame(self):
+        """Candidate slots per frame: L, R, M, S for stereo below 32 bits, else one per channel."""
+        return 4 if self.channels == 2 and self.bits_per_sample < 32 else self.channels
+
+    def lpc_params(self):
+        """K4's records of the last analysis (flacgpu_device_buffer 7: after the host's re-decision of order ties), one
+        per (frame, candidate), as a structured array of LPC_DTYPE.  The fields behind a non-zero status are stale."""
+        out = np.zeros(self.last_frames * self.candidates_per_frame(), dtype=LPC_DTYPE)
+        src = self.device_buffer(7)
+        if not src:
+            raise GpuError(-1, "flacgpu_device_buffer(7)")
+        hip = C.CDLL("libamdhip64.so")
+        hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        rc = hip.hipMemcpy(out.ctypes.data, src, out.nbytes, 2)   # hipMemcpyDeviceToHost
+        if rc:
+            raise RuntimeError(f"hipMemcpy of the LPC records: HIP error {rc}")
+        return out
+
+    def test_lpc_rows(self, ac, n, bps):
+        """flacgpu_test_lpc_rows (a test hook): K4 alone, through the product's launcher for this context's max_lpc_order,
+        on rows of f64 autocorrelations ([rows][lags], lags 0 .. max_lpc_order in front, at most 36) with a length and an
+        effective bps per row.  Returns (records as K4 left them, LPC_DTYPE; the rows K4 listed as order ties;
+        [lpc_failed, order_ties, log2_edge] of the launch)."""
+        ac = np.ascontiguousarray(ac, dtype=np.float64)
+        rows, ld = ac.shape
+        n = np.ascontiguousarray(n, dtype=np.uint32)
+        bps = np.ascontiguousarray(bps, dtype=np.uint32)
+        assert n.shape == (rows,) and bps.shape == (rows,)
+        out = np.zeros(rows, dtype=LPC_DTYPE)
+        ties = np.zeros(rows, dtype=np.uint32)
+        counters = np.zeros(3, dtype=np.uint32)
+        u32p = C.POINTER(C.c_uint32)
+        rc = _lib.lib().flacgpu_test_lpc_rows(self._h, ac.ctypes.data_as(C.POINTER(C.c_double)), ld, n.ctypes.data_as(u32p),
+                                              bps.ctypes.data_as(u32p), rows, out.ctypes.data, ties.ctypes.data_as(u32p),
+                                              counters.ctypes.data_as(u32p))
+        if rc:
+            raise GpuError(rc, "flacgpu_test_lpc_rows")
+        return out, sorted(int(v) for v in ties[:min(int(counters[1]), rows)]), [int(v) for v in counters]
 
     def experiment_mfma_autocorr(self):
         """EXPERIMENT (not on the product path): f64-MFMA autocorrelation of the last batch.

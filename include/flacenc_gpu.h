@@ -201,7 +201,11 @@ int flacgpu_handed_subframes(flacgpu_ctx *ctx, uint32_t *handed, uint32_t *subfr
 /* Device pointers of the last analysis (for callers that chain further device work):
  * which: 0 frame plans, 1 subframe plans, 2 residuals, 3 planar pcm, 4 packed frame bytes,
  * 5 frame byte offsets (uint64[n_frames + 1]), 6 the autocorrelation of every candidate (double[n_frames * candidates][36]:
- * lags 0 .. max_lpc_order of the windowed samples, encode.rs:3403-3413 -- bit for bit the reference's sums). */
+ * lags 0 .. max_lpc_order of the windowed samples, encode.rs:3403-3413 -- bit for bit the reference's sums),
+ * 7 the LPC parameters of every candidate ([n_frames * candidates] records of 136 bytes: int32 status -- 0 ok, else the
+ * reference's error: 1 InsufficientLpcSamples (or no candidate / all zero), 2 NoBestLpcOrder, 3 ZeroLpCoefficients,
+ * 4 LpNegativeShiftError --, uint8 order, precision, shift, size hint, int32 qlp[32]; the fields behind a non-zero status
+ * are stale), handed out after what flacgpu_resolve re-decides (synchronous). */
 void *flacgpu_device_buffer(flacgpu_ctx *ctx, int which);
 /* The plans (0, 1) and the frame bytes / offsets (4, 5) an asynchronous call leaves in HBM are FINAL only after a resolving
  * entry point has run: flacgpu_fetch, flacgpu_fetch_frames, flacgpu_frames_ready, flacgpu_verify_device -- or this one, for
