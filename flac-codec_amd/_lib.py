@@ -171,6 +171,16 @@ class FrameRecord(C.Structure):
                 ("blocking", C.c_uint32), ("status", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class FrameAnalysis(C.Structure):
+    """flacgpu_frame_analysis: one frame of flacgpu_decoder_analyze (40 bytes)."""
+    _fields_ = [("row_offset", C.c_uint64), ("first_subframe", C.c_uint64), ("block_size", C.c_uint32),
+                ("header_bytes", C.c_uint32), ("status", C.c_uint32), ("assignment_code", C.c_uint32),
+                ("plan", FramePlan)]
+
+
+AN_WIDE, AN_PARTS_CLIPPED = 1, 2   # flacgpu_subframe_plan.reserved[0] of an analysed subframe
+
+
 class RawStream(C.Structure):
     """flacgpu_raw_stream: one input's summary of a raw frame scan (32 bytes)."""
     _fields_ = [("first_frame", C.c_uint64), ("skipped_bytes", C.c_uint64), ("frames", C.c_uint32),
@@ -372,6 +382,10 @@ def _load():
                                                 C.POINTER(C.c_uint32), q]
     L.flacgpu_decoder_frame_records.argtypes = [vp, C.POINTER(FrameRecord), C.c_size_t]
     L.flacgpu_decoder_decode_frames.argtypes = [vp, vp, C.c_size_t, C.c_uint32, C.POINTER(FrameRecord), C.c_size_t]
+    L.flacgpu_analyze_frame_host.argtypes = [C.c_char_p, C.c_size_t, C.c_uint32, C.POINTER(FrameAnalysis),
+                                             C.POINTER(SubframePlan), vp, C.c_size_t]
+    L.flacgpu_decoder_plan_analysis.argtypes = [vp, q, q, q]
+    L.flacgpu_decoder_analyze.argtypes = [vp, C.c_uint32, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t]
     L.flacgpu_timeline_host.argtypes = [C.POINTER(FrameRecord), C.c_size_t, C.POINTER(TimelineFrame), C.c_size_t,
                                         C.POINTER(TimelineResult)]
     L.flacgpu_timeline_piece_bytes.argtypes = []

@@ -6,6 +6,7 @@
 #include "kernels/types.h"
 #include "kernels/sample_types.h"
 #include "kernels/frame_extent.h"
+#include "kernels/frame_analysis.h"
 #include "kernels/meta_walk.h"
 #include "kernels/meta_feed_rule.h"
 #include "kernels/byte_shift.h"
@@ -32,6 +33,7 @@ namespace {
 #include "kernels/gather.inc"
 #include "kernels/session.inc"
 #include "kernels/decode_many.inc"
+#include "kernels/analyze_many.inc"
 
 constexpr uint32_t kSlotTail = 64;   // zero bytes behind every stream's region (at least)
 // k_scan_blocks reads 16 bytes of look-ahead behind a block, and k_scan_emit (slot_pend) and k_spec_end (the CRC test of
@@ -106,6 +108,9 @@ struct flacgpu_decoder {
     std::vector<ManyFrame> raw_tab;   // uploaded to raw_frames by the first decode_frames of the scan
     bool raw_tab_uploaded = false;
     DevBuf raw_frames;
+    // flacgpu_decoder_analyze: the scan's frame table with the analysis' own offsets, uploaded by the first call of a scan
+    DevBuf an_frames;
+    bool an_tab_uploaded = false;
     uint64_t raw_elements = 0, raw_scratch = 0;
     bool session = false;   // owned by a flacgpu_decoder_session: the scan calls and destroy are refused
     // a container session's decoder: decode / decode_as hash into the session's MD5 chains (decode_impl), not k_md5_many
@@ -343,6 +348,7 @@ int device_meta_walk(flacgpu_decoder *d, const uint8_t *const *data, const size_
 
 // The end of both scans: the frame table onto the device, the batch's sizes and its slots' streams into the handle.
 int finish_scan(flacgpu_decoder *d, SlotLayout &lay, uint64_t total, uint64_t scratch_total) {
+    d->an_tab_uploaded = false;
     if (!d->frame_tab.empty()) {
         if (int rc = d->frames.ensure(sizeof(ManyFrame) * d->frame_tab.size())) return rc;
         HIP_TRY(hipMemcpyAsync(d->frames.p, d->frame_tab.data(), sizeof(ManyFrame) * d->frame_tab.size(),
@@ -1137,6 +1143,91 @@ int decode_frames_impl(flacgpu_decoder *d, int32_t *out, uint32_t flags, flacgpu
     HIP_TRY(hipStreamSynchronize(d->st));
     memcpy(records, d->records.data(), sizeof(flacgpu_frame_record) * F);
     for (uint32_t f = 0; f < F; f++) records[f].status = pair_status(counts, f);
+    return FLACGPU_OK;
+}
+
+// ---- frame analysis (flacgpu_decoder_plan_analysis / flacgpu_decoder_analyze) ----
+// The frames an analysis covers: every kept frame of a raw scan, else the scan's frame table.
+const std::vector<ManyFrame> &analysis_table(const flacgpu_decoder *d) { return d->raw ? d->raw_tab : d->frame_tab; }
+struct AnalysisSizes {
+    uint64_t frames = 0, subframes = 0, rows = 0;
+};
+AnalysisSizes analysis_sizes(const flacgpu_decoder *d) {
+    AnalysisSizes z;
+    for (const ManyFrame &fr : analysis_table(d)) {
+        z.frames++;
+        z.subframes += fr.channels;
+        z.rows += (uint64_t)fr.channels * ((fr.n + 3u) & ~3u);
+    }
+    return z;
+}
+
+// flacgpu_decoder_analyze behind its argument checks.  The frame pass' table is the scan's with `slot` = the frame (so
+// that k_frame_crc's pair f is frame f's own), `scratch` = row_offset and `out` = first_subframe: the two prefix sums.
+// rows == nullptr: the records-only pass.
+int analyze_impl(flacgpu_decoder *d, uint32_t flags, flacgpu_frame_analysis *frames, flacgpu_subframe_plan *subframes,
+                 int32_t *rows, const AnalysisSizes &z) {
+    DeviceGuard guard(d->device);
+    const uint32_t F = (uint32_t)z.frames;
+    if (!F) return FLACGPU_OK;
+    if (!d->an_tab_uploaded) {
+        std::vector<ManyFrame> tab;
+        try {
+            tab = analysis_table(d);
+        } catch (const std::bad_alloc &) {
+            g_last_error = "flacgpu_decoder_analyze: out of host memory";
+            return FLACGPU_ERR_UNSUPPORTED;
+        }
+        uint64_t sub_at = 0, row_at = 0;
+        for (uint32_t f = 0; f < F; f++) {
+            ManyFrame &fr = tab[f];
+            fr.slot = f;
+            fr.out = sub_at;
+            fr.scratch = row_at;
+            sub_at += fr.channels;
+            row_at += (uint64_t)fr.channels * ((fr.n + 3u) & ~3u);
+        }
+        if (int rc = d->an_frames.ensure(sizeof(ManyFrame) * (size_t)F)) return rc;
+        HIP_TRY(hipMemcpyAsync(d->an_frames.p, tab.data(), sizeof(ManyFrame) * (size_t)F, hipMemcpyHostToDevice, d->st));
+        HIP_TRY(hipStreamSynchronize(d->st));   // the table leaves scope
+        d->an_tab_uploaded = true;
+    }
+    // host output: the three arrays are staged back to back in one buffer, each at a multiple of 16 bytes
+    const size_t fb = sizeof(flacgpu_frame_analysis) * (size_t)F, sb = sizeof(flacgpu_subframe_plan) * (size_t)z.subframes;
+    const size_t rb = rows ? 4 * (size_t)z.rows : 0;
+    const size_t s_at = (fb + 15) & ~(size_t)15, r_at = s_at + ((sb + 15) & ~(size_t)15);
+    const bool staged = !(flags & FLACGPU_DECODE_OUT_DEVICE);
+    flacgpu_frame_analysis *d_frames = frames;
+    flacgpu_subframe_plan *d_subs = subframes;
+    int32_t *d_rows = rows;
+    if (staged) {
+        if (int rc = d->out_stage.ensure(r_at + rb)) return rc;
+        uint8_t *base = d->out_stage.as<uint8_t>();
+        d_frames = reinterpret_cast<flacgpu_frame_analysis *>(base);
+        d_subs = reinterpret_cast<flacgpu_subframe_plan *>(base + s_at);
+        d_rows = rows ? reinterpret_cast<int32_t *>(base + r_at) : nullptr;
+    }
+    FramePass pass{d};
+    if (int rc = pass.open(d->an_frames.as<const ManyFrame>(), F, 0, F)) return rc;
+    HIP_TRY(hipMemsetAsync(d_subs, 0, sb, d->st));   // every entry a subframe does not use is 0
+    hipLaunchKernelGGL(k_frame_crc, dim3(F), dim3(64), 0, d->st, d->bytes.as<const uint8_t>(), pass.frames,
+                       d->counts.as<uint32_t>());
+    const uint32_t lanes = 32;   // as K_d1: every lane reads and writes cache lines of its own
+    if (rows)
+        hipLaunchKernelGGL(k_analyze_many<true>, dim3((F + lanes - 1) / lanes), dim3(lanes), 0, d->st,
+                           d->bytes.as<const uint32_t>(), pass.frames, F, d->counts.as<const uint32_t>(), d_frames, d_subs,
+                           d_rows);
+    else
+        hipLaunchKernelGGL(k_analyze_many<false>, dim3((F + lanes - 1) / lanes), dim3(lanes), 0, d->st,
+                           d->bytes.as<const uint32_t>(), pass.frames, F, d->counts.as<const uint32_t>(), d_frames, d_subs,
+                           d_rows);
+    HIP_TRY(hipGetLastError());
+    if (staged) {
+        HIP_TRY(hipMemcpyAsync(frames, d_frames, fb, hipMemcpyDeviceToHost, d->st));
+        HIP_TRY(hipMemcpyAsync(subframes, d_subs, sb, hipMemcpyDeviceToHost, d->st));
+        if (rb) HIP_TRY(hipMemcpyAsync(rows, d_rows, rb, hipMemcpyDeviceToHost, d->st));
+    }
+    HIP_TRY(hipStreamSynchronize(d->st));
     return FLACGPU_OK;
 }
 
@@ -2182,6 +2273,36 @@ int flacgpu_decoder_decode_frames(flacgpu_decoder *d, int32_t *out, size_t out_c
         return FLACGPU_ERR_BUFFER_TOO_SMALL;
     }
     return decode_frames_impl(d, out, flags, records);
+}
+
+int flacgpu_decoder_plan_analysis(flacgpu_decoder *d, uint64_t *n_frames, uint64_t *n_subframes, uint64_t *row_elements) {
+    if (!d || !n_frames || !n_subframes || !row_elements) return FLACGPU_ERR_INVALID_ARG;
+    *n_frames = *n_subframes = *row_elements = 0;
+    if (!d->scanned) {
+        g_last_error = "flacgpu_decoder_plan_analysis: no scanned batch";
+        return FLACGPU_ERR_INVALID_ARG;
+    }
+    const AnalysisSizes z = analysis_sizes(d);
+    *n_frames = z.frames;
+    *n_subframes = z.subframes;
+    *row_elements = z.rows;
+    return FLACGPU_OK;
+}
+
+int flacgpu_decoder_analyze(flacgpu_decoder *d, uint32_t flags, flacgpu_frame_analysis *frames, size_t frames_cap,
+                            flacgpu_subframe_plan *subframes, size_t subframes_cap, int32_t *rows, size_t rows_cap) {
+    if (!d || (flags & ~FLACGPU_DECODE_OUT_DEVICE)) return FLACGPU_ERR_INVALID_ARG;
+    if (!d->scanned) {
+        g_last_error = "flacgpu_decoder_analyze: no scanned batch";
+        return FLACGPU_ERR_INVALID_ARG;
+    }
+    const AnalysisSizes z = analysis_sizes(d);
+    if (z.frames && (!frames || !subframes)) return FLACGPU_ERR_INVALID_ARG;
+    if (frames_cap < z.frames || subframes_cap < z.subframes || (rows && rows_cap < z.rows)) {
+        g_last_error = "output buffer too small";
+        return FLACGPU_ERR_BUFFER_TOO_SMALL;
+    }
+    return analyze_impl(d, flags, frames, subframes, rows, z);
 }
 
 int flacgpu_decoder_plan_timeline(flacgpu_decoder *d, const flacgpu_out_format *fmt, flacgpu_timeline_result *results,

@@ -1,7 +1,9 @@
 """Verification of FLAC files on the GPU, the counterpart of the reference's `decode::verify` (decode.rs:1282-1310):
 every frame must be found and parse with a correct CRC-16, and the MD5 of the decoded samples is compared with
 STREAMINFO's.  Many files go through one batch (gpu.decode_many).  FlacStreamReader / FrameBuf are the counterpart of
-`decode::FlacStreamReader` (decode.rs:1099-1268): the reader of what encode.FlacStreamWriter writes."""
+`decode::FlacStreamReader` (decode.rs:1099-1268): the reader of what encode.FlacStreamWriter writes.  FrameIterator, Frame
+and the subframe and residual classes are the counterpart of `stream::FrameIterator` (stream.rs:1621-3079): the frames of
+a file as they are coded, analysed in one GPU batch (gpu.analyze_many)."""
 import enum
 import os
 
@@ -218,3 +220,191 @@ class FlacFileChunkReader:
 
     def close(self):
         self._session.close()
+
+
+# ---- frame analysis: the reference's FrameIterator / Frame / Subframe / Residuals / ResidualPartition ------------------
+class FrameHeader:
+    """A frame's header (stream.rs FrameHeader).  channel_assignment is "INDEPENDENT", "LEFT_SIDE", "SIDE_RIGHT" or
+    "MID_SIDE"; frame_number is the coded number: a frame number, or with blocking_strategy a sample number."""
+    __slots__ = ("blocking_strategy", "block_size", "sample_rate", "channel_assignment", "channels", "bits_per_sample",
+                 "frame_number")
+
+    def __repr__(self):
+        return "FrameHeader(%s)" % ", ".join("%s=%r" % (k, getattr(self, k)) for k in self.__slots__)
+
+
+class Standard:
+    """A Rice-coded residual partition."""
+    __slots__ = ("rice", "residuals")
+
+    def __init__(self, rice, residuals):
+        self.rice, self.residuals = rice, residuals
+
+
+class Escaped:
+    """A partition whose residuals are stored as plain signed values of escape_size bits."""
+    __slots__ = ("escape_size", "residuals")
+
+    def __init__(self, escape_size, residuals):
+        self.escape_size, self.residuals = escape_size, residuals
+
+
+class ConstantPartition:
+    """An escaped partition of 0 bits per residual: partition_len zeros (ResidualPartition::Constant)."""
+    __slots__ = ("partition_len",)
+
+    def __init__(self, partition_len):
+        self.partition_len = partition_len
+
+    @property
+    def residuals(self):
+        return np.zeros(self.partition_len, dtype=np.int64)
+
+
+class Residuals:
+    """The residual section of a FIXED or LPC subframe: `partitions` is a list of Standard, Escaped and
+    ConstantPartition.  A subframe of more than 64 partitions (`clipped`) lists the first 64."""
+    __slots__ = ("_method", "_order", "partitions", "clipped")
+
+    def __init__(self, method, order, partitions, clipped):
+        self._method, self._order, self.partitions, self.clipped = method, order, partitions, clipped
+
+    def coding_method(self):
+        return "RICE2" if self._method else "RICE"
+
+    def partition_order(self):
+        return self._order
+
+
+class Subframe:
+    """Base of Constant, Verbatim, Fixed and Lpc; wasted_bps is common to all."""
+    __slots__ = ("wasted_bps", "wide")
+    name = ""
+
+    def subframe_type(self):
+        return self.name
+
+
+class Constant(Subframe):
+    __slots__ = ("block_size", "sample")
+    name = "CONSTANT"
+
+
+class Verbatim(Subframe):
+    __slots__ = ("samples",)
+    name = "VERBATIM"
+
+
+class Fixed(Subframe):
+    __slots__ = ("order", "warm_up", "residuals")
+    name = "FIXED"
+
+
+class Lpc(Subframe):
+    __slots__ = ("order", "warm_up", "precision", "shift", "coefficients", "residuals")
+    name = "LPC"
+
+
+class Frame:
+    """One frame as it is coded (stream.rs Frame): `header` and one subframe per channel.  Nothing is decoded: the
+    subframes hold warm-up samples, predictor and residuals as the bit stream states them, after wasted-bit removal.
+    `bits` is the frame's length, `status` the analysis' (bit 0: the frame does not parse -- subframes is then empty
+    --, bit 1: its CRC-16 is wrong)."""
+    __slots__ = ("header", "subframes", "bits", "status")
+
+
+_RATES = (0, 88200, 176400, 192000, 8000, 16000, 22050, 24000, 32000, 44100, 48000, 96000)
+_ASSIGNMENTS = {8: "LEFT_SIDE", 9: "SIDE_RIGHT", 10: "MID_SIDE"}
+
+
+def _subframe(rec, row, n):
+    """rec: a SUBFRAME_DTYPE record, row: its n row elements (exact integers)."""
+    kind = int(rec["type"])
+    s = (Constant, Verbatim, Fixed, Lpc)[kind]()
+    s.wasted_bps = int(rec["wasted"])
+    s.wide = bool(int(rec["reserved"][0]) & 1)
+    if kind == 0:
+        s.block_size, s.sample = n, int(row[0])
+        return s
+    if kind == 1:
+        s.samples = row[:n]
+        return s
+    order = s.order = int(rec["order"])
+    s.warm_up = row[:order]
+    if kind == 3:
+        s.precision, s.shift = int(rec["precision"]), int(rec["shift"])
+        s.coefficients = [int(c) for c in rec["coeffs"][:order]]
+    parts, at, plen = [], order, int(rec["part_len"])
+    listed = min(int(rec["n_partitions"]), 64)
+    for p in range(listed):
+        count = plen - order if p == 0 else plen
+        if int(rec["rice"][p]) != 0xFF:
+            parts.append(Standard(int(rec["rice"][p]), row[at:at + count]))
+        elif int(rec["escape_bits"][p]):
+            parts.append(Escaped(int(rec["escape_bits"][p]), row[at:at + count]))
+        else:
+            parts.append(ConstantPartition(count))
+        at += count
+    s.residuals = Residuals(int(rec["coding_method"]), int(rec["partition_order"]), parts, bool(int(rec["reserved"][0]) & 2))
+    return s
+
+
+class FrameIterator:
+    """Iterates over the frames of a FLAC file as they are coded, yielding (Frame, offset) with `offset` the frame's
+    first byte in `data` -- the reference's stream::FrameIterator, with every frame of the file analysed in one GPU
+    batch on first use (gpu.analyze_many).  data: the bytes of a .flac file, or with raw=True of a raw frame stream.
+    A frame that holds a subframe wider than 32 bits (the side channel of 32-bit stereo) is parsed again on the host
+    (gpu.analyze_frame_host), so that its values are exact."""
+
+    def __init__(self, data, raw=False, device=-1):
+        self._data = data.read() if hasattr(data, "read") else bytes(data)
+        self._raw, self._device = raw, device
+        self._frames = None
+
+    def _analyse(self):
+        data = self._data
+        if self._raw:
+            records, _ = gpu.scan_frames_host(data)
+            offsets = [int(x) for x in records["byte_offset"]]
+            rate0 = bps0 = 0
+        else:
+            info, offs, _ = gpu.scan_stream_host(data)
+            offsets = [int(x) for x in offs]
+            rate0, bps0 = int(info.sample_rate), int(info.bits_per_sample)
+        an = gpu.analyze_many([data], raw=self._raw, rows=True, out="host", device=self._device)
+        if an.frames.size != len(offsets):
+            raise DecodeError("the device scan found %d frames, the host scan %d" % (an.frames.size, len(offsets)))
+        out = []
+        for f, at in enumerate(offsets):
+            fa, subs = an.frames[f], an.subframes_of(f)
+            n, hb, status = int(fa["block_size"]), int(fa["header_bytes"]), int(fa["status"])
+            length = hb + (int(fa["plan"]["body_bits"]) + 7) // 8 + 2
+            rows = [an.row(f, c) for c in range(len(subs))]
+            if not status & 1 and any(int(s["reserved"][0]) & 1 for s in subs):
+                fa, subs, rows = gpu.analyze_frame_host(data[at:at + length], bps0)
+            h = FrameHeader()
+            b = data[at:at + hb]
+            h.blocking_strategy = bool(b[1] & 1)
+            h.block_size = n
+            rcode, code = b[2] & 15, int(fa["assignment_code"])
+            tail = b[hb - 1 - (1 if rcode == 12 else 2 if rcode in (13, 14) else 0):hb - 1]
+            h.sample_rate = (rate0 if rcode == 0 else _RATES[rcode] if rcode < 12 else
+                             int.from_bytes(tail, "big") * {12: 1000, 13: 1, 14: 10}[rcode])
+            h.channel_assignment = _ASSIGNMENTS.get(code, "INDEPENDENT")
+            h.channels = int(fa["plan"]["channels"])
+            h.bits_per_sample = (0, 8, 12, 0, 16, 20, 24, 32)[(b[3] >> 1) & 7] or bps0
+            ones = 8 - (b[4] ^ 0xFF).bit_length()
+            h.frame_number = b[4] & (0x7F >> ones)
+            for i in range(1, ones):
+                h.frame_number = h.frame_number << 6 | (b[4 + i] & 0x3F)
+            fr = Frame()
+            fr.header, fr.status = h, int(fa["status"])
+            fr.bits = 8 * length if not status & 1 else 0
+            fr.subframes = [] if status & 1 else [_subframe(s, rows[c], n) for c, s in enumerate(subs)]
+            out.append((fr, at))
+        self._frames = out
+
+    def __iter__(self):
+        if self._frames is None:
+            self._analyse()
+        return iter(self._frames)

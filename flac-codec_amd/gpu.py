@@ -491,6 +491,61 @@ def scan_frames_host(data, speculative=False):
     return frames, raw
 
 
+# flacgpu_frame_analysis / flacgpu_subframe_plan as flacgpu_decoder_analyze fills them
+ANALYSIS_FRAME_DTYPE = np.dtype(_lib.FrameAnalysis)
+SUBFRAME_DTYPE = np.dtype(_lib.SubframePlan)
+
+
+def analyze_frame_host(frame, streaminfo_bps=0, rows=True):
+    """flacgpu_analyze_frame_host: what one frame (header .. CRC-16, as a scan gives it) is made of, on the host alone
+    (no GPU needed).  Returns (analysis, subframes, rows64): an ANALYSIS_FRAME_DTYPE record, a SUBFRAME_DTYPE array of
+    the frame's channels, and -- rows=True -- an int64 array [channels, roundup4(block_size)] (None otherwise, and for
+    a frame whose header does not parse).  analysis["status"] bit 0: the frame does not parse; the subframe records
+    and rows are then unspecified."""
+    frame = bytes(frame)
+    fa = np.zeros(1, dtype=ANALYSIS_FRAME_DTYPE)
+    subs = np.zeros(8, dtype=SUBFRAME_DTYPE)
+    L = _lib.lib()
+
+    def call(buf):
+        rc = L.flacgpu_analyze_frame_host(frame, len(frame), streaminfo_bps,
+                                          fa.ctypes.data_as(C.POINTER(_lib.FrameAnalysis)),
+                                          subs.ctypes.data_as(C.POINTER(_lib.SubframePlan)),
+                                          buf.ctypes.data if buf is not None and buf.size else None,
+                                          buf.size if buf is not None else 0)
+        if rc:
+            raise GpuError(rc, "flacgpu_analyze_frame_host")
+
+    call(None)   # the records alone: they say how large the rows are
+    ch, n = int(fa[0]["plan"]["channels"]), int(fa[0]["block_size"])
+    rows64 = None
+    if rows and ch and n:
+        rows64 = np.zeros((ch, (n + 3) & ~3), dtype=np.int64)
+        call(rows64)
+    return fa[0], subs[:ch], rows64
+
+
+class FrameAnalysis:
+    """What analyze_many / Decoder.analyze return: `frames` (ANALYSIS_FRAME_DTYPE) and `subframes` (SUBFRAME_DTYPE) are
+    numpy structured arrays mirroring flacgpu_frame_analysis and flacgpu_subframe_plan; `rows` is flat int32 -- a numpy
+    array, a CUDA tensor for out="device", None for the records-only pass."""
+    __slots__ = ("frames", "subframes", "rows")
+
+    def __init__(self, frames, subframes, rows):
+        self.frames, self.subframes, self.rows = frames, subframes, rows
+
+    def subframes_of(self, f):
+        """The subframe records of frame f, one per channel."""
+        at = int(self.frames[f]["first_subframe"])
+        return self.subframes[at:at + int(self.frames[f]["plan"]["channels"])]
+
+    def row(self, f, c):
+        """The block_size elements of channel c's row of frame f (a CONSTANT row is defined at [0] alone)."""
+        n = int(self.frames[f]["block_size"])
+        at = int(self.frames[f]["row_offset"]) + c * ((n + 3) & ~3)
+        return self.rows[at:at + n]
+
+
 TIMELINE_FRAME_DTYPE = np.dtype([(name, np.dtype(ct).str) for name, ct in _lib.TimelineFrame._fields_])
 
 
@@ -664,6 +719,50 @@ class Decoder:
         if rc:
             raise GpuError(rc, "flacgpu_decoder_decode_frames")
         return frames
+
+    def plan_analysis(self):
+        """flacgpu_decoder_plan_analysis for the handle's scanned batch: (frames, subframe records, int32 row elements)."""
+        nf, ns, nr = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        rc = _lib.lib().flacgpu_decoder_plan_analysis(self._h, C.byref(nf), C.byref(ns), C.byref(nr))
+        if rc:
+            raise GpuError(rc, "flacgpu_decoder_plan_analysis")
+        return nf.value, ns.value, nr.value
+
+    def analyze(self, rows=False, out="host"):
+        """flacgpu_decoder_analyze of the handle's scanned batch (any scan, or a session's feed): a FrameAnalysis.
+        rows=False is the records-only pass (no sample is stored, .rows is None).  out="device" has the kernel write
+        into torch tensors on the decoder's device: the rows stay there as an int32 CUDA tensor, the records come back
+        as numpy arrays either way."""
+        if out not in ("device", "host"):
+            raise ValueError("out must be 'device' or 'host'")
+        nf, ns, nr = self.plan_analysis()
+        L = _lib.lib()
+        if out == "device":
+            import torch
+
+            dev = f"cuda:{self.device_index}"
+            t_frames = torch.empty(nf * ANALYSIS_FRAME_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+            t_subs = torch.empty(ns * SUBFRAME_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+            t_rows = torch.empty(nr, dtype=torch.int32, device=dev) if rows else None
+            torch.cuda.synchronize(self.device_index)
+            rc = L.flacgpu_decoder_analyze(self._h, _lib.DECODE_OUT_DEVICE, t_frames.data_ptr() if nf else None, nf,
+                                           t_subs.data_ptr() if ns else None, ns,
+                                           t_rows.data_ptr() if rows and nr else None, nr if rows else 0)
+            if rc:
+                raise GpuError(rc, "flacgpu_decoder_analyze")
+            frames = t_frames.cpu().numpy().view(ANALYSIS_FRAME_DTYPE)
+            subs = t_subs.cpu().numpy().view(SUBFRAME_DTYPE)
+            return FrameAnalysis(frames, subs, t_rows)
+        frames = np.zeros(nf, dtype=ANALYSIS_FRAME_DTYPE)
+        subs = np.zeros(ns, dtype=SUBFRAME_DTYPE)
+        # one element more than none, so that rows=True never passes the NULL that selects the records-only pass
+        r = np.zeros(max(nr, 1), dtype=np.int32) if rows else None
+        rc = L.flacgpu_decoder_analyze(self._h, 0, frames.ctypes.data if nf else None, nf,
+                                       subs.ctypes.data if ns else None, ns, r.ctypes.data if rows else None,
+                                       r.size if rows else 0)
+        if rc:
+            raise GpuError(rc, "flacgpu_decoder_analyze")
+        return FrameAnalysis(frames, subs, r[:nr] if rows else None)
 
     def plan_timeline(self, fmt, check=True):
         """flacgpu_decoder_plan_timeline for the handle's last raw scan: (results, out_bytes, mask_bytes), `results` the
@@ -1048,6 +1147,35 @@ def decode_frames(blobs, device=-1, out="device", decoder=None, speculative=Fals
         if own:
             dec.close()
     return flat, frames, list(raw)[:len(blobs)]
+
+
+def analyze_many(blobs, raw=False, speculative=False, rows=False, out="host", decoder=None, device=-1):
+    """What every frame of a batch of FLAC streams is made of, in one GPU call (flacgpu_decoder_scan or, raw=True,
+    flacgpu_decoder_scan_frames_ex, then flacgpu_decoder_analyze): subframe types, orders, wasted bits, predictors, Rice
+    methods, partition orders and parameters, exact bit lengths and -- rows=True -- the residual rows as they are coded.
+    The counterpart of the reference's FrameIterator for a whole batch; nothing is decoded.
+
+    Returns a FrameAnalysis: .frames / .subframes are numpy structured arrays mirroring flacgpu_frame_analysis and
+    flacgpu_subframe_plan, .rows flat int32 (numpy, or a CUDA tensor for out="device"; None with rows=False),
+    .subframes_of(f) and .row(f, c) pick a frame's records and rows.  Frames come in the scan's order: by input, then
+    position.  speculative=True (with raw=True alone) scans with FLACGPU_SCAN_SPECULATIVE."""
+    if speculative and not raw:
+        raise ValueError("speculative goes with raw=True")
+    if out == "device":
+        import torch
+
+        torch.cuda.init()   # torch's HIP runtime first, as in decode_many
+    own = decoder is None
+    dec = Decoder(device) if own else decoder
+    try:
+        if raw:
+            dec.scan_frames(blobs, speculative)
+        else:
+            dec.scan(blobs)
+        return dec.analyze(rows=rows, out=out)
+    finally:
+        if own:
+            dec.close()
 
 
 def decode_many(blobs, device=-1, out="device", verify_md5=True, decoder=None, dtype="int32", layout="flat",

@@ -784,6 +784,65 @@ int flacgpu_decoder_frame_records(flacgpu_decoder *d, flacgpu_frame_record *reco
 int flacgpu_decoder_decode_frames(flacgpu_decoder *d, int32_t *out, size_t out_cap_elements, uint32_t flags,
                                   flacgpu_frame_record *records, size_t cap);
 
+/* ---- batch decoder: frame analysis -----------------------------------------------------------------------------------
+ * What every frame of a scanned batch is made of: the reference's FrameIterator / Frame / Subframe / Residuals /
+ * ResidualPartition (stream.rs:1621-3079) for a whole batch in one call, as the records the encoder states its own
+ * decisions in.  One lane per frame walks the frame's bits (csrc/kernels/frame_analysis.h, the same function on the host
+ * and on the device) under the tests of decode_frames: status bit 0 is decode_frames' bit 0, bit 1 its bit 1.  No sample
+ * is reconstructed.
+ *   frames      one flacgpu_frame_analysis per frame of the scan, in the scan's order (after scan_frames: the order of
+ *               the records).  `plan` is a flacgpu_frame_plan as flacgpu_analyze writes it: `assignment` is
+ *               FLACGPU_ASSIGN_*, that is 0 for independent channels and the coded 8, 9, 10 otherwise, so that the plan
+ *               goes into flacgpu_pack_plans as it is; the value as CODED in the header (0..10, independent channels
+ *               code channels - 1) stands in `assignment_code`.  plan.block_size is block_size & 0xFFFF, body_bits the
+ *               sum of the subframes' bits.
+ *   subframes   the frame's subframe c at first_subframe + c, a flacgpu_subframe_plan with the meaning the encoder
+ *               gives each field: type, wasted, bps (the coded width less the wasted bits; the side channel's width is
+ *               the stream's + 1), order, precision / shift / coeffs[0..order) (LPC only; 0 otherwise, FIXED included),
+ *               coding_method, partition_order as coded, n_partitions = 1 << partition_order, part_len = n >>
+ *               partition_order, bits (exact), rice[p] (0xFF: escaped), escape_bits[p] (0: the all-zero partition),
+ *               source (independent: c; 8: 0, SIDE; 9: SIDE, 1; 10: MID, SIDE).  Every entry a subframe does not use is
+ *               0.  reserved[0] holds two flags:
+ *                 FLACGPU_AN_WIDE          the subframe is wider than 32 bits (the 33-bit side channel of 32-bit stereo,
+ *                                          SubframeWidth::Wide): its int32 row holds the low 32 bits of every value
+ *                 FLACGPU_AN_PARTS_CLIPPED more than FLACGPU_MAX_PARTITIONS partitions (a foreign stream may have 2^15):
+ *                                          rice[] / escape_bits[] hold the first 64; partition_order, n_partitions,
+ *                                          part_len and bits stay true
+ *   rows        optional, int32: channel c of a frame at row_offset + c * roundup4(block_size) (the layout of the
+ *               decoder's own scratch), the row flacgpu_analyze documents: FIXED / LPC the `order` warm-up samples, then
+ *               the n - order residuals as coded; VERBATIM the n samples; CONSTANT the value at [0]; all after
+ *               wasted-bit removal.  Elements [n, roundup4(n)) and the rest of a CONSTANT row are unspecified.
+ * A frame with status bit 0 has unspecified subframe records and rows; nothing outside its own records and rows is
+ * written, whatever its bits say.
+ *   analyze_frame_host   the rule on the host alone, for one frame [frame, frame + len) (len: header .. CRC-16, as a scan
+ *                        gives it); no device needed.  streaminfo_bps: the sample size of a header that leaves it to the
+ *                        STREAMINFO (0: none known, such a frame gets status bit 0).  subframes: 8 records.  rows64 (may
+ *                        be NULL: records only) receives channel c at c * roundup4(block_size) as int64, so that a wide
+ *                        subframe is exact; rows64_cap < channels * roundup4(block_size) writes nothing and returns
+ *                        FLACGPU_ERR_BUFFER_TOO_SMALL.  row_offset and first_subframe are 0.
+ *   plan_analysis        the sizes for the handle's scanned batch: frames, subframe records, row elements.
+ *   analyze              fills the three outputs, in host memory or (FLACGPU_DECODE_OUT_DEVICE, the only flag) device
+ *                        memory; rows == NULL selects the records-only pass, which stores no sample.  Works after scan,
+ *                        scan_frames(_ex), the two device scans and a session's feed (that feed's frames), and may
+ *                        alternate with every decode call on one scan, in any order.  A refused call (no scanned batch,
+ *                        a cap too small: FLACGPU_ERR_BUFFER_TOO_SMALL, an unknown flag) writes nothing; a batch without
+ *                        frames succeeds with zero counts. */
+#define FLACGPU_AN_WIDE 1u
+#define FLACGPU_AN_PARTS_CLIPPED 2u
+typedef struct {              /* 40 bytes */
+    uint64_t row_offset;      /* first int32 of the frame's rows */
+    uint64_t first_subframe;  /* index of the frame's subframe 0 */
+    uint32_t block_size, header_bytes;
+    uint32_t status;          /* bit 0: did not parse, bit 1: CRC-16 wrong */
+    uint32_t assignment_code; /* the channel assignment as coded, 0..10 */
+    flacgpu_frame_plan plan;
+} flacgpu_frame_analysis;
+int flacgpu_analyze_frame_host(const uint8_t *frame, size_t len, uint32_t streaminfo_bps, flacgpu_frame_analysis *analysis,
+                               flacgpu_subframe_plan *subframes, int64_t *rows64, size_t rows64_cap);
+int flacgpu_decoder_plan_analysis(flacgpu_decoder *d, uint64_t *n_frames, uint64_t *n_subframes, uint64_t *row_elements);
+int flacgpu_decoder_analyze(flacgpu_decoder *d, uint32_t flags, flacgpu_frame_analysis *frames, size_t frames_cap,
+                            flacgpu_subframe_plan *subframes, size_t subframes_cap, int32_t *rows, size_t rows_cap);
+
 /* ---- batch decoder: streams that already lie in device memory -------------------------------------------------------
  * The scans' second front door, for compressed bytes that are born or delivered in device memory: the frames
  * flacgpu_encode_device leaves there (flacgpu_device_buffer 4 and 5), a shard broadcast into every rank's GPU, a shard

@@ -26,6 +26,8 @@ over flacgpu_decode_stream and the oracle's CPU decoder on one core; writes prof
     python tools/decode_many_probe.py --timeline --kernels-only
     python tools/decode_many_probe.py --raw|--timeline --label parent --package-root DIR --parent-all-legs   (a parent that
                                              has every leg of the mode: each is then held to the parent's own spread of it)
+    python tools/decode_many_probe.py --analyze [--out profiles/r25_frame_analysis.json] [--reps 15]
+    python tools/decode_many_probe.py --analyze --kernels-only      (a warm call and three more per leg, for rocprofv3)
     python tools/decode_many_probe.py --session [--out profiles/r22_decoder_session.json] [--reps 15]
     python tools/decode_many_probe.py --session --container [--out profiles/r24_container_session.json] [--reps 15]
                                              [--workloads clips,hour] [--hour-seconds N]   (container sessions: whole
@@ -528,6 +530,71 @@ def raw_frames(args):
     with open(args.out, "w") as f:
         json.dump(res, f, indent=1)
     print(json.dumps({args.label: rec, "verdict": res.get("verdict")}, indent=1), flush=True)
+
+
+def analyze(args):
+    """The --analyze leg: frame analysis (flacgpu_decoder_analyze; DESIGN.md 4b "Frame analysis") against decode_frames on
+    ONE raw scan of the 1024 clips, handle warm, device output, one process: the records-only pass, the pass with rows,
+    and decode_frames, each call alone (the scan is not timed), median and min to max of --reps runs, the shader clock
+    before and after each leg: profiles/r25_frame_analysis.json.  No test asserts a time; the yardstick is decode_frames
+    in the same process.  --kernels-only: a warm call and three more per leg, for rocprofv3 --kernel-trace --stats."""
+    import torch
+
+    from flac_codec_amd import _lib
+    from flac_codec_amd.gpu import ANALYSIS_FRAME_DTYPE, SUBFRAME_DTYPE, Decoder, scan_stream_host
+
+    blobs = make_blobs("clips")
+    bare = [b[int(scan_stream_host(b)[1][0]):] for b in blobs]   # from the first frame on
+    dec = Decoder(0)
+    _, _, _, frames = dec.scan_frames(bare)
+    nf, ns, nr = dec.plan_analysis()
+    L = _lib.lib()
+    t_frames = torch.empty(nf * ANALYSIS_FRAME_DTYPE.itemsize, dtype=torch.uint8, device="cuda:0")
+    t_subs = torch.empty(ns * SUBFRAME_DTYPE.itemsize, dtype=torch.uint8, device="cuda:0")
+    t_rows = torch.empty(nr, dtype=torch.int32, device="cuda:0")
+    t_pcm = torch.empty(dec.raw_elements, dtype=torch.int32, device="cuda:0")
+    torch.cuda.synchronize()
+
+    def analysis(rows):
+        rc = L.flacgpu_decoder_analyze(dec._h, _lib.DECODE_OUT_DEVICE, t_frames.data_ptr(), nf, t_subs.data_ptr(), ns,
+                                       t_rows.data_ptr() if rows else None, nr if rows else 0)
+        assert rc == 0, rc
+
+    legs = {"analyze_records_only": lambda: analysis(False), "analyze_with_rows": lambda: analysis(True),
+            "decode_frames": lambda: dec.decode_frames(t_pcm.data_ptr(), dec.raw_elements, _lib.DECODE_OUT_DEVICE,
+                                                       frames.copy())}
+    if args.kernels_only:
+        for fn in legs.values():
+            for _ in range(4):
+                fn()
+        torch.cuda.synchronize()
+        dec.close()
+        return
+    res = {"tool": "tools/decode_many_probe.py --analyze", "workload": "clips: 1024 x 10 s, 16 kHz mono 16-bit",
+           "device_output": True, "one_scan": "scan_frames, not timed", "build_id": _lib.build_id(), "frames": int(nf),
+           "subframes": int(ns), "row_elements": int(nr), "reps": args.reps, "legs": {}}
+    if os.path.exists(args.out):   # keep a kernel_stats record merged earlier
+        with open(args.out) as f:
+            res["kernel_stats"] = json.load(f).get("kernel_stats", {})
+    for name, fn in legs.items():
+        fn()
+        torch.cuda.synchronize()   # warm: buffers grown, tables uploaded, code loaded
+        sclk_before = _sclk_mhz()
+        times = []
+        for _ in range(args.reps):
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            times.append(time.perf_counter() - t0)
+        res["legs"][name] = dict(_spread(times), sclk_mhz_before=sclk_before, sclk_mhz_after=_sclk_mhz())
+    status = t_frames.cpu().numpy().view(ANALYSIS_FRAME_DTYPE)["status"]
+    res["frames_with_status"] = int((status != 0).sum())
+    ref = res["legs"]["decode_frames"]["median_s"]
+    res["over_decode_frames_median"] = {k: v["median_s"] / ref for k, v in res["legs"].items()}
+    dec.close()
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res, indent=1), flush=True)
 
 
 def session(args):
@@ -1141,7 +1208,7 @@ def merge_stats(args):
                                                                    "k_finish_many", "k_md5_many", "k_finish_as",
                                                                    "k_pad_rows", "k_finish_window", "k_spec_end",
                                                                    "k_fill_runs", "k_gather_slots", "k_meta_walk",
-                                                                   "k_cand_heads"))}   # (k_scan_ and k_link cover the raw kernels)
+                                                                   "k_cand_heads", "k_analyze_many"))}   # (k_scan_ and k_link cover the raw kernels)
     res.setdefault("kernel_stats", {})[args.stats_label] = mine
     gather = [v for k, v in mine.items() if "k_gather_slots" in k]
     if gather and "compressed_bytes" in res:   # --device-input: the gather against the plain copy
@@ -1165,6 +1232,7 @@ def main():
     ap.add_argument("--speculative", action="store_true",
                     help="with --raw: add the FLACGPU_SCAN_SPECULATIVE leg, profiles/r14_speculative.json")
     ap.add_argument("--timeline", action="store_true", help="the timeline leg: profiles/r16_timeline.json")
+    ap.add_argument("--analyze", action="store_true", help="the frame analysis leg: profiles/r25_frame_analysis.json")
     ap.add_argument("--session", action="store_true", help="the decoder session leg: profiles/r22_decoder_session.json")
     ap.add_argument("--container", action="store_true",
                     help="with --session: the container session leg, profiles/r24_container_session.json")
@@ -1183,10 +1251,11 @@ def main():
     ap.add_argument("--kernels-only", action="store_true", help="one warm decode per workload (for rocprofv3)")
     args = ap.parse_args()
     if args.reps is None:
-        args.reps = 15 if args.device_input or args.session else 3
+        args.reps = 15 if args.device_input or args.session or args.analyze else 3
     if not args.out:
         args.out = os.path.join(ROOT, "profiles", "r15_device_input.json" if args.device_input else
                                 "r16_timeline.json" if args.timeline else
+                                "r25_frame_analysis.json" if args.analyze else
                                 "r24_container_session.json" if args.session and args.container else
                                 "r22_decoder_session.json" if args.session else
                                 "r14_speculative.json" if args.raw and args.speculative else
@@ -1207,6 +1276,8 @@ def main():
         return device_input(args)
     if args.timeline:
         return timeline(args)
+    if args.analyze:
+        return analyze(args)
     if args.session and args.container:
         if args.workloads == "clips,tracks,hour":
             args.workloads = "clips,hour"
