@@ -13,6 +13,7 @@
 #include "kernels/session_slots_rule.h"
 #include "flac_stream.h"
 #include "session_rule.h"
+#include "container_rule.h"
 
 #include <stdlib.h>
 #include <string.h>
@@ -157,21 +158,25 @@ struct Candidates {
 };
 
 // A decoder session's feed (kernels/session.inc): every slot is built by k_session_slots from `srcs` (device addresses),
-// and the links are k_link_session's under `info`; both tables have one entry per slot and go up into the two buffers.
-// container: a container session's feed -- the regular scan's candidates, linked by k_link_container.
+// and the links are made under `info`; both tables have one entry per slot and go up into the two buffers.
 struct SessionFill {
     const SessionSrc *srcs;
     const SessionSlot *info;
     DevBuf *src_tab, *info_tab;
-    bool container = false;
 };
 
+// The rule that links a scan's candidates: k_link (regular streams), k_link_raw (raw frame streams), and the two of a
+// session's feed, k_link_session (raw) and k_link_container (regular).  The raw rules take the candidates with a sample
+// rate and a sample size of their own (k_scan_subset); a feed's slots come from its SessionFill.
+enum class LinkRule { Regular, Raw, Session, Container };
+
 // The device half of a scan: fills every slot (zero tails, 64 bytes of look-ahead) -- host input in one upload, device
-// input with k_gather_slots, a session's feed (fill != null; `in` is not looked at) with k_session_slots -- and runs the
-// scan kernels; the candidates come down into `c`.  raw: the scan of raw frame streams (k_scan_subset, k_link_raw or a
-// session's k_link_session), with the extents and the headers it asks for.
-int device_scan(flacgpu_decoder *d, const ScanInput &in, const SlotLayout &lay, bool raw, bool want_spec, bool want_heads,
-                Candidates &c, const SessionFill *fill = nullptr) {
+// input with k_gather_slots, a session's feed (`fill`, given with its two rules and no other; `in` is not looked at) with
+// k_session_slots -- and runs the scan kernels; the candidates come down into `c`, with the extents and the headers the
+// caller asks for.
+int device_scan(flacgpu_decoder *d, const ScanInput &in, const SlotLayout &lay, LinkRule rule, bool want_spec,
+                bool want_heads, Candidates &c, const SessionFill *fill = nullptr) {
+    const bool raw = rule == LinkRule::Raw || rule == LinkRule::Session;
     const std::vector<ScanSlot> &slots = lay.slots;
     const uint64_t at = lay.at;
     const uint32_t S = (uint32_t)slots.size();
@@ -279,14 +284,13 @@ int device_scan(flacgpu_decoder *d, const ScanInput &in, const SlotLayout &lay, 
     p.link = d->link.as<int32_t>();
     p.n_cand = n_cand;
     hipLaunchKernelGGL(k_scan_emit, dim3(n_wg), dim3(WG), 0, d->st, p);
-    if (n_cand && fill && fill->container)
-        hipLaunchKernelGGL(k_link_container, dim3((n_cand + WG - 1) / WG), dim3(WG), 0, d->st, p,
-                           fill->info_tab->as<const SessionSlot>());
-    else if (n_cand && fill)
-        hipLaunchKernelGGL(k_link_session, dim3((n_cand + WG - 1) / WG), dim3(WG), 0, d->st, p,
-                           fill->info_tab->as<const SessionSlot>());
-    else if (n_cand && raw) hipLaunchKernelGGL(k_link_raw, dim3((n_cand + WG - 1) / WG), dim3(WG), 0, d->st, p);
-    else if (n_cand) hipLaunchKernelGGL(k_link, dim3((n_cand + WG - 1) / WG), dim3(WG), 0, d->st, p);
+    const dim3 link_grid((n_cand + WG - 1) / WG);
+    if (n_cand && rule == LinkRule::Container)
+        hipLaunchKernelGGL(k_link_container, link_grid, dim3(WG), 0, d->st, p, fill->info_tab->as<const SessionSlot>());
+    else if (n_cand && rule == LinkRule::Session)
+        hipLaunchKernelGGL(k_link_session, link_grid, dim3(WG), 0, d->st, p, fill->info_tab->as<const SessionSlot>());
+    else if (n_cand && rule == LinkRule::Raw) hipLaunchKernelGGL(k_link_raw, link_grid, dim3(WG), 0, d->st, p);
+    else if (n_cand) hipLaunchKernelGGL(k_link, link_grid, dim3(WG), 0, d->st, p);
     if (n_cand && want_spec)
         hipLaunchKernelGGL(k_spec_end, dim3((n_cand + 63) / 64), dim3(64), 0, d->st, p, d->spec_len.as<uint32_t>());
     if (n_cand && want_heads)
@@ -361,6 +365,62 @@ int finish_scan(flacgpu_decoder *d, SlotLayout &lay, uint64_t total, uint64_t sc
     return FLACGPU_OK;
 }
 
+// The running sizes of a scan's two layouts: decode_frames' (every kept frame of a raw scan) and the regular batch
+// calls' (every stream of a regular scan, the uniform streams of a raw one).
+struct RawTotals {
+    uint64_t elements = 0, raw_scratch = 0, total = 0, scratch_total = 0;
+};
+
+// Where candidate k of a slot that ends at slot_end ends by its link
+flacenc::RawEnd end_by_link(const Candidates &c, size_t k, uint64_t slot_end) {
+    const int32_t link = c.link[k];
+    if (link == LINK_HOLD) return flacenc::RawEnd{flacenc::kRawHold, false};
+    if (link == LINK_NONE) return flacenc::RawEnd{flacenc::kRawNone, false};
+    return flacenc::RawEnd{link == LINK_END ? slot_end : c.pos[link], false};
+}
+
+// The chain walk (regular_walk, host/raw_walk.h) over slot s, whose positions below `judged` are judged, along the links
+// the device left (k_link, or a feed's k_link_container with its LINK_HOLD): every kept frame joins frame_tab with
+// STREAMINFO's channels and sample size, `out` counted in samples per channel from *samples on (lay_out_regular makes
+// it absolute).  A frame without an end is not taken, and nothing behind it.
+flacenc::RegularWalk walk_regular_slot(flacgpu_decoder *d, const Candidates &c, const SlotLayout &lay, uint32_t s,
+                                       uint64_t judged, const flacgpu_stream_info &info, uint64_t *samples) {
+    const ScanSlot &sl = lay.slots[s];
+    const uint64_t slot_end = sl.base + sl.len;
+    return flacenc::regular_walk(
+        c.pos.data(), c.cand0[s], c.end_of(s), sl.base, slot_end, judged,
+        [&](size_t k, uint64_t) { return end_by_link(c, k, slot_end); },
+        [&](size_t k, uint64_t at, uint64_t end) {
+            ManyFrame f{};
+            f.start = at;
+            f.end = end;
+            f.cap = lay.end_of(s) - 4;
+            f.n = (c.info[k] & 0xFFFFu) + 1u;
+            f.slot = s;
+            f.channels = info.channels;
+            f.bps = info.bits_per_sample;
+            f.out = *samples;
+            d->frame_tab.push_back(f);
+            *samples += f.n;
+        });
+}
+
+// The regular batch's output layout: the streams one after another, interleaved; every frame's place in it and in the
+// planar scratch.
+RawTotals lay_out_regular(flacgpu_decoder *d, const SlotLayout &lay) {
+    RawTotals tot;
+    for (flacgpu_decoded_stream &r : d->res) {
+        r.out_offset = tot.total;
+        if (r.rc == FLACGPU_OK) tot.total += r.info.decoded_samples * r.info.channels;
+    }
+    for (ManyFrame &f : d->frame_tab) {
+        f.out = d->res[lay.slot_stream[f.slot]].out_offset + f.out * f.channels;
+        f.scratch = tot.scratch_total;
+        tot.scratch_total += (uint64_t)f.channels * ((f.n + 3u) & ~3u);
+    }
+    return tot;
+}
+
 int scan_impl(flacgpu_decoder *d, const ScanInput &in, const size_t *len, uint32_t n) {
     const uint8_t *const *data = in.data;
     d->res.assign(n, flacgpu_decoded_stream{});
@@ -386,66 +446,21 @@ int scan_impl(flacgpu_decoder *d, const ScanInput &in, const size_t *len, uint32
     d->n_slots = S;
     if (S) {
         Candidates c;
-        if (int rc = device_scan(d, in, lay, false, false, false, c)) return rc;
-        // ---- host walk: follow the links from each region's first byte (the host scan's lost-sync rule: a frame
-        // without an end is not taken, and nothing behind it is decoded)
+        if (int rc = device_scan(d, in, lay, LinkRule::Regular, false, false, c)) return rc;
+        // ---- host walk: the chain from each region's first byte to its end (the host scan's lost-sync rule)
         for (uint32_t s = 0; s < S; s++) {
-            const ScanSlot &sl = lay.slots[s];
             flacgpu_stream_info &info = d->res[lay.slot_stream[s]].info;
-            uint32_t i = c.cand0[s];
+            const size_t first = d->frame_tab.size();
             uint64_t samples = 0;
-            uint32_t F = 0;
-            if (i >= c.end_of(s) || c.pos[i] != sl.base) {
-                info.bad_frames = 1;
-            } else {
-                for (;;) {
-                    const int32_t nx = c.link[i];
-                    if (nx == LINK_NONE) {
-                        info.bad_frames = 1;
-                        break;
-                    }
-                    ManyFrame f{};
-                    f.start = c.pos[i];
-                    f.end = nx == LINK_END ? sl.base + sl.len : c.pos[nx];
-                    f.cap = lay.end_of(s) - 4;
-                    f.n = (c.info[i] & 0xFFFFu) + 1u;
-                    f.slot = s;
-                    f.channels = info.channels;
-                    f.bps = info.bits_per_sample;
-                    f.out = samples;   // stream-relative here, made absolute below
-                    d->frame_tab.push_back(f);
-                    samples += f.n;
-                    F++;
-                    if (nx == LINK_END) break;
-                    i = (uint32_t)nx;
-                }
-            }
-            info.frames = F;
+            const uint64_t slot_end = lay.slots[s].base + lay.slots[s].len;
+            if (walk_regular_slot(d, c, lay, s, slot_end, info, &samples).lost) info.bad_frames = 1;
+            info.frames = (uint32_t)(d->frame_tab.size() - first);
             info.decoded_samples = samples;
         }
     }
-    // ---- output layout: streams one after another, interleaved
-    uint64_t total = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        flacgpu_decoded_stream &r = d->res[i];
-        r.out_offset = total;
-        if (r.rc == FLACGPU_OK) total += r.info.decoded_samples * r.info.channels;
-    }
-    uint64_t scratch_total = 0;
-    for (ManyFrame &f : d->frame_tab) {
-        const flacgpu_decoded_stream &r = d->res[lay.slot_stream[f.slot]];
-        f.out = r.out_offset + f.out * f.channels;
-        f.scratch = scratch_total;
-        scratch_total += (uint64_t)f.channels * ((f.n + 3u) & ~3u);
-    }
-    return finish_scan(d, lay, total, scratch_total);
+    const RawTotals tot = lay_out_regular(d, lay);
+    return finish_scan(d, lay, tot.total, tot.scratch_total);
 }
-
-// The running sizes of a raw scan's two layouts: decode_frames' (every kept frame) and the regular batch calls' (the
-// uniform streams alone).
-struct RawTotals {
-    uint64_t elements = 0, raw_scratch = 0, total = 0, scratch_total = 0;
-};
 
 // A kept frame [at, end) of stream i (positions in the batch buffer; slot_end: the end of its slot): its record, with
 // byte_offset as given, and its entry in decode_frames' table.  The header was accepted by K_s1: n, header_bytes and the
@@ -515,10 +530,8 @@ flacenc::RawWalk walk_slot(const Candidates &c, const ScanSlot &sl, uint32_t s, 
     return flacenc::raw_walk(
         c.pos.data(), c.cand0[s], c.end_of(s), sl.base, slot_end,
         [&](size_t k, uint64_t at) {
-            const int32_t link = c.link[k];
-            if (link == LINK_HOLD) return flacenc::RawEnd{flacenc::kRawHold, false};
-            if (link == LINK_NONE) return c.spec.empty() || !c.spec[k] ? flacenc::RawEnd{} : flacenc::RawEnd{at + c.spec[k], true};
-            return flacenc::RawEnd{link == LINK_END ? slot_end : c.pos[link], false};
+            if (c.link[k] == LINK_NONE && !c.spec.empty() && c.spec[k]) return flacenc::RawEnd{at + c.spec[k], true};
+            return end_by_link(c, k, slot_end);
         },
         keep, count);
 }
@@ -561,7 +574,7 @@ int scan_raw_impl(flacgpu_decoder *d, const ScanInput &in, const size_t *len, ui
     const uint32_t S = (uint32_t)lay.slots.size();
     d->n_slots = S;
     if (S)
-        if (int rc = device_scan(d, in, lay, true, spec, in.device, c)) return rc;
+        if (int rc = device_scan(d, in, lay, LinkRule::Raw, spec, in.device, c)) return rc;
     const uint32_t n_cand = c.n;
     // ---- host walk, stream by stream: the candidates in ascending order, those below the cursor ignored, one without
     // an end passed over, one with an end kept and the cursor moved to that end.  A kept frame's record is read from
@@ -617,16 +630,9 @@ struct flacgpu_decoder_session {
     flacgpu_session_timing timing{};       // of the last feed or finish
     DevBuf other, chunks, src_tab, info_tab;
     // ---- a container session (DESIGN.md 4b "Container sessions"): regular .flac streams, MD5 across feeds ----
-    enum : uint32_t { CS_META = 0, CS_FRAMES = 1, CS_LOST = 2, CS_REFUSED = 3 };
-    struct Container {
-        MetaFeed meta{};             // the metadata walk so far (CS_META)
-        uint32_t phase = CS_META;
-        uint64_t fed = 0;            // bytes fed to this stream
-        flacgpu_stream_info info{};  // metadata_of_record's: STREAMINFO from CS_FRAMES on, what a refused stream reports
-        uint32_t min_frame = 0;
-        // cumulative: the frames decided, their samples per channel, the bytes dropped; bad_frames / bad_crc16 as the
-        // one-shot decode counts them (lost synchronisation, and what the hashing decode of every feed found)
-        uint64_t frames = 0, samples = 0, skipped = 0;
+    struct Container : flacenc::ContainerStream {   // the rule's state (host/container_rule.h), and the device session's own
+        // cumulative, as the one-shot decode counts them: lost synchronisation, and what the hashing decode of every
+        // feed found
         uint32_t bad_frames = 0, bad_crc16 = 0;
         bool in_feed = false;        // the last feed decided frames for this stream
         bool broken = false;         // such a feed was never hashed: the chain says nothing
@@ -642,6 +648,82 @@ struct flacgpu_decoder_session {
 };
 
 namespace {
+// What the feeds of the two device sessions share (session_step, container_step).  The feed's slots and the decoder's
+// new per-stream tables are built here, in locals: a call refused before commit_and_scan has touched neither the session
+// nor its decoder, whose last feed can still be decoded; a failure behind it leaves the session dead.
+struct SessionFeed {
+    using Clock = std::chrono::steady_clock;
+    flacgpu_decoder_session *ses;
+    const uint8_t *tails;   // the buffer the held tails lie in: the decoder's batch buffer, `other` from the commit on
+    SlotLayout lay;
+    Candidates c;
+    std::vector<SessionSrc> srcs;
+    std::vector<SessionSlot> info;
+    std::vector<flacgpu_decoded_stream> res;
+    std::vector<int32_t> slot_of;
+    std::vector<flacgpu_raw_stream> raw_streams;
+    Clock::time_point t0, t1, t2;
+
+    explicit SessionFeed(flacgpu_decoder_session *s) : ses(s), tails(s->d->bytes.as<const uint8_t>()) {}
+    void begin(uint32_t n) {
+        res.assign(n, flacgpu_decoded_stream{});
+        slot_of.assign(n, -1);
+        raw_streams.assign(n, flacgpu_raw_stream{});
+    }
+    // stream i's slot: its held tail, then the `fresh` new bytes at `chunk` (a DEVICE address)
+    void add(uint32_t i, const flacgpu_decoder_session::Stream &st, const uint8_t *chunk, uint64_t fresh, bool final,
+             uint32_t channels, uint32_t min_frame) {
+        slot_of[i] = (int32_t)lay.add(i, 0, st.held + fresh, channels, min_frame);
+        srcs.push_back(SessionSrc{reinterpret_cast<uint64_t>(tails + st.at), st.held,
+                                  fresh ? reinterpret_cast<uint64_t>(chunk) : 0, fresh});
+        info.push_back(SessionSlot{final ? 1u : 0u, ses->W});
+    }
+    // device_scan's limit, before anything has changed
+    int refused() const {
+        if (lay.at + 64 <= ((uint64_t)1 << 34)) return FLACGPU_OK;
+        g_last_error = "flacgpu_decoder_session_feed: the feed's slots exceed 16 GiB";
+        return FLACGPU_ERR_UNSUPPORTED;
+    }
+    // The commit point (nothing here up to the scan allocates), and the scan under `rule`
+    int commit_and_scan(LinkRule rule, bool want_heads) {
+        flacgpu_decoder *d = ses->d;
+        const uint32_t S = (uint32_t)lay.slots.size();
+        d->scanned = d->raw = false;
+        d->res.swap(res);
+        d->slot_of.swap(slot_of);
+        d->raw_streams.swap(raw_streams);
+        d->frame_tab.clear();
+        d->records.clear();
+        d->raw_tab.clear();
+        d->raw_tab_uploaded = false;
+        d->n_slots = S;
+        d->slot_bytes = 0;
+        ses->dead = true;   // until the feed is through: a failure from here on leaves the tails in neither buffer for certain
+        std::swap(d->bytes.p, ses->other.p);
+        std::swap(d->bytes.cap, ses->other.cap);
+        t0 = Clock::now();
+        d->scan_sync_s[0] = d->scan_sync_s[1] = 0;   // what a feed without a slot reports
+        if (S) {
+            const SessionFill fill{srcs.data(), info.data(), &ses->src_tab, &ses->info_tab};
+            if (int rc = device_scan(d, ScanInput{nullptr, true}, lay, rule, false, want_heads, c, &fill)) return rc;
+        }
+        t1 = Clock::now();
+        return FLACGPU_OK;
+    }
+    void walked() { t2 = Clock::now(); }
+    // the feed is through, its frame table on the device
+    void done() {
+        const auto ms = [](Clock::duration v) { return std::chrono::duration<double, std::milli>(v).count(); };
+        flacgpu_session_timing &t = ses->timing;
+        t.to_first_sync_ms = ses->d->scan_sync_s[0] * 1e3;
+        t.to_second_sync_ms = ses->d->scan_sync_s[1] * 1e3;
+        t.scan_rest_ms = ms(t1 - t0) - t.to_first_sync_ms - t.to_second_sync_ms;
+        t.walk_ms = ms(t2 - t1);
+        t.table_upload_ms = ms(Clock::now() - t2);
+        ses->dead = false;
+    }
+};
+
 // One feed behind its argument checks (finish: no bytes, every stream flushed).  chunk[i]: DEVICE address of stream i's
 // new bytes (null: none), len[i] their count.  The slots are tail + chunk, built and scanned on the device; the host
 // walks the links as scan_raw_impl does, stops at the first LINK_HOLD and keeps the session's counts.
@@ -649,65 +731,27 @@ int session_step(flacgpu_decoder_session *ses, const uint8_t *const *chunk, cons
                  bool finish) {
     flacgpu_decoder *d = ses->d;
     const uint32_t n = (uint32_t)ses->streams.size();
-    SlotLayout lay;
-    Candidates c;
-    std::vector<SessionSrc> srcs;
-    std::vector<SessionSlot> info;
-    const uint8_t *const tails = d->bytes.as<const uint8_t>();   // `other` from the swap below on
-    // the feed's layout and the decoder's new per-stream tables, in locals: a call refused below has touched neither the
-    // session nor its decoder, whose last feed can still be decoded
-    std::vector<flacgpu_decoded_stream> res;
-    std::vector<int32_t> slot_of;
-    std::vector<flacgpu_raw_stream> raw_streams;
+    SessionFeed feed(ses);
     try {
-        res.assign(n, flacgpu_decoded_stream{});
-        slot_of.assign(n, -1);
-        raw_streams.assign(n, flacgpu_raw_stream{});
+        feed.begin(n);
         for (uint32_t i = 0; i < n; i++) {
             const flacgpu_decoder_session::Stream &st = ses->streams[i];
             const uint64_t fresh = chunk && chunk[i] ? len[i] : 0;
-            if (!(st.held + fresh)) continue;   // nothing held, nothing new
-            slot_of[i] = (int32_t)lay.add(i, 0, st.held + fresh, 0, 0);
-            srcs.push_back(SessionSrc{reinterpret_cast<uint64_t>(tails + st.at), st.held,
-                                      fresh ? reinterpret_cast<uint64_t>(chunk[i]) : 0, fresh});
-            info.push_back(SessionSlot{finish || (flush && flush[i]) ? 1u : 0u, ses->W});
+            if (st.held + fresh)   // else nothing held, nothing new
+                feed.add(i, st, fresh ? chunk[i] : nullptr, fresh, finish || (flush && flush[i]), 0, 0);
         }
     } catch (const std::bad_alloc &) {
         g_last_error = "flacgpu_decoder_session_feed: out of host memory";
         return FLACGPU_ERR_UNSUPPORTED;
     }
-    const uint32_t S = (uint32_t)lay.slots.size();
-    if (lay.at + 64 > ((uint64_t)1 << 34)) {   // device_scan's limit, before anything has changed
-        g_last_error = "flacgpu_decoder_session_feed: the feed's slots exceed 16 GiB";
-        return FLACGPU_ERR_UNSUPPORTED;
-    }
-    // ---- from here on the feed is under way (nothing below up to the scan allocates)
-    d->scanned = d->raw = false;
-    d->res.swap(res);
-    d->slot_of.swap(slot_of);
-    d->raw_streams.swap(raw_streams);
-    d->frame_tab.clear();
-    d->records.clear();
-    d->n_slots = S;
-    d->slot_bytes = 0;
-    ses->dead = true;   // until the feed is through: a failure from here on leaves the tails in neither buffer for certain
-    std::swap(d->bytes.p, ses->other.p);
-    std::swap(d->bytes.cap, ses->other.cap);
-    const auto t0 = std::chrono::steady_clock::now();
-    if (S) {
-        const SessionFill fill{srcs.data(), info.data(), &ses->src_tab, &ses->info_tab};
-        if (int rc = device_scan(d, ScanInput{nullptr, true}, lay, true, false, true, c, &fill)) return rc;
-    } else {
-        d->scan_sync_s[0] = d->scan_sync_s[1] = 0;
-    }
-    const auto t1 = std::chrono::steady_clock::now();
-    std::vector<ManyFrame> &all = d->raw_tab;
-    all.clear();
-    d->raw_tab_uploaded = false;
+    if (int rc = feed.refused()) return rc;
+    if (int rc = feed.commit_and_scan(LinkRule::Session, true)) return rc;
+    const SlotLayout &lay = feed.lay;
+    const Candidates &c = feed.c;
     RawTotals tot;
     try {
         d->records.reserve(c.n);
-        all.reserve(c.n);
+        d->raw_tab.reserve(c.n);
         d->frame_tab.reserve(c.n);
         for (uint32_t i = 0; i < n; i++) {
             flacgpu_decoder_session::Stream &st = ses->streams[i];
@@ -722,7 +766,7 @@ int session_step(flacgpu_decoder_session *ses, const uint8_t *const *chunk, cons
                                        c.heads.data() + kHeadBytes * k, false, tot);
                     },
                     &st.count);
-                const uint64_t h = flacenc::session_hold(w, sl.base, sl.len, info[s].final, st.count);
+                const uint64_t h = flacenc::session_hold(w, sl.base, sl.len, feed.info[s].final, st.count);
                 st.base += h - sl.base;
                 st.held = sl.base + sl.len - h;
                 st.at = h;
@@ -736,16 +780,9 @@ int session_step(flacgpu_decoder_session *ses, const uint8_t *const *chunk, cons
         g_last_error = "flacgpu_decoder_session_feed: out of host memory";
         return FLACGPU_ERR_UNSUPPORTED;
     }
-    const auto t2 = std::chrono::steady_clock::now();
-    if (int rc = finish_raw_scan(d, lay, tot, "flacgpu_decoder_session_feed")) return rc;
-    const auto t3 = std::chrono::steady_clock::now();
-    const auto ms = [](std::chrono::steady_clock::duration v) { return std::chrono::duration<double, std::milli>(v).count(); };
-    ses->timing.to_first_sync_ms = d->scan_sync_s[0] * 1e3;
-    ses->timing.to_second_sync_ms = d->scan_sync_s[1] * 1e3;
-    ses->timing.scan_rest_ms = ms(t1 - t0) - ses->timing.to_first_sync_ms - ses->timing.to_second_sync_ms;
-    ses->timing.walk_ms = ms(t2 - t1);
-    ses->timing.table_upload_ms = ms(t3 - t2);
-    ses->dead = false;
+    feed.walked();
+    if (int rc = finish_raw_scan(d, feed.lay, tot, "flacgpu_decoder_session_feed")) return rc;
+    feed.done();
     return FLACGPU_OK;
 }
 
@@ -755,7 +792,6 @@ int session_step(flacgpu_decoder_session *ses, const uint8_t *const *chunk, cons
 // host feed has changed it, and comes down with the counts.  Nothing of the session changes but that table and its flag.
 int container_meta(flacgpu_decoder_session *ses, int door, const uint8_t *const *data, const size_t *len,
                    std::vector<MetaFeed> &meta, std::vector<uint64_t> &used) {
-    using Ses = flacgpu_decoder_session;
     flacgpu_decoder *d = ses->d;
     const uint32_t n = (uint32_t)ses->cs.size();
     std::vector<DevSource> src;
@@ -771,7 +807,7 @@ int container_meta(flacgpu_decoder_session *ses, int door, const uint8_t *const 
     }
     for (uint32_t i = 0; i < n; i++) {
         meta[i] = ses->cs[i].meta;
-        if (door == 2 || ses->cs[i].phase != Ses::CS_META || !data[i] || !len[i]) continue;
+        if (door == 2 || ses->cs[i].phase != flacenc::CS_META || !data[i] || !len[i]) continue;
         any = true;
         if (door == 0) used[i] = meta_feed(meta[i], data[i], len[i]);
         else src[i] = DevSource{data[i], len[i]};
@@ -800,99 +836,43 @@ int container_meta(flacgpu_decoder_session *ses, int door, const uint8_t *const 
 
 // One feed of a container session behind its argument checks and container_meta (finish: no bytes, the input ends).
 // chunk[i]: DEVICE address of what stream i was fed behind its metadata (null: none), len[i] the count; fed_now[i]: all
-// the bytes it was fed.  A stream in its frame phase gets a slot of tail + chunk with STREAMINFO's channels and
-// min_frame; the device finds the regular scan's candidates and links them by the rule (k_link_container), and the host
-// follows the chain from the cursor (regular_walk, host/raw_walk.h) as scan_impl follows k_link's.  The decoder is left
-// as scan_impl leaves it, for the batch "every STREAMINFO with the frames decided now".
+// the bytes it was fed.  The rule of a stream is host/container_rule.h's; a stream in its frame phase gets a slot of
+// tail + chunk with STREAMINFO's channels and min_frame, the device finds the regular scan's candidates and links them by
+// the rule (k_link_container), and the host follows the chain from the cursor as scan_impl follows k_link's.  The
+// decoder is left as scan_impl leaves it, for the batch "every STREAMINFO with the frames decided now".
 int container_step(flacgpu_decoder_session *ses, const uint8_t *const *chunk, const uint64_t *len, const uint64_t *fed_now,
                    const std::vector<MetaFeed> &meta, bool finish) {
     using Ses = flacgpu_decoder_session;
     flacgpu_decoder *d = ses->d;
     const uint32_t n = (uint32_t)ses->streams.size();
-    SlotLayout lay;
-    Candidates c;
-    std::vector<SessionSrc> srcs;
-    std::vector<SessionSlot> info;
-    const uint8_t *const tails = d->bytes.as<const uint8_t>();   // `other` from the swap below on
-    // everything the feed changes, in locals: a call refused below has touched neither the session nor its decoder
-    std::vector<flacgpu_decoded_stream> res;
-    std::vector<int32_t> slot_of;
-    std::vector<flacgpu_raw_stream> raw_streams;
-    std::vector<Ses::Stream> streams;
+    SessionFeed feed(ses);
+    std::vector<Ses::Stream> streams;   // the session's own state in copies, swapped in at the commit
     std::vector<Ses::Container> cs;
     try {
-        res.assign(n, flacgpu_decoded_stream{});
-        slot_of.assign(n, -1);
-        raw_streams.assign(n, flacgpu_raw_stream{});
+        feed.begin(n);
         streams = ses->streams;
         cs = ses->cs;
         for (uint32_t i = 0; i < n; i++) {
             Ses::Container &k = cs[i];
             Ses::Stream &st = streams[i];
-            k.fed += fed_now[i];
             if (!ses->hashed && k.in_feed) k.broken = true;   // the feed before decided frames that were never hashed
             k.in_feed = false;
-            if (k.phase == Ses::CS_META) {
-                k.meta = meta[i];
-                if (k.meta.phase == MF_DONE || k.meta.phase == MF_REFUSED || finish) {
-                    MetaRecord rec;
-                    meta_feed_record(k.meta, k.meta.phase == MF_DONE ? k.meta.taken : k.fed, rec);
-                    size_t at = 0;
-                    if (flacenc::metadata_of_record(rec, &k.info, &k.min_frame, &at)) {
-                        k.phase = Ses::CS_REFUSED;
-                    } else {
-                        k.phase = Ses::CS_FRAMES;
-                        st.base = at;
-                    }
-                }
-            }
+            flacenc::container_begin(k, meta[i], fed_now[i], finish, &st.base);
             const uint64_t fresh = chunk && chunk[i] ? len[i] : 0;
-            if (k.phase == Ses::CS_FRAMES && st.held + fresh) {
-                slot_of[i] = (int32_t)lay.add(i, 0, st.held + fresh, k.info.channels, k.min_frame);
-                srcs.push_back(SessionSrc{reinterpret_cast<uint64_t>(tails + st.at), st.held,
-                                          fresh ? reinterpret_cast<uint64_t>(chunk[i]) : 0, fresh});
-                info.push_back(SessionSlot{finish ? 1u : 0u, ses->W});
-            } else if (k.phase == Ses::CS_LOST) {
-                k.skipped += fed_now[i];
-            }
-            if (k.phase == Ses::CS_REFUSED) k.skipped = k.fed;
+            if (k.phase == flacenc::CS_FRAMES && st.held + fresh)
+                feed.add(i, st, fresh ? chunk[i] : nullptr, fresh, finish, k.info.channels, k.min_frame);
         }
     } catch (const std::bad_alloc &) {
         g_last_error = "flacgpu_decoder_session_feed: out of host memory";
         return FLACGPU_ERR_UNSUPPORTED;
     }
-    const uint32_t S = (uint32_t)lay.slots.size();
-    if (lay.at + 64 > ((uint64_t)1 << 34)) {   // device_scan's limit, before anything has changed
-        g_last_error = "flacgpu_decoder_session_feed: the feed's slots exceed 16 GiB";
-        return FLACGPU_ERR_UNSUPPORTED;
-    }
-    // ---- from here on the feed is under way (nothing below up to the scan allocates)
-    d->scanned = d->raw = false;
-    d->res.swap(res);
-    d->slot_of.swap(slot_of);
-    d->raw_streams.swap(raw_streams);
-    d->frame_tab.clear();
-    d->records.clear();
-    d->raw_tab.clear();
-    d->raw_tab_uploaded = false;
-    d->n_slots = S;
-    d->slot_bytes = 0;
+    if (int rc = feed.refused()) return rc;
     ses->streams.swap(streams);
     ses->cs.swap(cs);
-    ses->dead = true;   // until the feed is through
-    std::swap(d->bytes.p, ses->other.p);
-    std::swap(d->bytes.cap, ses->other.cap);
-    const auto t0 = std::chrono::steady_clock::now();
-    if (S) {
-        SessionFill fill{srcs.data(), info.data(), &ses->src_tab, &ses->info_tab};
-        fill.container = true;
-        if (int rc = device_scan(d, ScanInput{nullptr, true}, lay, false, false, false, c, &fill)) return rc;
-    } else {
-        d->scan_sync_s[0] = d->scan_sync_s[1] = 0;
-    }
-    const auto t1 = std::chrono::steady_clock::now();
+    if (int rc = feed.commit_and_scan(LinkRule::Container, false)) return rc;
+    const SlotLayout &lay = feed.lay;
     try {
-        d->frame_tab.reserve(c.n);
+        d->frame_tab.reserve(feed.c.n);
         for (uint32_t i = 0; i < n; i++) {
             Ses::Container &k = ses->cs[i];
             Ses::Stream &st = ses->streams[i];
@@ -901,43 +881,14 @@ int container_step(flacgpu_decoder_session *ses, const uint8_t *const *chunk, co
             uint64_t samples = 0;
             if (s >= 0) {
                 const ScanSlot &sl = lay.slots[s];
-                const uint64_t slot_end = sl.base + sl.len;
-                const flacenc::RegularWalk w = flacenc::regular_walk(
-                    c.pos.data(), c.cand0[s], c.end_of((uint32_t)s), sl.base, slot_end,
-                    flacenc::session_judged(sl.base, sl.len, finish),
-                    [&](size_t q, uint64_t) {
-                        const int32_t link = c.link[q];
-                        if (link == LINK_HOLD) return flacenc::RawEnd{flacenc::kRawHold, false};
-                        if (link == LINK_NONE) return flacenc::RawEnd{flacenc::kRawNone, false};
-                        return flacenc::RawEnd{link == LINK_END ? slot_end : c.pos[link], false};
-                    },
-                    [&](size_t q, uint64_t at, uint64_t end) {
-                        ManyFrame f{};
-                        f.start = at;
-                        f.end = end;
-                        f.cap = lay.end_of((uint32_t)s) - 4;
-                        f.n = (c.info[q] & 0xFFFFu) + 1u;
-                        f.slot = (uint32_t)s;
-                        f.channels = k.info.channels;
-                        f.bps = k.info.bits_per_sample;
-                        f.out = samples;   // stream-relative here, made absolute below
-                        d->frame_tab.push_back(f);
-                        samples += f.n;
-                    });
+                const flacenc::RegularWalk w = walk_regular_slot(d, feed.c, lay, (uint32_t)s,
+                                                                 flacenc::session_judged(sl.base, sl.len, finish), k.info, &samples);
+                k.bad_frames += w.lost;
                 st.base += w.cursor - sl.base;
-                if (w.lost) {   // nothing from the cursor on is kept, now or later
-                    k.phase = Ses::CS_LOST;
-                    k.bad_frames++;
-                    k.skipped += slot_end - w.cursor;
-                    st.held = st.at = 0;
-                } else {
-                    st.held = slot_end - w.cursor;
-                    st.at = w.cursor;
-                }
+                st.held = flacenc::container_end(k, w, sl.base + sl.len, d->frame_tab.size() - first, samples);
+                st.at = w.cursor;
             }
             const size_t F = d->frame_tab.size() - first;
-            k.frames += F;
-            k.samples += samples;
             k.in_feed = F != 0;
             if (F) {
                 flacgpu_decoded_stream &r = d->res[i];
@@ -949,12 +900,7 @@ int container_step(flacgpu_decoder_session *ses, const uint8_t *const *chunk, co
             } else {
                 d->res[i].rc = FLACGPU_ERR_INVALID_ARG;
             }
-            flacgpu_raw_stream &sum = d->raw_streams[i];
-            sum.first_frame = first;
-            sum.frames = (uint32_t)k.frames;
-            sum.skipped_bytes = k.skipped;
-            sum.gaps = k.skipped ? 1 : 0;
-            sum.uniform = k.phase == Ses::CS_FRAMES || k.phase == Ses::CS_LOST;
+            d->raw_streams[i] = flacenc::container_summary(k, first);
         }
     } catch (const std::bad_alloc &) {
         g_last_error = "flacgpu_decoder_session_feed: out of host memory";
@@ -964,31 +910,13 @@ int container_step(flacgpu_decoder_session *ses, const uint8_t *const *chunk, co
         g_last_error = "flacgpu_decoder_session_feed: more than 2^31 - 1 frames";
         return FLACGPU_ERR_UNSUPPORTED;
     }
-    // ---- output layout, as scan_impl's: streams one after another, interleaved
-    uint64_t total = 0, scratch_total = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        flacgpu_decoded_stream &r = d->res[i];
-        r.out_offset = total;
-        if (r.rc == FLACGPU_OK) total += r.info.decoded_samples * r.info.channels;
-    }
-    for (ManyFrame &f : d->frame_tab) {
-        f.out = d->res[lay.slot_stream[f.slot]].out_offset + f.out * f.channels;
-        f.scratch = scratch_total;
-        scratch_total += (uint64_t)f.channels * ((f.n + 3u) & ~3u);
-    }
-    const auto t2 = std::chrono::steady_clock::now();
-    d->raw_elements = total;
+    const RawTotals tot = lay_out_regular(d, lay);
+    feed.walked();
+    d->raw_elements = tot.total;
     d->raw_scratch = 0;
-    if (int rc = finish_scan(d, lay, total, scratch_total)) return rc;
-    const auto t3 = std::chrono::steady_clock::now();
-    const auto ms = [](std::chrono::steady_clock::duration v) { return std::chrono::duration<double, std::milli>(v).count(); };
-    ses->timing.to_first_sync_ms = d->scan_sync_s[0] * 1e3;
-    ses->timing.to_second_sync_ms = d->scan_sync_s[1] * 1e3;
-    ses->timing.scan_rest_ms = ms(t1 - t0) - ses->timing.to_first_sync_ms - ses->timing.to_second_sync_ms;
-    ses->timing.walk_ms = ms(t2 - t1);
-    ses->timing.table_upload_ms = ms(t3 - t2);
+    if (int rc = finish_scan(d, feed.lay, tot.total, tot.scratch_total)) return rc;
     ses->hashed = d->frame_tab.empty();
-    ses->dead = false;
+    feed.done();
     return FLACGPU_OK;
 }
 
@@ -2000,7 +1928,7 @@ int flacgpu_decoder_session_verdict(flacgpu_decoder_session *s, flacgpu_decoded_
         flacgpu_decoded_stream &r = res[i];
         r.out_offset = total;   // the one-shot batch's layout
         r.info = k.info;
-        if (k.phase == flacgpu_decoder_session::CS_REFUSED) {
+        if (k.phase == flacenc::CS_REFUSED) {
             r.rc = FLACGPU_ERR_INVALID_ARG;
             continue;
         }
@@ -2089,42 +2017,28 @@ static int session_call(flacgpu_decoder_session *s, int door, const uint8_t *con
         g_last_error = std::string(who) + ": out of host memory";
         return FLACGPU_ERR_UNSUPPORTED;
     }
-    if (door == 1) {
-        if (int rc = open_device_door(d, data, len, n, stream, who)) {
-            s->dead = rc == FLACGPU_ERR_HIP;
-            return rc;
+    int rc = door == 1 ? open_device_door(d, data, len, n, stream, who) : FLACGPU_OK;
+    // a container's metadata is walked where it lies: device chunks on the decoder's stream, behind the caller's
+    if (!rc && s->container) rc = container_meta(s, door, data, len, meta, used);
+    if (rc) {
+        s->dead = rc == FLACGPU_ERR_HIP;
+        return rc;
+    }
+    for (uint32_t i = 0; door != 2 && i < n; i++)
+        if (data[i] && len[i]) {
+            fed_now[i] = len[i];
+            fed += len[i];
+            if (s->container && s->cs[i].phase >= flacenc::CS_LOST) continue;   // dropped
+            bytes[i] = len[i] - used[i];   // the metadata's bytes are not the scan's
+            fresh += bytes[i];
+            if (door == 1 && bytes[i]) chunk[i] = data[i] + used[i];
         }
-        if (s->container)   // on the decoder's stream, behind the caller's: the metadata is walked where it lies
-            if (int rc = container_meta(s, door, data, len, meta, used)) {
-                s->dead = rc == FLACGPU_ERR_HIP;
-                return rc;
-            }
-        for (uint32_t i = 0; i < n; i++)
-            if (data[i] && len[i]) {
-                fed_now[i] = len[i];
-                fed += len[i];
-                if (s->container && s->cs[i].phase >= flacgpu_decoder_session::CS_LOST) continue;   // dropped
-                if (len[i] == used[i]) continue;
-                chunk[i] = data[i] + used[i];
-                bytes[i] = len[i] - used[i];
-                fresh += bytes[i];
-            }
-    } else if (door == 0) {
+    if (door == 0) {
         // the chunks alone go up: into the pinned staging at 16-byte boundaries, one copy, and the kernel joins them to
         // the tails that never left the device
-        if (s->container)
-            if (int rc = container_meta(s, door, data, len, meta, used)) return rc;
-        for (uint32_t i = 0; i < n; i++)
-            if (data[i] && len[i]) {
-                fed_now[i] = len[i];
-                fed += len[i];
-                if (s->container && s->cs[i].phase >= flacgpu_decoder_session::CS_LOST) continue;   // dropped
-                bytes[i] = len[i] - used[i];   // the metadata's bytes never go up
-                fresh += bytes[i];
-            }
         const uint64_t up = fresh + 16 * (uint64_t)n;
         if (fresh) {
-            int rc = d->staging.ensure(up);
+            rc = d->staging.ensure(up);
             if (!rc) rc = s->chunks.ensure(up);
             if (rc) {
                 s->dead = rc == FLACGPU_ERR_HIP;
@@ -2147,9 +2061,9 @@ static int session_call(flacgpu_decoder_session *s, int door, const uint8_t *con
         }
     }
     const double stage_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_in).count();
+    // s->fed counts what the session took in: all a container session was fed, its metadata and the bytes of dropped
+    // streams included (`fed`); of a raw session the bytes that went to the scan (`fresh`), which are all it was fed
     if (s->container) {
-        if (door == 2)
-            if (int rc = container_meta(s, door, data, len, meta, used)) return rc;
         if (int rc = container_step(s, chunk.data(), bytes.data(), fed_now.data(), meta, door == 2)) return rc;
         if (s->meta_fresh) s->meta_on_device = true;   // the feed is committed: the table is the streams' state
         s->timing.stage_ms = stage_ms;

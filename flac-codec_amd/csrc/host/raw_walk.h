@@ -1,8 +1,11 @@
 // raw_walk.h -- the walk that turns a raw frame stream's candidate headers into kept frames (DESIGN.md 4b "Raw frame
 // streams", "Decoder sessions"), stated once for its four callers: the host rules (scan_raw_frames, flac_stream.cpp;
 // session_decide, session_rule.cpp), which find a candidate's end with CRC-16 loops, and the batch decoder's two
-// (scan_raw_impl, session_step: decode_many.hip), which read it from the device scan's tables.  Beside it what those
-// callers build around a walk alike.  Header only, plain C++: no HIP call, no global state.
+// (scan_raw_impl, session_step: decode_many.hip, through walk_slot), which read it from the device scan's tables.
+// Beside it what those callers build around a walk alike, and regular_walk, the chain of a regular stream's frames, for
+// its three: container_decide (session_rule.cpp) with CRC-16 loops, scan_impl and container_step (decode_many.hip,
+// through walk_regular_slot) from the device's links.  The rest of a container session's rule is container_rule.h's.
+// Header only, plain C++: no HIP call, no global state.
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -84,7 +87,7 @@ static inline uint64_t session_hold(const RawWalk &w, uint64_t begin, uint64_t l
     return h;
 }
 
-// ---- a container session's walk (DESIGN.md 4b "Container sessions") ----
+// ---- a regular stream's walk: the one-shot scan's, and a container session's (DESIGN.md 4b "Container sessions") ----
 // A regular stream's frames are a chain from the cursor: the frame at the cursor ends where the next begins, and a
 // cursor that is no candidate, or a frame without an end, loses the stream for good.
 struct RegularWalk {

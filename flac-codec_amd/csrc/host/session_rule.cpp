@@ -5,8 +5,7 @@
 #include <algorithm>
 #include <new>
 
-#include "../kernels/meta_feed_rule.h"
-#include "raw_walk.h"
+#include "container_rule.h"
 
 namespace flacenc {
 RegularWalk container_decide(const uint8_t *d, size_t L, bool final, uint32_t W, const flacgpu_stream_info &info,
@@ -80,21 +79,13 @@ struct flacgpu_session_host {
     struct Stream {
         std::vector<uint8_t> held;   // the bytes that cannot be judged yet
         uint64_t base = 0;           // offset of held[0] from the stream's first byte
-        flacenc::SessionCount count;
-        // a container session's (DESIGN.md 4b "Container sessions")
-        MetaFeed meta{};
-        uint32_t phase = 0;         // CS_*
-        uint64_t fed = 0;            // bytes fed to this stream
-        flacgpu_stream_info info{};  // STREAMINFO, from CS_FRAMES on
-        uint32_t min_frame = 0;
+        flacenc::SessionCount count;     // a raw session's
+        flacenc::ContainerStream rule;   // a container session's (host/container_rule.h)
     };
     std::vector<Stream> streams;
     uint32_t W = 0;
     bool finished = false, container = false;
 };
-namespace {
-enum : uint32_t { CS_META = 0, CS_FRAMES = 1, CS_LOST = 2, CS_REFUSED = 3 };
-}
 
 int flacgpu_session_host_open(uint32_t n_streams, uint32_t max_frame_bytes, flacgpu_session_host **out) {
     if (!out) return FLACGPU_ERR_INVALID_ARG;
@@ -114,7 +105,7 @@ int flacgpu_session_host_open(uint32_t n_streams, uint32_t max_frame_bytes, flac
 int flacgpu_session_host_open_container(uint32_t n_streams, uint32_t max_frame_bytes, flacgpu_session_host **out) {
     if (int rc = flacgpu_session_host_open(n_streams, max_frame_bytes, out)) return rc;
     (*out)->container = true;
-    for (flacgpu_session_host::Stream &st : (*out)->streams) meta_feed_init(st.meta);
+    for (flacgpu_session_host::Stream &st : (*out)->streams) meta_feed_init(st.rule.meta);
     return FLACGPU_OK;
 }
 
@@ -162,49 +153,25 @@ static int container_host_step(flacgpu_session_host *s, const uint8_t *const *da
         uint64_t elements = 0;
         for (uint32_t i = 0; i < n; i++) {
             flacgpu_session_host::Stream &st = next[i];
+            flacenc::ContainerStream &k = st.rule;
             const uint8_t *chunk = !finish && data[i] && len[i] ? data[i] : nullptr;
-            size_t fresh = chunk ? len[i] : 0;
-            st.fed += fresh;
+            const size_t fresh = chunk ? len[i] : 0;
             const size_t first = recs.size();
-            if (st.phase == CS_META) {
-                const size_t used = (size_t)meta_feed(st.meta, chunk, fresh);
-                if (st.meta.phase == MF_DONE || st.meta.phase == MF_REFUSED || finish) {
-                    MetaRecord rec;
-                    meta_feed_record(st.meta, st.meta.phase == MF_DONE ? st.meta.taken : st.fed, rec);
-                    size_t at = 0;
-                    if (flacenc::metadata_of_record(rec, &st.info, &st.min_frame, &at)) st.phase = CS_REFUSED;
-                    else {
-                        st.phase = CS_FRAMES;
-                        st.base = at;
-                    }
-                }
-                chunk = chunk ? chunk + used : nullptr;   // metadata bytes are never held
-                fresh -= used;
-            }
-            if (st.phase == CS_FRAMES) {
-                if (fresh) st.held.insert(st.held.end(), chunk, chunk + fresh);
-                const flacenc::RegularWalk w = flacenc::container_decide(st.held.data(), st.held.size(), finish, s->W, st.info,
-                                                                         st.min_frame, st.base, i, recs, &elements);
-                st.count.frames += (uint32_t)(recs.size() - first);
+            MetaFeed meta = k.meta;
+            const size_t used = k.phase == flacenc::CS_META ? (size_t)meta_feed(meta, chunk, fresh) : 0;
+            flacenc::container_begin(k, meta, fresh, finish, &st.base);
+            if (k.phase == flacenc::CS_FRAMES) {
+                if (fresh > used) st.held.insert(st.held.end(), chunk + used, chunk + fresh);   // metadata is never held
+                const size_t L = st.held.size();
+                const flacenc::RegularWalk w =
+                    flacenc::container_decide(st.held.data(), L, finish, s->W, k.info, k.min_frame, st.base, i, recs, &elements);
+                uint64_t samples = 0;
+                for (size_t q = first; q < recs.size(); q++) samples += recs[q].block_size;
                 st.base += w.cursor;
-                if (w.lost) {
-                    st.phase = CS_LOST;
-                    st.count.skipped = st.held.size() - w.cursor;
-                    st.held.clear();
-                } else {
-                    st.held.erase(st.held.begin(), st.held.begin() + w.cursor);
-                }
-            } else if (st.phase == CS_LOST) {
-                st.count.skipped += fresh;
+                st.held.erase(st.held.begin(), st.held.begin() + w.cursor);
+                st.held.resize((size_t)flacenc::container_end(k, w, L, recs.size() - first, samples));
             }
-            if (st.phase == CS_REFUSED) st.count.skipped = st.fed;
-            flacgpu_raw_stream &sum = sums[i];
-            sum = flacgpu_raw_stream{};
-            sum.first_frame = first;
-            sum.frames = st.count.frames;
-            sum.skipped_bytes = st.count.skipped;
-            sum.gaps = st.count.skipped ? 1 : 0;
-            sum.uniform = st.phase == CS_FRAMES || st.phase == CS_LOST;
+            sums[i] = flacenc::container_summary(k, first);
         }
         *total_frames = recs.size();
         if (recs.size() > cap || (!recs.empty() && !records)) return FLACGPU_ERR_BUFFER_TOO_SMALL;
