@@ -149,3 +149,19 @@ void launch_autocorr_mfma(const Params &p, uint32_t blocks, uint32_t n, const do
     hipLaunchKernelGGL(k_autocorr_mfma, dim3(blocks), dim3(WG), 0, st, p, n, win, ac);
 }
 }  // namespace flacgpu_k
+
+#if AC4_TIMELINE
+// measurement builds only (tools/ac4_timeline.py): the tile records of the last k_autocorr4 launches, copied to the host
+// (clear != 0: zeroed afterwards); returns the buffer's size in bytes, 0 on a HIP error
+extern "C" size_t flacgpu_ac4_timeline(void *dst, size_t bytes, int clear) {
+    const size_t all = sizeof(uint32_t) * AC4_TL_WAVES * AC4_TL_TILES * AC4_TL_WORDS;
+    if (hipDeviceSynchronize() != hipSuccess) return 0;
+    if (dst && hipMemcpyFromSymbol(dst, HIP_SYMBOL(ac4_tl), bytes < all ? bytes : all) != hipSuccess) return 0;
+    if (clear) {
+        void *sym = nullptr;
+        if (hipGetSymbolAddress(&sym, HIP_SYMBOL(ac4_tl)) != hipSuccess || hipMemset(sym, 0, all) != hipSuccess) return 0;
+        if (hipDeviceSynchronize() != hipSuccess) return 0;
+    }
+    return all;
+}
+#endif

@@ -187,17 +187,51 @@ constexpr Ac4Share ac4_share(int ns, int lg0, int lg1, int lg2, int lg3) {
     return ac4_share_n<STEREO>(ns, lg);
 }
 
+// A staged load is a GLOBAL load whatever the compiler knows about its pointer (a frame pointer read from Params::inter_tab
+// is a generic one): while a flat load is in flight gfx9 cannot count vmcnt, and every wait would be for all the staging sets.
+// (One set: the loads as they were, nothing to count.)
+// The staging sets of a producer: AC4_FETCH_DEPTH (kernels/shape.h) for the stereo producers; ONE for independent channels,
+// whose units carry more per-unit state (row pointers, the planar copy's) -- a second set takes those instantiations from
+// four waves per SIMD to three (or from three to two), and held to their occupancy they spill (DESIGN.md section 4).
+template <bool STEREO>
+constexpr int ac4_depth() { return STEREO ? AC4_FETCH_DEPTH : 1; }
+#define AC4_DEPTH_OF(P) (std::remove_cv_t<std::remove_reference_t<decltype(P)>>::DEPTH)
+typedef int32_t ac4_i2 __attribute__((ext_vector_type(2)));
+typedef double ac4_d2 __attribute__((ext_vector_type(2)));
+template <int DEPTH, class T>
+__device__ __forceinline__ T ac4_ld(const void *q) {
+    if constexpr (DEPTH > 1) return *(const __attribute__((address_space(1))) T *)q;
+    else return *reinterpret_cast<const T *>(q);
+}
+template <int DEPTH>
+__device__ __forceinline__ int2 ac4_ld_int2(const void *q) {
+    const ac4_i2 v = ac4_ld<DEPTH, ac4_i2>(q);
+    return make_int2(v.x, v.y);
+}
+template <int DEPTH>
+__device__ __forceinline__ double2 ac4_ld_double2(const void *q) {
+    const ac4_d2 v = ac4_ld<DEPTH, ac4_d2>(q);
+    return make_double2(v.x, v.y);
+}
+// The ORs of a conversion are formed where it stands and not wherever their first reader is (the kernel's tail): left to
+// sink behind the f64 blocks they keep the staged registers alive across the request that refills them, and the loop then
+// copies whole sets at its end -- behind a wait for every load in flight.
+template <int DEPTH>
+__device__ __forceinline__ void ac4_pin(uint32_t &v) {
+    if constexpr (DEPTH > 1) asm volatile("" : "+v"(v));
+}
 template <int U, bool STEREO>
 struct Ac4Producer {
     static constexpr int NU = U > 0 ? U : 1;
+    static constexpr int DEPTH = ac4_depth<STEREO>();
     const int32_t *gsrc[NU];   // this lane's 2 samples of tile 0, per unit
     const double *wsrc[NU];    // their window values (tile 0)
     uint32_t dst_a[NU], dst_b[NU];  // f64 indices of the two converted rows inside a buffer (+ column)
     uint32_t sh_a[NU], sh_b[NU];    // right shifts (wasted bits; mid: + 1)
     int32_t sgn;                // second output = other + sgn * own (L-lanes: mid, R-lanes: side)
     uint32_t ntiles;
-    int2 stage[NU];
-    double2 wst[NU];
+    int2 stage[DEPTH][NU];     // the rotating staging sets (ac4_fetch_slot, kernels/shape.h)
+    double2 wst[DEPTH][NU];
 };
 
 // U units per tile for this wave, the first of them U0
@@ -250,22 +284,23 @@ __device__ __forceinline__ void ac4_setup(const Params &p, uint32_t frame0, uint
         }
     }
 }
-template <int U, bool STEREO>
+// the loads of tile t (clamped to the frame) into staging set SET = ac4_fetch_slot(t).set
+template <int SET, int U, bool STEREO>
 __device__ __forceinline__ void ac4_fetch(Ac4Producer<U, STEREO> &P, uint32_t t) {
-    t = t < P.ntiles ? t : P.ntiles - 1;
+    t = ac4_fetch_slot(t, P.ntiles, AC4_DEPTH_OF(P)).tile;
 #pragma unroll
     for (int it = 0; it < U; it++) {
-        P.stage[it] = *reinterpret_cast<const int2 *>(P.gsrc[it] + t * AC4_TS);
-        P.wst[it] = *reinterpret_cast<const double2 *>(P.wsrc[it] + t * AC4_TS);
+        P.stage[SET][it] = ac4_ld_int2<AC4_DEPTH_OF(P)>(P.gsrc[it] + t * AC4_TS);
+        P.wst[SET][it] = ac4_ld_double2<AC4_DEPTH_OF(P)>(P.wsrc[it] + t * AC4_TS);
     }
 }
 // windowed[i] = (f64)x[i] * w[i] (encode.rs:1799) of the staged samples into buffer `dst`
-template <int U, bool STEREO>
+template <int SET, int U, bool STEREO>
 __device__ __forceinline__ void ac4_convert(const Ac4Producer<U, STEREO> &P, double *dst) {
 #pragma unroll
     for (int it = 0; it < U; it++) {
-        const double w[2] = {P.wst[it].x, P.wst[it].y};
-        const int32_t own[2] = {P.stage[it].x, P.stage[it].y};
+        const double w[2] = {P.wst[SET][it].x, P.wst[SET][it].y};
+        const int32_t own[2] = {P.stage[SET][it].x, P.stage[SET][it].y};
         double a[2], b[2];
 #pragma unroll
         for (int e = 0; e < 2; e++) {
@@ -295,14 +330,15 @@ __device__ __forceinline__ void ac4_convert(const Ac4Producer<U, STEREO> &P, dou
 template <int U>
 struct Ac4Direct {
     static constexpr int NU = U > 0 ? U : 1;
+    static constexpr int DEPTH = ac4_depth<true>();
     const int32_t *gsrc[NU];   // this lane's (l, r) of tile 0
     const double *wsrc[NU];
     uint32_t dst[NU];          // f64 index of the L entry; R, mid, side follow at AC4_LDW strides
     uint32_t orow[NU];         // candidate row of L within the group
     uint32_t ors[NU][4];
     uint32_t ntiles;
-    int2 stage[NU];
-    double wst[NU];
+    int2 stage[DEPTH][NU];
+    double wst[DEPTH][NU];
 };
 template <int U, int U0>
 __device__ __forceinline__ void ac4_setup_direct(const Params &p, uint32_t frame0, uint32_t nframes, uint32_t n,
@@ -324,29 +360,31 @@ __device__ __forceinline__ void ac4_setup_direct(const Params &p, uint32_t frame
         for (int c = 0; c < 4; c++) P.ors[it][c] = 0;
     }
 }
-template <int U>
+template <int SET, int U>
 __device__ __forceinline__ void ac4_fetch(Ac4Direct<U> &P, uint32_t t) {
-    t = t < P.ntiles ? t : P.ntiles - 1;
+    t = ac4_fetch_slot(t, P.ntiles, AC4_DEPTH_OF(P)).tile;
 #pragma unroll
     for (int it = 0; it < U; it++) {
-        P.stage[it] = *reinterpret_cast<const int2 *>(P.gsrc[it] + t * (AC4_TS * 2));
-        P.wst[it] = P.wsrc[it][t * AC4_TS];
+        P.stage[SET][it] = ac4_ld_int2<AC4_DEPTH_OF(P)>(P.gsrc[it] + t * (AC4_TS * 2));
+        P.wst[SET][it] = ac4_ld<AC4_DEPTH_OF(P), double>(P.wsrc[it] + t * AC4_TS);
     }
 }
 // (a second copy of this loop without the window multiplications for the tiles under window values of exactly 1.0 was
 // measured SLOWER -- k_autocorr4 0.151 -> 0.156 ms: the copy costs more than four multiplications; the `flat` argument is
 // what is left of it)
-template <int U>
+template <int SET, int U>
 __device__ __forceinline__ void ac4_convert(Ac4Direct<U> &P, double *dst, bool = false) {
 #pragma unroll
     for (int it = 0; it < U; it++) {
-        const int32_t l = P.stage[it].x, r = P.stage[it].y;
+        const int32_t l = P.stage[SET][it].x, r = P.stage[SET][it].y;
         const int32_t m = (l + r) >> 1, sd = l - r;   // <= 24-bit inputs: no overflow (encode.rs:2721, 2734)
-        const double w = P.wst[it];
+        const double w = P.wst[SET][it];
         P.ors[it][0] |= (uint32_t)l;
         P.ors[it][1] |= (uint32_t)r;
         P.ors[it][2] |= (uint32_t)m;
         P.ors[it][3] |= (uint32_t)sd;
+#pragma unroll
+        for (int c = 0; c < 4; c++) ac4_pin<AC4_DEPTH_OF(P)>(P.ors[it][c]);
         double *d = dst + P.dst[it];
         d[0] = (double)l * w;
         d[AC4_LDW] = (double)r * w;
@@ -379,14 +417,15 @@ __device__ __forceinline__ void ac4_finish(const Ac4Direct<U> &P, uint32_t *ors)
 template <int U>
 struct Ac4Split {
     static constexpr int NU = U > 0 ? U : 1;
+    static constexpr int DEPTH = ac4_depth<false>();
     const int32_t *gsrc[NU];   // this lane's first sample of tile 0 (the second one `stride` dwords further)
     int32_t *pdst[NU];         // the same pair in the planar row
     const double *wsrc[NU];
     uint32_t dst[NU], orow[NU], ors[NU];
     uint32_t ntiles, stride;
     bool store;                // false: one channel -- the input IS the planar row (Params::split_dst == nullptr)
-    int2 stage[NU];
-    double2 wst[NU];
+    int2 stage[DEPTH][NU];
+    double2 wst[DEPTH][NU];
 };
 template <int U, int U0>
 __device__ __forceinline__ void ac4_setup_split(const Params &p, uint32_t frame0, uint32_t nframes, uint32_t n,
@@ -411,25 +450,26 @@ __device__ __forceinline__ void ac4_setup_split(const Params &p, uint32_t frame0
         P.ors[it] = 0;
     }
 }
-template <int U>
+template <int SET, int U>
 __device__ __forceinline__ void ac4_fetch(Ac4Split<U> &P, uint32_t t) {
-    t = t < P.ntiles ? t : P.ntiles - 1;
+    t = ac4_fetch_slot(t, P.ntiles, AC4_DEPTH_OF(P)).tile;
 #pragma unroll
     for (int it = 0; it < U; it++) {
         const int32_t *s = P.gsrc[it] + (size_t)t * AC4_TS * P.stride;
-        P.stage[it] = make_int2(s[0], s[P.stride]);
-        P.wst[it] = *reinterpret_cast<const double2 *>(P.wsrc[it] + t * AC4_TS);
+        P.stage[SET][it] = make_int2(ac4_ld<AC4_DEPTH_OF(P), int32_t>(s), ac4_ld<AC4_DEPTH_OF(P), int32_t>(s + P.stride));
+        P.wst[SET][it] = ac4_ld_double2<AC4_DEPTH_OF(P)>(P.wsrc[it] + t * AC4_TS);
     }
 }
-template <int U>
+template <int SET, int U>
 __device__ __forceinline__ void ac4_convert(Ac4Split<U> &P, double *dst, uint32_t t) {
     t = t < P.ntiles ? t : P.ntiles - 1;   // (the prefetch clamps: the last tile is stored twice, same bytes)
 #pragma unroll
     for (int it = 0; it < U; it++) {
-        const int2 v = P.stage[it];
+        const int2 v = P.stage[SET][it];
         P.ors[it] |= (uint32_t)v.x | (uint32_t)v.y;
+        ac4_pin<AC4_DEPTH_OF(P)>(P.ors[it]);
         if (P.store) *reinterpret_cast<int2 *>(P.pdst[it] + t * AC4_TS) = v;
-        *reinterpret_cast<double2 *>(dst + P.dst[it]) = make_double2((double)v.x * P.wst[it].x, (double)v.y * P.wst[it].y);
+        *reinterpret_cast<double2 *>(dst + P.dst[it]) = make_double2((double)v.x * P.wst[SET][it].x, (double)v.y * P.wst[SET][it].y);
     }
 }
 template <int U>
@@ -449,13 +489,14 @@ __device__ __forceinline__ void ac4_finish(const Ac4Split<U> &P, uint32_t *ors) 
 template <int U, int C>
 struct Ac4SplitC {
     static constexpr int NU = U > 0 ? U : 1;
+    static constexpr int DEPTH = ac4_depth<false>();
     const int32_t *gsrc[NU];   // this lane's (ch, ch + 1) pair of tile 0
     int32_t *pdst[NU];         // planar row of ch at this lane's sample (row of ch + 1: + ldb)
     const double *wsrc[NU];
     uint32_t dst[NU], orow[NU], ors[NU][2];
     uint32_t ntiles, ldb;
-    int2 stage[NU];
-    double wst[NU];
+    int2 stage[DEPTH][NU];
+    double wst[DEPTH][NU];
 };
 template <int U, int U0, int C>
 __device__ __forceinline__ void ac4_setup_split(const Params &p, uint32_t frame0, uint32_t nframes, uint32_t n,
@@ -481,31 +522,33 @@ __device__ __forceinline__ void ac4_setup_split(const Params &p, uint32_t frame0
         P.ors[it][0] = P.ors[it][1] = 0;
     }
 }
-template <int U, int C>
+template <int SET, int U, int C>
 __device__ __forceinline__ void ac4_fetch(Ac4SplitC<U, C> &P, uint32_t t) {
-    t = t < P.ntiles ? t : P.ntiles - 1;
+    t = ac4_fetch_slot(t, P.ntiles, AC4_DEPTH_OF(P)).tile;
 #pragma unroll
     for (int it = 0; it < U; it++) {
-        P.stage[it] = *reinterpret_cast<const int2 *>(P.gsrc[it] + (size_t)t * (AC4_TS * C));
-        P.wst[it] = P.wsrc[it][t * AC4_TS];
+        P.stage[SET][it] = ac4_ld_int2<AC4_DEPTH_OF(P)>(P.gsrc[it] + (size_t)t * (AC4_TS * C));
+        P.wst[SET][it] = ac4_ld<AC4_DEPTH_OF(P), double>(P.wsrc[it] + t * AC4_TS);
     }
 }
-template <int U, int C>
+template <int SET, int U, int C>
 __device__ __forceinline__ void ac4_convert(Ac4SplitC<U, C> &P, double *dst, uint32_t t) {
     t = t < P.ntiles ? t : P.ntiles - 1;   // (the prefetch clamps: the last tile is stored twice, same bytes)
 #pragma unroll
     for (int it = 0; it < U; it++) {
-        const int2 v = P.stage[it];
+        const int2 v = P.stage[SET][it];
         P.ors[it][0] |= (uint32_t)v.x;
         P.ors[it][1] |= (uint32_t)v.y;
+        ac4_pin<AC4_DEPTH_OF(P)>(P.ors[it][0]);
+        ac4_pin<AC4_DEPTH_OF(P)>(P.ors[it][1]);
         if (P.pdst[it]) {   // (wave-uniform: XPOSE batches keep no planar rows)
             int32_t *o = P.pdst[it] + t * AC4_TS;
             o[0] = v.x;
             o[P.ldb] = v.y;
         }
         double *d = dst + P.dst[it];
-        d[0] = (double)v.x * P.wst[it];
-        d[AC4_LDW] = (double)v.y * P.wst[it];
+        d[0] = (double)v.x * P.wst[SET][it];
+        d[AC4_LDW] = (double)v.y * P.wst[SET][it];
     }
 }
 template <int U, int C>
@@ -521,6 +564,56 @@ __device__ __forceinline__ void ac4_finish(const Ac4SplitC<U, C> &P, uint32_t *o
         }
     }
 }
+// Measurement builds (-DAC4_TIMELINE=1, tools/ac4_timeline.py): every lag-group wave of k_autocorr4 leaves, per tile, the
+// low words of six 100 MHz time stamps in a side buffer of the library's own (ac4_tl, read back through
+// flacgpu_ac4_timeline): 0 top of the tile, 1 its staged loads have arrived (the wait in front of the conversion; the
+// tile's first sixteen LDS reads are issued before it and are awaited with it), 2 tile t + 1 converted and the next
+// loads requested, 3 / 4 the two f64 blocks done, 5 past the barrier.  The stamps stay in scalar registers while the tile
+// runs; the record of tile t is stored by lane 0 in tile t + 1, behind that tile's load wait, so that no store of the
+// timeline's own is outstanding where a wave waits for its input.
+#ifndef AC4_TIMELINE
+#define AC4_TIMELINE 0
+#endif
+#if AC4_TIMELINE
+constexpr uint32_t AC4_TL_WAVES = 512 * 4, AC4_TL_TILES = 128, AC4_TL_WORDS = 8;
+__device__ uint32_t ac4_tl[AC4_TL_WAVES * AC4_TL_TILES * AC4_TL_WORDS];
+struct Ac4Timeline {
+    uint32_t rec[6], t_prev;   // (stamps 0 and 1 of a tile are taken while the previous tile's record is still unwritten)
+    uint32_t cur[2];
+    uint32_t *row;   // this wave's records, nullptr: not recorded
+    bool pending;
+};
+__device__ __forceinline__ void ac4_tl_init(Ac4Timeline &T, uint32_t group, uint32_t nwaves, uint32_t ntiles) {
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t w = group * nwaves + wave;
+    T.row = (nwaves <= 4 && w < AC4_TL_WAVES && ntiles <= AC4_TL_TILES) ? ac4_tl + (size_t)w * AC4_TL_TILES * AC4_TL_WORDS : nullptr;
+    T.pending = false;
+    T.t_prev = 0;
+}
+__device__ __forceinline__ void ac4_tl_flush(Ac4Timeline &T) {
+    if (T.row && T.pending && (threadIdx.x & 63) == 0) {
+        uint32_t *o = T.row + T.t_prev * AC4_TL_WORDS;
+        *reinterpret_cast<uint4 *>(o) = make_uint4(T.rec[0], T.rec[1], T.rec[2], T.rec[3]);
+        *reinterpret_cast<uint4 *>(o + 4) = make_uint4(T.rec[4], T.rec[5], T.t_prev, 1u);
+    }
+    T.pending = false;
+}
+#define AC4_STAMP(k)                                                                    \
+    do {                                                                                \
+        __builtin_amdgcn_sched_barrier(0);                                              \
+        (k < 2 ? tl.cur[k & 1] : tl.rec[k]) = (uint32_t)__builtin_amdgcn_s_memrealtime(); \
+        __builtin_amdgcn_sched_barrier(0);                                              \
+    } while (0)
+// the wait for staging set SET, made here and not at the conversion's first use of it
+#define AC4_TL_ARRIVED(P, SET, U)                                                       \
+    do {                                                                                \
+        _Pragma("unroll") for (int it_ = 0; it_ < (U); it_++)                           \
+            asm volatile("" ::"v"((P).stage[SET][it_].x), "v"((P).stage[SET][it_].y)); \
+    } while (0)
+#else
+#define AC4_STAMP(k) do { } while (0)
+#endif
+
 __device__ __forceinline__ void ac4_read(const double *row, uint32_t col, double (&w)[16]) {
 #pragma unroll
     for (int q = 0; q < 8; q++) {
@@ -561,27 +654,49 @@ __device__ __forceinline__ void ac4_wave(const Params &p, double (*wt)[64 * AC4_
     double acc[LG];
 #pragma unroll
     for (int k = 0; k < LG; k++) acc[k] = -0.0;  // f64 `sum()` identity
-    auto convert = [&](double *dstbuf, uint32_t t) {
-        if constexpr (SPLIT) ac4_convert(P, dstbuf, t);
-        else if constexpr (DIRECT) ac4_convert(P, dstbuf, t >= p.fma_t0 && t < p.fma_t1);
-        else ac4_convert(P, dstbuf);
+    auto convert = [&](auto set, double *dstbuf, uint32_t t) {
+        constexpr int SET = decltype(set)::value;
+        if constexpr (SPLIT) ac4_convert<SET>(P, dstbuf, t);
+        else if constexpr (DIRECT) ac4_convert<SET>(P, dstbuf, t >= p.fma_t0 && t < p.fma_t1);
+        else ac4_convert<SET>(P, dstbuf);
     };
     const uint32_t myrow = lane * AC4_LDW;
     double w0[16], w1[16];
 #pragma unroll
     for (int s = 0; s < 16; s++) w1[s] = 0.0;
-    ac4_fetch(P, 0);
-    convert(wt[0], 0);
-    ac4_fetch(P, 1);
+#if AC4_TIMELINE
+    Ac4Timeline tl;
+    ac4_tl_init(tl, group, blockDim.x >> 6, P.ntiles);
+#endif
+    // the input pipeline (ac4_fetch_slot, kernels/shape.h): tile 0 converted, tiles 1 .. DEPTH requested
+    constexpr uint32_t D = decltype(P)::DEPTH;
+    static_assert(D == 1 || D == 2, "the tile loop is unrolled for one or two staging sets");
+    ac4_fetch<0>(P, 0);
+    convert(std::integral_constant<int, 0>{}, wt[0], 0);
+    ac4_fetch<1 % D>(P, 1);
+    if constexpr (D == 2) ac4_fetch<0>(P, 2);
     __syncthreads();
-    auto tile = [&](auto first, uint32_t t) {
+    // PHASE = t % DEPTH: the set of tile t + 1 is a compile-time constant, the staging registers statically indexed
+    auto tile = [&](auto first, auto phase, uint32_t t) {
         constexpr bool FIRST = decltype(first)::value;
+        constexpr int SET = (int)ac4_fetch_slot(decltype(phase)::value + 1u, ~0u, D).set;
         ac4_progress_prio(t, P.ntiles);
+        AC4_STAMP(0);
         const double *cur = wt[t & 1] + myrow;
         ac4_read(cur, 0, w0);
         __builtin_amdgcn_sched_barrier(0);
-        convert(wt[(t + 1) & 1], t + 1);   // tile t + 1 (a repeat of the last tile at the end: unused)
-        ac4_fetch(P, t + 2);
+#if AC4_TIMELINE
+        AC4_TL_ARRIVED(P, SET, U);
+        AC4_STAMP(1);
+        ac4_tl_flush(tl);   // the record of tile t - 1
+        tl.rec[0] = tl.cur[0];
+        tl.rec[1] = tl.cur[1];
+#endif
+        // tile t + 1 (a repeat of the last tile at the end: unused); only ITS loads are awaited (a counted vmcnt): the
+        // requests of tile t + 2 .. t + DEPTH stay in flight across the f64 blocks
+        convert(std::integral_constant<int, SET>{}, wt[(t + 1) & 1], t + 1);
+        ac4_fetch<SET>(P, ac4_fetch_next(t, D));
+        AC4_STAMP(2);
         __builtin_amdgcn_sched_barrier(0);
         // tiles [fma_t0, fma_t1): every term's factors lie under window values of exactly 1.0 (wave-uniform)
         const bool exact = !FIRST && t >= p.fma_t0 && t < p.fma_t1;
@@ -590,15 +705,37 @@ __device__ __forceinline__ void ac4_wave(const Params &p, double (*wt)[64 * AC4_
         } else {
             ac3_block<A, LG, FIRST>(w0, w1, acc);
         }
+        AC4_STAMP(3);
         ac4_read(cur, 16, w1);
         __builtin_amdgcn_sched_barrier(0);
         if (exact) ac3_block<A, LG, false, true>(w1, w0, acc);
         else ac3_block<A, LG, false>(w1, w0, acc);
+        AC4_STAMP(4);
         __syncthreads();
+        AC4_STAMP(5);
+#if AC4_TIMELINE
+        tl.t_prev = t;
+        tl.pending = true;
+#endif
     };
-    tile(std::true_type{}, 0);
+    tile(std::true_type{}, std::integral_constant<uint32_t, 0>{}, 0);
+    if constexpr (D == 1) {
 #pragma unroll 1
-    for (uint32_t t = 1; t < P.ntiles; t++) tile(std::false_type{}, t);
+        for (uint32_t t = 1; t < P.ntiles; t++) tile(std::false_type{}, std::integral_constant<uint32_t, 0>{}, t);
+    } else {
+        // pairs of tiles and a tail of its own, not a loop left in its middle: the edge such an exit leaves in the flow
+        // graph (from behind the odd tile to the loop's top) makes the compiler wait for both sets at the top
+        uint32_t t = 1;
+#pragma unroll 1
+        for (; t + 1 < P.ntiles; t += 2) {
+            tile(std::false_type{}, std::integral_constant<uint32_t, 1>{}, t);
+            tile(std::false_type{}, std::integral_constant<uint32_t, 0>{}, t + 1);
+        }
+        if (t < P.ntiles) tile(std::false_type{}, std::integral_constant<uint32_t, 1>{}, t);
+    }
+#if AC4_TIMELINE
+    ac4_tl_flush(tl);
+#endif
     if constexpr (DIRECT) {   // the tile loop ended with a barrier
         ac4_finish(P, ors);
         __syncthreads();
@@ -702,21 +839,26 @@ __device__ __forceinline__ void ac4_wave_deep(const Params &p, double (*wt)[64 *
     double wa[16], wb[16], wc[16], wd[16];
 #pragma unroll
     for (int s = 0; s < 16; s++) wc[s] = wd[s] = 0.0;
-    ac4_fetch(P, 0);
-    ac4_convert(P, wt[0]);
-    ac4_fetch(P, 1);
+    // the input pipeline of ac4_wave (ac4_fetch_slot, kernels/shape.h); the loop below is unrolled by two tiles already
+    constexpr uint32_t D = decltype(P)::DEPTH;
+    static_assert(D == 1 || D == 2, "the tile loop is unrolled for one or two staging sets");
+    ac4_fetch<0>(P, 0);
+    ac4_convert<0>(P, wt[0]);
+    ac4_fetch<1 % D>(P, 1);
+    if constexpr (D == 2) ac4_fetch<0>(P, 2);
     __syncthreads();
     const uint32_t myrow = lane * AC4_LDW;
-    // one tile: X0, X1 receive its two blocks; Y0, Y1 hold the previous tile's
-    auto tile = [&](auto first, uint32_t t, double (&X0)[16], double (&X1)[16], double (&Y0)[16], double (&Y1)[16]) {
+    // one tile: X0, X1 receive its two blocks; Y0, Y1 hold the previous tile's; PHASE = t % DEPTH
+    auto tile = [&](auto first, auto phase, uint32_t t, double (&X0)[16], double (&X1)[16], double (&Y0)[16], double (&Y1)[16]) {
         constexpr bool FIRST = decltype(first)::value;
+        constexpr int SET = (int)ac4_fetch_slot(decltype(phase)::value + 1u, ~0u, D).set;
         ac4_progress_prio(t, P.ntiles);
         const double *cur = wt[t & 1] + myrow;
         ac4_read(cur, 0, X0);
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (DIRECT) ac4_convert(P, wt[(t + 1) & 1], t + 1 >= p.fma_t0 && t + 1 < p.fma_t1);
-        else ac4_convert(P, wt[(t + 1) & 1]);
-        ac4_fetch(P, t + 2);
+        if constexpr (DIRECT) ac4_convert<SET>(P, wt[(t + 1) & 1], t + 1 >= p.fma_t0 && t + 1 < p.fma_t1);
+        else ac4_convert<SET>(P, wt[(t + 1) & 1]);
+        ac4_fetch<SET>(P, ac4_fetch_next(t, D));
         __builtin_amdgcn_sched_barrier(0);
         const bool exact = !FIRST && t >= p.fma_t0 && t < p.fma_t1;   // (see ac4_wave)
         if (exact) {
@@ -733,14 +875,16 @@ __device__ __forceinline__ void ac4_wave_deep(const Params &p, double (*wt)[64 *
         }
         __syncthreads();
     };
-    tile(std::true_type{}, 0, wa, wb, wc, wd);
+    using Ph0 = std::integral_constant<uint32_t, 0>;
+    using Ph1 = std::integral_constant<uint32_t, 1 % D>;
+    tile(std::true_type{}, Ph0{}, 0, wa, wb, wc, wd);
     uint32_t t = 1;
 #pragma unroll 1
     for (; t + 1 < P.ntiles; t += 2) {  // n is a multiple of 64: an even number of tiles
-        tile(std::false_type{}, t, wc, wd, wa, wb);
-        tile(std::false_type{}, t + 1, wa, wb, wc, wd);
+        tile(std::false_type{}, Ph1{}, t, wc, wd, wa, wb);
+        tile(std::false_type{}, Ph0{}, t + 1, wa, wb, wc, wd);
     }
-    if (t < P.ntiles) tile(std::false_type{}, t, wc, wd, wa, wb);
+    if (t < P.ntiles) tile(std::false_type{}, Ph1{}, t, wc, wd, wa, wb);
     if constexpr (DIRECT) {   // the tile loop ended with a barrier
         ac4_finish(P, ors);
         __syncthreads();

@@ -32,6 +32,26 @@ FLACGPU_HD constexpr uint32_t frame_fb_words_exhaustive_stereo(uint32_t bps, uin
     return (((16u + 2u) * 8u + 2u * (n * bps + 64u) + 31u) / 32u + 2u + 3u) & ~3u;
 }
 
+// k_autocorr4 / k_autocorr4_deep (kernels/autocorr.inc): how far ahead of its conversion a 32-sample tile of input is
+// requested, in tiles, and the ONE rule of which tile a request reads and which of the AC4_FETCH_DEPTH rotating
+// staging register sets receives it.  The producers' schedule: before the tile loop they request tile 0, convert it and
+// request tiles 1 .. DEPTH; in tile t they convert tile t + 1 out of its set and then request tile
+// ac4_fetch_next(t) = t + 1 + DEPTH into the set that conversion has just freed -- the same set, because the set of a
+// tile is its index modulo DEPTH.  A request past the frame's end reads the LAST tile again (the clamp keeps every
+// address inside the frame; what such a request brings is converted into a buffer nobody reads, or not at all).
+// DEPTH 1 is the schedule this kernel had before the second set (profiles/ac4_fetch_depth.json).
+#ifndef AC4_FETCH_DEPTH
+#define AC4_FETCH_DEPTH 2
+#endif
+struct Ac4FetchSlot {
+    uint32_t tile;   // the tile whose samples the request reads: t, clamped to the frame
+    uint32_t set;    // the staging set its loads go to and its conversion reads
+};
+FLACGPU_HD constexpr Ac4FetchSlot ac4_fetch_slot(uint32_t t, uint32_t ntiles, uint32_t depth = AC4_FETCH_DEPTH) {
+    return Ac4FetchSlot{t < ntiles ? t : ntiles - 1u, t % depth};
+}
+FLACGPU_HD constexpr uint32_t ac4_fetch_next(uint32_t t, uint32_t depth = AC4_FETCH_DEPTH) { return t + 1u + depth; }
+
 // block lengths the wave kernels are instantiated for: 64 lanes x SPL samples
 #define FLACGPU_WAVE_SIZES(X) X(4096, 64) X(2304, 36) X(2048, 32) X(1152, 18) X(1024, 16)
 inline bool wave_block_size(uint32_t B) {
