@@ -628,14 +628,8 @@ static void fill_params(const flacgpu_ctx *c, uint32_t n_frames, uint32_t last_l
     p.f0 = 0;
     p.fcount = n_frames;
     p.ac_split = (uint32_t)c->lag_split;
-    p.fma_t0 = p.fma_t1 = 0;
-    // integer samples below 2^26 (candidates of <= 25 bits + the side channel's extra bit) have exact f64 products
-    if (!c->knobs.no_ac_fma && c->bps + (c->stereo4 ? 1u : 0u) <= 26u && c->flat_hi > c->flat_lo) {
-        // (the margin is the most lags a launch can carry -- its lag count is the order + 1 rounded up to four --, not the order)
-        const uint32_t maxlag = c->opts.max_lpc_order <= 16 ? 16u : 32u;
-        p.fma_t0 = (c->flat_lo + maxlag + 31u) / 32u;      // first 32-sample tile whose every partner sample is flat too
-        p.fma_t1 = c->flat_hi / 32u;                        // tiles t < fma_t1 end inside the flat run
-    }
+    flacenc_route::fused_tile_range(c->bps, c->stereo4, c->opts.max_lpc_order, c->flat_lo, c->flat_hi, c->knobs.no_ac_fma, &p.fma_t0,
+                                    &p.fma_t1);
     p.planar = c->d_planar;
     p.inter = nullptr;
     p.split_src = nullptr;
@@ -931,19 +925,18 @@ static int analyze_impl(flacgpu_ctx *c, const int32_t *d_pcm, int layout, uint32
     }
     if (fork) HIP_TRY(hipEventRecord(c->ev_join, sf));
     if (lpc) {
-        const uint32_t H = ((p.max_lpc_order + 1) + 3u) & ~3u;
         begin(3);
         // the whole blocks (of this range) in one launch, the in-place kernels with K4 in their tail; a short last frame
         // in one of its own
         // (a ragged batch: every frame in ONE launch of the kernel that takes each candidate's length and window from the tables)
         const uint32_t full = ragged ? 0u : (last_len == B) ? n_frames : n_frames - 1;
         const uint32_t ac_n = ranged ? rcnt : full;
-        if (ragged) launch_autocorr_ragged(H, p, st);
-        if (ac_n && dispatch_autocorr(H, p, c->knobs, rf0, ac_n, B, c->d_window_full, st) != r.k4_in_autocorr) {
+        if (ragged) launch_autocorr_ragged(p, st);
+        if (ac_n && dispatch_autocorr(p, c->knobs, rf0, ac_n, B, c->d_window_full, st) != r.k4_in_autocorr) {
             g_last_error = "internal: the autocorrelation launcher and the route disagree about K4";
             return FLACGPU_ERR_UNSUPPORTED;
         }
-        if (full != n_frames && !ragged) (void)dispatch_autocorr(H, p, c->knobs, full, 1, last_len, c->d_window_last, st);
+        if (full != n_frames && !ragged) (void)dispatch_autocorr(p, c->knobs, full, 1, last_len, c->d_window_last, st);
         if (!r.k4_in_autocorr || full != n_frames) {
             begin(4);
             launch_lpc(p, (ncb + 63) / 64, st);
@@ -1306,7 +1299,6 @@ int flacgpu_encode_device(flacgpu_ctx *c, const int32_t *d_pcm, int layout, uint
     HIP_TRY(hipStreamWaitEvent(st1, c->ev_fork, 0));
     const uint32_t h = ((n_frames / 2) + 15u) & ~15u;  // 16 frames = one autocorrelation wave group
     const bool lpc = p.max_lpc_order > 0;
-    const uint32_t H = ((p.max_lpc_order + 1) + 3u) & ~3u;
     const size_t l64 = (size_t)frame_fb_words(c->channels, c->bps, B) * sizeof(int32_t);
     for (int half = 0; half < 2; half++) {
         hipStream_t st = half ? st1 : st0;
@@ -1321,7 +1313,7 @@ int flacgpu_encode_device(flacgpu_ctx *c, const int32_t *d_pcm, int layout, uint
         if (c->stereo4 && !p.exhaustive) hipLaunchKernelGGL(k_stereo_stats_t<false>, dim3(r.fcount), dim3(WG), 0, st, r);
         hipLaunchKernelGGL(k_candinfo, dim3((ncb + WG - 1) / WG), dim3(WG), 0, st, r, c->d_orbits, (const unsigned long long *)nullptr);
         if (lpc) {
-            if (!dispatch_autocorr(H, r, c->knobs, r.f0, r.fcount, B, c->d_window_full, st))
+            if (!dispatch_autocorr(r, c->knobs, r.f0, r.fcount, B, c->d_window_full, st))
                 launch_lpc(r, (ncb + 63) / 64, st);
         }
         if (!launch_cand64(r, c->knobs, B, (ncb + 3) / 4, st)) hipLaunchKernelGGL(k_decide, dim3(r.fcount), dim3(64), 0, st, r);

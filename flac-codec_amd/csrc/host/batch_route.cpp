@@ -106,8 +106,8 @@ Route plan_route(const RouteContext &c, const RouteBatch &b) {
     // segments stay where they are when every stage finds its frames through the table (Params::inter_tab); one channel's
     // rows are Params::planar, which has no table
     r.segments_in_place = b.segments_in_place_wanted && r.in_place() && C_ >= 2;
-    // K4 in the tail of the autocorrelation kernel: its in-place instantiations for up to 16 lags (autocorr.hip
-    // launch_autocorr3; the deep kernel of orders 17..32 leaves K4 to k_lpc_u)
+    // K4 in the tail of the autocorrelation kernel: its in-place instantiations for up to 16 lags (plan_autocorr's
+    // fused_k4 below; the deep kernel of orders 17..32 leaves K4 to k_lpc_u)
     r.k4_in_autocorr = r.in_place() && c.max_lpc_order >= 1 && c.max_lpc_order <= 16;
 
     // ---- flacgpu_encode_device (int32 samples: no entry point hands it a stream-width upload)
@@ -137,7 +137,116 @@ Route plan_route(const RouteContext &c, const RouteBatch &b) {
     return r;
 }
 
+void fused_tile_range(uint32_t bps, uint32_t stereo4, uint32_t max_lpc_order, uint32_t flat_lo, uint32_t flat_hi, bool no_ac_fma,
+                      uint32_t *t0, uint32_t *t1) {
+    *t0 = *t1 = 0;
+    // integer samples below 2^26 (candidates of <= 25 bits + the side channel's extra bit) have exact f64 products
+    if (!no_ac_fma && bps + (stereo4 ? 1u : 0u) <= 26u && flat_hi > flat_lo) {
+        // (the margin is the most lags a launch can carry -- its lag count is the order + 1 rounded up to four --, not the order)
+        const uint32_t maxlag = max_lpc_order <= 16 ? 16u : 32u;
+        *t0 = (flat_lo + maxlag + 31u) / 32u;      // first 32-sample tile whose every partner sample is flat too
+        *t1 = flat_hi / 32u;                        // tiles t < t1 end inside the flat run
+    }
+}
+
+AcKernel plan_autocorr(const AcLaunch &a) {
+    AcKernel k;
+    const uint32_t H = ((a.max_lpc_order + 1) + 3u) & ~3u;   // the generic kernels' lag count: order + 1 rounded up to four
+    if (a.ragged) {
+        k.family = AcKernel::RAGGED;
+        k.size = H <= 36 ? H : 36;
+        return k;
+    }
+    // EXPERIMENT switch (bench.py --experiment mfma_autocorr): the re-associating f64-MFMA kernel in place of the exact one, to
+    // measure what a whole step costs with the autocorrelation off the VALU pipe.  NOT bit-exact; never set in production.
+    if (a.mfma && a.max_lpc_order >= 1 && a.max_lpc_order <= 16 && a.whole_batch && a.n == a.block_size) {
+        k.family = AcKernel::MFMA;
+        k.size = 17;
+        k.ns = 0;
+        return k;
+    }
+    // k_autocorr4 / _deep: frame length a multiple of 32 (orders 17..32: two blocks of history, a multiple of 64), and either
+    // stereo L/R/M/S candidates of <= 24-bit samples (mid/side formed with one v_mad_i32_i24) or independent channels of any width
+    const bool stereo = a.stereo4 && a.ncand == 4 && a.channels == 2 && a.bps <= 24;
+    const bool indep = !a.stereo4 && a.ncand == a.channels;
+    const bool deep = a.max_lpc_order > 16;
+    if (a.n < 32 || a.n % 32 != 0 || (!stereo && !indep) || (deep && a.n % 64 != 0)) {
+        k.family = AcKernel::AC2;
+        k.size = H <= 36 ? H : 36;
+        return k;
+    }
+    // a short last frame has a window of its own: no fused tiles
+    k.fused_tiles = a.n == a.block_size && a.fma_t0 < a.fma_t1;
+    k.stereo = stereo;
+    if (deep) {
+        // (K4 in the tail of the deep kernel, as in k_autocorr4: measured and removed -- 228 instead of 153 VGPRs leave no room
+        // for another kernel's wave beside two of these, and the four-context step of config 5 goes 0.566 -> 0.588 ms,
+        // profiles/r04_autocorr_lpc_fuse.json)
+        k.family = AcKernel::AC4_DEEP;
+        k.size = 33;
+        k.producer = (stereo && a.inter) ? AcKernel::DIRECT : AcKernel::PLANAR;
+        return k;
+    }
+    k.family = AcKernel::AC4;
+    const uint32_t nl = a.max_lpc_order + 1;
+    k.size = nl <= 5 ? 5 : nl <= 9 ? 9 : nl <= 13 ? 13 : 17;
+    const uint32_t groups = (a.nframes * a.ncand + 63) / 64;
+    // 4 waves per 64 candidates (lags split 4 ways) by default: the f64 stream needs two waves per SIMD to issue at full rate and
+    // 8192 frames are only 512 candidate groups (0.23 ms against 0.31 ms split 2 ways).  When other contexts keep the SIMDs busy
+    // anyway, the 2-way split wins: the int -> f64 x window conversion is replicated 2x instead of 4x (71 M instead of 92 M
+    // instructions).
+    if (stereo && a.inter) {   // interleaved input read in place (the route selects this only with the 4-way split)
+        // small batches (<= 1024 frames: at most 64 workgroups for 256 CUs) are a latency problem -- the serial walk over a
+        // frame's samples -- and take the eight-wave split of the lags, whose walk is shorter (512 frames: 0.0555 -> 0.0441 ms
+        // per batch in the four-context loop, profiles/r04_batch_sweep.json); large batches are a throughput problem and keep
+        // four waves (the eight-wave kernel reads the tile twice as often)
+        k.producer = AcKernel::DIRECT;
+        k.ns = (groups <= 64 && k.size == 13) ? 8 : 4;
+        k.fused_k4 = true;
+    } else if (!stereo && a.split_src) {   // interleaved independent channels: the producers split them on the way (no K0 pass)
+        k.producer = a.channels == 8 ? AcKernel::SPLIT8 : a.channels == 4 ? AcKernel::SPLIT4 : AcKernel::SPLIT;
+        k.fused_k4 = true;
+    } else {
+        k.ns = a.ac_split == 2 ? 2 : 4;
+    }
+    return k;
+}
+
 }  // namespace flacenc_route
+
+// Test hook (tests/test_autocorr_edge_matrix_oracle.py; not in the public header, needs no device): the kernel of one
+// autocorrelation launch.  in[17]: ncand, stereo4, channels, bps, max LPC order, n, block size, inter set, split_src set,
+// ac_split, frames in the launch, the launch covers the batch, experiment_mfma_ac, the window's flat run [flat_lo, flat_hi),
+// no_ac_fma, ragged.  out[9]: AcKernel's fields in their order, then fma_t0 and fma_t1 as fused_tile_range gives them.
+extern "C" void flacenc_plan_autocorr_row(const int32_t *in, uint32_t *out) {
+    using namespace flacenc_route;
+    AcLaunch a;
+    a.ncand = (uint32_t)in[0];
+    a.stereo4 = (uint32_t)in[1];
+    a.channels = (uint32_t)in[2];
+    a.bps = (uint32_t)in[3];
+    a.max_lpc_order = (uint32_t)in[4];
+    a.n = (uint32_t)in[5];
+    a.block_size = (uint32_t)in[6];
+    a.inter = in[7] != 0;
+    a.split_src = in[8] != 0;
+    a.ac_split = (uint32_t)in[9];
+    a.nframes = (uint32_t)in[10];
+    a.whole_batch = in[11] != 0;
+    a.mfma = in[12] != 0;
+    fused_tile_range(a.bps, a.stereo4, a.max_lpc_order, (uint32_t)in[13], (uint32_t)in[14], in[15] != 0, &a.fma_t0, &a.fma_t1);
+    a.ragged = in[16] != 0;
+    const AcKernel k = plan_autocorr(a);
+    out[0] = (uint32_t)k.family;
+    out[1] = k.size;
+    out[2] = k.ns;
+    out[3] = (uint32_t)k.producer;
+    out[4] = k.stereo;
+    out[5] = k.fused_k4;
+    out[6] = k.fused_tiles;
+    out[7] = a.fma_t0;
+    out[8] = a.fma_t1;
+}
 
 // Test hook (tests/test_route_table.py, tools/route_table_check.cpp; not in the public header, needs no device): the route of
 // one row of the test's matrix.  in[18]: channels, bps, block size, max LPC order, max partition order, exhaustive, layout,

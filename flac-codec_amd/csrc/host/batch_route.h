@@ -66,5 +66,35 @@ struct Route {
 
 Route plan_route(const RouteContext &c, const RouteBatch &b);
 
+// ---- which autocorrelation kernel ONE launch runs (autocorr.hip switches on the answer and on nothing else; a test that
+// names an instantiation asks the same function through flacenc_plan_autocorr_row).  The inputs are what the launchers read
+// from Params, the knobs and their arguments.
+struct AcLaunch {
+    uint32_t ncand = 0, stereo4 = 0, channels = 0, bps = 0, max_lpc_order = 0;
+    uint32_t n = 0, block_size = 0;     // the launch's frame length; the context's block size
+    bool inter = false;                 // Params::inter set (Route::DIRECT_STEREO)
+    bool split_src = false;             // Params::split_src set (Route::SPLIT / SPLIT_XPOSE)
+    uint32_t ac_split = 4;              // Params::ac_split (FLACGPU_TUNE_LAG_SPLIT)
+    uint32_t nframes = 0;               // frames in the launch
+    bool whole_batch = false;           // the launch covers the batch: frame0 == 0 && nframes == Params::n_frames
+    bool mfma = false;                  // Knobs::experiment_mfma_ac
+    uint32_t fma_t0 = 0, fma_t1 = 0;    // Params::fma_t0 / fma_t1 (fused_tile_range)
+    bool ragged = false;                // launch_autocorr_ragged: every frame its own length
+};
+struct AcKernel {
+    enum Family { AC4, AC4_DEEP, AC2, RAGGED, MFMA } family = AC2;
+    uint32_t size = 0;                  // AC4: NL (5, 9, 13, 17); AC2 / RAGGED: H (4 .. 36); AC4_DEEP: 33; MFMA: 17
+    uint32_t ns = 4;                    // lag-group waves per 64 candidates (MFMA: one wave per candidate, 0)
+    enum Producer { PLANAR, DIRECT, SPLIT, SPLIT4, SPLIT8 } producer = PLANAR;
+    bool stereo = false;                // the STEREO template argument of k_autocorr4 / _deep
+    bool fused_k4 = false;              // K4 in the kernel's tail: what dispatch_autocorr returns
+    bool fused_tiles = false;           // tiles [fma_t0, fma_t1) take one v_fma_f64 per term in this launch
+};
+AcKernel plan_autocorr(const AcLaunch &a);
+// Params::fma_t0 / fma_t1 of a context: the 32-sample tiles of a FULL block whose every product has both factors under window
+// values of exactly 1.0 ([flat_lo, flat_hi): the flat run of the block's window); t0 >= t1: none
+void fused_tile_range(uint32_t bps, uint32_t stereo4, uint32_t max_lpc_order, uint32_t flat_lo, uint32_t flat_hi, bool no_ac_fma,
+                      uint32_t *t0, uint32_t *t1);
+
 }  // namespace flacenc_route
 #endif

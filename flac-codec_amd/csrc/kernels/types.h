@@ -222,10 +222,11 @@ bool launch_cand64_direct(const Params &p, const Knobs &kn, uint32_t B, uint32_t
 bool launch_cand64_direct_short(const Params &p, const Knobs &kn, uint32_t B, uint32_t blocks, hipStream_t st);
 // autocorr.hip
 // returns true when the kernel also ran K4 in its tail (the DIRECT and SPLIT k_autocorr4 instantiations): no launch_lpc then
-bool dispatch_autocorr(uint32_t H, const Params &p, const Knobs &kn, uint32_t frame0, uint32_t nframes, uint32_t n,
-                       const double *win, hipStream_t st);
+// (which kernel: flacenc_route::plan_autocorr, host/batch_route.h)
+bool dispatch_autocorr(const Params &p, const Knobs &kn, uint32_t frame0, uint32_t nframes, uint32_t n, const double *win,
+                       hipStream_t st);
 // a RAGGED batch (Params::frame_n): every frame of the batch in one launch, each candidate with its frame's length and window
-void launch_autocorr_ragged(uint32_t H, const Params &p, hipStream_t st);
+void launch_autocorr_ragged(const Params &p, hipStream_t st);
 void launch_autocorr_mfma(const Params &p, uint32_t blocks, uint32_t n, const double *win, double *ac,
                           hipStream_t st);
 // pack.hip
