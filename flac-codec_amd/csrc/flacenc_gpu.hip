@@ -118,6 +118,68 @@ static uint32_t *defer_stats_of(const flacgpu_ctx *c);
 static int ctx_sync(flacgpu_ctx *c);
 static hipStream_t ctx_stream(flacgpu_ctx *c);
 
+// THE BATCH IN HAND: everything that is true of the batch submitted last, and nothing that outlives it.  An entry point
+// builds the record while it queues the batch's launches and commits it by ONE assignment behind them (analyze_impl, the
+// two-ranges branch of flacgpu_encode_device, flacgpu_pack_plans), so nothing of the batch before can reach the new one, and
+// a call refused for its arguments leaves the old record -- and the old batch -- as it was.  Who reads what:
+//   every fetch / wait entry        n_frames, stream (ctx_stream), packed_valid
+//   pack_impl, flacgpu_verify_device  params, route, kind (frame numbers from d_seg_fn: pack_params_of), host_out*, resid_valid
+//   resolve_order_ties              params, route, ties_*, fir_rechecked, first_frame / rate (the re-assembly), frame_len_of
+//   ensure_planar                   planar_valid, direct_src, seg_direct + segs (K0 segment by segment)
+//   flacgpu_fetch_decoded           frame_len_of (kind, rag_n, last_len)
+//   flacgpu_frame_offsets / flacgpu_place_frames   total_valid, packed_total
+//   the asynchronous host path      host_out*, out_in_host, ties_*
+struct Batch {
+    enum Kind { NONE, PLAIN, SEGMENTS, RAGGED } kind = NONE;
+    uint32_t n_frames = 0, last_len = 0;
+    Params params{};
+    Route route;                    // which kernels the batch runs (host/batch_route.h), decided by the entry it arrived through
+    hipStream_t stream = nullptr;   // stream the analysis / the last assembly was submitted to
+    // false: the batch was analysed from the caller's interleaved PCM in place (direct_src, which must stay valid until
+    // the results were fetched); d_planar is filled on demand (ensure_planar)
+    bool planar_valid = true;
+    const int32_t *direct_src = nullptr;
+    bool seg_direct = false;               // SEGMENTS read in place (Params::inter_tab): ensure_planar walks segs
+    std::vector<flacgpu_segment> segs;
+    std::vector<uint32_t> rag_n;           // RAGGED: every frame's length (host re-decision, flacgpu_fetch_decoded)
+    uint64_t first_frame = 0;              // arguments of the last frame assembly (re-run after a re-decision)
+    uint32_t rate = 0;
+    // flacgpu_encode_packed_async_host: k_frame64 writes the batch's frames straight into this pinned host buffer (no
+    // d_packed, no download) when every frame of the batch takes it; out_in_host says it did
+    uint8_t *host_out = nullptr;
+    size_t host_out_cap = 0;
+    bool out_in_host = false;
+    bool resid_valid = false;       // d_resid holds the batch's residual rows
+    bool packed_valid = false;      // the frames were assembled
+    bool total_valid = false;       // packed_total: the packed bytes once they are final (flacgpu_frame_offsets)
+    uint64_t packed_total = 0;
+    bool ties_checked = true;       // the analysis has been looked at by resolve_order_ties (or there was none)
+    uint32_t ties_resolved = 0;     // candidates re-decided on the host
+    uint32_t fir_rechecked = 0;     // candidate waves that asked for the checked FIR re-run (Params::check_fir) and got it
+
+    bool numbered() const { return kind == SEGMENTS || kind == RAGGED; }   // frame numbers per frame, in d_seg_fn
+};
+// the host form of the kernels' frame_len()
+static uint32_t frame_len_of(const Batch &b, size_t f) {
+    return (b.kind == Batch::RAGGED && f < b.rag_n.size()) ? b.rag_n[f] : (f + 1 == b.n_frames) ? b.last_len : b.params.block_size;
+}
+
+// What an entry point hands analyze_impl / pack_impl about the batch it submits.  The default is a whole PLAIN batch into
+// d_packed, which is also what pack_impl needs to assemble the batch in hand once more.
+struct Submission {
+    Batch::Kind kind = Batch::PLAIN;
+    const flacgpu_segment *segs = nullptr;   // SEGMENTS read in place (seg_direct): the segments, n_segs of them
+    uint32_t n_segs = 0;
+    bool seg_direct = false;
+    const uint32_t *rag_n = nullptr;         // RAGGED: the n_frames lengths on the host (on the device: d_rag_tab)
+    uint32_t f0 = 0, count = 0;              // the frame range this call launches for (Route::range_frames); count 0: the whole batch
+    Route route;
+    uint32_t packed_bytes = 0;               // != 0: the PCM sits in d_in as interleaved little-endian samples of that many bytes
+    uint8_t *host_out = nullptr;             // Batch::host_out
+    size_t host_out_cap = 0;
+    hipEvent_t after_layout = nullptr;       // recorded right behind k_layout (the frame sizes are known from there on)
+};
+
 struct flacgpu_ctx {
     flacgpu_options opts;
     uint32_t bps, channels, max_frames, ldb, ncand, stereo4;
@@ -137,14 +199,11 @@ struct flacgpu_ctx {
     uint32_t *d_ties = nullptr;     // candidates whose LPC order estimates tie (K4: note_order_tie), [F * NC]
     double tie_band = 1e-9, tie_perturb = 0.0;
     Knobs knobs;                  // the FLACGPU_* environment, read once at flacgpu_create
-    // a batch made of SEGMENTS (flacgpu_encode_segments*): per-frame frame numbers and PCM addresses on the device, their
-    // pinned staging copy, and the segments themselves (ensure_planar walks them)
+    Batch batch;                  // the batch in hand
+    // a batch made of SEGMENTS (flacgpu_encode_segments*): per-frame frame numbers and PCM addresses on the device and their
+    // pinned staging copy
     uint64_t *d_seg_fn = nullptr, *h_seg = nullptr;
     const int32_t **d_seg_ptr = nullptr;
-    std::vector<flacgpu_segment> segs;
-    bool seg_pending = false;   // the next analyze_impl belongs to a segments call
-    bool seg_active = false;    // the batch in hand is made of segments (frame numbers from d_seg_fn)
-    bool seg_direct = false;    // ... read in place (Params::inter_tab)
     // a RAGGED batch (flacgpu_encode_ragged_device): the per-frame tables (Params::frame_n, frame_win; frame numbers in
     // d_seg_fn), their pinned staging copy, the run table that gathers the frames into d_in, and the window pool -- kept
     // between calls: rag_pool_at lists the pool's windows (length, offset in doubles), and a batch whose every length has
@@ -156,35 +215,19 @@ struct flacgpu_ctx {
     std::vector<std::pair<uint32_t, uint32_t>> rag_pool_at;    // sorted by length
     std::vector<double> rag_pool_host;                         // the upload's source (valid until the next upload)
     uint64_t rag_pool_uploads = 0;                             // (flacgpu_ragged_pool_uploads: what a test of the reuse reads)
-    std::vector<uint32_t> rag_n;                               // the batch in hand's lengths (host re-decision, fetch_decoded)
-    bool rag_pending = false, rag_active = false;              // as seg_pending / seg_active
-    const uint32_t *k0_frame_n = nullptr;                      // launch_k0's length table: d_rag_tab for a ragged batch
     bool drained = false;       // nothing of this context is in flight (its last batch was waited for, nothing submitted since):
                                 // the asynchronous entries then skip their hipStreamSynchronize -- with more streams than
                                 // hardware queues a synchronise of an IDLE stream still waits behind the other streams' work
     bool env_no_direct = false;     // FLACGPU_NO_DIRECT as read at creation; copy_input: FLACGPU_TUNE_COPY_INPUT.  knobs.no_direct
     bool copy_input = false;        //   is their OR
-    bool ties_checked = true;       // the last analysis has been looked at by resolve_order_ties
-    uint32_t ties_resolved = 0;     // candidates re-decided on the host for the last analysis
-    uint32_t fir_rechecked = 0;     // candidate waves of the last analysis that asked for the checked FIR re-run
-                                    // (Params::check_fir) and got it
-    Route route;                    // which kernels the batch in hand runs (host/batch_route.h), decided when it arrived
-    uint64_t last_first_frame = 0;  // arguments of the last frame assembly (re-run after a re-decision)
-    uint32_t last_rate = 0;
     uint32_t *h_stats = nullptr;    // pinned copy of the 4 counters (asynchronous host path)
     int32_t *d_big = nullptr;       // blocks > LDS_BLOCK_LIMIT: per-workgroup arrays of the generic kernels
     unsigned long long *d_abs = nullptr;   // stereo, fast channel choice: K0's sums of |l|, |r|, |mid|, |side| per frame
-    bool abs_valid = false;         // K0 of the batch in hand filled d_abs (k_candinfo then makes the choice)
     int32_t *d_decoded = nullptr;   // [F][C][ldb] PCM decoded back from the packed frames (lazy)
     uint32_t *d_verify = nullptr;   // [4] verify counters
     hipStream_t aux_stream = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_layout = nullptr;
     bool two_ranges = false;         // FLACGPU_TUNE_TWO_RANGES
-    // flacgpu_encode_packed_async_host: k_frame64 writes the batch's frames straight into this pinned host
-    // buffer (no d_packed, no download) when every frame of the batch takes it; out_in_host says it did
-    uint8_t *host_out = nullptr;
-    size_t host_out_cap = 0;
-    bool out_in_host = false;
     bool blocking_wait = false;      // FLACGPU_TUNE_BLOCKING_WAIT
     int lag_split = 4;               // FLACGPU_TUNE_LAG_SPLIT
     uint32_t *d_packed = nullptr;   // packed frame bytes (as 32-bit words)
@@ -193,27 +236,16 @@ struct flacgpu_ctx {
     PackParams::SubEdgeRec *d_edges = nullptr;   // k_sub64: [F][C] edge records (5..8 channels)
     uint32_t layout_epoch = 0;
     uint64_t packed_cap = 0;        // bytes
-    bool packed_valid = false;
-    // flacgpu_frame_offsets / flacgpu_place_frames: the packed bytes of the batch in hand once they are final (total_valid),
-    // and the run table's pinned and device copies, kept between calls; ev_place: the last placement has run
-    uint64_t packed_total = 0;
-    bool total_valid = false, place_pending = false;
+    // flacgpu_place_frames: the run table's pinned and device copies, kept between calls; ev_place: the last placement has run
+    bool place_pending = false;
     PlaceRun *h_runs = nullptr, *d_runs = nullptr;
     uint32_t runs_cap = 0;
     hipEvent_t ev_place = nullptr;
-    bool resid_valid = false;      // d_resid holds the rows of the last analysed batch
-    // a batch cut into frame ranges by flacgpu_encode_device (Route::range_frames): analyze_impl / pack_impl launch their kernels for
-    // frames [rng_f0, rng_f0 + rng_cnt) only; rng_cnt == 0: the whole batch
-    uint32_t rng_f0 = 0, rng_cnt = 0;
     uint32_t flat_lo = 0, flat_hi = 0;    // samples [flat_lo, flat_hi) of a full block lie under window values of exactly 1.0
     uint32_t chunk_samples = 64u << 20;   // FLACGPU_TUNE_CHUNK_MSAMPLES (0: never cut)
     bool chunk_auto = true;               // nobody set the tuning: only stereo batches are cut (measured: +9 %; 8 channels: +-0)
-    bool planar_valid = true;       // false: the last batch was analysed from the caller's interleaved PCM in
-    const int32_t *direct_src = nullptr;   //   place (direct_src); d_planar is filled on demand (ensure_planar)
-    Params last_params;
     uint32_t window_last_len = 0;
     hipStream_t own_stream = nullptr;
-    hipStream_t last_stream = nullptr;  // stream the last analysis / assembly was submitted to
     // asynchronous host path (flacgpu_encode_packed_async ...)
     uint64_t *h_off = nullptr;          // pinned: byte offsets of the frames of the batch in flight
     hipEvent_t ev_sizes = nullptr, ev_bytes = nullptr, ev_null = nullptr;
@@ -222,8 +254,6 @@ struct flacgpu_ctx {
     // packing kernels, before this batch's sizes are known; the remainder (if any) follows once they are
     uint64_t prev_total = 0, early_bytes = 0;
     uint8_t *early_dst = nullptr;
-    // last call
-    uint32_t last_frames = 0, last_len = 0;
     bool timing = false;
     hipEvent_t ev[FLACGPU_N_KERNELS + 1];
     bool ev_ok = false;
@@ -234,7 +264,7 @@ struct flacgpu_ctx {
 #define CTX_GUARD(c) DeviceGuard device_guard_((c)->device)   // (kernels/types.h)
 
 // Waits for the work this context submitted last (never for other contexts: no device-wide sync).
-static hipStream_t ctx_stream(flacgpu_ctx *c) { return c->last_stream ? c->last_stream : c->own_stream; }
+static hipStream_t ctx_stream(flacgpu_ctx *c) { return c->batch.stream ? c->batch.stream : c->own_stream; }
 static int ctx_sync(flacgpu_ctx *c) {
     HIP_TRY(hipStreamSynchronize(ctx_stream(c)));
     return FLACGPU_OK;
@@ -330,15 +360,19 @@ int upload_window(flacgpu_ctx *c, uint32_t n, double *dst, hipStream_t st) {
 size_t pack_lds_bytes(uint32_t block_size) { return (size_t)pack_sb_words(block_size) * 4; }
 
 // K0 for frames [f0, f0 + fcount): split the channels into planar rows and OR every candidate's
-// samples.  Returns true when the orbits are already accumulated.
+// samples.  frame_n: a ragged batch's length table on the device (else nullptr).  Says what it left behind: the orbits
+// already accumulated; the sums of |l|, |r|, |mid|, |side| in d_abs (k_candinfo then makes the fast channel choice).
 constexpr uint32_t kGridY = 65535;   // frames per launch of the kernels that index frames with blockIdx.y
+struct K0Result {
+    bool have_orbits = false, have_abs = false;
+};
 
-bool launch_k0(flacgpu_ctx *c, const int32_t *d_pcm, int layout, uint32_t n_frames, uint32_t last_len,
-               uint32_t f0, uint32_t fcount, hipStream_t st) {
+K0Result launch_k0(flacgpu_ctx *c, const int32_t *d_pcm, int layout, uint32_t n_frames, uint32_t last_len,
+                   uint32_t f0, uint32_t fcount, const uint32_t *frame_n, hipStream_t st) {
     if (fcount > kGridY) {   // batches of more than 65535 frames: several launches
-        bool r = false;
+        K0Result r;
         for (uint32_t f = f0; f < f0 + fcount; f += kGridY)
-            r = launch_k0(c, d_pcm, layout, n_frames, last_len, f, std::min(kGridY, f0 + fcount - f), st);
+            r = launch_k0(c, d_pcm, layout, n_frames, last_len, f, std::min(kGridY, f0 + fcount - f), frame_n, st);
         return r;
     }
     const uint32_t B = c->opts.block_size;
@@ -346,22 +380,21 @@ bool launch_k0(flacgpu_ctx *c, const int32_t *d_pcm, int layout, uint32_t n_fram
     if (layout == FLACGPU_LAYOUT_INTERLEAVED && c->channels == 2) {
         unsigned long long *abs = (c->d_abs && c->ncand == 4) ? c->d_abs : nullptr;   // (zeroed by the caller)
         hipLaunchKernelGGL(k_deinterleave2, grid, dim3(WG), 0, st, (const int2 *)d_pcm, c->d_planar, B, c->ldb,
-                           n_frames, last_len, c->d_orbits, c->ncand, f0, abs, c->k0_frame_n);
-        c->abs_valid = abs != nullptr;
-        return true;
+                           n_frames, last_len, c->d_orbits, c->ncand, f0, abs, frame_n);
+        return {true, abs != nullptr};
     }
     if (layout == FLACGPU_LAYOUT_INTERLEAVED && c->ncand == c->channels) {
         switch (c->channels) {
 #define X(C) case C: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_deinterleave_n<C>), grid, dim3(WG), 0, st, d_pcm, \
-                                        c->d_planar, B, c->ldb, n_frames, last_len, c->d_orbits, f0, c->k0_frame_n); return true;
+                                        c->d_planar, B, c->ldb, n_frames, last_len, c->d_orbits, f0, frame_n); return {true, false};
             X(1) X(3) X(4) X(5) X(6) X(7) X(8)
 #undef X
         default: break;
         }
     }
     hipLaunchKernelGGL(k_deinterleave, grid, dim3(WG), 0, st, d_pcm, c->d_planar, c->channels, B, c->ldb,
-                       n_frames, last_len, layout == FLACGPU_LAYOUT_PLANAR, f0, c->k0_frame_n);
-    return false;
+                       n_frames, last_len, layout == FLACGPU_LAYOUT_PLANAR, f0, frame_n);
+    return {false, false};
 }
 
 // K0 for stream-width little-endian input (k_deinterleave_packed); false: no instantiation / layout
@@ -370,7 +403,7 @@ bool packed_k0_supported(uint32_t block_size, uint32_t channels, uint32_t bytes)
     return bytes >= 1 && bytes <= 3 && block_size % 4 == 0 && ((size_t)block_size * channels * bytes) % 16 == 0;
 }
 template <int C>
-void launch_k0_packed_c(flacgpu_ctx *c, uint32_t bytes, const dim3 &grid, uint32_t n_frames, uint32_t last_len,
+bool launch_k0_packed_c(flacgpu_ctx *c, uint32_t bytes, const dim3 &grid, uint32_t n_frames, uint32_t last_len,
                         uint32_t f0, hipStream_t st) {
     const uint32_t *in = reinterpret_cast<const uint32_t *>(c->d_in);
     const uint32_t B = c->opts.block_size;
@@ -383,19 +416,22 @@ void launch_k0_packed_c(flacgpu_ctx *c, uint32_t bytes, const dim3 &grid, uint32
     default: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_deinterleave_packed<C, 3>), grid, dim3(WG), 0, st, in, c->d_planar, B,
                                 c->ldb, n_frames, last_len, c->d_orbits, f0, abs); break;
     }
-    c->abs_valid = abs != nullptr;
+    return abs != nullptr;
 }
-void launch_k0_packed(flacgpu_ctx *c, uint32_t bytes, uint32_t n_frames, uint32_t last_len, hipStream_t st) {
+// (the orbits always; returns K0Result::have_abs)
+bool launch_k0_packed(flacgpu_ctx *c, uint32_t bytes, uint32_t n_frames, uint32_t last_len, hipStream_t st) {
     const uint32_t B = c->opts.block_size;
+    bool have_abs = false;
     for (uint32_t f0 = 0; f0 < n_frames; f0 += kGridY) {
         const dim3 grid(std::max<uint32_t>(1u, (B / 4 + WG - 1) / WG), std::min(kGridY, n_frames - f0));   // 4 PCM frames per lane
         switch (c->channels) {
-#define X(C) case C: launch_k0_packed_c<C>(c, bytes, grid, n_frames, last_len, f0, st); break;
+#define X(C) case C: have_abs = launch_k0_packed_c<C>(c, bytes, grid, n_frames, last_len, f0, st); break;
             X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8)
 #undef X
         default: break;
         }
     }
+    return have_abs;
 }
 __global__ void __launch_bounds__(WG) k_copy16(const uint4 *__restrict__ src, uint4 *__restrict__ dst, size_t n16) {
     for (size_t i = (size_t)blockIdx.x * WG + threadIdx.x; i < n16; i += (size_t)gridDim.x * WG) dst[i] = src[i];
@@ -724,108 +760,84 @@ static int next_layout_epoch(flacgpu_ctx *c, PackParams &q, hipStream_t st) {
 // residual rows, flacgpu_device_buffer): a DIRECT batch never split its channels, so K0 runs now, from the
 // caller's buffer
 static int ensure_planar(flacgpu_ctx *c) {
-    if (c->planar_valid) return FLACGPU_OK;
-    if (!c->direct_src || c->last_frames == 0) return FLACGPU_OK;
+    Batch &b = c->batch;
+    if (b.planar_valid) return FLACGPU_OK;
+    if (!b.direct_src || b.n_frames == 0) return FLACGPU_OK;
     if (int rc = ctx_sync(c)) return rc;
-    if (c->seg_active && c->seg_direct) {   // frame f0 + i of segment s is frame i of its own buffer
+    if (b.kind == Batch::SEGMENTS && b.seg_direct) {   // frame f0 + i of segment s is frame i of its own buffer
         uint32_t f0 = 0;
         const size_t frame_ints = (size_t)c->opts.block_size * c->channels;
-        for (const flacgpu_segment &g : c->segs) {
-            (void)launch_k0(c, g.pcm - (ptrdiff_t)(f0 * frame_ints), FLACGPU_LAYOUT_INTERLEAVED, c->last_frames, c->last_len, f0,
-                            g.n_frames, ctx_stream(c));
+        for (const flacgpu_segment &g : b.segs) {
+            (void)launch_k0(c, g.pcm - (ptrdiff_t)(f0 * frame_ints), FLACGPU_LAYOUT_INTERLEAVED, b.n_frames, b.last_len, f0,
+                            g.n_frames, nullptr, ctx_stream(c));
             f0 += g.n_frames;
         }
     } else
-    (void)launch_k0(c, c->direct_src, FLACGPU_LAYOUT_INTERLEAVED, c->last_frames, c->last_len, 0, c->last_frames,
-                    ctx_stream(c));
+    (void)launch_k0(c, b.direct_src, FLACGPU_LAYOUT_INTERLEAVED, b.n_frames, b.last_len, 0, b.n_frames, nullptr, ctx_stream(c));
     HIP_TRY(hipGetLastError());
     if (int rc = ctx_sync(c)) return rc;
-    c->planar_valid = true;
+    b.planar_valid = true;
     return FLACGPU_OK;
 }
 
-// given: the batch's route where the caller has asked plan_route already (flacgpu_encode_device, the segment entries)
-static int analyze_impl(flacgpu_ctx *c, const int32_t *d_pcm, int layout, uint32_t n_frames,
-                        uint32_t last_len, hipStream_t st, uint32_t packed_bytes, const Route *given = nullptr);
-
-// A batch that is NOT made of segments begins: the per-frame tables of an earlier flacgpu_encode_segments* batch on this
-// context (frame numbers, addresses, the segments ensure_planar would walk) must not reach its frame assembly or verifier.
-static void begin_plain_batch(flacgpu_ctx *c) {
-    c->seg_active = c->seg_pending = c->seg_direct = false;
-    c->rag_active = c->rag_pending = false;
-    c->k0_frame_n = nullptr;
-    c->segs.clear();
-}
-
-static void launch_candidates_and_decide(flacgpu_ctx *c, const Params &p, const Params &pf, const Params &pg, bool ranged,
-                                         hipStream_t st, const std::function<void(int)> &begin);
-
-// A batch has been submitted on `st`: what every later entry point reads about it.  only_copy: the caller's buffer where the
-// kernels read it in place and wrote no planar rows (ensure_planar fills them on demand); analysed: LPC order ties may be
-// waiting for the host's re-decision (resolve_order_ties); packed: the frames were assembled in the same go.
-static void batch_submitted(flacgpu_ctx *c, const Params &p, const Route &r, hipStream_t st, const int32_t *only_copy,
-                            bool analysed, bool packed) {
-    c->last_frames = p.n_frames;
-    c->last_len = p.last_len;
-    c->last_params = p;
-    c->last_stream = st;
-    c->route = r;
-    c->resid_valid = false;
-    c->planar_valid = only_copy == nullptr;
-    c->direct_src = only_copy;
-    c->packed_valid = packed;
-    c->total_valid = false;
-    if (analysed) {
-        c->ties_checked = p.max_lpc_order == 0;
-        c->ties_resolved = 0;
-        c->fir_rechecked = 0;
-    }
-    c->drained = false;
-}
-
-int flacgpu_analyze_device(flacgpu_ctx *c, const int32_t *d_pcm, int layout, uint32_t n_frames,
-                           uint32_t last_len, void *stream) {
-    if (!c || !d_pcm) {
-        g_last_error = "invalid analyze arguments";
-        return FLACGPU_ERR_INVALID_ARG;
-    }
-    CTX_GUARD(c);
-    hipStream_t st;
-    if (int rc = resolve_stream(c, stream, &st)) return rc;
-    return analyze_impl(c, d_pcm, layout, n_frames, last_len, st, 0);
-}
-
-static int analyze_impl(flacgpu_ctx *c, const int32_t *d_pcm, int layout, uint32_t n_frames,
-                        uint32_t last_len, hipStream_t st, uint32_t packed_bytes, const Route *given) {
-    if (!c || !d_pcm || n_frames == 0 || n_frames > c->max_frames || last_len == 0 ||
+// What refuses a batch of whole blocks (and a last one of last_len) for its arguments.  Every entry asks BEFORE it uploads,
+// launches or writes anything -- a table, a staging array, the record --, so a refused call leaves the batch in hand
+// fetchable.  (A ragged batch's lengths: flacenc_ragged::plan.)
+static int refuse_batch(const flacgpu_ctx *c, const void *pcm, int layout, uint64_t n_frames, uint32_t last_len) {
+    if (!c || !pcm || n_frames == 0 || n_frames > c->max_frames || last_len == 0 ||
         last_len > c->opts.block_size || (layout != 0 && layout != 1)) {
         g_last_error = "invalid analyze arguments";
         return FLACGPU_ERR_INVALID_ARG;
     }
-    // (a batch made of segments announces itself just before; the entry points that start a batch WITHOUT passing here --
-    // the two-ranges branch of flacgpu_encode_device, flacgpu_pack_plans -- call begin_plain_batch themselves)
-    if (c->rng_cnt == 0 || c->rng_f0 == 0) {
-        if (c->seg_pending) {
-            c->seg_active = true;
-            c->seg_pending = false;
-            c->rag_active = c->rag_pending;   // (a ragged batch announces itself as a segments batch does: frame numbers from d_seg_fn)
-            c->rag_pending = false;
-            c->k0_frame_n = c->rag_active ? c->d_rag_tab : nullptr;
-        } else {
-            begin_plain_batch(c);
-        }
-    }
-    const uint32_t B = c->opts.block_size;
-    const bool ragged = c->rag_active;   // (its lengths were checked by flacenc_ragged::plan, its windows lie in the pool)
     // the reference collects partitions into ArrayVec<_, 64> and panics beyond (encode.rs:3880)
-    if (!ragged)
-    for (uint32_t n : {n_frames > 1 ? B : last_len, last_len}) {
+    for (uint32_t n : {n_frames > 1 ? c->opts.block_size : last_len, last_len}) {
         uint32_t tz = (uint32_t)__builtin_ctz(n);
         if ((tz < c->opts.max_partition_order ? tz : c->opts.max_partition_order) > (uint32_t)MAXP) {
             g_last_error = "effective partition order > 6: the reference panics (MAX_PARTITIONS = 64)";
             return FLACGPU_ERR_UNSUPPORTED;
         }
     }
+    return FLACGPU_OK;
+}
+
+// The analysis of a batch the entry has checked (refuse_batch) and routed; the record is committed behind the launches.
+static int analyze_impl(flacgpu_ctx *c, const int32_t *d_pcm, int layout, uint32_t n_frames, uint32_t last_len, hipStream_t st,
+                        const Submission &s);
+
+static void launch_candidates_and_decide(flacgpu_ctx *c, const Params &p, const Params &pf, const Params &pg, bool ranged,
+                                         hipStream_t st, const std::function<void(int)> &begin);
+
+// The record of a batch submitted on `st`, as far as every batch has it.
+static Batch new_batch(Batch::Kind kind, const Params &p, const Route &r, hipStream_t st) {
+    Batch b;
+    b.kind = kind;
+    b.n_frames = p.n_frames;
+    b.last_len = p.last_len;
+    b.params = p;
+    b.route = r;
+    b.stream = st;
+    return b;
+}
+static void commit_batch(flacgpu_ctx *c, Batch &&b) {
+    c->batch = std::move(b);
+    c->drained = false;
+}
+
+int flacgpu_analyze_device(flacgpu_ctx *c, const int32_t *d_pcm, int layout, uint32_t n_frames,
+                           uint32_t last_len, void *stream) {
+    if (int rc = refuse_batch(c, d_pcm, layout, n_frames, last_len)) return rc;
+    CTX_GUARD(c);
+    hipStream_t st;
+    if (int rc = resolve_stream(c, stream, &st)) return rc;
+    Submission s;
+    s.route = route_of(c, aligned16(d_pcm), layout, n_frames, last_len);
+    return analyze_impl(c, d_pcm, layout, n_frames, last_len, st, s);
+}
+
+static int analyze_impl(flacgpu_ctx *c, const int32_t *d_pcm, int layout, uint32_t n_frames, uint32_t last_len, hipStream_t st,
+                        const Submission &s) {
+    const uint32_t B = c->opts.block_size;
+    const bool ragged = s.kind == Batch::RAGGED;   // (its windows lie in the pool)
     if (!ragged && last_len != B && last_len != c->window_last_len) {
         if (int rc = upload_window(c, last_len, c->d_window_last, st)) return rc;
         c->window_last_len = last_len;
@@ -837,8 +849,6 @@ static int analyze_impl(flacgpu_ctx *c, const int32_t *d_pcm, int layout, uint32
         p.frame_win = c->d_rag_tab + c->max_frames;
         p.window_pool = c->d_rag_pool;
     }
-    c->host_out = nullptr;   // a new batch: frames go to d_packed unless flacgpu_encode_packed_async_host says otherwise
-    c->out_in_host = false;
 
     int evi = 0;
     for (auto &u : c->ev_used) u = false;
@@ -856,10 +866,10 @@ static int analyze_impl(flacgpu_ctx *c, const int32_t *d_pcm, int layout, uint32
         mark(k);
     };
 
-    const Route r = given ? *given : route_of(c, aligned16(d_pcm), layout, n_frames, last_len, packed_bytes);
+    const Route &r = s.route;
     const uint32_t ncb = n_frames * c->ncand;
-    const bool ranged = c->rng_cnt != 0;                 // (flacgpu_encode_device: a route with range_frames != 0)
-    const uint32_t rf0 = ranged ? c->rng_f0 : 0u, rcnt = ranged ? c->rng_cnt : n_frames;
+    const bool ranged = s.count != 0;                    // (flacgpu_encode_device: a route with range_frames != 0)
+    const uint32_t rf0 = ranged ? s.f0 : 0u, rcnt = ranged ? s.count : n_frames;
     const bool first_range = rf0 == 0;
     if (first_range) HIP_TRY(hipMemsetAsync(c->d_stats_base, 0, sizeof(uint32_t) * (kTurnWords + 4 + (size_t)ncb), st));  // + d_orbits
     // The input (Route::Input).  DIRECT_STEREO and SPLIT_XPOSE leave the caller's buffer the only copy of the input: it must
@@ -876,31 +886,30 @@ static int analyze_impl(flacgpu_ctx *c, const int32_t *d_pcm, int layout, uint32
         p.xpose = xpose ? 1u : 0u;
         if (c->channels == 1) p.planar = d_pcm;   // [frame][B] with ldb == B
     }
-    c->abs_valid = false;
     if (c->d_abs && first_range) HIP_TRY(hipMemsetAsync(c->d_abs, 0, sizeof(unsigned long long) * 4 * n_frames, st));
     // K0 (+ OR of every candidate's samples -> wasted bits)
     if (!r.in_place()) begin(0);
-    bool have_orbits = true;
+    K0Result k0{true, false};
     if (r.input == Route::K0_PACKED) {
-        launch_k0_packed(c, packed_bytes, n_frames, last_len, st);
+        k0.have_abs = launch_k0_packed(c, s.packed_bytes, n_frames, last_len, st);
     } else if (r.input == Route::PLANAR_IN_PLACE) {
         p.planar = d_pcm;  // [frame][ch][B] with ldb == B
-        have_orbits = false;
+        k0.have_orbits = false;
     } else if (r.input == Route::K0_COPY) {
-        have_orbits = launch_k0(c, d_pcm, layout, n_frames, last_len, 0, n_frames, st);
+        k0 = launch_k0(c, d_pcm, layout, n_frames, last_len, 0, n_frames, p.frame_n, st);
     }
-    if (!have_orbits)
+    if (!k0.have_orbits)
         launch_orbits(p, c->d_orbits, st);
     const size_t dyn2 = (2 * (size_t)B + B / 16 + 16) * sizeof(int32_t);
     // (K0 summed the magnitudes on the way otherwise; direct input without LPC: k_cand64p<..., SELF> makes the choice)
-    if (c->stereo4 && !p.exhaustive && !c->abs_valid && !(direct && p.max_lpc_order == 0)) {
+    if (c->stereo4 && !p.exhaustive && !k0.have_abs && !(direct && p.max_lpc_order == 0)) {
         begin(1);
         if (direct) hipLaunchKernelGGL(k_stereo_stats_t<true>, dim3(n_frames), dim3(WG), 0, st, p);
         else hipLaunchKernelGGL(k_stereo_stats_t<false>, dim3(n_frames), dim3(WG), 0, st, p);
     }
     if (!r.in_place())
         hipLaunchKernelGGL(k_candinfo, dim3((ncb + WG - 1) / WG), dim3(WG), 0, st, p, c->d_orbits,
-                           c->abs_valid ? c->d_abs : nullptr);
+                           k0.have_abs ? c->d_abs : nullptr);
     // frames [0, fast_analysis) take the wave-per-candidate kernel, the rest (other block sizes, a short last frame,
     // candidates wider than 25 bits) the generic LDS ones; a range is all fast
     Params pf = p, pg = p;
@@ -948,7 +957,16 @@ static int analyze_impl(flacgpu_ctx *c, const int32_t *d_pcm, int layout, uint32
     // need them, the device-side packer recomputes residuals in registers instead
     if (c->timing) (void)hipEventRecord(c->ev[evi], st);
     HIP_TRY(hipGetLastError());
-    batch_submitted(c, p, r, st, (direct || xpose) ? d_pcm : nullptr, true, false);
+    Batch b = new_batch(s.kind, p, r, st);
+    b.direct_src = (direct || xpose) ? d_pcm : nullptr;   // the only copy of the input: no planar rows were written
+    b.planar_valid = b.direct_src == nullptr;
+    b.seg_direct = s.seg_direct;
+    if (s.segs) b.segs.assign(s.segs, s.segs + s.n_segs);
+    if (s.rag_n) b.rag_n.assign(s.rag_n, s.rag_n + n_frames);
+    b.host_out = s.host_out;
+    b.host_out_cap = s.host_out_cap;
+    b.ties_checked = p.max_lpc_order == 0;   // else LPC order ties may be waiting for the host's re-decision
+    commit_batch(c, std::move(b));
     if (c->timing) {
         HIP_TRY(hipStreamSynchronize(st));
         for (auto &m : c->last_ms) m = 0.f;
@@ -987,8 +1005,8 @@ static void launch_candidates_and_decide(flacgpu_ctx *c, const Params &p, const 
     }
 }
 
-static int pack_impl(flacgpu_ctx *c, uint64_t first_frame_number, uint32_t sample_rate, hipStream_t st,
-                     hipEvent_t after_layout);
+// The frame assembly of the batch in hand, or of the range s names (Submission() for the whole batch once more)
+static int pack_impl(flacgpu_ctx *c, uint64_t first_frame_number, uint32_t sample_rate, hipStream_t st, const Submission &s);
 
 // The candidates K4 listed (two best order estimates closer than the device's log() can be trusted
 // to separate) are re-decided here with the HOST's libm -- Levinson, order choice and quantisation
@@ -996,9 +1014,9 @@ static int pack_impl(flacgpu_ctx *c, uint64_t first_frame_number, uint32_t sampl
 // candidate stage, the assignment decision and (when done before) the frame assembly run again, so
 // that the output is what the reference produces with this host's libm (encode.rs:3656-3702).
 static int resolve_order_ties(flacgpu_ctx *c) {
-    if (c->ties_checked || c->last_frames == 0) return FLACGPU_OK;
+    if (c->batch.ties_checked || c->batch.n_frames == 0) return FLACGPU_OK;
     if (int rc = ctx_sync(c)) return rc;
-    c->ties_checked = true;
+    c->batch.ties_checked = true;
     uint32_t s[4];
     if (int rc = copy_sync(c, s, c->d_stats, sizeof s, hipMemcpyDeviceToHost)) return rc;
     const uint32_t cap = c->max_frames * c->ncand;
@@ -1009,10 +1027,10 @@ static int resolve_order_ties(flacgpu_ctx *c) {
     static_assert(sizeof(flacenc::HostLpc) == sizeof(LpcParams), "same record on both sides");
     std::vector<uint32_t> list(n_ties);
     if (int rc = copy_sync(c, list.data(), c->d_ties, sizeof(uint32_t) * n_ties, hipMemcpyDeviceToHost)) return rc;
-    Params p = c->last_params;
+    Params p = c->batch.params;
     if (recheck_fir) {
         p.check_fir = 1;   // the candidate stage below tests every FIR exactly (fir64_overflows)
-        c->fir_rechecked = s[3];
+        c->batch.fir_rechecked = s[3];
     }
     const size_t nc = (size_t)p.n_frames * p.ncand;
     std::vector<double> ac;
@@ -1036,37 +1054,34 @@ static int resolve_order_ties(flacgpu_ctx *c) {
             if (int rc = copy_sync(c, row, c->d_ac + (size_t)idx * AC_LD, sizeof row, hipMemcpyDeviceToHost)) return rc;
             if (int rc = copy_sync(c, &info, c->d_cinfo + idx, sizeof info, hipMemcpyDeviceToHost)) return rc;
         }
-        const uint32_t frame = idx / p.ncand;
-        const uint32_t n = (c->rag_active && frame < c->rag_n.size()) ? c->rag_n[frame]   // (frame_len()'s rule on the host)
-                           : (frame + 1 == p.n_frames) ? p.last_len : p.block_size;
         flacenc::HostLpc h;
-        flacenc::lpc_from_autocorr(row, p.max_lpc_order, n, info.bps, &h);
+        flacenc::lpc_from_autocorr(row, p.max_lpc_order, frame_len_of(c->batch, idx / p.ncand), info.bps, &h);
         HIP_TRY(hipMemcpyAsync(c->d_lpc + idx, &h, sizeof h, hipMemcpyHostToDevice, st));
         HIP_TRY(hipStreamSynchronize(st));   // `h` is a local
     }
     // candidate stage + assignment again (k_fixed's results are still in place)
     Params pf = p, pg = p;
     pf.f0 = 0;
-    pf.fcount = c->route.fast_analysis;
-    pg.f0 = c->route.fast_analysis;
-    pg.fcount = p.n_frames - c->route.fast_analysis;
+    pf.fcount = c->batch.route.fast_analysis;
+    pg.f0 = c->batch.route.fast_analysis;
+    pg.fcount = p.n_frames - c->batch.route.fast_analysis;
     launch_candidates_and_decide(c, p, pf, pg, false, st, [](int) {});
     HIP_TRY(hipGetLastError());
-    c->resid_valid = false;
-    c->ties_resolved = n_ties;
-    if (c->packed_valid)
-        if (int rc = pack_impl(c, c->last_first_frame, c->last_rate, st, nullptr)) return rc;
+    c->batch.resid_valid = false;
+    c->batch.ties_resolved = n_ties;
+    if (c->batch.packed_valid)
+        if (int rc = pack_impl(c, c->batch.first_frame, c->batch.rate, st, Submission())) return rc;
     return ctx_sync(c);
 }
 
 static int ensure_residual_rows(flacgpu_ctx *c) {
-    if (c->resid_valid) return FLACGPU_OK;
+    if (c->batch.resid_valid) return FLACGPU_OK;
     // (the rows take the place of what the candidate kernel handed to k_frame64 -- Params::hand_meta --: a frame assembly that
     // follows fetches its samples itself)
-    c->last_params.hand_meta = nullptr;
+    c->batch.params.hand_meta = nullptr;
     if (int rc = ensure_planar(c)) return rc;   // k_emit reads planar rows
     if (int rc = ctx_sync(c)) return rc;
-    const Params &p = c->last_params;
+    const Params &p = c->batch.params;
     if (p.block_size > LDS_BLOCK_LIMIT)
         hipLaunchKernelGGL(k_emit_t<true>, dim3(p.n_frames * p.channels), dim3(WG), 0, ctx_stream(c), p);
     else
@@ -1074,15 +1089,15 @@ static int ensure_residual_rows(flacgpu_ctx *c) {
                            (size_t)p.block_size * sizeof(int32_t), ctx_stream(c), p);
     HIP_TRY(hipGetLastError());
     if (int rc = ctx_sync(c)) return rc;
-    c->resid_valid = true;
+    c->batch.resid_valid = true;
     return FLACGPU_OK;
 }
 
 int flacgpu_fetch(flacgpu_ctx *c, flacgpu_frame_plan *plans, flacgpu_subframe_plan *subs,
                   int32_t *residuals) {
-    if (!c || c->last_frames == 0) return FLACGPU_ERR_INVALID_ARG;
+    if (!c || c->batch.n_frames == 0) return FLACGPU_ERR_INVALID_ARG;
     CTX_GUARD(c);
-    const size_t F = c->last_frames;
+    const size_t F = c->batch.n_frames;
     hipStream_t st = c->own_stream;
     if (int rc = ctx_sync(c)) return rc;
     if (int rc = resolve_order_ties(c)) return rc;
@@ -1102,87 +1117,86 @@ int flacgpu_fetch(flacgpu_ctx *c, flacgpu_frame_plan *plans, flacgpu_subframe_pl
 int flacgpu_analyze(flacgpu_ctx *c, const int32_t *pcm, int layout, uint32_t n_frames,
                     uint32_t last_len, flacgpu_frame_plan *plans, flacgpu_subframe_plan *subs,
                     int32_t *residuals) {
-    if (!c || !pcm || n_frames == 0 || n_frames > c->max_frames || last_len == 0 ||
-        last_len > c->opts.block_size) {
-        g_last_error = "invalid analyze arguments";
-        return FLACGPU_ERR_INVALID_ARG;
-    }
+    if (int rc = refuse_batch(c, pcm, layout, n_frames, last_len)) return rc;
     CTX_GUARD(c);
     const size_t B = c->opts.block_size, C = c->channels;
     const size_t count = ((size_t)(n_frames - 1) * B + last_len) * C;
     HIP_TRY(hipMemcpyAsync(c->d_in, pcm, count * sizeof(int32_t), hipMemcpyHostToDevice, c->own_stream));
     // planar host input with a short last frame is laid out [frame][ch][len]; handled by K0
-    int rc = analyze_impl(c, c->d_in, layout, n_frames, last_len, c->own_stream, 0);
-    if (rc) return rc;
+    Submission s;
+    s.route = route_of(c, aligned16(c->d_in), layout, n_frames, last_len);
+    if (int rc = analyze_impl(c, c->d_in, layout, n_frames, last_len, c->own_stream, s)) return rc;
     return flacgpu_fetch(c, plans, subs, residuals);
 }
 
-
-// after_layout: an event recorded right behind k_layout (the frame sizes are known from there on)
-static int pack_impl(flacgpu_ctx *c, uint64_t first_frame_number, uint32_t sample_rate, hipStream_t st,
-                     hipEvent_t after_layout);
-
 int flacgpu_pack_device(flacgpu_ctx *c, uint64_t first_frame_number, uint32_t sample_rate,
                         void *stream) {
-    if (!c || c->last_frames == 0) {
+    if (!c || c->batch.n_frames == 0) {
         g_last_error = "flacgpu_pack_device: no analysed batch";
         return FLACGPU_ERR_INVALID_ARG;
     }
     CTX_GUARD(c);
     hipStream_t st;
     if (int rc = resolve_stream(c, stream, &st)) return rc;
-    return pack_impl(c, first_frame_number, sample_rate, st, nullptr);
+    return pack_impl(c, first_frame_number, sample_rate, st, Submission());
 }
 
-static int pack_impl(flacgpu_ctx *c, uint64_t first_frame_number, uint32_t sample_rate, hipStream_t st,
-                     hipEvent_t after_layout) {
-    c->last_first_frame = first_frame_number;
-    c->last_rate = sample_rate;
-    const Params &p = c->last_params;
+// What the frame assembly and the verifier are told about a batch's output: its frame numbers (per frame from d_seg_fn
+// where the batch has a table of them), into d_packed
+static PackParams pack_params_of(const flacgpu_ctx *c, const Batch &b, uint64_t first_frame_number, uint32_t sample_rate) {
     PackParams q;
     q.first_frame_number = first_frame_number;
-    if (c->seg_active) q.frame_numbers = c->d_seg_fn;
+    if (b.numbered()) q.frame_numbers = c->d_seg_fn;
     q.sample_rate = sample_rate;
-    q.out_words = c->d_packed;   // (k_layout does not look at it; replaced below for host output)
+    q.out_words = c->d_packed;
     q.frame_off = c->d_frame_off;
     q.cap_bytes = c->packed_cap;
+    return q;
+}
+
+static int pack_impl(flacgpu_ctx *c, uint64_t first_frame_number, uint32_t sample_rate, hipStream_t st, const Submission &s) {
+    Batch &b = c->batch;
+    b.first_frame = first_frame_number;
+    b.rate = sample_rate;
+    const Params &p = b.params;
+    PackParams q = pack_params_of(c, b, first_frame_number, sample_rate);   // (out_words: replaced below for host output)
     hipEvent_t *ev = c->ev;  // reuse the event pool: [0..3]
     if (c->timing) (void)hipEventRecord(ev[0], st);
-    const bool ranged = c->rng_cnt != 0;
+    const bool ranged = s.count != 0;
     if (int rc = next_layout_epoch(c, q, st)) return rc;
     if (ranged) {   // this range's frames only: their offsets continue from the previous range's end (frame_off[f0])
         Params pr = p;
-        pr.f0 = c->rng_f0;
-        pr.fcount = c->rng_cnt;
+        pr.f0 = s.f0;
+        pr.fcount = s.count;
         launch_layout(pr, q, st);
     } else {
         launch_layout(p, q, st);
     }
-    if (after_layout) HIP_TRY(hipEventRecord(after_layout, st));
+    if (s.after_layout) HIP_TRY(hipEventRecord(s.after_layout, st));
     // frames of a wave block length are assembled whole in LDS by k_frame64 (residuals recomputed
     // from the PCM, CRC-16 from LDS, one write of the finished bytes); any other frame goes
     // through k_emit (residual rows) -> k_pack (one workgroup per subframe, zero-filled output,
     // atomic OR at shared words) -> k_crc
     // (which frames: Route::fast_pack; a range is all fast)
     const uint32_t B = p.block_size;
-    const uint32_t n_fast = c->route.fast_pack;
+    const uint32_t n_fast = b.route.fast_pack;
     const bool fused = n_fast != 0;
     Params pf = p, pg = p;
-    pf.f0 = ranged ? c->rng_f0 : 0u;
-    pf.fcount = ranged ? c->rng_cnt : n_fast;
+    pf.f0 = ranged ? s.f0 : 0u;
+    pf.fcount = ranged ? s.count : n_fast;
     pg.f0 = n_fast;
     pg.fcount = p.n_frames - n_fast;
     uint32_t fbw = frame_fb_words(p.channels, c->bps, B);   // k_frame64's LDS image
     if (c->stereo4 && p.exhaustive) fbw = std::min(fbw, frame_fb_words_exhaustive_stereo(c->bps, B));
     // host output: k_frame64 only ever stores (dwords inside a frame, bytes at its ends), so it can write
     // over PCIe into pinned memory; the generic packer builds its frames with atomic ORs and cannot
-    c->out_in_host = c->host_out && c->route.host_out_possible && c->host_out_cap >= c->packed_cap;
-    if (c->out_in_host) q.out_words = reinterpret_cast<uint32_t *>(c->host_out);
+    b.out_in_host = b.host_out && b.route.host_out_possible && b.host_out_cap >= c->packed_cap;
+    if (b.out_in_host) q.out_words = reinterpret_cast<uint32_t *>(b.host_out);
     if (pg.fcount) launch_zero(q, p.n_frames, st);
     if (c->timing) (void)hipEventRecord(ev[1], st);
     if (pf.fcount) launch_frame64(pf, q, B, pf.fcount, (size_t)fbw * sizeof(int32_t), st);
     if (pg.fcount) {
-        if (!c->resid_valid) {  // residual rows of these frames
+        if (!b.resid_valid) {  // residual rows of these frames
             if (p.block_size > LDS_BLOCK_LIMIT)
                 hipLaunchKernelGGL(k_emit_t<true>, dim3(pg.fcount * p.channels), dim3(WG), 0, st, pg);
             else
@@ -1200,9 +1214,9 @@ static int pack_impl(flacgpu_ctx *c, uint64_t first_frame_number, uint32_t sampl
     }
     if (c->timing) (void)hipEventRecord(ev[3], st);
     HIP_TRY(hipGetLastError());
-    c->packed_valid = true;
-    c->total_valid = false;
-    c->last_stream = st;
+    b.packed_valid = true;
+    b.total_valid = false;
+    b.stream = st;
     c->drained = false;
     if (c->timing) {
         HIP_TRY(hipStreamSynchronize(st));
@@ -1262,38 +1276,36 @@ int flacgpu_encode_device(flacgpu_ctx *c, const int32_t *d_pcm, int layout, uint
         g_last_error = "invalid encode arguments";
         return FLACGPU_ERR_INVALID_ARG;
     }
+    if (int rc = refuse_batch(c, d_pcm, layout, n_frames, last_len)) return rc;
     const uint32_t B = c->opts.block_size;
-    const Route route = route_of(c, aligned16(d_pcm), layout, n_frames, last_len, 0, false, true);
+    Submission s;
+    s.route = route_of(c, aligned16(d_pcm), layout, n_frames, last_len, 0, false, true);
+    const Route &route = s.route;
     hipStream_t st0;
     if (int rc = resolve_stream(c, stream, &st0)) return rc;
-    if (!route.two_ranges || n_frames > c->max_frames) {   // (too many frames: analyze_impl says so)
-        if (route.range_frames) {   // the whole kernel chain range by range, each range's frame offsets continuing from the one before
-            int rc = FLACGPU_OK;
-            for (uint32_t f0 = 0; f0 < n_frames && rc == FLACGPU_OK; f0 += route.range_frames) {
-                c->rng_f0 = f0;
-                c->rng_cnt = std::min(route.range_frames, n_frames - f0);
-                rc = analyze_impl(c, d_pcm, layout, n_frames, last_len, st0, 0, &route);
-                if (rc == FLACGPU_OK) rc = pack_impl(c, first_frame_number, sample_rate, st0, nullptr);
-            }
-            c->rng_f0 = c->rng_cnt = 0;
-            return rc;
+    if (!route.two_ranges) {
+        // (with Route::range_frames the whole kernel chain range by range, each range's frame offsets continuing from the one before)
+        const uint32_t step = route.range_frames ? route.range_frames : n_frames;
+        for (uint32_t f0 = 0; f0 < n_frames; f0 += step) {
+            s.f0 = f0;
+            s.count = route.range_frames ? std::min(step, n_frames - f0) : 0u;
+            if (int rc = analyze_impl(c, d_pcm, layout, n_frames, last_len, st0, s)) return rc;
+            if (int rc = pack_impl(c, first_frame_number, sample_rate, st0, s)) return rc;
         }
-        if (int rc = analyze_impl(c, d_pcm, layout, n_frames, last_len, st0, 0, &route)) return rc;
-        return pack_impl(c, first_frame_number, sample_rate, st0, nullptr);
+        return FLACGPU_OK;
     }
     hipStream_t st1 = c->aux_stream;
-    begin_plain_batch(c);   // (this branch never passes analyze_impl)
     Params p;
     fill_params(c, n_frames, last_len, p);
-    PackParams q;
-    q.first_frame_number = first_frame_number;
-    q.sample_rate = sample_rate;
-    q.out_words = c->d_packed;
-    q.frame_off = c->d_frame_off;
-    q.cap_bytes = c->packed_cap;
     // (planar rows are read in place unless the caller asked for a copy: FLACGPU_TUNE_COPY_INPUT / FLACGPU_NO_DIRECT)
     const bool planar_direct = route.input == Route::PLANAR_IN_PLACE;
     if (planar_direct) p.planar = d_pcm;
+    Batch b = new_batch(Batch::PLAIN, p, route, st0);   // (committed behind the launches)
+    b.ties_checked = p.max_lpc_order == 0;
+    b.packed_valid = true;
+    b.first_frame = first_frame_number;
+    b.rate = sample_rate;
+    PackParams q = pack_params_of(c, b, first_frame_number, sample_rate);
     HIP_TRY(hipMemsetAsync(c->d_stats_base, 0, sizeof(uint32_t) * (kTurnWords + 4 + (size_t)n_frames * c->ncand), st0));  // + d_orbits
     HIP_TRY(hipEventRecord(c->ev_fork, st0));
     HIP_TRY(hipStreamWaitEvent(st1, c->ev_fork, 0));
@@ -1307,8 +1319,8 @@ int flacgpu_encode_device(flacgpu_ctx *c, const int32_t *d_pcm, int layout, uint
         r.fcount = half ? n_frames - h : h;
         r.turn_counter = c->d_stats_base + half;   // the two ranges' candidate kernels may run side by side
         const uint32_t ncb = r.fcount * c->ncand;
-        bool have_orbits = false;
-        if (!planar_direct) have_orbits = launch_k0(c, d_pcm, layout, n_frames, last_len, r.f0, r.fcount, st);
+        // (whatever K0 summed, k_stereo_stats runs for both halves and k_candinfo is told of no sums)
+        const bool have_orbits = !planar_direct && launch_k0(c, d_pcm, layout, n_frames, last_len, r.f0, r.fcount, nullptr, st).have_orbits;
         if (!have_orbits) launch_orbits(r, c->d_orbits, st);
         if (c->stereo4 && !p.exhaustive) hipLaunchKernelGGL(k_stereo_stats_t<false>, dim3(r.fcount), dim3(WG), 0, st, r);
         hipLaunchKernelGGL(k_candinfo, dim3((ncb + WG - 1) / WG), dim3(WG), 0, st, r, c->d_orbits, (const unsigned long long *)nullptr);
@@ -1327,9 +1339,7 @@ int flacgpu_encode_device(flacgpu_ctx *c, const int32_t *d_pcm, int layout, uint
     HIP_TRY(hipEventRecord(c->ev_join, st1));
     HIP_TRY(hipStreamWaitEvent(st0, c->ev_join, 0));
     HIP_TRY(hipGetLastError());
-    batch_submitted(c, p, route, st0, nullptr, true, true);
-    c->last_first_frame = first_frame_number;
-    c->last_rate = sample_rate;
+    commit_batch(c, std::move(b));
     return FLACGPU_OK;
 }
 
@@ -1360,6 +1370,7 @@ static int segments_common(flacgpu_ctx *c, const flacgpu_segment *segs, uint32_t
         g_last_error = "flacgpu_encode_segments: more frames than the context was created for";
         return FLACGPU_ERR_INVALID_ARG;
     }
+    if (int rc = refuse_batch(c, segs[0].pcm, FLACGPU_LAYOUT_INTERLEAVED, total, B)) return rc;   // (the partition order)
     const size_t F = c->max_frames;
     if (int rc = ensure_segment_tables(c)) return rc;
     // the staging arrays and the device tables of the batch before are free once BOTH streams are idle: the one this call
@@ -1371,13 +1382,17 @@ static int segments_common(flacgpu_ctx *c, const flacgpu_segment *segs, uint32_t
     // otherwise gathered into d_in and routed as one plain batch there
     bool all_aligned = true;
     for (uint32_t i = 0; i < n_segs; i++) all_aligned = all_aligned && aligned16(segs[i].pcm);
-    Route route = route_of(c, all_aligned, FLACGPU_LAYOUT_INTERLEAVED, (uint32_t)total, B, 0, on_device);
-    const bool direct = route.segments_in_place;
-    if (!direct) route = route_of(c, aligned16(c->d_in), FLACGPU_LAYOUT_INTERLEAVED, (uint32_t)total, B);
+    Submission s;
+    s.kind = Batch::SEGMENTS;
+    s.route = route_of(c, all_aligned, FLACGPU_LAYOUT_INTERLEAVED, (uint32_t)total, B, 0, on_device);
+    const bool direct = s.route.segments_in_place;
+    if (!direct) s.route = route_of(c, aligned16(c->d_in), FLACGPU_LAYOUT_INTERLEAVED, (uint32_t)total, B);
+    s.seg_direct = direct;
+    s.segs = segs;
+    s.n_segs = n_segs;
     uint64_t *fn = c->h_seg;
     const int32_t **ptr = reinterpret_cast<const int32_t **>(c->h_seg + F);
     uint32_t f = 0;
-    c->segs.assign(segs, segs + n_segs);
     for (uint32_t i = 0; i < n_segs; i++) {
         for (uint32_t k = 0; k < segs[i].n_frames; k++, f++) {
             fn[f] = segs[i].first_frame_number + k;
@@ -1390,14 +1405,8 @@ static int segments_common(flacgpu_ctx *c, const flacgpu_segment *segs, uint32_t
     }
     HIP_TRY(hipMemcpyAsync(c->d_seg_fn, fn, sizeof(uint64_t) * total, hipMemcpyHostToDevice, st));
     if (direct) HIP_TRY(hipMemcpyAsync(c->d_seg_ptr, ptr, sizeof(int32_t *) * total, hipMemcpyHostToDevice, st));
-    c->seg_pending = true;
-    c->seg_direct = direct;
-    c->rng_f0 = c->rng_cnt = 0;
-    if (int rc = analyze_impl(c, direct ? segs[0].pcm : c->d_in, FLACGPU_LAYOUT_INTERLEAVED, (uint32_t)total, B, st, 0, &route)) {
-        c->seg_pending = false;   // (refused before the analysis took the announcement)
-        return rc;
-    }
-    return pack_impl(c, segs[0].first_frame_number, sample_rate, st, nullptr);
+    if (int rc = analyze_impl(c, direct ? segs[0].pcm : c->d_in, FLACGPU_LAYOUT_INTERLEAVED, (uint32_t)total, B, st, s)) return rc;
+    return pack_impl(c, segs[0].first_frame_number, sample_rate, st, s);
 }
 
 int flacgpu_encode_segments_device(flacgpu_ctx *c, const flacgpu_segment *segs, uint32_t n_segs, uint32_t sample_rate,
@@ -1526,23 +1535,17 @@ int flacgpu_encode_ragged_device(flacgpu_ctx *c, const flacgpu_ragged_frame *fra
     HIP_TRY(hipMemcpyAsync(c->d_seg_fn, fn, sizeof(uint64_t) * n_frames, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(c->d_rag_runs, c->h_rag_runs, sizeof(PlaceRun) * n_frames, hipMemcpyHostToDevice, st));
     if (int rc = launch_place_runs(c->d_rag_runs, n_frames, groups, st)) return rc;
-    c->rag_n = lens;
-    c->segs.clear();
-    c->seg_pending = true;
-    c->rag_pending = true;
-    c->seg_direct = false;
-    c->rng_f0 = c->rng_cnt = 0;
     RouteBatch rb;
     rb.n_frames = n_frames;
     rb.last_len = lens[n_frames - 1];
     rb.layout = FLACGPU_LAYOUT_INTERLEAVED;
     rb.ragged = true;
-    const Route route = flacenc_route::plan_route(route_context_of(c), rb);
-    if (int rc = analyze_impl(c, c->d_in, FLACGPU_LAYOUT_INTERLEAVED, n_frames, lens[n_frames - 1], st, 0, &route)) {
-        c->seg_pending = c->rag_pending = false;   // (refused before the analysis took the announcement)
-        return rc;
-    }
-    return pack_impl(c, frames[0].frame_number, sample_rate, st, nullptr);
+    Submission s;
+    s.kind = Batch::RAGGED;
+    s.rag_n = lens.data();
+    s.route = flacenc_route::plan_route(route_context_of(c), rb);
+    if (int rc = analyze_impl(c, c->d_in, FLACGPU_LAYOUT_INTERLEAVED, n_frames, lens[n_frames - 1], st, s)) return rc;
+    return pack_impl(c, frames[0].frame_number, sample_rate, st, s);
 }
 
 // how often this context has uploaded its ragged window pool (a test of the pool's reuse reads it)
@@ -1550,12 +1553,12 @@ uint64_t flacgpu_ragged_pool_uploads(const flacgpu_ctx *c) { return c ? c->rag_p
 
 int flacgpu_fetch_frames(flacgpu_ctx *c, uint8_t *out, size_t cap, uint64_t *offsets,
                          uint64_t *total) {
-    if (!c || !c->packed_valid) {
+    if (!c || !c->batch.packed_valid) {
         g_last_error = "flacgpu_fetch_frames: nothing packed";
         return FLACGPU_ERR_INVALID_ARG;
     }
     CTX_GUARD(c);
-    const size_t F = c->last_frames;
+    const size_t F = c->batch.n_frames;
     if (int rc = ctx_sync(c)) return rc;
     if (int rc = resolve_order_ties(c)) return rc;
     std::vector<uint64_t> off;
@@ -1571,8 +1574,8 @@ int flacgpu_fetch_frames(flacgpu_ctx *c, uint8_t *out, size_t cap, uint64_t *off
         g_last_error = "output buffer too small";
         return FLACGPU_ERR_BUFFER_TOO_SMALL;
     }
-    if (c->out_in_host) {   // the batch was assembled into the caller's host buffer (ctx_sync above: complete)
-        if (out != c->host_out) memcpy(out, c->host_out, bytes);
+    if (c->batch.out_in_host) {   // the batch was assembled into the caller's host buffer (ctx_sync above: complete)
+        if (out != c->batch.host_out) memcpy(out, c->batch.host_out, bytes);
         return FLACGPU_OK;
     }
     if (int rc = copy_sync(c, out, c->d_packed, bytes, hipMemcpyDeviceToHost)) return rc;
@@ -1581,35 +1584,35 @@ int flacgpu_fetch_frames(flacgpu_ctx *c, uint8_t *out, size_t cap, uint64_t *off
 
 // flacgpu_fetch_frames up to and including the download of the offsets; the frame bytes stay where they are
 int flacgpu_frame_offsets(flacgpu_ctx *c, uint64_t *offsets, uint64_t *total) {
-    if (!c || !c->packed_valid) {
+    if (!c || !c->batch.packed_valid) {
         g_last_error = "flacgpu_frame_offsets: nothing packed";
         return FLACGPU_ERR_INVALID_ARG;
     }
     CTX_GUARD(c);
-    const size_t F = c->last_frames;
+    const size_t F = c->batch.n_frames;
     if (int rc = ctx_sync(c)) return rc;
     if (int rc = resolve_order_ties(c)) return rc;
     if (offsets) {
         if (int rc = copy_sync(c, offsets, c->d_frame_off, sizeof(uint64_t) * (F + 1), hipMemcpyDeviceToHost)) return rc;
-        c->packed_total = offsets[F];
-    } else if (int rc = copy_sync(c, &c->packed_total, c->d_frame_off + F, sizeof(uint64_t), hipMemcpyDeviceToHost)) {
+        c->batch.packed_total = offsets[F];
+    } else if (int rc = copy_sync(c, &c->batch.packed_total, c->d_frame_off + F, sizeof(uint64_t), hipMemcpyDeviceToHost)) {
         return rc;
     }
-    c->total_valid = true;
-    if (total) *total = c->packed_total;
+    c->batch.total_valid = true;
+    if (total) *total = c->batch.packed_total;
     return FLACGPU_OK;
 }
 
 int flacgpu_place_frames(flacgpu_ctx *c, const flacgpu_place_run *runs, uint32_t n_runs) {
-    if (!c || !c->packed_valid || c->out_in_host || (n_runs && !runs)) {
+    if (!c || !c->batch.packed_valid || c->batch.out_in_host || (n_runs && !runs)) {
         g_last_error = "flacgpu_place_frames: nothing packed in device memory, or no run table";
         return FLACGPU_ERR_INVALID_ARG;
     }
-    if (!c->total_valid)   // (the frames are final only behind the re-decisions: flacgpu_resolve)
+    if (!c->batch.total_valid)   // (the frames are final only behind the re-decisions: flacgpu_resolve)
         if (int rc = flacgpu_frame_offsets(c, nullptr, nullptr)) return rc;
     for (uint32_t i = 0; i < n_runs; i++) {
         uint64_t end = 0, dend = 0;
-        if (__builtin_add_overflow(runs[i].src, runs[i].n, &end) || end > c->packed_total ||
+        if (__builtin_add_overflow(runs[i].src, runs[i].n, &end) || end > c->batch.packed_total ||
             __builtin_add_overflow(runs[i].dst, runs[i].n, &dend) || (runs[i].n && !runs[i].dst)) {
             g_last_error = "flacgpu_place_frames: run " + std::to_string(i) + " reaches past the packed frames, or has no destination";
             return FLACGPU_ERR_INVALID_ARG;
@@ -1649,6 +1652,7 @@ int flacgpu_encode_frames(flacgpu_ctx *c, const int32_t *pcm, int layout, uint32
         g_last_error = "invalid encode arguments";
         return FLACGPU_ERR_INVALID_ARG;
     }
+    if (int rc = refuse_batch(c, pcm, layout, n_frames, last_len)) return rc;   // (before the upload: d_in may be the batch in hand's rows)
     CTX_GUARD(c);
     const size_t B = c->opts.block_size, C = c->channels;
     const size_t count = ((size_t)(n_frames - 1) * B + last_len) * C;
@@ -1672,12 +1676,11 @@ int flacgpu_pack_plans(flacgpu_ctx *c, const int32_t *pcm, uint32_t n_frames, ui
     }
     CTX_GUARD(c);
     hipStream_t st = c->own_stream;
-    begin_plain_batch(c);   // (no analyze_impl here)
     const size_t B = c->opts.block_size, C = c->channels;
     const size_t count = ((size_t)(n_frames - 1) * B + last_len) * C;
     HIP_TRY(hipMemcpyAsync(c->d_in, pcm, count * sizeof(int32_t), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(c->d_stats_base, 0, sizeof(uint32_t) * (kTurnWords + 4 + (size_t)n_frames * c->ncand), st));
-    (void)launch_k0(c, c->d_in, FLACGPU_LAYOUT_INTERLEAVED, n_frames, last_len, 0, n_frames, st);
+    (void)launch_k0(c, c->d_in, FLACGPU_LAYOUT_INTERLEAVED, n_frames, last_len, 0, n_frames, nullptr, st);
     HIP_TRY(hipMemcpyAsync(c->d_fplan, plans, sizeof(*plans) * n_frames, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(c->d_out, subs, sizeof(*subs) * n_frames * C, hipMemcpyHostToDevice, st));
     Params p;
@@ -1689,11 +1692,9 @@ int flacgpu_pack_plans(flacgpu_ctx *c, const int32_t *pcm, uint32_t n_frames, ui
     rb.n_frames = n_frames;
     rb.last_len = last_len;
     rb.aligned16 = aligned16(c->d_in);
-    batch_submitted(c, p, flacenc_route::plan_route(rc, rb), st, nullptr, false, false);
+    commit_batch(c, new_batch(Batch::PLAIN, p, flacenc_route::plan_route(rc, rb), st));   // (no analysis: no ties to look at)
     HIP_TRY(hipStreamSynchronize(st));   // the host arrays may go away
-    c->host_out = nullptr;
-    c->out_in_host = false;
-    return pack_impl(c, first_frame_number, sample_rate, st, nullptr);
+    return pack_impl(c, first_frame_number, sample_rate, st, Submission());
 }
 
 // ---- asynchronous host path ------------------------------------------------------------------
@@ -1844,8 +1845,8 @@ static bool packed_async_args_ok(const flacgpu_ctx *c, const uint8_t *pcm_le, ui
             (bytes_per_sample == (c->bps + 7) / 8 && packed_k0_supported(c->opts.block_size, c->channels, bytes_per_sample)));
 }
 
-static int packed_async_impl(flacgpu_ctx *c, const uint8_t *pcm_le, uint32_t bytes_per_sample, uint32_t n_frames, uint32_t last_len,
-                             uint64_t first_frame_number, uint32_t sample_rate, uint8_t *out_host, size_t out_cap);
+static int packed_async_impl(flacgpu_ctx *c, Batch::Kind kind, const uint8_t *pcm_le, uint32_t bytes_per_sample, uint32_t n_frames,
+                             uint32_t last_len, uint64_t first_frame_number, uint32_t sample_rate, uint8_t *out_host, size_t out_cap);
 
 int flacgpu_encode_packed_async_host(flacgpu_ctx *c, const uint8_t *pcm_le, uint32_t bytes_per_sample,
                                      uint32_t n_frames, uint32_t last_len, uint64_t first_frame_number,
@@ -1854,8 +1855,10 @@ int flacgpu_encode_packed_async_host(flacgpu_ctx *c, const uint8_t *pcm_le, uint
         g_last_error = "flacgpu_encode_packed_async: invalid arguments / unsupported sample width for this stream shape";
         return FLACGPU_ERR_INVALID_ARG;
     }
+    if (int rc = refuse_batch(c, pcm_le, FLACGPU_LAYOUT_INTERLEAVED, n_frames, last_len)) return rc;   // (the partition order)
     CTX_GUARD(c);
-    return packed_async_impl(c, pcm_le, bytes_per_sample, n_frames, last_len, first_frame_number, sample_rate, out_host, out_cap);
+    return packed_async_impl(c, Batch::PLAIN, pcm_le, bytes_per_sample, n_frames, last_len, first_frame_number, sample_rate, out_host,
+                             out_cap);
 }
 
 // The same with the batch made of SEGMENTS (frames of several streams, each numbered by its own stream): the segments' whole
@@ -1878,6 +1881,7 @@ int flacgpu_encode_segments_packed_async_host(flacgpu_ctx *c, const uint8_t *pcm
                        "unsupported sample width for this stream shape";
         return FLACGPU_ERR_INVALID_ARG;
     }
+    if (int rc = refuse_batch(c, pcm_le, FLACGPU_LAYOUT_INTERLEAVED, total, c->opts.block_size)) return rc;   // (the partition order)
     CTX_GUARD(c);
     if (int rc = ensure_segment_tables(c)) return rc;
     if (!c->drained) {   // (the table's staging copy of the batch before must be free; one batch per context at a time)
@@ -1889,18 +1893,13 @@ int flacgpu_encode_segments_packed_async_host(flacgpu_ctx *c, const uint8_t *pcm
     for (uint32_t i = 0; i < n_segs; i++)
         for (uint32_t k = 0; k < segs[i].n_frames; k++) fn[f++] = segs[i].first_frame_number + k;
     HIP_TRY(hipMemcpyAsync(c->d_seg_fn, fn, sizeof(uint64_t) * total, hipMemcpyHostToDevice, c->own_stream));
-    c->segs.clear();          // (nothing is read in place: the batch is one contiguous run of blocks in the context's input buffer)
-    c->seg_pending = true;
-    c->seg_direct = false;
-    c->rng_f0 = c->rng_cnt = 0;
-    const int rc = packed_async_impl(c, pcm_le, bytes_per_sample, (uint32_t)total, c->opts.block_size, segs[0].first_frame_number,
-                                     sample_rate, out_host, out_cap);
-    if (rc) c->seg_pending = false;   // (refused before the analysis took the announcement)
-    return rc;
+    // (nothing is read in place: the batch is one contiguous run of blocks in the context's input buffer)
+    return packed_async_impl(c, Batch::SEGMENTS, pcm_le, bytes_per_sample, (uint32_t)total, c->opts.block_size,
+                             segs[0].first_frame_number, sample_rate, out_host, out_cap);
 }
 
-static int packed_async_impl(flacgpu_ctx *c, const uint8_t *pcm_le, uint32_t bytes_per_sample, uint32_t n_frames, uint32_t last_len,
-                             uint64_t first_frame_number, uint32_t sample_rate, uint8_t *out_host, size_t out_cap) {
+static int packed_async_impl(flacgpu_ctx *c, Batch::Kind kind, const uint8_t *pcm_le, uint32_t bytes_per_sample, uint32_t n_frames,
+                             uint32_t last_len, uint64_t first_frame_number, uint32_t sample_rate, uint8_t *out_host, size_t out_cap) {
     hipStream_t st = c->own_stream;
     // FLACGPU_TRACE_SUBMIT=1: where a submission spends its host time (stderr)
     static const bool trace = [] {
@@ -1917,28 +1916,31 @@ static int packed_async_impl(flacgpu_ctx *c, const uint8_t *pcm_le, uint32_t byt
     // caller's pinned buffer -- was measured, profiles/r04_pipeline_ab.json, and removed; flacgpu_link_probe still times both ways.)
     HIP_TRY(hipMemcpyAsync(c->d_in, pcm_le, bytes, hipMemcpyHostToDevice, st));
     if (trace) tr_up = since();
-    const int arc = analyze_impl(c, c->d_in, FLACGPU_LAYOUT_INTERLEAVED, n_frames, last_len, st,
-                                 bytes_per_sample == 4 ? 0 : bytes_per_sample);
-    if (arc) return arc;
-    if (trace) tr_an = since();
+    Submission s;
+    s.kind = kind;
+    s.packed_bytes = bytes_per_sample == 4 ? 0 : bytes_per_sample;
+    s.route = route_of(c, aligned16(c->d_in), FLACGPU_LAYOUT_INTERLEAVED, n_frames, last_len, s.packed_bytes);
+    s.host_out = (reinterpret_cast<uintptr_t>(out_host) & 3u) ? nullptr : out_host;
+    s.host_out_cap = out_cap;
     // the frame sizes leave the device as soon as k_layout has run (second stream), so that the host
     // can size the copy of the bytes while k_frame64 is still assembling them
-    c->host_out = (reinterpret_cast<uintptr_t>(out_host) & 3u) ? nullptr : out_host;
-    c->host_out_cap = out_cap;
-    if (int rc = pack_impl(c, first_frame_number, sample_rate, st, c->ev_layout)) return rc;
+    s.after_layout = c->ev_layout;
+    if (int rc = analyze_impl(c, c->d_in, FLACGPU_LAYOUT_INTERLEAVED, n_frames, last_len, st, s)) return rc;
+    if (trace) tr_an = since();
+    if (int rc = pack_impl(c, first_frame_number, sample_rate, st, s)) return rc;
     if (trace) tr_pk = since();
     // frames written straight to the host buffer: they are there when the stream has drained
-    if (c->out_in_host)
+    if (c->batch.out_in_host)
         if (int rc = record_waitable(c, c->ev_bytes, st)) return rc;
     c->early_bytes = 0;
     c->early_dst = nullptr;
-    if (!c->out_in_host && c->knobs.early_download && c->host_out && c->prev_total) {
-        const uint64_t guess = std::min<uint64_t>(std::min<uint64_t>(c->packed_cap, c->host_out_cap),
+    if (!c->batch.out_in_host && c->knobs.early_download && c->batch.host_out && c->prev_total) {
+        const uint64_t guess = std::min<uint64_t>(std::min<uint64_t>(c->packed_cap, c->batch.host_out_cap),
                                                   c->prev_total + c->prev_total / 8 + 4096);
-        HIP_TRY(hipMemcpyAsync(c->host_out, c->d_packed, guess, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(c->batch.host_out, c->d_packed, guess, hipMemcpyDeviceToHost, st));
         if (int rc = record_waitable(c, c->ev_bytes, st)) return rc;
         c->early_bytes = guess;
-        c->early_dst = c->host_out;
+        c->early_dst = c->batch.host_out;
         g_early_downloads.fetch_add(1, std::memory_order_relaxed);
     }
     HIP_TRY(hipStreamWaitEvent(c->aux_stream, c->ev_layout, 0));
@@ -1961,20 +1963,20 @@ int flacgpu_frames_ready(flacgpu_ctx *c, const uint64_t **offsets, uint64_t *tot
     }
     CTX_GUARD(c);
     if (int rc = wait_waitable(c, c->ev_sizes)) return rc;
-    if (!c->ties_checked) {
+    if (!c->batch.ties_checked) {
         if (c->h_stats[1] == 0 && c->h_stats[3] == 0) {
-            c->ties_checked = true;   // the common case: nothing to re-decide, nothing to wait for
+            c->batch.ties_checked = true;   // the common case: nothing to re-decide, nothing to wait for
         } else {                      // order ties: host re-decision, then the sizes again
             if (int rc = resolve_order_ties(c)) return rc;
-            if (c->out_in_host)   // assembled again, into the host buffer again
+            if (c->batch.out_in_host)   // assembled again, into the host buffer again
                 if (int rc = record_waitable(c, c->ev_bytes, ctx_stream(c))) return rc;
-            if (int rc = copy_sync(c, c->h_off, c->d_frame_off, sizeof(uint64_t) * ((size_t)c->last_frames + 1),
+            if (int rc = copy_sync(c, c->h_off, c->d_frame_off, sizeof(uint64_t) * ((size_t)c->batch.n_frames + 1),
                                    hipMemcpyDeviceToHost))
                 return rc;
         }
     }
     if (offsets) *offsets = c->h_off;
-    if (total) *total = c->h_off[c->last_frames];
+    if (total) *total = c->h_off[c->batch.n_frames];
     return FLACGPU_OK;
 }
 
@@ -1985,21 +1987,21 @@ int flacgpu_fetch_frames_async(flacgpu_ctx *c, uint8_t *out, size_t cap) {
     }
     CTX_GUARD(c);
     if (int rc = wait_waitable(c, c->ev_sizes)) return rc;
-    const uint64_t bytes = c->h_off[c->last_frames];
+    const uint64_t bytes = c->h_off[c->batch.n_frames];
     if (cap < bytes) {
         g_last_error = "output buffer too small";
         return FLACGPU_ERR_BUFFER_TOO_SMALL;
     }
-    if (c->out_in_host) {   // k_frame64 wrote them there; the event was recorded behind it
-        if (out != c->host_out) {
+    if (c->batch.out_in_host) {   // k_frame64 wrote them there; the event was recorded behind it
+        if (out != c->batch.host_out) {
             if (int rc = wait_waitable(c, c->ev_bytes)) return rc;
-            memcpy(out, c->host_out, bytes);
+            memcpy(out, c->batch.host_out, bytes);
         }
         c->bytes_pending = true;
         return FLACGPU_OK;
     }
     c->prev_total = bytes;
-    if (c->early_bytes && out == c->early_dst && c->ties_resolved == 0 && c->fir_rechecked == 0) {
+    if (c->early_bytes && out == c->early_dst && c->batch.ties_resolved == 0 && c->batch.fir_rechecked == 0) {
         // the early copy (queued behind the kernels at submission) holds the first early_bytes; the rest now
         if (bytes > c->early_bytes) {
             g_early_remainders.fetch_add(1, std::memory_order_relaxed);
@@ -2025,7 +2027,7 @@ int flacgpu_wait(flacgpu_ctx *c) {
         c->sizes_pending = false;
         // the frames were stored by the batch's last kernel (out_in_host) or copied by the last command of the context's own
         // stream, and the sizes' copy on the second stream was waited for by flacgpu_frames_ready: nothing is in flight
-        c->drained = c->last_stream == c->own_stream || c->last_stream == nullptr;
+        c->drained = c->batch.stream == c->own_stream || c->batch.stream == nullptr;
         return FLACGPU_OK;
     }
     if (int rc = ctx_sync(c)) return rc;
@@ -2034,14 +2036,14 @@ int flacgpu_wait(flacgpu_ctx *c) {
 
 int flacgpu_experiment_mfma_autocorr(flacgpu_ctx *c, float *kernel_ms, uint32_t *compared,
                                      uint32_t *params_differ, double *max_rel_err) {
-    if (!c || c->last_frames == 0 || c->opts.max_lpc_order == 0 || c->opts.max_lpc_order > 16 ||
-        c->last_len != c->opts.block_size || c->rag_active) {
+    if (!c || c->batch.n_frames == 0 || c->opts.max_lpc_order == 0 || c->opts.max_lpc_order > 16 ||
+        c->batch.last_len != c->opts.block_size || c->batch.kind == Batch::RAGGED) {
         g_last_error = "mfma experiment: needs an analysed batch of full blocks with 1 <= max_lpc_order <= 16";
         return FLACGPU_ERR_INVALID_ARG;
     }
     CTX_GUARD(c);
     hipStream_t st = c->own_stream;
-    Params p = c->last_params;
+    Params p = c->batch.params;
     const size_t nc = (size_t)p.n_frames * p.ncand;
     std::vector<LpcParams> exact(nc), mfma(nc);
     std::vector<double> ac_exact(nc * AC_LD), ac_mfma(nc * AC_LD);
@@ -2087,30 +2089,24 @@ int flacgpu_experiment_mfma_autocorr(flacgpu_ctx *c, float *kernel_ms, uint32_t 
 
 int flacgpu_verify_device(flacgpu_ctx *c, uint32_t sample_rate, uint64_t first_frame_number,
                           flacgpu_verify_result *result, float *kernel_ms) {
-    if (!c || !c->packed_valid || !result) {
+    if (!c || !c->batch.packed_valid || !result) {
         g_last_error = "flacgpu_verify_device: nothing packed";
         return FLACGPU_ERR_INVALID_ARG;
     }
-    if (c->out_in_host) {
+    if (c->batch.out_in_host) {
         g_last_error = "flacgpu_verify_device: the batch was assembled into the caller's host buffer";
         return FLACGPU_ERR_UNSUPPORTED;
     }
     CTX_GUARD(c);
     if (int rc = resolve_order_ties(c)) return rc;
     hipStream_t st = c->own_stream;
-    Params p = c->last_params;
+    Params p = c->batch.params;
     const size_t F = c->max_frames, C = c->channels;
     if (!c->d_decoded) {
         HIP_TRY(hipMalloc((void **)&c->d_decoded, sizeof(int32_t) * (F * C * c->ldb + 64)));
         HIP_TRY(hipMalloc((void **)&c->d_verify, sizeof(uint32_t) * (4 + F)));  // counters + per-frame codes
     }
-    PackParams q;
-    q.first_frame_number = first_frame_number;
-    if (c->seg_active) q.frame_numbers = c->d_seg_fn;
-    q.sample_rate = sample_rate;
-    q.out_words = c->d_packed;
-    q.frame_off = c->d_frame_off;
-    q.cap_bytes = c->packed_cap;
+    const PackParams q = pack_params_of(c, c->batch, first_frame_number, sample_rate);
     if (int rc = ensure_planar(c)) return rc;
     if (int rc = ctx_sync(c)) return rc;
     HIP_TRY(hipMemsetAsync(c->d_verify, 0, sizeof(uint32_t) * (4 + (size_t)p.n_frames), st));
@@ -2152,15 +2148,15 @@ int flacgpu_verify_device(flacgpu_ctx *c, uint32_t sample_rate, uint64_t first_f
 }
 
 int flacgpu_fetch_decoded(flacgpu_ctx *c, int32_t *interleaved) {
-    if (!c || !c->d_decoded || !interleaved || c->last_frames == 0) return FLACGPU_ERR_INVALID_ARG;
+    if (!c || !c->d_decoded || !interleaved || c->batch.n_frames == 0) return FLACGPU_ERR_INVALID_ARG;
     CTX_GUARD(c);
-    const size_t F = c->last_frames, C = c->channels, B = c->opts.block_size, ldb = c->ldb;
+    const size_t F = c->batch.n_frames, C = c->channels, ldb = c->ldb;
     std::vector<int32_t> planar(F * C * ldb);
     if (int rc = ctx_sync(c)) return rc;
     if (int rc = copy_sync(c, planar.data(), c->d_decoded, sizeof(int32_t) * planar.size(), hipMemcpyDeviceToHost)) return rc;
     size_t o = 0;
     for (size_t f = 0; f < F; f++) {
-        const size_t n = (c->rag_active && f < c->rag_n.size()) ? c->rag_n[f] : (f + 1 == F) ? c->last_len : B;
+        const size_t n = frame_len_of(c->batch, f);
         for (size_t i = 0; i < n; i++)
             for (size_t ch = 0; ch < C; ch++) interleaved[o++] = planar[(f * C + ch) * ldb + i];
     }
@@ -2180,13 +2176,13 @@ int flacgpu_get_stats(flacgpu_ctx *c, flacgpu_stats *out) {
     uint32_t s[4];
     if (int rc = ctx_sync(c)) return rc;
     if (int rc = copy_sync(c, s, c->d_stats, sizeof s, hipMemcpyDeviceToHost)) return rc;
-    out->frames = c->last_frames;
+    out->frames = c->batch.n_frames;
     out->lpc_failed = s[0];
     out->order_ties = s[1];
     out->log2_edge = s[2];
-    out->order_ties_resolved = c->ties_resolved;
+    out->order_ties_resolved = c->batch.ties_resolved;
     out->fir_recheck = s[3];
-    out->fir_rechecked = c->fir_rechecked;
+    out->fir_rechecked = c->batch.fir_rechecked;
     uint32_t d[kDeferWords];
     if (int rc = copy_sync(c, d, defer_stats_of(c), sizeof d, hipMemcpyDeviceToHost)) return rc;
     uint64_t decided = 0, refetched = 0;   // (64 counter lines of 32 bits each: summed wide, handed out saturated)
@@ -2284,9 +2280,9 @@ int flacgpu_handed_subframes(flacgpu_ctx *c, uint32_t *handed, uint32_t *subfram
     if (!c) return FLACGPU_ERR_INVALID_ARG;
     CTX_GUARD(c);
     if (int rc = ctx_sync(c)) return rc;
-    const bool on = c->last_frames && c->last_params.hand_meta;
+    const bool on = c->batch.n_frames && c->batch.params.hand_meta;
     uint32_t n = 0;
-    const uint32_t total = on ? c->last_frames * 2u : 0u;
+    const uint32_t total = on ? c->batch.n_frames * 2u : 0u;
     if (on) {
         std::vector<uint32_t> flags(total);
         if (int rc = copy_sync(c, flags.data(), c->d_hand, sizeof(uint32_t) * total, hipMemcpyDeviceToHost)) return rc;
