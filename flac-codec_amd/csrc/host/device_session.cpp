@@ -72,8 +72,6 @@ int plan_shape(const flacenc_options *o, uint32_t bps, uint32_t channels, size_t
     return 0;
 }
 
-constexpr uint64_t kMaxSamples = 68719476736ull;   // Encoder::MAX_SAMPLES, encode.rs:1880
-
 struct Stream {
     uint64_t total = 0, fed = 0;    // samples per channel: declared, received
     bool known = true;              // the total was declared at open (false: `total` is unused)
@@ -310,10 +308,7 @@ int flacenc_device_session_finalize(flacenc_device_session *s, flacenc_session_f
         f.header_len = f.tail_len = 0;
         f.altered = (uint32_t)std::min<uint64_t>(m.altered, 0xFFFFFFFFull);
         std::memset(f.md5, 0, 16);
-        if (!m.status && m.known && m.fed != m.total) m.status = FLACENC_ERR_SAMPLE_COUNT_MISMATCH;
-        // Encoder::finalize_inner without a total (encode.rs:2088-2097)
-        if (!m.status && !m.known && m.fed >= kMaxSamples) m.status = FLACENC_ERR_EXCESSIVE_TOTAL_SAMPLES;
-        if (!m.status && !m.known && !m.fed) m.status = FLACENC_ERR_NO_SAMPLES;
+        if (!m.status) m.status = totals_verdict(m.known, m.total, m.fed);   // Encoder::finalize_inner (encode.rs:2079-2097)
         f.status = m.status;
         if (!m.status && m.carry) tails.push_back(i);
     }

@@ -26,8 +26,6 @@ using namespace flacenc_host;
 
 namespace {
 
-constexpr uint64_t kMaxFrameNumber = (1ull << 36) - 1;   // FrameNumber::MAX_FRAME_NUMBER
-
 int refuse(int rc, const std::string &why) {
     set_last_error("flacenc_device_stream_writer: " + why);
     return rc;

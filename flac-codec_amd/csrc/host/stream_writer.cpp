@@ -1,8 +1,9 @@
 // stream_writer.cpp -- host driver: the reference's Encoder<W> + FlacSampleWriter /
 // FlacByteWriter / FlacChannelWriter / FlacStreamWriter (encode.rs:48-1290, 1853-2160),
 // batching PCM blocks into the gfx950 analysis (include/flacenc_gpu.h) and doing what the
-// reference keeps sequential: MD5, frame headers, Rice bit-packing, CRC, seek points,
-// metadata.  C ABI: include/flacenc_stream.h.
+// reference keeps sequential: MD5, frame headers, Rice bit-packing, CRC.  A writer is TRANSPORT (sink, analysis lanes,
+// MD5, backlogs, statistics) around a StreamLedger (stream_ledger.h), which holds the container state: seek points, counts,
+// STREAMINFO, the metadata bytes.  C ABI: include/flacenc_stream.h.
 #if defined(__x86_64__) && defined(__GNUC__)
 #include <immintrin.h>
 #endif
@@ -32,22 +33,39 @@
 #include "frame_pack.h"
 
 namespace {
+thread_local std::string g_err;   // flacenc_last_error()
+}
 
-using flacenc::Md5;
-using flacenc::Md5Lane;
-using flacenc::Md5Pool;
-
-thread_local std::string g_err;
+// ---- what the host driver's other units share with this file (host_internal.h); more of it where its subject is defined ----
+namespace flacenc_host {
+void set_last_error(const std::string &text) { g_err = text; }
 
 double now_ms() {
     using namespace std::chrono;
     return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
 }
 
-constexpr uint64_t kMaxSamples = 68719476736ull;         // Encoder::MAX_SAMPLES, encode.rs:1880
-constexpr uint32_t kMaxFrameSize = (1u << 24) - 1;       // Streaminfo::MAX_FRAME_SIZE
-constexpr size_t kMaxSeekPoints = (1u << 24) / 18;       // SeekTable::MAX_POINTS
-constexpr uint64_t kMaxFrameNumber = (1ull << 36) - 1;   // FrameNumber::MAX_FRAME_NUMBER
+flacgpu_options gpu_options(const flacenc_options &o, uint32_t block_size) {
+    flacgpu_options g{};
+    g.block_size = block_size;
+    g.max_partition_order = o.max_partition_order;
+    g.max_lpc_order = o.max_lpc_order;
+    g.mid_side = o.mid_side;
+    g.exhaustive_channel_correlation = o.exhaustive_channel_correlation;
+    g.window_kind = o.window_kind;
+    g.window_param = o.window_param;
+    return g;
+}
+}  // namespace flacenc_host
+
+using namespace flacenc_host;
+
+namespace {
+
+using flacenc::Md5;
+using flacenc::Md5Lane;
+using flacenc::Md5Pool;
+
 constexpr size_t kDirectFrames = 64;   // blocks in one write call from which they are encoded without staging
 
 // ---- output sink (W: Write + Seek) --------------------------------------------------
@@ -85,126 +103,6 @@ struct Sink {
     }
     uint64_t start() const { return (memory || fixed) ? 0 : cb.start; }
 };
-
-struct SeekPoint {
-    uint64_t sample_offset, byte_offset;
-    uint16_t frame_samples;
-    bool defined;
-};
-
-// SeekTableInterval::filter, encode.rs:1338-1358
-std::vector<SeekPoint> filter_points(const flacenc_options &o, uint32_t sample_rate,
-                                     const std::vector<SeekPoint> &in) {
-    std::vector<SeekPoint> out;
-    if (o.seektable_mode == FLACENC_SEEKTABLE_SECONDS) {
-        const uint64_t nth = static_cast<uint32_t>((o.seektable_value & 0xFFu) * sample_rate);
-        uint64_t offset = 0;
-        for (const auto &p : in)
-            if (offset >= p.sample_offset && offset < p.sample_offset + p.frame_samples) {
-                offset += nth;
-                out.push_back(p);
-            }
-    } else if (o.seektable_mode == FLACENC_SEEKTABLE_FRAMES) {
-        const size_t step = o.seektable_value ? o.seektable_value : 1;
-        for (size_t i = 0; i < in.size(); i += step) out.push_back(in[i]);
-    }
-    return out;
-}
-
-// ---- metadata serialisation (metadata/mod.rs:257-266, 904-960, 1740-1760, 1826-1831,
-//      2010-2036, 2118-2139) ----------------------------------------------------------
-struct StreamInfo {
-    uint32_t min_block = 0, max_block = 0, min_frame = 0, max_frame = 0;
-    uint32_t sample_rate = 0, channels = 0, bps = 0;
-    uint64_t total_samples = 0;  // 0 = None
-    uint8_t md5[16] = {0};
-};
-
-void put_be(std::vector<uint8_t> &v, uint64_t x, int bytes) {
-    for (int i = bytes - 1; i >= 0; i--) v.push_back(static_cast<uint8_t>(x >> (8 * i)));
-}
-void put_block_header(std::vector<uint8_t> &v, bool last, uint8_t type, uint32_t size) {
-    v.push_back(static_cast<uint8_t>((last ? 0x80 : 0) | type));
-    put_be(v, size, 3);
-}
-
-struct MetaLayout {
-    bool vorbis = false;              // a VORBIS_COMMENT block is present (sorts first)
-    std::vector<uint8_t> vorbis_body;
-    bool seektable = false;           // a SEEKTABLE block is present
-    bool seektable_after_padding = false;  // inserted at finalize => pushed last
-    std::vector<SeekPoint> points;
-    bool padding = false;
-    uint32_t padding_size = 0;
-};
-
-std::vector<uint8_t> build_metadata(const StreamInfo &si, const MetaLayout &m) {
-    std::vector<uint8_t> v;
-    v.insert(v.end(), {'f', 'L', 'a', 'C'});
-    int remaining = (m.seektable ? 1 : 0) + (m.padding ? 1 : 0) + (m.vorbis ? 1 : 0);
-    put_block_header(v, remaining == 0, 0, 34);
-    put_be(v, si.min_block, 2);
-    put_be(v, si.max_block, 2);
-    put_be(v, si.min_frame, 3);
-    put_be(v, si.max_frame, 3);
-    // 20 bits rate | 3 bits channels-1 | 5 bits bps-1 | 36 bits total samples
-    uint64_t packed = (static_cast<uint64_t>(si.sample_rate) << 44) |
-                      (static_cast<uint64_t>(si.channels - 1) << 41) |
-                      (static_cast<uint64_t>(si.bps - 1) << 36) | (si.total_samples & 0xFFFFFFFFFull);
-    put_be(v, packed, 8);
-    v.insert(v.end(), si.md5, si.md5 + 16);
-    auto emit_seektable = [&]() {
-        remaining--;
-        put_block_header(v, remaining == 0, 3, static_cast<uint32_t>(m.points.size() * 18));
-        for (const auto &p : m.points) {
-            if (p.defined) {
-                put_be(v, p.sample_offset, 8);
-                put_be(v, p.byte_offset, 8);
-                put_be(v, p.frame_samples, 2);
-            } else {  // SeekPoint::Placeholder
-                put_be(v, ~0ull, 8);
-                put_be(v, 0, 8);
-                put_be(v, 0, 2);
-            }
-        }
-    };
-    auto emit_padding = [&]() {
-        remaining--;
-        put_block_header(v, remaining == 0, 1, m.padding_size);
-        v.insert(v.end(), m.padding_size, 0);
-    };
-    if (m.vorbis) {  // VorbisComment::to_writer, metadata/mod.rs:2512-2536
-        remaining--;
-        put_block_header(v, remaining == 0, 4, static_cast<uint32_t>(m.vorbis_body.size()));
-        v.insert(v.end(), m.vorbis_body.begin(), m.vorbis_body.end());
-    }
-    // block order after Encoder::new's sort (encode.rs:1944-1951): VORBIS_COMMENT < SEEKTABLE < PADDING;
-    // a SEEKTABLE created at finalize is pushed behind PADDING (metadata/mod.rs:4425-4441)
-    if (m.seektable && !m.seektable_after_padding) emit_seektable();
-    if (m.padding) emit_padding();
-    if (m.seektable && m.seektable_after_padding) emit_seektable();
-    return v;
-}
-
-int options_error(const flacenc_options &o) {
-    if (o.block_size < 16 || o.block_size > 65535) return FLACENC_ERR_INVALID_BLOCK_SIZE;
-    if (o.max_lpc_order > 32) return FLACENC_ERR_INVALID_LPC_ORDER;
-    if (o.max_partition_order > 15) return FLACENC_ERR_INVALID_MAX_PARTITIONS;
-    if (o.padding < 0 || o.padding >= (1 << 24)) return FLACENC_ERR_EXCESSIVE_PADDING;
-    return 0;
-}
-
-flacgpu_options gpu_options(const flacenc_options &o, uint32_t block_size) {
-    flacgpu_options g{};
-    g.block_size = block_size;
-    g.max_partition_order = o.max_partition_order;
-    g.max_lpc_order = o.max_lpc_order;
-    g.mid_side = o.mid_side;
-    g.exhaustive_channel_correlation = o.exhaustive_channel_correlation;
-    g.window_kind = o.window_kind;
-    g.window_param = o.window_param;
-    return g;
-}
 
 int map_gpu_error(int rc) {
     g_err = std::string("gpu: ") + flacgpu_last_error();
@@ -458,7 +356,7 @@ size_t pack_le2_avx2(const int32_t *, size_t, uint8_t *) { return 0; }
 bool have_avx2() { return false; }
 #endif
 
-void pack_le(const int32_t *s, size_t count, unsigned width, uint8_t *d) {
+void flacenc_host::pack_le(const int32_t *s, size_t count, unsigned width, uint8_t *d) {
     switch (width) {
     case 1:
         for (size_t i = 0; i < count; i++) d[i] = static_cast<uint8_t>(s[i]);
@@ -490,12 +388,8 @@ struct flacenc_writer {
     enum Kind { SAMPLE, BYTE, CHANNEL } kind = SAMPLE;
     flacenc_options o{};
     Sink sink;
-    StreamInfo si;
-    MetaLayout meta;
-    size_t metadata_len = 0;
-    uint64_t frame_number = 0, samples_written = 0, byte_count = 0;  // Counter::count
-    uint64_t samples_submitted = 0;   // samples_written + the batches still in flight
-    std::vector<SeekPoint> seekpoints;
+    StreamLedger led;                 // the stream's container state: everything but the frames' bytes
+    uint64_t samples_submitted = 0;   // led.samples_written + the batches still in flight
     Md5 md5;
     bool finalized = false;
     flacgpu_ctx *gpu = nullptr;   // = lanes[0]->gpu (the synchronous paths use this one)
@@ -528,7 +422,6 @@ struct flacenc_writer {
     std::vector<uint8_t> outbuf;  // frames fetched from the device
     flacenc_stats stats{};
 
-    bool header_only = false;
     CtxKey gpu_key{};
     ~flacenc_writer() {
         for (auto &f : inflight) (void)flacgpu_wait(f.lane->gpu);   // nothing may still write into a pooled lane
@@ -563,61 +456,17 @@ struct flacenc_writer {
     // Encoder::new, encode.rs:1882-1980
     int init(const flacenc_options &opts, uint32_t rate, uint32_t bps, uint32_t channels,
              bool has_total, uint64_t total_pcm_frames, const flacenc_sink *s) {
-        o = opts;
-        if (int e = options_error(o)) return e;
-        if (rate >= 1048576u) return FLACENC_ERR_INVALID_SAMPLE_RATE;
-        if (channels < 1 || channels > 8) return FLACENC_ERR_EXCESSIVE_CHANNELS;
-        if (has_total && total_pcm_frames >= kMaxSamples) return FLACENC_ERR_EXCESSIVE_TOTAL_SAMPLES;
+        std::vector<uint8_t> hdr;
+        if (int e = led.open(opts, rate, bps, channels, has_total, total_pcm_frames, hdr)) return e;
+        o = led.o;   // (the writer keeps no pointers into caller memory)
         if (s) {
             sink.memory = false;
             sink.cb = *s;
         }
-        si.min_block = si.max_block = o.block_size;
-        si.sample_rate = rate;
-        si.channels = channels;
-        si.bps = bps;
-        si.total_samples = has_total ? total_pcm_frames : 0;
         bytes_per_sample = (bps + 7) / 8;
-        meta.padding = o.padding > 0;
-        meta.padding_size = static_cast<uint32_t>(o.padding);
-        if (o.n_comment_fields || o.vendor_string) {
-            auto put_le32 = [&](uint32_t x) {
-                for (int i = 0; i < 4; i++) meta.vorbis_body.push_back(static_cast<uint8_t>(x >> (8 * i)));
-            };
-            const std::string vendor = o.vendor_string ? o.vendor_string : "flac-codec 1.3.2";
-            put_le32(static_cast<uint32_t>(vendor.size()));
-            meta.vorbis_body.insert(meta.vorbis_body.end(), vendor.begin(), vendor.end());
-            put_le32(o.n_comment_fields);
-            for (uint32_t i = 0; i < o.n_comment_fields; i++) {
-                const std::string f = o.comment_fields[i];
-                put_le32(static_cast<uint32_t>(f.size()));
-                meta.vorbis_body.insert(meta.vorbis_body.end(), f.begin(), f.end());
-            }
-            meta.vorbis = true;
-        }
-        // the writer keeps no pointers into caller memory
-        o.vendor_string = nullptr;
-        o.comment_fields = nullptr;
-        if (has_total && o.seektable_mode != FLACENC_SEEKTABLE_NONE) {
-            // placeholder SEEKTABLE, encode.rs:1920-1939 + EncoderSeekPoint::placeholders :2131
-            std::vector<SeekPoint> all;
-            for (uint64_t off = 0; off < total_pcm_frames; off += o.block_size) {
-                uint64_t rem = total_pcm_frames - off;
-                uint16_t fs = static_cast<uint16_t>(rem > 65535 ? o.block_size
-                                                                 : std::min<uint64_t>(rem, o.block_size));
-                all.push_back({off, 0, fs, false});
-            }
-            meta.points = filter_points(o, rate, all);
-            if (meta.points.size() > kMaxSeekPoints) meta.points.resize(kMaxSeekPoints);
-            for (auto &p : meta.points) p.defined = false;
-            meta.seektable = true;
-        }
-        std::vector<uint8_t> hdr = build_metadata(si, meta);
-        metadata_len = hdr.size();
-        if (sink.memory && !sink.fixed && has_total && !header_only)   // one allocation instead of doublings
+        if (sink.memory && !sink.fixed && has_total)   // one allocation instead of doublings
             sink.mem.reserve(hdr.size() + static_cast<size_t>(total_pcm_frames) * channels * bytes_per_sample * 3 / 4);
         if (int e = sink.write(hdr.data(), hdr.size())) return e;
-        if (header_only) return 0;   // flacenc_stream_header: bookkeeping without an analysis lane
         batch_frames = o.batch_frames ? o.batch_frames : 256;
         unsigned hw = std::thread::hardware_concurrency();
         pack_threads = o.pack_threads ? o.pack_threads : std::max(1u, std::min(hw, 16u));
@@ -675,29 +524,17 @@ struct flacenc_writer {
     // Encoder::encode for a run of blocks (encode.rs:1997-2022 + encode_frame's tail
     // :2408-2436), `n_frames` blocks of block_size, the last one `last_len` long.
     int encode_blocks(const int32_t *interleaved, uint32_t n_frames, uint32_t last_len) {
-        const uint32_t B = o.block_size, C = si.channels;
+        const uint32_t B = o.block_size, C = led.si.channels;
         if (o.host_pack) {
             plans.resize(n_frames);
             subs.resize(static_cast<size_t>(n_frames) * C);
             rows.resize(static_cast<size_t>(n_frames) * C * B);
         }
-        // ExcessiveTotalSamples is raised BEFORE the offending frame is encoded (:2006-2011)
-        uint32_t usable = n_frames;
-        int deferred = 0;
-        if (si.total_samples) {
-            uint64_t w = samples_written;
-            for (uint32_t f = 0; f < n_frames; f++) {
-                w += (f + 1 == n_frames) ? last_len : B;
-                if (w > si.total_samples) {
-                    usable = f;
-                    deferred = FLACENC_ERR_EXCESSIVE_TOTAL_SAMPLES;
-                    break;
-                }
-            }
-        }
+        const StreamLedger::Admit adm = led.admit(led.samples_written, n_frames, last_len);
+        if (adm.error) return adm.error;
+        const uint32_t usable = adm.usable;
         if (usable) {
             const uint32_t ll = (usable == n_frames) ? last_len : B;
-            if (frame_number + usable - 1 > kMaxFrameNumber) return FLACENC_ERR_EXCESSIVE_FRAME_NUMBER;
             PackedBatch pb;
             size_t dev_total = 0;
             double t0 = now_ms();
@@ -707,7 +544,7 @@ struct flacenc_writer {
                 stats.gpu_ms += now_ms() - t0;
                 if (rc) return map_gpu_error(rc);
                 t0 = now_ms();
-                if (int e = pack_batch(si.sample_rate, si.bps, C, frame_number, usable, B, plans.data(),
+                if (int e = pack_batch(led.si.sample_rate, led.si.bps, C, led.frame_number, usable, B, plans.data(),
                                        subs.data(), rows.data(), pack_threads, pb))
                     return e;
                 stats.pack_ms += now_ms() - t0;
@@ -717,7 +554,7 @@ struct flacenc_writer {
                 uint64_t total = 0;
                 // first the sizes, then a buffer of exactly that size (grown, reused by every batch)
                 int rc = flacgpu_encode_frames(gpu, interleaved, FLACGPU_LAYOUT_INTERLEAVED, usable, ll,
-                                               frame_number, si.sample_rate, nullptr, 0, off.data(), &total);
+                                               led.frame_number, led.si.sample_rate, nullptr, 0, off.data(), &total);
                 if (rc == FLACGPU_ERR_BUFFER_TOO_SMALL) {
                     if (outbuf.size() < total) outbuf.resize(total);
                     rc = flacgpu_fetch_frames(gpu, outbuf.data(), outbuf.size(), off.data(), &total);
@@ -727,28 +564,14 @@ struct flacenc_writer {
                 pb.offsets.assign(off.begin(), off.end());
                 dev_total = total;
             }
-            for (uint32_t f = 0; f < usable; f++) {
-                const uint32_t n = (f + 1 == usable) ? ll : B;
-                seekpoints.push_back({samples_written, byte_count + pb.offsets[f], static_cast<uint16_t>(n), true});
-                samples_written += n;
-                const uint32_t size = static_cast<uint32_t>(pb.offsets[f + 1] - pb.offsets[f]);
-                if (size != 0 && size < kMaxFrameSize) {  // :2414-2436
-                    si.min_frame = si.min_frame ? std::min(si.min_frame, size) : size;
-                    si.max_frame = std::max(si.max_frame, size);
-                }
-            }
-            frame_number += usable;
+            led.frames(usable, ll, [&](uint64_t k) { return static_cast<uint32_t>(pb.offsets[k + 1] - pb.offsets[k]); });
+            led.frame_number += usable;
             const uint8_t *obytes = o.host_pack ? pb.bytes.data() : outbuf.data();
             const size_t olen = o.host_pack ? pb.bytes.size() : dev_total;
-            byte_count += olen;
             if (int e = sink.write(obytes, olen)) return e;
         }
-        if (deferred) {
-            // the reference pushes the seekpoint and bumps samples_written before failing
-            seekpoints.push_back({samples_written, byte_count, static_cast<uint16_t>(B), true});
-            samples_written += (usable + 1 == n_frames) ? last_len : B;
-        }
-        return deferred;
+        if (adm.deferred) led.overrun(n_frames, usable, last_len);
+        return adm.deferred;
     }
 
     // ---- device-side frame assembly, pipelined: Encoder::encode for a run of blocks (encode.rs:
@@ -758,25 +581,13 @@ struct flacenc_writer {
     // to `depth` batches in flight on their own contexts and streams.
     int submit_blocks(const int32_t *interleaved, uint32_t n_frames, uint32_t last_len) {
         if (failed) return failed;
-        const uint32_t B = o.block_size, C = si.channels;
-        // ExcessiveTotalSamples is raised BEFORE the offending frame is encoded (:2006-2011)
-        uint32_t usable = n_frames;
-        int deferred = 0;
-        if (si.total_samples) {
-            uint64_t w = samples_submitted;
-            for (uint32_t f = 0; f < n_frames; f++) {
-                w += (f + 1 == n_frames) ? last_len : B;
-                if (w > si.total_samples) {
-                    usable = f;
-                    deferred = FLACENC_ERR_EXCESSIVE_TOTAL_SAMPLES;
-                    break;
-                }
-            }
-        }
+        const uint32_t B = o.block_size, C = led.si.channels;
+        const StreamLedger::Admit adm = led.admit(samples_submitted, n_frames, last_len);
+        if (adm.error) return adm.error;
+        const uint32_t usable = adm.usable;
         const size_t all_samples = (static_cast<size_t>(n_frames - 1) * B + last_len) * C;
         if (usable) {
             const uint32_t ll = (usable == n_frames) ? last_len : B;
-            if (frame_number + usable - 1 > kMaxFrameNumber) return FLACENC_ERR_EXCESSIVE_FRAME_NUMBER;
             while (inflight.size() >= depth)
                 if (int rc = retire_oldest()) return rc;
             // lanes are used round-robin and retired in order: lane (n mod depth) is free again
@@ -820,31 +631,28 @@ struct flacenc_writer {
             const size_t worst = flacgpu_packed_cap(lane->gpu);
             if (worst <= (size_t(64) << 20))
                 if (int rc = lane->reserve_out(worst)) return rc;
-            int rc = flacgpu_encode_packed_async_host(lane->gpu, lane->pin_in, upload_width, usable, ll, frame_number,
-                                                      si.sample_rate, lane->pin_out, lane->pin_out_cap);
+            int rc = flacgpu_encode_packed_async_host(lane->gpu, lane->pin_in, upload_width, usable, ll, led.frame_number,
+                                                      led.si.sample_rate, lane->pin_out, lane->pin_out_cap);
             stats.gpu_ms += now_ms() - t1;
             if (rc) return map_gpu_error(rc);
             inflight.push_back({lane, usable, ll, ticket});
-            frame_number += usable;
+            led.frame_number += usable;
             samples_submitted += static_cast<uint64_t>(usable - 1) * B + ll;
         } else {
             md5_worker.wait(md5_worker.pushed);
             md5_samples(interleaved, all_samples);
         }
-        if (deferred) {
+        if (adm.deferred) {
             if (int rc = retire_all()) return rc;
-            // the reference pushes the seekpoint and bumps samples_written before failing
-            seekpoints.push_back({samples_written, byte_count, static_cast<uint16_t>(B), true});
-            samples_written += (usable + 1 == n_frames) ? last_len : B;
-            samples_submitted = samples_written;
+            led.overrun(n_frames, usable, last_len);
+            samples_submitted = led.samples_written;
         }
-        return deferred;
+        return adm.deferred;
     }
 
     int retire_oldest() {
         InFlight f = inflight.front();
         inflight.pop_front();
-        const uint32_t B = o.block_size;
         const double t0 = now_ms();
         const uint64_t *off = nullptr;
         uint64_t total = 0;
@@ -858,17 +666,7 @@ struct flacenc_writer {
             failed = map_gpu_error(rc);
             return failed;
         }
-        for (uint32_t k = 0; k < f.n_frames; k++) {
-            const uint32_t n = (k + 1 == f.n_frames) ? f.last_len : B;
-            seekpoints.push_back({samples_written, byte_count + off[k], static_cast<uint16_t>(n), true});
-            samples_written += n;
-            const uint32_t size = static_cast<uint32_t>(off[k + 1] - off[k]);
-            if (size != 0 && size < kMaxFrameSize) {  // :2414-2436
-                si.min_frame = si.min_frame ? std::min(si.min_frame, size) : size;
-                si.max_frame = std::max(si.max_frame, size);
-            }
-        }
-        byte_count += total;
+        led.frames(f.n_frames, f.last_len, [&](uint64_t k) { return static_cast<uint32_t>(off[k + 1] - off[k]); });
         if (int e = sink.write(f.lane->pin_out, total)) {
             failed = e;
             return e;
@@ -884,7 +682,7 @@ struct flacenc_writer {
     // Cut whole blocks out of `data` (count samples), batch by batch; returns the samples consumed
     // through *consumed_out: whole batches, or every whole block at the final flush.
     int process(const int32_t *data, size_t count, bool final_flush, size_t *consumed_out) {
-        const size_t frame_samples = static_cast<size_t>(o.block_size) * si.channels;
+        const size_t frame_samples = static_cast<size_t>(o.block_size) * led.si.channels;
         size_t consumed = 0;
         int rc = 0;
         size_t whole_all = count / frame_samples;
@@ -929,7 +727,7 @@ struct flacenc_writer {
     // backlog has been topped up to a whole batch and drained, whole batches are encoded straight
     // from the caller's buffer and only the tail (< one batch) is kept
     int write_direct(const int32_t *samples, size_t count) {
-        const size_t frame_samples = static_cast<size_t>(o.block_size) * si.channels;
+        const size_t frame_samples = static_cast<size_t>(o.block_size) * led.si.channels;
         const size_t batch_samples = static_cast<size_t>(batch_frames) * frame_samples;
         // a call that brings many blocks at once is encoded from the caller's buffer right away, in
         // batches of at most batch_frames (the last one smaller); small writes accumulate to a batch
@@ -969,7 +767,7 @@ struct flacenc_writer {
             return FLACENC_ERR_UNSUPPORTED;
         }
         if (!backlog.empty()) {
-            size_t usable = backlog.size() - backlog.size() % si.channels;
+            size_t usable = backlog.size() - backlog.size() % led.si.channels;
             if (usable == 0) {
                 // Frame with zero PCM frames: `chunks_exact(0)` panics in the reference
                 // (audio.rs:177 via encode.rs:2020); surfaced as an error here
@@ -978,9 +776,9 @@ struct flacenc_writer {
             }
             if (o.host_pack) {
                 md5_samples(backlog.data(), usable);
-                rc = encode_blocks(backlog.data(), 1, static_cast<uint32_t>(usable / si.channels));
+                rc = encode_blocks(backlog.data(), 1, static_cast<uint32_t>(usable / led.si.channels));
             } else {
-                rc = submit_blocks(backlog.data(), 1, static_cast<uint32_t>(usable / si.channels));
+                rc = submit_blocks(backlog.data(), 1, static_cast<uint32_t>(usable / led.si.channels));
             }
             backlog.clear();
             if (rc) return rc;
@@ -992,53 +790,23 @@ struct flacenc_writer {
     }
 
     int finalize_encoder() {
-        // SEEKTABLE, encode.rs:2029-2076
-        if (o.seektable_mode != FLACENC_SEEKTABLE_NONE) {
-            std::vector<SeekPoint> enc = filter_points(o, si.sample_rate, seekpoints);
-            if (meta.seektable) {
-                const size_t n = meta.points.size();
-                for (size_t i = 0; i < n; i++) {
-                    if (i < enc.size()) meta.points[i] = enc[i];
-                    else meta.points[i] = SeekPoint{0, 0, 0, false};
-                }
-            } else if (meta.padding) {
-                if (enc.size() > kMaxSeekPoints) {
-                    g_err = "more seek points than a SEEKTABLE holds (the reference panics)";
-                    return FLACENC_ERR_UNSUPPORTED;
-                }
-                const uint64_t st_total = static_cast<uint64_t>(enc.size()) * 18 + 4;
-                if (enc.size() * 18 < (1u << 24) && meta.padding_size >= st_total) {
-                    meta.padding_size -= static_cast<uint32_t>(st_total);
-                    meta.points = enc;
-                    meta.seektable = true;
-                    meta.seektable_after_padding = true;
-                }
-            }
-        }
-        // total samples, encode.rs:2079-2097
-        if (si.total_samples) {
-            if (si.total_samples != samples_written) return FLACENC_ERR_SAMPLE_COUNT_MISMATCH;
-        } else {
-            if (samples_written >= kMaxSamples) return FLACENC_ERR_EXCESSIVE_TOTAL_SAMPLES;
-            if (samples_written == 0) return FLACENC_ERR_NO_SAMPLES;
-            si.total_samples = samples_written;
-        }
-        if (!header_only) md5.digest(si.md5);
-        std::vector<uint8_t> hdr = build_metadata(si, meta);
-        if (hdr.size() != metadata_len) {
-            g_err = "internal: metadata size changed at finalize";
-            return FLACENC_ERR_IO;
+        uint8_t digest[16];
+        md5.digest(digest);
+        std::vector<uint8_t> hdr;
+        if (int e = led.close(digest, hdr)) {
+            if (led.why) g_err = led.why;
+            return e;
         }
         if (int e = sink.seek(sink.start())) return e;
         if (int e = sink.write(hdr.data(), hdr.size())) return e;
         if (sink.fixed) sink.mem_pos = sink.fixed_len;
         else if (sink.memory) sink.mem_pos = sink.mem.size();
-        stats.frames = frame_number;
-        stats.samples_per_channel = samples_written;
-        stats.bytes_written = metadata_len + byte_count;
-        stats.min_frame_size = si.min_frame;
-        stats.max_frame_size = si.max_frame;
-        std::memcpy(stats.md5, si.md5, 16);
+        stats.frames = led.frame_number;
+        stats.samples_per_channel = led.samples_written;
+        stats.bytes_written = led.metadata_len + led.byte_count;
+        stats.min_frame_size = led.si.min_frame;
+        stats.max_frame_size = led.si.max_frame;
+        std::memcpy(stats.md5, led.si.md5, 16);
         return 0;
     }
 
@@ -1233,7 +1001,7 @@ int flacenc_write_channels(flacenc_writer *w, const int32_t *const *channels, ui
                            size_t len) {
     if (!w || !channels) return FLACENC_ERR_INVALID_ARG;
     if (w->finalized) return FLACENC_ERR_FINALIZED;
-    if (n_channels != w->si.channels) return FLACENC_ERR_CHANNEL_COUNT_MISMATCH;  // encode.rs:856-859
+    if (n_channels != w->led.si.channels) return FLACENC_ERR_CHANNEL_COUNT_MISMATCH;  // encode.rs:856-859
     const size_t base = w->backlog.size();
     w->backlog.resize(base + len * n_channels);
     int32_t *d = w->backlog.data() + base;
@@ -1453,28 +1221,18 @@ static int stream_header_impl(const flacenc_options *opts, uint32_t sample_rate,
         last_frame_len > opts->block_size)
         return FLACENC_ERR_INVALID_ARG;
     if (bits_per_sample < 1 || bits_per_sample > 32) return FLACENC_ERR_INVALID_BITS_PER_SAMPLE;
-    flacenc_writer w;
-    w.header_only = true;
-    if (int rc = w.init(*opts, sample_rate, bits_per_sample, channels, has_total, total_pcm_frames, nullptr)) return rc;
-    const uint32_t B = opts->block_size;
-    for (uint64_t f = 0; f < n_frames; f++) {
-        const uint32_t n = (f + 1 == n_frames) ? last_frame_len : B;
-        w.seekpoints.push_back({w.samples_written, w.byte_count, static_cast<uint16_t>(n), true});
-        w.samples_written += n;
-        const uint32_t size = frame_sizes[f];
-        if (size != 0 && size < kMaxFrameSize) {
-            w.si.min_frame = w.si.min_frame ? std::min(w.si.min_frame, size) : size;
-            w.si.max_frame = std::max(w.si.max_frame, size);
-        }
-        w.byte_count += size;
+    StreamLedger led;
+    std::vector<uint8_t> hdr;
+    if (int rc = led.open(*opts, sample_rate, bits_per_sample, channels, has_total, total_pcm_frames, hdr)) return rc;
+    led.frames(n_frames, last_frame_len, [&](uint64_t k) { return frame_sizes[k]; });
+    led.frame_number = n_frames;
+    if (int rc = led.close(md5, hdr)) {
+        if (led.why) g_err = led.why;
+        return rc;
     }
-    w.frame_number = n_frames;
-    std::memcpy(w.si.md5, md5, 16);
-    w.finalized = true;
-    if (int rc = w.finalize_encoder()) return rc;
-    *len = w.metadata_len;
-    if (!out || cap < w.metadata_len) return FLACENC_ERR_INVALID_ARG;
-    std::memcpy(out, w.sink.mem.data(), w.metadata_len);
+    *len = hdr.size();
+    if (!out || cap < hdr.size()) return FLACENC_ERR_INVALID_ARG;
+    std::memcpy(out, hdr.data(), hdr.size());
     return 0;
 }
 
@@ -1502,29 +1260,6 @@ int flacenc_stream_header_len(const flacenc_options *opts, uint32_t sample_rate,
     if (!opts || !len) return FLACENC_ERR_INVALID_ARG;
     if (bits_per_sample < 1 || bits_per_sample > 32) return FLACENC_ERR_INVALID_BITS_PER_SAMPLE;
     return flacenc_host::stream_header_len(*opts, sample_rate, bits_per_sample, channels, total_pcm_frames, len, has_total != 0);
-}
-
-// The 34 bytes of a STREAMINFO block body (metadata/mod.rs:1599-1630, 1740-1760) as the writers
-// serialise them: exposed so that the layout can be checked against the reference's literal bytes.
-int flacenc_streaminfo_bytes(uint32_t min_block, uint32_t max_block, uint32_t min_frame, uint32_t max_frame,
-                             uint32_t sample_rate, uint32_t channels, uint32_t bits_per_sample,
-                             uint64_t total_samples, const uint8_t md5[16], uint8_t out[34]) {
-    if (!md5 || !out) return FLACENC_ERR_INVALID_ARG;
-    StreamInfo si;
-    si.min_block = min_block;
-    si.max_block = max_block;
-    si.min_frame = min_frame;
-    si.max_frame = max_frame;
-    si.sample_rate = sample_rate;
-    si.channels = channels;
-    si.bps = bits_per_sample;
-    si.total_samples = total_samples;
-    std::memcpy(si.md5, md5, 16);
-    MetaLayout m;
-    const std::vector<uint8_t> v = build_metadata(si, m);   // "fLaC" + header (4) + body (34)
-    if (v.size() != 42) return FLACENC_ERR_IO;
-    std::memcpy(out, v.data() + 8, 34);
-    return 0;
 }
 
 int flacenc_writer_stats(flacenc_writer *w, flacenc_stats *out) {
@@ -1623,36 +1358,8 @@ void flacenc_stream_writer_free(flacenc_stream_writer *w) { delete w; }
 
 }  // extern "C"
 
-// ---- what coalesce.cpp shares with this file (host_internal.h) -----------------------------------------------------------
 namespace flacenc_host {
-double now_ms() { return ::now_ms(); }
-int options_error(const flacenc_options &o) { return ::options_error(o); }
-flacgpu_options gpu_options(const flacenc_options &o, uint32_t block_size) { return ::gpu_options(o, block_size); }
-void pack_le(const int32_t *s, size_t count, unsigned width, uint8_t *d) { ::pack_le(s, count, width, d); }
-int stream_header_len(const flacenc_options &o, uint32_t sample_rate, uint32_t bits_per_sample, uint32_t channels,
-                      uint64_t total_pcm_frames, size_t *len, bool has_total) {
-    flacenc_writer w;
-    w.header_only = true;
-    const int rc = w.init(o, sample_rate, bits_per_sample, channels, has_total, total_pcm_frames, nullptr);
-    w.finalized = true;   // (nothing to flush: the destructor must not try)
-    if (!rc && len) *len = w.metadata_len;
-    return rc;
-}
-int subset_frame_error(uint32_t rate, uint32_t bps) {
-    {  // SampleRate::try_from + "Streaminfo => NonSubsetSampleRate"
-        bool named = false;
-        for (uint32_t r : {88200u, 176400u, 192000u, 8000u, 16000u, 22050u, 24000u, 32000u, 44100u, 48000u, 96000u})
-            named |= (r == rate);
-        bool coded = named || (rate % 1000 == 0 && rate / 1000 < 255) ||
-                     (rate % 10 == 0 && rate / 10 < 65535) || rate < 65535;
-        if (!coded) return rate < (1u << 20) ? FLACENC_ERR_NON_SUBSET_SAMPLE_RATE : FLACENC_ERR_INVALID_SAMPLE_RATE;
-    }
-    if (!(bps == 8 || bps == 12 || bps == 16 || bps == 20 || bps == 24 || bps == 32))
-        return FLACENC_ERR_NON_SUBSET_BITS_PER_SAMPLE;
-    return 0;
-}
 void run_parallel(unsigned helpers, const std::function<void()> &fn) { WorkerPool::get().run(helpers, fn); }
-void set_last_error(const std::string &text) { g_err = text; }
 void release_lane_pool() {
     std::vector<Lane *> all;
     {

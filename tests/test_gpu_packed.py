@@ -85,13 +85,34 @@ def test_pipelined_writer_byte_identical(depth):
 
 
 def test_excessive_total_samples_with_batches_in_flight():
+    """12 blocks written in batches of 4, three in flight, against a smaller declared total: the error is raised before the
+    offending frame is encoded (encode.rs:2006-2011), so behind the header stand exactly the frames in front of it -- the
+    oracle's, whose bytes do not depend on the total.  (samples_written in flacenc_writer_stats is set at finalize only:
+    the bytes are compared, not the counters.)"""
     from flac_codec_amd import encode as E
+    from flac_codec_amd import gpu
+    from test_stream_header_unknown_total import header_len
 
-    pcm = synth_fast(990, 2, 16, 4096 * 12)
-    w = E.FlacSampleWriter(None, E.Options.default().batch_frames(4).pipeline_depth(3), 44100, 16, 2, 4096 * 2 * 6)
-    with pytest.raises(E.ExcessiveTotalSamples):
-        w.write(pcm)
-    w.close()
+    B = 4096
+    pcm = synth_fast(990, 2, 16, B * 12)
+    rc, ref, _ = orc.encode_stream(orc.options("default"), 44100, 16, 2, pcm, total_known=True)
+    assert rc == 0
+    _, offsets, _ = gpu.scan_stream_host(ref)
+    starts = [int(v) for v in offsets] + [len(ref)]
+    assert len(starts) == 13
+    # (total per channel, frames in front of the excess): a batch's first block; mid-batch; a block where the total leaves
+    # room for a short last block of 100 samples only
+    for total, usable in ((8 * B, 8), (6 * B, 6), (5 * B + 100, 5)):
+        for host_pack in (False, True):
+            opts = E.Options.default().batch_frames(4).pipeline_depth(3).host_pack(host_pack)
+            w = E.FlacSampleWriter(None, opts, 44100, 16, 2, total * 2)
+            with pytest.raises(E.ExcessiveTotalSamples):
+                w.write(pcm)
+            data = w.getvalue()
+            w.close()
+            rc, hlen = header_len(opts._c_options(), 1, total)
+            assert rc == 0
+            assert data[hlen:] == ref[starts[0]:starts[usable]], (total, host_pack, len(data) - hlen)
 
 
 def test_batch_front_end_matches_oracle():

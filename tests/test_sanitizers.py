@@ -1,5 +1,5 @@
 """CPU-only sanitizer job: the threaded host C++ of the product library (host/md5_mb.cpp,
-frame_pack.cpp, checksums.cpp, lpc_host.cpp, stream_writer.cpp) built with ASan + UBSan and with TSan, and the
+frame_pack.cpp, checksums.cpp, lpc_host.cpp, stream_writer.cpp, stream_ledger.cpp) built with ASan + UBSan and with TSan, and the
 oracle built with ASan + UBSan, exercised by the host-side test files in a child interpreter that has the
 sanitizer runtime preloaded.  Never on the GPU build path: the device code is not instrumented and these
 libraries are only ever loaded here."""
