@@ -31,6 +31,7 @@
 #include "kernels/types.h"
 #include "kernels/place_rule.h"
 #include "batch_route.h"
+#include "plan_check.h"
 #include "lpc_host.h"
 #include "ragged_plan.h"
 
@@ -1186,8 +1187,7 @@ static int pack_impl(flacgpu_ctx *c, uint64_t first_frame_number, uint32_t sampl
     pf.fcount = ranged ? s.count : n_fast;
     pg.f0 = n_fast;
     pg.fcount = p.n_frames - n_fast;
-    uint32_t fbw = frame_fb_words(p.channels, c->bps, B);   // k_frame64's LDS image
-    if (c->stereo4 && p.exhaustive) fbw = std::min(fbw, frame_fb_words_exhaustive_stereo(c->bps, B));
+    const uint32_t fbw = flacenc_route::frame_image_words(route_context_of(c));   // k_frame64's LDS image: what check_plans bounds a caller's frame by
     // host output: k_frame64 only ever stores (dwords inside a frame, bytes at its ends), so it can write
     // over PCIe into pinned memory; the generic packer builds its frames with atomic ORs and cannot
     b.out_in_host = b.host_out && b.route.host_out_possible && b.host_out_cap >= c->packed_cap;
@@ -1677,6 +1677,21 @@ int flacgpu_pack_plans(flacgpu_ctx *c, const int32_t *pcm, uint32_t n_frames, ui
     CTX_GUARD(c);
     hipStream_t st = c->own_stream;
     const size_t B = c->opts.block_size, C = c->channels;
+    // (the route of a batch whose input was copied into planar rows, as below: only its frame assembly is run)
+    RouteContext rc = route_context_of(c);
+    rc.knobs.no_direct = true;
+    RouteBatch rb;
+    rb.n_frames = n_frames;
+    rb.last_len = last_len;
+    rb.aligned16 = aligned16(c->d_in);
+    const Route route = flacenc_route::plan_route(rc, rb);
+    // a plan the kernels cannot hold (host/plan_check.h) is refused before anything is copied or launched
+    const flacenc_route::PlanFault bad = flacenc_route::check_plans(rc, route, n_frames, last_len, c->packed_cap, plans, subs);
+    if (bad.bad) {
+        g_last_error = "flacgpu_pack_plans: frame " + std::to_string(bad.frame) +
+                       (bad.subframe < C ? ", subframe " + std::to_string(bad.subframe) : std::string(", frame plan")) + ": " + bad.field;
+        return FLACGPU_ERR_INVALID_ARG;
+    }
     const size_t count = ((size_t)(n_frames - 1) * B + last_len) * C;
     HIP_TRY(hipMemcpyAsync(c->d_in, pcm, count * sizeof(int32_t), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(c->d_stats_base, 0, sizeof(uint32_t) * (kTurnWords + 4 + (size_t)n_frames * c->ncand), st));
@@ -1685,14 +1700,7 @@ int flacgpu_pack_plans(flacgpu_ctx *c, const int32_t *pcm, uint32_t n_frames, ui
     HIP_TRY(hipMemcpyAsync(c->d_out, subs, sizeof(*subs) * n_frames * C, hipMemcpyHostToDevice, st));
     Params p;
     fill_params(c, n_frames, last_len, p);
-    // (the route of a batch whose input was copied into planar rows, as above: only its frame assembly is run)
-    RouteContext rc = route_context_of(c);
-    rc.knobs.no_direct = true;
-    RouteBatch rb;
-    rb.n_frames = n_frames;
-    rb.last_len = last_len;
-    rb.aligned16 = aligned16(c->d_in);
-    commit_batch(c, new_batch(Batch::PLAIN, p, flacenc_route::plan_route(rc, rb), st));   // (no analysis: no ties to look at)
+    commit_batch(c, new_batch(Batch::PLAIN, p, route, st));   // (no analysis: no ties to look at)
     HIP_TRY(hipStreamSynchronize(st));   // the host arrays may go away
     return pack_impl(c, first_frame_number, sample_rate, st, Submission());
 }

@@ -52,8 +52,7 @@ Route plan_route(const RouteContext &c, const RouteBatch &b) {
     // recomputed from the PCM, CRC-16 from LDS, one write of the finished bytes) -- orders 17..32 and 5..8 channels for
     // 4096-sample blocks only (and not both); any other frame goes through k_emit (residual rows) -> k_pack (one workgroup
     // per subframe, zero-filled output, atomic OR at shared words) -> k_crc
-    const uint32_t fbw = (c.stereo4 && c.exhaustive && frame_fb_words_exhaustive_stereo(c.bps, B) < fbw_any)
-                             ? frame_fb_words_exhaustive_stereo(c.bps, B) : fbw_any;
+    const uint32_t fbw = frame_image_words(c);   // (the exhaustive stereo choice gets the smaller image)
     const bool f64w = narrow && wave_block_size(B) && (c.max_lpc_order <= 16 || (B == FN && C_ <= 4)) && (C_ <= 4 || B == FN) &&
                       po_ok && fits_lds(fbw) && !kn.no_fused_pack && !kn.no_frame64;
     r.fast_pack = f64w ? full : 0;
@@ -253,8 +252,8 @@ extern "C" void flacenc_plan_autocorr_row(const int32_t *in, uint32_t *out) {
 // aligned16, last_len, n_frames, packed bytes, lag split, timing, segments-in-place wanted, knobs (bit 0 no_direct, 1 no_w64,
 // 2 no_fused_pack, 3 no_frame64, 4 no_direct_short, 5 no_xpose, 6 no_hand, 7 experiment_mfma_ac), FLACGPU_TUNE_CHUNK_MSAMPLES
 // (-1: never set), two_ranges, whole call.  out[9]: Route's fields in their order.
-extern "C" void flacenc_plan_route_row(const int32_t *in, uint32_t *out) {
-    using namespace flacenc_route;
+namespace flacenc_route {
+void route_row(const int32_t *in, RouteContext &c, RouteBatch &b) {
     Knobs kn;
     const uint32_t bits = (uint32_t)in[14];
     kn.no_direct = bits & 1u;
@@ -265,7 +264,7 @@ extern "C" void flacenc_plan_route_row(const int32_t *in, uint32_t *out) {
     kn.no_xpose = bits & 32u;
     kn.no_hand = bits & 64u;
     kn.experiment_mfma_ac = bits & 128u;
-    RouteContext c = route_context((uint32_t)in[0], (uint32_t)in[1], (uint32_t)in[2], (uint32_t)in[3], (uint32_t)in[4], in[5] != 0, kn);
+    c = route_context((uint32_t)in[0], (uint32_t)in[1], (uint32_t)in[2], (uint32_t)in[3], (uint32_t)in[4], in[5] != 0, kn);
     c.lag_split = in[11];
     c.timing = in[12] != 0;
     if (in[15] >= 0) {
@@ -273,7 +272,6 @@ extern "C" void flacenc_plan_route_row(const int32_t *in, uint32_t *out) {
         c.chunk_auto = false;
     }
     c.two_ranges = in[16] != 0;
-    RouteBatch b;
     b.layout = in[6];
     b.aligned16 = in[7] != 0;
     b.last_len = (uint32_t)in[8];
@@ -281,6 +279,13 @@ extern "C" void flacenc_plan_route_row(const int32_t *in, uint32_t *out) {
     b.packed_bytes = (uint32_t)in[10];
     b.segments_in_place_wanted = in[13] != 0;
     b.whole_call = in[17] != 0;
+}
+}  // namespace flacenc_route
+extern "C" void flacenc_plan_route_row(const int32_t *in, uint32_t *out) {
+    using namespace flacenc_route;
+    RouteContext c;
+    RouteBatch b;
+    route_row(in, c, b);
     const Route r = plan_route(c, b);
     out[0] = (uint32_t)r.input;
     out[1] = r.hand;

@@ -65,6 +65,15 @@ struct Route {
 };
 
 Route plan_route(const RouteContext &c, const RouteBatch &b);
+// words of the LDS image a wave assembly launch of this context gets (plan_route sizes by it, pack_impl launches with it):
+// whatever the channel choice, or the smaller image of the exhaustive stereo choice
+inline uint32_t frame_image_words(const RouteContext &c) {
+    const uint32_t any = frame_fb_words(c.channels, c.bps, c.block_size);
+    const uint32_t ex = frame_fb_words_exhaustive_stereo(c.bps, c.block_size);
+    return (c.stereo4 && c.exhaustive && ex < any) ? ex : any;
+}
+// the context and the batch of one row of the test hooks (flacenc_plan_route_row's in[18])
+void route_row(const int32_t *in, RouteContext &c, RouteBatch &b);
 
 // ---- which autocorrelation kernel ONE launch runs (autocorr.hip switches on the answer and on nothing else; a test that
 // names an instantiation asks the same function through flacenc_plan_autocorr_row).  The inputs are what the launchers read

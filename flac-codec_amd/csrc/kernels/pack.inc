@@ -279,6 +279,9 @@ __device__ __forceinline__ void pack_subframe(const Params &p, const PackParams 
             uint32_t k = sp->rice[pj - first_j], eb = sp->escape_bits[pj - first_j];
             const uint32_t pstart0 = pj * plen > order ? pj * plen : order;
             if (lo == pstart0) mybits += hb + (k == 0xFF ? 5u : 0u);
+            // an EMPTY first partition (order == part_len: 1024-sample blocks, order 16, partition order 6 -- a caller's plan,
+            // the encoder never chooses it) has no residual to bring its header along: the first residual's lane writes it
+            if (lo == order && order == plen && np > 1) mybits += hb + (sp->rice[0] == 0xFF ? 5u : 0u);
             for (uint32_t i = lo; i < hi; i++) {
                 if (i == bound) {
                     pj++;
@@ -307,6 +310,11 @@ __device__ __forceinline__ void pack_subframe(const Params &p, const PackParams 
             uint32_t bound = (pj + 1) * plen;
             uint32_t k = sp->rice[pj - first_j], eb = sp->escape_bits[pj - first_j];
             const uint32_t pstart0 = pj * plen > order ? pj * plen : order;
+            if (lo == order && order == plen && np > 1) {   // the header of an empty first partition
+                const uint32_t k0 = sp->rice[0];
+                if (k0 != 0xFF) { lds_put(sb, mypos, k0, hb); mypos += hb; }
+                else { lds_put(sb, mypos, esc_code, hb); lds_put(sb, mypos + hb, sp->escape_bits[0], 5); mypos += hb + 5; }
+            }
             if (lo == pstart0) {
                 if (k != 0xFF) { lds_put(sb, mypos, k, hb); mypos += hb; }
                 else { lds_put(sb, mypos, esc_code, hb); lds_put(sb, mypos + hb, eb, 5); mypos += hb + 5; }
@@ -772,8 +780,9 @@ __device__ __forceinline__ void wave_subframe(const Params &p, uint32_t frame, u
             int32_t hp[MAXO];
 #pragma unroll
             for (int kk = 0; kk < MAXO; kk++) hp[kk] = lane_prev(x[SPL - MAXO + kk]);
-            // the residual, in place (encode.rs:3181-3197); taps rounded up to a multiple of 2 (coefficients beyond the order
-            // are zero): one region with a run-time tap count (fir64_dyn, wave_cand.inc)
+            // the residual, in place (encode.rs:3181-3197); taps rounded up to a multiple of 2 (the tap behind an odd order
+            // is zeroed by fir_coeffs_from itself: a caller's plan may hold anything in coeffs[order ..]): one region
+            // with a run-time tap count (fir64_dyn, wave_cand.inc)
             fir64_dyn<SPL, MAXO, 6, FIR_TURN(SPL)>(x, hp, cw, order, shift);
         }
     }

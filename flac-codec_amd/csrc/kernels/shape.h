@@ -19,9 +19,38 @@ constexpr uint32_t LDS_BLOCK_LIMIT = 16384;
 
 // words of LDS a whole frame of 4096-sample subframes may need (VERBATIM everywhere + header +
 // CRC-16 + one guard word for the funnel shifts); multiple of 4 words
-FLACGPU_HD constexpr uint32_t frame_fb_words(uint32_t channels, uint32_t bps, uint32_t n = FN) {
-    return (((16u + 2u) * 8u + channels * (n * (bps + 1u) + 64u) + 31u) / 32u + 2u + 3u) & ~3u;
+constexpr uint32_t FRAME_FB_FIXED_BITS = (16u + 2u) * 8u;   // the longest frame header and the CRC-16
+constexpr uint32_t FRAME_FB_SPARE_WORDS = 2u;               // the guard word, and one for the rounding of the frame's end
+FLACGPU_HD constexpr uint32_t frame_fb_words_of_body(uint32_t body_bits) {
+    return ((FRAME_FB_FIXED_BITS + body_bits + 31u) / 32u + FRAME_FB_SPARE_WORDS + 3u) & ~3u;
 }
+FLACGPU_HD constexpr uint32_t frame_fb_words(uint32_t channels, uint32_t bps, uint32_t n = FN) {
+    return frame_fb_words_of_body(channels * (n * (bps + 1u) + 64u));
+}
+// The sizing rule read the other way: the most body bits (the sum of a frame's subframes) an image of `fb_words` words
+// holds under ANY frame header.  The frame kernels size their image for what the encoder can decide; a caller's plan
+// (flacgpu_pack_plans) is held to this instead (host/plan_check.cpp).  What the kernels touch of a frame of flen bytes:
+// words [0, (flen + 3) / 4] (Rice fields OR into the word behind their end, the CRC tail reads word (flen - 2) / 4) and,
+// copying out, whole 16-byte groups up to word (3 + flen + 3) / 4 - 1 -- inside fb_words (a multiple of 4) when
+// (flen + 3) / 4 + 1 <= fb_words.
+FLACGPU_HD constexpr uint32_t frame_fb_max_body_bits(uint32_t fb_words) {
+    return (fb_words - FRAME_FB_SPARE_WORDS) * 32u - FRAME_FB_FIXED_BITS;
+}
+static_assert(frame_fb_words_of_body(frame_fb_max_body_bits(6152u)) == 6152u && frame_fb_words_of_body(frame_fb_max_body_bits(6152u) + 1u) > 6152u,
+              "frame_fb_max_body_bits is frame_fb_words_of_body read the other way");
+// the 17-word CRC slice rows of a workgroup of NT lanes (crc16_words_share, kernels/pack.inc): a frame kernel runs at
+// most three rows (k_sub64: four, per subframe image)
+constexpr uint32_t CRC_SLICE_WORDS = 17u;
+FLACGPU_HD constexpr uint32_t frame_crc_max_words(uint32_t nt, uint32_t rows = 3u) { return rows * CRC_SLICE_WORDS * nt; }
+// k_sub64's image (sub64.hip launch_sub64) holds a subframe of at most its VERBATIM form at the stream's width
+FLACGPU_HD constexpr uint32_t sub64_max_sub_bits(uint32_t bps) { return 8u + FN * bps; }
+// dynamic LDS words of k_pack: the subframe's bit string behind the <= 16-byte frame header (a chosen subframe is never
+// longer than its VERBATIM form: <= 40 + 33 n bits)
+FLACGPU_HD constexpr uint32_t pack_sb_words(uint32_t block_size) {
+    return ((block_size * 33u / 32u + 32u) + 3u) & ~3u;
+}
+FLACGPU_HD constexpr uint32_t pack_max_sub_bits(uint32_t n) { return 40u + 33u * n; }
+static_assert((128u + pack_max_sub_bits(16u) + 31u) / 32u + 1u <= pack_sb_words(16u), "k_pack's bit string holds the header and such a subframe");
 
 // Stereo frames whose channel assignment is chosen EXHAUSTIVELY (first minimum of the candidate pairs' bit counts,
 // encode.rs:2747-2786): the chosen pair is never larger than L + R, and a chosen subframe never larger than its

@@ -201,11 +201,7 @@ __device__ __forceinline__ uint64_t frame_number_of(const PackParams &q, uint32_
 }
 
 
-// words reserved for a subframe's bit string: a chosen subframe is never longer than its
-// VERBATIM form (<= 40 + 33 n bits) plus the 16-byte frame header; multiple of 4 words
-__host__ __device__ constexpr uint32_t pack_sb_words(uint32_t block_size) {
-    return ((block_size * 33u / 32u + 32u) + 3u) & ~3u;
-}
+// (pack_sb_words, the words reserved for a subframe's bit string: kernels/shape.h)
 
 Knobs read_knobs();   // flacenc_gpu.hip
 

@@ -304,7 +304,17 @@ int flacgpu_encode_frames(flacgpu_ctx *ctx, const int32_t *pcm, int layout, uint
  * flacenc_pack_frames, include/flacenc_stream.h): `pcm` (host, interleaved, as for flacgpu_analyze)
  * is split into rows, `plans` [n_frames] / `subframes` [n_frames * channels] replace what an analysis
  * would have decided, and the packers produce the frame bytes (flacgpu_fetch_frames).  The decisions
- * must be consistent with the PCM (residuals are recomputed from it). */
+ * must be consistent with the PCM (residuals are recomputed from it): that stays the caller's contract.
+ * What the kernels assume of a plan and never test is checked on the host before anything is copied or
+ * launched: channels and block_size equal to the context's (the last frame: last_frame_len), type, source,
+ * bps + wasted equal to the stream's width (one more for a side source), order <= 4 (FIXED) or 1 .. the
+ * context's max_lpc_order (LPC) and no larger than part_len, precision 1..15 with coefficients that fit it,
+ * shift 0..15, coding_method 0 / 1 with rice[i] <= 14 / 30 or 0xFF and escape_bits[i] <= 31, partition_order
+ * <= min(max_partition_order, 6), n_partitions == 1 << partition_order, part_len << partition_order equal to
+ * the frame's length, body_bits equal to the sum of the subframes' bits, and a frame (a header of at most 16
+ * bytes + ceil(body_bits / 8) + 2) no longer than the image its assembly kernel is launched with -- a plan
+ * coded longer than its VERBATIM form (a Rice parameter far off) can be.  Such a plan is refused with
+ * FLACGPU_ERR_INVALID_ARG, flacgpu_last_error naming the first offending frame, subframe and field. */
 int flacgpu_pack_plans(flacgpu_ctx *ctx, const int32_t *pcm, uint32_t n_frames, uint32_t last_frame_len,
                        const flacgpu_frame_plan *plans, const flacgpu_subframe_plan *subframes,
                        uint64_t first_frame_number, uint32_t sample_rate);
